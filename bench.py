@@ -15,6 +15,12 @@ Other configs (strong scaling, the cloud is fixed and sharded by index range):
     --config c5   sample_scans/bunny.txt tiled x557 = 20 022 479 points, k=80, hybrid eps=0.0062   (BASELINE configs[4])
     --verify      every rank checks the sampled reference goldens (tests/golden/g7_*) that fall into its range
 
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds every other measurement of the
+line: first call of a fresh process, the lattice and uneven-density secondaries, repeated regions, end to end with
+PCIe transfers, the class surface, the sweep with distances, the CPU baseline (--no-extras / --no-cpu-baseline take
+parts of it off again).  --dump-outputs DIR writes what the last timed step computed (K, H and a seeded sample of
+neighbour rows, see dump_outputs) as DIR/<name>.npy.
+
 Prints ONE JSON line on rank 0 (see README/DESIGN.md for the field definitions).
 """
 import argparse
@@ -197,6 +203,40 @@ def verify_against_golden(handle, cfg, lo, hi, oracle, kh=None):
     return int(len(rows))
 
 
+DUMP_BUDGET = 48 << 20        # bytes of .npy data per run, all ranks together
+
+
+def dump_outputs(path, handle, sc, lo, hi, k, rank, world):
+    """What the last timed step handed its caller, rows [lo, hi) of this rank: K and H (float32), and the neighbour
+    rows of the table the step left on the device (indices as float64, distances float32; not held under slab
+    ownership).  Whatever exceeds half the budget is a fixed, seeded sample of rows, sorted, its row numbers
+    stored next to it (float64).  More than one rank: every file name ends in _rank<r>."""
+    os.makedirs(path, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    half = DUMP_BUDGET // world // 2
+    nq = hi - lo
+    rng = np.random.default_rng(20240917)
+
+    def save(name, a, dtype):
+        np.save(os.path.join(path, f"{name}{tag}.npy"), np.ascontiguousarray(a, dtype=dtype))
+
+    K, H = sc.download() if sc is not None else handle.get_fit(lo, hi, coefs=False, H2=False)[1:3]
+    if nq * 8 > half:
+        rows = np.sort(rng.choice(nq, half // 16, replace=False))
+        save("curvature_rows", rows + lo, np.float64)
+        K, H = K[rows], H[rows]
+    save("K", K, np.float32)
+    save("H", H, np.float32)
+    if (sc is not None and sc.slab) or nq == 0:
+        return
+    m = min(nq, half // (8 + 12 * k))
+    rows = np.sort(rng.choice(nq, m, replace=False)) + lo
+    idx, dist, _ = handle.get_neighbor_rows(rows)
+    save("neighbor_rows", rows, np.float64)
+    save("neighbor_idx", idx, np.float64)
+    save("neighbor_dist", dist, np.float32)
+
+
 def secondary_lattice(capi, shapes, k):
     """The reference's OWN 1 M-point torus (utils.py:883-896: a 1000 x 1000 (theta, phi) lattice, every point with
     symmetric partners at nearly equal distances) through the same step, on a fresh handle."""
@@ -279,9 +319,15 @@ def main():
     ap.add_argument("--ownership", choices=("auto", "range", "slab"), default="auto",
                     help="multi-GPU: which rows a rank answers -- its index range, or a slab of equal population along the cloud's "
                          "longest axis (clouds in no spatial order; auto: slab for c4, range otherwise)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip first-call / end-to-end / lattice / repeat measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="every measurement beyond the headline: first call, secondaries, repeats, end to end, class surface, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip first-call / end-to-end / lattice / repeat measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    extras_on = args.full and not args.no_extras
 
     # ONE JSON line on stdout: whatever the libraries below print on it (RCCL 2.27 announces its version there at
     # communicator creation, hipcc may talk during a rebuild) goes to stderr instead -- at the descriptor level.
@@ -311,7 +357,7 @@ def main():
 
     # ---- first call of a fresh process: library load, hipMalloc of every buffer, cell-size search from scratch ------
     first_call_ms = None
-    if world == 1 and not args.no_extras and args.config == "c3":
+    if world == 1 and extras_on and args.config == "c3":
         pts0 = shapes.torus_random(n_total, seed=99)
         t0 = time.perf_counter()
         h0 = _capi.Handle(local_rank)
@@ -381,7 +427,7 @@ def main():
     # order is free, and a GPU that has just worked holds its clocks -- the W warm-up steps alone (3 ms) leave the first
     # region 5-6 % slower than the same region repeated (repeat_ms_per_step).
     secondary = uneven = None
-    if world == 1 and not dist_mode and not args.no_extras and args.config == "c3":
+    if world == 1 and not dist_mode and extras_on and args.config == "c3":
         secondary = secondary_lattice(_capi, shapes, k)
         uneven = secondary_uneven(_capi, k)
     # Clock ramp: a fresh process's first 20-step region (17 ms) otherwise measures the GPU's way up to its working clocks
@@ -403,6 +449,8 @@ def main():
     for _ in range(args.warmup):
         step()
     dt, acc, last_tm = timed_region(args.steps)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, handle, sc, lo, hi, k, rank, world)
 
     verified = None
     if args.verify:
@@ -417,7 +465,7 @@ def main():
 
     repeats = [1e3 * dt / args.steps]
     extras = {}
-    if not args.no_extras:
+    if extras_on:
         for _ in range(2):                                    # spread of the same region, same process, same box
             d2, _, _ = timed_region(args.steps)
             repeats.append(1e3 * d2 / args.steps)
@@ -591,7 +639,7 @@ def main():
             out["secondary"] = secondary
         if uneven is not None:
             out["secondary_uneven_density"] = uneven
-        if world == 1 and not args.no_cpu_baseline and args.config == "c3":
+        if world == 1 and args.full and not args.no_cpu_baseline and args.config == "c3":
             out["cpu_baseline"] = cpu_baseline(local, k)
             out["cpu_baseline"]["host_cpus"] = os.cpu_count()
         sys.stdout.flush()

@@ -24,6 +24,17 @@ def _free_port():
     return p
 
 
+def _spawn(fn, args, nprocs):
+    """torch.multiprocessing.spawn(fn, args, nprocs) from a separate interpreter: torch is never imported in this
+    process.  Here it would bring its own copies of libamdhip64.so.7 / librccl.so.1, and the GPU tests that run later
+    in the same session would load those instead of the ROCm installation's."""
+    import subprocess
+    code = (f"import sys; sys.path[:0] = {sys.path!r}; import torch.multiprocessing as tmp_mp; "
+            f"from {fn.__module__} import {fn.__name__} as fn; tmp_mp.spawn(fn, args={tuple(args)!r}, nprocs={nprocs}, join=True)")
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+
+
 class GlooExchange:
     """Stand-in for RcclExchange on host tensors: one broadcast per rank (shards may differ in size), asynchronous."""
 
@@ -153,14 +164,13 @@ def _worker(rank, world, port, n, k, out_dir):
 
 @pytest.mark.parametrize("n", [3000, 3001])
 def test_two_rank_sharding_matches_single_process(tmp_path, n):
-    import torch.multiprocessing as tmp_mp
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import pct_oracle as oracle
     import pointCloudToolbox  # noqa: F401
     from point_cloud_toolbox_amd import shapes
 
     k, port = 20, _free_port()
-    tmp_mp.spawn(_worker, args=(2, port, n, k, str(tmp_path)), nprocs=2, join=True)
+    _spawn(_worker, (2, port, n, k, str(tmp_path)), 2)
     parts = [np.load(tmp_path / f"out_{r}.npz") for r in range(2)]
     K, H = np.concatenate([p["K"] for p in parts]), np.concatenate([p["H"] for p in parts])
     ref = oracle.pipeline_batched(shapes.torus_random(n, seed=21), k, workers=1)
@@ -212,12 +222,11 @@ def _pipeline_worker(rank, world, port, n, steps, out_dir):
 
 
 def test_double_buffered_exchange_delivers_every_cloud_intact(tmp_path):
-    import torch.multiprocessing as tmp_mp
     import pointCloudToolbox  # noqa: F401
     from point_cloud_toolbox_amd import shapes
 
     world, n, steps, port = 2, 4001, 5, _free_port()
-    tmp_mp.spawn(_pipeline_worker, args=(world, port, n, steps, str(tmp_path)), nprocs=world, join=True)
+    _spawn(_pipeline_worker, (world, port, n, steps, str(tmp_path)), world)
     got = np.load(os.path.join(str(tmp_path), "pipe.npz"))
     for i in range(steps):
         want = np.concatenate([shapes.torus_scan_order(n, world, r, seed=100 + i) for r in range(world)])
@@ -255,12 +264,11 @@ def _slab_pipeline_worker(rank, world, port, n, steps, out_dir):
 
 
 def test_slab_ownership_sends_the_rows_back_in_a_second_exchange(tmp_path):
-    import torch.multiprocessing as tmp_mp
     import pointCloudToolbox  # noqa: F401
     from point_cloud_toolbox_amd import shapes
 
     world, n, steps, port = 2, 5001, 4, _free_port()
-    tmp_mp.spawn(_slab_pipeline_worker, args=(world, port, n, steps, str(tmp_path)), nprocs=world, join=True)
+    _spawn(_slab_pipeline_worker, (world, port, n, steps, str(tmp_path)), world)
     got = np.load(os.path.join(str(tmp_path), "slab_pipe.npz"))
     for i in range(steps):
         assert np.array_equal(got[f"arr_{i}"], shapes.torus_random(n, seed=200 + i)), f"cloud {i}"
@@ -290,14 +298,13 @@ def _slab_oracle_worker(rank, world, port, n, k, out_dir):
 
 
 def test_two_rank_slab_ownership_matches_single_process(tmp_path):
-    import torch.multiprocessing as tmp_mp
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import pct_oracle as oracle
     import pointCloudToolbox  # noqa: F401
     from point_cloud_toolbox_amd import shapes
 
     n, k, port = 4101, 20, _free_port()
-    tmp_mp.spawn(_slab_oracle_worker, args=(2, port, n, k, str(tmp_path)), nprocs=2, join=True)
+    _spawn(_slab_oracle_worker, (2, port, n, k, str(tmp_path)), 2)
     parts = [np.load(tmp_path / f"slab_out_{r}.npz") for r in range(2)]
     K, H = np.concatenate([p["K"] for p in parts]), np.concatenate([p["H"] for p in parts])
     ref = oracle.pipeline_batched(shapes.torus_random(n, seed=22), k, workers=1)
