@@ -228,6 +228,28 @@ int pct_voxel_downsample_f32(pct_ctx* ctx, const float* xyz, int64_t n, double v
  * this estimator as an option.) */
 int pct_surface_variation(pct_ctx* ctx, int32_t k_total, float* out);
 
+/* ---- principal_curvatures_via_principal_component_analysis (pct:901-950) ------------------------------------- */
+/* For every point of the loaded (whole) cloud: its k nearest points as the reference ranks them --
+ * np.linalg.norm(points - point, axis=1) in the cloud's dtype, the nearest entry (the point itself or a duplicate of it)
+ * dropped; k >= N takes N - 1 --, np.cov of their raw coordinates in float64 (about their own mean, ddof 1), its
+ * eigen-decomposition: lambda_1 >= lambda_2 the two largest eigenvalues, their eigenvectors, K = lambda_1 lambda_2,
+ * H = (lambda_1 + lambda_2) / 2.  Kept on the device for pct_get_pca.  2 <= min(k, N - 1) <= 511, else PCT_ERR_INVALID;
+ * PCT_ERR_NONFINITE for any non-finite coordinate.  algo: the sweep that fetches the candidates (pct_knn_algo; every
+ * choice gives the same bits).  Float32 clouds: near-ties of the float32 norm at the k-th place may resolve differently
+ * from NumPy's argsort.  Float64 clouds: ranked by float64 distances; the sweep ranks the cloud recentred on its first
+ * point and rounded to float32, rows it cannot vouch for go through an exhaustive float64 pass (O(N) per row),
+ * *exact_rows (may be NULL) counts them.  That pass is limited to 2^30 point visits (rows x N): beyond, PCT_ERR_INVALID
+ * with the reason, before it runs -- k = 511 on a float64 cloud of more than ~32 000 points (no room for candidates
+ * beyond k), or float32 rounding of the recentred cloud that is not small against the neighbour spacing.  keep_neighbors != 0 keeps every row's
+ * neighbour indices for pct_get_pca.  Like pct_surface_variation this REPLACES the neighbour table and drops the fit
+ * results of the handle: a caller that keeps those runs it on a handle of its own. */
+int pct_pca_curvatures(pct_ctx* ctx, int32_t k, int32_t algo, int32_t keep_neighbors, int64_t* exact_rows);
+/* Rows [begin, end) of the last pct_pca_curvatures, float64 host arrays (any pointer may be NULL): l1, l2, K, H (rows),
+ * dirs (rows, 3, 2) C order -- column 0 the eigenvector of lambda_1, column 1 that of lambda_2, each with its component
+ * of largest magnitude positive (the reference's signs are LAPACK's) -- and idx (rows, k) int32, the neighbours used. */
+int pct_get_pca(pct_ctx* ctx, int64_t begin, int64_t end, double* l1, double* l2, double* dirs, double* K, double* H,
+                int32_t* idx);
+
 /* ---- ingest / egress around the path (host code, no device needed) ------- */
 /* The text scans read_from_file parses with np.loadtxt (pct:51): rows x cols of whitespace-separated numbers,
  * '#' comments and blank lines skipped.  Values are correctly rounded float64 (what Python's float() gives). */

@@ -89,6 +89,8 @@ SIGNATURES = {
     "pct_voxel_downsample": (C.c_int, [_p, _f64p, C.c_int64, C.c_double, _i64p, _i64p]),
     "pct_voxel_downsample_f32": (C.c_int, [_p, _f32p, C.c_int64, C.c_double, _i64p, _i64p]),
     "pct_surface_variation": (C.c_int, [_p, C.c_int32, _f32p]),
+    "pct_pca_curvatures": (C.c_int, [_p, C.c_int32, C.c_int32, C.c_int32, _i64p]),
+    "pct_get_pca": (C.c_int, [_p, C.c_int64, C.c_int64, _f64p, _f64p, _f64p, _f64p, _f64p, _i32p]),
     "pct_text_shape": (C.c_int, [C.c_char_p, _i64p, _i32p]),
     "pct_text_load": (C.c_int, [C.c_char_p, C.c_int64, C.c_int32, _f64p]),
     "pct_format_float": (C.c_int, [C.c_double, C.c_char_p]),
@@ -481,6 +483,27 @@ class Handle:
         self._check(self._lib.pct_surface_variation(self._h, int(k_total), _ptr(out, _f32p)))
         self.k = int(k_total) - 1
         return out
+
+    def pca_curvatures(self, k, algo=KNN_AUTO, keep_neighbors=False):
+        """principal_curvatures_via_principal_component_analysis (pct:901-950) of the loaded cloud, kept on the device
+        (``get_pca``).  Returns the number of float64 rows that went through the exhaustive pass."""
+        exact = C.c_int64(0)
+        st = self._lib.pct_pca_curvatures(self._h, int(k), int(algo), int(bool(keep_neighbors)), C.byref(exact))
+        if st == PCT_ERR_NONFINITE:
+            raise ValueError("array must not contain infs or NaNs")              # what scipy.linalg.eigh says (pct:925)
+        self._check(st)
+        self.pca_k = min(int(k), self.n - 1)
+        return exact.value
+
+    def get_pca(self, begin, end, want_idx=False):
+        """(l1, l2, dirs (rows, 3, 2), K, H[, idx (rows, k)]) of rows [begin, end), float64."""
+        rows = int(end) - int(begin)
+        l1, l2, K, H = (np.empty(rows, np.float64) for _ in range(4))
+        dirs = np.empty((rows, 3, 2), np.float64)
+        idx = np.empty((rows, self.pca_k), np.int32) if want_idx else None
+        self._check(self._lib.pct_get_pca(self._h, int(begin), int(end), _ptr(l1, _f64p), _ptr(l2, _f64p), _ptr(dirs, _f64p),
+                                          _ptr(K, _f64p), _ptr(H, _f64p), _ptr(idx, _i32p)))
+        return (l1, l2, dirs, K, H) + ((idx,) if want_idx else ())
 
     def timings(self):
         t = Timings()

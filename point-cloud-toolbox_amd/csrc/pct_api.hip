@@ -225,7 +225,8 @@ void pct_destroy(pct_ctx* ctx) {
                       &ctx->scan_tmp, &ctx->occ, &ctx->redo, &ctx->row_of, &ctx->owned_pos, &ctx->cell_own, &ctx->cell_oth, &ctx->own_start, &ctx->sorted4, &ctx->sorted4d, &ctx->red, &ctx->nbr_pos,
                       &ctx->nbr_dist, &ctx->nbr_cnt, &ctx->counters, &ctx->coefs, &ctx->K, &ctx->H, &ctx->H2,
                       &ctx->stage_a, &ctx->stage_b, &ctx->stage_c, &ctx->stage_d, &ctx->row_done, &ctx->redo_m, &ctx->flag_buf, &ctx->dens_buf, &ctx->pub_pos, &ctx->pub_dist, &ctx->pub_cnt, &ctx->qpts4, &ctx->fit_flag, &ctx->lvl_src,
-                      &ctx->tree_codes, &ctx->tree_vals, &ctx->tree_lvl, &ctx->tree_head, &ctx->tree_marks, &ctx->tree_seg, &ctx->tree_runs, &ctx->tree_range, &ctx->tree_bucket, &ctx->tree_tmp};
+                      &ctx->tree_codes, &ctx->tree_vals, &ctx->tree_lvl, &ctx->tree_head, &ctx->tree_marks, &ctx->tree_seg, &ctx->tree_runs, &ctx->tree_range, &ctx->tree_bucket, &ctx->tree_tmp,
+                      &ctx->pca, &ctx->pca_aux, &ctx->pca_nbr, &ctx->pca_orig};
     for (pct_buf* b : all) release(b);
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     for (auto& e : ctx->ev)
@@ -254,6 +255,7 @@ static int new_cloud(pct_ctx* ctx, int64_t n) {
     ctx->slab_parts = ctx->slab_part = 0;
     ctx->slab_split_valid = false;
     ctx->grid_valid = ctx->knn_valid = ctx->fit_valid = ctx->pts4_valid = ctx->qpts4_valid = false;
+    ctx->pca_valid = false;
     ctx->has_f64 = false;
     ctx->no_cull = ctx->culled = false;
     ctx->retries = 0;
@@ -1089,6 +1091,75 @@ int pct_surface_variation(pct_ctx* ctx, int32_t k_total, float* out) {
         ctx->cull_box_valid = false;   // the cached box was too small for this cloud: measure it again next time
     }
     ctx->fit_valid = false;
+    return PCT_OK;
+}
+
+int pct_pca_curvatures(pct_ctx* ctx, int32_t k, int32_t algo, int32_t keep_neighbors, int64_t* exact_rows) {
+    PCT_TRY(begin_call(ctx));
+    PCT_TRY(refuse_in_slab_mode(ctx, "pct_pca_curvatures"));
+    if (ctx->n <= 0) return pct_fail(ctx, PCT_ERR_INVALID, "no cloud loaded");
+    if (ctx->q_begin != 0 || ctx->q_end != ctx->n)
+        return pct_fail(ctx, PCT_ERR_INVALID, "pct_pca_curvatures answers whole clouds (query range [%lld,%lld) of %lld points)",
+                        (long long)ctx->q_begin, (long long)ctx->q_end, (long long)ctx->n);
+    const int64_t kk = k < ctx->n - 1 ? k : ctx->n - 1;      // pct:916: argsort(...)[1:k+1] of N entries holds min(k, N-1)
+    if (kk > PCT_K_MAX)
+        return pct_fail(ctx, PCT_ERR_INVALID, "k=%d: the PCA estimator takes at most %d neighbours (the sweep's range)", k, PCT_K_MAX);
+    if (kk < 2)      // np.cov of fewer than two points is NaN, and scipy.linalg.eigh refuses it
+        return pct_fail(ctx, PCT_ERR_INVALID, "k=%d on %lld points leaves %lld neighbours: array must not contain infs or NaNs",
+                        k, (long long)ctx->n, (long long)kk);
+    ctx->pca_valid = false;
+    double R = 0.0, origin[3] = {0, 0, 0};
+    bool bad = false;
+    // float64 clouds: from here until pct_pca_restore the handle's cloud is the recentred one the sweep ranks
+    int st = pct_pca_prep(ctx, &R, &bad, origin);
+    if (st == PCT_OK && bad) st = pct_fail(ctx, PCT_ERR_NONFINITE, "array must not contain infs or NaNs");
+    const int64_t room = (PCT_K_MAX < ctx->n - 1 ? PCT_K_MAX : ctx->n - 1) - kk;
+    const int32_t kc = (int32_t)(kk + (room < PCT_PCA_EXTRA ? room : PCT_PCA_EXTRA));
+    bool again = false;
+    if (st == PCT_OK) st = run_knn(ctx, kc, 0.0, algo);
+    if (st == PCT_OK) st = finish_knn_stats(ctx, &again);     // (whole clouds: nothing was left out of the cell list)
+    const int rs = pct_pca_restore(ctx);
+    PCT_TRY(st);
+    PCT_TRY(rs);
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
+    int64_t exact = 0;
+    st = pct_launch_pca(ctx, (int32_t)kk, 2.0 * R * (1.0 + 1e-9), origin, keep_neighbors != 0, &exact);
+    if (ctx->has_f64) ctx->grid_valid = false;        // (the cell list holds the recentred float32 cloud)
+    ctx->knn_valid = ctx->fit_valid = false;           // (the table in place holds the over-fetched candidates)
+    PCT_TRY(st);
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->tm.fit_ms = ev_ms(ctx, 5, 6);
+    ctx->tm.total_ms = ev_ms(ctx, 2, 6);
+    ctx->pca_valid = true;
+    ctx->pca_has_nbr = keep_neighbors != 0;
+    ctx->pca_k = (int32_t)kk;
+    ctx->pca_rows = ctx->n;
+    if (exact_rows) *exact_rows = exact;
+    return PCT_OK;
+}
+
+int pct_get_pca(pct_ctx* ctx, int64_t begin, int64_t end, double* l1, double* l2, double* dirs, double* K, double* H,
+                int32_t* idx) {
+    PCT_TRY(begin_call(ctx));
+    if (!ctx->pca_valid) return pct_fail(ctx, PCT_ERR_INVALID, "no PCA frame on this handle (pct_pca_curvatures)");
+    if (begin < 0 || end > ctx->pca_rows || begin > end)
+        return pct_fail(ctx, PCT_ERR_INVALID, "bad row range [%lld,%lld) of %lld", (long long)begin, (long long)end, (long long)ctx->pca_rows);
+    if (idx && !ctx->pca_has_nbr)
+        return pct_fail(ctx, PCT_ERR_INVALID, "pct_get_pca: the neighbourhoods were not kept (pct_pca_curvatures keep_neighbors)");
+    const int64_t n = ctx->pca_rows, rows = end - begin;
+    if (rows == 0) return PCT_OK;
+    const double* o = (const double*)ctx->pca.p;
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    double* outs[4] = {l1, l2, K, H};
+    for (int i = 0; i < 4; ++i)
+        if (outs[i]) PCT_HIP(ctx, hipMemcpyAsync(outs[i], o + (int64_t)i * n + begin, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (dirs) PCT_HIP(ctx, hipMemcpyAsync(dirs, o + 4 * n + 6 * begin, (size_t)rows * 6 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (idx) PCT_HIP(ctx, hipMemcpyAsync(idx, (const int32_t*)ctx->pca_nbr.p + begin * ctx->pca_k, (size_t)rows * ctx->pca_k * sizeof(int32_t),
+                                         hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->tm.export_ms = ev_ms(ctx, 0, 1);
     return PCT_OK;
 }
 

@@ -206,6 +206,15 @@ struct pct_ctx {
     pct_buf qpts4;      // float4 {x,y,z,index} of EVERY point in public order, for pct_query_points (built on first use)
     bool qpts4_valid = false;
 
+    // PCA principal curvatures (pct_pca.hip), public order: double [lambda_1 | lambda_2 | K | H | frame (n,3,2)]
+    pct_buf pca;
+    pct_buf pca_aux;    // float32 rounding offset, flags, rows handed to the exact pass and their bounds
+    pct_buf pca_nbr;    // int32 (n,k): the neighbourhoods used (pct_pca_curvatures with keep_neighbors)
+    pct_buf pca_orig;   // double4 (n): float64 clouds' uploaded records while the sweep sees them recentred
+    bool pca_valid = false, pca_has_nbr = false, pca_recentred = false;
+    int32_t pca_k = 0;
+    int64_t pca_rows = 0;
+
     pct_timings tm = {};
 };
 
@@ -347,3 +356,10 @@ int pct_launch_mesh_energies(pct_ctx* ctx, const double* d_v, const int* d_tri, 
                              bool f64, double* d_partial, int nblk, double* d_out);
 int pct_voxel_downsample_device(pct_ctx* ctx, const void* d_xyz, bool f64, int64_t n, double voxel, int64_t* d_out, int64_t* count);
 int pct_launch_surface_variation(pct_ctx* ctx, float* d_out);
+// PCA principal curvatures (pct_pca.hip).  The sweep fetches up to PCT_PCA_EXTRA candidates beyond k per point, re-ranked
+// in the cloud's dtype.  prep: non-finite coordinates; float64 clouds: the cloud recentred on its first point for the
+// sweep (origin), the float32 rounding offset R of that; restore: the uploaded cloud back after the sweep
+#define PCT_PCA_EXTRA 16
+int pct_pca_prep(pct_ctx* ctx, double* round_off, bool* nonfinite, double origin[3]);
+int pct_pca_restore(pct_ctx* ctx);
+int pct_launch_pca(pct_ctx* ctx, int32_t k, double round2, const double origin[3], bool keep_neighbors, int64_t* exact_rows);

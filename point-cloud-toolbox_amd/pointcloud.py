@@ -375,6 +375,42 @@ class PointCloud:
         self.last_timings = h.timings()
         return K, H
 
+    # ------------------------------------------------------- PCA estimator
+    def principal_curvatures_via_principal_component_analysis(self, k_neighbors, algorithm="auto"):
+        """Eigenvalues of every neighbourhood's covariance as 'principal curvatures' (pct:901-950), on the GPU.
+
+        Sets ``pca_principal_curvature_values_1`` / ``_2`` (the two largest eigenvalues), ``principal_curvature_directions``
+        (N, 3, 2: their eigenvectors as columns), ``pca_K_values`` and ``pca_H_values``, all float64, and returns None.
+        The neighbourhoods are the reference's: the k nearest points in the cloud's dtype, the point itself dropped.  The
+        work runs on a device handle of its own: the planted table, the fit results and ``kdtree`` stay as they are.
+        ``algorithm`` (extension, as ``plant_kdtree``) picks the sweep that fetches the candidates; the values do not
+        depend on it.  Eigenvector signs: the component of largest magnitude is positive (the reference's are LAPACK's)."""
+        pts = np.asarray(self.points)
+        if pts.ndim != 2 or pts.shape[1] != 3:
+            raise ValueError("points must have shape (N, 3)")
+        algo = _ALGORITHMS[algorithm]
+        n = len(pts)
+        if n == 0:                                           # the reference's loop runs zero times
+            l1, l2, K, H, dirs = np.zeros(0), np.zeros(0), np.zeros(0), np.zeros(0), np.zeros((0, 3, 2))
+        else:
+            if min(int(k_neighbors), n - 1) < 2:             # np.cov of < 2 neighbours is NaN: eigh refuses it (pct:925)
+                raise ValueError("array must not contain infs or NaNs")
+            if pts.dtype != np.float64:
+                pts = pts.astype(np.float32, copy=False)
+            h = _capi.acquire_handle(self._device)
+            try:
+                h.set_points(pts)
+                self.pca_exact_rows = h.pca_curvatures(int(k_neighbors), algo)
+                l1, l2, dirs, K, H = h.get_pca(0, n)
+                self.last_pca_timings = h.timings()
+            finally:
+                _capi.release_handle(h)
+        self.pca_principal_curvature_values_1 = l1
+        self.pca_principal_curvature_values_2 = l2
+        self.principal_curvature_directions = dirs
+        self.pca_K_values = K
+        self.pca_H_values = H
+
     # --------------------------------------------------------- staticmethods
     # The reference calls these once per point in a Python loop (pct:644-647, 668): one device context serves all
     # calls of the process (created on first use, released at exit), under a lock -- a handle has ONE stream.

@@ -1,0 +1,115 @@
+"""CPU restatement of principal_curvatures_via_principal_component_analysis (pointCloudToolbox.py:901-950).
+
+Per point: the k nearest points by np.linalg.norm(points - point, axis=1) IN THE CLOUD'S DTYPE with the first entry of
+the ranking dropped (pct:914-916), np.cov of their raw coordinates in float64 (pct:922), eigh (pct:925), the two largest
+eigenvalues and their eigenvectors, K = l1 l2, H = (l1 + l2) / 2 (pct:933-934).  The k-NN here is a float64 k-d tree
+over-fetch re-ranked by the dtype's norm (exact ties by index), or a caller-supplied index table.  Test helper only."""
+import numpy as np
+from scipy.spatial import cKDTree
+
+F32_ULP_TIE = 4          # the k-th and (k+1)-th distances within this many float32 ulps: the row is "ambiguous"
+
+
+def dtype_norm(points, rows, cand):
+    """np.linalg.norm(points[cand] - points[rows, None], axis=-1) as the reference computes it (in the cloud's dtype)."""
+    d = points[cand] - points[rows][:, None, :]
+    s = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+    return np.sqrt(s)
+
+
+def knn(points, k, rows=None, extra=24):
+    """(idx (rows, k), ambiguous (rows,)) -- the reference's neighbour set and whether its k-th place is a near-tie."""
+    n = len(points)
+    rows = np.arange(n) if rows is None else np.asarray(rows)
+    k = min(k, n - 1)
+    m = min(n, k + 1 + extra)
+    tree = cKDTree(points.astype(np.float64))
+    idx_out = np.empty((len(rows), k), np.int64)
+    amb = np.zeros(len(rows), bool)
+    for lo in range(0, len(rows), 4096):
+        r = rows[lo:lo + 4096]
+        _, cand = tree.query(points[r].astype(np.float64), m)
+        cand = np.asarray(cand).reshape(len(r), m)
+        dist = dtype_norm(points, r, cand)
+        order = np.lexsort((cand, dist), axis=1)          # by distance, exact ties by index
+        key_idx = np.take_along_axis(cand, order, 1)
+        key_d = np.take_along_axis(dist, order, 1)
+        idx_out[lo:lo + len(r)] = key_idx[:, 1:k + 1]
+        if k + 1 < m:
+            dk = key_d[:, k].astype(np.float32)
+            dk1 = key_d[:, k + 1].astype(np.float32)
+            ulp = np.spacing(np.maximum(dk, np.float32(np.finfo(np.float32).tiny)))
+            amb[lo:lo + len(r)] = np.abs(dk1.astype(np.float64) - dk) <= F32_ULP_TIE * ulp
+    return idx_out, amb
+
+
+def frame(points, idx):
+    """l1, l2, l3, dirs (rows, 3, 2), K, H of the neighbourhoods points[idx] (float64, two passes, eigh)."""
+    out = {key: [] for key in ("l1", "l2", "l3", "dirs")}
+    for lo in range(0, len(idx), 2048):
+        nb = points[idx[lo:lo + 2048]].astype(np.float64)
+        c = nb - nb.mean(axis=1, keepdims=True)
+        cov = np.einsum("rki,rkj->rij", c, c) / (nb.shape[1] - 1)
+        w, v = np.linalg.eigh(cov)                         # ascending
+        out["l1"].append(w[:, 2]); out["l2"].append(w[:, 1]); out["l3"].append(w[:, 0])
+        out["dirs"].append(v[:, :, [2, 1]])
+    res = {key: np.concatenate(val) for key, val in out.items()}
+    res["K"] = res["l1"] * res["l2"]
+    res["H"] = (res["l1"] + res["l2"]) / 2
+    return res
+
+
+def restate(points, k, rows=None):
+    idx, amb = knn(points, k, rows)
+    res = frame(points, idx)
+    res["idx"], res["ambiguous"] = idx, amb
+    return res
+
+
+def compare(got, ref, l3, rows_mask=None):
+    """Boolean (rows,) mask of the rows that meet the issue's bars: eigenvalues and H within 1e-12 l1, K within 1e-12 l1^2,
+    each direction equal up to sign within 1e-9 l1 / gap where its gap exceeds 1e-6 l1, span{v1, v2} as a projector
+    within 1e-9 l1 / (l2 - l3)."""
+    l1, l2 = ref["l1"], ref["l2"]
+    scale = np.maximum(np.abs(l1), 1e-300)
+    ok = np.abs(got["l1"] - l1) <= 1e-12 * scale
+    ok &= np.abs(got["l2"] - l2) <= 1e-12 * scale
+    ok &= np.abs(got["H"] - ref["H"]) <= 1e-12 * scale
+    ok &= np.abs(got["K"] - ref["K"]) <= 1e-12 * scale * scale
+    gaps = [l1 - l2, np.minimum(l1 - l2, l2 - l3)]
+    for c in range(2):
+        g, r = got["dirs"][:, :, c], ref["dirs"][:, :, c]
+        err = np.minimum(np.abs(g - r).max(1), np.abs(g + r).max(1))
+        has_gap = gaps[c] > 1e-6 * scale
+        ok &= ~has_gap | (err <= 1e-9 * scale / np.where(has_gap, gaps[c], 1.0))
+    pg = np.einsum("ric,rjc->rij", got["dirs"], got["dirs"])
+    pr = np.einsum("ric,rjc->rij", ref["dirs"], ref["dirs"])
+    gap = l2 - l3
+    has_gap = gap > 1e-6 * scale
+    perr = np.abs(pg - pr).reshape(len(l1), -1).max(1)
+    ok &= ~has_gap | (perr <= 1e-9 * scale / np.where(has_gap, gap, 1.0))
+    return ok if rows_mask is None else ok | ~rows_mask
+
+
+def valid_set(points, row, idx_row, k):
+    """idx_row is a set of k nearest points of `row` under the reference's key, near-ties (4 float32 ulps) allowed.  The
+    entry the reference drops is the point itself or an exact duplicate of it: a set holding the row stands for the same
+    coordinates with that duplicate in the row's place."""
+    n = len(points)
+    idx_row = np.asarray(idx_row).copy()
+    if (idx_row == row).any():
+        twins = np.flatnonzero((points == points[row]).all(1))
+        spare = [j for j in twins if j != row and j not in idx_row]
+        if not spare:
+            return False
+        idx_row[idx_row == row] = spare[0]
+    others = np.delete(np.arange(n), row)
+    d = dtype_norm(points, np.array([row]), others[None])[0].astype(np.float64)
+    chosen = np.isin(others, idx_row)
+    if chosen.sum() != k or len(set(idx_row.tolist())) != k:
+        return False
+    if chosen.all():
+        return True
+    worst_in, best_out = d[chosen].max(), d[~chosen].min()
+    tol = F32_ULP_TIE * np.spacing(np.float32(max(worst_in, np.finfo(np.float32).tiny)))
+    return worst_in <= best_out + tol
