@@ -226,7 +226,8 @@ void pct_destroy(pct_ctx* ctx) {
                       &ctx->nbr_dist, &ctx->nbr_cnt, &ctx->counters, &ctx->coefs, &ctx->K, &ctx->H, &ctx->H2,
                       &ctx->stage_a, &ctx->stage_b, &ctx->stage_c, &ctx->stage_d, &ctx->row_done, &ctx->redo_m, &ctx->flag_buf, &ctx->dens_buf, &ctx->pub_pos, &ctx->pub_dist, &ctx->pub_cnt, &ctx->qpts4, &ctx->fit_flag, &ctx->lvl_src,
                       &ctx->tree_codes, &ctx->tree_vals, &ctx->tree_lvl, &ctx->tree_head, &ctx->tree_marks, &ctx->tree_seg, &ctx->tree_runs, &ctx->tree_range, &ctx->tree_bucket, &ctx->tree_tmp,
-                      &ctx->pca, &ctx->pca_aux, &ctx->pca_nbr, &ctx->pca_orig};
+                      &ctx->pca, &ctx->pca_aux, &ctx->pca_nbr, &ctx->pca_orig,
+                      &ctx->bin_rec, &ctx->bin_mat, &ctx->bin_plan, &ctx->bin_base};
     for (pct_buf* b : all) release(b);
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     for (auto& e : ctx->ev)
@@ -1004,6 +1005,7 @@ int pct_neighbor_study_curvatures(pct_ctx* ctx, const int64_t* sample_rows, int6
     if (e != hipSuccess) return pct_fail(ctx, PCT_ERR_HIP, "sample upload failed: %s", hipGetErrorString(e));
     int* d_spos = (int*)ctx->stage_c.p;
     if (ctx->knn_sorted_space) {      // public index -> neighbour-table row, on the device
+        PCT_TRY(pct_ensure_row_of(ctx));
         PCT_TRY(pct_launch_gather_int(ctx, (const int*)ctx->row_of.p, d_spos, n_samples));
     }
     int* d_cnt = (int*)ctx->stage_b.p;

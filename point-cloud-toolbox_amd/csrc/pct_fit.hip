@@ -851,6 +851,7 @@ int pct_launch_fit_table(pct_ctx* ctx) {
 }
 
 int pct_launch_gather_fit(pct_ctx* ctx, int64_t first, int64_t rows, float* d_coefs, float* d_K, float* d_H, float* d_H2) {
+    PCT_TRY(pct_ensure_row_of(ctx));
     PCT_LAUNCH(k_gather_fit, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, ctx->stream, (const int*)ctx->row_of.p,
                        first, rows, (const float*)ctx->coefs.p, (const float*)ctx->K.p, (const float*)ctx->H.p,
                        (const float*)ctx->H2.p, d_coefs, d_K, d_H, d_H2);

@@ -7,6 +7,8 @@
 //   occupancy mean points-per-cell as seen by a point (drives the cell size)
 //   scan      exclusive scan of the counts -> cell starts, ordered occupied list
 //   scatter   counting sort of the float4 records into cell order, owned points first in each cell
+// hist and scatter of the whole-cloud builds are a two-level counting sort with LDS counters only (k_bin_*, below);
+// the level passes, slab-owned handles and very large grids keep the per-point atomics of k_hist / k_scatter.
 //
 // All kernels are HBM/L2 streaming passes over 16 B records with 64-wide waves.  Host side (pct_build_grid): outlier-
 // trimmed grid box, cell size by occupancy (warm-started, speculative box from the previous similar cloud), one
@@ -133,8 +135,11 @@ struct PackAcc {
 // every block onto one cache line cost more than the pass itself.)
 // carry = 0: nothing of the pass wrote the record directly (k_pack), so its previous content is not read and the
 // 128-byte memset in front of the pass -- a launch of its own -- is not needed.
-__global__ __launch_bounds__(kBlock) void k_pack_final(const PackRed* __restrict__ parts, int n_parts, PackRed* __restrict__ red,
-                                                       PackRed* __restrict__ host_copy, int carry) {
+// (NT = threads of the calling block, all of which call: k_pack_final, and k_bin_plan on the speculative build's chain)
+template <int NT>
+__device__ __forceinline__ void pack_fold(const PackRed* __restrict__ parts, int n_parts, PackRed* __restrict__ red,
+                                          PackRed* __restrict__ host_copy, int carry) {
+    constexpr int kBlock = NT;
     __shared__ PackRed sh[kBlock / 64];
     int bb[6] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN, INT32_MIN};
     double s[3] = {0, 0, 0}, ss[3] = {0, 0, 0};
@@ -187,6 +192,11 @@ __global__ __launch_bounds__(kBlock) void k_pack_final(const PackRed* __restrict
         *red = out;
         *host_copy = out;
     }
+}
+
+__global__ __launch_bounds__(kBlock) void k_pack_final(const PackRed* __restrict__ parts, int n_parts, PackRed* __restrict__ red,
+                                                       PackRed* __restrict__ host_copy, int carry) {
+    pack_fold<kBlock>(parts, n_parts, red, host_copy, carry);
 }
 
 // xyz (n,3) -> float4 {x,y,z,index}; finite check; bbox and moments (fp64, about the origin: the reference
@@ -771,6 +781,329 @@ __global__ __launch_bounds__(kBlock) void k_scatter_raw(const float* __restrict_
     if (pts4d) sorted4d[pos] = pts4d[i];
 }
 
+// ---- two-level counting sort with LDS counters only (k_bin_*) -----------------------------------------------------
+// The whole-cloud builds (every grid point is owned or not by its public index: the caller's rows, the full pack, the
+// range-culled pack) sort without per-point global atomics.  A bucket is a contiguous range of 2^shift cell ids, so
+// bucket order followed by cell order inside a bucket is the global cell order and a bucket's points occupy one
+// contiguous range of sorted4.
+//   k_bin_count    tile of input rows -> per-bucket counts in LDS -> one row of the [tile][bucket] matrix
+//                  (+ the PackAcc record of the speculative build, one per tile, folded by a spare block of k_bin_cells)
+//   k_bin_colscan  exclusive scan down every column of the matrix, column totals
+//   k_bin_plan     bucket starts; work list of (bucket, chunk) items: a bucket above `chunk` records is shared by
+//                  several blocks, the way occ feeds the sweep
+//   k_bin_scatter  the same tiles again: LDS cursors start at bucket start + matrix entry, every record goes to its
+//                  bucket's range of bin_rec (runs of one tile and bucket are adjacent: the L2 combines the stores)
+//   k_bin_cells    per item: per-cell, per-class counts in LDS -> cell_own / cell_oth.  The only item of a bucket stores
+//                  all its cells (zeros too: no clearing fill); the items of a shared bucket add their non-zero counts
+//                  (one atomic per non-empty (item, cell, class)) and keep the value returned, their run's offset
+//   (k_scan_sums, k_scan_tiles, event, k_scan_apply as for every build)
+//   k_bin_place    per item: LDS cursors from cell_start (+ cell_own for the other class, + the run offset), every
+//                  record to its place in sorted4; owned_pos / sorted4d along; row_of on first need (k_bin_row_of)
+// Kernel boundaries are the only ordering between blocks.
+constexpr int kBinBlock = 256;        // fine level: one block per work item
+constexpr int kBinWide = 1024;        // coarse level: one block per tile, four rows per thread in flight
+constexpr int kBinTileRows = 4096;       // input rows per tile (times a whole factor for clouds above kBinMaxTiles tiles)
+constexpr int kBinMaxTiles = 1024;
+constexpr int kBinMaxBuckets = 4096;     // LDS counters of the coarse level
+constexpr int kBinMaxCounters = 8192;    // LDS counters of the fine level: cells per bucket x classes
+constexpr int kBinMinChunk = 4096;       // records per work item (at least; never below the fine counters)
+
+struct BinShape {
+    bool ok;             // the bucket scheme covers this grid
+    int shift;           // log2 cells per bucket
+    int nb;              // buckets
+    int cls;             // classes: 1 = every point owned, 2 = owned / other
+    int tile_rows, ntiles;
+    int chunk;           // records per work item
+    int max_items;       // upper bound of the work list: every bucket at least one item
+    int max_shared;      // upper bound of the items of shared buckets
+};
+
+// Sizing: about a thousand buckets (each a few thousand points at the sweep's occupancies), cells per bucket a power of
+// two from 256 up to what the fine LDS counters hold; a grid that would still need more than kBinMaxBuckets is not covered.
+__host__ BinShape bin_shape(int64_t n, int64_t ncell, bool sharded) {
+    BinShape s = {};
+    s.cls = sharded ? 2 : 1;
+    int max_shift = 8;                                // 2^shift * cls <= kBinMaxCounters
+    while ((s.cls << (max_shift + 1)) <= kBinMaxCounters) ++max_shift;
+    s.shift = 8;
+    while (((ncell + ((int64_t)1 << s.shift) - 1) >> s.shift) > 1024 && s.shift < max_shift) ++s.shift;
+    const int64_t nb = (ncell + ((int64_t)1 << s.shift) - 1) >> s.shift;
+    s.ok = n >= 1 && n < ((int64_t)1 << 31) - kBinTileRows && ncell >= 1 && nb <= kBinMaxBuckets;
+    if (!s.ok) return s;
+    s.nb = (int)nb;
+    const int64_t f = (n + (int64_t)kBinTileRows * kBinMaxTiles - 1) / ((int64_t)kBinTileRows * kBinMaxTiles);
+    s.tile_rows = (int)(kBinTileRows * (f < 1 ? 1 : f));
+    s.ntiles = (int)((n + s.tile_rows - 1) / s.tile_rows);
+    s.chunk = (s.cls << s.shift) > kBinMinChunk ? (s.cls << s.shift) : kBinMinChunk;
+    s.max_items = s.nb + (int)(n / s.chunk);
+    s.max_shared = 2 * (int)(n / s.chunk) + 1;          // sum of ceil(c / chunk) over the buckets with c > chunk
+    return s;
+}
+
+// the cell of a record: k_hist_raw's expression (a non-finite row is binned at the origin)
+__device__ __forceinline__ int bin_cell(float x, float y, float z, const pct_grid& g) {
+    const bool ok = isfinite(x) && isfinite(y) && isfinite(z);
+    const int cx = cell_coord(ok ? (double)x : g.ox, g.ox, g.inv_cell, g.nx);
+    const int cy = cell_coord(ok ? (double)y : g.oy, g.oy, g.inv_cell, g.ny);
+    const int cz = cell_coord(ok ? (double)z : g.oz, g.oz, g.inv_cell, g.nz);
+    return (cz * g.ny + cy) * g.nx + cx;
+}
+
+// RAW: rows of the caller's xyz array (public index = row); otherwise float4 records with the public index in w
+template <bool RAW>
+__device__ __forceinline__ float4 bin_load(const float* __restrict__ xyz, const float4* __restrict__ pts4, int64_t i) {
+    if (RAW) return make_float4(xyz[3 * i + 0], xyz[3 * i + 1], xyz[3 * i + 2], __int_as_float((int)i));
+    return pts4[i];
+}
+
+template <bool RAW>
+__global__ __launch_bounds__(kBinWide) void k_bin_count(const float* __restrict__ xyz, const float4* __restrict__ pts4, int64_t n,
+                                                         int tile_rows, pct_grid g, int shift, int nb,
+                                                         unsigned* __restrict__ mat, PackRed* __restrict__ parts) {
+    __shared__ unsigned s_cnt[kBinMaxBuckets];
+    for (int b = threadIdx.x; b < nb; b += kBinWide) s_cnt[b] = 0;
+    __syncthreads();
+    const float sh[3] = {0.f, 0.f, 0.f};
+    PackAcc acc;
+    acc.init();
+    const int64_t r0 = (int64_t)blockIdx.x * tile_rows, r1 = min(n, r0 + tile_rows);
+    for (int64_t base = r0 + threadIdx.x; base < r1; base += 4 * kBinWide) {
+        float4 p[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (base + j * kBinWide < r1) p[j] = bin_load<RAW>(xyz, pts4, base + j * kBinWide);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (base + j * kBinWide >= r1) continue;
+            if (parts) {
+                const bool ok = isfinite(p[j].x) && isfinite(p[j].y) && isfinite(p[j].z);
+                acc.bad |= !ok;
+                if (ok) acc.add(p[j].x, p[j].y, p[j].z, sh);
+            }
+            atomicAdd(&s_cnt[bin_cell(p[j].x, p[j].y, p[j].z, g) >> shift], 1u);
+        }
+    }
+    __syncthreads();
+    for (int b = threadIdx.x; b < nb; b += kBinWide) mat[(size_t)blockIdx.x * nb + b] = s_cnt[b];
+    if (parts) acc.commit<kBinWide / 64>(parts + blockIdx.x);
+}
+
+// 16 columns x 64 groups of tiles per block (a thread holds at most kBinMaxTiles / 64 entries: all of them in flight
+// at once): mat[t][b] becomes the number of bucket b's records in the tiles before t
+constexpr int kBinScanCols = 16, kBinScanGroups = 64, kBinScanPer = kBinMaxTiles / kBinScanGroups;
+__global__ __launch_bounds__(kBinScanCols * kBinScanGroups) void k_bin_colscan(unsigned* __restrict__ mat, int ntiles, int nb, unsigned* __restrict__ tot) {
+    __shared__ unsigned s[kBinScanGroups][kBinScanCols];
+    const int lane = threadIdx.x % kBinScanCols, grp = threadIdx.x / kBinScanCols;
+    const int col = blockIdx.x * kBinScanCols + lane;
+    const int per = (ntiles + kBinScanGroups - 1) / kBinScanGroups;
+    const int t0 = grp * per;
+    unsigned v[kBinScanPer], sum = 0;
+#pragma unroll
+    for (int j = 0; j < kBinScanPer; ++j) {
+        v[j] = (j < per && t0 + j < ntiles && col < nb) ? mat[(size_t)(t0 + j) * nb + col] : 0u;
+        sum += v[j];
+    }
+    s[grp][lane] = sum;
+    __syncthreads();
+    unsigned run = 0;
+    for (int q = 0; q < grp; ++q) run += s[q][lane];
+    if (col >= nb) return;
+#pragma unroll
+    for (int j = 0; j < kBinScanPer; ++j) {
+        if (j < per && t0 + j < ntiles) mat[(size_t)(t0 + j) * nb + col] = run;
+        run += v[j];
+    }
+    if (grp == kBinScanGroups - 1) tot[col] = run;
+}
+
+// plan words: [0] work items  [1] items of shared buckets  [2] shared buckets; bstart = plan + 16 (nb + 1 words)
+// item = {bucket, first record, end of its records, slot of its run offsets or -1 for the only item of its bucket}
+__global__ __launch_bounds__(1024) void k_bin_plan(const unsigned* __restrict__ tot, int nb, int chunk, int* __restrict__ plan,
+                                                   int4* __restrict__ items) {
+    __shared__ int4 sh[1024];
+    constexpr int per = kBinMaxBuckets / 1024;
+    int4 v[per];
+    int4 mine = make_int4(0, 0, 0, 0);
+    for (int j = 0; j < per; ++j) {
+        const int b = threadIdx.x * per + j;
+        const int c = b < nb ? (int)tot[b] : 0;
+        const int ni = b < nb ? max(1, (c + chunk - 1) / chunk) : 0;        // an empty bucket's item stores its zeros
+        v[j] = make_int4(c, ni, ni > 1 ? ni : 0, ni > 1 ? 1 : 0);
+        mine = add3(mine, v[j]);
+    }
+    sh[threadIdx.x] = mine;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+        int4 a = make_int4(0, 0, 0, 0);
+        if ((int)threadIdx.x >= o) a = sh[threadIdx.x - o];
+        __syncthreads();
+        sh[threadIdx.x] = add3(sh[threadIdx.x], a);
+        __syncthreads();
+    }
+    int4 run = make_int4(sh[threadIdx.x].x - mine.x, sh[threadIdx.x].y - mine.y, sh[threadIdx.x].z - mine.z, 0);
+    int* bstart = plan + 16;
+    for (int j = 0; j < per; ++j) {
+        const int b = threadIdx.x * per + j;
+        if (b < nb) {
+            bstart[b] = run.x;
+            for (int ch = 0; ch < v[j].y; ++ch)
+                items[run.y + ch] = make_int4(b, run.x + ch * chunk, run.x + min(v[j].x, (ch + 1) * chunk), v[j].z ? run.z + ch : -1);
+        }
+        run = add3(run, v[j]);
+    }
+    if (threadIdx.x == 1023) {
+        bstart[nb] = run.x;
+        plan[0] = run.y;
+        plan[1] = run.z;
+        plan[2] = sh[1023].w;
+    }
+}
+
+template <bool RAW>
+__global__ __launch_bounds__(kBinWide) void k_bin_scatter(const float* __restrict__ xyz, const float4* __restrict__ pts4, int64_t n,
+                                                           int tile_rows, pct_grid g, int shift, int nb, int chunk,
+                                                           const unsigned* __restrict__ mat, const int* __restrict__ plan,
+                                                           float4* __restrict__ rec, int* __restrict__ cell_own, int* __restrict__ cell_oth) {
+    __shared__ unsigned s_cur[kBinMaxBuckets];
+    const int* bstart = plan + 16;
+    for (int b = threadIdx.x; b < nb; b += kBinWide) s_cur[b] = (unsigned)bstart[b] + mat[(size_t)blockIdx.x * nb + b];
+    __syncthreads();
+    const int64_t r0 = (int64_t)blockIdx.x * tile_rows, r1 = min(n, r0 + tile_rows);
+    for (int64_t base = r0 + threadIdx.x; base < r1; base += 4 * kBinWide) {
+        float4 p[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (base + j * kBinWide < r1) p[j] = bin_load<RAW>(xyz, pts4, base + j * kBinWide);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (base + j * kBinWide >= r1) continue;
+            const unsigned pos = atomicAdd(&s_cur[bin_cell(p[j].x, p[j].y, p[j].z, g) >> shift], 1u);
+            if (pos < (unsigned)n) rec[pos] = p[j];   // (guard: the caller's rows must not change between the two passes)
+        }
+    }
+    // the counters of the shared buckets are added to by k_bin_cells: cleared here, a kernel boundary ahead of it
+    if (plan[2] > 0) {
+        for (int b = blockIdx.x; b < nb; b += gridDim.x) {
+            if (bstart[b + 1] - bstart[b] <= chunk) continue;
+            const int64_t c0 = (int64_t)b << shift, c1 = min(g.ncell, c0 + ((int64_t)1 << shift));
+            for (int64_t c = c0 + threadIdx.x; c < c1; c += kBinWide) {
+                cell_own[c] = 0;
+                if (cell_oth) cell_oth[c] = 0;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBinBlock) void k_bin_cells(const float4* __restrict__ rec, const int* __restrict__ plan,
+                                                         const int4* __restrict__ items, pct_grid g, int shift, int q_begin, int q_end,
+                                                         int* __restrict__ cell_own, int* __restrict__ cell_oth, int* __restrict__ base,
+                                                         const PackRed* __restrict__ parts, int n_parts, PackRed* __restrict__ red,
+                                                         PackRed* __restrict__ red_host) {
+    extern __shared__ int s_c[];                    // cells per bucket x classes counters
+    // the grid's last block is not an item's: it folds the tiles' PackAcc records of a speculative build beside the
+    // others (k_pack_final's work, off the chain: a one-block kernel of its own cost 5 us there)
+    if (blockIdx.x == gridDim.x - 1) {
+        if (parts) pack_fold<kBinBlock>(parts, n_parts, red, red_host, 0);
+        return;
+    }
+    if ((int)blockIdx.x >= plan[0]) return;
+    const int4 it = items[blockIdx.x];
+    const int r0 = it.y, r1 = it.z, slot = it.w;
+    const int cpb = 1 << shift, nc = cell_oth ? 2 * cpb : cpb;
+    const int64_t c0 = (int64_t)it.x << shift;
+    const int ncl = (int)min((int64_t)cpb, g.ncell - c0);
+    for (int k = threadIdx.x; k < nc; k += kBinBlock) s_c[k] = 0;
+    __syncthreads();
+    for (int base = r0 + threadIdx.x; base < r1; base += 4 * kBinBlock) {
+        float4 p[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (base + j * kBinBlock < r1) p[j] = rec[base + j * kBinBlock];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (base + j * kBinBlock >= r1) continue;
+            const int l = bin_cell(p[j].x, p[j].y, p[j].z, g) - (int)c0;
+            const int idx = __float_as_int(p[j].w);
+            const bool owned = !cell_oth || (idx >= q_begin && idx < q_end);
+            if ((unsigned)l < (unsigned)cpb) atomicAdd(&s_c[(owned ? 0 : cpb) + l], 1);
+        }
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < nc; k += kBinBlock) {
+        const int l = k & (cpb - 1);
+        if (l >= ncl) continue;
+        int* arr = k < cpb ? cell_own : cell_oth;
+        const int v = s_c[k];
+        if (slot < 0) arr[c0 + l] = v;
+        else base[(size_t)slot * nc + k] = v ? atomicAdd(&arr[c0 + l], v) : 0;
+    }
+}
+
+__global__ __launch_bounds__(kBinBlock) void k_bin_place(const float4* __restrict__ rec, const int* __restrict__ plan,
+                                                         const int4* __restrict__ items, pct_grid g, int shift, int q_begin, int q_end,
+                                                         int64_t n, int64_t n_owned, const int* __restrict__ cell_start,
+                                                         const int* __restrict__ cell_own, const int* __restrict__ cell_oth,
+                                                         const int* __restrict__ own_start, const int* __restrict__ base,
+                                                         float4* __restrict__ sorted4, int* __restrict__ row_of, int* __restrict__ owned_pos,
+                                                         const double4* __restrict__ pts4d, double4* __restrict__ sorted4d) {
+    extern __shared__ int s_cur[];                  // cells per bucket x classes cursors, then (two classes) cells per bucket words:
+    if ((int)blockIdx.x >= plan[0]) return;         // neighbour-table row minus sorted position of the cell's owned points
+    const int4 it = items[blockIdx.x];
+    const int r0 = it.y, r1 = it.z, slot = it.w;
+    if (r0 >= r1) return;
+    const int cpb = 1 << shift, nc = cell_oth ? 2 * cpb : cpb;
+    const int64_t c0 = (int64_t)it.x << shift;
+    const int ncl = (int)min((int64_t)cpb, g.ncell - c0);
+    int* s_row = s_cur + nc;
+    for (int k = threadIdx.x; k < nc; k += kBinBlock) {
+        const int l = k & (cpb - 1);
+        if (l >= ncl) continue;
+        int s = cell_start[c0 + l];
+        if (k >= cpb) s += cell_own[c0 + l];                       // owned points first inside every cell
+        else if (cell_oth) s_row[l] = own_start[c0 + l] - s;
+        if (slot >= 0) s += base[(size_t)slot * nc + k];
+        s_cur[k] = s;
+    }
+    __syncthreads();
+    for (int base = r0 + threadIdx.x; base < r1; base += 4 * kBinBlock) {
+        float4 p[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (base + j * kBinBlock < r1) p[j] = rec[base + j * kBinBlock];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (base + j * kBinBlock >= r1) continue;
+            const int l = bin_cell(p[j].x, p[j].y, p[j].z, g) - (int)c0;
+            const int idx = __float_as_int(p[j].w);
+            const bool owned = !cell_oth || (idx >= q_begin && idx < q_end);
+            if ((unsigned)l >= (unsigned)ncl) continue;
+            const int pos = atomicAdd(&s_cur[(owned ? 0 : cpb) + l], 1);
+            if ((unsigned)pos >= (unsigned)n) continue;
+            sorted4[pos] = p[j];
+            if (pts4d) sorted4d[pos] = pts4d[idx];
+            if (owned) {
+                const int row = cell_oth ? pos + s_row[l] : pos;   // (every point owned: rows are sorted positions)
+                if ((unsigned)row < (unsigned)n_owned && (unsigned)(idx - q_begin) < (unsigned)n_owned) {
+                    owned_pos[row] = pos;
+                    if (row_of) row_of[idx - q_begin] = row;       // (null: built on first need, pct_ensure_row_of)
+                }
+            }
+        }
+    }
+}
+
+// row_of from the finished cell list: the public index rides in w of every sorted record.  The fused step never reads
+// row_of (its results stay in table-row order); this is the one 4-byte store per point at a random address that the
+// build would otherwise make (9 of k_bin_place's 25 us at 1 M points), paid by the first call that gathers through it.
+__global__ __launch_bounds__(256) void k_bin_row_of(const float4* __restrict__ sorted4, const int* __restrict__ owned_pos, int64_t n_owned,
+                                                    int q_begin, int* __restrict__ row_of) {
+    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (row >= n_owned) return;
+    const int idx = __float_as_int(sorted4[owned_pos[row]].w);
+    if ((unsigned)(idx - q_begin) < (unsigned)n_owned) row_of[idx - q_begin] = (int)row;
+}
+
 __global__ __launch_bounds__(256) void k_gather_int(const int* __restrict__ map, int* __restrict__ io, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) io[i] = map[io[i]];
@@ -1146,6 +1479,12 @@ int pct_build_grid(pct_ctx* ctx, int32_t k, double eps) {
     }
     a = fmin(a, emax * 1.0001 + 1e-30);
 
+    // Which build: the two-level LDS counting sort (k_bin_*) wherever a grid point is owned or not by its public index
+    // alone and every point is binned -- the caller's rows (raw), the full pack, the range-culled pack -- and the bucket
+    // scheme covers the grid (bin_shape, per pass).  The level passes (own_flag, sub_box), the slab-owned handles and
+    // larger grids keep the per-point atomics of k_hist / k_scatter; PCT_GRID_ATOMIC=1 forces those everywhere (A/B runs,
+    // parity tests).
+    const bool bin_allowed = !own_flag && !sub_box && !slab && !pct_getenv("PCT_GRID_ATOMIC");
     PCT_TRY(pct_reserve(ctx, &ctx->cell_of, (size_t)n * sizeof(int)));
     PCT_TRY(pct_reserve(ctx, &ctx->cell_fill, (size_t)n * sizeof(int)));   // in-cell arrival ranks
     // queries per work item: 16 - 20 measured best for k_knn_pair and k_knn_duo (one staged stencil serves more queries; a
@@ -1209,13 +1548,46 @@ int pct_build_grid(pct_ctx* ctx, int32_t k, double eps) {
             set_dims(&g, bbox, a);
             hit_cap = true;
         }
+        const BinShape bs = bin_allowed ? bin_shape(n, g.ncell, sharded) : BinShape{};
+        const bool bin = bs.ok;
+        // (the bin build writes every counter itself: no clearing fill)
         PCT_TRY(pct_reserve(ctx, &ctx->cell_own, (size_t)g.ncell * sizeof(int)));
-        PCT_HIP(ctx, hipMemsetAsync(ctx->cell_own.p, 0, (size_t)g.ncell * sizeof(int), ctx->stream));
+        if (!bin) PCT_HIP(ctx, hipMemsetAsync(ctx->cell_own.p, 0, (size_t)g.ncell * sizeof(int), ctx->stream));
         if (sharded) {
             PCT_TRY(pct_reserve(ctx, &ctx->cell_oth, (size_t)g.ncell * sizeof(int)));
-            PCT_HIP(ctx, hipMemsetAsync(ctx->cell_oth.p, 0, (size_t)g.ncell * sizeof(int), ctx->stream));
+            if (!bin) PCT_HIP(ctx, hipMemsetAsync(ctx->cell_oth.p, 0, (size_t)g.ncell * sizeof(int), ctx->stream));
         }
         const float4* src = from_base ? (const float4*)ctx->lvl_src.p : (const float4*)ctx->pts4.p;
+        int* bin_plan = nullptr;
+        int4* bin_items = nullptr;
+        const size_t bin_lds = (size_t)(bs.cls << bs.shift) * sizeof(int);
+        if (bin) {
+            // scratch of this pass (sized by its grid): bucket-partitioned records, [tile][bucket] matrix, plan words +
+            // bucket starts + column totals + work list, run offsets of the shared buckets' items
+            PCT_TRY(pct_reserve(ctx, &ctx->bin_rec, (size_t)n * sizeof(float4)));
+            PCT_TRY(pct_reserve(ctx, &ctx->bin_mat, (size_t)bs.ntiles * bs.nb * sizeof(unsigned)));
+            const size_t plan_words = 16 + (size_t)(bs.nb + 1) + (size_t)bs.nb;
+            const size_t items_at = (plan_words * sizeof(int) + 15) / 16 * 16;
+            PCT_TRY(pct_reserve(ctx, &ctx->bin_plan, items_at + (size_t)bs.max_items * sizeof(int4)));
+            PCT_TRY(pct_reserve(ctx, &ctx->bin_base, (size_t)bs.max_shared * (bs.cls << bs.shift) * sizeof(int)));
+            bin_plan = (int*)ctx->bin_plan.p;
+            unsigned* bin_tot = (unsigned*)(bin_plan + 16 + bs.nb + 1);
+            bin_items = (int4*)((char*)ctx->bin_plan.p + items_at);
+            PackRed* parts = spec ? red_parts(ctx) : nullptr;
+#define PCT_BIN_SRC(K, ...) do { if (raw) PCT_LAUNCH(K<true>, __VA_ARGS__); else PCT_LAUNCH(K<false>, __VA_ARGS__); } while (0)
+            PCT_BIN_SRC(k_bin_count, dim3(bs.ntiles), dim3(kBinWide), 0, ctx->stream, ctx->xyz_view, src, n, bs.tile_rows, g, bs.shift, bs.nb,
+                        (unsigned*)ctx->bin_mat.p, parts);
+            PCT_LAUNCH(k_bin_colscan, dim3((bs.nb + kBinScanCols - 1) / kBinScanCols), dim3(kBinScanCols * kBinScanGroups), 0, ctx->stream, (unsigned*)ctx->bin_mat.p, bs.ntiles, bs.nb, bin_tot);
+            PCT_LAUNCH(k_bin_plan, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned*)bin_tot, bs.nb, bs.chunk, bin_plan, bin_items);
+            PCT_BIN_SRC(k_bin_scatter, dim3(bs.ntiles), dim3(kBinWide), 0, ctx->stream, ctx->xyz_view, src, n, bs.tile_rows, g, bs.shift, bs.nb,
+                        bs.chunk, (const unsigned*)ctx->bin_mat.p, (const int*)bin_plan, (float4*)ctx->bin_rec.p, (int*)ctx->cell_own.p,
+                        sharded ? (int*)ctx->cell_oth.p : nullptr);
+#undef PCT_BIN_SRC
+            PCT_LAUNCH(k_bin_cells, dim3(bs.max_items + 1), dim3(kBinBlock), bin_lds, ctx->stream, (const float4*)ctx->bin_rec.p, (const int*)bin_plan,
+                       (const int4*)bin_items, g, bs.shift, (int)ctx->q_begin, (int)ctx->q_end, (int*)ctx->cell_own.p,
+                       sharded ? (int*)ctx->cell_oth.p : nullptr, (int*)ctx->bin_base.p, (const PackRed*)parts, bs.ntiles,
+                       (PackRed*)ctx->red.p, (PackRed*)ctx->pin);
+        } else
         if (raw) {
             const int nhb = grid_1d(n, kBlock, 0);
             PCT_LAUNCH(k_hist_raw, dim3(nhb), dim3(kBlock), 0, ctx->stream, ctx->xyz_view, n, g, g_begin, g_end, (int*)ctx->cell_of.p,
@@ -1254,7 +1626,19 @@ int pct_build_grid(pct_ctx* ctx, int32_t k, double eps) {
         PCT_LAUNCH(k_scan_apply, dim3(nblk), dim3(kBlock), 0, ctx->stream,
                            (const int*)ctx->cell_own.p, sharded ? (const int*)ctx->cell_oth.p : nullptr, g.ncell, items_q,
                            (const int4*)ctx->scan_tmp.p, (int*)ctx->cell_cnt.p, (int*)ctx->own_start.p, (int2*)ctx->occ.p);
-        if (raw)
+        // (the chained sweep's passes read each other's lists: its first pass keeps row_of complete)
+        const bool lazy_rows = bin && !ctx->level_mode;
+        ctx->row_of_valid = !lazy_rows;
+        ctx->row_of_rows = n_owned;
+        ctx->row_of_begin = (int)ctx->q_begin;
+        if (bin)
+            PCT_LAUNCH(k_bin_place, dim3(bs.max_items), dim3(kBinBlock), bin_lds + (sharded ? bin_lds / 2 : 0), ctx->stream,
+                       (const float4*)ctx->bin_rec.p, (const int*)bin_plan, (const int4*)bin_items, g, bs.shift, (int)ctx->q_begin,
+                       (int)ctx->q_end, n, n_owned, (const int*)ctx->cell_cnt.p, (const int*)ctx->cell_own.p,
+                       sharded ? (const int*)ctx->cell_oth.p : nullptr, (const int*)ctx->own_start.p, (const int*)ctx->bin_base.p,
+                       (float4*)ctx->sorted4.p, lazy_rows ? nullptr : (int*)ctx->row_of.p, (int*)ctx->owned_pos.p,
+                       ctx->has_f64 ? (const double4*)ctx->pts4d.p : nullptr, ctx->has_f64 ? (double4*)ctx->sorted4d.p : nullptr);
+        else if (raw)
             PCT_LAUNCH(k_scatter_raw, dim3(grid_1d(n, kBlock, 0)), dim3(kBlock), 0, ctx->stream, ctx->xyz_view, (const int*)ctx->cell_of.p,
                        (const int*)ctx->cell_cnt.p, (const int*)ctx->cell_own.p, (const int*)ctx->own_start.p, (const int*)ctx->cell_fill.p, n,
                        g_begin, (float4*)ctx->sorted4.p, (int*)ctx->row_of.p, (int*)ctx->owned_pos.p,
@@ -1282,6 +1666,13 @@ int pct_build_grid(pct_ctx* ctx, int32_t k, double eps) {
                 ctx->spec_valid = false;
                 return pct_build_grid(ctx, k, eps);
             }
+        }
+        if (bin && pct_getenv("PCT_GRID_DEBUG")) {          // (debugging only: waits for the stream)
+            int pw[3] = {0, 0, 0};
+            PCT_HIP(ctx, hipMemcpyAsync(pw, bin_plan, sizeof(pw), hipMemcpyDeviceToHost, ctx->stream));
+            PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            fprintf(stderr, "[grid] bin build: %d buckets of %d cells, %d tiles of %d rows, %d work items of up to %d records, %d of them in %d shared buckets\n",
+                    bs.nb, 1 << bs.shift, bs.ntiles, bs.tile_rows, pw[0], bs.chunk, pw[1], pw[2]);
         }
         const unsigned long long s2 = ((const ScanTotals*)(ctx->pin + 128))->sumsq;
         tot = ((const ScanTotals*)(ctx->pin + 128))->tot;
@@ -1349,6 +1740,19 @@ int pct_build_grid(pct_ctx* ctx, int32_t k, double eps) {
     ctx->n_occ = tot.y;
     ctx->tm.occupied_cells = tot.y;
     ctx->grid_valid = true;
+    return PCT_OK;
+}
+
+// Every reader of ctx->row_of calls this first (pct_get_fit's gather, the row export, the neighbour study).
+int pct_ensure_row_of(pct_ctx* ctx) {
+    if (ctx->row_of_valid) return PCT_OK;
+    const int64_t rows = ctx->row_of_rows;
+    if (rows > 0) {
+        PCT_LAUNCH(k_bin_row_of, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, ctx->stream, (const float4*)ctx->sorted4.p,
+                   (const int*)ctx->owned_pos.p, rows, ctx->row_of_begin, (int*)ctx->row_of.p);
+        PCT_HIP(ctx, hipGetLastError());
+    }
+    ctx->row_of_valid = true;
     return PCT_OK;
 }
 

@@ -154,6 +154,11 @@ struct pct_ctx {
     pct_buf own_start;  // int32 (ncell+1) first neighbour-table row of every cell
     pct_buf cell_fill;  // int32 (n) arrival rank of every point in its cell and class
     pct_buf scan_tmp;   // block sums
+    // two-level counting sort of the whole-cloud builds (pct_grid.hip, k_bin_*), sized per pass
+    pct_buf bin_rec;    // float4 (n_grid) the records partitioned by bucket (a contiguous range of cell ids)
+    pct_buf bin_mat;    // u32 (tiles, buckets) records of every input tile per bucket, then their column-wise exclusive scan
+    pct_buf bin_plan;   // plan words, bucket starts, column totals, int4 work list {bucket, chunk, offset slot, 0}
+    pct_buf bin_base;   // int32 (shared items, cells per bucket x classes) run offsets of the items that share a bucket
     pct_buf occ;        // int2 (n_items) work items {cell id, chunk of items_q queries}
     pct_buf redo;       // int32 (n) queries the fast sweep handed to the exact sweep
     int64_t n_items = 0;
@@ -162,6 +167,10 @@ struct pct_ctx {
     pct_buf sorted4;    // float4 (n) cell-sorted, w = public index bits
     pct_buf sorted4d;   // double4 (n) cell-sorted native coords (has_f64)
     pct_buf row_of;     // int32 (owned) neighbour-table row of public index q_begin + i
+    // the k_bin_* build leaves row_of to the first reader (pct_ensure_row_of: from w of the sorted records)
+    bool row_of_valid = true;
+    int64_t row_of_rows = 0;
+    int32_t row_of_begin = 0;
     pct_buf owned_pos;  // int32 (owned) sorted position of every table row
     pct_buf red;        // small reduction scratch
     // 4 KiB of pinned, device-visible host memory: kernels drop their few result words here so that a
@@ -351,6 +360,7 @@ int pct_launch_fit_rows_f64(pct_ctx* ctx, const int32_t* d_idx, const int32_t* d
                             int32_t k, int32_t pitch, double* d_coefs, double* d_K, double* d_H);
 int pct_launch_query_points(pct_ctx* ctx, const double* d_q, int64_t m, int32_t k, double eps, int32_t* d_idx, double* d_dist);
 int pct_launch_gather_int(pct_ctx* ctx, const int* d_map, int* d_inout, int64_t n);
+int pct_ensure_row_of(pct_ctx* ctx);     // before any read of ctx->row_of
 int pct_launch_export_rows(pct_ctx* ctx, const int64_t* d_rows, int64_t n_rows, int32_t* d_idx, float* d_dist, int32_t* d_cnt);
 int pct_launch_mesh_energies(pct_ctx* ctx, const double* d_v, const int* d_tri, int64_t n_tri, const void* d_K, const void* d_H,
                              bool f64, double* d_partial, int nblk, double* d_out);

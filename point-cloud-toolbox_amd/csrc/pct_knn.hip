@@ -2670,6 +2670,7 @@ int pct_launch_export_neighbors(pct_ctx* ctx, int64_t begin, int64_t end, int32_
 
 int pct_launch_export_rows(pct_ctx* ctx, const int64_t* d_rows, int64_t n_rows, int32_t* d_idx, float* d_dist, int32_t* d_cnt) {
     const bool sorted = ctx->knn_sorted_space;
+    if (sorted) PCT_TRY(pct_ensure_row_of(ctx));
     PCT_LAUNCH(k_export_rows, dim3((unsigned)n_rows), dim3(128), 0, ctx->stream,
                        (const float4*)(sorted ? ctx->sorted4.p : ctx->pts4.p), sorted && ctx->has_f64 ? (const double4*)ctx->sorted4d.p : nullptr,
                        sorted ? (const int*)ctx->row_of.p : nullptr,

@@ -387,6 +387,7 @@ int pct_build_tree(pct_ctx* ctx, int32_t k, double eps, bool* usable) {
     PCT_LAUNCH(k_tree_gather, grid1, block, 0, ctx->stream, (const float4*)ctx->pts4.p, (const unsigned*)vals, n,
                        (float4*)ctx->sorted4.p, (int*)ctx->owned_pos.p, (int*)ctx->row_of.p,
                        ctx->has_f64 ? (const double4*)ctx->pts4d.p : nullptr, ctx->has_f64 ? (double4*)ctx->sorted4d.p : nullptr);
+    ctx->row_of_valid = true;
     PCT_LAUNCH(k_tree_buckets, dim3(((1u << kTreeBucketBits) + 2 + 255) / 256), block, 0, ctx->stream, (const u64*)codes, n, (int*)ctx->tree_bucket.p);
     PCT_LAUNCH(k_tree_level, grid1, block, 0, ctx->stream, (const u64*)codes, n, n_min, max_level, (unsigned char*)ctx->tree_lvl.p);
     PCT_LAUNCH(k_tree_heads, grid1, block, 0, ctx->stream, (const u64*)codes, (const unsigned char*)ctx->tree_lvl.p, n, head);
