@@ -272,15 +272,23 @@ def _fit_chunk(points, idx, rows, count):
     return out
 
 
-def _curv_f32(coefs):
-    """pct:398-431 vectorised, float32 arithmetic in the same operation order."""
+def _curv_f32(coefs, scalar_pow=False):
+    """pct:398-431 vectorised, float32 arithmetic in the same operation order.
+
+    ``scalar_pow``: NumPy's ARRAY float32 power is a SIMD routine of its own -- on the build the goldens were captured
+    with it differs from the correctly rounded w ** 1.5 by one ulp on 21 % of inputs -- while the reference raises a
+    float32 SCALAR to 1.5 (pct:413), which is libm's powf (one ulp off on 0.05 %).  True evaluates the power element by
+    element the reference's way, for comparisons at the level of single ulps; the default is the fast one."""
     c = np.asarray(coefs, dtype=np.float32)
     A, B, C, D, E = (c[:, i] for i in range(5))
     one, two = np.float32(1), np.float32(2)
     Fx, Fy, Fxx, Fyy, Fxy = D, E, two * A, two * B, C
     w = one + Fx * Fx + Fy * Fy
     den_k = w * w
-    den_h = np.power(w, np.float32(1.5))
+    if scalar_pow:
+        den_h = np.array([x ** 1.5 for x in w], dtype=np.float32)
+    else:
+        den_h = np.power(w, np.float32(1.5))
     K = (Fxx * Fyy - Fxy * Fxy) / den_k
     H = ((one + Fx * Fx) * Fyy - two * Fx * Fy * Fxy + (one + Fy * Fy) * Fxx) / (two * den_h)
     return K.astype(np.float32), H.astype(np.float32), (H * H).astype(np.float32)

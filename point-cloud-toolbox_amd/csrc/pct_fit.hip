@@ -10,8 +10,8 @@
 // (odd row pitch -> conflict-free column reads; letting every lane stream its
 // own row from global instead was measured 2x slower), then every lane walks
 // its own row twice, gathers issued eight neighbours ahead of their use:
-//   pass 1  centred neighbours (native dtype, pct:641) -> fp64 sums -> 3x3
-//           covariance about the neighbour mean, ddof=1 (pct:277) -> cyclic
+//   pass 1  centred neighbours (native dtype, pct:641) -> fp64 sums about the
+//           first neighbour -> 3x3 covariance, ddof=1 (pct:277) -> cyclic
 //           Jacobi eigen-solve -> normal = eigenvector of the smallest
 //           eigenvalue (== Vt[-1], pct:283) -> sign flip by far-minus-near
 //           neighbour (pct:286-297) -> Rodrigues rotation to +z (pct:300-312)
@@ -262,11 +262,16 @@ __global__ __launch_bounds__(kFitBlock) void k_fit(FitArgs a) {
     double sx = 0, sy = 0, sz = 0, sxx = 0, sxy = 0, sxz = 0, syy = 0, syz = 0, szz = 0;
     double fx = 0, fy = 0, fz = 0, lx = 0, ly = 0, lz = 0;
     // gathers are issued four neighbours ahead of their use (the row walk is latency-bound otherwise)
+    // The moments are taken about the FIRST neighbour, not about the query: the covariance does not care, and a query far
+    // from its neighbourhood (caller-supplied rows with a foreign query, far outliers) no longer costs sxx - sx * mx its
+    // digits -- about the query, 1 000 neighbourhood radii away, the rotation moved by 1e-10, enough to round the
+    // float32 design rows differently from np.cov's (centred) rotation and to miss the contract in H 50- to 1 000-fold.
 #define PASS1_ACC(x, y, z)                                                          \
     do {                                                                            \
-        sx += x; sy += y; sz += z;                                                  \
-        sxx = fma(x, x, sxx); sxy = fma(x, y, sxy); sxz = fma(x, z, sxz);           \
-        syy = fma(y, y, syy); syz = fma(y, z, syz); szz = fma(z, z, szz);           \
+        const double dx = x - fx, dy = y - fy, dz = z - fz;                         \
+        sx += dx; sy += dy; sz += dz;                                               \
+        sxx = fma(dx, dx, sxx); sxy = fma(dx, dy, sxy); sxz = fma(dx, dz, sxz);     \
+        syy = fma(dy, dy, syy); syz = fma(dy, dz, syz); szz = fma(dz, dz, szz);     \
     } while (0)
     // A table entry that is not a record of the cloud (host-supplied rows are validated before they get here, the
     // sweep's rows are the sweep's responsibility: this is the last line of defence) is clamped, never dereferenced,
@@ -577,9 +582,10 @@ __global__ __launch_bounds__(64) void k_fit_svd(FitArgs a, const int* __restrict
             load_centred<F64>(a, (int)min((unsigned)my[j], a.n_pts - 1u), qx, qy, qz, qp.x, qp.y, qp.z, x, y, z);
             if (j == 0) { fx = x; fy = y; fz = z; }
             lx = x; ly = y; lz = z;
-            sx += x; sy += y; sz += z;
-            sxx = fma(x, x, sxx); sxy = fma(x, y, sxy); sxz = fma(x, z, sxz);
-            syy = fma(y, y, syy); syz = fma(y, z, syz); szz = fma(z, z, szz);
+            const double dx = x - fx, dy = y - fy, dz = z - fz;      // about the first neighbour, as k_fit
+            sx += dx; sy += dy; sz += dz;
+            sxx = fma(dx, dx, sxx); sxy = fma(dx, dy, sxy); sxz = fma(dx, dz, sxz);
+            syy = fma(dy, dy, syy); syz = fma(dy, dz, syz); szz = fma(dz, dz, szz);
         }
         double rot[9];
         plane_rotation<F64>(m, sx, sy, sz, sxx, sxy, sxz, syy, syz, szz, fx, fy, fz, lx, ly, lz, rot);

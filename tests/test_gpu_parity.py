@@ -788,7 +788,9 @@ def test_far_outliers_do_not_coarsen_the_cell_list(gpu):
     assert t["cell_size"] < 1.5 * cell0, (t["cell_size"], cell0)
     ref = oracle.pipeline_batched(np.asarray(pc.points), 30)
     assert np.array_equal(pc.neighbor_indices, ref["idx"]) and np.array_equal(pc.dists, ref["dists"])
-    clean = np.arange(len(both)) < len(pts)          # the outliers' own quadrics are ill-conditioned by construction
+    # the outliers' own quadrics are ill-conditioned by construction (a query hundreds of neighbourhood radii away from its
+    # neighbours): what the fit owes such rows is pinned by test_gpu_fit_conditioning.py::test_queries_outside_their_neighbourhood
+    clean = np.arange(len(both)) < len(pts)
     assert_curvature(K, H, ref["K"], ref["H"], mask=clean)
 
 
