@@ -51,7 +51,7 @@ typedef struct pct_timings {
     float upload_ms;          /* H2D of coordinates (0 when device-resident)            */
     float grid_ms;            /* bounding box + cell sizing + counting sort             */
     float knn_ms;             /* neighbour sweep kernel(s) only (fast + exact redo)     */
-    float knn_fast_ms;        /* of which the dominant kernel k_knn_fast alone          */
+    float knn_fast_ms;        /* of which the fast sweep alone: k_knn_pair, k_knn_duo or k_knn_fast, see sweep_variant */
     float fit_ms;             /* fused plane-align + quadric fit + curvature kernel     */
     float export_ms;          /* sorted-space -> public index translation               */
     float total_ms;
@@ -74,7 +74,10 @@ typedef struct pct_timings {
     int64_t fit_svd_rows;     /* rows of the last fit solved by the SVD kernel (lstsq's gelsd semantics: ill-conditioned
                                  or under-determined design matrices) instead of the normal equations */
     int32_t algo;             /* the sweep that produced the table in place (pct_knn_algo; what PCT_KNN_AUTO chose) */
-    int32_t reserved;
+    int32_t sweep_variant;    /* the fast sweep kernel the call launched last, 0 = none (exact-only or exhaustive sweep,
+                                 k > 127, no work items).  Bits 0-1: family (1 k_knn_fast, 2 k_knn_pair, 3 k_knn_duo);
+                                 then one bit per template argument: 2 R = 2, 3 EPS, 4 PRE, 5 PAIR, 6 Q64, 7 TREE, 8 DIST
+                                 (k_knn_pair and k_knn_duo report PRE = PAIR = 1).  Every variant returns the same rows */
 } pct_timings;
 
 /* ---- lifetime ---------------------------------------------------------- */

@@ -129,7 +129,16 @@ int pct_device_count(int* count) {
 // action).  Twice in two rounds a GPU test run died with nothing but "Fatal Python error: Aborted" in its log -- no
 // GPU fault line, no glibc diagnostic: the raiser is some library's bare abort(), possibly on a runtime
 // helper thread that a Python traceback cannot show.  Tests, bench.py and smoke() switch this on.
-extern "C++" { const char* pct_last_launch = "(none)"; }
+extern "C++" {
+const char* pct_last_launch = "(none)";
+const char* pct_launch_name(const char* where, const char* instantiation) {
+    const size_t len = strlen(where) + 2 + strlen(instantiation) + 1;
+    char* s = (char*)malloc(len);
+    if (!s) return where;
+    snprintf(s, len, "%s  %s", where, instantiation);
+    return s;
+}
+}
 static struct sigaction g_prev_abrt;
 static int g_abrt_fd = 2;       // PCT_ABORT_TRACE=<fd>: a descriptor of the REAL stderr (a test runner that captures fd 2
                                 // -- pytest -- would swallow the trace with the dying process; tests/conftest.py dups it
@@ -470,6 +479,7 @@ static int run_knn(pct_ctx* ctx, int32_t k, double eps, int32_t algo, bool fuse_
     ctx->eps = eps;
     PCT_HIP(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
     ctx->tm.levels = 0;
+    ctx->tm.sweep_variant = 0;         // (set by the fast sweep's launch, pct_knn.hip)
     ctx->tm.algo = algo;
     const auto run_levels = [&]() -> int {
         ctx->tm.algo = PCT_KNN_GRID_LEVELS;

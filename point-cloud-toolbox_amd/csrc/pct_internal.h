@@ -25,6 +25,34 @@ extern const char* pct_last_launch;
         __atomic_store_n(&pct_last_launch, __FILE__ ":" PCT_STR(__LINE__) "  " #kernelName, __ATOMIC_RELAXED); \
         hipLaunchKernelGGL((kernelName), __VA_ARGS__);                                       \
     } while (0)
+// The same from a launcher template, whose kernel argument is spelled in template parameters: the instantiation's own
+// __PRETTY_FUNCTION__ follows the position, so the word still names every template argument by value.  One string per
+// instantiation, composed at its first launch and never freed (the abort hook may read it at any time).
+const char* pct_launch_name(const char* where, const char* instantiation);
+#define PCT_LAUNCH_T(kernelName, ...)                                                        \
+    do {                                                                                     \
+        static const char* const name_ = pct_launch_name(__FILE__ ":" PCT_STR(__LINE__) "  " #kernelName, __PRETTY_FUNCTION__); \
+        __atomic_store_n(&pct_last_launch, name_, __ATOMIC_RELAXED);                         \
+        hipLaunchKernelGGL((kernelName), __VA_ARGS__);                                       \
+    } while (0)
+
+// Staging capacities of the fast sweeps (candidates of a work item's stencil held in LDS per wave), defined HERE ONLY:
+// the sweep kernels (pct_knn.hip) are compiled for them, the work-item census counts overflows against them and the
+// hierarchical list's build (pct_tree.hip) refines its segments down to them.  A -D that overrides one must reach EVERY
+// translation unit (PCT_EXTRA_FLAGS does; a per-file flag would size the tree's refinement for another capacity than
+// the kernels stage).
+#ifndef PCT_STAGE_CAP
+#define PCT_STAGE_CAP 512                  // uniform list, one list register (k_knn_fast<1>, k_knn_pair)
+#endif
+#ifndef PCT_STAGE_CAP2
+#define PCT_STAGE_CAP2 768                 // ... two list registers (k_knn_fast<2>)
+#endif
+#ifndef PCT_TREE_CAP
+#define PCT_TREE_CAP 768                   // staged candidates of a work item of the hierarchical cell list (A/B: 512 | 768 | 1024)
+#endif
+#ifndef PCT_TREE_CAP2
+#define PCT_TREE_CAP2 1024                 // ... for k + 1 > 64 (two list registers): the proofs want ~2.6 (k+1) stencil points
+#endif
 
 // ---------------------------------------------------------------------------
 // Uniform cell list over the float32-rounded cloud.

@@ -260,9 +260,6 @@ template <int R, bool EPS, bool PRE, bool PAIR = false, bool Q64 = false, bool T
 __global__ __launch_bounds__(64 * kFastWaves<R>, (TREE ? (R == 1 ? (PCT_TREE_CAP <= 512 ? 6 : PCT_TREE_CAP <= 768 ? 4 : 3) : (PCT_TREE_CAP2 <= 768 ? 4 : 3)) : R == 1 ? (Q64 ? 5 : 6) : 4)) void k_knn_fast(KnnArgs a, const int2* __restrict__ items, int64_t n_items,
                                                                   int items_q, int* __restrict__ redo,
                                                                   int* __restrict__ redo_count) {
-#ifndef PCT_STAGE_CAP2
-#define PCT_STAGE_CAP2 768
-#endif
     // (tree items: an octree level changes the population fourfold on a surface; segments whose stencil exceeds the
     // staging area are split further at build time (k_tree_refine), so the capacity trades refinement and trips to
     // the exact sweep against occupancy: 768 slots / 4 blocks per CU measured best -- 1/r^2 scan, 1 M points: fast
@@ -2382,33 +2379,169 @@ int reserve_table(pct_ctx* ctx, int32_t k, double eps, bool with_dist = true) {
     return PCT_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Which fast sweep a call takes: decided once (plan_sweep), launched once (launch_sweep), reported in
+// pct_timings.sweep_variant.  Every choice returns the same rows bit for bit; only the timings tell them apart.
+// ---------------------------------------------------------------------------
+enum SweepFamily { kNoSweep = 0, kFast = 1, kPair = 2, kDuo = 3 };      // none | k_knn_fast | k_knn_pair | k_knn_duo
+
+// the six (PRE, PAIR, Q64, TREE) forms k_knn_fast exists in: its static assertions and launch bounds know no other
+enum FastForm { kPlain, kPre, kPrePair, kPrePairQ64, kTree, kTreeQ64, kFastForms };
+struct FastFlags { bool pre, pair, q64, tree; };
+constexpr FastFlags kFastFlags[kFastForms] = {{false, false, false, false}, {true, false, false, false}, {true, true, false, false},
+                                              {true, true, true, false},    {true, true, false, true},   {true, true, true, true}};
+
+struct SweepPlan {
+    SweepFamily family = kNoSweep;
+    FastForm form = kPlain;             // family == kFast: which of the six (the four flags below, as one value)
+    int R = 1;                          // list registers per lane
+    bool eps = false, pre = false, pair = false, q64 = false, tree = false;
+    bool dist = true;                   // the distance table is written
+    bool lean() const { return family == kPair || family == kDuo; }
+    // pct_timings.sweep_variant (include/pct_hip.h)
+    int32_t variant() const {
+        if (family == kNoSweep) return 0;
+        return family | (R == 2) << 2 | eps << 3 | pre << 4 | pair << 5 | q64 << 6 | tree << 7 | dist << 8;
+    }
+};
+
+// tree: the hierarchical cell list is in place (whole clouds, one pass), else the uniform one; exact_only / phase as in
+// pct_launch_knn_grid.  Every tuning switch (PCT_*: A/B aids, read per call -- tests flip them) is read here.
+SweepPlan plan_sweep(const pct_ctx* ctx, int32_t k, double eps, bool tree, bool exact_only, int phase) {
+    SweepPlan p;
+    if (exact_only || phase == 2 || ctx->n_items <= 0) return p;
+    p.eps = eps > 0;
+    p.tree = tree;
+    const bool r1 = k + 1 <= pct_fast_r1_max(), f64 = ctx->has_f64;
+    const bool no_pair = pct_getenv("PCT_NO_PAIR") != nullptr;
+    bool lean = ctx->n_items < ((int64_t)1 << 31) - 8 && !no_pair;
+    if (tree) {
+        // float64 clouds: the variant whose bounds are widened by the distance between a query and its float32 rounding
+        // (Q64); where that distance is not small against the item's cells the proofs fail and the exact sweep answers
+        p.form = f64 ? kTreeQ64 : kTree;
+    } else {
+        // The float32 pre-selection squares coordinate differences of up to three cell edges: outside this window
+        // they overflow (or the eps ball's radius underflows) and every candidate would fail the threshold test,
+        // so such clouds take the variant that keys every candidate in float64.
+        const pct_grid& g = ctx->grid;
+        const double c2 = g.cell * g.cell;
+        const bool f32_ok = c2 > 1e-30 && c2 < 1e30 && (!(eps > 0) || eps * eps > 1e-36);
+        // Float64 clouds pre-select too (Q64: bounds widened by the rounding distance of the query) unless that
+        // distance is not small against a cell edge -- coordinates so large that float32 resolves them barely finer
+        // than the cells: there every query would be sent to the exact sweep.
+        const double far = fmax(fmax(fabs(g.ox), fabs(g.ox + g.nx * g.cell)),
+                                fmax(fmax(fabs(g.oy), fabs(g.oy + g.ny * g.cell)), fmax(fabs(g.oz), fabs(g.oz + g.nz * g.cell))));
+        const bool near = far * 0x1p-23 < g.cell * 0x1p-7;
+        p.form = f64 ? (f32_ok && near && !ctx->level_mode && !no_pair ? kPrePairQ64 : kPlain) : !f32_ok ? kPlain : no_pair ? kPre : kPrePair;
+        // the scalar-lean kernels take the plain sweep only: one pass, ownership by index range
+        lean = lean && phase == 0 && (!f64 || near) && f32_ok && !ctx->own_flag && !ctx->level_mode;
+    }
+    // rows of up to kFastR1Max entries: k_knn_pair; up to 128 (two list registers): k_knn_duo; anything else: k_knn_fast
+    if (lean && r1 && !pct_getenv("PCT_NO_PAIR_KERNEL")) p.family = kPair;
+    else if (lean && !r1 && k + 1 <= 128 && !pct_getenv("PCT_NO_DUO_KERNEL")) p.family = kDuo;
+    else p.family = kFast;
+    p.R = p.family == kDuo || (p.family == kFast && !r1) ? 2 : 1;
+    const FastFlags f = p.lean() ? FastFlags{true, true, f64, tree} : kFastFlags[p.form];
+    p.pre = f.pre; p.pair = f.pair; p.q64 = f.q64;
+    // the fused curvature call, whose fit never reads distances, has the lean kernels write no distance table
+    // (pct_get_neighbors derives the same bits from the positions when asked)
+    p.dist = !(p.lean() && ctx->skip_dist_req && !pct_getenv("PCT_KEEP_DIST"));
+    return p;
+}
+
+PairArgs make_pair_args(const pct_ctx* ctx, const KnnArgs& a, bool tree, int* redo, int* redo_count) {
+    PairArgs pa = {};
+    pa.pts = a.pts; pa.ptsd = a.ptsd; pa.cell_start = a.cell_start;
+    pa.items = (const int2*)ctx->occ.p;
+    pa.nbr_pos = a.nbr_pos; pa.nbr_dist = a.nbr_dist; pa.nbr_cnt = a.nbr_cnt;
+    pa.redo = redo; pa.redo_count = redo_count; pa.counters = a.counters;
+    pa.n_items = (int)ctx->n_items; pa.items_q = ctx->items_q;
+    pa.k = a.k; pa.pitch = a.pitch; pa.stats = a.stats; pa.eps2 = a.eps2; pa.g = a.g;
+    pa.items_per_xcd = pct_getenv("PCT_NO_XCD_MAP") ? 0 : (int)((ctx->n_items + 7) / 8);
+    if (tree) {
+        pa.tree_seg = a.tree_seg; pa.tree_runs = a.tree_runs; pa.tree_bits = a.tree_bits;
+        return pa;
+    }
+    pa.cell_own = a.cell_own; pa.own_start = a.own_start;
+    // x / d = (x * magic) >> shift for every x < 2^30 (cell ids): shift = 30 + ceil(log2 d), magic = ceil(2^shift / d) < 2^32
+    const auto magic = [](unsigned d, unsigned* mg, int* sh) {
+        int l = 0;
+        while ((1ull << l) < d) ++l;
+        *sh = 30 + l;
+        *mg = (unsigned)(((1ull << *sh) + d - 1) / d);
+    };
+    magic((unsigned)a.g.nx, &pa.magic_x, &pa.shift_x);
+    magic((unsigned)a.g.nx * (unsigned)a.g.ny, &pa.magic_xy, &pa.shift_xy);
+    return pa;
+}
+
+// Runtime values -> template arguments: f(std::bool_constant...) for the bools given, f(std::integral_constant<int, i>) for i < N
+template <class F, class... Rest>
+void with_bools(F&& f, bool b, Rest... rest) {
+    if constexpr (sizeof...(rest) == 0) {
+        if (b) f(std::true_type{}); else f(std::false_type{});
+    } else {
+        if (b) with_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+        else with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+    }
+}
+template <int N, class F>
+void with_index(int i, F&& f) {
+    if constexpr (N > 0) {
+        if (i == N - 1) f(std::integral_constant<int, N - 1>{}); else with_index<N - 1>(i, f);
+    }
+}
+
+// The one launch site of each family (PCT_LAUNCH_T: the abort trace names the instantiation by its argument values).
+template <int R, bool EPS, bool PRE, bool PAIR, bool Q64, bool TREE>
+void launch_fast(pct_ctx* ctx, const KnnArgs& a, int* redo, int* redo_count) {
+    const dim3 grid((unsigned)((ctx->n_items + kFastWaves<R> - 1) / kFastWaves<R>)), block(64 * kFastWaves<R>);
+    PCT_LAUNCH_T((k_knn_fast<R, EPS, PRE, PAIR, Q64, TREE>), grid, block, 0, ctx->stream, a, (const int2*)ctx->occ.p, ctx->n_items,
+                 ctx->items_q, redo, redo_count);
+}
+// (blocks are dealt to the 8 XCDs in turn, PairArgs::items_per_xcd; PCT_NO_XCD_MAP: one block per item in order)
+template <bool EPS, bool DIST, bool Q64, bool TREE>
+void launch_pair(pct_ctx* ctx, const PairArgs& pa) {
+    const int64_t n_blk = pa.items_per_xcd ? (int64_t)pa.items_per_xcd * 8 : ctx->n_items;
+    PCT_LAUNCH_T((k_knn_pair<EPS, DIST, Q64, TREE>), dim3((unsigned)((n_blk + kPairWaves - 1) / kPairWaves)), dim3(64 * kPairWaves), 0,
+                 ctx->stream, pa);
+}
+template <bool EPS, bool DIST, bool Q64, bool TREE>
+void launch_duo(pct_ctx* ctx, const PairArgs& pa) {
+    const int64_t n_blk = pa.items_per_xcd ? (int64_t)pa.items_per_xcd * 8 : ctx->n_items;
+    PCT_LAUNCH_T((k_knn_duo<EPS, DIST, Q64, TREE>), dim3((unsigned)n_blk), dim3(64), 0, ctx->stream, pa);
+}
+
+int launch_sweep(pct_ctx* ctx, const SweepPlan& p, const KnnArgs& a, int* redo, int* redo_count) {
+    if (p.family == kNoSweep) return PCT_OK;
+    if (p.family == kFast) {
+        with_bools([&](auto r2, auto e) {
+            with_index<kFastForms>(p.form, [&](auto form) {
+                constexpr FastFlags f = kFastFlags[form];
+                launch_fast<(r2 ? 2 : 1), e, f.pre, f.pair, f.q64, f.tree>(ctx, a, redo, redo_count);
+            });
+        }, p.R == 2, p.eps);
+    } else {
+        const PairArgs pa = make_pair_args(ctx, a, p.tree, redo, redo_count);
+        with_bools([&](auto e, auto d, auto q, auto t) {
+            if (p.family == kDuo) launch_duo<e, d, q, t>(ctx, pa);
+            else launch_pair<e, d, q, t>(ctx, pa);
+        }, p.eps, p.dist, p.q64, p.tree);
+    }
+    PCT_HIP(ctx, hipGetLastError());
+    ctx->tm.sweep_variant = p.variant();
+    return PCT_OK;
+}
+
 }  // namespace
 
 // phase 0: fast sweep + exact sweep of what it flagged (or, exact_only, the exact sweep of every query);
 // phase 1: fast sweep only, the flagged rows stay in ctx->redo (level passes); phase 2: exact sweep of ctx->redo
 int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, int phase) {
     const int64_t n_rows = ctx->own_flag ? ctx->own_count : ctx->q_end - ctx->q_begin;
-    // The plain sweep of a float32 cloud with one list register goes to the scalar-lean kernel (k_knn_pair); there the
-    // fused curvature call, whose fit never reads distances, writes no distance table (pct_get_neighbors derives the
-    // same bits from the positions when asked).
-    const double c2_ = ctx->grid.cell * ctx->grid.cell;                // (the float32 pre-selection's range, see f32_ok below)
-    const bool f32_ok_ = c2_ > 1e-30 && c2_ < 1e30 && (!(eps > 0) || eps * eps > 1e-36);
-    // (float64 clouds take it too unless the rounding distance of the queries is not small against a cell edge --
-    // coordinates so large that float32 resolves them barely finer than the cells: see q64_ok below)
-    const pct_grid& gg_ = ctx->grid;
-    const double far_ = fmax(fmax(fabs(gg_.ox), fabs(gg_.ox + gg_.nx * gg_.cell)),
-                             fmax(fmax(fabs(gg_.oy), fabs(gg_.oy + gg_.ny * gg_.cell)), fmax(fabs(gg_.oz), fabs(gg_.oz + gg_.nz * gg_.cell))));
-    const bool q64_ok_ = !ctx->has_f64 || far_ * 0x1p-23 < gg_.cell * 0x1p-7;
-    const bool pair_kernel = !exact_only && phase == 0 && q64_ok_ && f32_ok_ && !ctx->own_flag && !ctx->level_mode && ctx->n_items > 0 &&
-                             k + 1 <= pct_fast_r1_max() && ctx->n_items < ((int64_t)1 << 31) - 8 && !pct_getenv("PCT_NO_PAIR") &&
-                             !pct_getenv("PCT_NO_PAIR_KERNEL");
-    // rows of 62 .. 128 entries: the same scheme with two list registers (k_knn_duo)
-    const bool duo_kernel = !exact_only && phase == 0 && q64_ok_ && f32_ok_ && !ctx->own_flag && !ctx->level_mode && ctx->n_items > 0 &&
-                            k + 1 > pct_fast_r1_max() && k + 1 <= 128 && ctx->n_items < ((int64_t)1 << 31) - 8 &&
-                            !pct_getenv("PCT_NO_PAIR") && !pct_getenv("PCT_NO_DUO_KERNEL");
-    const bool skip_dist = (pair_kernel || duo_kernel) && ctx->skip_dist_req && !pct_getenv("PCT_KEEP_DIST");
+    const SweepPlan plan = plan_sweep(ctx, k, eps, false, exact_only, phase);
     if (phase != 2) {
-        PCT_TRY(reserve_table(ctx, k, eps, !skip_dist));
+        PCT_TRY(reserve_table(ctx, k, eps, plan.dist));
         PCT_TRY(pct_reserve(ctx, &ctx->redo, ((size_t)n_rows + 16) * sizeof(int)));
         if (ctx->level_mode) PCT_TRY(pct_reserve(ctx, &ctx->redo_m, ((size_t)n_rows + 16) * sizeof(int)));
     }
@@ -2417,99 +2550,7 @@ int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, in
     int* redo_count = (int*)ctx->counters.p + 14;            // counters buffer: 8 x u64, last int pair reserved
     int* redo = (int*)ctx->redo.p;
     const dim3 block(64 * kWavesPerBlock);
-    if (!exact_only && phase != 2 && ctx->n_items > 0) {
-        const dim3 grid1((unsigned)((ctx->n_items + kFastWaves<1> - 1) / kFastWaves<1>)), block1(64 * kFastWaves<1>);
-        const dim3 grid2((unsigned)((ctx->n_items + kFastWaves<2> - 1) / kFastWaves<2>)), block2(64 * kFastWaves<2>);
-        const int2* items = (const int2*)ctx->occ.p;
-        // The float32 pre-selection squares coordinate differences of up to three cell edges: outside this window
-        // they overflow (or the eps ball's radius underflows) and every candidate would fail the threshold test,
-        // so such clouds take the variant that keys every candidate in float64.
-        const double c2 = ctx->grid.cell * ctx->grid.cell;
-        const bool f32_ok = c2 > 1e-30 && c2 < 1e30 && (!(eps > 0) || eps * eps > 1e-36);
-        // Float64 clouds take the paired pre-selecting variant too (Q64: bounds widened by the rounding distance of the
-        // query) unless that distance is not small against a cell edge -- coordinates so large that float32 resolves
-        // them barely finer than the cells: there every query would be sent to the exact sweep.
-        const pct_grid& gg = ctx->grid;
-        const double far = fmax(fmax(fabs(gg.ox), fabs(gg.ox + gg.nx * gg.cell)),
-                                fmax(fmax(fabs(gg.oy), fabs(gg.oy + gg.ny * gg.cell)), fmax(fabs(gg.oz), fabs(gg.oz + gg.nz * gg.cell))));
-        const bool q64_ok = ctx->has_f64 && f32_ok && far * 0x1p-23 < gg.cell * 0x1p-7 && !ctx->level_mode;
-        const bool e = eps > 0, pre = !ctx->has_f64 && f32_ok, r1 = k + 1 <= pct_fast_r1_max();
-#define PCT_FAST(R_, E_, P_, GRID_, BLOCK_) \
-    PCT_LAUNCH((k_knn_fast<R_, E_, P_>), GRID_, BLOCK_, 0, ctx->stream, a, items, ctx->n_items, ctx->items_q, redo, redo_count)
-        const bool no_pair = pct_getenv("PCT_NO_PAIR") != nullptr;                 // tuning aid (read per call: tests flip it)
-#define PCT_FAST_PAIR(R_, E_, GRID_, BLOCK_) \
-    PCT_LAUNCH((k_knn_fast<R_, E_, true, true>), GRID_, BLOCK_, 0, ctx->stream, a, items, ctx->n_items, ctx->items_q, redo, redo_count)
-#define PCT_FAST_PAIR64(R_, E_, GRID_, BLOCK_) \
-    PCT_LAUNCH((k_knn_fast<R_, E_, true, true, true>), GRID_, BLOCK_, 0, ctx->stream, a, items, ctx->n_items, ctx->items_q, redo, redo_count)
-        // the plain sweep of a float32 cloud with one list register: the scalar-lean kernel (k_knn_pair)
-        if (pair_kernel || duo_kernel) {
-            PairArgs pa = {};
-            pa.pts = a.pts; pa.ptsd = a.ptsd; pa.cell_start = a.cell_start; pa.cell_own = a.cell_own; pa.own_start = a.own_start;
-            pa.items = items;
-            pa.nbr_pos = a.nbr_pos; pa.nbr_dist = a.nbr_dist; pa.nbr_cnt = a.nbr_cnt;
-            pa.redo = redo; pa.redo_count = redo_count; pa.counters = a.counters;
-            pa.n_items = (int)ctx->n_items; pa.items_q = ctx->items_q;
-            pa.k = a.k; pa.pitch = a.pitch; pa.stats = a.stats; pa.eps2 = a.eps2; pa.g = a.g;
-            // x / d = (x * magic) >> shift for every x < 2^30 (cell ids): shift = 30 + ceil(log2 d), magic = ceil(2^shift / d) < 2^32
-            const auto magic = [](unsigned d, unsigned* mg, int* sh) {
-                int l = 0;
-                while ((1ull << l) < d) ++l;
-                *sh = 30 + l;
-                *mg = (unsigned)(((1ull << *sh) + d - 1) / d);
-            };
-            magic((unsigned)a.g.nx, &pa.magic_x, &pa.shift_x);
-            magic((unsigned)a.g.nx * (unsigned)a.g.ny, &pa.magic_xy, &pa.shift_xy);
-            pa.items_per_xcd = (int)((ctx->n_items + 7) / 8);
-            if (pct_getenv("PCT_NO_XCD_MAP")) pa.items_per_xcd = 0;
-            const int64_t n_blk = pa.items_per_xcd ? (int64_t)pa.items_per_xcd * 8 : ctx->n_items;
-            const dim3 gridp((unsigned)((n_blk + kPairWaves - 1) / kPairWaves)), blockp(64 * kPairWaves);
-            if (duo_kernel) {
-                const dim3 gridd((unsigned)n_blk), blockd(64);
-                if (ctx->has_f64) {
-                    if (e && skip_dist) PCT_LAUNCH((k_knn_duo<true, false, true>), gridd, blockd, 0, ctx->stream, pa);
-                    else if (e) PCT_LAUNCH((k_knn_duo<true, true, true>), gridd, blockd, 0, ctx->stream, pa);
-                    else if (skip_dist) PCT_LAUNCH((k_knn_duo<false, false, true>), gridd, blockd, 0, ctx->stream, pa);
-                    else PCT_LAUNCH((k_knn_duo<false, true, true>), gridd, blockd, 0, ctx->stream, pa);
-                } else
-                if (e && skip_dist) PCT_LAUNCH((k_knn_duo<true, false>), gridd, blockd, 0, ctx->stream, pa);
-                else if (e) PCT_LAUNCH((k_knn_duo<true, true>), gridd, blockd, 0, ctx->stream, pa);
-                else if (skip_dist) PCT_LAUNCH((k_knn_duo<false, false>), gridd, blockd, 0, ctx->stream, pa);
-                else PCT_LAUNCH((k_knn_duo<false, true>), gridd, blockd, 0, ctx->stream, pa);
-            } else
-            if (ctx->has_f64) {
-                if (e && skip_dist) PCT_LAUNCH((k_knn_pair<true, false, true>), gridp, blockp, 0, ctx->stream, pa);
-                else if (e) PCT_LAUNCH((k_knn_pair<true, true, true>), gridp, blockp, 0, ctx->stream, pa);
-                else if (skip_dist) PCT_LAUNCH((k_knn_pair<false, false, true>), gridp, blockp, 0, ctx->stream, pa);
-                else PCT_LAUNCH((k_knn_pair<false, true, true>), gridp, blockp, 0, ctx->stream, pa);
-            } else
-            if (e && skip_dist) PCT_LAUNCH((k_knn_pair<true, false>), gridp, blockp, 0, ctx->stream, pa);
-            else if (e) PCT_LAUNCH((k_knn_pair<true, true>), gridp, blockp, 0, ctx->stream, pa);
-            else if (skip_dist) PCT_LAUNCH((k_knn_pair<false, false>), gridp, blockp, 0, ctx->stream, pa);
-            else PCT_LAUNCH((k_knn_pair<false, true>), gridp, blockp, 0, ctx->stream, pa);
-        } else
-        if (q64_ok && !no_pair) {
-            if (r1 && !e) PCT_FAST_PAIR64(1, false, grid1, block1);
-            else if (r1) PCT_FAST_PAIR64(1, true, grid1, block1);
-            else if (!e) PCT_FAST_PAIR64(2, false, grid2, block2);
-            else PCT_FAST_PAIR64(2, true, grid2, block2);
-        } else
-        if (r1 && !e && pre && !no_pair) PCT_FAST_PAIR(1, false, grid1, block1);
-        else if (r1 && e && pre && !no_pair) PCT_FAST_PAIR(1, true, grid1, block1);
-        else if (!r1 && !e && pre && !no_pair) PCT_FAST_PAIR(2, false, grid2, block2);
-        else if (!r1 && e && pre && !no_pair) PCT_FAST_PAIR(2, true, grid2, block2);
-        else if (r1 && !e && pre) PCT_FAST(1, false, true, grid1, block1);
-        else if (r1 && e && pre) PCT_FAST(1, true, true, grid1, block1);
-        else if (r1 && !e) PCT_FAST(1, false, false, grid1, block1);
-        else if (r1) PCT_FAST(1, true, false, grid1, block1);
-        else if (!e && pre) PCT_FAST(2, false, true, grid2, block2);
-        else if (e && pre) PCT_FAST(2, true, true, grid2, block2);
-        else if (!e) PCT_FAST(2, false, false, grid2, block2);
-        else PCT_FAST(2, true, false, grid2, block2);
-#undef PCT_FAST
-#undef PCT_FAST_PAIR
-#undef PCT_FAST_PAIR64
-        PCT_HIP(ctx, hipGetLastError());
-    }
+    PCT_TRY(launch_sweep(ctx, plan, a, redo, redo_count));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[7], ctx->stream));      // end of the dominant kernel
     // exact pass: the flagged queries (device-side count, fixed grid) or, for testing, every query
     if (phase != 1) {
@@ -2535,14 +2576,9 @@ int pct_launch_knn_tree(pct_ctx* ctx, int32_t k, double eps) {
     if (ctx->level_mode || ctx->own_flag || ctx->q_begin != 0 || ctx->q_end != ctx->n)
         return pct_fail(ctx, PCT_ERR_INVALID, "the tree sweep takes whole clouds");
     const int64_t n_rows = ctx->n;
-    // one list register: the scalar-lean kernel's TREE instantiation (k_knn_pair); it can leave the distance table out
-    // for the fused call, like the uniform list's
-    const bool lean_ok = ctx->n_items > 0 && ctx->n_items < ((int64_t)1 << 31) - 8 && !pct_getenv("PCT_NO_PAIR") &&
-                         !pct_getenv("PCT_TREE_EXACT_ONLY");
-    const bool pair_tree = lean_ok && k + 1 <= pct_fast_r1_max() && !pct_getenv("PCT_NO_PAIR_KERNEL");
-    const bool duo_tree = lean_ok && k + 1 > pct_fast_r1_max() && k + 1 <= 128 && !pct_getenv("PCT_NO_DUO_KERNEL");     // two list registers: k_knn_duo
-    const bool skip_dist = (pair_tree || duo_tree) && ctx->skip_dist_req && !pct_getenv("PCT_KEEP_DIST");
-    PCT_TRY(reserve_table(ctx, k, eps, !skip_dist));
+    const bool exact_only = pct_getenv("PCT_TREE_EXACT_ONLY") != nullptr;        // testing: every query through the exact sweep
+    const SweepPlan plan = plan_sweep(ctx, k, eps, true, exact_only, 0);
+    PCT_TRY(reserve_table(ctx, k, eps, plan.dist));
     PCT_TRY(pct_reserve(ctx, &ctx->redo, ((size_t)n_rows + 16) * sizeof(int)));
     KnnArgs a = make_args(ctx, k, eps, true);
     if (!ctx->dist_valid) a.nbr_dist = nullptr;
@@ -2554,57 +2590,7 @@ int pct_launch_knn_tree(pct_ctx* ctx, int32_t k, double eps) {
     a.tree_bucket = (const int*)ctx->tree_bucket.p;
     int* redo_count = (int*)ctx->counters.p + 14;
     int* redo = (int*)ctx->redo.p;
-    const int2* items = (const int2*)ctx->occ.p;
-    const bool r1 = k + 1 <= pct_fast_r1_max();
-    const bool exact_only = pct_getenv("PCT_TREE_EXACT_ONLY") != nullptr;        // testing: every query through the exact sweep
-    if (ctx->n_items > 0 && !exact_only) {
-        const dim3 grid1((unsigned)((ctx->n_items + kFastWaves<1> - 1) / kFastWaves<1>)), block1(64 * kFastWaves<1>);
-        const dim3 grid2((unsigned)((ctx->n_items + kFastWaves<2> - 1) / kFastWaves<2>)), block2(64 * kFastWaves<2>);
-        const bool e = eps > 0;
-        // float64 clouds: the variant whose bounds are widened by the distance between a query and its float32 rounding
-        // (Q64); where that distance is not small against the item's cells the proofs fail and the exact sweep answers
-#define PCT_TREE(R_, E_, Q_, GRID_, BLOCK_) \
-    PCT_LAUNCH((k_knn_fast<R_, E_, true, true, Q_, true>), GRID_, BLOCK_, 0, ctx->stream, a, items, ctx->n_items, ctx->items_q, redo, redo_count)
-        if (pair_tree || duo_tree) {
-            PairArgs pa = {};
-            pa.pts = a.pts; pa.ptsd = a.ptsd; pa.cell_start = a.cell_start;
-            pa.items = items;
-            pa.nbr_pos = a.nbr_pos; pa.nbr_dist = a.nbr_dist; pa.nbr_cnt = a.nbr_cnt;
-            pa.redo = redo; pa.redo_count = redo_count; pa.counters = a.counters;
-            pa.n_items = (int)ctx->n_items; pa.items_q = ctx->items_q;
-            pa.k = a.k; pa.pitch = a.pitch; pa.stats = a.stats; pa.eps2 = a.eps2; pa.g = a.g;
-            pa.tree_seg = a.tree_seg; pa.tree_runs = a.tree_runs; pa.tree_bits = a.tree_bits;
-            pa.items_per_xcd = pct_getenv("PCT_NO_XCD_MAP") ? 0 : (int)((ctx->n_items + 7) / 8);
-            const int64_t n_blk = pa.items_per_xcd ? (int64_t)pa.items_per_xcd * 8 : ctx->n_items;
-            const dim3 gridp((unsigned)((n_blk + kPairWaves - 1) / kPairWaves)), blockp(64 * kPairWaves);
-#define PCT_PAIR_TREE(E_, D_, Q_)                                                                       \
-    do {                                                                                                \
-        if (duo_tree) PCT_LAUNCH((k_knn_duo<E_, D_, Q_, true>), dim3((unsigned)n_blk), dim3(64), 0, ctx->stream, pa); \
-        else PCT_LAUNCH((k_knn_pair<E_, D_, Q_, true>), gridp, blockp, 0, ctx->stream, pa);           \
-    } while (0)
-            if (ctx->has_f64) {
-                if (e && skip_dist) PCT_PAIR_TREE(true, false, true);
-                else if (e) PCT_PAIR_TREE(true, true, true);
-                else if (skip_dist) PCT_PAIR_TREE(false, false, true);
-                else PCT_PAIR_TREE(false, true, true);
-            } else if (e && skip_dist) PCT_PAIR_TREE(true, false, false);
-            else if (e) PCT_PAIR_TREE(true, true, false);
-            else if (skip_dist) PCT_PAIR_TREE(false, false, false);
-            else PCT_PAIR_TREE(false, true, false);
-#undef PCT_PAIR_TREE
-        } else
-        if (ctx->has_f64) {
-            if (r1 && !e) PCT_TREE(1, false, true, grid1, block1);
-            else if (r1) PCT_TREE(1, true, true, grid1, block1);
-            else if (!e) PCT_TREE(2, false, true, grid2, block2);
-            else PCT_TREE(2, true, true, grid2, block2);
-        } else if (r1 && !e) PCT_TREE(1, false, false, grid1, block1);
-        else if (r1) PCT_TREE(1, true, false, grid1, block1);
-        else if (!e) PCT_TREE(2, false, false, grid2, block2);
-        else PCT_TREE(2, true, false, grid2, block2);
-#undef PCT_TREE
-        PCT_HIP(ctx, hipGetLastError());
-    }
+    PCT_TRY(launch_sweep(ctx, plan, a, redo, redo_count));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
     const int blocks = (32768 + kWavesPerBlock - 1) / kWavesPerBlock;        // device-side count, fixed grid
     const int* list = exact_only ? nullptr : redo;

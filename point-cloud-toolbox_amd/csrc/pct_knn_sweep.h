@@ -49,20 +49,8 @@ int pct_launch_knn_brute_wide(pct_ctx* ctx, const KnnArgs& a, int blocks);
 namespace {
 
 constexpr int kWavesPerBlock = 4;
-#ifndef PCT_STAGE_CAP
-#define PCT_STAGE_CAP 512
-#endif
-constexpr int kStageCap = PCT_STAGE_CAP;   // LDS-staged stencil candidates per wave and per 64 list slots (12 B each, SoA)
-#ifndef PCT_STAGE_CAP2
-#define PCT_STAGE_CAP2 768
-#endif
+constexpr int kStageCap = PCT_STAGE_CAP;   // LDS-staged stencil candidates per wave and per 64 list slots (12 B each, SoA); pct_internal.h
 constexpr int PCT_STAGE_CAP2_HOST = PCT_STAGE_CAP2;
-#ifndef PCT_TREE_CAP
-#define PCT_TREE_CAP 768                   // staged candidates of a work item of the hierarchical cell list (A/B: 512 | 768 | 1024)
-#endif
-#ifndef PCT_TREE_CAP2
-#define PCT_TREE_CAP2 1024                 // ... for k + 1 > 64 (two list registers): the proofs want ~2.6 (k+1) stencil points
-#endif
 
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }

@@ -410,13 +410,7 @@ int pct_build_tree(pct_ctx* ctx, int32_t k, double eps, bool* usable) {
     int64_t n_items = totals[0], n_segs = totals[1];
     if (n_items <= 0 || n_items > n || n_segs <= 0 || n_segs > n_items)
         return pct_fail(ctx, PCT_ERR_INVALID, "tree build: %lld items in %lld segments for %lld points", (long long)n_items, (long long)n_segs, (long long)n);
-    // staging capacity of the sweep that will run (k_knn_fast<..., TREE>)
-#ifndef PCT_TREE_CAP
-#define PCT_TREE_CAP 768
-#endif
-#ifndef PCT_TREE_CAP2
-#define PCT_TREE_CAP2 1024
-#endif
+    // staging capacity of the sweep that will run (pct_internal.h)
     int cap = k + 1 <= pct_fast_r1_max() ? PCT_TREE_CAP : PCT_TREE_CAP2;
     if (const char* e = pct_getenv("PCT_TREE_SPLIT")) { const int v = atoi(e); if (v >= 64 && v <= cap) cap = v; }       // tuning aid
     size_t room = (size_t)n_segs + nn / 8 + 64;           // segments the range table has room for
