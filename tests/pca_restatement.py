@@ -69,7 +69,9 @@ def restate(points, k, rows=None):
 def compare(got, ref, l3, rows_mask=None):
     """Boolean (rows,) mask of the rows that meet the issue's bars: eigenvalues and H within 1e-12 l1, K within 1e-12 l1^2,
     each direction equal up to sign within 1e-9 l1 / gap where its gap exceeds 1e-6 l1, span{v1, v2} as a projector
-    within 1e-9 l1 / (l2 - l3)."""
+    within 1e-9 l1 / (l2 - l3).  (These bars were set, not measured: tests/eig_exact.py holds the same quantities to
+    24 eps l1 and 96 eps l1 / gap against an exact eigen-solve -- 200 and 50 000 times tighter -- on small seeded clusters;
+    the bars here stay as they are for the large clouds, whose reference is eigh and not the exact value.)"""
     l1, l2 = ref["l1"], ref["l2"]
     scale = np.maximum(np.abs(l1), 1e-300)
     ok = np.abs(got["l1"] - l1) <= 1e-12 * scale
