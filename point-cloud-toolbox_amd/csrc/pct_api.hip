@@ -65,8 +65,6 @@ int pct_reserve(pct_ctx* ctx, pct_buf* b, size_t bytes) {
     return PCT_OK;
 }
 
-static void release(pct_buf* b) { pct_release(b); }
-
 static float ev_ms(const hipEvent_t* ev, int a, int b) {
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, ev[a], ev[b]) != hipSuccess) ms = 0.f;
@@ -74,30 +72,25 @@ static float ev_ms(const hipEvent_t* ev, int a, int b) {
 }
 static float ev_ms(pct_ctx* ctx, int a, int b) { return ev_ms(ctx->ev, a, b); }
 
-// pinned words the kernels of a fused call write for the host: sweep statistics (8 x u64) and the SVD row count, one set
-// per parity of the call (pct_set_async: the next call's kernels must not overwrite what the pending one's left)
-static unsigned long long* stat_slot(pct_ctx* ctx, int par) { return (unsigned long long*)(ctx->pin + (par ? 256 : 192)); }
-static long long* svd_slot(pct_ctx* ctx, int par) { return (long long*)(ctx->pin + 2048 + 8 * par); }
+// the statistics a sweep left, as the timings report them
+static void read_sweep_stats(const pct_sweep_words& w, pct_timings* t) {
+    t->ring_fallbacks = (int64_t)w.ring_fallbacks;
+    t->lds_overflows = (int64_t)w.lds_overflows;
+    t->flushes = (int64_t)w.flushes;
+    t->candidate_steps = (int64_t)w.candidate_steps;
+    t->redone_queries = (int64_t)w.redone_queries;
+}
 
-// bookkeeping of the pending fused call, whose kernels have finished: timings from its event set, statistics, the
-// uneven-density verdict for the next sweep
+// bookkeeping of the pending fused call, whose kernels have finished: timings from its event set, statistics
 static void finish_pending(pct_ctx* ctx, const hipEvent_t* ev) {
     pct_timings t = ctx->tm_snap;
-    const unsigned long long* c = stat_slot(ctx, ctx->pend_par);
-    t.ring_fallbacks = (int64_t)c[0];
-    t.lds_overflows = (int64_t)c[1];
-    t.flushes = (int64_t)c[2];
-    t.candidate_steps = (int64_t)c[3];
-    t.redone_queries = (int64_t)c[4];
-    t.grid_ms = ev_ms(ev, 2, 3);
-    t.knn_ms = ev_ms(ev, 3, 4);
-    t.knn_fast_ms = ctx->pend_sorted ? ev_ms(ev, 3, 7) : 0.f;
-    t.fit_ms = ev_ms(ev, 4, 6);
-    t.total_ms = ev_ms(ev, 2, 6);
-    t.fit_svd_rows = *svd_slot(ctx, ctx->pend_par);
-    const int64_t redone = (int64_t)(unsigned)(c[7] & 0xFFFFFFFFull);
-    if (ctx->pend_sorted && !ctx->pend_levels) ctx->uneven = redone * 20 > ctx->pend_owned && ctx->pend_owned >= 65536;
-    else if (ctx->pend_levels && t.levels <= 1) ctx->uneven = false;
+    read_sweep_stats(ctx->pin->stats[ctx->pend_par], &t);
+    t.grid_ms = ev_ms(ev, PCT_EV_CALL_BEGIN, PCT_EV_GRID_END);
+    t.knn_ms = ev_ms(ev, PCT_EV_GRID_END, PCT_EV_SWEEP_END);
+    t.knn_fast_ms = ctx->pend_sorted ? ev_ms(ev, PCT_EV_GRID_END, PCT_EV_FAST_END) : 0.f;
+    t.fit_ms = ev_ms(ev, PCT_EV_SWEEP_END, PCT_EV_FIT_END);
+    t.total_ms = ev_ms(ev, PCT_EV_CALL_BEGIN, PCT_EV_FIT_END);
+    t.fit_svd_rows = ctx->pin->svd_rows[ctx->pend_par];
     ctx->tm_done = t;
     ctx->pending = false;
 }
@@ -211,7 +204,7 @@ int pct_create(int device, pct_ctx** out) {
             delete ctx;
             return PCT_ERR_HIP;
         }
-    for (int i = 2; i <= 7; ++i)               // the second set of timing events (pct_set_async)
+    for (int i = PCT_EV_CALL_BEGIN; i <= PCT_EV_FAST_END; ++i)     // the second set of timing events (pct_set_async)
         if (hipEventCreate(&ctx->ev_prev[i]) != hipSuccess) {
             delete ctx;
             return PCT_ERR_HIP;
@@ -237,7 +230,7 @@ void pct_destroy(pct_ctx* ctx) {
                       &ctx->tree_codes, &ctx->tree_vals, &ctx->tree_lvl, &ctx->tree_head, &ctx->tree_marks, &ctx->tree_seg, &ctx->tree_runs, &ctx->tree_range, &ctx->tree_bucket, &ctx->tree_tmp,
                       &ctx->pca, &ctx->pca_aux, &ctx->pca_nbr, &ctx->pca_orig,
                       &ctx->bin_rec, &ctx->bin_mat, &ctx->bin_plan, &ctx->bin_base};
-    for (pct_buf* b : all) release(b);
+    for (pct_buf* b : all) pct_release(b);
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     for (auto& e : ctx->ev)
         if (e) (void)hipEventDestroy(e);
@@ -278,12 +271,12 @@ int pct_set_points_f32(pct_ctx* ctx, const float* xyz, int64_t n) {
     if (!xyz) return pct_fail(ctx, PCT_ERR_INVALID, "null coordinates");
     PCT_TRY(new_cloud(ctx, n));
     PCT_TRY(pct_reserve(ctx, &ctx->xyz, (size_t)n * 3 * sizeof(float)));
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_IO_BEGIN], ctx->stream));
     PCT_HIP(ctx, hipMemcpyAsync(ctx->xyz.p, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     ctx->xyz_view = (const float*)ctx->xyz.p;
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_IO_END], ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->tm.upload_ms = ev_ms(ctx, 0, 1);
+    ctx->tm.upload_ms = ev_ms(ctx, PCT_EV_IO_BEGIN, PCT_EV_IO_END);
     return PCT_OK;
 }
 
@@ -292,13 +285,13 @@ int pct_set_points_f64(pct_ctx* ctx, const double* xyz, int64_t n) {
     if (!xyz) return pct_fail(ctx, PCT_ERR_INVALID, "null coordinates");
     PCT_TRY(new_cloud(ctx, n));
     PCT_TRY(pct_reserve(ctx, &ctx->stage_a, (size_t)n * 3 * sizeof(double)));
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_IO_BEGIN], ctx->stream));
     PCT_HIP(ctx, hipMemcpyAsync(ctx->stage_a.p, xyz, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     PCT_TRY(pct_pack_points_f64(ctx, (const double*)ctx->stage_a.p));
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_IO_END], ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->has_f64 = true;
-    ctx->tm.upload_ms = ev_ms(ctx, 0, 1);
+    ctx->tm.upload_ms = ev_ms(ctx, PCT_EV_IO_BEGIN, PCT_EV_IO_END);
     return PCT_OK;
 }
 
@@ -422,14 +415,14 @@ int pct_scatter_records(pct_ctx* ctx, const float* dev_records, int64_t n_record
     PCT_TRY(begin_call(ctx));
     if (n_records < 0 || begin < 0 || end < begin || (n_records > 0 && !dev_records) || (end > begin && (!dev_K || !dev_H)))
         return pct_fail(ctx, PCT_ERR_INVALID, "pct_scatter_records: bad arguments");
-    PCT_TRY(pct_reserve(ctx, &ctx->counters, 64 * sizeof(unsigned long long)));
-    unsigned long long* d_hits = (unsigned long long*)ctx->counters.p + 32;
+    PCT_TRY(pct_reserve(ctx, &ctx->counters, sizeof(pct_dev_words)));
+    unsigned long long* d_hits = &pct_dev(ctx)->scatter_hits;
     PCT_HIP(ctx, hipMemsetAsync(d_hits, 0, sizeof(unsigned long long), ctx->stream));
     if (n_records > 0)
         PCT_LAUNCH(k_scatter_records, dim3((unsigned)((n_records + 255) / 256)), dim3(256), 0, ctx->stream, dev_records, n_records, begin,
                    end, dev_K, dev_H, d_hits);
     PCT_HIP(ctx, hipGetLastError());
-    unsigned long long* h = (unsigned long long*)(ctx->pin + 176);
+    unsigned long long* h = &ctx->pin->scatter_hits;
     PCT_HIP(ctx, hipMemcpyAsync(h, d_hits, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if ((int64_t)*h != end - begin)
@@ -477,36 +470,34 @@ static int run_knn(pct_ctx* ctx, int32_t k, double eps, int32_t algo, bool fuse_
     ctx->knn_valid = ctx->fit_valid = false;
     ctx->k = k;
     ctx->eps = eps;
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_CALL_BEGIN], ctx->stream));
     ctx->tm.levels = 0;
     ctx->tm.sweep_variant = 0;         // (set by the fast sweep's launch, pct_knn.hip)
     ctx->tm.algo = algo;
     const auto run_levels = [&]() -> int {
         ctx->tm.algo = PCT_KNN_GRID_LEVELS;
-        PCT_HIP(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+        PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_GRID_END], ctx->stream));
         ctx->levels_fuse_fit = fuse_fit;
         const int lst = pct_knn_levels(ctx, k, eps);
         ctx->levels_fuse_fit = false;
         PCT_TRY(lst);
-        PCT_HIP(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
-        PCT_HIP(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
+        PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FAST_END], ctx->stream));
+        PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_SWEEP_END], ctx->stream));
         ctx->tm.knn_launches = ctx->tm.levels;
         ctx->knn_valid = true;
-        ctx->last_levels = true;
         return PCT_OK;
     };
     // the hierarchical cell list takes whole clouds; a shard asked of it goes down the chain of cell lists
     const bool tree_ok = ctx->q_begin == 0 && ctx->q_end == ctx->n && ctx->n < ((int64_t)1 << 26);
     const auto run_tree = [&]() -> int {
         ctx->tm.algo = PCT_KNN_TREE;
-        ctx->last_levels = false;
         bool usable = false;
         PCT_TRY(pct_build_tree(ctx, k, eps, &usable));
         if (!usable && ctx->tree_hint_mismatch) return PCT_OK;       // (a remembered verdict that does not fit this cloud: the caller goes on)
         if (!usable) return run_levels();          // (extents or eps outside what the float32 pre-selection can square)
-        PCT_HIP(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+        PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_GRID_END], ctx->stream));
         PCT_TRY(pct_launch_knn_tree(ctx, k, eps));
-        PCT_HIP(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
+        PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_SWEEP_END], ctx->stream));
         ctx->tm.knn_launches = 1;
         ctx->knn_valid = true;
         return PCT_OK;
@@ -527,7 +518,6 @@ static int run_knn(pct_ctx* ctx, int32_t k, double eps, int32_t algo, bool fuse_
         ctx->tm.algo = algo;
     }
     if (algo == PCT_KNN_GRID_LEVELS) return run_levels();
-    ctx->last_levels = false;
     const bool grid = algo == PCT_KNN_GRID || algo == PCT_KNN_GRID_EXACT;
     if (grid) {
         ctx->grid_skewed = false;
@@ -585,44 +575,42 @@ static int run_knn(pct_ctx* ctx, int32_t k, double eps, int32_t algo, bool fuse_
         ctx->tm.grid_points = ctx->n;
         ctx->tm.cell_size = 0;
     }
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_GRID_END], ctx->stream));
     if (grid)
         PCT_TRY(pct_launch_knn_grid(ctx, k, eps, algo == PCT_KNN_GRID_EXACT));
     else
         PCT_TRY(pct_launch_knn_brute(ctx, k, eps));
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_SWEEP_END], ctx->stream));
     ctx->tm.knn_launches = 1;
     ctx->knn_valid = true;
     return PCT_OK;
 }
 
 static int finish_knn_stats(pct_ctx* ctx, bool* beyond_limits) {
-    unsigned long long* c = stat_slot(ctx, 0);                           // pinned: a plain DMA, no staging
+    pct_sweep_words& w = ctx->pin->stats[0];                             // pinned: a plain DMA, no staging
     // (the fused call's fit kernel has already written them there: one launch less in the step's tail)
     if (!ctx->stats_mirrored)
-        PCT_HIP(ctx, hipMemcpyAsync(c, ctx->counters.p, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));   // [7] low word: rows on the redo list
+        PCT_HIP(ctx, hipMemcpyAsync(&w, ctx->counters.p, sizeof(w), hipMemcpyDeviceToHost, ctx->stream));
     ctx->stats_mirrored = false;
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->tm.ring_fallbacks = (int64_t)c[0];
-    ctx->tm.lds_overflows = (int64_t)c[1];
-    ctx->tm.flushes = (int64_t)c[2];
-    ctx->tm.candidate_steps = (int64_t)c[3];
+    read_sweep_stats(w, &ctx->tm);
     if (pct_getenv("PCT_TREE_DEBUG") && ctx->collect_stats)
-        fprintf(stderr, "[tree] redone %llu, up-levelled %llu, candidate steps %llu, costliest exact query: %llu steps (row %llu)\n", c[4], c[0], c[3],
-                c[6] >> 32, c[6] & 0xffffffffull);
-    ctx->tm.redone_queries = (int64_t)c[4];
-    ctx->tm.grid_ms = ev_ms(ctx, 2, 3);
-    ctx->tm.knn_ms = ev_ms(ctx, 3, 4);
-    ctx->tm.knn_fast_ms = ctx->knn_sorted_space ? ev_ms(ctx, 3, 7) : 0.f;
+        fprintf(stderr, "[tree] redone %llu, up-levelled %llu, candidate steps %llu, costliest exact query: %llu steps (row %llu)\n", w.redone_queries,
+                w.ring_fallbacks, w.candidate_steps, w.costliest >> 32, w.costliest & 0xffffffffull);
+    ctx->tm.grid_ms = ev_ms(ctx, PCT_EV_CALL_BEGIN, PCT_EV_GRID_END);
+    ctx->tm.knn_ms = ev_ms(ctx, PCT_EV_GRID_END, PCT_EV_SWEEP_END);
+    ctx->tm.knn_fast_ms = ctx->knn_sorted_space ? ev_ms(ctx, PCT_EV_GRID_END, PCT_EV_FAST_END) : 0.f;
     // a sharded handle that left far points out of its grid met a query those points could matter to
-    *beyond_limits = ctx->knn_sorted_space && ctx->culled && c[5] > 0;
-    // uneven density: remember it for the next sweep on this handle (and forget it when a chain needed one pass)
-    const int64_t owned = ctx->q_end - ctx->q_begin;
-    const int64_t redone = (int64_t)(unsigned)(c[7] & 0xFFFFFFFFull);
-    if (ctx->knn_sorted_space && !ctx->last_levels) ctx->uneven = redone * 20 > owned && owned >= 65536;
-    else if (ctx->last_levels && ctx->tm.levels <= 1) ctx->uneven = false;
+    *beyond_limits = ctx->knn_sorted_space && ctx->culled && w.beyond_limits > 0;
     ctx->tm.limit_retries = ctx->retries;
     return PCT_OK;
+}
+
+// rare: a culled grid met a query the points it left out could matter to -- the caller repeats with every point in it
+static void retry_without_cull(pct_ctx* ctx) {
+    ctx->no_cull = true;
+    ctx->retries = 1;
+    ctx->cull_box_valid = false;   // the cached box was too small for this cloud: measure it again next time
 }
 
 int pct_knn(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
@@ -630,15 +618,13 @@ int pct_knn(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
     bool again = false;
     PCT_TRY(run_knn(ctx, k, eps, algo));
     PCT_TRY(finish_knn_stats(ctx, &again));
-    if (again) {                      // rare: redo with every point in the grid
-        ctx->no_cull = true;
-        ctx->retries = 1;
-        ctx->cull_box_valid = false;   // the cached box was too small for this cloud: measure it again next time
+    if (again) {
+        retry_without_cull(ctx);
         PCT_TRY(run_knn(ctx, k, eps, algo));
         PCT_TRY(finish_knn_stats(ctx, &again));
     }
     ctx->tm.fit_ms = 0;
-    ctx->tm.total_ms = ev_ms(ctx, 2, 4);
+    ctx->tm.total_ms = ev_ms(ctx, PCT_EV_CALL_BEGIN, PCT_EV_SWEEP_END);
     return PCT_OK;
 }
 
@@ -646,12 +632,12 @@ int pct_fit(pct_ctx* ctx) {
     PCT_TRY(begin_call(ctx));
     PCT_TRY(refuse_in_slab_mode(ctx, "pct_fit"));
     if (!ctx->knn_valid) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "plant the neighbour table first (pct_knn)");
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_BEGIN], ctx->stream));
     PCT_TRY(pct_launch_fit_table(ctx));
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_END], ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->tm.fit_ms = ev_ms(ctx, 5, 6);
-    ctx->tm.fit_svd_rows = *(const long long*)(ctx->pin + 2048);
+    ctx->tm.fit_ms = ev_ms(ctx, PCT_EV_FIT_BEGIN, PCT_EV_FIT_END);
+    ctx->tm.fit_svd_rows = ctx->pin->svd_rows[0];
     ctx->fit_rows = ctx->q_end - ctx->q_begin;
     ctx->fit_valid = true;
     ctx->fit_cloud_aligned = true;
@@ -670,23 +656,23 @@ int pct_set_async(pct_ctx* ctx, int32_t enable) {
 static int curvature_async(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
     const bool had = ctx->pending;
     if (had)          // the pending call keeps its timing events; this one records into the other set
-        for (int i = 2; i <= 7; ++i) { hipEvent_t t = ctx->ev[i]; ctx->ev[i] = ctx->ev_prev[i]; ctx->ev_prev[i] = t; }
+        for (int i = PCT_EV_CALL_BEGIN; i <= PCT_EV_FAST_END; ++i) { hipEvent_t t = ctx->ev[i]; ctx->ev[i] = ctx->ev_prev[i]; ctx->ev_prev[i] = t; }
     const int par = had ? ctx->pend_par ^ 1 : 0;
     ctx->retries = 0;
     ctx->fit_par = par;            // (also for the fits a chained sweep launches itself)
     int st = run_knn(ctx, k, eps, algo, true);
     if (st == PCT_OK) {
         st = [&]() -> int {
-            // (no event of its own for the start of the fit: it starts where the sweep's last event, ev[4], was recorded --
+            // (no event of its own for the start of the fit: it starts where the sweep's last event, PCT_EV_SWEEP_END, was recorded --
             // every event record is a marker packet between two kernels, ~3 us of dispatch gap)
             ctx->stats_mirrored = false;
             ctx->stats_mirror_req = true;
             const int fs = pct_launch_fit_table(ctx);
             ctx->stats_mirror_req = false;
             PCT_TRY(fs);
-            PCT_HIP(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
+            PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_END], ctx->stream));
             if (!ctx->stats_mirrored)     // (no fit kernel ran: the chained sweep fitted its passes itself, or there are no rows)
-                PCT_HIP(ctx, hipMemcpyAsync(stat_slot(ctx, par), ctx->counters.p, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+                PCT_HIP(ctx, hipMemcpyAsync(&ctx->pin->stats[par], ctx->counters.p, sizeof(pct_sweep_words), hipMemcpyDeviceToHost, ctx->stream));
             ctx->stats_mirrored = false;
             return PCT_OK;
         }();
@@ -695,14 +681,14 @@ static int curvature_async(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
     if (st != PCT_OK) {            // leave the handle in the plain state: nothing pending, events where they were
         (void)hipStreamSynchronize(ctx->stream);
         if (had) {
-            for (int i = 2; i <= 7; ++i) { hipEvent_t t = ctx->ev[i]; ctx->ev[i] = ctx->ev_prev[i]; ctx->ev_prev[i] = t; }
+            for (int i = PCT_EV_CALL_BEGIN; i <= PCT_EV_FAST_END; ++i) { hipEvent_t t = ctx->ev[i]; ctx->ev[i] = ctx->ev_prev[i]; ctx->ev_prev[i] = t; }
             finish_pending(ctx, ctx->ev);
         }
         return st;
     }
     if (had) {
         // its kernels lie in front of this call's mid-build wait on the stream: normally long finished (checked, not assumed)
-        if (hipEventQuery(ctx->ev_prev[6]) != hipSuccess) (void)hipEventSynchronize(ctx->ev_prev[6]);
+        if (hipEventQuery(ctx->ev_prev[PCT_EV_FIT_END]) != hipSuccess) (void)hipEventSynchronize(ctx->ev_prev[PCT_EV_FIT_END]);
         (void)hipGetLastError();
         finish_pending(ctx, ctx->ev_prev);
     }
@@ -710,8 +696,6 @@ static int curvature_async(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
     ctx->tm_snap = ctx->tm;
     ctx->pend_par = par;
     ctx->pend_sorted = ctx->knn_sorted_space;
-    ctx->pend_levels = ctx->last_levels;
-    ctx->pend_owned = ctx->q_end - ctx->q_begin;
     ctx->pending = true;
     ctx->fit_rows = ctx->q_end - ctx->q_begin;
     ctx->fit_valid = true;
@@ -733,16 +717,14 @@ int pct_curvature(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
         ctx->stats_mirror_req = true;
         PCT_TRY(pct_launch_fit_table(ctx));
         ctx->stats_mirror_req = false;
-        PCT_HIP(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
+        PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_END], ctx->stream));
         PCT_TRY(finish_knn_stats(ctx, &again));
         if (!again) break;
-        ctx->no_cull = true;          // rare: redo with every point in the grid
-        ctx->retries = 1;
-        ctx->cull_box_valid = false;   // the cached box was too small for this cloud: measure it again next time
+        retry_without_cull(ctx);
     }
-    ctx->tm.fit_ms = ev_ms(ctx, 4, 6);            // (the fit starts where the sweep's last event was recorded)
-    ctx->tm.fit_svd_rows = *svd_slot(ctx, 0);
-    ctx->tm.total_ms = ev_ms(ctx, 2, 6);
+    ctx->tm.fit_ms = ev_ms(ctx, PCT_EV_SWEEP_END, PCT_EV_FIT_END);            // (the fit starts where the sweep's last event was recorded)
+    ctx->tm.fit_svd_rows = ctx->pin->svd_rows[0];
+    ctx->tm.total_ms = ev_ms(ctx, PCT_EV_CALL_BEGIN, PCT_EV_FIT_END);
     ctx->tm_done = ctx->tm;
     ctx->fit_rows = ctx->q_end - ctx->q_begin;
     ctx->fit_valid = true;
@@ -763,15 +745,15 @@ int pct_get_neighbors(pct_ctx* ctx, int64_t begin, int64_t end, int32_t* idx, fl
     if (idx) PCT_TRY(pct_reserve(ctx, &ctx->stage_a, cells * sizeof(int)));
     if (dist) PCT_TRY(pct_reserve(ctx, &ctx->stage_b, cells * sizeof(float)));
     if (count) PCT_TRY(pct_reserve(ctx, &ctx->stage_c, (size_t)rows * sizeof(int)));
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_IO_BEGIN], ctx->stream));
     PCT_TRY(pct_launch_export_neighbors(ctx, begin, end, idx ? (int*)ctx->stage_a.p : nullptr,
                                         dist ? (float*)ctx->stage_b.p : nullptr, count ? (int*)ctx->stage_c.p : nullptr));
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_IO_END], ctx->stream));
     if (idx) PCT_HIP(ctx, hipMemcpyAsync(idx, ctx->stage_a.p, cells * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     if (dist) PCT_HIP(ctx, hipMemcpyAsync(dist, ctx->stage_b.p, cells * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     if (count) PCT_HIP(ctx, hipMemcpyAsync(count, ctx->stage_c.p, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->tm.export_ms = ev_ms(ctx, 0, 1);
+    ctx->tm.export_ms = ev_ms(ctx, PCT_EV_IO_BEGIN, PCT_EV_IO_END);
     return PCT_OK;
 }
 
@@ -846,14 +828,14 @@ int pct_fit_indices(pct_ctx* ctx, const int32_t* idx, const int32_t* count, cons
     PCT_TRY(pct_reserve(ctx, &ctx->K, (size_t)rows * sizeof(float)));
     PCT_TRY(pct_reserve(ctx, &ctx->H, (size_t)rows * sizeof(float)));
     PCT_TRY(pct_reserve(ctx, &ctx->H2, (size_t)rows * sizeof(float)));
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_BEGIN], ctx->stream));
     PCT_TRY(pct_launch_fit_rows(ctx, (const int*)ctx->stage_a.p, count ? (const int*)ctx->stage_c.p : nullptr,
                                 query ? (const int64_t*)ctx->stage_d.p : nullptr, rows, k, pitch, (float*)ctx->coefs.p,
                                 (float*)ctx->K.p, (float*)ctx->H.p, (float*)ctx->H2.p, false));
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_END], ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->tm.fit_ms = ev_ms(ctx, 5, 6);
-    ctx->tm.fit_svd_rows = *(const long long*)(ctx->pin + 2048);
+    ctx->tm.fit_ms = ev_ms(ctx, PCT_EV_FIT_BEGIN, PCT_EV_FIT_END);
+    ctx->tm.fit_svd_rows = ctx->pin->svd_rows[0];
     ctx->fit_rows = rows;
     ctx->fit_row_order = false;
     ctx->fit_valid = true;
@@ -1098,9 +1080,7 @@ int pct_surface_variation(pct_ctx* ctx, int32_t k_total, float* out) {
         PCT_HIP(ctx, hipMemcpyAsync(out, ctx->K.p, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
         PCT_TRY(finish_knn_stats(ctx, &again));
         if (!again) break;
-        ctx->no_cull = true;
-        ctx->retries = 1;
-        ctx->cull_box_valid = false;   // the cached box was too small for this cloud: measure it again next time
+        retry_without_cull(ctx);
     }
     ctx->fit_valid = false;
     return PCT_OK;
@@ -1133,16 +1113,16 @@ int pct_pca_curvatures(pct_ctx* ctx, int32_t k, int32_t algo, int32_t keep_neigh
     const int rs = pct_pca_restore(ctx);
     PCT_TRY(st);
     PCT_TRY(rs);
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_BEGIN], ctx->stream));
     int64_t exact = 0;
     st = pct_launch_pca(ctx, (int32_t)kk, 2.0 * R * (1.0 + 1e-9), origin, keep_neighbors != 0, &exact);
     if (ctx->has_f64) ctx->grid_valid = false;        // (the cell list holds the recentred float32 cloud)
     ctx->knn_valid = ctx->fit_valid = false;           // (the table in place holds the over-fetched candidates)
     PCT_TRY(st);
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_END], ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->tm.fit_ms = ev_ms(ctx, 5, 6);
-    ctx->tm.total_ms = ev_ms(ctx, 2, 6);
+    ctx->tm.fit_ms = ev_ms(ctx, PCT_EV_FIT_BEGIN, PCT_EV_FIT_END);
+    ctx->tm.total_ms = ev_ms(ctx, PCT_EV_CALL_BEGIN, PCT_EV_FIT_END);
     ctx->pca_valid = true;
     ctx->pca_has_nbr = keep_neighbors != 0;
     ctx->pca_k = (int32_t)kk;
@@ -1162,16 +1142,16 @@ int pct_get_pca(pct_ctx* ctx, int64_t begin, int64_t end, double* l1, double* l2
     const int64_t n = ctx->pca_rows, rows = end - begin;
     if (rows == 0) return PCT_OK;
     const double* o = (const double*)ctx->pca.p;
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_IO_BEGIN], ctx->stream));
     double* outs[4] = {l1, l2, K, H};
     for (int i = 0; i < 4; ++i)
         if (outs[i]) PCT_HIP(ctx, hipMemcpyAsync(outs[i], o + (int64_t)i * n + begin, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (dirs) PCT_HIP(ctx, hipMemcpyAsync(dirs, o + 4 * n + 6 * begin, (size_t)rows * 6 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (idx) PCT_HIP(ctx, hipMemcpyAsync(idx, (const int32_t*)ctx->pca_nbr.p + begin * ctx->pca_k, (size_t)rows * ctx->pca_k * sizeof(int32_t),
                                          hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_IO_END], ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->tm.export_ms = ev_ms(ctx, 0, 1);
+    ctx->tm.export_ms = ev_ms(ctx, PCT_EV_IO_BEGIN, PCT_EV_IO_END);
     return PCT_OK;
 }
 

@@ -54,8 +54,8 @@ struct FitArgs {
     int* flag_list;          // rows k_fit hands to k_fit_svd (ill-conditioned or under-determined design matrices)
     int* flag_count;
     int* flag_next;          // the count the NEXT launch will use: zeroed by this launch's first block (saves a memset launch)
-    const unsigned long long* stat_src;   // fused call: the sweep's eight statistics words ...
-    unsigned long long* stat_dst;         // ... copied to pinned host memory by the first block (saves a D2H copy)
+    const pct_sweep_words* stat_src;      // fused call: the sweep's statistics, eight 64-bit words ...
+    pct_sweep_words* stat_dst;            // ... copied to pinned host memory by the first block (saves a D2H copy)
     unsigned n_pts;          // records in pts: a table entry outside [0, n_pts) is never dereferenced (the row reads NaN)
     const int* row_mask;     // MASKED instantiation: only the rows with a non-zero entry are fitted (passes of the density-adaptive sweep)
     int svd_accumulate;      // the count of rows handed to k_fit_svd is ADDED to the host word (the passes of one fused call)
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(kFitBlock) void k_fit(FitArgs a) {
     const int lane = threadIdx.x;
     if (blockIdx.x == 0) {
         if (lane == 0 && a.flag_next) *a.flag_next = 0;
-        if (a.stat_dst && lane < 8) a.stat_dst[lane] = a.stat_src[lane];
+        if (a.stat_dst && lane < 8) ((unsigned long long*)a.stat_dst)[lane] = ((const unsigned long long*)a.stat_src)[lane];
     }
     const int64_t row0 = (a.blocks_per_xcd ? (int64_t)(blockIdx.x & 7u) * a.blocks_per_xcd + (blockIdx.x >> 3) : (int64_t)blockIdx.x) * kFitBlock;
     if (row0 >= a.rows) return;
@@ -744,8 +744,8 @@ int launch(pct_ctx* ctx, const FitArgs& a0, bool f64) {
     a.stat_src = nullptr;
     a.stat_dst = nullptr;
     if (ctx->stats_mirror_req && ctx->counters.p) {
-        a.stat_src = (const unsigned long long*)ctx->counters.p;
-        a.stat_dst = (unsigned long long*)(ctx->pin + (ctx->fit_par ? 256 : 192));
+        a.stat_src = &pct_dev(ctx)->sweep;
+        a.stat_dst = &ctx->pin->stats[ctx->fit_par];
         ctx->stats_mirrored = true;
     }
     ctx->stats_mirror_req = false;
@@ -768,7 +768,7 @@ int launch(pct_ctx* ctx, const FitArgs& a0, bool f64) {
     PCT_HIP(ctx, hipGetLastError());
     // the rows handed over: fixed grid, the list length is read on the device
     const int sblocks = blocks < 1024 ? blocks : 1024;
-    long long* note = (long long*)(ctx->pin + 2048 + 8 * ctx->fit_par);
+    long long* note = &ctx->pin->svd_rows[ctx->fit_par];
     if (a.coefs64) {
         if (f64)
             PCT_LAUNCH((k_fit_svd<true, true>), dim3(sblocks), dim3(64), 0, ctx->stream, a, a.flag_list, a.flag_count, note);

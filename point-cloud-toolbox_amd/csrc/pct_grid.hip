@@ -1120,6 +1120,10 @@ int grid_1d(int64_t n, int per_block, int cap) {
 
 // ---------------------------------------------------------------------------
 static PackRed* red_parts(pct_ctx* ctx) { return (PackRed*)((char*)ctx->red.p + 128); }
+static_assert(sizeof(PackRed) <= sizeof(pct_pinned::pack_red) && alignof(PackRed) <= 128, "pct_pinned::pack_red holds a PackRed");
+static_assert(sizeof(ScanTotals) <= sizeof(pct_pinned::scan_totals) && alignof(ScanTotals) <= 128, "pct_pinned::scan_totals holds a ScanTotals");
+static PackRed* pin_red(pct_ctx* ctx) { return (PackRed*)ctx->pin->pack_red; }
+static ScanTotals* pin_totals(pct_ctx* ctx) { return (ScanTotals*)ctx->pin->scan_totals; }
 
 static int red_reset(pct_ctx* ctx, int n_parts, bool zero = true) {
     PCT_TRY(pct_reserve(ctx, &ctx->red, 128 + (size_t)n_parts * sizeof(PackRed)));
@@ -1130,7 +1134,7 @@ static int red_reset(pct_ctx* ctx, int n_parts, bool zero = true) {
 // folds the n_parts block records of the pass just launched (the result also lands in pinned host memory)
 static int red_fold(pct_ctx* ctx, int n_parts, bool carry = true) {
     PCT_LAUNCH(k_pack_final, dim3(1), dim3(kBlock), 0, ctx->stream, (const PackRed*)red_parts(ctx), n_parts,
-                       (PackRed*)ctx->red.p, (PackRed*)ctx->pin, carry ? 1 : 0);
+                       (PackRed*)ctx->red.p, pin_red(ctx), carry ? 1 : 0);
     PCT_HIP(ctx, hipGetLastError());
     return PCT_OK;
 }
@@ -1139,7 +1143,7 @@ static int red_fold(pct_ctx* ctx, int n_parts, bool carry = true) {
 static int red_read(pct_ctx* ctx, int n_parts, PackRed* out, float* bbox, bool carry = true) {
     PCT_TRY(red_fold(ctx, n_parts, carry));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(out, ctx->pin, sizeof(*out));
+    memcpy(out, pin_red(ctx), sizeof(*out));
     for (int a = 0; a < 6; ++a) bbox[a] = order_float(out->bb[a]);
     return PCT_OK;
 }
@@ -1204,8 +1208,8 @@ static int slab_split(pct_ctx* ctx) {
     const int nh = grid_1d(n, kSlabHistBlock * 4, 512);
     if (vec) PCT_LAUNCH(k_slab_hist<true>, dim3(nh), dim3(kSlabHistBlock), 0, ctx->stream, ctx->xyz_view, n, axis, ctx->slab_x0, ctx->slab_inv, hist);
     else PCT_LAUNCH(k_slab_hist<false>, dim3(nh), dim3(kSlabHistBlock), 0, ctx->stream, ctx->xyz_view, n, axis, ctx->slab_x0, ctx->slab_inv, hist);
-    int* h_cut = (int*)(ctx->pin + 2560);                       // mapped pinned memory: the kernel writes the host's copy
-    long long* h_counts = (long long*)(ctx->pin + 3072);
+    int* h_cut = ctx->pin->slab_cut;                            // mapped pinned memory: the kernel writes the host's copy
+    long long* h_counts = ctx->pin->slab_counts;
     PCT_LAUNCH(k_slab_cut, dim3(1), dim3(kBlock), 0, ctx->stream, (const unsigned*)hist, (long long)n, parts, h_cut, h_counts);
     PCT_HIP(ctx, hipGetLastError());
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1293,14 +1297,14 @@ static int pack_near_owned(pct_ctx* ctx, double target, float* bbox, PackRed* re
     else { if (vec) PCT_CULL(false, true); else PCT_CULL(false, false); }
 #undef PCT_CULL
     PCT_HIP(ctx, hipGetLastError());
-    PCT_HIP(ctx, hipMemcpyAsync(ctx->pin + 160, ctx->scan_tmp.p, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(ctx->pin + 164, (const unsigned*)ctx->scan_tmp.p + 32, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(&ctx->pin->cull_kept, ctx->scan_tmp.p, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(&ctx->pin->cull_owned, (const unsigned*)ctx->scan_tmp.p + 32, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
     PCT_TRY(red_read(ctx, nchunk, red, bbox));
     if (red->bad) return pct_fail(ctx, PCT_ERR_NONFINITE, "Non-finite values in input points");
-    if (slab && (int64_t)((const unsigned*)(ctx->pin + 160))[1] != n_owned)
+    if (slab && (int64_t)ctx->pin->cull_owned != n_owned)
         return pct_fail(ctx, PCT_ERR_INVALID, "slab pack found %u owned points, the cut said %lld (was the cloud's buffer written meanwhile?)",
-                        ((const unsigned*)(ctx->pin + 160))[1], (long long)n_owned);
-    const int64_t kept = n_owned + (int64_t)*(const unsigned*)(ctx->pin + 160);
+                        ctx->pin->cull_owned, (long long)n_owned);
+    const int64_t kept = n_owned + (int64_t)ctx->pin->cull_kept;
     if ((int64_t)red->cnt != kept || kept > n)
         return pct_fail(ctx, PCT_ERR_INVALID, "cull pass kept %lld / counted %lld points", (long long)red->cnt, (long long)kept);
     ctx->pts4_valid = false;                 // pts4 is not the full public-order pack
@@ -1586,7 +1590,7 @@ int pct_build_grid(pct_ctx* ctx, int32_t k, double eps) {
             PCT_LAUNCH(k_bin_cells, dim3(bs.max_items + 1), dim3(kBinBlock), bin_lds, ctx->stream, (const float4*)ctx->bin_rec.p, (const int*)bin_plan,
                        (const int4*)bin_items, g, bs.shift, (int)ctx->q_begin, (int)ctx->q_end, (int*)ctx->cell_own.p,
                        sharded ? (int*)ctx->cell_oth.p : nullptr, (int*)ctx->bin_base.p, (const PackRed*)parts, bs.ntiles,
-                       (PackRed*)ctx->red.p, (PackRed*)ctx->pin);
+                       (PackRed*)ctx->red.p, pin_red(ctx));
         } else
         if (raw) {
             const int nhb = grid_1d(n, kBlock, 0);
@@ -1614,15 +1618,15 @@ int pct_build_grid(pct_ctx* ctx, int32_t k, double eps) {
         PCT_LAUNCH(k_scan_sums, dim3(nblk), dim3(kBlock), 0, ctx->stream,
                            (const int*)ctx->cell_own.p, sharded ? (const int*)ctx->cell_oth.p : nullptr, g.ncell, items_q,
                            (int4*)ctx->scan_tmp.p, sq_part);
-        PCT_TRY(pct_reserve(ctx, &ctx->counters, 64 * sizeof(unsigned long long)));
+        PCT_TRY(pct_reserve(ctx, &ctx->counters, sizeof(pct_dev_words)));
         PCT_LAUNCH(k_scan_tiles, dim3(1), dim3(1024), 0, ctx->stream, (int4*)ctx->scan_tmp.p, nblk,
-                           (const unsigned long long*)sq_part, (ScanTotals*)(ctx->pin + 128), (unsigned long long*)ctx->counters.p);
+                           (const unsigned long long*)sq_part, pin_totals(ctx), (unsigned long long*)&pct_dev(ctx)->sweep);
         ctx->counters_clean = true;
         // the totals this pass is judged by (and, with a deferred pack, the cloud's box) are in pinned memory from here on:
         // the host waits for THIS point, not for the end of the stream -- while it wakes up, decides and enqueues the
         // sweep, the device applies the scan and scatters the records (50 us at 1 M points; the read-back used to be ~25
         // us of an idle device).  A pass that is rejected has scattered for nothing, as before.
-        PCT_HIP(ctx, hipEventRecord(ctx->ev[8], ctx->stream));
+        PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_SCAN_TOTALS], ctx->stream));
         PCT_LAUNCH(k_scan_apply, dim3(nblk), dim3(kBlock), 0, ctx->stream,
                            (const int*)ctx->cell_own.p, sharded ? (const int*)ctx->cell_oth.p : nullptr, g.ncell, items_q,
                            (const int4*)ctx->scan_tmp.p, (int*)ctx->cell_cnt.p, (int*)ctx->own_start.p, (int2*)ctx->occ.p);
@@ -1651,10 +1655,10 @@ int pct_build_grid(pct_ctx* ctx, int32_t k, double eps) {
                            ctx->has_f64 ? (const double4*)ctx->pts4d.p : nullptr,
                            ctx->has_f64 ? (double4*)ctx->sorted4d.p : nullptr);
         PCT_HIP(ctx, hipGetLastError());
-        PCT_HIP(ctx, hipEventSynchronize(ctx->ev[8]));
+        PCT_HIP(ctx, hipEventSynchronize(ctx->ev[PCT_EV_SCAN_TOTALS]));
         if (spec) {                      // the deferred pack result is in: was the old box still right?
             spec = false;
-            memcpy(&red, ctx->pin, sizeof(red));
+            memcpy(&red, pin_red(ctx), sizeof(red));
             if (red.bad) return pct_fail(ctx, PCT_ERR_NONFINITE, "Non-finite values in input points");
             bool same = true;
             for (int ax = 0; ax < 3; ++ax) {
@@ -1674,8 +1678,8 @@ int pct_build_grid(pct_ctx* ctx, int32_t k, double eps) {
             fprintf(stderr, "[grid] bin build: %d buckets of %d cells, %d tiles of %d rows, %d work items of up to %d records, %d of them in %d shared buckets\n",
                     bs.nb, 1 << bs.shift, bs.ntiles, bs.tile_rows, pw[0], bs.chunk, pw[1], pw[2]);
         }
-        const unsigned long long s2 = ((const ScanTotals*)(ctx->pin + 128))->sumsq;
-        tot = ((const ScanTotals*)(ctx->pin + 128))->tot;
+        const unsigned long long s2 = pin_totals(ctx)->sumsq;
+        tot = pin_totals(ctx)->tot;
         ++iters;
         double m = (double)s2 / (double)(n_owned > 0 ? n_owned : 1);
         m_last = m;

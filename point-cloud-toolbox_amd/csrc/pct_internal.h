@@ -75,23 +75,72 @@ struct pct_buf {
     size_t cap = 0;
 };
 
+// The two word blocks a step's kernels and its host side talk through are laid out here and nowhere else.
+// Statistics of one sweep: 64 bytes, cleared (k_scan_tiles, reserve_table) and mirrored to the host as eight 64-bit words.
+struct pct_sweep_words {
+    unsigned long long ring_fallbacks, lds_overflows, flushes, candidate_steps, redone_queries;   // under pct_set_stats only
+    unsigned long long beyond_limits;      // queries the points left out of a culled grid could matter to (always counted)
+    unsigned long long costliest;          // the costliest exact query: 64-candidate steps << 32 | row
+    int redo_count, reserved;              // rows on the redo list (always counted)
+};
+static_assert(sizeof(pct_sweep_words) == 64, "eight 64-bit words");
+struct pct_dev_words {                     // ctx->counters: 512 bytes of device memory
+    union {
+        pct_sweep_words sweep;
+        unsigned long long census[4];      // pct_item_census, between a cell-list build and its sweep
+    };
+    unsigned long long unused[24];
+    unsigned long long scatter_hits;       // pct_scatter_records: records that fell into the asked rows
+    unsigned long long tail[31];
+};
+static_assert(sizeof(pct_dev_words) == 512, "what every user reserves");
+// ctx->pin: 4 KiB of pinned, device-visible host memory.  Kernels and small copies drop their few result words here, so
+// that a read-back is one stream synchronisation.  One field per read-back; no two share bytes.  A record type that
+// belongs to one file is aligned bytes here, whose size that file asserts.  The fields a kernel stores to directly
+// (scan_totals, stats, svd_rows, tree_totals, slab_cut, slab_counts) are aligned as they always were.
+struct pct_pinned {
+    alignas(128) unsigned char pack_red[128];        // PackRed, the pack reduction (pct_grid.hip)
+    alignas(128) unsigned char scan_totals[32];      // ScanTotals (pct_grid.hip)
+    unsigned cull_kept, cull_owned;                  // the cull pass: points kept beside the owned ones, owned points
+    unsigned long long scatter_hits;
+    // by parity of the fused call (pct_set_async: the next call's kernels must not overwrite what the pending one's left)
+    alignas(64) pct_sweep_words stats[2];            // the sweep's statistics, mirrored by the fit kernel or copied
+    alignas(64) unsigned char band_stats[704];       // BandStats of the chained sweep (pct_levels.hip)
+    alignas(32) int band_box[8];                     // ... and the box of its next band: min xyz, max xyz (ordered ints), count
+    alignas(2048) long long svd_rows[2];             // by parity: rows the call's fits handed to k_fit_svd
+    alignas(64) unsigned long long census[4];
+    alignas(128) long long tree_totals[2];           // the tree build: {items, segments}
+    alignas(32) int tree_counts[26];                 // ... its counts and level histogram
+    alignas(512) int slab_cut[PCT_SLAB_PARTS_MAX + 1];
+    alignas(512) long long slab_counts[PCT_SLAB_PARTS_MAX];
+};
+static_assert(sizeof(pct_pinned) <= 4096, "pct_create allocates 4096 bytes");
+
+enum pct_event {                           // ctx->ev
+    PCT_EV_IO_BEGIN, PCT_EV_IO_END,        // an upload or an export
+    PCT_EV_CALL_BEGIN, PCT_EV_GRID_END, PCT_EV_SWEEP_END,     // a sweep or a fused call: cell list | sweep | (fused) fit
+    PCT_EV_FIT_BEGIN, PCT_EV_FIT_END,      // a fit (a fused call records its end only)
+    PCT_EV_FAST_END,                       // end of the fast sweep, the dominant kernel
+    PCT_EV_SCAN_TOTALS,                    // the cell list's scan totals are in pinned memory (pct_build_grid)
+    PCT_EV_COUNT
+};
+
 struct pct_comm;            // RCCL communicator + exchange stream (pct_comm.hip); null on a single-GPU handle
 
 struct pct_ctx {
     int device = 0;
     pct_comm* comm = nullptr;
     hipStream_t stream = nullptr;
-    hipEvent_t ev[9] = {};         // [0..7] stage timings; [8]: the cell list's scan totals are in pinned memory (pct_build_grid)
+    hipEvent_t ev[PCT_EV_COUNT] = {};
     // Streams of clouds (pct_set_async): a fused call returns once its kernels are enqueued; its timing events, its
     // statistics words and its SVD row count wait in the set of the call's parity until the NEXT fused call has passed
     // its mid-build wait (everything of the previous call has completed by then) or until anything else is asked of the
     // handle (which first waits for the stream).  The host prepares step i + 1 while the device fits step i.
-    hipEvent_t ev_prev[9] = {};    // the timing events of the pending call while a new one records into ev
+    hipEvent_t ev_prev[PCT_EV_COUNT] = {};    // the timing events of the pending call while a new one records into ev
     bool async_mode = false;
     bool pending = false;          // a fused call has been enqueued and its bookkeeping has not been done
     int pend_par = 0;              // parity of the pending call: which pinned slots its kernels write
-    bool pend_sorted = false, pend_levels = false;
-    int64_t pend_owned = 0;
+    bool pend_sorted = false;      // its table is in a sorted space: knn_fast_ms applies
     int fit_par = 0;               // which pinned slots (statistics mirror, SVD row count) the fits being launched write
     pct_timings tm_snap = {};      // the host-side fields of the pending call's timings
     pct_timings tm_done = {};      // timings of the last call whose bookkeeping has been done
@@ -154,7 +203,6 @@ struct pct_ctx {
     pct_buf flag_buf;               // float (n): wanted log2 cell edge of every point still unanswered (NaN = answered)
     pct_buf dens_buf;               // float2 (n): log2 of the largest edge known too small / the smallest known too large
     pct_buf pub_pos, pub_dist, pub_cnt;   // public-space neighbour table the passes are merged into
-    bool uneven = false;
     bool auto_probe = false;        // PCT_KNN_AUTO on a cloud the hierarchical list could take: pct_build_grid gives up (grid_skewed)
     bool auto_probe_tree = false;   // ... and the census that follows may send the call there
     bool grid_skewed = false;       // rather than build a uniform list of more than 16 cells per point
@@ -163,7 +211,6 @@ struct pct_ctx {
     bool tree_check_bbox = false, tree_hint_mismatch = false;
     int64_t auto_tree_n = 0;        // PCT_KNN_AUTO sent a cloud of this size to the hierarchical list: the next one of the same
     int32_t auto_tree_calls = 0;    // size goes there directly (no uniform build first); re-examined every 16th call
-    bool last_levels = false;       // the table in place came from pct_knn_levels            // a plain grid sweep of this cloud left > 5 % of the queries to the exact kernel
     bool has_f64 = false;
     double occupancy_factor = 0.0; // 0 = default
     bool collect_stats = false;    // sweep statistics (costly same-address atomics)
@@ -201,10 +248,7 @@ struct pct_ctx {
     int32_t row_of_begin = 0;
     pct_buf owned_pos;  // int32 (owned) sorted position of every table row
     pct_buf red;        // small reduction scratch
-    // 4 KiB of pinned, device-visible host memory: kernels drop their few result words here so that a
-    // read-back is one stream synchronisation, not a copy command.  [0,128) PackRed  [128,192) scan totals
-    // [192,256) sweep counters  [256,1024) and [1024,1056) band statistics / band box of the density-adaptive sweep  [2048,2056) rows of the last fit that went to k_fit_svd  [2112,2144) work-item census of PCT_KNN_AUTO  [2176,2312) totals of the tree build
-    unsigned char* pin = nullptr;
+    pct_pinned* pin = nullptr;
     int64_t n_occ = 0;
     bool grid_valid = false;
     bool pts4_valid = false;
@@ -226,7 +270,7 @@ struct pct_ctx {
     bool knn_sorted_space = false; // false: rows/ids are public indices (brute force)
     bool skip_dist_req = false;    // the caller will not read distances from the table (the fused curvature call)
     bool dist_valid = true;        // nbr_dist holds the distances of the table in place (else: derived on demand)
-    pct_buf counters;   // int64[4] device counters (fallbacks, overflows)
+    pct_buf counters;   // pct_dev_words: the sweep's statistics words, the census, the scatter hit count
 
     // results, public order
     pct_buf coefs;      // float (n,6)
@@ -288,6 +332,7 @@ inline double pct_default_factor(int k) {
     return n <= 85 ? 0.52 : n <= 101 ? 0.52 - 0.07 * (n - 85) / 16.0 : 0.45 - 0.05 * (n - 101) / 27.0;
 }
 int pct_reserve(pct_ctx* ctx, pct_buf* b, size_t bytes);
+inline pct_dev_words* pct_dev(pct_ctx* ctx) { return (pct_dev_words*)ctx->counters.p; }     // after pct_reserve(&ctx->counters, sizeof(pct_dev_words))
 void pct_release(pct_buf* b);
 
 // Morton codes of the hierarchical cell list: 21 bits per axis, x in bit 0 of every triple

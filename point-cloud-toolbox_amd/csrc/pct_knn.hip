@@ -400,8 +400,8 @@ __global__ __launch_bounds__(64 * kFastWaves<R>, (TREE ? (R == 1 ? (PCT_TREE_CAP
             redo[base + lane] = row0 + lane;
         }
         if (a.stats && lane == 0) {
-            if (!hopeless) atomicAdd(&a.counters[1], 1ull);
-            atomicAdd(&a.counters[4], (unsigned long long)nq);
+            if (!hopeless) atomicAdd(&a.counters->lds_overflows, 1ull);
+            atomicAdd(&a.counters->redone_queries, (unsigned long long)nq);
         }
         return;
     }
@@ -1160,9 +1160,9 @@ __global__ __launch_bounds__(64 * kFastWaves<R>, (TREE ? (R == 1 ? (PCT_TREE_CAP
     }
     // statistics are opt-in: ~10^5 waves adding to the same words serialise at the memory side
     if (a.stats && lane == 0) {
-        atomicAdd(&a.counters[2], n_flush);
-        atomicAdd(&a.counters[3], n_step);
-        if (n_redo) atomicAdd(&a.counters[4], n_redo);
+        atomicAdd(&a.counters->flushes, n_flush);
+        atomicAdd(&a.counters->candidate_steps, n_step);
+        if (n_redo) atomicAdd(&a.counters->redone_queries, n_redo);
     }
 }
 
@@ -1215,7 +1215,7 @@ struct PairArgs {
     int* nbr_cnt;             // EPS only
     int* redo;
     int* redo_count;
-    unsigned long long* counters;
+    pct_sweep_words* counters;
     int n_items, items_q;
     int items_per_xcd;        // blocks are dealt to the 8 XCDs in turn: block b takes item (b % 8) * items_per_xcd + b / 8, so that
                               // the items one XCD's L2 serves at a time are neighbours in cell order (they share most of their stencils)
@@ -1362,8 +1362,8 @@ __global__ __launch_bounds__(64 * kPairWaves, (TREE ? 4 : Q64 ? 5 : 6)) void k_k
         base = __builtin_amdgcn_readfirstlane(base);
         if (lane < nq) a.redo[base + lane] = row0 + lane;
         if (a.stats && lane == 0) {
-            atomicAdd(&a.counters[1], 1ull);
-            atomicAdd(&a.counters[4], (unsigned long long)nq);
+            atomicAdd(&a.counters->lds_overflows, 1ull);
+            atomicAdd(&a.counters->redone_queries, (unsigned long long)nq);
         }
         return;
     }
@@ -1761,7 +1761,7 @@ __global__ __launch_bounds__(64 * kPairWaves, (TREE ? 4 : Q64 ? 5 : 6)) void k_k
         if (lane == 0) base = atomicAdd(a.redo_count, cnt);
         base = __builtin_amdgcn_readfirstlane(base);
         if ((redo_mask >> lane) & 1ull) a.redo[base + (int)__popcll(redo_mask & ((1ull << lane) - 1ull))] = row0 + lane;
-        if (a.stats && lane == 0) atomicAdd(&a.counters[4], (unsigned long long)cnt);
+        if (a.stats && lane == 0) atomicAdd(&a.counters->redone_queries, (unsigned long long)cnt);
     }
 }
 
@@ -1900,8 +1900,8 @@ __global__ __launch_bounds__(64, ((TREE ? PCT_TREE_CAP2 : PCT_DUO_CAP) <= 768 ? 
         base = __builtin_amdgcn_readfirstlane(base);
         if (lane < nq) a.redo[base + lane] = row0 + lane;
         if (a.stats && lane == 0) {
-            atomicAdd(&a.counters[1], 1ull);
-            atomicAdd(&a.counters[4], (unsigned long long)nq);
+            atomicAdd(&a.counters->lds_overflows, 1ull);
+            atomicAdd(&a.counters->redone_queries, (unsigned long long)nq);
         }
         return;
     }
@@ -2181,7 +2181,7 @@ __global__ __launch_bounds__(64, ((TREE ? PCT_TREE_CAP2 : PCT_DUO_CAP) <= 768 ? 
         if (lane == 0) base = atomicAdd(a.redo_count, cnt);
         base = __builtin_amdgcn_readfirstlane(base);
         if ((redo_mask >> lane) & 1ull) a.redo[base + (int)__popcll(redo_mask & ((1ull << lane) - 1ull))] = row0 + lane;
-        if (a.stats && lane == 0) atomicAdd(&a.counters[4], (unsigned long long)cnt);
+        if (a.stats && lane == 0) atomicAdd(&a.counters->redone_queries, (unsigned long long)cnt);
     }
 }
 
@@ -2301,7 +2301,7 @@ __global__ __launch_bounds__(64) void k_selftest(int* fails) {
 // One thread per work item: population and non-empty cells of its 27-cell stencil (pct_item_census).
 __global__ __launch_bounds__(256) void k_item_census(const int2* __restrict__ items, int64_t n_items, int items_q,
                                                      const int* __restrict__ cs, const int* __restrict__ cell_own, pct_grid g, int k,
-                                                     int cap, unsigned long long* __restrict__ out) {
+                                                     int cap, pct_dev_words* __restrict__ out) {
     __shared__ unsigned long long sh[4][4];
     unsigned long long v[4] = {0, 0, 0, 0};
     for (int64_t it = (int64_t)blockIdx.x * 256 + threadIdx.x; it < n_items; it += (int64_t)gridDim.x * 256) {
@@ -2335,7 +2335,7 @@ __global__ __launch_bounds__(256) void k_item_census(const int2* __restrict__ it
         if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][j] = v[j];
     }
     __syncthreads();
-    if (threadIdx.x < 4) atomicAdd(&out[threadIdx.x], sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x]);
+    if (threadIdx.x < 4) atomicAdd(&out->census[threadIdx.x], sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x]);
 }
 
 KnnArgs make_args(pct_ctx* ctx, int32_t k, double eps, bool grid) {
@@ -2361,7 +2361,7 @@ KnnArgs make_args(pct_ctx* ctx, int32_t k, double eps, bool grid) {
     a.nbr_cnt = eps > 0 ? (int*)ctx->nbr_cnt.p : nullptr;
     a.row_done = ctx->own_flag || ctx->level_mode ? (int*)ctx->row_done.p : nullptr;
     a.redo_m = a.row_done ? (int*)ctx->redo_m.p : nullptr;
-    a.counters = (unsigned long long*)ctx->counters.p;
+    a.counters = &pct_dev(ctx)->sweep;
     a.stats = ctx->collect_stats ? 1 : 0;
     return a;
 }
@@ -2373,8 +2373,8 @@ int reserve_table(pct_ctx* ctx, int32_t k, double eps, bool with_dist = true) {
     if (with_dist) PCT_TRY(pct_reserve(ctx, &ctx->nbr_dist, rows * ctx->nbr_pitch * sizeof(float)));
     ctx->dist_valid = with_dist;
     if (eps > 0) PCT_TRY(pct_reserve(ctx, &ctx->nbr_cnt, rows * sizeof(int)));
-    PCT_TRY(pct_reserve(ctx, &ctx->counters, 64 * sizeof(unsigned long long)));
-    if (!ctx->counters_clean) PCT_HIP(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
+    PCT_TRY(pct_reserve(ctx, &ctx->counters, sizeof(pct_dev_words)));
+    if (!ctx->counters_clean) PCT_HIP(ctx, hipMemsetAsync(&pct_dev(ctx)->sweep, 0, sizeof(pct_sweep_words), ctx->stream));
     ctx->counters_clean = false;
     return PCT_OK;
 }
@@ -2547,11 +2547,11 @@ int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, in
     }
     KnnArgs a = make_args(ctx, k, eps, true);
     if (!ctx->dist_valid) a.nbr_dist = nullptr;
-    int* redo_count = (int*)ctx->counters.p + 14;            // counters buffer: 8 x u64, last int pair reserved
+    int* redo_count = &pct_dev(ctx)->sweep.redo_count;
     int* redo = (int*)ctx->redo.p;
     const dim3 block(64 * kWavesPerBlock);
     PCT_TRY(launch_sweep(ctx, plan, a, redo, redo_count));
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[7], ctx->stream));      // end of the dominant kernel
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FAST_END], ctx->stream));      // end of the dominant kernel
     // exact pass: the flagged queries (device-side count, fixed grid) or, for testing, every query
     if (phase != 1) {
         const int64_t waves = exact_only ? n_rows : 32768;   // one query per wave for typical redo counts
@@ -2588,10 +2588,10 @@ int pct_launch_knn_tree(pct_ctx* ctx, int32_t k, double eps) {
     a.tree_codes = (const unsigned long long*)ctx->tree_codes.p + ctx->n;     // second half: the sorted codes
     a.tree_lvl = (const unsigned char*)ctx->tree_lvl.p;
     a.tree_bucket = (const int*)ctx->tree_bucket.p;
-    int* redo_count = (int*)ctx->counters.p + 14;
+    int* redo_count = &pct_dev(ctx)->sweep.redo_count;
     int* redo = (int*)ctx->redo.p;
     PCT_TRY(launch_sweep(ctx, plan, a, redo, redo_count));
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FAST_END], ctx->stream));
     const int blocks = (32768 + kWavesPerBlock - 1) / kWavesPerBlock;        // device-side count, fixed grid
     const int* list = exact_only ? nullptr : redo;
     if (k + 1 <= 64)
@@ -2604,19 +2604,19 @@ int pct_launch_knn_tree(pct_ctx* ctx, int32_t k, double eps) {
 }
 
 int pct_item_census(pct_ctx* ctx, int32_t k, unsigned long long out4[4]) {
-    PCT_TRY(pct_reserve(ctx, &ctx->counters, 64 * sizeof(unsigned long long)));
-    PCT_HIP(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
+    PCT_TRY(pct_reserve(ctx, &ctx->counters, sizeof(pct_dev_words)));
+    PCT_HIP(ctx, hipMemsetAsync(pct_dev(ctx), 0, sizeof(pct_sweep_words), ctx->stream));      // (the census shares its words with the sweep's, cleared whole)
     ctx->counters_clean = false;
     const int cap = k + 1 <= pct_fast_r1_max() ? kStageCap : PCT_STAGE_CAP2_HOST;
     const int blocks = (int)((ctx->n_items + 255) / 256 < 1024 ? (ctx->n_items + 255) / 256 : 1024);
     if (blocks > 0) {
         PCT_LAUNCH(k_item_census, dim3(blocks), dim3(256), 0, ctx->stream, (const int2*)ctx->occ.p, ctx->n_items, ctx->items_q,
-                           (const int*)ctx->cell_cnt.p, (const int*)ctx->cell_own.p, ctx->grid, k, cap, (unsigned long long*)ctx->counters.p);
+                           (const int*)ctx->cell_cnt.p, (const int*)ctx->cell_own.p, ctx->grid, k, cap, pct_dev(ctx));
         PCT_HIP(ctx, hipGetLastError());
     }
-    PCT_HIP(ctx, hipMemcpyAsync(ctx->pin + 2112, ctx->counters.p, 32, hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(ctx->pin->census, pct_dev(ctx)->census, sizeof(ctx->pin->census), hipMemcpyDeviceToHost, ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(out4, ctx->pin + 2112, 32);
+    memcpy(out4, ctx->pin->census, sizeof(ctx->pin->census));
     return PCT_OK;
 }
 

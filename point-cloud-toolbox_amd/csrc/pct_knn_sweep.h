@@ -39,7 +39,7 @@ struct KnnArgs {
     const unsigned char* tree_lvl;          // level every position is served at
     const int* tree_bucket;                 // first position of every 18-bit code prefix
     int stats;                // collect the counters below (off by default)
-    unsigned long long* counters;   // [0] ring fallbacks [1] LDS overflows [2] flushes [3] candidate steps [4] redone queries [5] queries beyond the culling limits (always counted)
+    pct_sweep_words* counters;
 };
 
 // rows of 128 .. PCT_K_MAX neighbours (pct_knn_wide.hip): list registers R = 4 | 8
@@ -483,7 +483,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_knn_exact(KnnArgs a, co
             if (have) continue;
             if (fmin(sw.tau_d, sw.eps2) <= guaranteed_r2(g, cx, cy, cz, gx, gy, gz, it.ring)) {
                 // final among the kept points; a handle that left points out must also be inside its limits
-                if (lane == 0 && fmin(sw.tau_d, sw.eps2) > limit_r2(g, cx, cy, cz, gx, gy, gz)) atomicAdd(&a.counters[5], 1ull);
+                if (lane == 0 && fmin(sw.tau_d, sw.eps2) > limit_r2(g, cx, cy, cz, gx, gy, gz)) atomicAdd(&a.counters->beyond_limits, 1ull);
                 break;
             }
             // widen: one ring at a time near the query, then by half the radius (a query clamped into a corner of a
@@ -492,7 +492,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_knn_exact(KnnArgs a, co
             have_next = it.next(g, cs, cx, cy, cz, nbase, nlim);
             if (have_next && nbase + lane < nlim) c_next = a.pts[nbase + lane];
         }
-        if (a.stats && lane == 0 && it.ring > 1) atomicAdd(&a.counters[0], 1ull);
+        if (a.stats && lane == 0 && it.ring > 1) atomicAdd(&a.counters->ring_fallbacks, 1ull);
         sw.store(row, a.pitch, a.nbr_pos, a.nbr_dist, a.nbr_cnt);
         if (a.row_done && lane == 0) a.row_done[row] = 1;
     }
@@ -575,9 +575,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_knn_exact_tree(KnnArgs 
             ++rounds;
         }
         if (a.stats && lane == 0) {
-            if (rounds > 0) atomicAdd(&a.counters[0], 1ull);
-            atomicAdd(&a.counters[3], steps);
-            atomicMax(&a.counters[6], (steps << 32) | (unsigned)row);      // the costliest query: 64-candidate steps, row
+            if (rounds > 0) atomicAdd(&a.counters->ring_fallbacks, 1ull);
+            atomicAdd(&a.counters->candidate_steps, steps);
+            atomicMax(&a.counters->costliest, (steps << 32) | (unsigned)row);      // the costliest query: 64-candidate steps, row
         }
         sw.store(row, a.pitch, a.nbr_pos, a.nbr_dist, a.nbr_cnt);
     }

@@ -97,6 +97,7 @@ struct BandStats {
     unsigned exact;                // pending queries only the exact sweep can answer
     unsigned pad;
 };
+static_assert(sizeof(BandStats) <= sizeof(pct_pinned::band_stats) && alignof(BandStats) <= 64, "pct_pinned::band_stats holds a BandStats");
 
 __global__ __launch_bounds__(256) void k_band_hist(const float* __restrict__ want, int64_t begin, int64_t end, float log_edge0,
                                                    BandStats* __restrict__ out) {
@@ -186,7 +187,7 @@ void swap_buf(T& a, T& b) { T t = a; a = b; b = t; }
 }  // namespace
 
 int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps) {
-    *(long long*)(ctx->pin + 2048 + 8 * ctx->fit_par) = 0;        // rows the passes' fits hand to k_fit_svd: summed over the passes of this call
+    ctx->pin->svd_rows[ctx->fit_par] = 0;                           // rows the passes' fits hand to k_fit_svd: summed over the passes of this call
     const int64_t nq = ctx->q_end - ctx->q_begin;
     if (ctx->n >= ((int64_t)1 << 29)) return pct_fail(ctx, PCT_ERR_INVALID, "the chained sweep handles clouds below 2^29 points");
     const int pitch = (k + 3) & ~3;
@@ -273,9 +274,9 @@ int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps) {
             PCT_LAUNCH(k_band_hist, dim3(512), dim3(256), 0, ctx->stream, (const float*)ctx->flag_buf.p, ctx->q_begin,
                                ctx->q_end, log_edge0, d_st);
             PCT_HIP(ctx, hipGetLastError());
-            PCT_HIP(ctx, hipMemcpyAsync(ctx->pin + 256, d_st, sizeof(BandStats), hipMemcpyDeviceToHost, ctx->stream));
+            PCT_HIP(ctx, hipMemcpyAsync(ctx->pin->band_stats, d_st, sizeof(BandStats), hipMemcpyDeviceToHost, ctx->stream));
             PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            memcpy(&st, ctx->pin + 256, sizeof(BandStats));
+            memcpy(&st, ctx->pin->band_stats, sizeof(BandStats));
             int64_t banded = 0;
             for (int b = 0; b < kBins; ++b) banded += st.hist[b];
             pending = banded + st.exact;
@@ -298,9 +299,9 @@ int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps) {
             PCT_LAUNCH(k_band_box, dim3(512), dim3(256), 0, ctx->stream, (const float*)ctx->flag_buf.p, ctx->xyz_view,
                                ctx->q_begin, ctx->q_end, lo, hi, d_box, (unsigned*)(d_box + 6));
             PCT_HIP(ctx, hipGetLastError());
-            PCT_HIP(ctx, hipMemcpyAsync(ctx->pin + 1024, d_box, sizeof(init), hipMemcpyDeviceToHost, ctx->stream));
+            PCT_HIP(ctx, hipMemcpyAsync(ctx->pin->band_box, d_box, sizeof(init), hipMemcpyDeviceToHost, ctx->stream));
             PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            const int* hb = (const int*)(ctx->pin + 1024);
+            const int* hb = ctx->pin->band_box;
             for (int a = 0; a < 6; ++a) ctx->level_box[a] = order_to_float(hb[a]);
             ctx->level_box_valid = true;
             ctx->own_flag = ctx->flag_buf.p;

@@ -401,7 +401,7 @@ int pct_build_tree(pct_ctx* ctx, int32_t k, double eps, bool* usable) {
     int2* seg_range = (int2*)ctx->tree_range.p;
     int* seg_pop = (int*)(seg_range + nn + 1);
     int* counts = seg_pop + nn + 1;                       // device: {items, segments, segments over the cap, their points, points per level [22]}
-    long long* totals = (long long*)(ctx->pin + 2176);    // host: {items, segments}
+    long long* totals = ctx->pin->tree_totals;            // host: {items, segments}
     PCT_LAUNCH(k_tree_items, grid1, block, 0, ctx->stream, (const u64*)codes, (const unsigned char*)ctx->tree_lvl.p,
                        (const int*)seg_start, (const u64*)sums, n, items_q, (int2*)ctx->occ.p, (int4*)ctx->tree_seg.p, seg_range, counts, totals);
     PCT_HIP(ctx, hipGetLastError());
@@ -418,11 +418,12 @@ int pct_build_tree(pct_ctx* ctx, int32_t k, double eps, bool* usable) {
     PCT_LAUNCH(k_tree_stencil, dim3((unsigned)((n_segs * 32 + 255) / 256)), block, 0, ctx->stream, (const u64*)codes, (const int*)ctx->tree_bucket.p,
                        (const int4*)ctx->tree_seg.p, (const int2*)seg_range, n_segs, cap, (int2*)ctx->tree_runs.p, seg_pop, counts + 2);
     PCT_HIP(ctx, hipGetLastError());
-    PCT_HIP(ctx, hipMemcpyAsync(ctx->pin + 2208, counts, 26 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    const int* h_counts = ctx->pin->tree_counts;
+    PCT_HIP(ctx, hipMemcpyAsync(ctx->pin->tree_counts, counts, sizeof(ctx->pin->tree_counts), hipMemcpyDeviceToHost, ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     tick(3);
     {   // levels between the 5th and the 95th percentile of the sampled points
-        const int* hist = (const int*)(ctx->pin + 2208) + 4;
+        const int* hist = &h_counts[4];
         long long tot = 0, acc = 0;
         for (int l = 0; l < 22; ++l) tot += hist[l];
         int lo = 0, hi = 21;
@@ -434,7 +435,7 @@ int pct_build_tree(pct_ctx* ctx, int32_t k, double eps, bool* usable) {
         for (int l = 0; l + 1 < 22; ++l) best2 = best2 > (long long)hist[l] + hist[l + 1] ? best2 : (long long)hist[l] + hist[l + 1];
         ctx->tree_two_level_share = tot > 0 ? (double)best2 / (double)tot : 1.0;
     }
-    const int64_t bad_segs = ((const int*)(ctx->pin + 2208))[2], bad_pts = ((const int*)(ctx->pin + 2208))[3];
+    const int64_t bad_segs = h_counts[2], bad_pts = h_counts[3];
     if (bad_segs > 0 && !pct_getenv("PCT_TREE_NO_REFINE")) {
         if ((size_t)(n_segs + bad_pts) > room) {          // rare: most of the cloud is being split -- a larger table, contents kept
             room = (size_t)(n_segs + bad_pts) + 64;
@@ -451,14 +452,13 @@ int pct_build_tree(pct_ctx* ctx, int32_t k, double eps, bool* usable) {
                            (int4*)ctx->tree_seg.p, (const int2*)seg_range, (const int*)seg_pop, (int2*)ctx->tree_runs.p, (int2*)ctx->occ.p,
                            (unsigned char*)ctx->tree_lvl.p, counts);
         PCT_HIP(ctx, hipGetLastError());
-        PCT_HIP(ctx, hipMemcpyAsync(ctx->pin + 2208, counts, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        PCT_HIP(ctx, hipMemcpyAsync(ctx->pin->tree_counts, counts, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
         PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        const int* fin = (const int*)(ctx->pin + 2208);
-        if (fin[0] < n_items || fin[0] > n_items + bad_pts || fin[1] < n_segs || (size_t)fin[1] > room)
-            return pct_fail(ctx, PCT_ERR_INVALID, "tree refinement: %d items, %d segments (from %lld / %lld, %lld points split)", fin[0], fin[1],
+        if (h_counts[0] < n_items || h_counts[0] > n_items + bad_pts || h_counts[1] < n_segs || (size_t)h_counts[1] > room)
+            return pct_fail(ctx, PCT_ERR_INVALID, "tree refinement: %d items, %d segments (from %lld / %lld, %lld points split)", h_counts[0], h_counts[1],
                             (long long)n_items, (long long)n_segs, (long long)bad_pts);
-        n_items = fin[0];
-        n_segs = fin[1];
+        n_items = h_counts[0];
+        n_segs = h_counts[1];
     }
     tick(4);
     if (debug)

@@ -1677,6 +1677,52 @@ def test_asynchronous_calls_of_a_stream_of_clouds(gpu):
     ref.close()
 
 
+def test_async_statistics_survive_a_chained_sweep_behind_them(gpu):
+    """pct_set_async: the second of two pending plain sweeps keeps its statistics words and its SVD row count in the
+    pinned slots of parity 1 while the call behind it, a chained sweep, reads its band statistics back.  What
+    stage_times_done() then says of the second call, and timings() of the chained one after a wait, is what a blocking
+    handle says of the same calls (every field but the measured times), and K and H are the same bits.  Asynchronous
+    calls run with statistics off, so the compared counters are zero on both sides: this pins the contract for later
+    work on the asynchronous path.  That the two read-backs cannot share bytes is a property of the pinned page's layout
+    (struct pct_pinned), not something this test could show."""
+    capi = gpu["capi"]
+    rng = np.random.default_rng(41)
+    n = 20_000
+    r = 10.0 ** rng.uniform(-2.0, 0.0, size=n)                          # density ~ 1/r^2
+    th = rng.uniform(0, 2 * np.pi, size=n)
+    scan = np.stack([r * np.cos(th), r * np.sin(th), 0.02 * np.sin(8 * r)], 1).astype(np.float32)
+    ref, h = capi.Handle(0), capi.Handle(0)
+    ref.set_points(scan)                                                # the same three calls, blocking
+    ref.curvature(30, 0.0, capi.KNN_GRID)
+    ref.curvature(30, 0.0, capi.KNN_GRID)
+    t_grid = ref.timings()
+    ref.curvature(30, 0.0, capi.KNN_GRID_LEVELS)
+    t_levels = ref.timings()
+    _, K0, H0, _ = ref.get_fit(0, n, coefs=False, H2=False)
+    h.set_async(True)
+    h.set_points(scan)
+    h.curvature(30, 0.0, capi.KNN_GRID)
+    h.curvature(30, 0.0, capi.KNN_GRID)                                 # parity 1
+    h.curvature(30, 0.0, capi.KNN_GRID_LEVELS)                          # does the bookkeeping of the call before it
+    done = h.stage_times_done().as_dict()
+    print("second call, asynchronous:", done, "\nblocking:", t_grid)
+    for f in ("algo", "sweep_variant", "levels", "grid_points", "ring_fallbacks", "lds_overflows", "flushes", "candidate_steps",
+              "redone_queries", "fit_svd_rows"):
+        assert done[f] == t_grid[f], (f, done[f], t_grid[f])
+    assert done["algo"] == capi.KNN_GRID
+    h.synchronize()
+    t = h.timings()
+    print("chained call, asynchronous:", t, "\nblocking:", t_levels)
+    assert t["algo"] == capi.KNN_GRID_LEVELS and t["levels"] >= 1
+    for f in t_levels:
+        if not f.endswith("_ms"):                                      # (elapsed times are measurements)
+            assert t[f] == t_levels[f], (f, t[f], t_levels[f])
+    _, K, H, _ = h.get_fit(0, n, coefs=False, H2=False)
+    assert K.tobytes() == K0.tobytes() and H.tobytes() == H0.tobytes()
+    h.close()
+    ref.close()
+
+
 def test_curvature_stream_gives_every_cloud_its_own_values_in_order(gpu):
     """point_cloud_toolbox_amd.stream.curvature_stream: clouds of different sizes and dtypes through two handles in turn
     (asynchronous calls, transfers under the other cloud's kernels) -- the values of a plain handle, in input order; a
