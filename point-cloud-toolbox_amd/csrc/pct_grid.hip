@@ -10,10 +10,17 @@
 // hist and scatter of the whole-cloud builds are a two-level counting sort with LDS counters only (k_bin_*, below);
 // the level passes, slab-owned handles and very large grids keep the per-point atomics of k_hist / k_scatter.
 //
-// All kernels are HBM/L2 streaming passes over 16 B records with 64-wide waves.  Host side (pct_build_grid): outlier-
-// trimmed grid box, cell size by occupancy (warm-started, speculative box from the previous similar cloud), one
-// host synchronisation per accepted build; small results come back through pinned memory the kernels write.
+// All kernels are HBM/L2 streaming passes over 16 B records with 64-wide waves.  Host side, top to bottom of a build:
+//   select_source   where the points come from (GridSource) and that source's pack pass; outlier-trimmed grid box, or
+//                   the previous similar cloud's box with this cloud's own box checked later (check_deferred_box)
+//   EdgeSearch      cell size by occupancy, warm-started (pct_grid_edge.h: host arithmetic only, tested on the CPU)
+//   choose_build    the counting sort or one of the three per-point-atomics builds, once per pass
+//   launch_count, launch_scan, launch_place     every launch of a pass, each expression once
+//   commit_grid     everything an accepted build leaves in the handle
+//   pct_build_grid  the pass loop, the cell budget, the PCT_KNN_AUTO give-up and the (at most two) restarts
+// One host synchronisation per accepted build; small results come back through pinned memory the kernels write.
 #include "pct_internal.h"
+#include "pct_grid_edge.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -802,44 +809,7 @@ __global__ __launch_bounds__(kBlock) void k_scatter_raw(const float* __restrict_
 // Kernel boundaries are the only ordering between blocks.
 constexpr int kBinBlock = 256;        // fine level: one block per work item
 constexpr int kBinWide = 1024;        // coarse level: one block per tile, four rows per thread in flight
-constexpr int kBinTileRows = 4096;       // input rows per tile (times a whole factor for clouds above kBinMaxTiles tiles)
-constexpr int kBinMaxTiles = 1024;
-constexpr int kBinMaxBuckets = 4096;     // LDS counters of the coarse level
-constexpr int kBinMaxCounters = 8192;    // LDS counters of the fine level: cells per bucket x classes
-constexpr int kBinMinChunk = 4096;       // records per work item (at least; never below the fine counters)
-
-struct BinShape {
-    bool ok;             // the bucket scheme covers this grid
-    int shift;           // log2 cells per bucket
-    int nb;              // buckets
-    int cls;             // classes: 1 = every point owned, 2 = owned / other
-    int tile_rows, ntiles;
-    int chunk;           // records per work item
-    int max_items;       // upper bound of the work list: every bucket at least one item
-    int max_shared;      // upper bound of the items of shared buckets
-};
-
-// Sizing: about a thousand buckets (each a few thousand points at the sweep's occupancies), cells per bucket a power of
-// two from 256 up to what the fine LDS counters hold; a grid that would still need more than kBinMaxBuckets is not covered.
-__host__ BinShape bin_shape(int64_t n, int64_t ncell, bool sharded) {
-    BinShape s = {};
-    s.cls = sharded ? 2 : 1;
-    int max_shift = 8;                                // 2^shift * cls <= kBinMaxCounters
-    while ((s.cls << (max_shift + 1)) <= kBinMaxCounters) ++max_shift;
-    s.shift = 8;
-    while (((ncell + ((int64_t)1 << s.shift) - 1) >> s.shift) > 1024 && s.shift < max_shift) ++s.shift;
-    const int64_t nb = (ncell + ((int64_t)1 << s.shift) - 1) >> s.shift;
-    s.ok = n >= 1 && n < ((int64_t)1 << 31) - kBinTileRows && ncell >= 1 && nb <= kBinMaxBuckets;
-    if (!s.ok) return s;
-    s.nb = (int)nb;
-    const int64_t f = (n + (int64_t)kBinTileRows * kBinMaxTiles - 1) / ((int64_t)kBinTileRows * kBinMaxTiles);
-    s.tile_rows = (int)(kBinTileRows * (f < 1 ? 1 : f));
-    s.ntiles = (int)((n + s.tile_rows - 1) / s.tile_rows);
-    s.chunk = (s.cls << s.shift) > kBinMinChunk ? (s.cls << s.shift) : kBinMinChunk;
-    s.max_items = s.nb + (int)(n / s.chunk);
-    s.max_shared = 2 * (int)(n / s.chunk) + 1;          // sum of ceil(c / chunk) over the buckets with c > chunk
-    return s;
-}
+// (kBinTileRows, kBinMaxTiles, kBinMaxBuckets, kBinMaxCounters, kBinMinChunk, BinShape and bin_shape: pct_grid_edge.h)
 
 // the cell of a record: k_hist_raw's expression (a non-finite row is binned at the origin)
 __device__ __forceinline__ int bin_cell(float x, float y, float z, const pct_grid& g) {
@@ -1367,7 +1337,108 @@ int pct_pack_points_f64(pct_ctx* ctx, const double* d_xyz64) {
     return PCT_OK;
 }
 
-static void set_dims(pct_grid* g, const float* bbox, double a) {
+// ---- where the grid's points come from ---------------------------------------------------------------------------------
+enum class GridSource {
+    LevelBase,     // later passes of the density-adaptive sweep: the points in the cell order of its first pass, and that pass's box
+    CulledPack,    // sharded handle: the owned rows and the points near them (pack_near_owned)
+    CallerRows,    // the caller's rows on the (trimmed) box of the previous similar cloud; this cloud's box is checked later
+    FullPack,      // every point, packed and measured first
+};
+
+struct GridPoints {
+    GridSource src;
+    float bbox[6];           // grid box
+    PackRed red;             // the pack pass's record (CallerRows: filled in by check_deferred_box)
+    Box3 kept_box;           // CulledPack: the box that was applied
+    int64_t n;               // points the grid holds
+    int g_begin, g_end;      // the owned range of the grid's records (0, 0: ownership by own_flag)
+    bool raw;                // the histogram and the placement read the caller's rows (k_bin_*<true>, k_hist_raw, k_scatter_raw)
+    bool from_base;          // ... or the level base (k_hist_agg)
+    bool deferred_box;       // the cloud's own box rides on the first pass and has not been checked yet
+};
+
+// Decides the source from ctx and runs its pack pass.  *restart: the kept part cannot fill a row; culling is ruled out
+// on the handle and the caller starts over.
+static int select_source(pct_ctx* ctx, int32_t k, double target, bool slab, int64_t n_owned, bool sharded, GridPoints* s, bool* restart) {
+    const bool own_flag = ctx->own_flag != nullptr;
+    // (a slab's owned points are found by the pack itself: it always runs, with an open box after a limit retry)
+    const bool try_cull = slab ? n_owned > 0
+                               : !own_flag && sharded && n_owned > 0 && !ctx->has_f64 && !ctx->no_cull && !pct_getenv("PCT_NO_CULL");
+    // Speculation: a handle fed a stream of similar clouds builds the cell list over the (trimmed) box of the previous
+    // call without waiting for the new bounding box -- any box is a valid grid box, points outside are clamped into
+    // the boundary cells -- and checks the new box at the synchronisation that ends the first pass.  One host round
+    // trip less per build.
+    const bool spec = !try_cull && !own_flag && !ctx->level_mode && ctx->hint_edge > 0 && ctx->spec_valid && ctx->spec_n == ctx->n &&
+                      !pct_getenv("PCT_NO_SPEC");
+    *s = GridPoints{};
+    s->src = own_flag && ctx->lvl_src_valid ? GridSource::LevelBase : try_cull ? GridSource::CulledPack : spec ? GridSource::CallerRows
+                                                                                                               : GridSource::FullPack;
+    switch (s->src) {
+    case GridSource::LevelBase:
+        for (int a = 0; a < 6; ++a) s->bbox[a] = ctx->lvl_bbox[a];
+        ctx->n_grid = ctx->n;
+        ctx->g_begin = 0;
+        ctx->culled = false;
+        break;
+    case GridSource::CulledPack:
+        PCT_TRY(pack_near_owned(ctx, target, s->bbox, &s->red, &s->kept_box));
+        if (ctx->n_grid < (int64_t)k + 1) {
+            // The kept part cannot even fill a row (a few owned rows and a culling box -- possibly a stale one of the
+            // previous cloud -- that holds nobody else): the table would carry "missing" entries that the fused fit,
+            // launched before the limits are checked, must never see without a count array.  Take every point.
+            ctx->no_cull = true;
+            ctx->cull_box_valid = false;
+            *restart = true;
+            return PCT_OK;
+        }
+        PCT_TRY(trim_box(ctx, s->red, s->bbox));
+        break;
+    case GridSource::CallerRows:
+        // no pack pass at all: the histogram reads the caller's rows and takes the cloud's box along (k_hist_raw)
+        PCT_TRY(red_reset(ctx, grid_1d(ctx->n, kBlock, 0), false));
+        ctx->pts4_valid = false;
+        ctx->n_grid = ctx->n;
+        ctx->g_begin = ctx->q_begin;
+        ctx->culled = false;
+        for (int a = 0; a < 6; ++a) s->bbox[a] = ctx->spec_bbox[a];
+        break;
+    case GridSource::FullPack:
+        PCT_TRY(pack_all(ctx, s->bbox, &s->red));
+        PCT_TRY(trim_box(ctx, s->red, s->bbox));
+        break;
+    }
+    s->raw = s->deferred_box = s->src == GridSource::CallerRows;
+    s->from_base = s->src == GridSource::LevelBase;
+    s->n = ctx->n_grid;
+    s->g_begin = own_flag ? 0 : (int)ctx->g_begin;
+    s->g_end = own_flag ? 0 : (int)(ctx->g_begin + n_owned);
+    return PCT_OK;
+}
+
+// The deferred pack result is in: was the old box still right?  (Within 2 % of the previous cloud's extent per face.)
+enum class BoxCheck { Accept, Restart, NonFinite };
+static BoxCheck check_deferred_box(pct_ctx* ctx, GridPoints* s) {
+    s->deferred_box = false;
+    memcpy(&s->red, pin_red(ctx), sizeof(s->red));
+    if (s->red.bad) return BoxCheck::NonFinite;
+    bool same = true;
+    for (int ax = 0; ax < 3; ++ax) {
+        const float lo = order_float(s->red.bb[ax]), hi = order_float(s->red.bb[3 + ax]);
+        const float tol = 0.02f * (ctx->spec_raw[3 + ax] - ctx->spec_raw[ax]) + 1e-30f;
+        same = same && fabsf(lo - ctx->spec_raw[ax]) <= tol && fabsf(hi - ctx->spec_raw[3 + ax]) <= tol;
+    }
+    return same ? BoxCheck::Accept : BoxCheck::Restart;
+}
+
+// ---- the grid of one pass ----------------------------------------------------------------------------------------------
+// The box and the dimensions for edge a.  sub_box (a fast level pass): 2.5 edges of THIS cell size around the owned
+// points (their stencils must end inside the box: the points outside it are left out of the cell list).
+static void size_grid(const pct_ctx* ctx, bool sub_box, float* bbox, double a, pct_grid* g) {
+    if (sub_box)
+        for (int ax = 0; ax < 3; ++ax) {
+            bbox[ax] = ctx->level_box[ax] - (float)(2.5 * a);
+            bbox[3 + ax] = ctx->level_box[3 + ax] + (float)(2.5 * a);
+        }
     g->ox = bbox[0]; g->oy = bbox[1]; g->oz = bbox[2];
     g->cell = a;
     g->inv_cell = 1.0 / a;
@@ -1389,6 +1460,247 @@ static void set_dims(pct_grid* g, const float* bbox, double a) {
     g->ncell = (int64_t)g->nx * g->ny * g->nz;
 }
 
+// what every pass of a build writes, sized by the points and not by the grid
+static int reserve_lists(pct_ctx* ctx, int64_t n, int64_t n_owned) {
+    PCT_TRY(pct_reserve(ctx, &ctx->cell_of, (size_t)n * sizeof(int)));
+    PCT_TRY(pct_reserve(ctx, &ctx->cell_fill, (size_t)n * sizeof(int)));   // in-cell arrival ranks
+    PCT_TRY(pct_reserve(ctx, &ctx->sorted4, (size_t)n * sizeof(float4)));
+    PCT_TRY(pct_reserve(ctx, &ctx->row_of, (size_t)((ctx->own_flag ? n : n_owned) + 1) * sizeof(int)));
+    PCT_TRY(pct_reserve(ctx, &ctx->owned_pos, (size_t)n_owned * sizeof(int)));
+    if (ctx->has_f64) PCT_TRY(pct_reserve(ctx, &ctx->sorted4d, (size_t)n * sizeof(double4)));
+    return PCT_OK;
+}
+
+// the cell-size search of one build (pct_grid_edge.h) on the box of its source and the handle's warm start
+static EdgeSearch edge_search(const pct_ctx* ctx, const GridPoints& s, double target, double eps) {
+    EdgeSearch es = {};
+    es.target = target; es.n = s.n; es.eps = eps;
+    es.ex = (double)s.bbox[3] - s.bbox[0]; es.ey = (double)s.bbox[4] - s.bbox[1]; es.ez = (double)s.bbox[5] - s.bbox[2];
+    es.hint_edge = ctx->hint_edge; es.hint_guess = ctx->hint_guess; es.hint_target = ctx->hint_target;
+    es.level_edge = ctx->level_edge;
+    // a level pass takes the edge it is given: its owned set is a mix of densities, and the mean population the search
+    // steers on would be pulled to the dense minority (pct_levels.hip sizes by the geometric mean instead)
+    es.max_iter = es.level_edge > 0 ? 1 : ctx->level_mode ? 2 : 8;
+    return es;
+}
+
+// ---- which build, and its launches -------------------------------------------------------------------------------------
+// Dispatch: the two-level LDS counting sort (k_bin_*) wherever a grid point is owned or not by its public index alone and
+// every point is binned -- the caller's rows, the full pack, the range-culled pack -- and the bucket scheme covers the
+// grid (bin_shape, per pass).  The level passes (own_flag, sub_box), the slab-owned handles and larger grids keep the
+// per-point atomics; PCT_GRID_ATOMIC=1 forces those everywhere (A/B runs, parity tests).
+enum class GridBuild {
+    Bin,             // k_bin_count, k_bin_colscan, k_bin_plan, k_bin_scatter, k_bin_cells | k_bin_place
+    AtomicRaw,       // k_hist_raw (+ k_pack_final while the box is deferred)                 | k_scatter_raw
+    AtomicBase,      // k_hist_agg                                                             | k_scatter
+    AtomicPacked,    // k_hist                                                                 | k_scatter
+};
+static GridBuild choose_build(bool bin_allowed, const BinShape& bs, const GridPoints& s) {
+    return bin_allowed && bs.ok ? GridBuild::Bin : s.raw ? GridBuild::AtomicRaw : s.from_base ? GridBuild::AtomicBase : GridBuild::AtomicPacked;
+}
+
+// Scratch of one bin pass (sized by its grid): bucket-partitioned records (bin_rec), [tile][bucket] matrix (bin_mat),
+// plan words + bucket starts + column totals + work list (bin_plan), run offsets of the shared buckets' items (bin_base).
+struct BinScratch {
+    int* plan;
+    unsigned* tot;       // column totals, inside bin_plan
+    int4* items;         // work list, inside bin_plan
+    size_t lds;          // fine counters of one class
+};
+static int bin_scratch(pct_ctx* ctx, const BinShape& bs, int64_t n, BinScratch* b) {
+    PCT_TRY(pct_reserve(ctx, &ctx->bin_rec, (size_t)n * sizeof(float4)));
+    PCT_TRY(pct_reserve(ctx, &ctx->bin_mat, (size_t)bs.ntiles * bs.nb * sizeof(unsigned)));
+    const size_t plan_words = 16 + (size_t)(bs.nb + 1) + (size_t)bs.nb;
+    const size_t items_at = (plan_words * sizeof(int) + 15) / 16 * 16;
+    PCT_TRY(pct_reserve(ctx, &ctx->bin_plan, items_at + (size_t)bs.max_items * sizeof(int4)));
+    PCT_TRY(pct_reserve(ctx, &ctx->bin_base, (size_t)bs.max_shared * (bs.cls << bs.shift) * sizeof(int)));
+    b->plan = (int*)ctx->bin_plan.p;
+    b->tot = (unsigned*)(b->plan + 16 + bs.nb + 1);
+    b->items = (int4*)((char*)ctx->bin_plan.p + items_at);
+    b->lds = (size_t)(bs.cls << bs.shift) * sizeof(int);
+    return PCT_OK;
+}
+
+// what the launches of one pass share
+struct GridPass {
+    GridBuild build;
+    pct_grid g;
+    BinShape bs;
+    BinScratch bin;
+    const float4* src;       // packed records (pts4 or the level base)
+    int64_t n_owned;
+    bool sharded, sub_box;
+};
+
+// the two passes over the input tiles, from the caller's rows (RAW) or from packed records
+template <bool RAW>
+static void launch_bin_count(pct_ctx* ctx, int64_t n, const GridPass& p, PackRed* parts) {
+    PCT_LAUNCH_T(k_bin_count<RAW>, dim3(p.bs.ntiles), dim3(kBinWide), 0, ctx->stream, ctx->xyz_view, p.src, n, p.bs.tile_rows, p.g, p.bs.shift,
+                 p.bs.nb, (unsigned*)ctx->bin_mat.p, parts);
+}
+template <bool RAW>
+static void launch_bin_scatter(pct_ctx* ctx, int64_t n, const GridPass& p, int* cell_oth) {
+    PCT_LAUNCH_T(k_bin_scatter<RAW>, dim3(p.bs.ntiles), dim3(kBinWide), 0, ctx->stream, ctx->xyz_view, p.src, n, p.bs.tile_rows, p.g, p.bs.shift,
+                 p.bs.nb, p.bs.chunk, (const unsigned*)ctx->bin_mat.p, (const int*)p.bin.plan, (float4*)ctx->bin_rec.p, (int*)ctx->cell_own.p, cell_oth);
+}
+
+// First half of a pass: per-cell counts of owned / other points in cell_own / cell_oth (and, while the box is deferred,
+// the cloud's PackRed record on its way to pinned memory).
+static int launch_count(pct_ctx* ctx, const GridPoints& s, GridPass& p) {
+    const pct_grid& g = p.g;
+    const int64_t n = s.n;
+    const float* own_flag = (const float*)ctx->own_flag;
+    const bool bin = p.build == GridBuild::Bin;            // (writes every counter itself: no clearing fill)
+    PCT_TRY(pct_reserve(ctx, &ctx->cell_own, (size_t)g.ncell * sizeof(int)));
+    if (!bin) PCT_HIP(ctx, hipMemsetAsync(ctx->cell_own.p, 0, (size_t)g.ncell * sizeof(int), ctx->stream));
+    if (p.sharded) {
+        PCT_TRY(pct_reserve(ctx, &ctx->cell_oth, (size_t)g.ncell * sizeof(int)));
+        if (!bin) PCT_HIP(ctx, hipMemsetAsync(ctx->cell_oth.p, 0, (size_t)g.ncell * sizeof(int), ctx->stream));
+    }
+    if (bin) PCT_TRY(bin_scratch(ctx, p.bs, n, &p.bin));
+    int* cell_oth = p.sharded ? (int*)ctx->cell_oth.p : nullptr;
+    PackRed* parts = s.deferred_box ? red_parts(ctx) : nullptr;
+    const int nhb = grid_1d(n, kBlock, 0);
+    if (bin) {
+        const BinShape& bs = p.bs;
+        s.raw ? launch_bin_count<true>(ctx, n, p, parts) : launch_bin_count<false>(ctx, n, p, parts);
+        PCT_LAUNCH(k_bin_colscan, dim3((bs.nb + kBinScanCols - 1) / kBinScanCols), dim3(kBinScanCols * kBinScanGroups), 0, ctx->stream,
+                   (unsigned*)ctx->bin_mat.p, bs.ntiles, bs.nb, p.bin.tot);
+        PCT_LAUNCH(k_bin_plan, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned*)p.bin.tot, bs.nb, bs.chunk, p.bin.plan, p.bin.items);
+        s.raw ? launch_bin_scatter<true>(ctx, n, p, cell_oth) : launch_bin_scatter<false>(ctx, n, p, cell_oth);
+        PCT_LAUNCH(k_bin_cells, dim3(bs.max_items + 1), dim3(kBinBlock), p.bin.lds, ctx->stream, (const float4*)ctx->bin_rec.p, (const int*)p.bin.plan,
+                   (const int4*)p.bin.items, g, bs.shift, (int)ctx->q_begin, (int)ctx->q_end, (int*)ctx->cell_own.p, cell_oth,
+                   (int*)ctx->bin_base.p, (const PackRed*)parts, bs.ntiles, (PackRed*)ctx->red.p, pin_red(ctx));
+    } else if (p.build == GridBuild::AtomicRaw) {
+        PCT_LAUNCH(k_hist_raw, dim3(nhb), dim3(kBlock), 0, ctx->stream, ctx->xyz_view, n, g, s.g_begin, s.g_end, (int*)ctx->cell_of.p,
+                   (int*)ctx->cell_fill.p, (int*)ctx->cell_own.p, cell_oth, parts);
+        if (parts) PCT_TRY(red_fold(ctx, nhb, false));
+    } else if (p.build == GridBuild::AtomicBase) {
+        PCT_LAUNCH(k_hist_agg, dim3(nhb), dim3(kBlock), 0, ctx->stream, p.src, n, g, own_flag, ctx->own_lo, ctx->own_hi, p.sub_box ? 1 : 0,
+                   (int*)ctx->cell_of.p, (int*)ctx->cell_fill.p, (int*)ctx->cell_own.p, (int*)ctx->cell_oth.p);
+    } else {
+        PCT_LAUNCH(k_hist, dim3(nhb), dim3(kBlock), 0, ctx->stream, p.src, n, g, s.g_begin, s.g_end, own_flag, ctx->own_lo, ctx->own_hi,
+                   p.sub_box ? 1 : 0, (int*)ctx->cell_of.p, (int*)ctx->cell_fill.p, (int*)ctx->cell_own.p, cell_oth);
+    }
+    return PCT_OK;
+}
+
+// Between the halves: cell starts, the ordered work list (occ) and -- in pinned memory from PCT_EV_SCAN_TOTALS on -- the
+// totals and the occupancy statistic the pass is judged by.
+static int launch_scan(pct_ctx* ctx, const GridPass& p, int items_q, int nblk) {
+    const int* cell_oth = p.sharded ? (const int*)ctx->cell_oth.p : nullptr;
+    PCT_TRY(pct_reserve(ctx, &ctx->scan_tmp, (size_t)(nblk + 1) * sizeof(int4) + (size_t)nblk * sizeof(unsigned long long)));
+    unsigned long long* sq_part = (unsigned long long*)((int4*)ctx->scan_tmp.p + nblk + 1);
+    PCT_TRY(pct_reserve(ctx, &ctx->cell_cnt, (size_t)(p.g.ncell + 1) * sizeof(int)));
+    PCT_TRY(pct_reserve(ctx, &ctx->own_start, (size_t)(p.g.ncell + 1) * sizeof(int)));
+    PCT_TRY(pct_reserve(ctx, &ctx->occ, ((size_t)(p.n_owned < p.g.ncell ? p.n_owned : p.g.ncell) + (size_t)p.n_owned / items_q + 16) * sizeof(int2)));
+    PCT_LAUNCH(k_scan_sums, dim3(nblk), dim3(kBlock), 0, ctx->stream, (const int*)ctx->cell_own.p, cell_oth, p.g.ncell, items_q,
+               (int4*)ctx->scan_tmp.p, sq_part);
+    PCT_TRY(pct_reserve(ctx, &ctx->counters, sizeof(pct_dev_words)));
+    PCT_LAUNCH(k_scan_tiles, dim3(1), dim3(1024), 0, ctx->stream, (int4*)ctx->scan_tmp.p, nblk,
+               (const unsigned long long*)sq_part, pin_totals(ctx), (unsigned long long*)&pct_dev(ctx)->sweep);
+    ctx->counters_clean = true;
+    // the totals this pass is judged by (and, with a deferred pack, the cloud's box) are in pinned memory from here on:
+    // the host waits for THIS point, not for the end of the stream -- while it wakes up, decides and enqueues the
+    // sweep, the device applies the scan and scatters the records (50 us at 1 M points; the read-back used to be ~25
+    // us of an idle device).  A pass that is rejected has scattered for nothing, as before.
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_SCAN_TOTALS], ctx->stream));
+    PCT_LAUNCH(k_scan_apply, dim3(nblk), dim3(kBlock), 0, ctx->stream, (const int*)ctx->cell_own.p, cell_oth, p.g.ncell, items_q,
+               (const int4*)ctx->scan_tmp.p, (int*)ctx->cell_cnt.p, (int*)ctx->own_start.p, (int2*)ctx->occ.p);
+    return PCT_OK;
+}
+
+// Second half, after the scan: every record to its place in sorted4 (owned_pos, sorted4d and -- unless lazy -- row_of along).
+static int launch_place(pct_ctx* ctx, const GridPoints& s, const GridPass& p) {
+    const pct_grid& g = p.g;
+    const int64_t n = s.n;
+    // (the chained sweep's passes read each other's lists: its first pass keeps row_of complete)
+    const bool lazy_rows = p.build == GridBuild::Bin && !ctx->level_mode;
+    ctx->row_of_valid = !lazy_rows;
+    ctx->row_of_rows = p.n_owned;
+    ctx->row_of_begin = (int)ctx->q_begin;
+    const int* cell_oth = p.sharded ? (const int*)ctx->cell_oth.p : nullptr;
+    const double4* pts4d = ctx->has_f64 ? (const double4*)ctx->pts4d.p : nullptr;
+    double4* sorted4d = ctx->has_f64 ? (double4*)ctx->sorted4d.p : nullptr;
+    if (p.build == GridBuild::Bin)
+        PCT_LAUNCH(k_bin_place, dim3(p.bs.max_items), dim3(kBinBlock), p.bin.lds + (p.sharded ? p.bin.lds / 2 : 0), ctx->stream,
+                   (const float4*)ctx->bin_rec.p, (const int*)p.bin.plan, (const int4*)p.bin.items, g, p.bs.shift, (int)ctx->q_begin,
+                   (int)ctx->q_end, n, p.n_owned, (const int*)ctx->cell_cnt.p, (const int*)ctx->cell_own.p, cell_oth,
+                   (const int*)ctx->own_start.p, (const int*)ctx->bin_base.p, (float4*)ctx->sorted4.p,
+                   lazy_rows ? nullptr : (int*)ctx->row_of.p, (int*)ctx->owned_pos.p, pts4d, sorted4d);
+    else if (p.build == GridBuild::AtomicRaw)
+        PCT_LAUNCH(k_scatter_raw, dim3(grid_1d(n, kBlock, 0)), dim3(kBlock), 0, ctx->stream, ctx->xyz_view, (const int*)ctx->cell_of.p,
+                   (const int*)ctx->cell_cnt.p, (const int*)ctx->cell_own.p, (const int*)ctx->own_start.p, (const int*)ctx->cell_fill.p, n,
+                   s.g_begin, (float4*)ctx->sorted4.p, (int*)ctx->row_of.p, (int*)ctx->owned_pos.p, pts4d, sorted4d);
+    else                    // AtomicBase, AtomicPacked
+        PCT_LAUNCH(k_scatter, dim3(grid_1d(n, kBlock, 0)), dim3(kBlock), 0, ctx->stream, p.src, (const int*)ctx->cell_of.p,
+                   (const int*)ctx->cell_cnt.p, (const int*)ctx->cell_own.p, (const int*)ctx->own_start.p, (const int*)ctx->cell_fill.p, n,
+                   s.g_begin, (float4*)ctx->sorted4.p, (int*)ctx->row_of.p, (int*)ctx->owned_pos.p, pts4d, sorted4d);
+    PCT_HIP(ctx, hipGetLastError());
+    return PCT_OK;
+}
+
+// PCT_GRID_DEBUG: the work list a bin pass planned (debugging only: waits for the stream)
+static int debug_bin_plan(pct_ctx* ctx, const GridPass& p) {
+    int pw[3] = {0, 0, 0};
+    PCT_HIP(ctx, hipMemcpyAsync(pw, p.bin.plan, sizeof(pw), hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    fprintf(stderr, "[grid] bin build: %d buckets of %d cells, %d tiles of %d rows, %d work items of up to %d records, %d of them in %d shared buckets\n",
+            p.bs.nb, 1 << p.bs.shift, p.bs.ntiles, p.bs.tile_rows, pw[0], p.bs.chunk, pw[1], pw[2]);
+    return PCT_OK;
+}
+
+// ---- bookkeeping of an accepted build ------------------------------------------------------------------------------
+static int commit_grid(pct_ctx* ctx, const GridPoints& s, pct_grid g, const EdgeSearch& es, int iters, double m_last, int4 tot,
+                       int64_t n_owned, bool sub_box) {
+    const bool own_flag = ctx->own_flag != nullptr, level_pass = es.level_edge > 0;
+    const int64_t n = s.n;
+    // faces of the culling box become limits of what the grid can vouch for (cell units from the origin)
+    for (int ax = 0; ax < 3; ++ax) {
+        const double o = ax == 0 ? g.ox : ax == 1 ? g.oy : g.oz;
+        g.lim_lo[ax] = ctx->culled ? ((double)s.kept_box.lo[ax] - o) * g.inv_cell : -INFINITY;
+        g.lim_hi[ax] = ctx->culled ? ((double)s.kept_box.hi[ax] - o) * g.inv_cell : INFINITY;
+    }
+    if (pct_getenv("PCT_GRID_DEBUG"))
+        fprintf(stderr, "[grid] box [%g %g %g]-[%g %g %g] edge %g dims %d x %d x %d = %lld cells, %d passes, occupancy %.1f, items %d\n", s.bbox[0],
+                s.bbox[1], s.bbox[2], s.bbox[3], s.bbox[4], s.bbox[5], g.cell, g.nx, g.ny, g.nz, (long long)g.ncell, iters, m_last, tot.y);
+    if (ctx->level_mode && !own_flag)                    // first pass of a density-adaptive sweep: its (trimmed) box serves the later ones
+        for (int a = 0; a < 6; ++a) ctx->lvl_bbox[a] = s.bbox[a];
+    ctx->grid = g;
+    ctx->tm.grid_iters += iters;
+    ctx->tm.cells = g.ncell;
+    ctx->tm.cell_size = g.cell;
+    ctx->tm.grid_points = n;
+    ctx->tm.occupancy = m_last;
+    if (s.src != GridSource::CulledPack && !own_flag && !ctx->level_mode) {       // remember the box for the next similar cloud
+        for (int a = 0; a < 6; ++a) ctx->spec_bbox[a] = s.bbox[a];
+        if (s.red.cnt > 0)                // raw bounding box of this cloud (before trimming)
+            for (int a = 0; a < 6; ++a) ctx->spec_raw[a] = order_float(s.red.bb[a]);
+        ctx->spec_n = ctx->n;
+        ctx->spec_valid = true;
+    }
+    if (m_last > 0 && !level_pass) {        // the warm start of the next build
+        ctx->hint_edge = es.hint_after(g.cell, m_last);
+        ctx->hint_guess = es.first_guess;
+        ctx->hint_target = es.target;
+    }
+    if ((tot.x != n && !sub_box) || tot.x > n || tot.z != n_owned)
+        return pct_fail(ctx, PCT_ERR_INVALID, "cell scan totals %d/%d != %lld/%lld", tot.x, tot.z, (long long)n, (long long)n_owned);
+    // A uniform cell list cannot resolve every cloud (tight clusters very far apart exhaust the cell budget):
+    // refuse when the sweep would degenerate into an all-pairs scan of hours rather than run it.
+    if (!level_pass && m_last > 64.0 * es.target && m_last * 27.0 * (double)n_owned > 1e12)
+        return pct_fail(ctx, PCT_ERR_INVALID,
+                        "the cell list cannot resolve this cloud: a point shares its cell with %.0f others on average at the "
+                        "smallest usable cell edge %.3g (%lld cells); thin it out or split it into compact pieces",
+                        m_last, g.cell, (long long)g.ncell);
+    ctx->n_items = tot.y;
+    ctx->nonempty_cells = tot.w;
+    ctx->n_occ = tot.y;
+    ctx->tm.occupied_cells = tot.y;
+    ctx->grid_valid = true;
+    return PCT_OK;
+}
+
 // Chooses the cell edge so that a point shares its cell with about
 // factor*(k+1) points, then counting-sorts the cloud.  With that occupancy the
 // 27-cell stencil (guaranteed radius = one cell edge) contains the k+1 nearest
@@ -1406,345 +1718,98 @@ int pct_build_grid(pct_ctx* ctx, int32_t k, double eps) {
     int64_t cell_cap = (int64_t)1 << 27;
     if (ctx->level_mode) cell_cap = (int64_t)1 << 24;
     else if (32 * ctx->n > cell_cap) cell_cap = 32 * ctx->n < ((int64_t)1 << 30) ? 32 * ctx->n : (int64_t)1 << 30;
-    const float* own_flag = (const float*)ctx->own_flag;   // level passes: ownership by wanted-edge band
+    const bool own_flag = ctx->own_flag != nullptr;        // level passes: ownership by wanted-edge band
     const bool slab = ctx->slab_parts >= 1 && !own_flag;
-    if (slab) PCT_TRY(slab_split(ctx));                    // (sets the owned count: q_begin = 0, q_end = this slab's population)
-    const int64_t n_owned = own_flag ? ctx->own_count : ctx->q_end - ctx->q_begin;
-    const bool sharded = own_flag || ctx->q_begin > 0 || ctx->q_end < ctx->n || slab;   // some points are candidates only
-
-    float bbox[6];
-    PackRed red;
-    Box3 kept_box = {};
-    // (a slab's owned points are found by the pack itself: it always runs, with an open box after a limit retry)
-    const bool try_cull = slab ? n_owned > 0
-                               : !own_flag && sharded && n_owned > 0 && !ctx->has_f64 && !ctx->no_cull && !pct_getenv("PCT_NO_CULL");
-    ctx->tm.grid_iters = 0;
-    // Speculation: a handle fed a stream of similar clouds builds the cell list over the (trimmed) box of the previous
-    // call without waiting for the new bounding box -- any box is a valid grid box, points outside are clamped into
-    // the boundary cells -- and checks the new box at the synchronisation that ends the first pass.  One host round
-    // trip less per build.
-    bool spec = !try_cull && !own_flag && !ctx->level_mode && ctx->hint_edge > 0 && ctx->spec_valid && ctx->spec_n == ctx->n &&
-                !pct_getenv("PCT_NO_SPEC");
-    // later passes of the density-adaptive sweep: the points in the cell order of its first pass, and that pass's box
-    const bool from_base = own_flag && ctx->lvl_src_valid;
-    if (from_base) {
-        for (int a = 0; a < 6; ++a) bbox[a] = ctx->lvl_bbox[a];
-        red = PackRed{};
-        ctx->n_grid = ctx->n;
-        ctx->g_begin = 0;
-        ctx->culled = false;
-    } else
-    if (try_cull) {
-        PCT_TRY(pack_near_owned(ctx, target, bbox, &red, &kept_box));
-        if (ctx->n_grid < (int64_t)k + 1) {
-            // The kept part cannot even fill a row (a few owned rows and a culling box -- possibly a stale one of the
-            // previous cloud -- that holds nobody else): the table would carry "missing" entries that the fused fit,
-            // launched before the limits are checked, must never see without a count array.  Take every point.
-            ctx->no_cull = true;
-            ctx->cull_box_valid = false;
-            return pct_build_grid(ctx, k, eps);
-        }
-        PCT_TRY(trim_box(ctx, red, bbox));
-    } else if (spec) {
-        // no pack pass at all: the histogram reads the caller's rows and takes the cloud's box along (k_hist_raw)
-        PCT_TRY(red_reset(ctx, grid_1d(ctx->n, kBlock, 0), false));
-        ctx->pts4_valid = false;
-        ctx->n_grid = ctx->n;
-        ctx->g_begin = ctx->q_begin;
-        ctx->culled = false;
-        for (int a = 0; a < 6; ++a) bbox[a] = ctx->spec_bbox[a];
-    } else {
-        PCT_TRY(pack_all(ctx, bbox, &red));
-        PCT_TRY(trim_box(ctx, red, bbox));
-    }
-    const bool raw = spec;                                                // (spec is cleared once the box has been checked)
     const bool sub_box = ctx->level_edge > 0 && ctx->level_box_valid;
-    const int64_t n = ctx->n_grid;                                        // points the grid holds
-    const int g_begin = own_flag ? 0 : (int)ctx->g_begin, g_end = own_flag ? 0 : (int)(ctx->g_begin + n_owned);
-
-    double ex = (double)bbox[3] - bbox[0], ey = (double)bbox[4] - bbox[1], ez = (double)bbox[5] - bbox[2];
-    double emax = fmax(ex, fmax(ey, ez));
-    if (!(emax > 0)) emax = 1.0;
-    // first guess: the cloud is a surface whose area is about the bbox's half-surface * 1.2
-    double area = 1.2 * (ex * ey + ey * ez + ex * ez);
-    if (!(area > 0)) area = emax * emax;
-    double a = sqrt(target * area / (double)n);
-    if (!(a > 0) || !isfinite(a)) a = emax;
-    // Warm start: a handle that sees a stream of similar clouds (same scanner, same shard of the same job) reuses
-    // the edge the last build converged to, rescaled by the first-guess ratio, and so normally needs one pass.
-    const double first_guess_raw = a;
-    bool hinted = false;                                  // the first edge comes from the previous cloud on this handle
-    const bool level_pass = ctx->level_edge > 0;          // a later level of the density-adaptive sweep: edge given
-    if (level_pass) {
-        a = ctx->level_edge;
-    } else if (ctx->hint_edge > 0 && ctx->hint_guess > 0) {
-        const double r = first_guess_raw / ctx->hint_guess * sqrt(ctx->hint_target / target);   // guess ~ sqrt(target)
-        if (r > 0.5 && r < 2.0) { a = ctx->hint_edge * r * sqrt(target / ctx->hint_target); hinted = true; }
-    }
-    a = fmin(a, emax * 1.0001 + 1e-30);
-
-    // Which build: the two-level LDS counting sort (k_bin_*) wherever a grid point is owned or not by its public index
-    // alone and every point is binned -- the caller's rows (raw), the full pack, the range-culled pack -- and the bucket
-    // scheme covers the grid (bin_shape, per pass).  The level passes (own_flag, sub_box), the slab-owned handles and
-    // larger grids keep the per-point atomics of k_hist / k_scatter; PCT_GRID_ATOMIC=1 forces those everywhere (A/B runs,
-    // parity tests).
     const bool bin_allowed = !own_flag && !sub_box && !slab && !pct_getenv("PCT_GRID_ATOMIC");
-    PCT_TRY(pct_reserve(ctx, &ctx->cell_of, (size_t)n * sizeof(int)));
-    PCT_TRY(pct_reserve(ctx, &ctx->cell_fill, (size_t)n * sizeof(int)));   // in-cell arrival ranks
     // queries per work item: 16 - 20 measured best for k_knn_pair and k_knn_duo (one staged stencil serves more queries; a
     // cell of ~28 points is one or two items; 1 M torus, k = 50: sweep 0.376 | 0.366 | 0.363 | 0.364 | 0.370 ms at 12 | 14 | 18 |
     // 20 | 24; the reference's lattice torus 0.510 | 0.489 | 0.500 at 12 | 16 | 18; k = 80: 0.597 | 0.574 | 0.583 --
     // tools/items_q_probe.py, tools/lattice_probe.py)
     int items_q = 16;
     if (const char* e = pct_getenv("PCT_ITEMS_Q")) { const int v = atoi(e); if (v >= 1 && v <= 64) items_q = v; }   // tuning aid
-    ctx->items_q = items_q;
-    PCT_TRY(pct_reserve(ctx, &ctx->sorted4, (size_t)n * sizeof(float4)));
-    PCT_TRY(pct_reserve(ctx, &ctx->row_of, (size_t)((own_flag ? n : n_owned) + 1) * sizeof(int)));
-    PCT_TRY(pct_reserve(ctx, &ctx->owned_pos, (size_t)n_owned * sizeof(int)));
-    if (ctx->has_f64) PCT_TRY(pct_reserve(ctx, &ctx->sorted4d, (size_t)n * sizeof(double4)));
-    int nblk = 0;
-    pct_grid g = {};
-    double a_prev = 0, m_prev = 0;
-    int iters = 0;
-    // a level pass takes the edge it is given: its owned set is a mix of densities, and the mean population this
-    // loop steers on would be pulled to the dense minority (pct_levels.hip sizes by the geometric mean instead)
-    const int max_iter = level_pass ? 1 : ctx->level_mode ? 2 : 8;
-    const double win_lo = 0.88, win_hi = 1.12;
-    int4 tot = make_int4(0, 0, 0, 0);
-    double m_last = 0, d_last = 2.0;
-    // Every pass runs the whole build (histogram, scan, scatter) and only then reads back the occupancy statistic
-    // together with the scan totals: the first cell size is accepted in the common case, which then costs ONE host
-    // synchronisation instead of two; a rejected size costs a speculative scatter.
-    for (int it = 0; it < max_iter; ++it) {
-        if (eps > 0 && a > eps * 1.000001) a = eps * 1.000001;   // one ring already covers the eps ball
-        // sub-box of a fast level pass: 2.5 edges of the FINAL cell size around the owned points (their stencils must
-        // end inside the box: the points outside it are left out of the cell list)
-        const auto set_box = [&]() {
-            if (!sub_box) return;
-            for (int ax = 0; ax < 3; ++ax) {
-                bbox[ax] = ctx->level_box[ax] - (float)(2.5 * a);
-                bbox[3 + ax] = ctx->level_box[3 + ax] + (float)(2.5 * a);
+
+    // A restart first rules itself out on the handle (select_source: no culling; below: no speculation), so a build
+    // starts over twice at the most; everything else a restarted build finds in ctx is what any build finds.
+    for (int attempt = 0; attempt < 3; ++attempt) {
+        ctx->tm.grid_iters = 0;
+        if (slab) PCT_TRY(slab_split(ctx));                // (sets the owned count: q_begin = 0, q_end = this slab's population)
+        const int64_t n_owned = own_flag ? ctx->own_count : ctx->q_end - ctx->q_begin;
+        const bool sharded = own_flag || ctx->q_begin > 0 || ctx->q_end < ctx->n || slab;   // some points are candidates only
+        GridPoints s;
+        bool restart = false;
+        PCT_TRY(select_source(ctx, k, target, slab, n_owned, sharded, &s, &restart));
+        if (restart) continue;
+        const int64_t n = s.n;
+        ctx->items_q = items_q;
+        PCT_TRY(reserve_lists(ctx, n, n_owned));
+        EdgeSearch es = edge_search(ctx, s, target, eps);
+        double a = es.first();
+        GridPass p = {};
+        p.src = s.from_base ? (const float4*)ctx->lvl_src.p : (const float4*)ctx->pts4.p;
+        p.n_owned = n_owned; p.sharded = sharded; p.sub_box = sub_box;
+        int iters = 0;
+        int4 tot = make_int4(0, 0, 0, 0);
+        double m_last = 0;
+        // Every pass runs the whole build (histogram, scan, scatter) and only then reads back the occupancy statistic
+        // together with the scan totals: the first cell size is accepted in the common case, which then costs ONE host
+        // synchronisation instead of two; a rejected size costs a speculative scatter.
+        for (int it = 0; it < es.max_iter; ++it) {
+            a = es.clamp_eps(a);
+            size_grid(ctx, sub_box, s.bbox, a, &p.g);
+            // PCT_KNN_AUTO: a surface wants about a third of a cell per point; an edge that asks for 16 cells per point was
+            // steered there by a dense minority (the size-biased occupancy) -- a 1/r^2 scan wants 130 per point, 1.6 ms of
+            // counters and scans that the hierarchical list does not need.  Nothing was built: the caller goes there.
+            if (!own_flag && !(es.level_edge > 0) && p.g.ncell > 16 * n && p.g.ncell > ((int64_t)1 << 20)) {
+                if (it == 0 && es.hinted) {
+                    // ... unless the edge is the PREVIOUS cloud's (same size, similar box, another density -- a torus after
+                    // a 1/r^2 scan inherited its 130 cells per point): this cloud's own first guess, then
+                    a = es.fallback_first();
+                    size_grid(ctx, sub_box, s.bbox, a, &p.g);
+                } else if (ctx->auto_probe) {
+                    ctx->grid_skewed = true;
+                    ctx->grid_valid = false;
+                    return PCT_OK;
+                }
             }
-        };
-        set_box();
-        set_dims(&g, bbox, a);
-        // PCT_KNN_AUTO: a surface wants about a third of a cell per point; an edge that asks for 16 cells per point was
-        // steered there by a dense minority (the size-biased occupancy) -- a 1/r^2 scan wants 130 per point, 1.6 ms of
-        // counters and scans that the hierarchical list does not need.  Nothing was built: the caller goes there.
-        if (!own_flag && !level_pass && g.ncell > 16 * n && g.ncell > ((int64_t)1 << 20)) {
-            if (it == 0 && hinted) {
-                // ... unless the edge is the PREVIOUS cloud's (same size, similar box, another density -- a torus after
-                // a 1/r^2 scan inherited its 130 cells per point): this cloud's own first guess, then
-                hinted = false;
-                a = fmin(first_guess_raw, emax * 1.0001 + 1e-30);
-                set_box();
-                set_dims(&g, bbox, a);
-            } else if (ctx->auto_probe) {
-                ctx->grid_skewed = true;
-                ctx->grid_valid = false;
-                return PCT_OK;
+            bool hit_cap = false;            // the cell budget, not the occupancy target, set this edge
+            while (p.g.ncell > cell_cap) {
+                a *= cbrt((double)p.g.ncell / (double)cell_cap) * 1.01;
+                size_grid(ctx, sub_box, s.bbox, a, &p.g);
+                hit_cap = true;
             }
-        }
-        bool hit_cap = false;            // the cell budget, not the occupancy target, set this edge
-        while (g.ncell > cell_cap) {
-            a *= cbrt((double)g.ncell / (double)cell_cap) * 1.01;
-            set_box();
-            set_dims(&g, bbox, a);
-            hit_cap = true;
-        }
-        const BinShape bs = bin_allowed ? bin_shape(n, g.ncell, sharded) : BinShape{};
-        const bool bin = bs.ok;
-        // (the bin build writes every counter itself: no clearing fill)
-        PCT_TRY(pct_reserve(ctx, &ctx->cell_own, (size_t)g.ncell * sizeof(int)));
-        if (!bin) PCT_HIP(ctx, hipMemsetAsync(ctx->cell_own.p, 0, (size_t)g.ncell * sizeof(int), ctx->stream));
-        if (sharded) {
-            PCT_TRY(pct_reserve(ctx, &ctx->cell_oth, (size_t)g.ncell * sizeof(int)));
-            if (!bin) PCT_HIP(ctx, hipMemsetAsync(ctx->cell_oth.p, 0, (size_t)g.ncell * sizeof(int), ctx->stream));
-        }
-        const float4* src = from_base ? (const float4*)ctx->lvl_src.p : (const float4*)ctx->pts4.p;
-        int* bin_plan = nullptr;
-        int4* bin_items = nullptr;
-        const size_t bin_lds = (size_t)(bs.cls << bs.shift) * sizeof(int);
-        if (bin) {
-            // scratch of this pass (sized by its grid): bucket-partitioned records, [tile][bucket] matrix, plan words +
-            // bucket starts + column totals + work list, run offsets of the shared buckets' items
-            PCT_TRY(pct_reserve(ctx, &ctx->bin_rec, (size_t)n * sizeof(float4)));
-            PCT_TRY(pct_reserve(ctx, &ctx->bin_mat, (size_t)bs.ntiles * bs.nb * sizeof(unsigned)));
-            const size_t plan_words = 16 + (size_t)(bs.nb + 1) + (size_t)bs.nb;
-            const size_t items_at = (plan_words * sizeof(int) + 15) / 16 * 16;
-            PCT_TRY(pct_reserve(ctx, &ctx->bin_plan, items_at + (size_t)bs.max_items * sizeof(int4)));
-            PCT_TRY(pct_reserve(ctx, &ctx->bin_base, (size_t)bs.max_shared * (bs.cls << bs.shift) * sizeof(int)));
-            bin_plan = (int*)ctx->bin_plan.p;
-            unsigned* bin_tot = (unsigned*)(bin_plan + 16 + bs.nb + 1);
-            bin_items = (int4*)((char*)ctx->bin_plan.p + items_at);
-            PackRed* parts = spec ? red_parts(ctx) : nullptr;
-#define PCT_BIN_SRC(K, ...) do { if (raw) PCT_LAUNCH(K<true>, __VA_ARGS__); else PCT_LAUNCH(K<false>, __VA_ARGS__); } while (0)
-            PCT_BIN_SRC(k_bin_count, dim3(bs.ntiles), dim3(kBinWide), 0, ctx->stream, ctx->xyz_view, src, n, bs.tile_rows, g, bs.shift, bs.nb,
-                        (unsigned*)ctx->bin_mat.p, parts);
-            PCT_LAUNCH(k_bin_colscan, dim3((bs.nb + kBinScanCols - 1) / kBinScanCols), dim3(kBinScanCols * kBinScanGroups), 0, ctx->stream, (unsigned*)ctx->bin_mat.p, bs.ntiles, bs.nb, bin_tot);
-            PCT_LAUNCH(k_bin_plan, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned*)bin_tot, bs.nb, bs.chunk, bin_plan, bin_items);
-            PCT_BIN_SRC(k_bin_scatter, dim3(bs.ntiles), dim3(kBinWide), 0, ctx->stream, ctx->xyz_view, src, n, bs.tile_rows, g, bs.shift, bs.nb,
-                        bs.chunk, (const unsigned*)ctx->bin_mat.p, (const int*)bin_plan, (float4*)ctx->bin_rec.p, (int*)ctx->cell_own.p,
-                        sharded ? (int*)ctx->cell_oth.p : nullptr);
-#undef PCT_BIN_SRC
-            PCT_LAUNCH(k_bin_cells, dim3(bs.max_items + 1), dim3(kBinBlock), bin_lds, ctx->stream, (const float4*)ctx->bin_rec.p, (const int*)bin_plan,
-                       (const int4*)bin_items, g, bs.shift, (int)ctx->q_begin, (int)ctx->q_end, (int*)ctx->cell_own.p,
-                       sharded ? (int*)ctx->cell_oth.p : nullptr, (int*)ctx->bin_base.p, (const PackRed*)parts, bs.ntiles,
-                       (PackRed*)ctx->red.p, pin_red(ctx));
-        } else
-        if (raw) {
-            const int nhb = grid_1d(n, kBlock, 0);
-            PCT_LAUNCH(k_hist_raw, dim3(nhb), dim3(kBlock), 0, ctx->stream, ctx->xyz_view, n, g, g_begin, g_end, (int*)ctx->cell_of.p,
-                       (int*)ctx->cell_fill.p, (int*)ctx->cell_own.p, sharded ? (int*)ctx->cell_oth.p : nullptr, spec ? red_parts(ctx) : nullptr);
-            if (spec) PCT_TRY(red_fold(ctx, nhb, false));
-        } else
-        if (from_base)
-            PCT_LAUNCH(k_hist_agg, dim3(grid_1d(n, kBlock, 0)), dim3(kBlock), 0, ctx->stream, src, n, g, own_flag, ctx->own_lo,
-                               ctx->own_hi, sub_box ? 1 : 0, (int*)ctx->cell_of.p, (int*)ctx->cell_fill.p, (int*)ctx->cell_own.p,
-                               (int*)ctx->cell_oth.p);
-        else
-        PCT_LAUNCH(k_hist, dim3(grid_1d(n, kBlock, 0)), dim3(kBlock), 0, ctx->stream,
-                           src, n, g, g_begin, g_end, own_flag, ctx->own_lo, ctx->own_hi, sub_box ? 1 : 0, (int*)ctx->cell_of.p,
-                           (int*)ctx->cell_fill.p, (int*)ctx->cell_own.p, sharded ? (int*)ctx->cell_oth.p : nullptr);
-        nblk = (int)((g.ncell + kScanTile - 1) / kScanTile);
-        if (pct_getenv("PCT_GRID_DEBUG"))
-            fprintf(stderr, "[grid] pass %d: n %lld owned %lld edge %g dims %d x %d x %d = %lld cells (%d scan tiles), box [%g %g %g]-[%g %g %g]\n", it,
-                    (long long)n, (long long)n_owned, a, g.nx, g.ny, g.nz, (long long)g.ncell, nblk, bbox[0], bbox[1], bbox[2], bbox[3], bbox[4], bbox[5]);
-        PCT_TRY(pct_reserve(ctx, &ctx->scan_tmp, (size_t)(nblk + 1) * sizeof(int4) + (size_t)nblk * sizeof(unsigned long long)));
-        unsigned long long* sq_part = (unsigned long long*)((int4*)ctx->scan_tmp.p + nblk + 1);
-        PCT_TRY(pct_reserve(ctx, &ctx->cell_cnt, (size_t)(g.ncell + 1) * sizeof(int)));
-        PCT_TRY(pct_reserve(ctx, &ctx->own_start, (size_t)(g.ncell + 1) * sizeof(int)));
-        PCT_TRY(pct_reserve(ctx, &ctx->occ, ((size_t)(n_owned < g.ncell ? n_owned : g.ncell) + (size_t)n_owned / items_q + 16) * sizeof(int2)));
-        PCT_LAUNCH(k_scan_sums, dim3(nblk), dim3(kBlock), 0, ctx->stream,
-                           (const int*)ctx->cell_own.p, sharded ? (const int*)ctx->cell_oth.p : nullptr, g.ncell, items_q,
-                           (int4*)ctx->scan_tmp.p, sq_part);
-        PCT_TRY(pct_reserve(ctx, &ctx->counters, sizeof(pct_dev_words)));
-        PCT_LAUNCH(k_scan_tiles, dim3(1), dim3(1024), 0, ctx->stream, (int4*)ctx->scan_tmp.p, nblk,
-                           (const unsigned long long*)sq_part, pin_totals(ctx), (unsigned long long*)&pct_dev(ctx)->sweep);
-        ctx->counters_clean = true;
-        // the totals this pass is judged by (and, with a deferred pack, the cloud's box) are in pinned memory from here on:
-        // the host waits for THIS point, not for the end of the stream -- while it wakes up, decides and enqueues the
-        // sweep, the device applies the scan and scatters the records (50 us at 1 M points; the read-back used to be ~25
-        // us of an idle device).  A pass that is rejected has scattered for nothing, as before.
-        PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_SCAN_TOTALS], ctx->stream));
-        PCT_LAUNCH(k_scan_apply, dim3(nblk), dim3(kBlock), 0, ctx->stream,
-                           (const int*)ctx->cell_own.p, sharded ? (const int*)ctx->cell_oth.p : nullptr, g.ncell, items_q,
-                           (const int4*)ctx->scan_tmp.p, (int*)ctx->cell_cnt.p, (int*)ctx->own_start.p, (int2*)ctx->occ.p);
-        // (the chained sweep's passes read each other's lists: its first pass keeps row_of complete)
-        const bool lazy_rows = bin && !ctx->level_mode;
-        ctx->row_of_valid = !lazy_rows;
-        ctx->row_of_rows = n_owned;
-        ctx->row_of_begin = (int)ctx->q_begin;
-        if (bin)
-            PCT_LAUNCH(k_bin_place, dim3(bs.max_items), dim3(kBinBlock), bin_lds + (sharded ? bin_lds / 2 : 0), ctx->stream,
-                       (const float4*)ctx->bin_rec.p, (const int*)bin_plan, (const int4*)bin_items, g, bs.shift, (int)ctx->q_begin,
-                       (int)ctx->q_end, n, n_owned, (const int*)ctx->cell_cnt.p, (const int*)ctx->cell_own.p,
-                       sharded ? (const int*)ctx->cell_oth.p : nullptr, (const int*)ctx->own_start.p, (const int*)ctx->bin_base.p,
-                       (float4*)ctx->sorted4.p, lazy_rows ? nullptr : (int*)ctx->row_of.p, (int*)ctx->owned_pos.p,
-                       ctx->has_f64 ? (const double4*)ctx->pts4d.p : nullptr, ctx->has_f64 ? (double4*)ctx->sorted4d.p : nullptr);
-        else if (raw)
-            PCT_LAUNCH(k_scatter_raw, dim3(grid_1d(n, kBlock, 0)), dim3(kBlock), 0, ctx->stream, ctx->xyz_view, (const int*)ctx->cell_of.p,
-                       (const int*)ctx->cell_cnt.p, (const int*)ctx->cell_own.p, (const int*)ctx->own_start.p, (const int*)ctx->cell_fill.p, n,
-                       g_begin, (float4*)ctx->sorted4.p, (int*)ctx->row_of.p, (int*)ctx->owned_pos.p,
-                       ctx->has_f64 ? (const double4*)ctx->pts4d.p : nullptr, ctx->has_f64 ? (double4*)ctx->sorted4d.p : nullptr);
-        else
-        PCT_LAUNCH(k_scatter, dim3(grid_1d(n, kBlock, 0)), dim3(kBlock), 0, ctx->stream,
-                           src, (const int*)ctx->cell_of.p, (const int*)ctx->cell_cnt.p,
-                           (const int*)ctx->cell_own.p, (const int*)ctx->own_start.p, (const int*)ctx->cell_fill.p, n,
-                           g_begin, (float4*)ctx->sorted4.p, (int*)ctx->row_of.p, (int*)ctx->owned_pos.p,
-                           ctx->has_f64 ? (const double4*)ctx->pts4d.p : nullptr,
-                           ctx->has_f64 ? (double4*)ctx->sorted4d.p : nullptr);
-        PCT_HIP(ctx, hipGetLastError());
-        PCT_HIP(ctx, hipEventSynchronize(ctx->ev[PCT_EV_SCAN_TOTALS]));
-        if (spec) {                      // the deferred pack result is in: was the old box still right?
-            spec = false;
-            memcpy(&red, pin_red(ctx), sizeof(red));
-            if (red.bad) return pct_fail(ctx, PCT_ERR_NONFINITE, "Non-finite values in input points");
-            bool same = true;
-            for (int ax = 0; ax < 3; ++ax) {
-                const float lo = order_float(red.bb[ax]), hi = order_float(red.bb[3 + ax]);
-                const float tol = 0.02f * (ctx->spec_raw[3 + ax] - ctx->spec_raw[ax]) + 1e-30f;
-                same = same && fabsf(lo - ctx->spec_raw[ax]) <= tol && fabsf(hi - ctx->spec_raw[3 + ax]) <= tol;
+            const pct_grid& g = p.g;
+            p.bs = bin_allowed ? bin_shape(n, g.ncell, sharded) : BinShape{};
+            p.build = choose_build(bin_allowed, p.bs, s);
+            const bool bin = p.build == GridBuild::Bin;
+            PCT_TRY(launch_count(ctx, s, p));
+            const int nblk = (int)((g.ncell + kScanTile - 1) / kScanTile);
+            if (pct_getenv("PCT_GRID_DEBUG"))
+                fprintf(stderr, "[grid] pass %d: n %lld owned %lld edge %g dims %d x %d x %d = %lld cells (%d scan tiles), box [%g %g %g]-[%g %g %g]\n", it,
+                        (long long)n, (long long)n_owned, a, g.nx, g.ny, g.nz, (long long)g.ncell, nblk, s.bbox[0], s.bbox[1], s.bbox[2], s.bbox[3], s.bbox[4], s.bbox[5]);
+            PCT_TRY(launch_scan(ctx, p, items_q, nblk));
+            PCT_TRY(launch_place(ctx, s, p));
+            PCT_HIP(ctx, hipEventSynchronize(ctx->ev[PCT_EV_SCAN_TOTALS]));
+            if (s.deferred_box) {
+                const BoxCheck box = check_deferred_box(ctx, &s);
+                if (box == BoxCheck::NonFinite) return pct_fail(ctx, PCT_ERR_NONFINITE, "Non-finite values in input points");
+                if (box == BoxCheck::Restart) {          // a different cloud: start over the regular way
+                    ctx->spec_valid = false;
+                    restart = true;
+                    break;
+                }
             }
-            if (!same) {                 // a different cloud: start over the regular way
-                ctx->spec_valid = false;
-                return pct_build_grid(ctx, k, eps);
-            }
+            if (bin && pct_getenv("PCT_GRID_DEBUG")) PCT_TRY(debug_bin_plan(ctx, p));
+            tot = pin_totals(ctx)->tot;
+            m_last = (double)pin_totals(ctx)->sumsq / (double)(n_owned > 0 ? n_owned : 1);
+            ++iters;
+            if (es.accept(m_last, a, g.ncell, cell_cap, hit_cap, it)) break;
+            a = es.next(m_last, a);
         }
-        if (bin && pct_getenv("PCT_GRID_DEBUG")) {          // (debugging only: waits for the stream)
-            int pw[3] = {0, 0, 0};
-            PCT_HIP(ctx, hipMemcpyAsync(pw, bin_plan, sizeof(pw), hipMemcpyDeviceToHost, ctx->stream));
-            PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            fprintf(stderr, "[grid] bin build: %d buckets of %d cells, %d tiles of %d rows, %d work items of up to %d records, %d of them in %d shared buckets\n",
-                    bs.nb, 1 << bs.shift, bs.ntiles, bs.tile_rows, pw[0], bs.chunk, pw[1], pw[2]);
-        }
-        const unsigned long long s2 = pin_totals(ctx)->sumsq;
-        tot = pin_totals(ctx)->tot;
-        ++iters;
-        double m = (double)s2 / (double)(n_owned > 0 ? n_owned : 1);
-        m_last = m;
-        bool eps_bound = eps > 0 && a >= eps;            // cannot grow past eps
-        bool capped = g.ncell * 2 > cell_cap && m < target;
-        if ((m >= win_lo * target && m <= win_hi * target) || it == max_iter - 1 || (eps_bound && m < target) ||
-            capped || (a >= emax && m < target) || (hit_cap && m > target))      // (cannot refine past the cell budget)
-            break;
-        double d = 2.0;
-        if (a_prev > 0 && m != m_prev && a != a_prev) {
-            d = log(m / m_prev) / log(a / a_prev);
-            if (!(d >= 1.0)) d = 1.0;
-            if (d > 3.0) d = 3.0;
-        }
-        a_prev = a;
-        m_prev = m;
-        d_last = d;
-        double f = pow(target / m, 1.0 / d);
-        f = fmin(fmax(f, 1.0 / 16.0), 16.0);
-        a = fmin(a * f, emax * 1.0001 + 1e-30);
+        if (restart) continue;
+        return commit_grid(ctx, s, p.g, es, iters, m_last, tot, n_owned, sub_box);
     }
-    // faces of the culling box become limits of what the grid can vouch for (cell units from the origin)
-    for (int ax = 0; ax < 3; ++ax) {
-        const double o = ax == 0 ? g.ox : ax == 1 ? g.oy : g.oz;
-        g.lim_lo[ax] = ctx->culled ? ((double)kept_box.lo[ax] - o) * g.inv_cell : -INFINITY;
-        g.lim_hi[ax] = ctx->culled ? ((double)kept_box.hi[ax] - o) * g.inv_cell : INFINITY;
-    }
-    if (pct_getenv("PCT_GRID_DEBUG"))
-        fprintf(stderr, "[grid] box [%g %g %g]-[%g %g %g] edge %g dims %d x %d x %d = %lld cells, %d passes, occupancy %.1f, items %d\n", bbox[0],
-                bbox[1], bbox[2], bbox[3], bbox[4], bbox[5], g.cell, g.nx, g.ny, g.nz, (long long)g.ncell, iters, m_last, tot.y);
-    if (ctx->level_mode && !own_flag)                    // first pass of a density-adaptive sweep: its (trimmed) box serves the later ones
-        for (int a2 = 0; a2 < 6; ++a2) ctx->lvl_bbox[a2] = bbox[a2];
-    ctx->grid = g;
-    ctx->tm.grid_iters += iters;
-    ctx->tm.cells = g.ncell;
-    ctx->tm.cell_size = g.cell;
-    ctx->tm.grid_points = n;
-    ctx->tm.occupancy = m_last;
-    if (!try_cull && !own_flag && !ctx->level_mode) {       // remember the box for the next similar cloud
-        for (int a2 = 0; a2 < 6; ++a2) ctx->spec_bbox[a2] = bbox[a2];
-        if (red.cnt > 0)                  // raw bounding box of this cloud (before trimming)
-            for (int a2 = 0; a2 < 6; ++a2) ctx->spec_raw[a2] = order_float(red.bb[a2]);
-        ctx->spec_n = ctx->n;
-        ctx->spec_valid = true;
-    }
-    if (m_last > 0 && !level_pass) {        // what the heuristic first guess should have been for this cloud
-        ctx->hint_edge = g.cell * pow(target / m_last, 1.0 / d_last);
-        ctx->hint_guess = first_guess_raw;
-        ctx->hint_target = target;
-    }
-    if ((tot.x != n && !sub_box) || tot.x > n || tot.z != n_owned)
-        return pct_fail(ctx, PCT_ERR_INVALID, "cell scan totals %d/%d != %lld/%lld", tot.x, tot.z, (long long)n, (long long)n_owned);
-    // A uniform cell list cannot resolve every cloud (tight clusters very far apart exhaust the cell budget):
-    // refuse when the sweep would degenerate into an all-pairs scan of hours rather than run it.
-    if (!level_pass && m_last > 64.0 * target && m_last * 27.0 * (double)n_owned > 1e12)
-        return pct_fail(ctx, PCT_ERR_INVALID,
-                        "the cell list cannot resolve this cloud: a point shares its cell with %.0f others on average at the "
-                        "smallest usable cell edge %.3g (%lld cells); thin it out or split it into compact pieces",
-                        m_last, g.cell, (long long)g.ncell);
-    ctx->n_items = tot.y;
-    ctx->nonempty_cells = tot.w;
-    ctx->n_occ = tot.y;
-    ctx->tm.occupied_cells = tot.y;
-    ctx->grid_valid = true;
-    return PCT_OK;
+    return pct_fail(ctx, PCT_ERR_INVALID, "cell-list build: restarted more than twice");
 }
 
 // Every reader of ctx->row_of calls this first (pct_get_fit's gather, the row export, the neighbour study).

@@ -1,0 +1,200 @@
+"""The cell-size controller and the counting sort's sizing rule (csrc/pct_grid_edge.h), on the CPU.
+
+A stand-alone program that includes nothing but that header drives EdgeSearch with occupancy models m = c * a^d and prints
+what it did; every expectation below is worked out from the rule (*Cell size* and *Sizing*) and written out
+here, not recomputed from the header."""
+import math
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "point-cloud-toolbox_amd", "csrc")
+
+PROGRAM = r"""
+#include "pct_grid_edge.h"
+#include <stdio.h>
+
+static EdgeSearch search(double target, double eps, double extent) {
+    EdgeSearch es = {};
+    es.target = target; es.n = 36000; es.ex = es.ey = es.ez = extent; es.eps = eps; es.max_iter = 8;
+    es.first();
+    return es;
+}
+
+// the loop of pct_build_grid on the model m = a^d, from edge a0 (a* = target^(1/d) is the answer)
+static void model(const char* name, double target, double d, double off, double eps_rel) {
+    const double a_star = pow(target, 1.0 / d);
+    EdgeSearch es = search(target, eps_rel * a_star, 1e6);
+    double a = off * a_star, m = 0;
+    int it = 0;
+    for (; it < es.max_iter; ++it) {
+        a = es.clamp_eps(a);
+        m = pow(a, d);
+        printf("%s_%g_a%d %.17g\n", name, target, it, a / a_star);
+        if (es.accept(m, a, 1, (int64_t)1 << 27, false, it)) break;
+        a = es.next(m, a);
+    }
+    printf("%s_%g_passes %d\n%s_%g_m %.17g\n%s_%g_d %.17g\n", name, target, it + 1, name, target, m / target, name, target, es.d_last);
+    if (eps_rel > 0) printf("%s_%g_over_eps %.17g\n%s_%g_within %d\n", name, target, a / (eps_rel * a_star), name, target, (int)(a <= eps_rel * a_star * 1.000001));
+}
+
+static void warm(const char* name, double r, double hint_target, double level_edge) {
+    EdgeSearch es = {};
+    es.target = 27; es.n = 36000; es.ex = es.ey = es.ez = 1; es.max_iter = 8;
+    es.first();
+    const double g0 = es.first_guess;           // (so that r = 0.5 and r = 2 below are met exactly)
+    es.hint_edge = 0.04; es.hint_guess = g0 / r; es.hint_target = hint_target; es.level_edge = level_edge;
+    const double a = es.first();
+    printf("%s %.17g\n%s_hinted %d\n%s_guess %.17g\n", name, a, name, (int)es.hinted, name, es.first_guess);
+    const double back = es.fallback_first();
+    printf("%s_fallback %.17g\n%s_fallback_hinted %d\n", name, back, name, (int)es.hinted);
+}
+
+static void shape(const char* name, int64_t n, int64_t ncell, bool sharded) {
+    const BinShape s = bin_shape(n, ncell, sharded);
+    printf("%s_ok %d\n", name, (int)s.ok);
+    if (s.ok) printf("%s_shift %d\n%s_nb %d\n%s_tile_rows %d\n%s_ntiles %d\n%s_chunk %d\n", name, s.shift, name, s.nb, name, s.tile_rows,
+                     name, s.ntiles, name, s.chunk);
+}
+
+int main() {
+    const double targets[2] = {27.0, 29.5};
+    for (double target : targets) {
+        model("d2", target, 2, 1.5, 0);
+        model("d3", target, 3, 1.5, 0);
+        model("d1", target, 1, 1.5, 0);
+        model("dhalf", target, 0.5, 1.5, 0);
+        model("d4", target, 4, 1.5, 0);
+        model("far_above", target, 2, 100, 0);
+        model("far_below", target, 2, 0.01, 0);
+        model("eps", target, 2, 1.5, 0.5);
+        const EdgeSearch box = search(target, 0, 1);          // emax = 1
+        const int64_t cap = (int64_t)1 << 27;
+        printf("at_emax_%g %d\n", target, (int)box.accept(0.5 * target, 1.0, 1, cap, false, 0));
+        printf("below_emax_%g %d\n", target, (int)box.accept(0.5 * target, 0.99, 1, cap, false, 0));
+        printf("hit_cap_%g %d\n", target, (int)box.accept(2 * target, 0.5, 1, cap, true, 0));
+        printf("no_hit_cap_%g %d\n", target, (int)box.accept(2 * target, 0.5, 1, cap, false, 0));
+        printf("hit_cap_low_%g %d\n", target, (int)box.accept(0.5 * target, 0.5, 1, cap, true, 0));
+        printf("half_budget_%g %d\n", target, (int)box.accept(0.5 * target, 0.5, cap / 2 + 1, cap, false, 0));
+        printf("last_pass_%g %d\n", target, (int)box.accept(100 * target, 0.5, 1, cap, false, 7));
+        printf("not_last_pass_%g %d\n", target, (int)box.accept(100 * target, 0.5, 1, cap, false, 6));
+        printf("window_lo_%g %d\n", target, (int)box.accept(0.89 * target, 0.5, 1, cap, false, 0));
+        printf("window_hi_%g %d\n", target, (int)box.accept(1.13 * target, 0.5, 1, cap, false, 0));
+        printf("hint_after_%g %.17g\n", target, box.hint_after(0.05, 30.0));
+    }
+    warm("r075", 0.75, 27, 0);
+    warm("r15_other_target", 1.5, 29.5, 0);
+    warm("r05", 0.5, 27, 0);
+    warm("r20", 2.0, 27, 0);
+    warm("r04", 0.4, 27, 0);
+    warm("r25", 2.5, 27, 0);
+    warm("level", 0.75, 27, 0.123);
+    shape("m1", 1000000, 700000, false);
+    shape("m5", 5000000, 6900000, false);
+    shape("m5_sharded", 5000000, 6900000, true);
+    shape("huge_grid", 5000000, 48000000, false);
+    shape("one", 1, 1, false);
+    shape("n_max", ((int64_t)1 << 31) - 4096, 700000, false);
+    shape("n_below_max", ((int64_t)1 << 31) - 4097, 700000, false);
+    return 0;
+}
+"""
+
+
+@pytest.fixture(scope="module")
+def out(tmp_path_factory):
+    cxx = shutil.which(os.environ.get("CXX", "g++")) or shutil.which("c++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    d = tmp_path_factory.mktemp("grid_edge")
+    src, exe = d / "edge.cpp", d / "edge"
+    src.write_text(PROGRAM)
+    subprocess.run([cxx, "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-Werror", "-I", CSRC, str(src), "-o", str(exe), "-lm"], check=True)
+    text = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
+    return {k: float(v) for k, v in (ln.split() for ln in text.splitlines())}
+
+
+def test_header_includes_the_c_library_only():
+    with open(os.path.join(CSRC, "pct_grid_edge.h")) as f:
+        includes = [ln.split()[1] for ln in f if ln.startswith("#include")]
+    assert sorted(includes) == ["<math.h>", "<stdint.h>"]
+
+
+TARGETS = ["27", "29.5"]
+close = lambda x, y: math.isclose(x, y, rel_tol=1e-12)       # pow and log are not correctly rounded: a few ulp
+
+
+@pytest.mark.parametrize("t", TARGETS)
+def test_surface_lands_on_the_second_pass(out, t):
+    """m ~ a^2, 1.5 x off: m = 2.25 target is rejected; with no previous pass the step takes d = 2, exact here."""
+    assert out[f"d2_{t}_passes"] == 2
+    assert out[f"d2_{t}_a0"] == pytest.approx(1.5, rel=1e-12) and close(out[f"d2_{t}_a1"], 1.0) and close(out[f"d2_{t}_m"], 1.0)
+
+
+@pytest.mark.parametrize("t", TARGETS)
+def test_other_dimensions_land_on_the_third_pass(out, t):
+    """The second pass still steps with d = 2; the third with the measured exponent."""
+    # d = 3: m0 = 1.5^3 target, a1 = a0 / sqrt(1.5^3); m1 = 1.5^-1.5 target = 0.544: rejected; then d = 3 is exact
+    assert out[f"d3_{t}_passes"] == 3 and close(out[f"d3_{t}_a1"], 1.5 / math.sqrt(3.375)) and close(out[f"d3_{t}_a2"], 1.0)
+    assert close(out[f"d3_{t}_d"], 3.0)
+    # d = 1: m0 = 1.5 target, a1 = a0 / sqrt(1.5); m1 = 1.2247 target: rejected; then d = 1 is exact
+    assert out[f"d1_{t}_passes"] == 3 and close(out[f"d1_{t}_a1"], math.sqrt(1.5)) and close(out[f"d1_{t}_a2"], 1.0)
+    assert close(out[f"d1_{t}_d"], 1.0)
+
+
+@pytest.mark.parametrize("t", TARGETS)
+def test_measured_exponent_is_clamped(out, t):
+    # d = 0.5 (a* = target^2): m0 = 1.5^(1/2) t, a1 = a0 * 1.5^(-1/4), m1 = 1.5^(3/8) t = 1.164 t: rejected; the measured 0.5
+    # becomes 1: a2 = a1 * 1.5^(-3/8) = 1.5^(3/8) a*  (unclamped it would have been a* itself)
+    assert close(out[f"dhalf_{t}_a1"], 1.5 ** 0.75) and close(out[f"dhalf_{t}_a2"], 1.5 ** 0.375)
+    # d = 4: m0 = 1.5^4 t, a1 = a0 / 1.5^2 = a* / 1.5, m1 = 1.5^-4 t; the measured 4 becomes 3: a2 = a1 * 1.5^(4/3) = 1.5^(1/3) a*
+    assert close(out[f"d4_{t}_a1"], 1.0 / 1.5) and close(out[f"d4_{t}_a2"], 1.5 ** (1.0 / 3.0))
+    # (1.5^(3/16) target = 1.079 target is inside the window; 1.5^(4/3) target is not)
+    assert out[f"dhalf_{t}_passes"] == 3 and out[f"dhalf_{t}_d"] == 1.0 and out[f"d4_{t}_passes"] > 3 and out[f"d4_{t}_d"] == 3.0
+
+
+@pytest.mark.parametrize("t", TARGETS)
+def test_step_is_clamped_to_a_factor_of_16(out, t):
+    assert close(out[f"far_above_{t}_a1"], 100.0 / 16.0) and close(out[f"far_below_{t}_a1"], 0.16)
+
+
+@pytest.mark.parametrize("t", TARGETS)
+def test_eps_bounds_the_edge(out, t):
+    """eps = a* / 2: the edge is eps * 1.000001 at once, m = target / 4 there, and that is accepted (eps_bound)."""
+    assert out[f"eps_{t}_passes"] == 1 and out[f"eps_{t}_within"] == 1 and close(out[f"eps_{t}_over_eps"], 1.000001)
+    assert close(out[f"eps_{t}_m"], 0.25 * 1.000001 ** 2)
+
+
+@pytest.mark.parametrize("t", ["27", "29.5"])
+def test_accept_conditions(out, t):
+    assert out[f"at_emax_{t}"] == 1 and out[f"below_emax_{t}"] == 0              # a >= emax with m < target
+    assert out[f"hit_cap_{t}"] == 1 and out[f"no_hit_cap_{t}"] == 0 and out[f"hit_cap_low_{t}"] == 0     # hit_cap with m > target
+    assert out[f"half_budget_{t}"] == 1                                          # more than half the cell budget, m < target
+    assert out[f"last_pass_{t}"] == 1 and out[f"not_last_pass_{t}"] == 0         # it == max_iter - 1, whatever m
+    assert out[f"window_lo_{t}"] == 1 and out[f"window_hi_{t}"] == 0             # 0.88 .. 1.12 of target
+    assert close(out[f"hint_after_{t}"], 0.05 * math.sqrt(float(t) / 30.0))      # no step taken: d = 2
+
+
+def test_warm_start(out):
+    g0 = math.sqrt(27 * 3.6 / 36000)             # unit box: half-surface 3 * 1.2, 36000 points
+    for name in ("r075", "r15_other_target", "r05", "r20", "r04", "r25", "level"):
+        assert close(out[name + "_guess"], g0)
+        assert close(out[name + "_fallback"], g0) and out[name + "_fallback_hinted"] == 0
+    assert out["r075_hinted"] == 1 and close(out["r075"], 0.04 * 0.75)
+    # another target on the previous call: r = 1.5 * sqrt(29.5 / 27) = 1.568, the edge hint * r * sqrt(27 / 29.5) = hint * 1.5
+    assert out["r15_other_target_hinted"] == 1 and close(out["r15_other_target"], 0.04 * (1.5 * math.sqrt(29.5 / 27)) * math.sqrt(27 / 29.5))
+    for name in ("r05", "r20", "r04", "r25"):    # the interval is open
+        assert out[name + "_hinted"] == 0 and close(out[name], g0), name
+    assert out["level"] == 0.123 and out["level_hinted"] == 0
+
+
+def test_bin_shape(out):
+    got = lambda name: tuple(int(out[f"{name}_{f}"]) for f in ("ok", "shift", "nb", "tile_rows", "ntiles", "chunk"))
+    assert got("m1") == (1, 10, 684, 4096, 245, 4096)
+    assert got("m5") == (1, 13, 843, 8192, 611, 8192)
+    assert got("m5_sharded") == (1, 12, 1685, 8192, 611, 8192)       # two classes: 2 * 2^12 fine counters
+    assert out["huge_grid_ok"] == 0                                  # 48 M cells / 2^13 = 5860 buckets > 4096
+    assert got("one") == (1, 8, 1, 4096, 1, 4096)
+    assert out["n_max_ok"] == 0 and out["n_below_max_ok"] == 1
