@@ -1,6 +1,7 @@
 // C ABI of the curvature path (include/pct_hip.h).  Host-side orchestration
 // only: buffer ownership, launch order, hipEvent timing, status mapping.
 #include "pct_internal.h"
+#include "pct_auto_route.h"
 
 #include <execinfo.h>
 #include <math.h>
@@ -443,30 +444,93 @@ int pct_set_stats(pct_ctx* ctx, int32_t enable) {
     return PCT_OK;
 }
 
-// neighbour sweep without timing bookkeeping; events 2..4 bracket grid / sweep
-static int run_knn(pct_ctx* ctx, int32_t k, double eps, int32_t algo, bool fuse_fit = false) {
-    ctx->levels_fitted = false;
-    ctx->skip_dist_req = fuse_fit;
+// ---- the sweep of a call: which structure serves it (the rules: pct_auto_route.h), built and swept ---------------------
+struct SweepDone { bool rows_fitted = false; };     // the passes of a chained sweep fitted the rows they answered: no fit is left to launch
+
+// The chain of cell lists.  fuse_par: every pass fits its rows, into the pinned slots of this parity (null: no fits).
+static int sweep_levels(pct_ctx* ctx, int32_t k, double eps, const int* fuse_par, SweepDone* done) {
+    ctx->tm.algo = PCT_KNN_GRID_LEVELS;
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_GRID_END], ctx->stream));
+    PCT_TRY(pct_knn_levels(ctx, k, eps, fuse_par));
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FAST_END], ctx->stream));
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_SWEEP_END], ctx->stream));
+    ctx->tm.knn_launches = ctx->tm.levels;
+    ctx->knn_valid = true;
+    done->rows_fitted = fuse_par != nullptr;
+    return PCT_OK;
+}
+
+// The hierarchical cell list of a whole cloud.  *verdict: Built -- swept; Unusable (extents or eps outside what the float32
+// pre-selection can square) -- the chain of cell lists swept instead; OtherCloud (expect_bbox: the box a remembered
+// verdict was given for, null: any cloud) -- nothing built or swept, the caller goes on.
+static int sweep_tree(pct_ctx* ctx, int32_t k, double eps, bool want_dist, const float* expect_bbox, const int* fuse_par, SweepDone* done,
+                      TreeVerdict* verdict) {
+    ctx->tm.algo = PCT_KNN_TREE;
+    PCT_TRY(pct_build_tree(ctx, k, eps, expect_bbox, verdict));
+    if (*verdict == TreeVerdict::OtherCloud) return PCT_OK;
+    if (*verdict == TreeVerdict::Unusable) return sweep_levels(ctx, k, eps, fuse_par, done);
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_GRID_END], ctx->stream));
+    PCT_TRY(pct_launch_knn_tree(ctx, k, eps, want_dist));
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_SWEEP_END], ctx->stream));
+    ctx->tm.knn_launches = 1;
+    ctx->knn_valid = true;
+    return PCT_OK;
+}
+
+// The exhaustive sweep: no cell list, the packed cloud
+static int sweep_brute(pct_ctx* ctx, int32_t k, double eps) {
+    float bbox[6];
+    PCT_TRY(pct_pack_points(ctx, bbox));
+    ctx->tm.grid_iters = 0;
+    ctx->tm.cells = ctx->tm.occupied_cells = 0;
+    ctx->tm.grid_points = ctx->n;
+    ctx->tm.cell_size = 0;
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_GRID_END], ctx->stream));
+    PCT_TRY(pct_launch_knn_brute(ctx, k, eps));
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_SWEEP_END], ctx->stream));
+    ctx->tm.knn_launches = 1;
+    ctx->knn_valid = true;
+    return PCT_OK;
+}
+
+// PCT_KNN_AUTO behind a uniform list just built, past the skew gate: is one cell size enough?  *route: Stay, or the
+// structure the census sends the call to instead (tree_reachable: the hierarchical list, else the chain of cell lists).
+static int examine_uniform_list(pct_ctx* ctx, int32_t k, bool tree_reachable, Route* route) {
+    const bool debug = pct_getenv("PCT_GRID_DEBUG") != nullptr;
+    const double skew = cell_skew(ctx->tm.occupancy, ctx->nonempty_cells, ctx->n);
+    if (debug) fprintf(stderr, "[auto] occupancy %.1f, %lld non-empty cells, skew %.2f\n", ctx->tm.occupancy, (long long)ctx->nonempty_cells, skew);
+    *route = Route::Stay;
+    if (!(skew > skew_min(tree_reachable))) return PCT_OK;
+    unsigned long long c[4];
+    PCT_TRY(pct_item_census(ctx, k, c));
+    const CensusShares s = census_shares(c);
+    if (debug) fprintf(stderr, "[auto] census: %llu queries, %llu overflow, %llu short, %.1f non-empty stencil cells\n", c[0], c[1], c[2], s.cells);
+    *route = census_route(s, ctx->n, tree_reachable);
+    return PCT_OK;
+}
+
+// Neighbour sweep without timing bookkeeping; events CALL_BEGIN | GRID_END | SWEEP_END bracket cell list and sweep.
+// fuse_par: the fused call -- its fit reads no distances, and the passes of a chained sweep fit their rows into the pinned slots of this parity.
+static int run_knn(pct_ctx* ctx, int32_t k, double eps, int32_t asked, const int* fuse_par = nullptr, SweepDone* done = nullptr) {
+    SweepDone unread;
+    if (!done) done = &unread;
+    *done = SweepDone{};
+    const bool want_dist = fuse_par == nullptr;
+    // 1. the request
     if (ctx->n <= 0) return pct_fail(ctx, PCT_ERR_INVALID, "no cloud loaded");
     if (k < 1 || k > PCT_K_MAX) return pct_fail(ctx, PCT_ERR_INVALID, "k=%d outside [1,%d]", k, PCT_K_MAX);
     if ((int64_t)k + 1 > ctx->n) return pct_fail(ctx, PCT_ERR_K_TOO_LARGE, "k+1=%d exceeds the cloud size %lld", k + 1, (long long)ctx->n);
     if (!(eps >= 0) || isinf(eps)) eps = 0;
-    bool auto_req = algo == PCT_KNN_AUTO;
-    if (algo == PCT_KNN_AUTO) algo = ctx->n >= 4096 ? PCT_KNN_GRID : PCT_KNN_BRUTE;
-    // cKDTree.query takes any k (pct:83).  The fast sweeps sort lists of one or two registers per lane (k <= 127);
-    // longer rows go through the wave-per-query sweeps, whose running list is 64 R wide for any power of two R: the
-    // exact sweep over the cell list (any cloud size), the exhaustive sweep where that was asked for.
-    if (k > 127) {
-        if (algo != PCT_KNN_BRUTE) algo = PCT_KNN_GRID_EXACT;
-        auto_req = false;
+    const bool whole = ctx->q_begin == 0 && ctx->q_end == ctx->n;
+    Request rq;
+    switch (resolve_request(asked, k, ctx->n, whole, ctx->slab_parts >= 1, fuse_par != nullptr, &rq)) {
+        case Refusal::UnknownAlgorithm: return pct_fail(ctx, PCT_ERR_INVALID, "unknown algorithm %d", rq.algo);
+        case Refusal::SlabNeedsFusedGrid: return pct_fail(ctx, PCT_ERR_INVALID, "slab ownership: pct_curvature with PCT_KNN_AUTO / PCT_KNN_GRID only");
+        case Refusal::None: break;
     }
-    if (algo != PCT_KNN_GRID && algo != PCT_KNN_BRUTE && algo != PCT_KNN_GRID_EXACT && algo != PCT_KNN_GRID_LEVELS && algo != PCT_KNN_TREE)
-        return pct_fail(ctx, PCT_ERR_INVALID, "unknown algorithm %d", algo);
-    if (ctx->slab_parts >= 1) {            // one cell list over the slab and its margin (include/pct_hip.h)
-        if (!fuse_fit || (algo != PCT_KNN_GRID && algo != PCT_KNN_GRID_EXACT))
-            return pct_fail(ctx, PCT_ERR_INVALID, "slab ownership: pct_curvature with PCT_KNN_AUTO / PCT_KNN_GRID only");
-        auto_req = false;
-    }
+    const int32_t algo = rq.algo;
+    RouteSwitches sw = {false, false};             // (they matter to PCT_KNN_AUTO only)
+    if (rq.auto_req) sw = RouteSwitches{pct_getenv("PCT_NO_TREE") != nullptr, pct_getenv("PCT_NO_AUTO_LEVELS") != nullptr};
     ctx->knn_valid = ctx->fit_valid = false;
     ctx->k = k;
     ctx->eps = eps;
@@ -474,124 +538,62 @@ static int run_knn(pct_ctx* ctx, int32_t k, double eps, int32_t algo, bool fuse_
     ctx->tm.levels = 0;
     ctx->tm.sweep_variant = 0;         // (set by the fast sweep's launch, pct_knn.hip)
     ctx->tm.algo = algo;
-    const auto run_levels = [&]() -> int {
-        ctx->tm.algo = PCT_KNN_GRID_LEVELS;
-        PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_GRID_END], ctx->stream));
-        ctx->levels_fuse_fit = fuse_fit;
-        const int lst = pct_knn_levels(ctx, k, eps);
-        ctx->levels_fuse_fit = false;
-        PCT_TRY(lst);
-        PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FAST_END], ctx->stream));
-        PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_SWEEP_END], ctx->stream));
-        ctx->tm.knn_launches = ctx->tm.levels;
-        ctx->knn_valid = true;
-        return PCT_OK;
-    };
-    // the hierarchical cell list takes whole clouds; a shard asked of it goes down the chain of cell lists
-    const bool tree_ok = ctx->q_begin == 0 && ctx->q_end == ctx->n && ctx->n < ((int64_t)1 << 26);
-    const auto run_tree = [&]() -> int {
-        ctx->tm.algo = PCT_KNN_TREE;
-        bool usable = false;
-        PCT_TRY(pct_build_tree(ctx, k, eps, &usable));
-        if (!usable && ctx->tree_hint_mismatch) return PCT_OK;       // (a remembered verdict that does not fit this cloud: the caller goes on)
-        if (!usable) return run_levels();          // (extents or eps outside what the float32 pre-selection can square)
-        PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_GRID_END], ctx->stream));
-        PCT_TRY(pct_launch_knn_tree(ctx, k, eps));
-        PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_SWEEP_END], ctx->stream));
-        ctx->tm.knn_launches = 1;
-        ctx->knn_valid = true;
-        return PCT_OK;
-    };
-    if (algo == PCT_KNN_TREE) return tree_ok ? run_tree() : run_levels();
-    // a handle fed a stream of similar clouds: what the census said about the last one of this size still holds
-    if (auto_req && tree_ok && ctx->auto_tree_n == ctx->n && (++ctx->auto_tree_calls & 15) != 0 && !pct_getenv("PCT_NO_TREE") &&
-        !pct_getenv("PCT_NO_AUTO_LEVELS")) {
-        // (the verdict holds for clouds of this size AND this bounding box, within 2 % per face -- the same test the
-        // speculative cell-list build applies to "a stream of similar clouds")
-        ctx->tree_check_bbox = true;
-        ctx->tree_hint_mismatch = false;
-        const int st = run_tree();
-        ctx->tree_check_bbox = false;
-        if (!ctx->tree_hint_mismatch) return st;
-        ctx->tree_hint_mismatch = false;
+    TreeVerdict tree;
+    if (algo == PCT_KNN_TREE)
+        return rq.tree_ok ? sweep_tree(ctx, k, eps, want_dist, nullptr, fuse_par, done, &tree) : sweep_levels(ctx, k, eps, fuse_par, done);
+    // 2. the remembered hierarchical list
+    if (remembered_applies(rq, ctx->n, ctx->auto_tree_n, &ctx->auto_tree_calls, sw)) {
+        PCT_TRY(sweep_tree(ctx, k, eps, want_dist, ctx->auto_tree_bbox, fuse_par, done, &tree));
+        if (tree != TreeVerdict::OtherCloud) return PCT_OK;
         ctx->auto_tree_n = 0;
         ctx->tm.algo = algo;
     }
-    if (algo == PCT_KNN_GRID_LEVELS) return run_levels();
-    const bool grid = algo == PCT_KNN_GRID || algo == PCT_KNN_GRID_EXACT;
-    if (grid) {
-        ctx->grid_skewed = false;
-        ctx->auto_probe = auto_req && algo == PCT_KNN_GRID && tree_ok && ctx->n >= 16384 && !pct_getenv("PCT_NO_TREE") && !pct_getenv("PCT_NO_AUTO_LEVELS");
-        ctx->auto_probe_tree = ctx->auto_probe;
-        const int bst = pct_build_grid(ctx, k, eps);
-        ctx->auto_probe = false;
-        PCT_TRY(bst);
-        if (ctx->grid_skewed) {                    // the uniform list was not built: far too many cells per point
-            ctx->grid_skewed = false;
-            const int st = run_tree();
-            if (st == PCT_OK && ctx->tm.algo == PCT_KNN_TREE) { ctx->auto_tree_n = ctx->n; memcpy(ctx->auto_tree_bbox, ctx->tree_bbox, sizeof(ctx->tree_bbox)); }
-            return st;
-        }
-        // PCT_KNN_AUTO on a whole cloud: is one cell size enough?  A point of a cloud of even density shares its cell
-        // with about as many points as a non-empty cell holds on average; where the density spans decades the first
-        // figure (size-biased) runs away from the second.  Only then the work items are counted: the share of queries
-        // whose 27-cell stencil overflows the staging area or cannot hold k+1 points -- they would all go through the
-        // wave-per-query exact sweep -- and how many stencil cells the others find non-empty (about 9-13 on a surface,
-        // up to 27 in a volume, where the chain of cell lists does not pay).
-        if (auto_req && algo == PCT_KNN_GRID && ctx->q_begin == 0 && ctx->q_end == ctx->n && ctx->n >= 65536 && ctx->n < ((int64_t)1 << 29) &&
-            ctx->nonempty_cells > 0 && !pct_getenv("PCT_NO_AUTO_LEVELS")) {
-            const double skew = ctx->tm.occupancy * (double)ctx->nonempty_cells / (double)ctx->n;
-            if (pct_getenv("PCT_GRID_DEBUG")) fprintf(stderr, "[auto] occupancy %.1f, %lld non-empty cells, skew %.2f\n", ctx->tm.occupancy, (long long)ctx->nonempty_cells, skew);
-            const double skew_min = ctx->auto_probe_tree ? 1.25 : 1.5;      // (the chain needs a wider spread to pay)
-            if (!(skew > skew_min)) ctx->auto_tree_n = 0;
-            if (skew > skew_min) {
-                unsigned long long c[4];
-                PCT_TRY(pct_item_census(ctx, k, c));
-                const double q = (double)(c[0] ? c[0] : 1), fail = (double)(c[1] + c[2]) / q, fine = (double)c[0] - (double)(c[1] + c[2]);
-                const double cells = fine > 0 ? (double)c[3] / fine : 27.0;
-                if (pct_getenv("PCT_GRID_DEBUG")) fprintf(stderr, "[auto] census: %llu queries, %llu overflow, %llu short, %.1f non-empty stencil cells\n", c[0], c[1], c[2], cells);
-                // (the hierarchical list costs ~1.7x a uniform one whatever the density; every query the uniform list
-                // would hand to the exact sweep costs about as much as twelve it answers itself)
-                // (the hierarchical list's build -- a dozen launches, three read-backs -- costs ~0.45 ms more than the
-                // uniform one whatever the cloud's size, a query handed to the exact sweep ~12 ns: below a million
-                // points the predicted share must be larger for the switch to pay)
-                const double fail_min = fmax(0.08, 37500.0 / (double)ctx->n);
-                if (ctx->auto_probe_tree ? fail > fail_min && cells < 15.0 : fail > 0.30 && fine > 0.02 * q && cells < 15.0) {
-                    if (ctx->auto_probe_tree) {
-                        const int st = run_tree();
-                        if (st == PCT_OK && ctx->tm.algo == PCT_KNN_TREE) { ctx->auto_tree_n = ctx->n; memcpy(ctx->auto_tree_bbox, ctx->tree_bbox, sizeof(ctx->tree_bbox)); }
-                        return st;
-                    }
-                    return run_levels();
-                }
-                ctx->auto_tree_n = 0;
-            }
-        }
-    } else {
-        float bbox[6];
-        PCT_TRY(pct_pack_points(ctx, bbox));
-        ctx->tm.grid_iters = 0;
-        ctx->tm.cells = ctx->tm.occupied_cells = 0;
-        ctx->tm.grid_points = ctx->n;
-        ctx->tm.cell_size = 0;
+    if (algo == PCT_KNN_GRID_LEVELS) return sweep_levels(ctx, k, eps, fuse_par, done);
+    if (algo == PCT_KNN_BRUTE) return sweep_brute(ctx, k, eps);
+    // 3. the uniform list (PCT_KNN_GRID, PCT_KNN_GRID_EXACT) -- and whether PCT_KNN_AUTO keeps it
+    const bool tree_reachable = may_give_up(rq, ctx->n, sw);
+    GridVerdict built;
+    PCT_TRY(pct_build_grid(ctx, k, eps, tree_reachable, &built));
+    Route route = built == GridVerdict::GaveUp ? Route::Tree : Route::Stay;      // (not built: far too many cells per point)
+    if (built == GridVerdict::Built && skew_gate(rq, whole, ctx->n, ctx->nonempty_cells, sw)) {
+        PCT_TRY(examine_uniform_list(ctx, k, tree_reachable, &route));
+        if (route == Route::Stay) ctx->auto_tree_n = 0;
     }
+    if (route == Route::Tree) {
+        PCT_TRY(sweep_tree(ctx, k, eps, want_dist, nullptr, fuse_par, done, &tree));
+        if (tree == TreeVerdict::Built) {          // the next cloud of this size and box goes there directly
+            ctx->auto_tree_n = ctx->n;
+            memcpy(ctx->auto_tree_bbox, ctx->tree_bbox, sizeof(ctx->tree_bbox));
+        }
+        return PCT_OK;
+    }
+    if (route == Route::Levels) return sweep_levels(ctx, k, eps, fuse_par, done);
+    // 4. the sweep
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_GRID_END], ctx->stream));
-    if (grid)
-        PCT_TRY(pct_launch_knn_grid(ctx, k, eps, algo == PCT_KNN_GRID_EXACT));
-    else
-        PCT_TRY(pct_launch_knn_brute(ctx, k, eps));
+    PCT_TRY(pct_launch_knn_grid(ctx, k, eps, algo == PCT_KNN_GRID_EXACT, 0, want_dist));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_SWEEP_END], ctx->stream));
     ctx->tm.knn_launches = 1;
     ctx->knn_valid = true;
     return PCT_OK;
 }
 
-static int finish_knn_stats(pct_ctx* ctx, bool* beyond_limits) {
+// The fused call's tail behind its sweep: the fit (where the passes of a chained sweep have not fitted their rows), its end
+// event, and the sweep's statistics words into pinned slot `par` -- mirrored by the fit kernel, else copied.
+// (no event of its own for the start of the fit: it starts where the sweep's last event, PCT_EV_SWEEP_END, was recorded --
+// every event record is a marker packet between two kernels, ~3 us of dispatch gap)
+static int fused_tail(pct_ctx* ctx, int par, const SweepDone& swept) {
+    bool mirrored = false;
+    if (!swept.rows_fitted) PCT_TRY(pct_launch_fit_table(ctx, FitSlot{par, true}, &mirrored));
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_END], ctx->stream));
+    if (!mirrored)                // (no fit kernel ran: the chained sweep fitted its passes itself, or there are no rows)
+        PCT_HIP(ctx, hipMemcpyAsync(&ctx->pin->stats[par], ctx->counters.p, sizeof(pct_sweep_words), hipMemcpyDeviceToHost, ctx->stream));
+    return PCT_OK;
+}
+
+// words_enqueued: the fused tail has sent the statistics words to pinned slot 0 already
+static int finish_knn_stats(pct_ctx* ctx, bool words_enqueued, bool* beyond_limits) {
     pct_sweep_words& w = ctx->pin->stats[0];                             // pinned: a plain DMA, no staging
-    // (the fused call's fit kernel has already written them there: one launch less in the step's tail)
-    if (!ctx->stats_mirrored)
-        PCT_HIP(ctx, hipMemcpyAsync(&w, ctx->counters.p, sizeof(w), hipMemcpyDeviceToHost, ctx->stream));
-    ctx->stats_mirrored = false;
+    if (!words_enqueued) PCT_HIP(ctx, hipMemcpyAsync(&w, ctx->counters.p, sizeof(w), hipMemcpyDeviceToHost, ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     read_sweep_stats(w, &ctx->tm);
     if (pct_getenv("PCT_TREE_DEBUG") && ctx->collect_stats)
@@ -617,11 +619,11 @@ int pct_knn(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
     PCT_TRY(begin_call(ctx));
     bool again = false;
     PCT_TRY(run_knn(ctx, k, eps, algo));
-    PCT_TRY(finish_knn_stats(ctx, &again));
+    PCT_TRY(finish_knn_stats(ctx, false, &again));
     if (again) {
         retry_without_cull(ctx);
         PCT_TRY(run_knn(ctx, k, eps, algo));
-        PCT_TRY(finish_knn_stats(ctx, &again));
+        PCT_TRY(finish_knn_stats(ctx, false, &again));
     }
     ctx->tm.fit_ms = 0;
     ctx->tm.total_ms = ev_ms(ctx, PCT_EV_CALL_BEGIN, PCT_EV_SWEEP_END);
@@ -633,7 +635,7 @@ int pct_fit(pct_ctx* ctx) {
     PCT_TRY(refuse_in_slab_mode(ctx, "pct_fit"));
     if (!ctx->knn_valid) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "plant the neighbour table first (pct_knn)");
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_BEGIN], ctx->stream));
-    PCT_TRY(pct_launch_fit_table(ctx));
+    PCT_TRY(pct_launch_fit_table(ctx, FitSlot{0, false}, nullptr));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_END], ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->tm.fit_ms = ev_ms(ctx, PCT_EV_FIT_BEGIN, PCT_EV_FIT_END);
@@ -650,38 +652,26 @@ int pct_set_async(pct_ctx* ctx, int32_t enable) {
     return PCT_OK;
 }
 
+// the timing events of the pending call <-> the set the next call records into
+static void swap_event_sets(pct_ctx* ctx) {
+    for (int i = PCT_EV_CALL_BEGIN; i <= PCT_EV_FAST_END; ++i) { hipEvent_t t = ctx->ev[i]; ctx->ev[i] = ctx->ev_prev[i]; ctx->ev_prev[i] = t; }
+}
+
 // pct_curvature of a stream of clouds (pct_set_async): enqueue and return.  The previous call's bookkeeping is done here,
 // after the cell list's mid-build wait -- which lies behind all of that call's kernels on the stream --, without a wait
 // of its own.
 static int curvature_async(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
     const bool had = ctx->pending;
-    if (had)          // the pending call keeps its timing events; this one records into the other set
-        for (int i = PCT_EV_CALL_BEGIN; i <= PCT_EV_FAST_END; ++i) { hipEvent_t t = ctx->ev[i]; ctx->ev[i] = ctx->ev_prev[i]; ctx->ev_prev[i] = t; }
+    if (had) swap_event_sets(ctx);          // the pending call keeps its timing events; this one records into the other set
     const int par = had ? ctx->pend_par ^ 1 : 0;
     ctx->retries = 0;
-    ctx->fit_par = par;            // (also for the fits a chained sweep launches itself)
-    int st = run_knn(ctx, k, eps, algo, true);
-    if (st == PCT_OK) {
-        st = [&]() -> int {
-            // (no event of its own for the start of the fit: it starts where the sweep's last event, PCT_EV_SWEEP_END, was recorded --
-            // every event record is a marker packet between two kernels, ~3 us of dispatch gap)
-            ctx->stats_mirrored = false;
-            ctx->stats_mirror_req = true;
-            const int fs = pct_launch_fit_table(ctx);
-            ctx->stats_mirror_req = false;
-            PCT_TRY(fs);
-            PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_END], ctx->stream));
-            if (!ctx->stats_mirrored)     // (no fit kernel ran: the chained sweep fitted its passes itself, or there are no rows)
-                PCT_HIP(ctx, hipMemcpyAsync(&ctx->pin->stats[par], ctx->counters.p, sizeof(pct_sweep_words), hipMemcpyDeviceToHost, ctx->stream));
-            ctx->stats_mirrored = false;
-            return PCT_OK;
-        }();
-    }
-    ctx->fit_par = 0;
+    SweepDone swept;
+    int st = run_knn(ctx, k, eps, algo, &par, &swept);
+    if (st == PCT_OK) st = fused_tail(ctx, par, swept);
     if (st != PCT_OK) {            // leave the handle in the plain state: nothing pending, events where they were
         (void)hipStreamSynchronize(ctx->stream);
         if (had) {
-            for (int i = PCT_EV_CALL_BEGIN; i <= PCT_EV_FAST_END; ++i) { hipEvent_t t = ctx->ev[i]; ctx->ev[i] = ctx->ev_prev[i]; ctx->ev_prev[i] = t; }
+            swap_event_sets(ctx);
             finish_pending(ctx, ctx->ev);
         }
         return st;
@@ -712,13 +702,11 @@ int pct_curvature(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
     if (async) return curvature_async(ctx, k, eps, algo);
     for (int attempt = 0; attempt < 2; ++attempt) {
         bool again = false;
-        PCT_TRY(run_knn(ctx, k, eps, algo, true));
-        ctx->stats_mirrored = false;
-        ctx->stats_mirror_req = true;
-        PCT_TRY(pct_launch_fit_table(ctx));
-        ctx->stats_mirror_req = false;
-        PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_END], ctx->stream));
-        PCT_TRY(finish_knn_stats(ctx, &again));
+        const int par = 0;
+        SweepDone swept;
+        PCT_TRY(run_knn(ctx, k, eps, algo, &par, &swept));
+        PCT_TRY(fused_tail(ctx, par, swept));
+        PCT_TRY(finish_knn_stats(ctx, true, &again));
         if (!again) break;
         retry_without_cull(ctx);
     }
@@ -1078,7 +1066,7 @@ int pct_surface_variation(pct_ctx* ctx, int32_t k_total, float* out) {
         PCT_TRY(pct_reserve(ctx, &ctx->K, (size_t)rows * sizeof(float)));
         PCT_TRY(pct_launch_surface_variation(ctx, (float*)ctx->K.p));
         PCT_HIP(ctx, hipMemcpyAsync(out, ctx->K.p, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        PCT_TRY(finish_knn_stats(ctx, &again));
+        PCT_TRY(finish_knn_stats(ctx, false, &again));
         if (!again) break;
         retry_without_cull(ctx);
     }
@@ -1109,7 +1097,7 @@ int pct_pca_curvatures(pct_ctx* ctx, int32_t k, int32_t algo, int32_t keep_neigh
     const int32_t kc = (int32_t)(kk + (room < PCT_PCA_EXTRA ? room : PCT_PCA_EXTRA));
     bool again = false;
     if (st == PCT_OK) st = run_knn(ctx, kc, 0.0, algo);
-    if (st == PCT_OK) st = finish_knn_stats(ctx, &again);     // (whole clouds: nothing was left out of the cell list)
+    if (st == PCT_OK) st = finish_knn_stats(ctx, false, &again);     // (whole clouds: nothing was left out of the cell list)
     const int rs = pct_pca_restore(ctx);
     PCT_TRY(st);
     PCT_TRY(rs);

@@ -719,7 +719,8 @@ __global__ __launch_bounds__(256) void k_gather_fit(const int* __restrict__ row_
     if (o_H2) o_H2[i] = H2[r];
 }
 
-int launch(pct_ctx* ctx, const FitArgs& a0, bool f64) {
+// slot: the pinned slots of the call (FitSlot); *mirrored (may be null): the fit kernel mirrors the statistics words
+int launch(pct_ctx* ctx, const FitArgs& a0, bool f64, FitSlot slot, bool* mirrored) {
     FitArgs a = a0;
     a.kp = a.k | 1;
     if (a.row_mask && ((size_t)kFitBlock * a.kp * sizeof(int) > 64 * 1024 || a.coefs64))
@@ -743,12 +744,11 @@ int launch(pct_ctx* ctx, const FitArgs& a0, bool f64) {
     }
     a.stat_src = nullptr;
     a.stat_dst = nullptr;
-    if (ctx->stats_mirror_req && ctx->counters.p) {
+    if (slot.mirror_stats && ctx->counters.p) {
         a.stat_src = &pct_dev(ctx)->sweep;
-        a.stat_dst = &ctx->pin->stats[ctx->fit_par];
-        ctx->stats_mirrored = true;
+        a.stat_dst = &ctx->pin->stats[slot.par];
+        if (mirrored) *mirrored = true;
     }
-    ctx->stats_mirror_req = false;
     a.flag_count = (int*)ctx->fit_flag.p + ctx->fit_parity;
     a.flag_next = (int*)ctx->fit_flag.p + (ctx->fit_parity ^ 1);
     ctx->fit_parity ^= 1;
@@ -768,7 +768,7 @@ int launch(pct_ctx* ctx, const FitArgs& a0, bool f64) {
     PCT_HIP(ctx, hipGetLastError());
     // the rows handed over: fixed grid, the list length is read on the device
     const int sblocks = blocks < 1024 ? blocks : 1024;
-    long long* note = &ctx->pin->svd_rows[ctx->fit_par];
+    long long* note = &ctx->pin->svd_rows[slot.par];
     if (a.coefs64) {
         if (f64)
             PCT_LAUNCH((k_fit_svd<true, true>), dim3(sblocks), dim3(64), 0, ctx->stream, a, a.flag_list, a.flag_count, note);
@@ -787,7 +787,7 @@ int launch(pct_ctx* ctx, const FitArgs& a0, bool f64) {
 // one pass of the density-adaptive sweep (pct_levels.hip): the rows it answered (row_done), fitted while its table is
 // still in ITS cell order -- gathers stay local; results go to public order.  The merged public-space table is fitted
 // only when a caller asks for the table first and the fit later (1.3 ms instead of 0.25 at 1 M points).
-int pct_launch_fit_pass(pct_ctx* ctx, int64_t rows) {
+int pct_launch_fit_pass(pct_ctx* ctx, int64_t rows, int par) {
     const int64_t nq = ctx->q_end - ctx->q_begin;
     PCT_TRY(pct_reserve(ctx, &ctx->coefs, (size_t)nq * 6 * sizeof(float)));
     PCT_TRY(pct_reserve(ctx, &ctx->K, (size_t)nq * sizeof(float)));
@@ -813,16 +813,11 @@ int pct_launch_fit_pass(pct_ctx* ctx, int64_t rows) {
     a.n_pts = (unsigned)ctx->n_grid;
     a.row_mask = (const int*)ctx->row_done.p;
     a.svd_accumulate = 1;                      // (pct_knn_levels zeroes the host word before the first pass)
-    return launch(ctx, a, ctx->has_f64);
+    return launch(ctx, a, ctx->has_f64, FitSlot{par, false}, nullptr);      // (a pass mirrors nothing: the sweep goes on behind it)
 }
 
 // fit from the device-resident neighbour table left by the sweep
-int pct_launch_fit_table(pct_ctx* ctx) {
-    if (ctx->levels_fitted) {                // the passes of the density-adaptive sweep have fitted their rows already
-        ctx->levels_fitted = false;
-        ctx->fit_row_order = false;
-        return PCT_OK;
-    }
+int pct_launch_fit_table(pct_ctx* ctx, FitSlot slot, bool* mirrored) {
     const int64_t nq = ctx->q_end - ctx->q_begin;
     PCT_TRY(pct_reserve(ctx, &ctx->coefs, (size_t)nq * 6 * sizeof(float)));
     PCT_TRY(pct_reserve(ctx, &ctx->K, (size_t)nq * sizeof(float)));
@@ -853,7 +848,7 @@ int pct_launch_fit_table(pct_ctx* ctx) {
     a.H = (float*)ctx->H.p;
     a.H2 = (float*)ctx->H2.p;
     a.n_pts = (unsigned)(sorted ? ctx->n_grid : ctx->n);
-    return launch(ctx, a, ctx->has_f64);
+    return launch(ctx, a, ctx->has_f64, slot, mirrored);
 }
 
 int pct_launch_gather_fit(pct_ctx* ctx, int64_t first, int64_t rows, float* d_coefs, float* d_K, float* d_H, float* d_H2) {
@@ -888,7 +883,7 @@ int pct_launch_fit_rows(pct_ctx* ctx, const int32_t* d_idx, const int32_t* d_cnt
     a.H2 = d_H2;
     a.n_pts = (unsigned)(sorted_space ? ctx->n_grid : ctx->n);
     // (rows with fewer than 6 points get lstsq's minimum-norm answer from k_fit_svd, as in every launch)
-    return launch(ctx, a, ctx->has_f64);
+    return launch(ctx, a, ctx->has_f64, FitSlot{0, false}, nullptr);       // (a blocking entry point: slot 0, no fused tail behind it)
 }
 
 // the diagnostics variant of pct_launch_fit_rows: float64 coefficients and curvatures, public-space ids
@@ -911,7 +906,7 @@ int pct_launch_fit_rows_f64(pct_ctx* ctx, const int32_t* d_idx, const int32_t* d
     a.K64 = d_K;
     a.H64 = d_H;
     a.n_pts = (unsigned)ctx->n;
-    return launch(ctx, a, ctx->has_f64);
+    return launch(ctx, a, ctx->has_f64, FitSlot{0, false}, nullptr);       // (a blocking entry point: slot 0, no fused tail behind it)
 }
 
 int pct_launch_prefix_rows(pct_ctx* ctx, const int* d_sample_row, int64_t n_samples, int n_lo, int n_hi, int* d_table,

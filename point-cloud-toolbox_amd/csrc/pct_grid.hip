@@ -1706,7 +1706,8 @@ static int commit_grid(pct_ctx* ctx, const GridPoints& s, pct_grid g, const Edge
 // 27-cell stencil (guaranteed radius = one cell edge) contains the k+1 nearest
 // points for nearly every query of a surface-like cloud; the sweep kernel
 // widens ring by ring for the rest.
-int pct_build_grid(pct_ctx* ctx, int32_t k, double eps) {
+int pct_build_grid(pct_ctx* ctx, int32_t k, double eps, bool may_give_up, GridVerdict* out) {
+    *out = GridVerdict::Built;
     // measured optima on surface clouds (tools/tune_factor.py): larger cells cost candidates, smaller ones cost
     // trips to the exact sweep; the LDS staging capacity caps the large side
     const double factor = ctx->occupancy_factor > 0 ? ctx->occupancy_factor : pct_default_factor(k);
@@ -1766,8 +1767,8 @@ int pct_build_grid(pct_ctx* ctx, int32_t k, double eps) {
                     // a 1/r^2 scan inherited its 130 cells per point): this cloud's own first guess, then
                     a = es.fallback_first();
                     size_grid(ctx, sub_box, s.bbox, a, &p.g);
-                } else if (ctx->auto_probe) {
-                    ctx->grid_skewed = true;
+                } else if (may_give_up) {
+                    *out = GridVerdict::GaveUp;
                     ctx->grid_valid = false;
                     return PCT_OK;
                 }

@@ -141,7 +141,6 @@ struct pct_ctx {
     bool pending = false;          // a fused call has been enqueued and its bookkeeping has not been done
     int pend_par = 0;              // parity of the pending call: which pinned slots its kernels write
     bool pend_sorted = false;      // its table is in a sorted space: knn_fast_ms applies
-    int fit_par = 0;               // which pinned slots (statistics mirror, SVD row count) the fits being launched write
     pct_timings tm_snap = {};      // the host-side fields of the pending call's timings
     pct_timings tm_done = {};      // timings of the last call whose bookkeeping has been done
     char err[512] = {0};
@@ -181,8 +180,6 @@ struct pct_ctx {
     int64_t own_count = 0;
     double level_edge = 0;          // > 0: first cell edge of this pass
     bool level_mode = false;        // a density-adaptive sweep is in progress (rows answered are recorded in row_done)
-    bool levels_fuse_fit = false;   // pct_curvature: every pass fits the rows it answered (in its own cell order)
-    bool levels_fitted = false;     // ... and did: pct_launch_fit_table has nothing left to do
     pct_buf lvl_src;                // float4 (n): the points in the cell order of the first pass (input of the later passes' builds)
     bool lvl_src_valid = false;
     float lvl_bbox[6] = {0, 0, 0, 0, 0, 0};
@@ -203,14 +200,10 @@ struct pct_ctx {
     pct_buf flag_buf;               // float (n): wanted log2 cell edge of every point still unanswered (NaN = answered)
     pct_buf dens_buf;               // float2 (n): log2 of the largest edge known too small / the smallest known too large
     pct_buf pub_pos, pub_dist, pub_cnt;   // public-space neighbour table the passes are merged into
-    bool auto_probe = false;        // PCT_KNN_AUTO on a cloud the hierarchical list could take: pct_build_grid gives up (grid_skewed)
-    bool auto_probe_tree = false;   // ... and the census that follows may send the call there
-    bool grid_skewed = false;       // rather than build a uniform list of more than 16 cells per point
-    float auto_tree_bbox[6] = {0, 0, 0, 0, 0, 0};   // ... whose bounding box was this (the next cloud must match it within 2 %)
     float tree_bbox[6] = {0, 0, 0, 0, 0, 0};        // bounding box of the cloud the hierarchical list was last built for
-    bool tree_check_bbox = false, tree_hint_mismatch = false;
     int64_t auto_tree_n = 0;        // PCT_KNN_AUTO sent a cloud of this size to the hierarchical list: the next one of the same
     int32_t auto_tree_calls = 0;    // size goes there directly (no uniform build first); re-examined every 16th call
+    float auto_tree_bbox[6] = {0, 0, 0, 0, 0, 0};   // ... whose bounding box was this (the next cloud must match it within 2 %)
     bool has_f64 = false;
     double occupancy_factor = 0.0; // 0 = default
     bool collect_stats = false;    // sweep statistics (costly same-address atomics)
@@ -264,11 +257,8 @@ struct pct_ctx {
     int fit_parity = 0;            // which of the two counts of fit_flag the next fit launch uses (the launch zeroes the other one)
     void* fit_flag_seen = nullptr; // the fit_flag allocation (pointer and capacity) whose head has been zeroed
     size_t fit_flag_cap_seen = 0;
-    bool stats_mirror_req = false; // pct_curvature: the fit about to be launched may mirror the sweep's statistics words
-    bool stats_mirrored = false;   // the fused fit copied the sweep's statistics words to pinned memory (no D2H copy needed)
     bool knn_valid = false;
     bool knn_sorted_space = false; // false: rows/ids are public indices (brute force)
-    bool skip_dist_req = false;    // the caller will not read distances from the table (the fused curvature call)
     bool dist_valid = true;        // nbr_dist holds the distances of the table in place (else: derived on demand)
     pct_buf counters;   // pct_dev_words: the sweep's statistics words, the census, the scatter hit count
 
@@ -399,25 +389,35 @@ __device__ inline int64_t pct_code_lower_bound(const unsigned long long* __restr
         if (s_ != PCT_OK) return s_; \
     } while (0)
 
+// What one call asks of another, and what it answers, travels in arguments and results -- never parked on the handle.
+// Which pinned parity slot (statistics mirror, SVD row count) the fits of a call write, and whether its fit kernel may
+// mirror the sweep's statistics words there (the fused call: one copy less in the step's tail).
+struct FitSlot { int par; bool mirror_stats; };
+enum class GridVerdict { Built, GaveUp };                  // GaveUp: more than 16 cells per point wanted, nothing built
+enum class TreeVerdict { Built, Unusable, OtherCloud };    // Unusable: not a cloud for it; OtherCloud: not the expected box; nothing built
+
 // grid build (pct_grid.hip)
 int pct_pack_points(pct_ctx* ctx, float* bbox6);
 int pct_pack_points_f64(pct_ctx* ctx, const double* d_xyz64);
-int pct_build_grid(pct_ctx* ctx, int32_t k, double eps);
-// neighbour sweeps (pct_knn.hip)
-int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, int phase = 0);
+// may_give_up: PCT_KNN_AUTO on a cloud the hierarchical list could take (pct_auto_route.h)
+int pct_build_grid(pct_ctx* ctx, int32_t k, double eps, bool may_give_up, GridVerdict* out);
+// neighbour sweeps (pct_knn.hip); want_dist = false: the caller reads no distances from the table (the fused call)
+int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, int phase, bool want_dist);
 int pct_launch_knn_brute(pct_ctx* ctx, int32_t k, double eps);
 // census of the work items of the cell list in place: out4 = {queries, queries whose stencil overflows the staging
 // area, queries whose stencil holds fewer than 2.5 (k+1) points (too few to vouch for k+1 within one cell edge), sum over the other queries of the non-empty cells in their
 // 27-cell stencil} -- what decides between the plain and the density-adaptive sweep before anything is swept
 int pct_item_census(pct_ctx* ctx, int32_t k, unsigned long long out4[4]);
-int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps);     // pct_levels.hip
-int pct_build_tree(pct_ctx* ctx, int32_t k, double eps, bool* usable);     // pct_tree.hip (usable = false: not a cloud for it, nothing was built)
-int pct_launch_knn_tree(pct_ctx* ctx, int32_t k, double eps);
+// pct_levels.hip; fuse_par: every pass fits the rows it answered, into the pinned slots of this parity (null: no fits)
+int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps, const int* fuse_par);
+// pct_tree.hip; expect_bbox: the box a remembered verdict of PCT_KNN_AUTO was given for (null: any cloud)
+int pct_build_tree(pct_ctx* ctx, int32_t k, double eps, const float* expect_bbox, TreeVerdict* out);
+int pct_launch_knn_tree(pct_ctx* ctx, int32_t k, double eps, bool want_dist);
 int pct_launch_export_neighbors(pct_ctx* ctx, int64_t begin, int64_t end,
                                 int32_t* d_idx, float* d_dist, int32_t* d_cnt);
 // fit (pct_fit.hip)
-int pct_launch_fit_table(pct_ctx* ctx);
-int pct_launch_fit_pass(pct_ctx* ctx, int64_t rows);
+int pct_launch_fit_table(pct_ctx* ctx, FitSlot slot, bool* mirrored);     // *mirrored (may be null): a fit kernel mirrored the statistics words
+int pct_launch_fit_pass(pct_ctx* ctx, int64_t rows, int par);
 int pct_launch_fit_rows(pct_ctx* ctx, const int32_t* d_idx, const int32_t* d_cnt,
                         const int64_t* d_query, int64_t rows, int32_t k, int32_t pitch,
                         float* d_coefs, float* d_K, float* d_H, float* d_H2, bool sorted_space);

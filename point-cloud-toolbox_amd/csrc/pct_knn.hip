@@ -2406,8 +2406,9 @@ struct SweepPlan {
 };
 
 // tree: the hierarchical cell list is in place (whole clouds, one pass), else the uniform one; exact_only / phase as in
-// pct_launch_knn_grid.  Every tuning switch (PCT_*: A/B aids, read per call -- tests flip them) is read here.
-SweepPlan plan_sweep(const pct_ctx* ctx, int32_t k, double eps, bool tree, bool exact_only, int phase) {
+// pct_launch_knn_grid; want_dist = false: the caller reads no distances from the table.  Every tuning switch (PCT_*: A/B
+// aids, read per call -- tests flip them) is read here.
+SweepPlan plan_sweep(const pct_ctx* ctx, int32_t k, double eps, bool tree, bool exact_only, int phase, bool want_dist) {
     SweepPlan p;
     if (exact_only || phase == 2 || ctx->n_items <= 0) return p;
     p.eps = eps > 0;
@@ -2445,7 +2446,7 @@ SweepPlan plan_sweep(const pct_ctx* ctx, int32_t k, double eps, bool tree, bool 
     p.pre = f.pre; p.pair = f.pair; p.q64 = f.q64;
     // the fused curvature call, whose fit never reads distances, has the lean kernels write no distance table
     // (pct_get_neighbors derives the same bits from the positions when asked)
-    p.dist = !(p.lean() && ctx->skip_dist_req && !pct_getenv("PCT_KEEP_DIST"));
+    p.dist = !(p.lean() && !want_dist && !pct_getenv("PCT_KEEP_DIST"));
     return p;
 }
 
@@ -2537,9 +2538,9 @@ int launch_sweep(pct_ctx* ctx, const SweepPlan& p, const KnnArgs& a, int* redo, 
 
 // phase 0: fast sweep + exact sweep of what it flagged (or, exact_only, the exact sweep of every query);
 // phase 1: fast sweep only, the flagged rows stay in ctx->redo (level passes); phase 2: exact sweep of ctx->redo
-int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, int phase) {
+int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, int phase, bool want_dist) {
     const int64_t n_rows = ctx->own_flag ? ctx->own_count : ctx->q_end - ctx->q_begin;
-    const SweepPlan plan = plan_sweep(ctx, k, eps, false, exact_only, phase);
+    const SweepPlan plan = plan_sweep(ctx, k, eps, false, exact_only, phase, want_dist);
     if (phase != 2) {
         PCT_TRY(reserve_table(ctx, k, eps, plan.dist));
         PCT_TRY(pct_reserve(ctx, &ctx->redo, ((size_t)n_rows + 16) * sizeof(int)));
@@ -2572,12 +2573,12 @@ int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, in
 // Neighbour sweep on the hierarchical cell list (pct_build_tree): fast sweep over its work items, then the exact sweep
 // on the same structure for what the fast one flagged.  The table is in Morton order (a sorted space like the uniform
 // list's: sorted4, owned_pos = identity, row_of).
-int pct_launch_knn_tree(pct_ctx* ctx, int32_t k, double eps) {
+int pct_launch_knn_tree(pct_ctx* ctx, int32_t k, double eps, bool want_dist) {
     if (ctx->level_mode || ctx->own_flag || ctx->q_begin != 0 || ctx->q_end != ctx->n)
         return pct_fail(ctx, PCT_ERR_INVALID, "the tree sweep takes whole clouds");
     const int64_t n_rows = ctx->n;
     const bool exact_only = pct_getenv("PCT_TREE_EXACT_ONLY") != nullptr;        // testing: every query through the exact sweep
-    const SweepPlan plan = plan_sweep(ctx, k, eps, true, exact_only, 0);
+    const SweepPlan plan = plan_sweep(ctx, k, eps, true, exact_only, 0, want_dist);
     PCT_TRY(reserve_table(ctx, k, eps, plan.dist));
     PCT_TRY(pct_reserve(ctx, &ctx->redo, ((size_t)n_rows + 16) * sizeof(int)));
     KnnArgs a = make_args(ctx, k, eps, true);

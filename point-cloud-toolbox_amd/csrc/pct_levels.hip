@@ -186,8 +186,8 @@ void swap_buf(T& a, T& b) { T t = a; a = b; b = t; }
 
 }  // namespace
 
-int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps) {
-    ctx->pin->svd_rows[ctx->fit_par] = 0;                           // rows the passes' fits hand to k_fit_svd: summed over the passes of this call
+int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps, const int* fuse_par) {
+    ctx->pin->svd_rows[fuse_par ? *fuse_par : 0] = 0;                   // rows the passes' fits hand to k_fit_svd: summed over the passes of this call
     const int64_t nq = ctx->q_end - ctx->q_begin;
     if (ctx->n >= ((int64_t)1 << 29)) return pct_fail(ctx, PCT_ERR_INVALID, "the chained sweep handles clouds below 2^29 points");
     const int pitch = (k + 3) & ~3;
@@ -214,11 +214,12 @@ int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps) {
     };
     const auto run_pass = [&](int64_t owned, bool exact) -> int {
         const double t0 = debug ? tick() : 0;
-        PCT_TRY(pct_build_grid(ctx, k, eps));
+        GridVerdict built;                                       // (nobody to give up for: always Built)
+        PCT_TRY(pct_build_grid(ctx, k, eps, false, &built));
         const double t1 = debug ? tick() : 0;
         PCT_TRY(pct_reserve(ctx, &ctx->row_done, (size_t)owned * sizeof(int)));
         PCT_HIP(ctx, hipMemsetAsync(ctx->row_done.p, 0, (size_t)owned * sizeof(int), ctx->stream));
-        PCT_TRY(pct_launch_knn_grid(ctx, k, eps, exact, exact ? 0 : 1));
+        PCT_TRY(pct_launch_knn_grid(ctx, k, eps, exact, exact ? 0 : 1, true));      // (k_merge_rows below reads the distances)
         if (!exact) {
             // the stencil of a well-sized pass holds about 11 cells' worth of points on a surface
             PCT_LAUNCH(k_classify, dim3(1024), dim3(256), 0, ctx->stream, (const int*)ctx->row_done.p, (const int*)ctx->redo_m.p,
@@ -227,7 +228,7 @@ int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps) {
                                (float*)ctx->flag_buf.p, (float2*)ctx->dens_buf.p);
             PCT_HIP(ctx, hipGetLastError());
         }
-        if (ctx->levels_fuse_fit) PCT_TRY(pct_launch_fit_pass(ctx, owned));       // before the next pass reorders the cloud
+        if (fuse_par) PCT_TRY(pct_launch_fit_pass(ctx, owned, *fuse_par));       // before the next pass reorders the cloud
         const double t2 = debug ? tick() : 0;
         const int64_t total = owned * k;
         PCT_LAUNCH(k_merge_rows, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream,
@@ -343,6 +344,6 @@ int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps) {
     ctx->nbr_pitch = pitch;
     ctx->knn_sorted_space = false;
     ctx->tm.levels = passes;
-    ctx->levels_fitted = ctx->levels_fuse_fit;
+    if (fuse_par) ctx->fit_row_order = false;      // the passes fitted their rows: results in public order
     return PCT_OK;
 }

@@ -29,6 +29,7 @@
 // test_chain_of_cell_lists_equals_exhaustive_sweep[tree], the fuzzers).  The sort and the two scans are rocPRIM's
 // device primitives; everything else here is hand-written.
 #include "pct_internal.h"
+#include "pct_auto_route.h"
 
 #include <cstring>
 #include <math.h>
@@ -295,19 +296,15 @@ struct MaxInt {
 // Morton order, levels, segments, items and stencil ranges of the whole cloud (public rows [0, n) all owned).
 // Leaves: sorted4 (Morton order), owned_pos (identity: table row = Morton position), occ (items + sentinel),
 // tree_seg / tree_runs, grid = the FINEST level's grid, n_items.
-int pct_build_tree(pct_ctx* ctx, int32_t k, double eps, bool* usable) {
+int pct_build_tree(pct_ctx* ctx, int32_t k, double eps, const float* expect_bbox, TreeVerdict* out) {
     const int64_t n = ctx->n;
     float bbox[6];
-    *usable = false;
+    *out = TreeVerdict::Unusable;
     PCT_TRY(pct_pack_points(ctx, bbox));                 // pts4 (public order) + bounding box; refuses non-finite input
     if (ctx->n_grid != n) return pct_fail(ctx, PCT_ERR_INVALID, "the tree sweep needs the whole cloud packed");
-    if (ctx->tree_check_bbox) {          // PCT_KNN_AUTO came here on a remembered verdict: is this still that kind of cloud?
-        bool same = true;
-        for (int a = 0; a < 3; ++a) {
-            const float tol = 0.02f * (ctx->auto_tree_bbox[3 + a] - ctx->auto_tree_bbox[a]) + 1e-30f;
-            same = same && fabsf(bbox[a] - ctx->auto_tree_bbox[a]) <= tol && fabsf(bbox[3 + a] - ctx->auto_tree_bbox[3 + a]) <= tol;
-        }
-        if (!same) { ctx->tree_hint_mismatch = true; return PCT_OK; }
+    if (expect_bbox && !same_box(bbox, expect_bbox)) {       // PCT_KNN_AUTO came here on a remembered verdict: no longer that kind of cloud
+        *out = TreeVerdict::OtherCloud;
+        return PCT_OK;
     }
     for (int a = 0; a < 6; ++a) ctx->tree_bbox[a] = bbox[a];
     double ext = 0;
@@ -319,7 +316,7 @@ int pct_build_tree(pct_ctx* ctx, int32_t k, double eps, bool* usable) {
     // clouds; here they are left to it).
     const double fine2 = ldexp(root, -kTreeBits) * ldexp(root, -kTreeBits);
     if (!(fine2 > 1e-30) || !(root * root < 1e30) || (eps > 0 && !(eps * eps > 1e-36))) return PCT_OK;
-    *usable = true;
+    *out = TreeVerdict::Built;
     pct_grid g = {};
     g.ox = bbox[0]; g.oy = bbox[1]; g.oz = bbox[2];
     g.cell = ldexp(root, -kTreeBits);
