@@ -210,7 +210,12 @@ int pct_neighbor_study_curvatures(pct_ctx* ctx, const int64_t* sample_rows, int6
 /* load_mesh_compute_energies (utils.py:702-765), the consumer of K/H: bending energy sum(mean(H^2) * area),
  * stretching energy sum(mean(K) * area) (both nansum) and total area over a triangle mesh.  vertices (V,3)
  * float64, triangles (T,3) int32, curvature arrays (V) float32 (curvature_is_f64 == 0, what the path
- * produces) or float64; face means are taken in that dtype as NumPy does.  out3 = {bending, stretching, area}. */
+ * produces) or float64 (1); the two arrays may differ (2: K float64, H float32; 3: K float32, H float64).  Each face
+ * mean is taken in the dtype of its own array, as NumPy does.  No triangles: zeros.  out3 = {bending, stretching, area}. */
+#define PCT_MESH_F32 0
+#define PCT_MESH_F64 1
+#define PCT_MESH_K64_H32 2
+#define PCT_MESH_K32_H64 3
 int pct_mesh_energies(pct_ctx* ctx, const double* vertices, int64_t n_vertices, const int32_t* triangles,
                       int64_t n_triangles, const void* gaussian, const void* mean, int32_t curvature_is_f64,
                       double* out3);

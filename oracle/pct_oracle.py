@@ -359,9 +359,10 @@ def curvature_tolerance_ok(x, ref, floor, rtol=1e-5):
 
 # --------------------------------------------------------------------------
 # N3  load_mesh_compute_energies  (/root/reference/utils.py:702-765)
-# utils.py cannot be imported here (needs open3d / pyvista), so this restatement is pinned by the closed-form
-# energies the reference itself quotes (main_shape_validation.py:33-45: sphere 4*pi / 4*pi) -- "parity unpinned"
-# by a reference run.
+# utils.py cannot be imported here (needs open3d / pyvista), but the function definition compiles on its own:
+# oracle/make_goldens_energies.py runs the reference's own body on seeded meshes (tests/golden/g12_energies.npz) and
+# tests/test_aux_exact.py holds this restatement to it bit for bit -- pinned.  (The reference returns 0, 0, 0 where the
+# areas sum to zero, utils.py:731-733; the sums below are the same zeros there.)
 # --------------------------------------------------------------------------
 def mesh_energies(vertices, triangles, gaussian_curvature, mean_curvature):
     vertices = np.asarray(vertices)

@@ -24,6 +24,8 @@ PCT_ERR_K_TOO_LARGE = 5
 PCT_ERR_OOM = 6
 PCT_ERR_NO_NEIGHBORS = 7
 
+MESH_F32, MESH_F64, MESH_K64_H32, MESH_K32_H64 = 0, 1, 2, 3      # pct_mesh_energies' curvature_is_f64
+
 KNN_AUTO, KNN_BRUTE, KNN_GRID, KNN_GRID_EXACT, KNN_GRID_LEVELS, KNN_TREE = 0, 1, 2, 3, 4, 5
 
 
@@ -299,23 +301,25 @@ class Handle:
         else:
             p = np.ascontiguousarray(pts, dtype=np.float32)
             self._check(self._lib.pct_set_points_f32(self._h, _ptr(p, _f32p), len(p)))
-        self.n = len(p)
+        self.n = self._rows = len(p)                 # (a new cloud is owned whole: new_cloud, pct_api.hip)
 
     def set_points_device(self, dev_ptr, n):
         self._check(self._lib.pct_set_points_device_f32(self._h, _p(int(dev_ptr)), int(n)))
-        self.n = int(n)
+        self.n = self._rows = int(n)
 
     def use_points_device(self, dev_ptr, n):
         """Zero-copy variant: the caller keeps the buffer alive and unchanged while the handle uses it."""
         self._check(self._lib.pct_use_points_device_f32(self._h, _p(int(dev_ptr)), int(n)))
-        self.n = int(n)
+        self.n = self._rows = int(n)
 
     def set_query_range(self, begin, end):
         self._check(self._lib.pct_set_query_range(self._h, int(begin), int(end)))
+        self._rows = int(end) - int(begin)
 
     # -- ownership by slab (multi-GPU, clouds in no spatial order; include/pct_hip.h) --------------------------------
     def set_query_slab(self, part, parts):
         self._check(self._lib.pct_set_query_slab(self._h, int(part), int(parts)))
+        self._rows = self.n                          # (index ranges are dropped: pct_set_query_slab)
 
     def slab_counts(self, parts):
         out = (C.c_int64 * int(parts))()
@@ -453,15 +457,16 @@ class Handle:
     def mesh_energies(self, vertices, triangles, gaussian, mean):
         v = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
         t = np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 3)
-        f64 = np.asarray(gaussian).dtype == np.float64 and np.asarray(mean).dtype == np.float64
-        dt = np.float64 if f64 else np.float32
-        g = np.ascontiguousarray(gaussian, dtype=dt)
-        m = np.ascontiguousarray(mean, dtype=dt)
+        # each array in its own dtype, as np.mean takes it (utils.py:753-755): float64 stays float64 whatever the other is
+        k64, h64 = np.asarray(gaussian).dtype == np.float64, np.asarray(mean).dtype == np.float64
+        g = np.ascontiguousarray(gaussian, dtype=np.float64 if k64 else np.float32)
+        m = np.ascontiguousarray(mean, dtype=np.float64 if h64 else np.float32)
+        kind = MESH_F64 if k64 and h64 else MESH_K64_H32 if k64 else MESH_K32_H64 if h64 else MESH_F32
         if len(g) != len(v) or len(m) != len(v):
             raise ValueError("one curvature value per vertex is required")
         out = np.zeros(3, np.float64)
         self._check(self._lib.pct_mesh_energies(self._h, _ptr(v, _f64p), len(v), _ptr(t, _i32p), len(t), g.ctypes.data_as(_p),
-                                               m.ctypes.data_as(_p), int(f64), _ptr(out, _f64p)))
+                                               m.ctypes.data_as(_p), kind, _ptr(out, _f64p)))
         return float(out[0]), float(out[1]), float(out[2])
 
     def voxel_downsample(self, xyz, voxel_size):
@@ -479,7 +484,8 @@ class Handle:
         return idx[:cnt.value].copy()
 
     def surface_variation(self, k_total):
-        out = np.empty(self.n, np.float32)
+        """One value per OWNED row (the query range; the whole cloud unless ``set_query_range`` narrowed it)."""
+        out = np.empty(self._rows, np.float32)
         self._check(self._lib.pct_surface_variation(self._h, int(k_total), _ptr(out, _f32p)))
         self.k = int(k_total) - 1
         return out

@@ -2,9 +2,9 @@
 // (next row N3 of the scope table).  Restates load_mesh_compute_energies,
 // /root/reference/utils.py:702-765:
 //   area_t      = 0.5 * || (v1 - v0) x (v2 - v0) ||              float64      (utils.py:723-728)
-//   face_K_t    = mean(K[tri]), face_H2_t = mean((H**2)[tri])    in the dtype of the curvature arrays
+//   face_K_t    = mean(K[tri]), face_H2_t = mean((H**2)[tri])    each in the dtype of ITS curvature array
 //                                                                 (float32 when they come from the path,
-//                                                                  utils.py:741-752)
+//                                                                  utils.py:741-752; K and H need not agree)
 //   bending     = nansum(face_H2 * area), stretching = nansum(face_K * area), total = sum(area)
 //                                                                 (utils.py:755-757)
 // The reference recomputes the three sums inside its per-triangle loop (O(T^2), 43 % of its profiled run);
@@ -18,9 +18,9 @@ namespace {
 
 constexpr int kMeshBlock = 256;
 
-template <typename T>
+template <typename TK, typename TH>
 __global__ __launch_bounds__(kMeshBlock) void k_mesh_energy(const double* __restrict__ v, const int* __restrict__ tri, int64_t n_tri,
-                                                            const T* __restrict__ K, const T* __restrict__ H,
+                                                            const TK* __restrict__ K, const TH* __restrict__ H,
                                                             double* __restrict__ partial) {
     double bend = 0, stretch = 0, area_sum = 0;
     for (int64_t t = (int64_t)blockIdx.x * kMeshBlock + threadIdx.x; t < n_tri; t += (int64_t)gridDim.x * kMeshBlock) {
@@ -29,10 +29,9 @@ __global__ __launch_bounds__(kMeshBlock) void k_mesh_energy(const double* __rest
         const double bx = v[3 * i2] - v[3 * i0], by = v[3 * i2 + 1] - v[3 * i0 + 1], bz = v[3 * i2 + 2] - v[3 * i0 + 2];
         const double cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
         const double area = 0.5 * sqrt((cx * cx + cy * cy) + cz * cz);
-        const T three = (T)3;
-        const T fk = ((K[i0] + K[i1]) + K[i2]) / three;                       // np.mean in the array's dtype
-        const T h0 = H[i0], h1 = H[i1], h2 = H[i2];
-        const T fh2 = ((h0 * h0 + h1 * h1) + h2 * h2) / three;
+        const TK fk = ((K[i0] + K[i1]) + K[i2]) / (TK)3;                      // np.mean in the array's dtype
+        const TH h0 = H[i0], h1 = H[i1], h2 = H[i2];
+        const TH fh2 = ((h0 * h0 + h1 * h1) + h2 * h2) / (TH)3;
         const double pb = (double)fh2 * area, ps = (double)fk * area;
         bend += isnan(pb) ? 0.0 : pb;                                          // nansum
         stretch += isnan(ps) ? 0.0 : ps;
@@ -65,13 +64,15 @@ __global__ __launch_bounds__(64) void k_mesh_final(const double* __restrict__ pa
 }  // namespace
 
 int pct_launch_mesh_energies(pct_ctx* ctx, const double* d_v, const int* d_tri, int64_t n_tri, const void* d_K, const void* d_H,
-                             bool f64, double* d_partial, int nblk, double* d_out) {
-    if (f64)
-        PCT_LAUNCH(k_mesh_energy<double>, dim3(nblk), dim3(kMeshBlock), 0, ctx->stream, d_v, d_tri, n_tri,
-                           (const double*)d_K, (const double*)d_H, d_partial);
-    else
-        PCT_LAUNCH(k_mesh_energy<float>, dim3(nblk), dim3(kMeshBlock), 0, ctx->stream, d_v, d_tri, n_tri,
-                           (const float*)d_K, (const float*)d_H, d_partial);
+                             bool k_f64, bool h_f64, double* d_partial, int nblk, double* d_out) {
+#define PCT_MESH_LAUNCH(TK, TH)                                                                                     \
+    PCT_LAUNCH((k_mesh_energy<TK, TH>), dim3(nblk), dim3(kMeshBlock), 0, ctx->stream, d_v, d_tri, n_tri, (const TK*)d_K, \
+               (const TH*)d_H, d_partial)
+    if (k_f64 && h_f64) PCT_MESH_LAUNCH(double, double);
+    else if (k_f64) PCT_MESH_LAUNCH(double, float);
+    else if (h_f64) PCT_MESH_LAUNCH(float, double);
+    else PCT_MESH_LAUNCH(float, float);
+#undef PCT_MESH_LAUNCH
     PCT_LAUNCH(k_mesh_final, dim3(1), dim3(64), 0, ctx->stream, (const double*)d_partial, nblk, d_out);
     PCT_HIP(ctx, hipGetLastError());
     return PCT_OK;

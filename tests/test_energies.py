@@ -1,8 +1,9 @@
 """N3: mesh energy integrals, the consumer of the path's K/H (utils.py:702-765).
 
-utils.py cannot be imported in the build container (open3d / pyvista missing), so the restatement in
-oracle/pct_oracle.py is pinned by the closed-form values the reference quotes for its validation shapes
-(main_shape_validation.py:33-45: sphere bending 4*pi, stretching 4*pi) -- parity unpinned by a reference run.
+The restatement in oracle/pct_oracle.py is pinned by a run of the reference's own function body
+(tests/golden/g12_energies.npz, tests/test_aux_exact.py) and, here, by the closed-form values the reference quotes for
+its validation shapes (main_shape_validation.py:33-45: sphere bending 4*pi, stretching 4*pi).  The kernel's launch edges,
+dtypes and bars: tests/test_gpu_aux.py.
 """
 import types
 
