@@ -37,7 +37,7 @@ const char* pct_launch_name(const char* where, const char* instantiation);
     } while (0)
 
 // Staging capacities of the fast sweeps (candidates of a work item's stencil held in LDS per wave), defined HERE ONLY:
-// the sweep kernels (pct_knn.hip) are compiled for them, the work-item census counts overflows against them and the
+// the sweep kernels (pct_knn_fast.hip, pct_knn_pair.hip, pct_knn_duo.hip) are compiled for them, the work-item census counts overflows against them and the
 // hierarchical list's build (pct_tree.hip) refines its segments down to them.  A -D that overrides one must reach EVERY
 // translation unit (PCT_EXTRA_FLAGS does; a per-file flag would size the tree's refinement for another capacity than
 // the kernels stage).

@@ -1,10 +1,11 @@
-// Shared by pct_knn.hip and pct_knn_wide.hip: the wave-per-query sweeps (exact sweep over the cell list, exhaustive
+// Shared by pct_knn.hip, the fast sweeps' files (pct_knn_fast.hip, pct_knn_pair.hip, pct_knn_duo.hip) and pct_knn_wide.hip: the wave-per-query sweeps (exact sweep over the cell list, exhaustive
 // sweep) and what they are built from -- the running list of 64 R (fp64 d2, sorted position) elements, its bitonic
 // network, the shell iterator over the cell list, the radius a searched cube vouches for.  R = 1, 2 are instantiated
 // in pct_knn.hip; R = 4, 8 (rows of up to 511 neighbours: cKDTree.query takes any k, pct:83) in pct_knn_wide.hip, a
 // translation unit of its own so that the hot kernels' file does not pay their compile time.
 #pragma once
 #include "pct_internal.h"
+#include "pct_sweep_plan.h"
 
 #include <math.h>
 #include <type_traits>
@@ -45,6 +46,11 @@ struct KnnArgs {
 // rows of 128 .. PCT_K_MAX neighbours (pct_knn_wide.hip): list registers R = 4 | 8
 int pct_launch_knn_exact_wide(pct_ctx* ctx, const KnnArgs& a, int blocks, const int* list, const int* list_count);
 int pct_launch_knn_brute_wide(pct_ctx* ctx, const KnnArgs& a, int blocks);
+// the fast sweeps, one translation unit per family (pct_knn_fast.hip, pct_knn_pair.hip, pct_knn_duo.hip): the launch of
+// the instantiation the plan names; errors are picked up by the caller (launch_sweep, pct_knn.hip)
+void pct_launch_sweep_fast(pct_ctx* ctx, const SweepPlan& p, const KnnArgs& a, int* redo, int* redo_count);
+void pct_launch_sweep_pair(pct_ctx* ctx, const SweepPlan& p, const KnnArgs& a, int* redo, int* redo_count);
+void pct_launch_sweep_duo(pct_ctx* ctx, const SweepPlan& p, const KnnArgs& a, int* redo, int* redo_count);
 
 namespace {
 

@@ -5,7 +5,7 @@
 // Morton code of their position in a 2^21-cube over the bounding box.  A cell of ANY octree level is then a
 // contiguous range of the sorted cloud, and so is every cell of its 27-cell stencil: the fast sweep stages 27 ranges
 // instead of 9 x-runs and everything behind the staging -- pre-selection, keys, network, proofs -- is the code the
-// uniform cell list runs (k_knn_fast<..., TREE>, pct_knn.hip).
+// uniform cell list runs (k_knn_pair / k_knn_duo / k_knn_fast<..., TREE>; pct_knn_item.h: load_item_head).
 //
 //   level of a point   first guess: the finest level whose cell around it holds >= n_min points (n_min ~ 0.45 (k+1):
 //                      on a surface the disc the 27-cell cube vouches for then holds about k+1).  Found without a

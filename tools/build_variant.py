@@ -1,5 +1,5 @@
 """Developer tool: an A/B build of the library with extra flags on chosen sources, next to the real one.
-    python tools/build_variant.py OUT.so pct_knn.hip=-DPCT_ABL_NO_SORT [pct_fit.hip=-DX ...]
+    python tools/build_variant.py OUT.so pct_knn_pair.hip=-DPCT_ABL_NO_SORT [pct_fit.hip=-DX ...]
     PCT_LIB=$PWD/OUT.so python bench.py --no-cpu-baseline --no-extras
 Objects are cached under csrc/.obj, so only the named sources are recompiled."""
 import os, sys

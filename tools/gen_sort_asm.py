@@ -3,7 +3,7 @@
 
     python tools/gen_sort_asm.py > point-cloud-toolbox_amd/csrc/pct_sort_pair.inc
 
-The network is the flip form of the bitonic sort (pct_knn.hip: fast_sort_sets): a merge of SIZE elements compares
+The network is the flip form of the bitonic sort (pct_knn_net.h: fast_sort_sets): a merge of SIZE elements compares
 element i with i ^ (SIZE - 1), then runs strides SIZE/4 .. 1; every compare-exchange leaves the smaller element at
 the lower lane, so "keep min or max" is one bit of the lane id (sel0..sel5 = all ones where that bit is set) and a
 level is  partner move + v_med3_u32(e, partner, sel).  What the compiler made of the C++ form: one shared temporary

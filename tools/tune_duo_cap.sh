@@ -1,4 +1,4 @@
-# developer tool: k_knn_duo with 768 (default) against 1024 staged slots (python tools/build_variant.py variants/duo1024.so pct_knn.hip=-DPCT_DUO_CAP=1024)
+# developer tool: k_knn_duo with 768 (default) against 1024 staged slots (python tools/build_variant.py variants/duo1024.so pct_knn_duo.hip=-DPCT_DUO_CAP=1024)
 # over the occupancy factor at k = 80 / 100 / 127 -- 1024 slots (3 waves per SIMD) lose at k = 80 (0.74 vs 0.62 ms), tie at 100, win at 127 (1.26 vs 2.54)
 for lib in "" variants/duo1024.so; do
   if [ -n "$lib" ]; then export PCT_LIB=$PWD/$lib; else unset PCT_LIB; fi
