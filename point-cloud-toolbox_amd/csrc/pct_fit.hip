@@ -11,9 +11,10 @@
 // own row from global instead was measured 2x slower), then every lane walks
 // its own row twice, gathers issued eight neighbours ahead of their use:
 //   pass 1  centred neighbours (native dtype, pct:641) -> fp64 sums about the
-//           first neighbour -> 3x3 covariance, ddof=1 (pct:277) -> cyclic
-//           Jacobi eigen-solve -> normal = eigenvector of the smallest
-//           eigenvalue (== Vt[-1], pct:283) -> sign flip by far-minus-near
+//           first neighbour -> 3x3 covariance, ddof=1 (pct:277) -> normal =
+//           eigenvector of the smallest eigenvalue (== Vt[-1], pct:283;
+//           direct_normal(), cyclic Jacobi where that row is not healthy)
+//           -> sign flip by far-minus-near
 //           neighbour (pct:286-297) -> Rodrigues rotation to +z (pct:300-312)
 //   pass 2  rotate (pct:315), round to float32 (pct:350), float32 design row
 //           [a^2,b^2,ab,a,b,1] (pct:358), fp64 normal equations, Cholesky
@@ -59,6 +60,7 @@ struct FitArgs {
     unsigned n_pts;          // records in pts: a table entry outside [0, n_pts) is never dereferenced (the row reads NaN)
     const int* row_mask;     // MASKED instantiation: only the rows with a non-zero entry are fitted (passes of the density-adaptive sweep)
     int svd_accumulate;      // the count of rows handed to k_fit_svd is ADDED to the host word (the passes of one fused call)
+    int force_jacobi;        // PCT_FIT_JACOBI=1: every row's normal through the cyclic Jacobi (A/B runs, route-against-route tests)
     int blocks_per_xcd;      // blocks are dealt to the 8 XCDs in turn: block b takes rows of block (b % 8) * blocks_per_xcd + b / 8, so
                              // that one XCD's L2 serves neighbouring rows (table rows are in cell order: their neighbours overlap)
 };
@@ -120,56 +122,131 @@ __device__ __forceinline__ void load_centred(const FitArgs& a, int id, double qx
     }
 }
 
+// The direct route to the normal: what the cyclic Jacobi is not needed for.  tests/test_eig_direct_route.py states it
+// operation for operation on the CPU and holds it to the exact reference; change the two together.
+constexpr int kNewtonCap = 6;                        // steps; a torus neighbourhood takes 2, l3 = l2 / 2 takes 6
+constexpr double kNewtonTol = 0x1p-14;               // |step| c2 <= kNewtonTol f': the refinement squares what is left
+constexpr double kCrossFloor = 1e-4;                 // |largest cross product| >= kCrossFloor trace^2
+
+// The largest (squared norm, the first of equal ones) of the cross products r0 x r1, r0 x r2, r1 x r2 of the rows of a
+// symmetric 3x3: for a matrix of rank two, its null vector.  Returns the squared norm.
+__device__ __forceinline__ double largest_row_cross(double b00, double b01, double b02, double b11, double b12, double b22,
+                                                    double& n0, double& n1, double& n2) {
+    n0 = b01 * b12 - b02 * b11; n1 = b02 * b01 - b00 * b12; n2 = b00 * b11 - b01 * b01;          // r0 x r1
+    double best = (n0 * n0 + n1 * n1) + n2 * n2;
+    {
+        const double c0 = b01 * b22 - b02 * b12, c1 = b02 * b02 - b00 * b22, c2 = b00 * b12 - b01 * b02;   // r0 x r2
+        const double nn = (c0 * c0 + c1 * c1) + c2 * c2;
+        if (nn > best) { n0 = c0; n1 = c1; n2 = c2; best = nn; }
+    }
+    {
+        const double c0 = b11 * b22 - b12 * b12, c1 = b12 * b02 - b01 * b22, c2 = b01 * b12 - b11 * b02;   // r1 x r2
+        const double nn = (c0 * c0 + c1 * c1) + c2 * c2;
+        if (nn > best) { n0 = c0; n1 = c1; n2 = c2; best = nn; }
+    }
+    return best;
+}
+
+// Unit eigenvector of the smallest eigenvalue of a symmetric positive semi-definite 3x3, without the Jacobi sweeps:
+//   the matrix scaled by the exact power of two that brings its trace into [1/2, 1) (the cubic's coefficients are
+//   products of three eigenvalues: unscaled, a neighbourhood of radius 1e-70 underflows);
+//   l3 = the smallest root of x^3 - c2 x^2 + c1 x - c0 by Newton from 0 (increasing and concave up to l3: monotone from
+//   the left, quadratic at a simple root);
+//   n = the largest cross product of two rows of A - l3 I;
+//   once more with l3 + n^T (A - l3 I) n / n^T n, the Rayleigh quotient of n: the error of the normal becomes
+//   eps l1 / gap3 where the cubic alone leaves eps (l1 / gap3)(l1 / l2);  one reciprocal square root.
+// false: the row is not healthy -- f' not positive, no converged step within the cap, a cross product below the floor
+// (near-equal small eigenvalues, lines, points, non-finite sums) -- and takes the Jacobi.
+__device__ __forceinline__ bool direct_normal(double a00, double a01, double a02, double a11, double a12, double a22,
+                                              double& n0, double& n1, double& n2) {
+    const double tr = (a00 + a11) + a22;
+    if (!(tr > 0.0 && tr < (double)INFINITY)) return false;
+    int e;
+    (void)frexp(tr, &e);
+    a00 = ldexp(a00, -e); a01 = ldexp(a01, -e); a02 = ldexp(a02, -e);
+    a11 = ldexp(a11, -e); a12 = ldexp(a12, -e); a22 = ldexp(a22, -e);
+    const double c2 = (a00 + a11) + a22;
+    const double m01 = a00 * a11 - a01 * a01, m02 = a00 * a22 - a02 * a02, m12 = a11 * a22 - a12 * a12;
+    const double c1 = (m01 + m02) + m12;
+    const double c0 = (a00 * m12 - a01 * (a01 * a22 - a12 * a02)) + a02 * (a01 * a12 - a11 * a02);
+    double lam = 0.0;
+    bool ok = false;
+#pragma unroll 1
+    for (int it = 0; it < kNewtonCap; ++it) {
+        const double f = ((lam - c2) * lam + c1) * lam - c0;
+        const double fp = (3.0 * lam - 2.0 * c2) * lam + c1;
+        if (!(fp > 0.0)) break;
+        const double step = f / fp;
+        lam -= step;
+        if (fabs(step) * c2 <= kNewtonTol * fp) { ok = true; break; }
+    }
+    const double floor2 = (kCrossFloor * (c2 * c2)) * (kCrossFloor * (c2 * c2));
+    double nn = largest_row_cross(a00 - lam, a01, a02, a11 - lam, a12, a22 - lam, n0, n1, n2);
+    if (!(ok && nn >= floor2)) return false;
+    {
+        const double b00 = a00 - lam, b11 = a11 - lam, b22 = a22 - lam;
+        const double w0 = (b00 * n0 + a01 * n1) + a02 * n2;
+        const double w1 = (a01 * n0 + b11 * n1) + a12 * n2;
+        const double w2 = (a02 * n0 + a12 * n1) + b22 * n2;
+        lam = lam + ((w0 * n0 + w1 * n1) + w2 * n2) / nn;
+    }
+    nn = largest_row_cross(a00 - lam, a01, a02, a11 - lam, a12, a22 - lam, n0, n1, n2);
+    if (!(nn >= floor2)) return false;
+    const double inv = rsqrt(nn);
+    n0 *= inv; n1 *= inv; n2 *= inv;
+    return true;
+}
+
 // Tangent-plane rotation from the moment sums of one centred neighbourhood:
-// covariance about the neighbour mean with ddof=1 (pct:277), cyclic Jacobi,
-// normal = eigenvector of the smallest eigenvalue (== Vt[-1], pct:283), sign
-// flip by the far-minus-near reference vector (pct:286-297), Rodrigues rotation
-// taking the normal to +z (pct:300-312).  rot = {r00,r01,r02, r10,.., r22}.
+// covariance about the neighbour mean with ddof=1 (pct:277), normal = unit
+// eigenvector of the smallest eigenvalue (== Vt[-1], pct:283) -- direct_normal()
+// on healthy rows, the cyclic Jacobi on the others and on every row when
+// force_jacobi is set (PCT_FIT_JACOBI=1) --, sign flip by the far-minus-near
+// reference vector (pct:286-297), Rodrigues rotation taking the normal to +z
+// (pct:300-312).  rot = {r00,r01,r02, r10,.., r22}.
 template <bool F64>
 __device__ __forceinline__ void plane_rotation(int m, double sx, double sy, double sz, double sxx, double sxy, double sxz,
                                                double syy, double syz, double szz, double fx, double fy, double fz,
-                                               double lx, double ly, double lz, double (&rot)[9]) {
+                                               double lx, double ly, double lz, bool force_jacobi, double (&rot)[9]) {
     const double inv_m = 1.0 / (double)m, inv_m1 = 1.0 / (double)(m - 1);
     const double mx = sx * inv_m, my_ = sy * inv_m, mz = sz * inv_m;
     double a00 = (sxx - sx * mx) * inv_m1, a01 = (sxy - sx * my_) * inv_m1, a02 = (sxz - sx * mz) * inv_m1;
     double a11 = (syy - sy * my_) * inv_m1, a12 = (syz - sy * mz) * inv_m1, a22 = (szz - sz * mz) * inv_m1;
 
-    // ---- cyclic Jacobi on the symmetric 3x3 --------------------------------
-    double v00 = 1, v01 = 0, v02 = 0, v10 = 0, v11 = 1, v12 = 0, v20 = 0, v21 = 0, v22 = 1;   // v[row][col]
+    double n0, n1, n2;          // the unit normal, normalised here once and nowhere below
+    if (force_jacobi || !direct_normal(a00, a01, a02, a11, a12, a22, n0, n1, n2)) {
+        // ---- cyclic Jacobi on the symmetric 3x3 ----------------------------
+        double v00 = 1, v01 = 0, v02 = 0, v10 = 0, v11 = 1, v12 = 0, v20 = 0, v21 = 0, v22 = 1;   // v[row][col]
 #pragma unroll 1
-    for (int sweep = 0; sweep < 8; ++sweep) {
-        // off-diagonal mass below 1e-22 of the trace: eigenvectors are converged far beyond fp64 round-off
-        const double off = fabs(a01) + fabs(a02) + fabs(a12);
-        if (off <= 1e-22 * (fabs(a00) + fabs(a11) + fabs(a22))) break;
-        JACOBI_ROT(a00, a11, a01, a02, a12, v00, v10, v20, v01, v11, v21);   // (p,q)=(0,1), r=2
-        JACOBI_ROT(a00, a22, a02, a01, a12, v00, v10, v20, v02, v12, v22);   // (0,2), r=1
-        JACOBI_ROT(a11, a22, a12, a01, a02, v01, v11, v21, v02, v12, v22);   // (1,2), r=0
+        for (int sweep = 0; sweep < 8; ++sweep) {
+            // off-diagonal mass below 1e-22 of the trace: eigenvectors are converged far beyond fp64 round-off
+            const double off = fabs(a01) + fabs(a02) + fabs(a12);
+            if (off <= 1e-22 * (fabs(a00) + fabs(a11) + fabs(a22))) break;
+            JACOBI_ROT(a00, a11, a01, a02, a12, v00, v10, v20, v01, v11, v21);   // (p,q)=(0,1), r=2
+            JACOBI_ROT(a00, a22, a02, a01, a12, v00, v10, v20, v02, v12, v22);   // (0,2), r=1
+            JACOBI_ROT(a11, a22, a12, a01, a02, v01, v11, v21, v02, v12, v22);   // (1,2), r=0
+        }
+        if (a00 <= a11 && a00 <= a22) { n0 = v00; n1 = v10; n2 = v20; }
+        else if (a11 <= a22)          { n0 = v01; n1 = v11; n2 = v21; }
+        else                          { n0 = v02; n1 = v12; n2 = v22; }
+        const double nn = sqrt((n0 * n0 + n1 * n1) + n2 * n2);
+        n0 = n0 / nn; n1 = n1 / nn; n2 = n2 / nn;
     }
-    double n0, n1, n2;
-    if (a00 <= a11 && a00 <= a22) { n0 = v00; n1 = v10; n2 = v20; }
-    else if (a11 <= a22)          { n0 = v01; n1 = v11; n2 = v21; }
-    else                          { n0 = v02; n1 = v12; n2 = v22; }
 
     // ---- orientation: far-minus-near neighbour (pct:286-297) ---------------
+    // the sign of n . r with r as subtracted: normalising r changes no sign, r == 0 gives 0 (no flip), NaN compares false
     double rx, ry, rz;
     if (F64) { rx = lx - fx; ry = ly - fy; rz = lz - fz; }
     else     { rx = (double)((float)lx - (float)fx); ry = (double)((float)ly - (float)fy); rz = (double)((float)lz - (float)fz); }
-    {
-        const double nn = sqrt((n0 * n0 + n1 * n1) + n2 * n2);
-        const double rn = sqrt((rx * rx + ry * ry) + rz * rz);
-        const double dot = ((n0 / nn) * (rx / rn) + (n1 / nn) * (ry / rn)) + (n2 / nn) * (rz / rn);
-        if (dot < 0) { n0 = -n0; n1 = -n1; n2 = -n2; }
-    }
+    if ((n0 * rx + n1 * ry) + n2 * rz < 0) { n0 = -n0; n1 = -n1; n2 = -n2; }
     // ---- Rodrigues rotation taking the normal to +z (pct:300-312) -----------
     double r00 = 1, r01 = 0, r02 = 0, r10 = 0, r11 = 1, r12 = 0, r20 = 0, r21 = 0, r22 = 1;
     {
-        const double nn = sqrt((n0 * n0 + n1 * n1) + n2 * n2);
-        const double ax = n0 / nn, ay = n1 / nn, az = n2 / nn;
-        const double v0 = ay, v1 = -ax;                    // a x (0,0,1)
-        const double c = az;
-        const double s = sqrt(v0 * v0 + v1 * v1);
-        if (s != 0.0) {
-            const double f = (1.0 - c) / (s * s);
+        const double v0 = n1, v1 = -n0;                    // a x (0,0,1)
+        const double c = n2;
+        const double ss = v0 * v0 + v1 * v1;               // s^2; s != 0 exactly where ss != 0
+        if (ss != 0.0) {
+            const double f = (1.0 - c) / ss;
             r00 = 1.0 + (-(v1 * v1)) * f;  r01 = (v1 * v0) * f;            r02 = v1;
             r10 = (v0 * v1) * f;           r11 = 1.0 + (-(v0 * v0)) * f;   r12 = -v0;
             r20 = -v1;                     r21 = v0;                       r22 = 1.0 + (-(v1 * v1) + -(v0 * v0)) * f;
@@ -312,7 +389,7 @@ __global__ __launch_bounds__(kFitBlock) void k_fit(FitArgs a) {
         return;
     }
     double rot[9];
-    plane_rotation<F64>(m, sx, sy, sz, sxx, sxy, sxz, syy, syz, szz, fx, fy, fz, lx, ly, lz, rot);
+    plane_rotation<F64>(m, sx, sy, sz, sxx, sxy, sxz, syy, syz, szz, fx, fy, fz, lx, ly, lz, a.force_jacobi != 0, rot);
     const double r00 = rot[0], r01 = rot[1], r02 = rot[2], r10 = rot[3], r11 = rot[4], r12 = rot[5], r20 = rot[6], r21 = rot[7], r22 = rot[8];
 
     // ---- pass 2: float32 design rows -> scaled fp64 normal equations --------
@@ -588,7 +665,7 @@ __global__ __launch_bounds__(64) void k_fit_svd(FitArgs a, const int* __restrict
             syy = fma(dy, dy, syy); syz = fma(dy, dz, syz); szz = fma(dz, dz, szz);
         }
         double rot[9];
-        plane_rotation<F64>(m, sx, sy, sz, sxx, sxy, sxz, syy, syz, szz, fx, fy, fz, lx, ly, lz, rot);
+        plane_rotation<F64>(m, sx, sy, sz, sxx, sxy, sxz, syy, syz, szz, fx, fy, fz, lx, ly, lz, a.force_jacobi != 0, rot);
 
         // ---- pass 2: the design rows, one by one ---------------------------------------------------------------
         Lstsq6 ls;
@@ -634,7 +711,8 @@ __global__ __launch_bounds__(64) void k_fit_svd(FitArgs a, const int* __restrict
 //   k_quadric_rows   fit_quadratic_surface (pct:331-360): float32 points -> lstsq (gelsd semantics) -> float32 (6,)
 // ---------------------------------------------------------------------------
 template <bool F64>
-__global__ __launch_bounds__(64) void k_plane_rotate(const void* __restrict__ nbrs, int64_t batch, int m, double* __restrict__ out) {
+__global__ __launch_bounds__(64) void k_plane_rotate(const void* __restrict__ nbrs, int64_t batch, int m, int force_jacobi,
+                                                     double* __restrict__ out) {
     const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (b >= batch) return;
     const auto at = [&](int j, double& x, double& y, double& z) {
@@ -656,7 +734,7 @@ __global__ __launch_bounds__(64) void k_plane_rotate(const void* __restrict__ nb
     at(0, fx, fy, fz);
     at(m - 1, lx, ly, lz);
     double rot[9];
-    plane_rotation<F64>(m, 0.0, 0.0, 0.0, sxx, sxy, sxz, syy, syz, szz, fx, fy, fz, lx, ly, lz, rot);
+    plane_rotation<F64>(m, 0.0, 0.0, 0.0, sxx, sxy, sxz, syy, syz, szz, fx, fy, fz, lx, ly, lz, force_jacobi != 0, rot);
     for (int j = 0; j < m; ++j) {
         double x, y, z;
         at(j, x, y, z);
@@ -719,6 +797,12 @@ __global__ __launch_bounds__(256) void k_gather_fit(const int* __restrict__ row_
     if (o_H2) o_H2[i] = H2[r];
 }
 
+// PCT_FIT_JACOBI=1 (read per call): the normal of every row through the cyclic Jacobi, the route before direct_normal()
+int fit_jacobi_forced() {
+    const char* e = pct_getenv("PCT_FIT_JACOBI");
+    return e && e[0] == '1' ? 1 : 0;
+}
+
 // slot: the pinned slots of the call (FitSlot); *mirrored (may be null): the fit kernel mirrors the statistics words
 int launch(pct_ctx* ctx, const FitArgs& a0, bool f64, FitSlot slot, bool* mirrored) {
     FitArgs a = a0;
@@ -731,6 +815,7 @@ int launch(pct_ctx* ctx, const FitArgs& a0, bool f64, FitSlot slot, bool* mirror
     int blocks = (int)((a.rows + kFitBlock - 1) / kFitBlock);
     if (blocks <= 0) return PCT_OK;
     a.blocks_per_xcd = pct_getenv("PCT_NO_XCD_MAP") ? 0 : (blocks + 7) / 8;
+    a.force_jacobi = fit_jacobi_forced();
     if (a.blocks_per_xcd) blocks = a.blocks_per_xcd * 8;
     // rows for k_fit_svd: list + its length (first word of the buffer's 64-byte head)
     // two counts used in turn: a launch counts in one and clears the other for the launch after it (both cleared once per
@@ -929,10 +1014,11 @@ int pct_launch_curvatures(pct_ctx* ctx, const float* d_coefs, int64_t rows, floa
 
 int pct_launch_plane_rotate(pct_ctx* ctx, const void* d_nbrs, bool f64, int64_t batch, int32_t m, double* d_out) {
     const unsigned blocks = (unsigned)((batch + 63) / 64);
+    const int jacobi = fit_jacobi_forced();
     if (f64)
-        PCT_LAUNCH(k_plane_rotate<true>, dim3(blocks), dim3(64), 0, ctx->stream, d_nbrs, batch, m, d_out);
+        PCT_LAUNCH(k_plane_rotate<true>, dim3(blocks), dim3(64), 0, ctx->stream, d_nbrs, batch, m, jacobi, d_out);
     else
-        PCT_LAUNCH(k_plane_rotate<false>, dim3(blocks), dim3(64), 0, ctx->stream, d_nbrs, batch, m, d_out);
+        PCT_LAUNCH(k_plane_rotate<false>, dim3(blocks), dim3(64), 0, ctx->stream, d_nbrs, batch, m, jacobi, d_out);
     PCT_HIP(ctx, hipGetLastError());
     return PCT_OK;
 }
