@@ -256,8 +256,9 @@ __device__ __forceinline__ void plane_rotation(int m, double sx, double sy, doub
     rot[0] = r00; rot[1] = r01; rot[2] = r02; rot[3] = r10; rot[4] = r11; rot[5] = r12; rot[6] = r20; rot[7] = r21; rot[8] = r22;
 }
 
-// STAGED = false: rows too long for the LDS staging area (k > 255, only reachable through caller-supplied rows:
-// pct_fit_indices takes any k the reference's fit would) are walked in global memory instead.
+// STAGED = false: rows too long for the LDS staging area (k > 255) are walked in global memory instead.  Both tables
+// get here: the resident one of the wide sweeps (k = 256 .. 511: sorted-space positions, the table's pitch, float64
+// clouds, eps counts) and caller-supplied rows (pct_fit_indices takes any k the reference's fit would).
 // MASKED: a compile-time variant, so that the row test leaves the hot instantiation's register allocation alone.
 template <bool F64, bool OUT64 = false, bool STAGED = true, bool MASKED = false>
 __global__ __launch_bounds__(kFitBlock) void k_fit(FitArgs a) {

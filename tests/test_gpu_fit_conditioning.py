@@ -6,7 +6,7 @@ checks on the CPU that the reference itself meets them.  Here the kernels do:
   (a) k_quadric_rows (always the SVD)           -- Handle.fit_quadric on every rung, m = 6, 7, 8, 50, 300
   (b) k_fit and its hand-over to k_fit_svd      -- the paired blocks as clouds through Handle.fit_indices, float32 / float64
   (c) the unrounded variant                     -- Handle.fit_indices_f64, against the conditioning term alone
-  (d) row lengths 0 ... 300, staged and unstaged, garbage behind the count
+  (d) row lengths 0 ... 512, staged and unstaged, garbage behind the count
   (e) row position: XCD block map, partial last block, SVD list spanning waves -- identical bits wherever a row sits
   (f) queries 0 ... 1 000 radii outside their neighbourhood
   (g) the float32 curvature formulas over coefficient space
@@ -118,16 +118,16 @@ def test_unrounded_fit_against_the_conditioning_term_alone(handle, m, dtype):
 
 
 # ---------------------------------------------------------------------------------------------------- (d) row lengths
-LENGTHS = tuple(range(0, 41)) + (63, 64, 65, 127, 128, 255, 256, 300)
+LENGTHS = tuple(range(0, 41)) + (63, 64, 65, 127, 128, 255, 256, 300, 448, 511, 512)
 
 
-@pytest.mark.parametrize("width", [40, 64, 65, 128, 255, 256, 300])
+@pytest.mark.parametrize("width", [40, 64, 65, 128, 255, 256, 300, 448, 511, 512])
 def test_row_lengths_with_garbage_behind_the_count(handle, gpu, width):
     """Rows of every length in one table (count array), the unused entries holding -1 and indices far outside the cloud.
-    width <= 255 is staged in LDS, 256 and 300 are walked in global memory.  Each row against the reference loop on its
+    width <= 255 is staged in LDS, 256 ... 512 are walked in global memory (512: one past the longest row a sweep writes).  Each row against the reference loop on its
     valid prefix; 2 ... 5 neighbours against lstsq's minimum-norm answer; 0 and 1 read NaN."""
     pts = gpu["shapes"].torus_random(3000, seed=21)
-    full, _ = oracle.knn(pts, 300)
+    full, _ = oracle.knn(pts, 512)                  # (a tie-free cloud: the row for a width is a prefix of this one)
     lengths = [n for n in LENGTHS if n <= width]
     rng = np.random.default_rng(width)
     query = rng.choice(len(pts), 3 * len(lengths), replace=False).astype(np.int64)

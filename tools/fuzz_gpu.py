@@ -1,5 +1,9 @@
 """Randomised cross-check of the grid sweep (plain, sharded, chained) against the exhaustive sweep (developer tool).
-python tools/fuzz_gpu.py [seconds] [seed]"""
+python tools/fuzz_gpu.py [seconds] [seed]
+
+The draw stops at k = 127 (the fixed-seed slices in the suite depend on it): rows of 128 ... 511 neighbours, the
+wave-per-query sweeps with 256- and 512-entry lists and the unstaged fit of their table, are held to an exact reference
+by tests/test_gpu_wide_rows.py."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
