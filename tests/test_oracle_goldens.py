@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import pct_oracle as oracle
+import study_exact as se
 
 FULL = ["g1_sphere2k_k30.npz", "g2_torus4k_k50.npz", "g3_egg4k_k50.npz",
         "g4_bunny4k_file_k30.npz", "g5_egggrid64_k30.npz"]
@@ -79,6 +80,55 @@ def test_neighbor_study(golden):
     g8 = golden("g8_neighbor_study.npz")
     res, _ = oracle.neighbor_study(g2["points"], g8["sample"])
     assert res == int(g8["result"])
+
+
+def _g13_study(golden, tag):
+    """One reference table per cloud of G13 for the per-seed draws and the three whole samples (228 rows, n = 3 ... 100):
+    shared by the tests of this process."""
+    g = golden("g13_neighbor_study.npz")
+    rows = np.concatenate([g["draw" + tag], g["whole_draw" + tag].ravel()])
+    return g, se.cached(("g13", tag), lambda: se.Study(g["points" + tag], rows, 3, 100, full=False))
+
+
+@pytest.mark.parametrize("tag", ("32", "64"))
+def test_neighbor_study_where_the_bisection_decides(golden, tag):
+    """G13 (oracle/make_goldens_study.py): the unmodified reference at tolerances where its bisection stops anywhere
+    between the bounds -- one converged count per seed (sample_size = 1) and three whole samples of 60, on a float32
+    torus and on a float64 copy that shows float32 rounding.  oracle.neighbor_study and the restatement of
+    tests/study_exact.py (table + bisect) reproduce every recorded number exactly: same NumPy, tie-free clouds.
+
+    Measured: float32 cases 34 / 23 / 24 distinct counts over 48 seeds, no seed left out by ``stable``, 1 / 0 / 0 of the
+    whole samples of 60; float64 at the tolerances scaled by 1 / 0.2^2 (K of a cloud scaled by s is K / s^2): the same
+    figures; float64 at the unscaled tolerances, 25 times stricter for that cloud: 6 / 14 / 5 distinct, 2 / 0 / 2 of 48
+    left out -- recorded and reproduced, but too few outcomes to count as a case that decides."""
+    g, st = _g13_study(golden, tag)
+    pts, draws, cases = g["points" + tag], g["draw" + tag], g["cases" + tag]
+    assert np.array_equal(g["points32"], se.torus32()) and np.array_equal(g["points64"], se.torus64())
+    assert np.array_equal(g["cases32"], np.array(se.GOLDEN_CASES)) and len(draws) == 48
+    assert np.array_equal(g["cases64"][3:, 0], [se.f64_tol(t) for t, _, _ in se.GOLDEN_CASES])
+    for s, d in zip(g["seeds"], draws):
+        np.random.seed(int(s))
+        assert np.random.randint(0, len(pts), 1)[0] == d                                  # the draw of pct:753
+    for c, (tol, lo, hi) in enumerate(cases):
+        lo, hi = int(lo), int(hi)
+        want = g["plus1_" + tag][:, c] - 1
+        assert np.array_equal(oracle.neighbor_study(pts, draws, tol, lo, hi)[1], want), (tag, tol, lo, hi)
+        whole = c == se.WHOLE_CASES[tag]                  # (the whole samples are judged where the GPU suite compares them)
+        got, comparable, _ = st.decide(tol, lo, hi, only=None if whole else slice(0, 48))
+        assert np.array_equal(got[:48], want), (tag, tol, lo, hi)
+        distinct = len(set(want.tolist()))
+        print(f"g13 float{tag} tol {tol} [{lo}, {hi}]: {distinct} distinct counts {want.min()} ... {want.max()}, "
+              f"left out {(~comparable[:48]).sum()} of 48 seeds" + (f", {(~comparable[48:]).reshape(3, 60).sum(1)} of 60" if whole else ""))
+        assert se.under_cap(comparable[:48])
+        assert not whole or all(se.under_cap(w) for w in comparable[48:].reshape(3, 60))
+        if tag == "32" or c >= 3:
+            assert distinct >= 15, (tag, tol, lo, hi, distinct)
+        for w, seed in enumerate(g["whole_seeds"]):
+            np.random.seed(int(seed))
+            rows = np.random.randint(0, len(pts), 60)
+            assert np.array_equal(rows, g["whole_draw" + tag][w])
+            assert oracle.neighbor_study(pts, rows, tol, lo, hi)[0] == g["whole" + tag][w, c]
+            assert se.result(got[48 + 60 * w: 108 + 60 * w]) == g["whole" + tag][w, c]
 
 
 def test_hybrid_eps_query_contract():
