@@ -195,10 +195,31 @@ int pct_fit_quadric(pct_ctx* ctx, const float* pts, int64_t batch, int32_t m, fl
  * The cloud is the float32-rounded one the tree is built from (pct:74); squared distances are accumulated in float64
  * as ((dx^2 + dy^2) + dz^2), rows ascending, exact ties by index.  idx (m,k) int32, dist (m,k) float64; missing
  * entries (k > N, or beyond eps when eps > 0): index N and +inf, as SciPy pads.  1 <= k <= 128.
- * Exhaustive sweep, one wave per query: meant for the hundreds of sample points of the neighbour study, not for
- * the per-point loop (that is pct_knn). */
+ * Exhaustive sweep, one wave per query, reading all N cloud points for each: what the hundreds of sample points of
+ * the neighbour study want.  The points of another cloud go through pct_query_points_algo below, which sends large
+ * query sets through the cell list; a cloud's own points are pct_knn's. */
 int pct_query_points(pct_ctx* ctx, const double* q_xyz, int64_t m, int32_t k, double eps,
                      int32_t* idx, double* dist);
+
+/* The same rows with the path named.  PCT_QUERY_SWEEP: pct_query_points' exhaustive sweep.  PCT_QUERY_GRID: the
+ * uniform cell list -- the resident one where a whole-cloud list is in place, else one built by this call and left
+ * resident --, queries binned by cell, the 27-cell stencil of a cell staged once for its queries, an exact shell-by-
+ * shell sweep for the queries the stencil cannot vouch for.  It takes the exhaustive sweep instead (same rows) where
+ * the table in place came from the hierarchical list or the chain of cell lists, on a handle with an owned range, and
+ * where a table or fit results in place would be invalidated by a build.  PCT_QUERY_AUTO: the sweep below 1024
+ * queries, below 4096 cloud points and below m * N = 2^34 pairs (the measured crossover); the cell list
+ * from there on.  A refusal of the cell-list build is returned, not rerouted.
+ * Errors as pct_query_points; PCT_ERR_INVALID for an unknown algo.  The resident neighbour table, fit results and
+ * PCA results are untouched. */
+#define PCT_QUERY_AUTO 0
+#define PCT_QUERY_SWEEP 1
+#define PCT_QUERY_GRID 2
+int pct_query_points_algo(pct_ctx* ctx, const double* q_xyz, int64_t m, int32_t k, double eps, int32_t algo,
+                          int32_t* idx, double* dist);
+/* Of the last pct_query_points_algo call: out = {route: 0 exhaustive sweep, 1 resident cell list, 2 cell list built by
+ * the call; queries answered from the staged 27-cell stencil; queries redone by the exact sweep; largest ring of cells
+ * a query reached}.  Zeros after the exhaustive sweep. */
+int pct_query_stats(pct_ctx* ctx, int64_t out[4]);
 
 /* explicit_quadratic_neighbor_study (pct:732-800), the numeric part: for every sample row s and every
  * neighbour count n in [n_lo, n_hi], the Gaussian curvature of the quadric fitted to the point itself plus

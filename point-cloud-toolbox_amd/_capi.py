@@ -27,6 +27,7 @@ PCT_ERR_NO_NEIGHBORS = 7
 MESH_F32, MESH_F64, MESH_K64_H32, MESH_K32_H64 = 0, 1, 2, 3      # pct_mesh_energies' curvature_is_f64
 
 KNN_AUTO, KNN_BRUTE, KNN_GRID, KNN_GRID_EXACT, KNN_GRID_LEVELS, KNN_TREE = 0, 1, 2, 3, 4, 5
+QUERY_AUTO, QUERY_SWEEP, QUERY_GRID = 0, 1, 2                    # pct_query_points_algo
 
 
 class Timings(C.Structure):
@@ -87,6 +88,8 @@ SIGNATURES = {
     "pct_plane_rotate": (C.c_int, [_p, _p, C.c_int32, C.c_int64, C.c_int32, _f64p]),
     "pct_fit_quadric": (C.c_int, [_p, _f32p, C.c_int64, C.c_int32, _f32p]),
     "pct_query_points": (C.c_int, [_p, _f64p, C.c_int64, C.c_int32, C.c_double, _i32p, _f64p]),
+    "pct_query_points_algo": (C.c_int, [_p, _f64p, C.c_int64, C.c_int32, C.c_double, C.c_int32, _i32p, _f64p]),
+    "pct_query_stats": (C.c_int, [_p, _i64p]),
     "pct_mesh_energies": (C.c_int, [_p, _f64p, C.c_int64, _i32p, C.c_int64, _p, _p, C.c_int32, _f64p]),
     "pct_voxel_downsample": (C.c_int, [_p, _f64p, C.c_int64, C.c_double, _i64p, _i64p]),
     "pct_voxel_downsample_f32": (C.c_int, [_p, _f32p, C.c_int64, C.c_double, _i64p, _i64p]),
@@ -363,15 +366,23 @@ class Handle:
                                                 _ptr(dist, _f32p), _ptr(cnt, _i32p)))
         return idx, dist, cnt
 
-    def query_points(self, q, k, eps=0.0):
-        """The reference tree's ``query`` for arbitrary points: (m,3) float64 -> idx (m,k) int32 (missing: N), dist (m,k) float64 (missing: inf)."""
+    def query_points(self, q, k, eps=0.0, algo=QUERY_AUTO):
+        """The reference tree's ``query`` for arbitrary points: (m,3) float64 -> idx (m,k) int32 (missing: N), dist (m,k) float64 (missing: inf).
+        ``algo``: QUERY_AUTO (large query sets through the cell list), QUERY_SWEEP, QUERY_GRID -- the same rows either way."""
         q = np.ascontiguousarray(q, dtype=np.float64)
         if q.ndim != 2 or q.shape[1] != 3:
             raise ValueError("query points must have shape (m, 3)")
         idx = np.empty((len(q), int(k)), np.int32)
         dist = np.empty((len(q), int(k)), np.float64)
-        self._check(self._lib.pct_query_points(self._h, _ptr(q, _f64p), len(q), int(k), float(eps or 0.0), _ptr(idx, _i32p), _ptr(dist, _f64p)))
+        self._check(self._lib.pct_query_points_algo(self._h, _ptr(q, _f64p), len(q), int(k), float(eps or 0.0), int(algo),
+                                                    _ptr(idx, _i32p), _ptr(dist, _f64p)))
         return idx, dist
+
+    def query_stats(self):
+        """Of the last ``query_points``: {route (0 sweep, 1 resident cell list, 2 cell list built), stencil, redone, max_ring}."""
+        out = np.zeros(4, np.int64)
+        self._check(self._lib.pct_query_stats(self._h, _ptr(out, _i64p)))
+        return {"route": int(out[0]), "stencil": int(out[1]), "redone": int(out[2]), "max_ring": int(out[3])}
 
     def get_neighbor_rows(self, rows):
         rows = np.ascontiguousarray(rows, dtype=np.int64)

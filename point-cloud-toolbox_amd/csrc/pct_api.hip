@@ -2,6 +2,7 @@
 // only: buffer ownership, launch order, hipEvent timing, status mapping.
 #include "pct_internal.h"
 #include "pct_auto_route.h"
+#include "pct_query_plan.h"
 
 #include <execinfo.h>
 #include <math.h>
@@ -227,7 +228,7 @@ void pct_destroy(pct_ctx* ctx) {
     pct_buf* all[] = {&ctx->xyz, &ctx->pts4, &ctx->pts4d, &ctx->cell_of, &ctx->cell_cnt, &ctx->cell_fill,
                       &ctx->scan_tmp, &ctx->occ, &ctx->redo, &ctx->row_of, &ctx->owned_pos, &ctx->cell_own, &ctx->cell_oth, &ctx->own_start, &ctx->sorted4, &ctx->sorted4d, &ctx->red, &ctx->nbr_pos,
                       &ctx->nbr_dist, &ctx->nbr_cnt, &ctx->counters, &ctx->coefs, &ctx->K, &ctx->H, &ctx->H2,
-                      &ctx->stage_a, &ctx->stage_b, &ctx->stage_c, &ctx->stage_d, &ctx->row_done, &ctx->redo_m, &ctx->flag_buf, &ctx->dens_buf, &ctx->pub_pos, &ctx->pub_dist, &ctx->pub_cnt, &ctx->qpts4, &ctx->fit_flag, &ctx->lvl_src,
+                      &ctx->stage_a, &ctx->stage_b, &ctx->stage_c, &ctx->stage_d, &ctx->row_done, &ctx->redo_m, &ctx->flag_buf, &ctx->dens_buf, &ctx->pub_pos, &ctx->pub_dist, &ctx->pub_cnt, &ctx->qpts4, &ctx->qry, &ctx->fit_flag, &ctx->lvl_src,
                       &ctx->tree_codes, &ctx->tree_vals, &ctx->tree_lvl, &ctx->tree_head, &ctx->tree_marks, &ctx->tree_seg, &ctx->tree_runs, &ctx->tree_range, &ctx->tree_bucket, &ctx->tree_tmp,
                       &ctx->pca, &ctx->pca_aux, &ctx->pca_nbr, &ctx->pca_orig,
                       &ctx->bin_rec, &ctx->bin_mat, &ctx->bin_plan, &ctx->bin_base};
@@ -456,6 +457,7 @@ static int sweep_levels(pct_ctx* ctx, int32_t k, double eps, const int* fuse_par
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_SWEEP_END], ctx->stream));
     ctx->tm.knn_launches = ctx->tm.levels;
     ctx->knn_valid = true;
+    ctx->knn_hier = true;
     done->rows_fitted = fuse_par != nullptr;
     return PCT_OK;
 }
@@ -474,6 +476,7 @@ static int sweep_tree(pct_ctx* ctx, int32_t k, double eps, bool want_dist, const
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_SWEEP_END], ctx->stream));
     ctx->tm.knn_launches = 1;
     ctx->knn_valid = true;
+    ctx->knn_hier = true;
     return PCT_OK;
 }
 
@@ -490,6 +493,7 @@ static int sweep_brute(pct_ctx* ctx, int32_t k, double eps) {
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_SWEEP_END], ctx->stream));
     ctx->tm.knn_launches = 1;
     ctx->knn_valid = true;
+    ctx->knn_hier = false;
     return PCT_OK;
 }
 
@@ -574,6 +578,7 @@ static int run_knn(pct_ctx* ctx, int32_t k, double eps, int32_t asked, const int
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_SWEEP_END], ctx->stream));
     ctx->tm.knn_launches = 1;
     ctx->knn_valid = true;
+    ctx->knn_hier = false;
     return PCT_OK;
 }
 
@@ -868,6 +873,73 @@ int pct_query_points(pct_ctx* ctx, const double* q_xyz, int64_t m, int32_t k, do
     PCT_HIP(ctx, hipMemcpyAsync(idx, ctx->stage_b.p, (size_t)m * k * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     PCT_HIP(ctx, hipMemcpyAsync(dist, ctx->stage_c.p, (size_t)m * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PCT_OK;
+}
+
+// pct_query_points with the path named: the exhaustive sweep above, or the uniform cell list (pct_query.hip).  The rule
+// is query_route's (pct_query_plan.h); what it reads of the handle is gathered here.  Nothing resident is disturbed: a
+// cell list is built only where no table or result in place refers to the cell order, and the timings of the call that
+// produced the table in place stay what they were.
+int pct_query_points_algo(pct_ctx* ctx, const double* q_xyz, int64_t m, int32_t k, double eps, int32_t algo, int32_t* idx, double* dist) {
+    PCT_TRY(begin_call(ctx));
+    PCT_TRY(refuse_in_slab_mode(ctx, "pct_query_points_algo"));
+    if (ctx->n <= 0 || !ctx->xyz_view) return pct_fail(ctx, PCT_ERR_INVALID, "no cloud loaded");
+    if (m < 0 || (m > 0 && (!q_xyz || !idx || !dist))) return pct_fail(ctx, PCT_ERR_INVALID, "bad query arrays");
+    if (k < 1 || k > 128) return pct_fail(ctx, PCT_ERR_INVALID, "k=%d outside [1,128]", k);
+    const pct_grid& g = ctx->grid;
+    bool finite_limits = false;
+    for (int a = 0; a < 3; ++a) finite_limits = finite_limits || isfinite(g.lim_lo[a]) || isfinite(g.lim_hi[a]);
+    QueryState qs = {};
+    qs.uniform_resident = ctx->grid_valid && ctx->grid_whole && !finite_limits;
+    qs.tree_resident = ctx->knn_valid && ctx->knn_hier;
+    qs.sorted_resident = (ctx->knn_valid && ctx->knn_sorted_space) || (ctx->fit_valid && ctx->fit_row_order);
+    qs.sharded = ctx->q_begin != 0 || ctx->q_end != ctx->n;      // (a culled list in place: finite limits, not uniform_resident)
+    qs.slab = ctx->slab_parts >= 1;
+    QueryRoute route;
+    if (!query_route(algo, ctx->n, m, k, qs, &route)) return pct_fail(ctx, PCT_ERR_INVALID, "unknown query algorithm %d", algo);
+    for (int i = 0; i < 4; ++i) ctx->query_stats[i] = 0;
+    if (m == 0) return PCT_OK;
+    for (int64_t i = 0; i < 3 * m; ++i)
+        if (!isfinite(q_xyz[i])) return pct_fail(ctx, PCT_ERR_NONFINITE, "query point %lld is not finite", (long long)(i / 3));
+    if (!(eps >= 0) || isinf(eps)) eps = 0;
+    if (route == QueryRoute::GridBuild) {
+        // an ordinary resident cell list afterwards, sized as the cloud's own sweep would size it for rows of k
+        // (two list registers at the most: the occupancy rule of longer rows is the exact-only sweep's)
+        int32_t kb = k < 127 ? k : 127;
+        if ((int64_t)kb + 1 > ctx->n) kb = ctx->n > 1 ? (int32_t)ctx->n - 1 : 1;
+        const pct_timings keep = ctx->tm;
+        GridVerdict built;
+        const int st = pct_build_grid(ctx, kb, 0.0, false, &built);
+        ctx->tm = keep;
+        ctx->counters_clean = false;       // (the words the build cleared belong to no sweep of this call)
+        if (st != PCT_OK) return st;       // (every refusal of the build is the caller's to see: none is turned into another route)
+        if (!(ctx->grid_valid && ctx->grid_whole))
+            return pct_fail(ctx, PCT_ERR_INVALID, "pct_query_points_algo: the cell list built is not one list over the whole cloud");
+    }
+    PCT_TRY(pct_reserve(ctx, &ctx->stage_a, (size_t)m * 3 * sizeof(double)));
+    PCT_TRY(pct_reserve(ctx, &ctx->stage_b, (size_t)m * k * sizeof(int32_t)));
+    PCT_TRY(pct_reserve(ctx, &ctx->stage_c, (size_t)m * k * sizeof(double)));
+    PCT_HIP(ctx, hipMemcpyAsync(ctx->stage_a.p, q_xyz, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (route == QueryRoute::Sweep)
+        PCT_TRY(pct_launch_query_points(ctx, (const double*)ctx->stage_a.p, m, k, eps, (int32_t*)ctx->stage_b.p, (double*)ctx->stage_c.p));
+    else
+        PCT_TRY(pct_launch_query_grid(ctx, (const double*)ctx->stage_a.p, m, k, eps, (int32_t*)ctx->stage_b.p, (double*)ctx->stage_c.p, ctx->query_words));
+    PCT_HIP(ctx, hipMemcpyAsync(idx, ctx->stage_b.p, (size_t)m * k * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(dist, ctx->stage_c.p, (size_t)m * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->query_stats[0] = (int64_t)route;
+    if (route != QueryRoute::Sweep) {
+        const int64_t redone = ctx->query_words[1];
+        ctx->query_stats[1] = m - redone;
+        ctx->query_stats[2] = redone;
+        ctx->query_stats[3] = ctx->query_words[2] > 1 ? ctx->query_words[2] : 1;     // (the 27 cells of stage 2 are ring 1)
+    }
+    return PCT_OK;
+}
+
+int pct_query_stats(pct_ctx* ctx, int64_t out[4]) {
+    if (!ctx || !out) return PCT_ERR_INVALID;
+    for (int i = 0; i < 4; ++i) out[i] = ctx->query_stats[i];
     return PCT_OK;
 }
 

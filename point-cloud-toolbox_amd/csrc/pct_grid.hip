@@ -1698,6 +1698,9 @@ static int commit_grid(pct_ctx* ctx, const GridPoints& s, pct_grid g, const Edge
     ctx->n_occ = tot.y;
     ctx->tm.occupied_cells = tot.y;
     ctx->grid_valid = true;
+    // what pct_query_points_algo may send caller-supplied queries through: every point filed, every point owned
+    ctx->grid_whole = !own_flag && !ctx->level_mode && !sub_box && !ctx->culled && n == ctx->n && ctx->q_begin == 0 && ctx->q_end == ctx->n &&
+                      ctx->slab_parts == 0;
     return PCT_OK;
 }
 
@@ -1708,6 +1711,7 @@ static int commit_grid(pct_ctx* ctx, const GridPoints& s, pct_grid g, const Edge
 // widens ring by ring for the rest.
 int pct_build_grid(pct_ctx* ctx, int32_t k, double eps, bool may_give_up, GridVerdict* out) {
     *out = GridVerdict::Built;
+    ctx->grid_valid = false;       // (the lists are being rewritten: valid again once a build is committed)
     // measured optima on surface clouds (tools/tune_factor.py): larger cells cost candidates, smaller ones cost
     // trips to the exact sweep; the LDS staging capacity caps the large side
     const double factor = ctx->occupancy_factor > 0 ? ctx->occupancy_factor : pct_default_factor(k);

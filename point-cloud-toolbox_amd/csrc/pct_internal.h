@@ -244,6 +244,7 @@ struct pct_ctx {
     pct_pinned* pin = nullptr;
     int64_t n_occ = 0;
     bool grid_valid = false;
+    bool grid_whole = false;       // the cell list in place is one uniform list over the WHOLE cloud, every point owned (commit_grid)
     bool pts4_valid = false;
 
     // neighbour table: one row per OWNED query (cell order, see own_start); entries are sorted positions
@@ -258,6 +259,7 @@ struct pct_ctx {
     void* fit_flag_seen = nullptr; // the fit_flag allocation (pointer and capacity) whose head has been zeroed
     size_t fit_flag_cap_seen = 0;
     bool knn_valid = false;
+    bool knn_hier = false;         // the table in place came from the hierarchical list or the chain of cell lists (run_knn)
     bool knn_sorted_space = false; // false: rows/ids are public indices (brute force)
     bool dist_valid = true;        // nbr_dist holds the distances of the table in place (else: derived on demand)
     pct_buf counters;   // pct_dev_words: the sweep's statistics words, the census, the scatter hit count
@@ -276,6 +278,11 @@ struct pct_ctx {
     pct_buf stage_a, stage_b, stage_c, stage_d;
     pct_buf qpts4;      // float4 {x,y,z,index} of EVERY point in public order, for pct_query_points (built on first use)
     bool qpts4_valid = false;
+    // pct_query_points_algo (pct_query.hip): scratch of a query through the cell list -- its words, the queries' cell ids
+    // and their order by cell, work items, redo list, sort scratch --, the words read back, and what pct_query_stats reports
+    pct_buf qry;
+    int32_t query_words[4] = {0, 0, 0, 0};
+    int64_t query_stats[4] = {0, 0, 0, 0};
 
     // PCA principal curvatures (pct_pca.hip), public order: double [lambda_1 | lambda_2 | K | H | frame (n,3,2)]
     pct_buf pca;
@@ -432,6 +439,9 @@ int pct_ensure_plain_records(pct_ctx* ctx);
 int pct_launch_fit_rows_f64(pct_ctx* ctx, const int32_t* d_idx, const int32_t* d_cnt, const int64_t* d_query, int64_t rows,
                             int32_t k, int32_t pitch, double* d_coefs, double* d_K, double* d_H);
 int pct_launch_query_points(pct_ctx* ctx, const double* d_q, int64_t m, int32_t k, double eps, int32_t* d_idx, double* d_dist);
+// pct_query.hip: the queries through the uniform cell list in place; host_words4 = {work items, rows redone by the exact
+// sweep, largest ring of those, 0} is complete once the stream has been waited for
+int pct_launch_query_grid(pct_ctx* ctx, const double* d_q, int64_t m, int32_t k, double eps, int32_t* d_idx, double* d_dist, int32_t* host_words4);
 int pct_launch_gather_int(pct_ctx* ctx, const int* d_map, int* d_inout, int64_t n);
 int pct_ensure_row_of(pct_ctx* ctx);     // before any read of ctx->row_of
 int pct_launch_export_rows(pct_ctx* ctx, const int64_t* d_rows, int64_t n_rows, int32_t* d_idx, float* d_dist, int32_t* d_cnt);

@@ -65,8 +65,9 @@ def _matrix_norms(points):
 
 class _DeviceTree:
     """``self.kdtree`` of the reference (SciPy's k-d tree of the float32 cloud, pct:74) as far as its callers use it
-    (pct:625, 759, 844): ``query(x, k)`` for arbitrary points, answered by the exhaustive device sweep
-    (``pct_query_points``).  Same return convention as SciPy: distances float64 ascending and indices, shape
+    (pct:625, 759, 844): ``query(x, k)`` for arbitrary points, answered on the device (``pct_query_points_algo`` with
+    ``PCT_QUERY_AUTO``: the exhaustive sweep for a few points, the cell list for the points of another cloud -- the same
+    rows either way).  Same return convention as SciPy: distances float64 ascending and indices, shape
     ``x.shape[:-1] + (k,)`` (the ``k`` axis squeezed for ``k == 1``), missing entries ``inf`` / ``n``."""
 
     def __init__(self, cloud):

@@ -1,0 +1,284 @@
+"""The rules of pct_query_points_algo (csrc/pct_query_plan.h), on the CPU: which path answers a set of caller-supplied
+queries, the cell a query anywhere in float64 is filed in, and the radius a searched cube of cells vouches for around a
+query that may lie outside the grid box.
+
+Two stand-alone programs that include nothing but that header.  The first prints what the route rule says; every
+expectation below is written out from the rule (include/pct_hip.h), each on both sides of its boundary.  The
+second -- compiled with -fsanitize=undefined, so that a conversion of an out-of-range double would end it -- prints the
+cells of queries at, inside and outside every face and up to +-1e300, and checks the radius against brute force: with
+every cell outside the searched cube filled with its nearest possible point (a boundary cell holds the points clamped
+into it: it reaches to infinity on its outer side), the true minimum distance to an excluded point is never below what
+the header vouches for."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "point-cloud-toolbox_amd", "csrc")
+
+CROSSOVER = 1 << 34              # kQueryAutoCrossover, restated: the measured constant
+
+ROUTE_PROGRAM = r"""
+#include "pct_query_plan.h"
+#include <stdio.h>
+
+static QueryState state(bool uniform, bool tree, bool sorted, bool sharded, bool slab) { return QueryState{uniform, tree, sorted, sharded, slab}; }
+// known * 10 + route
+static void route(const char* name, int algo, int64_t n, int64_t m, int k, QueryState s) {
+    QueryRoute r;
+    const bool known = query_route(algo, n, m, k, s, &r);
+    printf("%s %d\n", name, (int)known * 10 + (int)r);
+}
+
+int main() {
+    const QueryState fresh = state(false, false, false, false, false), resident = state(true, false, true, false, false);
+    printf("min_m %lld\nmin_n %lld\ncrossover %lld\n", (long long)kQueryAutoMinM, (long long)kQueryAutoMinN, (long long)kQueryAutoCrossover);
+    // ---- AUTO: the two floors (2^35 pairs: above the crossover in m n)
+    route("auto_m1023", PCT_QUERY_AUTO, 1 << 25, 1023, 16, resident);
+    route("auto_m1024", PCT_QUERY_AUTO, 1 << 25, 1024, 16, resident);
+    route("auto_n4095", PCT_QUERY_AUTO, 4095, 1 << 23, 16, resident);
+    route("auto_n4096", PCT_QUERY_AUTO, 4096, 1 << 23, 16, resident);
+    route("auto_study", PCT_QUERY_AUTO, 1 << 26, 500, 16, resident);
+    // ---- AUTO: the crossover in m n, on pairs above both floors
+    const int64_t n0 = 4099;                              // a prime: m n meets the constant nowhere exactly
+    const int64_t m_at = (kQueryAutoCrossover + n0 - 1) / n0;        // the smallest m with m n0 >= crossover
+    printf("prime_pair_ok %d\n", (int)(m_at >= kQueryAutoMinM && m_at * n0 >= kQueryAutoCrossover && (m_at - 1) * n0 < kQueryAutoCrossover));
+    route("auto_cross_below", PCT_QUERY_AUTO, n0, m_at - 1, 16, resident);
+    route("auto_cross_at", PCT_QUERY_AUTO, n0, m_at, 16, resident);
+    // exactly the constant, one pair below, one above (n = 8192)
+    route("auto_mn_minus", PCT_QUERY_AUTO, 8192, kQueryAutoCrossover / 8192 - 1, 16, resident);
+    route("auto_mn_exact", PCT_QUERY_AUTO, 8192, kQueryAutoCrossover / 8192, 16, resident);
+    route("auto_mn_plus", PCT_QUERY_AUTO, 8192, kQueryAutoCrossover / 8192 + 1, 16, resident);
+    route("auto_huge", PCT_QUERY_AUTO, ((int64_t)1 << 31) - 2000, (int64_t)1 << 30, 16, resident);
+    route("auto_build", PCT_QUERY_AUTO, 1 << 20, 1 << 20, 16, fresh);
+    // ---- the comparison itself, with pair counts that bind above both floors (whatever the constant is)
+    const int64_t pairs = (int64_t)1 << 32;
+    printf("reach_below %d\nreach_at %d\nreach_above %d\n", (int)query_pairs_reach(65535, 65536, pairs), (int)query_pairs_reach(65536, 65536, pairs),
+           (int)query_pairs_reach(65537, 65536, pairs));
+    printf("reach_prime_below %d\nreach_prime_at %d\n", (int)query_pairs_reach(1047808, 4099, pairs), (int)query_pairs_reach(1047809, 4099, pairs));   // ceil(2^32 / 4099) = 1047809
+    printf("reach_no_overflow %d\nreach_one %d\nreach_zero %d\n", (int)query_pairs_reach((int64_t)1 << 30, ((int64_t)1 << 31) - 2000, (int64_t)1 << 62),
+           (int)query_pairs_reach(1, 1, 1), (int)query_pairs_reach(0, 1, 1));
+    // ---- the requests by name
+    route("sweep_forced", PCT_QUERY_SWEEP, 1 << 20, 1 << 20, 16, resident);
+    route("grid_tiny_fresh", PCT_QUERY_GRID, 1, 1, 128, fresh);
+    route("grid_tiny_resident", PCT_QUERY_GRID, 2, 1, 1, resident);
+    route("unknown_3", 3, 1 << 20, 1 << 20, 16, resident);
+    route("unknown_neg", -1, 1 << 20, 1 << 20, 16, resident);
+    // ---- what sends GRID and AUTO back to the sweep
+    const int algos[2] = {PCT_QUERY_GRID, PCT_QUERY_AUTO};
+    const char* names[2] = {"grid", "auto"};
+    for (int i = 0; i < 2; ++i) {
+        char b[64];
+        snprintf(b, sizeof b, "%s_tree", names[i]);        route(b, algos[i], 1 << 20, 1 << 20, 16, state(false, true, true, false, false));
+        snprintf(b, sizeof b, "%s_tree_grid", names[i]);   route(b, algos[i], 1 << 20, 1 << 20, 16, state(true, true, true, false, false));
+        snprintf(b, sizeof b, "%s_sharded", names[i]);     route(b, algos[i], 1 << 20, 1 << 20, 16, state(true, false, true, true, false));
+        snprintf(b, sizeof b, "%s_slab", names[i]);        route(b, algos[i], 1 << 20, 1 << 20, 16, state(true, false, true, false, true));
+        snprintf(b, sizeof b, "%s_sorted", names[i]);      route(b, algos[i], 1 << 20, 1 << 20, 16, state(false, false, true, false, false));
+        snprintf(b, sizeof b, "%s_fresh", names[i]);       route(b, algos[i], 1 << 20, 1 << 20, 16, fresh);
+        snprintf(b, sizeof b, "%s_resident", names[i]);    route(b, algos[i], 1 << 20, 1 << 20, 16, resident);
+        snprintf(b, sizeof b, "%s_list_only", names[i]);   route(b, algos[i], 1 << 20, 1 << 20, 16, state(true, false, false, false, false));
+    }
+    return 0;
+}
+"""
+
+BOUND_PROGRAM = r"""
+#include "pct_query_plan.h"
+#include <stdio.h>
+#include <stdlib.h>
+
+// the nearest a point filed in cell i of an axis of n cells can be to position p (cell units): cell i spans [i, i + 1],
+// the first cell reaches down to -inf and the last up to +inf (points outside the grid box are clamped into them)
+static double axis_gap(int i, int n, double p) {
+    const double lo = i == 0 ? -INFINITY : (double)i, hi = i == n - 1 ? INFINITY : (double)(i + 1);
+    return p < lo ? lo - p : p > hi ? p - hi : 0.0;
+}
+
+static long cases = 0, finite_cases = 0, violations = 0, tight = 0;
+
+static void check(int nx, int ny, int nz, double px, double py, double pz) {
+    // the origin is 0 and the edge 1: positions are cell units
+    const int cx = query_cell_coord(px, 0.0, 1.0, nx), cy = query_cell_coord(py, 0.0, 1.0, ny), cz = query_cell_coord(pz, 0.0, 1.0, nz);
+    const double gx = px - cx, gy = py - cy, gz = pz - cz;
+    int ring_max = nx > ny ? nx : ny;
+    if (nz > ring_max) ring_max = nz;
+    for (int ring = 1; ring <= ring_max; ++ring) {
+        double truth = INFINITY;
+        for (int z = 0; z < nz; ++z)
+            for (int y = 0; y < ny; ++y)
+                for (int x = 0; x < nx; ++x) {
+                    if (abs(x - cx) <= ring && abs(y - cy) <= ring && abs(z - cz) <= ring) continue;      // searched
+                    const double ax = axis_gap(x, nx, px), ay = axis_gap(y, ny, py), az = axis_gap(z, nz, pz);
+                    const double d2 = (ax * ax + ay * ay) + az * az;
+                    if (d2 < truth) truth = d2;
+                }
+        const double g = query_guarantee_cells(nx, ny, nz, cx, cy, cz, gx, gy, gz, ring);
+        const double r2 = query_guaranteed_r2(nx, ny, nz, 1.0, cx, cy, cz, gx, gy, gz, ring);
+        ++cases;
+        if (truth < INFINITY) ++finite_cases;
+        // the header must never vouch for more than the truth; where nothing is excluded it may say +inf, else it must be finite
+        const bool ok = g * g <= truth * (1.0 + 1e-12) && r2 <= truth && (truth == INFINITY) == (g == INFINITY) && g >= (double)ring;
+        if (!ok) {
+            if (violations < 5) fprintf(stderr, "grid %d %d %d query %g %g %g ring %d: vouched %g, true %g\n", nx, ny, nz, px, py, pz, ring, g * g, truth);
+            ++violations;
+        }
+        if (truth < INFINITY && g * g >= truth * (1.0 - 1e-12)) ++tight;
+    }
+}
+
+static void cell(const char* name, double x, double o, double inv, int n) { printf("%s %d\n", name, query_cell_coord(x, o, inv, n)); }
+
+int main() {
+    // ---- the clamp: origin 2, edge 0.5, 7 cells: the box is [2, 5.5]
+    cell("cell_zero", 0.0, 2.0, 2.0, 7);
+    cell("cell_at_origin", 2.0, 2.0, 2.0, 7);
+    cell("cell_below_origin", 2.0 - 1e-9, 2.0, 2.0, 7);
+    cell("cell_in_first", 2.0 + 1e-9, 2.0, 2.0, 7);
+    cell("cell_below_face", 2.5 - 1e-9, 2.0, 2.0, 7);
+    cell("cell_at_face", 2.5, 2.0, 2.0, 7);
+    cell("cell_in_last", 5.5 - 1e-9, 2.0, 2.0, 7);
+    cell("cell_at_end", 5.5, 2.0, 2.0, 7);
+    cell("cell_past_end", 5.5 + 1e-9, 2.0, 2.0, 7);
+    cell("cell_p1e30", 1e30, 2.0, 2.0, 7);
+    cell("cell_m1e30", -1e30, 2.0, 2.0, 7);
+    cell("cell_p1e300", 1e300, 2.0, 2.0, 7);
+    cell("cell_m1e300", -1e300, 2.0, 2.0, 7);
+    cell("cell_p1e300_tiny_edge", 1e300, 2.0, 1e10, 7);              // the product overflows to +inf
+    cell("cell_m1e300_tiny_edge", -1e300, 2.0, 1e10, 7);
+    cell("cell_max", 1.7976931348623157e308, -1.7e308, 2.0, 7);      // the difference overflows
+    cell("cell_one_cell_p", 1e30, 2.0, 2.0, 1);
+    cell("cell_one_cell_m", -1e30, 2.0, 2.0, 1);
+    cell("cell_big_grid_p", 1e30, 0.0, 1.0, 1 << 30);
+    cell("cell_big_grid_in", 1073741823.5, 0.0, 1.0, 1 << 30);
+    // a guarantee for a query whose offset overflowed: +inf terms, no NaN
+    const double gi = query_guarantee_cells(7, 7, 7, 6, 3, 0, INFINITY, 0.5, -INFINITY, 1);
+    printf("overflowed_offsets %.17g\n", gi);
+    printf("overflowed_r2_is_nan %d\n", (int)isnan(query_guaranteed_r2(7, 1, 1, 0.5, 6, 0, 0, INFINITY, -INFINITY, INFINITY, 1)));
+
+    // ---- the radius against brute force
+    const int grids[6][3] = {{5, 4, 3}, {6, 5, 1}, {9, 1, 1}, {1, 1, 1}, {2, 2, 2}, {3, 7, 2}};
+    const double outside[7] = {0.0, 1e-9, 0.3, 1.0, 2.5, 17.25, 50.0};
+    for (int gi_ = 0; gi_ < 6; ++gi_) {
+        const int nx = grids[gi_][0], ny = grids[gi_][1], nz = grids[gi_][2];
+        const int dims[3] = {nx, ny, nz};
+        // per axis: positions inside cells, on every face, and outside on both sides
+        double pos[3][64];
+        int npos[3];
+        for (int a = 0; a < 3; ++a) {
+            int c = 0;
+            for (int i = 0; i <= dims[a]; ++i) {
+                pos[a][c++] = (double)i;                                    // on a face (the box's own two included)
+                if (i < dims[a]) { pos[a][c++] = i + 0.5; pos[a][c++] = i + 0.0625; pos[a][c++] = i + 0.9375; }
+            }
+            for (int o = 1; o < 7; ++o) { pos[a][c++] = -outside[o]; pos[a][c++] = dims[a] + outside[o]; }
+            npos[a] = c;
+        }
+        for (int i = 0; i < npos[0]; ++i)
+            for (int j = 0; j < npos[1]; ++j)
+                for (int l = 0; l < npos[2]; ++l) check(nx, ny, nz, pos[0][i], pos[1][j], pos[2][l]);
+    }
+    printf("bound_cases %ld\nbound_finite_cases %ld\nbound_violations %ld\nbound_tight %ld\n", cases, finite_cases, violations, tight);
+    return violations ? 1 : 0;
+}
+"""
+
+SWEEP, RESIDENT, BUILD = 0, 1, 2                 # QueryRoute
+KNOWN = 10
+
+
+def _compile_and_run(tmp_path_factory, name, program, extra=()):
+    cxx = shutil.which(os.environ.get("CXX", "g++")) or shutil.which("c++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    d = tmp_path_factory.mktemp(name)
+    src, exe = d / (name + ".cpp"), d / name
+    src.write_text(program)
+    subprocess.run([cxx, "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-Werror", *extra, "-I", CSRC, str(src), "-o", str(exe), "-lm"], check=True)
+    run = subprocess.run([str(exe)], capture_output=True, text=True, env=dict(os.environ, UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=0"))
+    assert run.returncode == 0, run.stderr[-2000:]
+    assert "runtime error" not in run.stderr, run.stderr[-2000:]
+    return {k: float(v) for k, v in (ln.split() for ln in run.stdout.splitlines())}
+
+
+@pytest.fixture(scope="module")
+def route(tmp_path_factory):
+    return _compile_and_run(tmp_path_factory, "query_route", ROUTE_PROGRAM)
+
+
+@pytest.fixture(scope="module")
+def bound(tmp_path_factory):
+    return _compile_and_run(tmp_path_factory, "query_bound", BOUND_PROGRAM, extra=("-fsanitize=undefined", "-fno-sanitize-recover=undefined"))
+
+
+def test_header_includes_the_c_library_and_the_public_header_only():
+    with open(os.path.join(CSRC, "pct_query_plan.h")) as f:
+        includes = [ln.split()[1] for ln in f if ln.startswith("#include")]
+    assert sorted(includes) == ['"../../include/pct_hip.h"', "<math.h>", "<stdint.h>"]
+
+
+def test_constants(route):
+    assert route["min_m"] == 1024 and route["min_n"] == 4096 and route["crossover"] == CROSSOVER
+
+
+def test_auto_keeps_small_query_sets_and_small_clouds_on_the_sweep(route):
+    assert route["auto_m1023"] == KNOWN + SWEEP and route["auto_m1024"] == KNOWN + RESIDENT
+    assert route["auto_n4095"] == KNOWN + SWEEP and route["auto_n4096"] == KNOWN + RESIDENT
+    assert route["auto_study"] == KNOWN + SWEEP                       # the neighbour study's 500 samples
+
+
+def test_auto_takes_the_grid_from_the_crossover_on(route):
+    assert route["prime_pair_ok"] == 1
+    assert route["auto_cross_below"] == KNOWN + SWEEP and route["auto_cross_at"] == KNOWN + RESIDENT
+    # n = 8192: m = 2^21 - 1 | 2^21 | 2^21 + 1, all far above the floor of 1024 queries -- the pair count alone decides
+    assert CROSSOVER // 8192 == 1 << 21
+    assert route["auto_mn_minus"] == KNOWN + SWEEP
+    assert route["auto_mn_exact"] == KNOWN + RESIDENT and route["auto_mn_plus"] == KNOWN + RESIDENT
+    assert route["auto_huge"] == KNOWN + RESIDENT                     # m n beyond 2^61: no overflow in the comparison
+    assert route["auto_build"] == KNOWN + BUILD
+
+
+def test_pair_count_comparison_binds(route):
+    """m n >= pairs, by division: 65536^2 = 2^32 exactly; 4099 is prime, ceil(2^32 / 4099) = 1 047 809."""
+    assert (route["reach_below"], route["reach_at"], route["reach_above"]) == (0, 1, 1)
+    assert -(-(1 << 32) // 4099) == 1047809
+    assert (route["reach_prime_below"], route["reach_prime_at"]) == (0, 1)
+    assert route["reach_no_overflow"] == 0          # 2^30 x (2^31 - 2000) < 2^62, and the product is never formed
+    assert route["reach_one"] == 1 and route["reach_zero"] == 0
+
+
+def test_requests_by_name(route):
+    assert route["sweep_forced"] == KNOWN + SWEEP
+    assert route["grid_tiny_fresh"] == KNOWN + BUILD and route["grid_tiny_resident"] == KNOWN + RESIDENT     # no floor for GRID
+    assert route["unknown_3"] == SWEEP and route["unknown_neg"] == SWEEP                                      # refused (known = 0)
+
+
+@pytest.mark.parametrize("algo", ("grid", "auto"))
+def test_fallbacks_to_the_sweep(route, algo):
+    assert route[f"{algo}_tree"] == KNOWN + SWEEP                     # the hierarchical list's table is in place
+    assert route[f"{algo}_tree_grid"] == KNOWN + SWEEP                # ... whatever else is
+    assert route[f"{algo}_sharded"] == KNOWN + SWEEP and route[f"{algo}_slab"] == KNOWN + SWEEP
+    assert route[f"{algo}_sorted"] == KNOWN + SWEEP                   # a table in cell order, its list gone: no rebuild under it
+    assert route[f"{algo}_fresh"] == KNOWN + BUILD
+    assert route[f"{algo}_resident"] == KNOWN + RESIDENT and route[f"{algo}_list_only"] == KNOWN + RESIDENT
+
+
+def test_cell_of_a_query_anywhere(bound):
+    assert bound["cell_zero"] == 0 and bound["cell_below_origin"] == 0 and bound["cell_at_origin"] == 0 and bound["cell_in_first"] == 0
+    assert bound["cell_below_face"] == 0 and bound["cell_at_face"] == 1
+    assert bound["cell_in_last"] == 6 and bound["cell_at_end"] == 6 and bound["cell_past_end"] == 6          # floor gives 7: clamped
+    assert bound["cell_p1e30"] == 6 and bound["cell_m1e30"] == 0 and bound["cell_p1e300"] == 6 and bound["cell_m1e300"] == 0
+    assert bound["cell_p1e300_tiny_edge"] == 6 and bound["cell_m1e300_tiny_edge"] == 0 and bound["cell_max"] == 6
+    assert bound["cell_one_cell_p"] == 0 and bound["cell_one_cell_m"] == 0
+    assert bound["cell_big_grid_p"] == (1 << 30) - 1 and bound["cell_big_grid_in"] == (1 << 30) - 1
+
+
+def test_overflowed_offsets_give_infinity_not_nan(bound):
+    assert bound["overflowed_offsets"] == 1.5                         # the y axis alone bounds it: min(0.5 + 1, 0.5 + 1)
+    assert bound["overflowed_r2_is_nan"] == 0
+
+
+def test_guarantee_never_exceeds_the_true_distance_to_an_excluded_point(bound):
+    assert bound["bound_violations"] == 0
+    assert bound["bound_cases"] > 100_000 and bound["bound_finite_cases"] > 30_000
+    assert bound["bound_tight"] > 1000                                # and it is the true minimum in many cases: not a trivial bound

@@ -57,7 +57,7 @@ def run(seed0=0, budget=None, cases=None, verbose=False):
         h.close()
         return it, f"seed={seed0} step {it}: {msg}; last ops: {log[-8:]}"
     while time.time() < t_end and (cases is None or it < cases):
-        ops = ["cloud"] if pts is None else ["cloud", "range", "knn", "knn", "curv", "curv", "stats", "factor", "query", "voxel", "survar", "async"]
+        ops = ["cloud"] if pts is None else ["cloud", "range", "knn", "knn", "curv", "curv", "stats", "factor", "query", "query_grid", "voxel", "survar", "async"]
         if knn: ops += ["fit", "get_nbr", "get_rows", "rows_fit", "rows_fit64", "study"]
         if fit: ops += ["get_fit", "get_fit"]
         w = np.array([0.25 if o in ("cloud", "range") else 0.5 if o in ("stats", "factor", "voxel", "async") else 1.0 for o in ops]) if pts is not None else None
@@ -124,6 +124,14 @@ def run(seed0=0, budget=None, cases=None, verbose=False):
             got = h.query_points(q, kq)
             f = _capi.Handle(0); f.set_points(pts); want = f.query_points(q, kq); f.close()
             if not (same(got[0], want[0]) and same(got[1], want[1])): return fail("query_points")
+        elif op == "query_grid":                                    # the cell list forced, against a fresh handle's exhaustive sweep
+            m = int(rng.integers(1, 300))
+            q = np.vstack([rng.normal(size=(m, 3)) * np.ptp(pts, axis=0).max() + pts.mean(0), pts[rng.integers(0, n, m)].astype(np.float64) + rng.normal(size=(m, 3)) * 1e-3,
+                           [[1e30, 0.0, 0.0]]])
+            kq = int(rng.integers(1, 129)); eq = 0.0 if rng.random() < 0.5 else float(np.ptp(pts, axis=0).max() * rng.uniform(0.01, 0.5))
+            got = h.query_points(q, kq, eq, _capi.QUERY_GRID)
+            f = _capi.Handle(0); f.set_points(pts); want = f.query_points(q, kq, eq, _capi.QUERY_SWEEP); f.close()
+            if not (same(got[0], want[0]) and same(got[1], want[1])): return fail(f"query_points QUERY_GRID (k={kq}, eps={eq}, stats {h.query_stats()})")
         elif op == "survar":                                        # PCA surface variation: plants its own table, drops the fit
             kt = min(int(rng.choice([8, 20, 40])), n - 1)
             if lo == 0 and hi == n:
