@@ -27,7 +27,8 @@ enum pct_status {
     PCT_ERR_NONFINITE = 4,    /* NaN/Inf in the cloud (pointCloudToolbox.py:273-274)   */
     PCT_ERR_K_TOO_LARGE = 5,  /* k + 1 > N (reference: IndexError at pct:640)          */
     PCT_ERR_OOM = 6,
-    PCT_ERR_NO_NEIGHBORS = 7  /* fit requested before a neighbour table exists         */
+    PCT_ERR_NO_NEIGHBORS = 7, /* fit requested before a neighbour table exists         */
+    PCT_ERR_LIMIT = 8         /* pct_query_ball: more entries than the caller allows   */
 };
 
 enum pct_knn_algo {
@@ -220,6 +221,38 @@ int pct_query_points_algo(pct_ctx* ctx, const double* q_xyz, int64_t m, int32_t 
  * the call; queries answered from the staged 27-cell stencil; queries redone by the exact sweep; largest ring of cells
  * a query reached}.  Zeros after the exhaustive sweep. */
 int pct_query_stats(pct_ctx* ctx, int64_t out[4]);
+
+/* self.kdtree.query_ball_point(x, r): every cloud point within r of each of m caller-supplied float64 query points, as
+ * CSR rows of any length.  Candidates are the float32-rounded cloud widened to float64 (pct:74), as in
+ * pct_query_points; d2 = (dx*dx + dy*dy) + dz*dz in float64, three separate operations, nothing fused.  A point is a
+ * member when d2 <= r*r, the product taken in float64: the test is INCLUSIVE -- unlike the strict d < eps of
+ * pct_query_points' bound.  Nothing else is special-cased: r = 0 keeps coinciding points, r = inf every point, a NaN r
+ * nothing, a negative r behaves as |r| (as SciPy's tree does); a query that coincides with a cloud point gets that
+ * point.  r: n_r = 1 radius for all queries, or n_r = m, one per query.
+ * Row i is the set of public indices that pass: ascending with PCT_BALL_SORTED, otherwise in an unspecified order that
+ * the same call on the same handle state reproduces byte for byte.  PCT_BALL_DISTANCES: float64 sqrt(d2) beside every
+ * index.  PCT_BALL_COUNT_ONLY: offsets alone, nothing is filled or kept.
+ * offsets (m + 1, host) is complete on return from PCT_OK, PCT_ERR_LIMIT and PCT_ERR_OOM.  offsets[m] > max_entries
+ * (max_entries <= 0: no cap) returns PCT_ERR_LIMIT: no rows are resident, the caller chunks its queries by the offsets.
+ * PCT_ERR_OOM: the row buffer could not be reserved.  m = 0 is accepted (offsets = {0}).  PCT_ERR_NONFINITE for a
+ * non-finite query coordinate; PCT_ERR_INVALID for an unknown algo or flag, n_r other than 1 or m, a slab handle.
+ * algo: PCT_QUERY_SWEEP reads all N points per query; PCT_QUERY_GRID goes through the uniform cell list -- the resident
+ * one, or one built by this call and left resident -- and falls back to the exhaustive path exactly where
+ * pct_query_points_algo does; PCT_QUERY_AUTO takes the cell list from 1024 queries, 4096 points and 2^26 pairs m N on.
+ * The rows are the same on every path.  They stay on the device until the next pct_query_ball or pct_set_points*; the
+ * resident neighbour table, fit results, PCA results and their timings are untouched. */
+#define PCT_BALL_SORTED 1
+#define PCT_BALL_DISTANCES 2
+#define PCT_BALL_COUNT_ONLY 4
+int pct_query_ball(pct_ctx* ctx, const double* q_xyz, int64_t m, const double* r, int64_t n_r, int32_t flags, int32_t algo,
+                   int64_t max_entries, int64_t* offsets);
+/* Rows [row_begin, row_end) of the last pct_query_ball: idx holds offsets[row_end] - offsets[row_begin] entries, dist
+ * (may be NULL; needs PCT_BALL_DISTANCES) as many.  PCT_ERR_INVALID without resident rows. */
+int pct_get_ball(pct_ctx* ctx, int64_t row_begin, int64_t row_end, int32_t* idx, double* dist);
+/* Of the last pct_query_ball: out = {route as pct_query_stats; queries answered from a cube of cells staged once for
+ * their work item; queries that streamed their candidates from global memory; largest cube half-width in cells}.
+ * Zeros behind the route after the exhaustive path. */
+int pct_ball_stats(pct_ctx* ctx, int64_t out[4]);
 
 /* explicit_quadratic_neighbor_study (pct:732-800), the numeric part: for every sample row s and every
  * neighbour count n in [n_lo, n_hi], the Gaussian curvature of the quadric fitted to the point itself plus

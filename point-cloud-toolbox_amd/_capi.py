@@ -23,11 +23,13 @@ PCT_ERR_NONFINITE = 4
 PCT_ERR_K_TOO_LARGE = 5
 PCT_ERR_OOM = 6
 PCT_ERR_NO_NEIGHBORS = 7
+PCT_ERR_LIMIT = 8
 
 MESH_F32, MESH_F64, MESH_K64_H32, MESH_K32_H64 = 0, 1, 2, 3      # pct_mesh_energies' curvature_is_f64
 
 KNN_AUTO, KNN_BRUTE, KNN_GRID, KNN_GRID_EXACT, KNN_GRID_LEVELS, KNN_TREE = 0, 1, 2, 3, 4, 5
-QUERY_AUTO, QUERY_SWEEP, QUERY_GRID = 0, 1, 2                    # pct_query_points_algo
+QUERY_AUTO, QUERY_SWEEP, QUERY_GRID = 0, 1, 2                    # pct_query_points_algo, pct_query_ball
+BALL_SORTED, BALL_DISTANCES, BALL_COUNT_ONLY = 1, 2, 4           # pct_query_ball's flags
 
 
 class Timings(C.Structure):
@@ -90,6 +92,9 @@ SIGNATURES = {
     "pct_query_points": (C.c_int, [_p, _f64p, C.c_int64, C.c_int32, C.c_double, _i32p, _f64p]),
     "pct_query_points_algo": (C.c_int, [_p, _f64p, C.c_int64, C.c_int32, C.c_double, C.c_int32, _i32p, _f64p]),
     "pct_query_stats": (C.c_int, [_p, _i64p]),
+    "pct_query_ball": (C.c_int, [_p, _f64p, C.c_int64, _f64p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, _i64p]),
+    "pct_get_ball": (C.c_int, [_p, C.c_int64, C.c_int64, _i32p, _f64p]),
+    "pct_ball_stats": (C.c_int, [_p, _i64p]),
     "pct_mesh_energies": (C.c_int, [_p, _f64p, C.c_int64, _i32p, C.c_int64, _p, _p, C.c_int32, _f64p]),
     "pct_voxel_downsample": (C.c_int, [_p, _f64p, C.c_int64, C.c_double, _i64p, _i64p]),
     "pct_voxel_downsample_f32": (C.c_int, [_p, _f32p, C.c_int64, C.c_double, _i64p, _i64p]),
@@ -377,6 +382,46 @@ class Handle:
         self._check(self._lib.pct_query_points_algo(self._h, _ptr(q, _f64p), len(q), int(k), float(eps or 0.0), int(algo),
                                                     _ptr(idx, _i32p), _ptr(dist, _f64p)))
         return idx, dist
+
+    def query_ball(self, q, r, flags=BALL_SORTED, algo=QUERY_AUTO, max_entries=0):
+        """``pct_query_ball``: every cloud point within ``r`` (one radius, or one per query; inclusive) of each (m,3)
+        float64 query.  Returns ``(status, offsets)`` -- PCT_OK, or PCT_ERR_LIMIT when the rows hold more than
+        ``max_entries`` entries (offsets valid, nothing resident); every other status raises.  The rows stay on the
+        device for ``get_ball``."""
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        if q.ndim != 2 or q.shape[1] != 3:
+            raise ValueError("query points must have shape (m,3)")
+        r = np.ascontiguousarray(np.atleast_1d(r), dtype=np.float64)
+        if r.ndim != 1:
+            raise ValueError("radii must be a scalar or have shape (m,)")
+        offsets = np.zeros(len(q) + 1, np.int64)
+        st = self._lib.pct_query_ball(self._h, _ptr(q, _f64p), len(q), _ptr(r, _f64p), len(r), int(flags), int(algo),
+                                      int(max_entries), _ptr(offsets, _i64p))
+        self._ball_offsets = offsets if st == PCT_OK and not flags & BALL_COUNT_ONLY else None
+        if st != PCT_ERR_LIMIT:
+            self._check(st)
+        return st, offsets
+
+    def get_ball(self, row_begin=0, row_end=None, want_dist=False):
+        """Rows [row_begin, row_end) of the last ``query_ball``: indices int32 (and distances float64), concatenated."""
+        off = getattr(self, "_ball_offsets", None)
+        if off is None:                       # (the library says why: nothing resident)
+            self._check(self._lib.pct_get_ball(self._h, int(row_begin), int(row_begin if row_end is None else row_end), None, None))
+            raise ValueError("no ball rows on this handle")
+        row_end = len(off) - 1 if row_end is None else int(row_end)
+        if not 0 <= row_begin <= row_end <= len(off) - 1:
+            raise ValueError(f"bad row range [{row_begin},{row_end}) of {len(off) - 1}")
+        count = int(off[row_end] - off[row_begin])
+        idx = np.empty(count, np.int32)
+        dist = np.empty(count, np.float64) if want_dist else None
+        self._check(self._lib.pct_get_ball(self._h, int(row_begin), row_end, _ptr(idx, _i32p), _ptr(dist, _f64p) if want_dist else None))
+        return (idx, dist) if want_dist else idx
+
+    def ball_stats(self):
+        """Of the last ``query_ball``: {route (as query_stats), staged, streamed, max_ring}."""
+        out = np.zeros(4, np.int64)
+        self._check(self._lib.pct_ball_stats(self._h, _ptr(out, _i64p)))
+        return {"route": int(out[0]), "staged": int(out[1]), "streamed": int(out[2]), "max_ring": int(out[3])}
 
     def query_stats(self):
         """Of the last ``query_points``: {route (0 sweep, 1 resident cell list, 2 cell list built), stencil, redone, max_ring}."""

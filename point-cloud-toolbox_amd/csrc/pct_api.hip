@@ -3,6 +3,7 @@
 #include "pct_internal.h"
 #include "pct_auto_route.h"
 #include "pct_query_plan.h"
+#include "pct_ball_plan.h"
 
 #include <execinfo.h>
 #include <math.h>
@@ -228,7 +229,7 @@ void pct_destroy(pct_ctx* ctx) {
     pct_buf* all[] = {&ctx->xyz, &ctx->pts4, &ctx->pts4d, &ctx->cell_of, &ctx->cell_cnt, &ctx->cell_fill,
                       &ctx->scan_tmp, &ctx->occ, &ctx->redo, &ctx->row_of, &ctx->owned_pos, &ctx->cell_own, &ctx->cell_oth, &ctx->own_start, &ctx->sorted4, &ctx->sorted4d, &ctx->red, &ctx->nbr_pos,
                       &ctx->nbr_dist, &ctx->nbr_cnt, &ctx->counters, &ctx->coefs, &ctx->K, &ctx->H, &ctx->H2,
-                      &ctx->stage_a, &ctx->stage_b, &ctx->stage_c, &ctx->stage_d, &ctx->row_done, &ctx->redo_m, &ctx->flag_buf, &ctx->dens_buf, &ctx->pub_pos, &ctx->pub_dist, &ctx->pub_cnt, &ctx->qpts4, &ctx->qry, &ctx->fit_flag, &ctx->lvl_src,
+                      &ctx->stage_a, &ctx->stage_b, &ctx->stage_c, &ctx->stage_d, &ctx->row_done, &ctx->redo_m, &ctx->flag_buf, &ctx->dens_buf, &ctx->pub_pos, &ctx->pub_dist, &ctx->pub_cnt, &ctx->qpts4, &ctx->qry, &ctx->ball_off, &ctx->ball_idx, &ctx->ball_alt, &ctx->ball_dist, &ctx->fit_flag, &ctx->lvl_src,
                       &ctx->tree_codes, &ctx->tree_vals, &ctx->tree_lvl, &ctx->tree_head, &ctx->tree_marks, &ctx->tree_seg, &ctx->tree_runs, &ctx->tree_range, &ctx->tree_bucket, &ctx->tree_tmp,
                       &ctx->pca, &ctx->pca_aux, &ctx->pca_nbr, &ctx->pca_orig,
                       &ctx->bin_rec, &ctx->bin_mat, &ctx->bin_plan, &ctx->bin_base};
@@ -261,6 +262,7 @@ static int new_cloud(pct_ctx* ctx, int64_t n) {
     ctx->slab_split_valid = false;
     ctx->grid_valid = ctx->knn_valid = ctx->fit_valid = ctx->pts4_valid = ctx->qpts4_valid = false;
     ctx->pca_valid = false;
+    ctx->ball_valid = false;
     ctx->has_f64 = false;
     ctx->no_cull = ctx->culled = false;
     ctx->retries = 0;
@@ -940,6 +942,95 @@ int pct_query_points_algo(pct_ctx* ctx, const double* q_xyz, int64_t m, int32_t 
 int pct_query_stats(pct_ctx* ctx, int64_t out[4]) {
     if (!ctx || !out) return PCT_ERR_INVALID;
     for (int i = 0; i < 4; ++i) out[i] = ctx->query_stats[i];
+    return PCT_OK;
+}
+
+// Radius search (pct_ball.hip).  The route is ball_route's (pct_ball_plan.h), from the same state pct_query_points_algo
+// reads; as there, a cell list is built only where nothing in place refers to the cell order, and the timings of the call
+// that produced the table in place stay what they were.
+int pct_query_ball(pct_ctx* ctx, const double* q_xyz, int64_t m, const double* r, int64_t n_r, int32_t flags, int32_t algo,
+                   int64_t max_entries, int64_t* offsets) {
+    PCT_TRY(begin_call(ctx));
+    PCT_TRY(refuse_in_slab_mode(ctx, "pct_query_ball"));
+    if (ctx->n <= 0 || !ctx->xyz_view) return pct_fail(ctx, PCT_ERR_INVALID, "no cloud loaded");
+    if (m < 0 || !offsets || (m > 0 && (!q_xyz || !r))) return pct_fail(ctx, PCT_ERR_INVALID, "bad query arrays");
+    if (m > 0 && n_r != 1 && n_r != m) return pct_fail(ctx, PCT_ERR_INVALID, "%lld radii for %lld queries (one, or one per query)", (long long)n_r, (long long)m);
+    if (flags & ~(PCT_BALL_SORTED | PCT_BALL_DISTANCES | PCT_BALL_COUNT_ONLY)) return pct_fail(ctx, PCT_ERR_INVALID, "unknown flags %d", flags);
+    const pct_grid& g = ctx->grid;
+    bool finite_limits = false;
+    for (int a = 0; a < 3; ++a) finite_limits = finite_limits || isfinite(g.lim_lo[a]) || isfinite(g.lim_hi[a]);
+    QueryState qs = {};
+    qs.uniform_resident = ctx->grid_valid && ctx->grid_whole && !finite_limits;
+    qs.tree_resident = ctx->knn_valid && ctx->knn_hier;
+    qs.sorted_resident = (ctx->knn_valid && ctx->knn_sorted_space) || (ctx->fit_valid && ctx->fit_row_order);
+    qs.sharded = ctx->q_begin != 0 || ctx->q_end != ctx->n;
+    qs.slab = ctx->slab_parts >= 1;
+    QueryRoute route;
+    if (!ball_route(algo, ctx->n, m, qs, &route)) return pct_fail(ctx, PCT_ERR_INVALID, "unknown query algorithm %d", algo);
+    ctx->ball_valid = false;                   // whatever was resident is the previous call's
+    for (int i = 0; i < 4; ++i) ctx->ball_stats[i] = 0;
+    offsets[0] = 0;
+    if (m == 0) {
+        ctx->ball_valid = !(flags & PCT_BALL_COUNT_ONLY);
+        ctx->ball_has_dist = (flags & PCT_BALL_DISTANCES) != 0;
+        ctx->ball_m = 0;
+        return PCT_OK;
+    }
+    for (int64_t i = 0; i < 3 * m; ++i)
+        if (!isfinite(q_xyz[i])) return pct_fail(ctx, PCT_ERR_NONFINITE, "query point %lld is not finite", (long long)(i / 3));
+    if (route == QueryRoute::GridBuild) {
+        // an ordinary resident cell list afterwards, sized as the cloud's own sweep would size it for rows of 30
+        int32_t kb = 30;
+        if ((int64_t)kb + 1 > ctx->n) kb = ctx->n > 1 ? (int32_t)ctx->n - 1 : 1;
+        const pct_timings keep = ctx->tm;
+        GridVerdict built;
+        const int st = pct_build_grid(ctx, kb, 0.0, false, &built);
+        ctx->tm = keep;
+        ctx->counters_clean = false;       // (the words the build cleared belong to no sweep of this call)
+        if (st != PCT_OK) return st;
+        if (!(ctx->grid_valid && ctx->grid_whole))
+            return pct_fail(ctx, PCT_ERR_INVALID, "pct_query_ball: the cell list built is not one list over the whole cloud");
+    }
+    PCT_TRY(pct_reserve(ctx, &ctx->stage_a, (size_t)m * 3 * sizeof(double)));
+    PCT_TRY(pct_reserve(ctx, &ctx->stage_b, (size_t)n_r * sizeof(double)));
+    PCT_HIP(ctx, hipMemcpyAsync(ctx->stage_a.p, q_xyz, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(ctx->stage_b.p, r, (size_t)n_r * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    ctx->ball_stats[0] = (int64_t)route;
+    const int st = pct_launch_ball(ctx, route != QueryRoute::Sweep, (const double*)ctx->stage_a.p, m, (const double*)ctx->stage_b.p,
+                                   n_r == m && m > 1 ? 1 : 0, flags, max_entries, offsets, ctx->ball_stats + 1);
+    if (st != PCT_OK) return st;
+    if (!(flags & PCT_BALL_COUNT_ONLY)) {
+        ctx->ball_valid = true;
+        ctx->ball_has_dist = (flags & PCT_BALL_DISTANCES) != 0;
+        ctx->ball_m = m;
+    }
+    return PCT_OK;
+}
+
+int pct_get_ball(pct_ctx* ctx, int64_t row_begin, int64_t row_end, int32_t* idx, double* dist) {
+    PCT_TRY(begin_call(ctx));
+    if (!ctx->ball_valid) return pct_fail(ctx, PCT_ERR_INVALID, "no ball rows on this handle (pct_query_ball)");
+    if (row_begin < 0 || row_end > ctx->ball_m || row_begin > row_end)
+        return pct_fail(ctx, PCT_ERR_INVALID, "bad row range [%lld,%lld) of %lld", (long long)row_begin, (long long)row_end, (long long)ctx->ball_m);
+    if (dist && !ctx->ball_has_dist) return pct_fail(ctx, PCT_ERR_INVALID, "pct_get_ball: no distances were asked for (PCT_BALL_DISTANCES)");
+    if (row_begin == row_end) return PCT_OK;
+    int64_t ends[2] = {0, 0};
+    const int64_t* d_off = (const int64_t*)ctx->ball_off.p;
+    PCT_HIP(ctx, hipMemcpyAsync(&ends[0], d_off + row_begin, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(&ends[1], d_off + row_end, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const int64_t count = ends[1] - ends[0];
+    if (count <= 0) return PCT_OK;
+    if (!idx) return pct_fail(ctx, PCT_ERR_INVALID, "null output");
+    PCT_HIP(ctx, hipMemcpyAsync(idx, (const int32_t*)ctx->ball_idx.p + ends[0], (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (dist) PCT_HIP(ctx, hipMemcpyAsync(dist, (const double*)ctx->ball_dist.p + ends[0], (size_t)count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PCT_OK;
+}
+
+int pct_ball_stats(pct_ctx* ctx, int64_t out[4]) {
+    if (!ctx || !out) return PCT_ERR_INVALID;
+    for (int i = 0; i < 4; ++i) out[i] = ctx->ball_stats[i];
     return PCT_OK;
 }
 

@@ -284,6 +284,15 @@ struct pct_ctx {
     int32_t query_words[4] = {0, 0, 0, 0};
     int64_t query_stats[4] = {0, 0, 0, 0};
 
+    // pct_query_ball (pct_ball.hip): the CSR rows of the last radius query, resident until the next one or a new cloud
+    pct_buf ball_off;   // int64 (m + 1) offsets
+    pct_buf ball_idx;   // int32 (entries) public indices
+    pct_buf ball_alt;   // ... the other buffer of the library's segmented sort (rows longer than k_ball_sort takes)
+    pct_buf ball_dist;  // double (entries), when asked for
+    bool ball_valid = false, ball_has_dist = false;
+    int64_t ball_m = 0;
+    int64_t ball_stats[4] = {0, 0, 0, 0};
+
     // PCA principal curvatures (pct_pca.hip), public order: double [lambda_1 | lambda_2 | K | H | frame (n,3,2)]
     pct_buf pca;
     pct_buf pca_aux;    // float32 rounding offset, flags, rows handed to the exact pass and their bounds
@@ -442,6 +451,11 @@ int pct_launch_query_points(pct_ctx* ctx, const double* d_q, int64_t m, int32_t 
 // pct_query.hip: the queries through the uniform cell list in place; host_words4 = {work items, rows redone by the exact
 // sweep, largest ring of those, 0} is complete once the stream has been waited for
 int pct_launch_query_grid(pct_ctx* ctx, const double* d_q, int64_t m, int32_t k, double eps, int32_t* d_idx, double* d_dist, int32_t* host_words4);
+// pct_ball.hip: radius search, m >= 1 queries and 1 (r_stride 0) or m (r_stride 1) radii on the device; grid: through the
+// cell list in place, else all n points per query.  h_offsets (m + 1) is complete on return whatever the status;
+// stat3 = {queries answered from a staged cube, queries streamed, largest ring}
+int pct_launch_ball(pct_ctx* ctx, bool grid, const double* d_q, int64_t m, const double* d_r, int r_stride, int32_t flags,
+                    int64_t max_entries, int64_t* h_offsets, int64_t stat3[3]);
 int pct_launch_gather_int(pct_ctx* ctx, const int* d_map, int* d_inout, int64_t n);
 int pct_ensure_row_of(pct_ctx* ctx);     // before any read of ctx->row_of
 int pct_launch_export_rows(pct_ctx* ctx, const int64_t* d_rows, int64_t n_rows, int32_t* d_idx, float* d_dist, int32_t* d_cnt);

@@ -7,10 +7,8 @@
 // strict, padding is index n and +inf.  Every comparison is on exact fp64 keys (Sweep<R>, pct_knn_sweep.h): no float32
 // pre-selection here.
 //
-//   stage 1  k_query_cell_ids, rocprim::radix_sort_pairs, k_query_items: the cell of every query (query_cell_coord,
-//            pct_query_plan.h), the query indices sorted by cell, work items {cell, first sorted query, <= kItemQ queries}.
-//            (The sort is the library's, as in pct_tree.hip, not a histogram over the cells: m is the small side, the
-//            grid may hold 2^27 cells, and no pass here is sized by the grid.)
+//   stage 1  pct_query_stage1 (pct_query_items.h, shared with pct_ball.hip): the cell of every query, the query indices
+//            sorted by cell, work items {cell, first sorted query, <= kItemQ queries}.
 //   stage 2  k_query_cells: one wave = one work item.  The item's 27-cell stencil is staged into LDS once (16-byte
 //            records {x, y, z, sorted position}, PCT_STAGE_CAP2 of them per wave), Sweep<R> runs over the staged
 //            candidates for each query of the item; a row is stored only if the 27 cells vouch for it
@@ -20,18 +18,12 @@
 //            array: candidates shell by shell from global memory, one step ahead of their use, until the searched cube
 //            vouches for the row or covers the grid.
 // Rows go straight to the caller's (m, k) arrays in the caller's query order, sorted positions translated to public indices.
-#include "pct_knn_sweep.h"
-#include "pct_query_plan.h"
-
-#include <rocprim/device/device_radix_sort.hpp>
+#include "pct_query_items.h"
 
 namespace {
 
-constexpr int kItemQ = 16;                           // queries per work item (the cloud's own items: pct_build_grid)
 constexpr int kQueryCap = PCT_STAGE_CAP2;            // staged candidates per wave: 768 x 16 B = 12 KiB, 4 waves + their pending
                                                      // buffers ~ 57 KiB per block, two blocks per CU's 160 KiB
-
-struct QueryWords { int n_items, redo_count, max_ring, reserved; };      // device words of one call, cleared before it
 
 struct QueryArgs {
     const float4* pts;          // cell-sorted candidate records {x, y, z, public index}
@@ -49,52 +41,6 @@ struct QueryArgs {
     int* idx_out;
     double* dist_out;
 };
-
-__global__ __launch_bounds__(256) void k_query_cell_ids(const double* __restrict__ q, int64_t m, pct_grid g, unsigned* __restrict__ keys,
-                                                        unsigned* __restrict__ vals) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= m) return;
-    const int cx = query_cell_coord(q[3 * i], g.ox, g.inv_cell, g.nx);
-    const int cy = query_cell_coord(q[3 * i + 1], g.oy, g.inv_cell, g.ny);
-    const int cz = query_cell_coord(q[3 * i + 2], g.oz, g.inv_cell, g.nz);
-    keys[i] = (unsigned)((cz * g.ny + cy) * g.nx + cx);       // < ncell <= 2^30 (pct_build_grid's cell budget)
-    vals[i] = (unsigned)i;
-}
-
-// One thread per sorted query: the thread at offset 0, kItemQ, 2 kItemQ ... of its cell's run appends an item.  (Both
-// bounds of the run by binary search over the sorted keys: ~20 cached loads, m is the small side of the problem.)
-__global__ __launch_bounds__(256) void k_query_items(const unsigned* __restrict__ keys, int64_t m, int4* __restrict__ items,
-                                                     QueryWords* __restrict__ words) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    bool head = false;
-    unsigned key = 0;
-    int nq = 0;
-    if (i < m) {
-        key = keys[i];
-        int64_t lo = 0, hi = i;                       // first position of the run: the smallest p with keys[p] >= key
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (keys[mid] < key) lo = mid + 1; else hi = mid;
-        }
-        head = ((i - lo) % kItemQ) == 0;
-        if (head) {
-            int64_t a = i, b = m;                     // end of the run: the smallest p > i with keys[p] > key
-            while (a < b) {
-                const int64_t mid = (a + b) >> 1;
-                if (keys[mid] <= key) a = mid + 1; else b = mid;
-            }
-            nq = (int)(a - i < kItemQ ? a - i : kItemQ);
-        }
-    }
-    const unsigned long long mask = __ballot(head);
-    int base = 0;
-    if ((threadIdx.x & 63) == 0 && mask) base = atomicAdd(&words->n_items, __popcll(mask));
-    base = __shfl(base, 0);
-    if (head) {
-        const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
-        items[base + rank] = make_int4((int)key, (int)i, nq, 0);         // at most m items: one per query
-    }
-}
 
 // the k nearest of the running list -> row qi of the caller's arrays
 template <int R>
@@ -282,8 +228,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_query_exact(QueryArgs a
     if (lane == 0 && ring_max > 0) atomicMax(&a.words->max_ring, ring_max);       // once per wave
 }
 
-size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace
 
 // m >= 1 queries (device array d_q) against the uniform cell list in place.  host_words4 = {work items, rows redone by
@@ -291,31 +235,9 @@ size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
 // anyway); rows stored by stage 2 = m - rows redone.
 int pct_launch_query_grid(pct_ctx* ctx, const double* d_q, int64_t m, int32_t k, double eps, int32_t* d_idx, double* d_dist, int32_t* host_words4) {
     const pct_grid& g = ctx->grid;
-    if (g.ncell > ((int64_t)1 << 31) - 1 || m > ((int64_t)1 << 30))
-        return pct_fail(ctx, PCT_ERR_INVALID, "query through the cell list: %lld cells / %lld queries out of range", (long long)g.ncell, (long long)m);
-    int bits = 1;
-    while (bits < 31 && ((int64_t)1 << bits) < g.ncell) ++bits;
-    unsigned* nul = nullptr;
-    size_t tmp_bytes = 0;
-    PCT_HIP(ctx, rocprim::radix_sort_pairs(nullptr, tmp_bytes, nul, nul, nul, nul, (size_t)m, 0, bits, ctx->stream));
-    // one allocation: words | keys | sorted keys | query indices | sorted query indices | items | redo list | sort scratch
-    const size_t um = round256((size_t)m * sizeof(unsigned));
-    const size_t off_keys = 256, off_keys2 = off_keys + um, off_vals = off_keys2 + um, off_vals2 = off_vals + um;
-    const size_t off_items = off_vals2 + um, off_redo = off_items + round256((size_t)m * sizeof(int4));
-    const size_t off_tmp = off_redo + um;
-    PCT_TRY(pct_reserve(ctx, &ctx->qry, off_tmp + round256(tmp_bytes) + 256));
-    char* base = (char*)ctx->qry.p;
-    QueryWords* words = (QueryWords*)base;
-    unsigned *keys = (unsigned*)(base + off_keys), *keys2 = (unsigned*)(base + off_keys2);
-    unsigned *vals = (unsigned*)(base + off_vals), *vals2 = (unsigned*)(base + off_vals2);
-    PCT_HIP(ctx, hipMemsetAsync(words, 0, sizeof(QueryWords), ctx->stream));
-    const unsigned nb = (unsigned)((m + 255) / 256);
-    PCT_LAUNCH(k_query_cell_ids, dim3(nb), dim3(256), 0, ctx->stream, d_q, m, g, keys, vals);
-    PCT_HIP(ctx, hipGetLastError());
-    PCT_HIP(ctx, rocprim::radix_sort_pairs(base + off_tmp, tmp_bytes, keys, keys2, vals, vals2, (size_t)m, 0, bits, ctx->stream));
-    PCT_LAUNCH(k_query_items, dim3(nb), dim3(256), 0, ctx->stream, (const unsigned*)keys2, m, (int4*)(base + off_items), words);
-    PCT_HIP(ctx, hipGetLastError());
-
+    QueryItems st;
+    PCT_TRY(pct_query_stage1(ctx, d_q, m, (size_t)m * sizeof(int), &st));       // extra: the redo list
+    QueryWords* words = st.words;
     QueryArgs a = {};
     a.pts = (const float4*)ctx->sorted4.p;
     a.cell_start = (const int*)ctx->cell_cnt.p;
@@ -325,10 +247,10 @@ int pct_launch_query_grid(pct_ctx* ctx, const double* d_q, int64_t m, int32_t k,
     a.n = (int)ctx->n;
     a.k = k;
     a.eps2 = eps > 0 ? eps * eps : (double)INFINITY;
-    a.q_sorted = vals2;
-    a.items = (const int4*)(base + off_items);
+    a.q_sorted = st.q_sorted;
+    a.items = st.items;
     a.words = words;
-    a.redo = (int*)(base + off_redo);
+    a.redo = (int*)st.extra;
     a.idx_out = d_idx;
     a.dist_out = d_dist;
     // device-side counts, fixed grids: at most m items / m redone queries, one per wave

@@ -68,7 +68,9 @@ class _DeviceTree:
     (pct:625, 759, 844): ``query(x, k)`` for arbitrary points, answered on the device (``pct_query_points_algo`` with
     ``PCT_QUERY_AUTO``: the exhaustive sweep for a few points, the cell list for the points of another cloud -- the same
     rows either way).  Same return convention as SciPy: distances float64 ascending and indices, shape
-    ``x.shape[:-1] + (k,)`` (the ``k`` axis squeezed for ``k == 1``), missing entries ``inf`` / ``n``."""
+    ``x.shape[:-1] + (k,)`` (the ``k`` axis squeezed for ``k == 1``), missing entries ``inf`` / ``n``.
+    ``query_ball_point(x, r)`` is SciPy's radius search (``pct_query_ball``: rows of any length, ``d <= r`` inclusive),
+    ``query_ball_point_csr`` the same rows as offsets and one index array."""
 
     def __init__(self, cloud):
         self._cloud = cloud
@@ -92,6 +94,71 @@ class _DeviceTree:
         idx, dist = self._cloud._ctx().query_points(flat, int(k), 0.0 if not np.isfinite(bound) else bound)
         shape = x.shape[:-1] + ((int(k),) if k > 1 else ())
         return dist.reshape(shape), idx.astype(np.intp).reshape(shape)
+
+    def _ball_csr(self, flat, radii, sorted, distances, max_entries):
+        """CSR rows of (m,3) queries with (m,) radii; the queries are chunked where one call would hold more than
+        ``max_entries`` entries (the capped call's count pass gives the offsets the chunks are cut by)."""
+        h = self._cloud._ctx()
+        flags = (_capi.BALL_SORTED if sorted else 0) | (_capi.BALL_DISTANCES if distances else 0)
+        one = len(radii) > 0 and bool((radii == radii[0]).all())
+        st, offsets = h.query_ball(flat, radii[:1] if one else radii, flags, _capi.QUERY_AUTO, max_entries)
+        if st == _capi.PCT_OK:
+            got = h.get_ball(0, len(flat), want_dist=distances)
+            return (offsets,) + (got if distances else (got,))
+        idx = np.empty(int(offsets[-1]), np.int32)
+        dist = np.empty(int(offsets[-1]), np.float64) if distances else None
+        begin = 0
+        while begin < len(flat):
+            # as many rows as the budget holds, one at the least (a single row longer than the budget goes alone, uncapped)
+            end = max(int(np.searchsorted(offsets, offsets[begin] + max_entries, side="right")) - 1, begin + 1)
+            st, part = h.query_ball(flat[begin:end], radii[:1] if one else radii[begin:end], flags, _capi.QUERY_AUTO, 0)
+            assert np.array_equal(part, offsets[begin:end + 1] - offsets[begin])
+            got = h.get_ball(0, end - begin, want_dist=distances)
+            idx[offsets[begin]:offsets[end]] = got[0] if distances else got
+            if distances:
+                dist[offsets[begin]:offsets[end]] = got[1]
+            begin = end
+        return (offsets, idx, dist) if distances else (offsets, idx)
+
+    def _ball_arguments(self, x, r):
+        x = np.asarray(x, dtype=np.float64)
+        if x.shape[-1:] != (3,):
+            raise ValueError(f"x must consist of vectors of length 3 but has shape {x.shape}")
+        if not np.isfinite(x).all():
+            raise ValueError("'x' must be finite, check for nan or inf values")
+        radii = np.empty(x.shape[:-1], np.float64)
+        radii[...] = r                                   # SciPy's broadcast, and its error for a shape that does not fit
+        return x, np.ascontiguousarray(x.reshape(-1, 3)), radii.reshape(-1)
+
+    def query_ball_point(self, x, r, p=2., eps=0, workers=1, return_sorted=None, return_length=False, max_entries=1 << 28):
+        """SciPy's ``query_ball_point``: the indices of every cloud point within ``r`` of ``x`` (inclusive), on the
+        device (``pct_query_ball``).  A single point gives a list (an int with ``return_length``), an array of points an
+        object array of lists (an int64 array of lengths); ``return_sorted=None`` sorts for a single point only.
+        ``max_entries``: entries one device call may hold before the queries are chunked."""
+        if eps != 0 or p != 2:
+            raise NotImplementedError("only exact Euclidean queries (eps=0, p=2) run on the device")
+        if return_sorted and return_length:
+            raise ValueError("return_sorted and return_length cannot both be asked for")
+        x, flat, radii = self._ball_arguments(x, r)
+        if return_length:
+            _, offsets = self._cloud._ctx().query_ball(flat, radii, _capi.BALL_COUNT_ONLY, _capi.QUERY_AUTO, 0)
+            lengths = np.diff(offsets).reshape(x.shape[:-1])
+            return int(lengths) if x.ndim == 1 else lengths
+        sort = bool(return_sorted) or (return_sorted is None and x.ndim == 1)
+        offsets, idx = self._ball_csr(flat, radii, sort, False, int(max_entries))
+        if x.ndim == 1:
+            return idx.tolist()
+        out = np.empty(len(flat), dtype=object)
+        rows = idx.tolist()
+        for i in range(len(flat)):
+            out[i] = rows[offsets[i]:offsets[i + 1]]
+        return out.reshape(x.shape[:-1])
+
+    def query_ball_point_csr(self, x, r, sorted=True, distances=False, max_entries=1 << 28):
+        """The same rows without the Python lists: ``(offsets int64 (m + 1), indices int32[, distances float64])`` for the
+        ``x.reshape(-1, 3)`` queries; row i is ``indices[offsets[i]:offsets[i + 1]]``."""
+        x, flat, radii = self._ball_arguments(x, r)
+        return self._ball_csr(flat, radii, bool(sorted), bool(distances), int(max_entries))
 
 
 class PointCloud:

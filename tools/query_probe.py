@@ -5,6 +5,11 @@
     python tools/query_probe.py gain           n = m = 65 536, k = 16: the three paths, and pct_query_points itself
     python tools/query_probe.py big            n = m = 1 M, k = 16 and 50, QUERY_GRID only; the share of queries redone
                                                by the exact sweep on the torus and on tests/wide_exact.py's clump
+    python tools/query_probe.py ball           radius search: random torus, n in {65 536, 1 M} x m in {1024 .. 1 M}, r for
+                                               rows of ~16, ~50 and ~500 points; QUERY_SWEEP | QUERY_GRID (resident) | QUERY_GRID (built by
+                                               the call), sorted rows, the download of the rows included; beside them SciPy's
+                                               cKDTree.query_ball_point(..., workers=-1, return_sorted=True) on the same host (tree build
+                                               apart).  BALL_PROBE_SECONDS (default 540) bounds the run: what is left then is not measured.
 
 Times are host wall time of the whole call -- upload of the queries, kernels, download of the rows -- around a call that
 ends in a stream synchronisation: what a caller of PointCloud.kdtree.query waits for.  Every shape is warmed up once, then
@@ -69,9 +74,76 @@ def paths(h, pts, q, k, sweep=True):
     return out
 
 
+TORUS_AREA = 4.0 * np.pi ** 2 * 1.0 * (1.0 / 3.0)          # shapes.torus_random: R = 1, r = 1/3
+
+
+def ball_probe(h):
+    from scipy.spatial import cKDTree                        # the reference's engine, for the column beside ours
+    t_end = time.perf_counter() + float(os.environ.get("BALL_PROBE_SECONDS", "540"))
+    flags = _capi.BALL_SORTED
+
+    def ball(q, r, algo):
+        st, off = h.query_ball(q, r, flags, algo)
+        assert st == _capi.PCT_OK
+        return off, h.get_ball(0, len(q))
+
+    for n in (65536, 1 << 20):
+        pts = shapes.torus_random(n, seed=1234)
+        t = time.perf_counter()
+        tree = cKDTree(pts)
+        tree_ms = (time.perf_counter() - t) * 1e3
+        for want_rows in (16, 50, 500):
+            r = float(np.sqrt(want_rows * TORUS_AREA / (np.pi * n)))
+            for m in (1024, 16384, 262144, 1 << 20):
+                if time.perf_counter() > t_end:
+                    print(json.dumps({"n": n, "m": m, "rows_wanted": want_rows, "skipped": "time"}), flush=True)
+                    continue
+                q = queries(pts, m, 5)
+                rec = {"n": n, "m": m, "mn_log2": float(np.log2(n * m)), "r": r, "rows_wanted": want_rows, "scipy_tree_build": tree_ms}
+                if m * want_rows > (1 << 28):
+                    rec["skipped"] = "entries"
+                    print(json.dumps(rec), flush=True)
+                    continue
+                h.set_points(pts)
+                h.knn(30)                                   # a resident whole-cloud list, as a planted cloud has
+                off, idx = ball(q, r, _capi.QUERY_GRID)
+                st = h.ball_stats()
+                assert st["route"] == 1, st
+                rec.update(entries=int(off[-1]), mean_row=float(off[-1] / m), longest_row=int(np.diff(off).max()), stats=st)
+                sweep = n * m <= (1 << 40)
+                if sweep:                                    # the same rows on both paths, at the size that is timed
+                    off2, idx2 = ball(q, r, _capi.QUERY_SWEEP)
+                    rec["same_rows"] = bool(np.array_equal(off, off2) and np.array_equal(idx, idx2))
+                reps = 3 if n * m > (1 << 30) else REPS
+                tg, ts = [], []
+                for _ in range(reps):                        # the two paths alternate inside one loop
+                    t = time.perf_counter(); ball(q, r, _capi.QUERY_GRID); tg.append((time.perf_counter() - t) * 1e3)
+                    if sweep:
+                        t = time.perf_counter(); ball(q, r, _capi.QUERY_SWEEP); ts.append((time.perf_counter() - t) * 1e3)
+                rec["grid_resident"] = (float(np.median(tg)), float(min(tg)), float(max(tg)))
+                if sweep:
+                    rec["sweep"] = (float(np.median(ts)), float(min(ts)), float(max(ts)))
+                tb = []
+                for _ in range(3):
+                    h.set_points(pts)                       # (a fresh cloud: the call builds the list; the upload is timed apart)
+                    t = time.perf_counter(); ball(q, r, _capi.QUERY_GRID); tb.append((time.perf_counter() - t) * 1e3)
+                    assert h.ball_stats()["route"] == 2
+                rec["grid_build"] = (float(np.median(tb[1:])), float(min(tb[1:])), float(max(tb[1:])))
+                if m * want_rows <= (1 << 24):
+                    tsp = []
+                    for _ in range(3):
+                        t = time.perf_counter(); tree.query_ball_point(q, r, workers=-1, return_sorted=True); tsp.append((time.perf_counter() - t) * 1e3)
+                    rec["scipy"] = (float(np.median(tsp[1:])), float(min(tsp[1:])), float(max(tsp[1:])))
+                print(json.dumps(rec), flush=True)
+
+
 def main():
     what = sys.argv[1] if len(sys.argv) > 1 else "gain"
     h = _capi.Handle(0)
+    if what == "ball":
+        ball_probe(h)
+        h.close()
+        return
     if what == "crossover":
         sizes = [4096, 16384, 65536, 262144, 1 << 20]
         ms = [1024, 4096, 16384, 65536, 262144, 1 << 20]
