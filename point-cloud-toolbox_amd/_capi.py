@@ -220,6 +220,14 @@ def _ptr(a, typ):
     return None if a is None else a.ctypes.data_as(typ)
 
 
+def _queries(q, message):
+    """Caller-supplied query points as a contiguous (m, 3) float64 array."""
+    q = np.ascontiguousarray(q, dtype=np.float64)
+    if q.ndim != 2 or q.shape[1] != 3:
+        raise ValueError(message)
+    return q
+
+
 _handle_pool = {}          # device -> one idle Handle whose device buffers stay allocated (PointCloud.close puts it there)
 
 
@@ -374,9 +382,7 @@ class Handle:
     def query_points(self, q, k, eps=0.0, algo=QUERY_AUTO):
         """The reference tree's ``query`` for arbitrary points: (m,3) float64 -> idx (m,k) int32 (missing: N), dist (m,k) float64 (missing: inf).
         ``algo``: QUERY_AUTO (large query sets through the cell list), QUERY_SWEEP, QUERY_GRID -- the same rows either way."""
-        q = np.ascontiguousarray(q, dtype=np.float64)
-        if q.ndim != 2 or q.shape[1] != 3:
-            raise ValueError("query points must have shape (m, 3)")
+        q = _queries(q, "query points must have shape (m, 3)")
         idx = np.empty((len(q), int(k)), np.int32)
         dist = np.empty((len(q), int(k)), np.float64)
         self._check(self._lib.pct_query_points_algo(self._h, _ptr(q, _f64p), len(q), int(k), float(eps or 0.0), int(algo),
@@ -388,9 +394,7 @@ class Handle:
         float64 query.  Returns ``(status, offsets)`` -- PCT_OK, or PCT_ERR_LIMIT when the rows hold more than
         ``max_entries`` entries (offsets valid, nothing resident); every other status raises.  The rows stay on the
         device for ``get_ball``."""
-        q = np.ascontiguousarray(q, dtype=np.float64)
-        if q.ndim != 2 or q.shape[1] != 3:
-            raise ValueError("query points must have shape (m,3)")
+        q = _queries(q, "query points must have shape (m,3)")
         r = np.ascontiguousarray(np.atleast_1d(r), dtype=np.float64)
         if r.ndim != 1:
             raise ValueError("radii must be a scalar or have shape (m,)")

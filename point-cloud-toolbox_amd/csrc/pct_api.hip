@@ -857,37 +857,11 @@ int pct_fit_indices_f64(pct_ctx* ctx, const int32_t* idx, const int32_t* count, 
     return PCT_OK;       // the resident float32 results and the neighbour table are untouched
 }
 
-int pct_query_points(pct_ctx* ctx, const double* q_xyz, int64_t m, int32_t k, double eps, int32_t* idx, double* dist) {
-    PCT_TRY(begin_call(ctx));
-    PCT_TRY(refuse_in_slab_mode(ctx, "pct_query_points"));
-    if (ctx->n <= 0 || !ctx->xyz_view) return pct_fail(ctx, PCT_ERR_INVALID, "no cloud loaded");
-    if (m < 0 || (m > 0 && (!q_xyz || !idx || !dist))) return pct_fail(ctx, PCT_ERR_INVALID, "bad query arrays");
-    if (k < 1 || k > 128) return pct_fail(ctx, PCT_ERR_INVALID, "k=%d outside [1,128]", k);
-    if (m == 0) return PCT_OK;
-    for (int64_t i = 0; i < 3 * m; ++i)
-        if (!isfinite(q_xyz[i])) return pct_fail(ctx, PCT_ERR_NONFINITE, "query point %lld is not finite", (long long)(i / 3));
-    if (!(eps >= 0) || isinf(eps)) eps = 0;
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_a, (size_t)m * 3 * sizeof(double)));
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_b, (size_t)m * k * sizeof(int32_t)));
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_c, (size_t)m * k * sizeof(double)));
-    PCT_HIP(ctx, hipMemcpyAsync(ctx->stage_a.p, q_xyz, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    PCT_TRY(pct_launch_query_points(ctx, (const double*)ctx->stage_a.p, m, k, eps, (int32_t*)ctx->stage_b.p, (double*)ctx->stage_c.p));
-    PCT_HIP(ctx, hipMemcpyAsync(idx, ctx->stage_b.p, (size_t)m * k * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(dist, ctx->stage_c.p, (size_t)m * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PCT_OK;
-}
-
-// pct_query_points with the path named: the exhaustive sweep above, or the uniform cell list (pct_query.hip).  The rule
-// is query_route's (pct_query_plan.h); what it reads of the handle is gathered here.  Nothing resident is disturbed: a
-// cell list is built only where no table or result in place refers to the cell order, and the timings of the call that
-// produced the table in place stay what they were.
-int pct_query_points_algo(pct_ctx* ctx, const double* q_xyz, int64_t m, int32_t k, double eps, int32_t algo, int32_t* idx, double* dist) {
-    PCT_TRY(begin_call(ctx));
-    PCT_TRY(refuse_in_slab_mode(ctx, "pct_query_points_algo"));
-    if (ctx->n <= 0 || !ctx->xyz_view) return pct_fail(ctx, PCT_ERR_INVALID, "no cloud loaded");
-    if (m < 0 || (m > 0 && (!q_xyz || !idx || !dist))) return pct_fail(ctx, PCT_ERR_INVALID, "bad query arrays");
-    if (k < 1 || k > 128) return pct_fail(ctx, PCT_ERR_INVALID, "k=%d outside [1,128]", k);
+// ---- queries of caller-supplied points: what pct_query_points, pct_query_points_algo and pct_query_ball share ----------------
+// What query_route and ball_route (pct_query_plan.h, pct_ball_plan.h) are told of the handle.  The only place that reads
+// these fields for routing: a residency flag missed here reroutes a call, and a wrong reroute is a rebuild that
+// invalidates a resident table.
+static QueryState query_state(const pct_ctx* ctx) {
     const pct_grid& g = ctx->grid;
     bool finite_limits = false;
     for (int a = 0; a < 3; ++a) finite_limits = finite_limits || isfinite(g.lim_lo[a]) || isfinite(g.lim_hi[a]);
@@ -897,27 +871,58 @@ int pct_query_points_algo(pct_ctx* ctx, const double* q_xyz, int64_t m, int32_t 
     qs.sorted_resident = (ctx->knn_valid && ctx->knn_sorted_space) || (ctx->fit_valid && ctx->fit_row_order);
     qs.sharded = ctx->q_begin != 0 || ctx->q_end != ctx->n;      // (a culled list in place: finite limits, not uniform_resident)
     qs.slab = ctx->slab_parts >= 1;
-    QueryRoute route;
-    if (!query_route(algo, ctx->n, m, k, qs, &route)) return pct_fail(ctx, PCT_ERR_INVALID, "unknown query algorithm %d", algo);
-    for (int i = 0; i < 4; ++i) ctx->query_stats[i] = 0;
-    if (m == 0) return PCT_OK;
+    return qs;
+}
+
+// The caller's arrays, in the two steps every entry takes them in: a cloud and the arrays themselves before the entry's
+// own arguments (others: whatever else the entry needs besides the m queries is there) ...
+static int check_query_arrays(pct_ctx* ctx, const double* q_xyz, int64_t m, bool others) {
+    if (ctx->n <= 0 || !ctx->xyz_view) return pct_fail(ctx, PCT_ERR_INVALID, "no cloud loaded");
+    if (m < 0 || !others || (m > 0 && !q_xyz)) return pct_fail(ctx, PCT_ERR_INVALID, "bad query arrays");
+    return PCT_OK;
+}
+// ... and their values after them, once the call is known to read any
+static int check_queries_finite(pct_ctx* ctx, const double* q_xyz, int64_t m) {
     for (int64_t i = 0; i < 3 * m; ++i)
         if (!isfinite(q_xyz[i])) return pct_fail(ctx, PCT_ERR_NONFINITE, "query point %lld is not finite", (long long)(i / 3));
-    if (!(eps >= 0) || isinf(eps)) eps = 0;
-    if (route == QueryRoute::GridBuild) {
-        // an ordinary resident cell list afterwards, sized as the cloud's own sweep would size it for rows of k
-        // (two list registers at the most: the occupancy rule of longer rows is the exact-only sweep's)
-        int32_t kb = k < 127 ? k : 127;
-        if ((int64_t)kb + 1 > ctx->n) kb = ctx->n > 1 ? (int32_t)ctx->n - 1 : 1;
-        const pct_timings keep = ctx->tm;
-        GridVerdict built;
-        const int st = pct_build_grid(ctx, kb, 0.0, false, &built);
-        ctx->tm = keep;
-        ctx->counters_clean = false;       // (the words the build cleared belong to no sweep of this call)
-        if (st != PCT_OK) return st;       // (every refusal of the build is the caller's to see: none is turned into another route)
-        if (!(ctx->grid_valid && ctx->grid_whole))
-            return pct_fail(ctx, PCT_ERR_INVALID, "pct_query_points_algo: the cell list built is not one list over the whole cloud");
+    return PCT_OK;
+}
+
+// QueryRoute::GridBuild for the entry `who`: an ordinary resident cell list afterwards, sized as the cloud's own sweep
+// would size it for rows of kb.  Nothing resident is disturbed: the route builds only where no table or result in place
+// refers to the cell order, and the timings of the call that produced the table in place stay what they were.
+static int build_query_grid(pct_ctx* ctx, int32_t kb, const char* who) {
+    if ((int64_t)kb + 1 > ctx->n) kb = ctx->n > 1 ? (int32_t)ctx->n - 1 : 1;
+    const pct_timings keep = ctx->tm;
+    GridVerdict built;
+    const int st = pct_build_grid(ctx, kb, 0.0, false, &built);
+    ctx->tm = keep;
+    ctx->counters_clean = false;       // (the words the build cleared belong to no sweep of this call)
+    if (st != PCT_OK) return st;       // (every refusal of the build is the caller's to see: none is turned into another route)
+    if (!(ctx->grid_valid && ctx->grid_whole))
+        return pct_fail(ctx, PCT_ERR_INVALID, "%s: the cell list built is not one list over the whole cloud", who);
+    return PCT_OK;
+}
+
+// The k nearest of m caller-supplied points.  algo names the path: the exhaustive sweep (pct_knn.hip) or the uniform cell
+// list (pct_query.hip), by query_route's rule.  algo == nullptr is pct_query_points: the sweep whatever is resident, so
+// never a list built, and query_stats stay those of the last pct_query_points_algo call.
+static int query_points(pct_ctx* ctx, const char* who, const double* q_xyz, int64_t m, int32_t k, double eps, const int32_t* algo,
+                        int32_t* idx, double* dist) {
+    PCT_TRY(begin_call(ctx));
+    PCT_TRY(refuse_in_slab_mode(ctx, who));
+    PCT_TRY(check_query_arrays(ctx, q_xyz, m, m == 0 || (idx && dist)));
+    if (k < 1 || k > 128) return pct_fail(ctx, PCT_ERR_INVALID, "k=%d outside [1,128]", k);
+    QueryRoute route = QueryRoute::Sweep;
+    if (algo) {
+        if (!query_route(*algo, ctx->n, m, k, query_state(ctx), &route)) return pct_fail(ctx, PCT_ERR_INVALID, "unknown query algorithm %d", *algo);
+        for (int i = 0; i < 4; ++i) ctx->query_stats[i] = 0;
     }
+    if (m == 0) return PCT_OK;
+    PCT_TRY(check_queries_finite(ctx, q_xyz, m));
+    if (!(eps >= 0) || isinf(eps)) eps = 0;
+    // (two list registers at the most: the occupancy rule of longer rows is the exact-only sweep's)
+    if (route == QueryRoute::GridBuild) PCT_TRY(build_query_grid(ctx, k < 127 ? k : 127, who));
     PCT_TRY(pct_reserve(ctx, &ctx->stage_a, (size_t)m * 3 * sizeof(double)));
     PCT_TRY(pct_reserve(ctx, &ctx->stage_b, (size_t)m * k * sizeof(int32_t)));
     PCT_TRY(pct_reserve(ctx, &ctx->stage_c, (size_t)m * k * sizeof(double)));
@@ -929,7 +934,7 @@ int pct_query_points_algo(pct_ctx* ctx, const double* q_xyz, int64_t m, int32_t 
     PCT_HIP(ctx, hipMemcpyAsync(idx, ctx->stage_b.p, (size_t)m * k * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     PCT_HIP(ctx, hipMemcpyAsync(dist, ctx->stage_c.p, (size_t)m * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->query_stats[0] = (int64_t)route;
+    if (algo) ctx->query_stats[0] = (int64_t)route;
     if (route != QueryRoute::Sweep) {
         const int64_t redone = ctx->query_words[1];
         ctx->query_stats[1] = m - redone;
@@ -939,34 +944,30 @@ int pct_query_points_algo(pct_ctx* ctx, const double* q_xyz, int64_t m, int32_t 
     return PCT_OK;
 }
 
+int pct_query_points(pct_ctx* ctx, const double* q_xyz, int64_t m, int32_t k, double eps, int32_t* idx, double* dist) {
+    return query_points(ctx, "pct_query_points", q_xyz, m, k, eps, nullptr, idx, dist);
+}
+
+int pct_query_points_algo(pct_ctx* ctx, const double* q_xyz, int64_t m, int32_t k, double eps, int32_t algo, int32_t* idx, double* dist) {
+    return query_points(ctx, "pct_query_points_algo", q_xyz, m, k, eps, &algo, idx, dist);
+}
+
 int pct_query_stats(pct_ctx* ctx, int64_t out[4]) {
     if (!ctx || !out) return PCT_ERR_INVALID;
     for (int i = 0; i < 4; ++i) out[i] = ctx->query_stats[i];
     return PCT_OK;
 }
 
-// Radius search (pct_ball.hip).  The route is ball_route's (pct_ball_plan.h), from the same state pct_query_points_algo
-// reads; as there, a cell list is built only where nothing in place refers to the cell order, and the timings of the call
-// that produced the table in place stay what they were.
+// Radius search (pct_ball.hip).  The route is ball_route's (pct_ball_plan.h), from the same state query_points reads.
 int pct_query_ball(pct_ctx* ctx, const double* q_xyz, int64_t m, const double* r, int64_t n_r, int32_t flags, int32_t algo,
                    int64_t max_entries, int64_t* offsets) {
     PCT_TRY(begin_call(ctx));
     PCT_TRY(refuse_in_slab_mode(ctx, "pct_query_ball"));
-    if (ctx->n <= 0 || !ctx->xyz_view) return pct_fail(ctx, PCT_ERR_INVALID, "no cloud loaded");
-    if (m < 0 || !offsets || (m > 0 && (!q_xyz || !r))) return pct_fail(ctx, PCT_ERR_INVALID, "bad query arrays");
+    PCT_TRY(check_query_arrays(ctx, q_xyz, m, offsets && (m == 0 || r)));
     if (m > 0 && n_r != 1 && n_r != m) return pct_fail(ctx, PCT_ERR_INVALID, "%lld radii for %lld queries (one, or one per query)", (long long)n_r, (long long)m);
     if (flags & ~(PCT_BALL_SORTED | PCT_BALL_DISTANCES | PCT_BALL_COUNT_ONLY)) return pct_fail(ctx, PCT_ERR_INVALID, "unknown flags %d", flags);
-    const pct_grid& g = ctx->grid;
-    bool finite_limits = false;
-    for (int a = 0; a < 3; ++a) finite_limits = finite_limits || isfinite(g.lim_lo[a]) || isfinite(g.lim_hi[a]);
-    QueryState qs = {};
-    qs.uniform_resident = ctx->grid_valid && ctx->grid_whole && !finite_limits;
-    qs.tree_resident = ctx->knn_valid && ctx->knn_hier;
-    qs.sorted_resident = (ctx->knn_valid && ctx->knn_sorted_space) || (ctx->fit_valid && ctx->fit_row_order);
-    qs.sharded = ctx->q_begin != 0 || ctx->q_end != ctx->n;
-    qs.slab = ctx->slab_parts >= 1;
     QueryRoute route;
-    if (!ball_route(algo, ctx->n, m, qs, &route)) return pct_fail(ctx, PCT_ERR_INVALID, "unknown query algorithm %d", algo);
+    if (!ball_route(algo, ctx->n, m, query_state(ctx), &route)) return pct_fail(ctx, PCT_ERR_INVALID, "unknown query algorithm %d", algo);
     ctx->ball_valid = false;                   // whatever was resident is the previous call's
     for (int i = 0; i < 4; ++i) ctx->ball_stats[i] = 0;
     offsets[0] = 0;
@@ -976,21 +977,8 @@ int pct_query_ball(pct_ctx* ctx, const double* q_xyz, int64_t m, const double* r
         ctx->ball_m = 0;
         return PCT_OK;
     }
-    for (int64_t i = 0; i < 3 * m; ++i)
-        if (!isfinite(q_xyz[i])) return pct_fail(ctx, PCT_ERR_NONFINITE, "query point %lld is not finite", (long long)(i / 3));
-    if (route == QueryRoute::GridBuild) {
-        // an ordinary resident cell list afterwards, sized as the cloud's own sweep would size it for rows of 30
-        int32_t kb = 30;
-        if ((int64_t)kb + 1 > ctx->n) kb = ctx->n > 1 ? (int32_t)ctx->n - 1 : 1;
-        const pct_timings keep = ctx->tm;
-        GridVerdict built;
-        const int st = pct_build_grid(ctx, kb, 0.0, false, &built);
-        ctx->tm = keep;
-        ctx->counters_clean = false;       // (the words the build cleared belong to no sweep of this call)
-        if (st != PCT_OK) return st;
-        if (!(ctx->grid_valid && ctx->grid_whole))
-            return pct_fail(ctx, PCT_ERR_INVALID, "pct_query_ball: the cell list built is not one list over the whole cloud");
-    }
+    PCT_TRY(check_queries_finite(ctx, q_xyz, m));
+    if (route == QueryRoute::GridBuild) PCT_TRY(build_query_grid(ctx, 30, "pct_query_ball"));      // (rows of 30: the cloud's usual sweep)
     PCT_TRY(pct_reserve(ctx, &ctx->stage_a, (size_t)m * 3 * sizeof(double)));
     PCT_TRY(pct_reserve(ctx, &ctx->stage_b, (size_t)n_r * sizeof(double)));
     PCT_HIP(ctx, hipMemcpyAsync(ctx->stage_a.p, q_xyz, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));

@@ -5,8 +5,8 @@
 // float64 point, d2 = ((dx*dx + dy*dy) + dz*dz) in fp64 without contraction, a candidate is a member when d2 <= r*r
 // (inclusive).  There is no ranking, so there is no running list: a pass over a query's candidates is a ballot per 64.
 //
-//   stage 1  pct_query_stage1 (pct_query_items.h, shared with pct_query.hip): the queries' cells, their order by cell,
-//            work items of <= kItemQ queries of one cell.
+//   stage 1  pct_query_stage1 (pct_query_items.h, shared with pct_query.hip, as are the item decode and the launch
+//            geometry below): the queries' cells, their order by cell, work items of <= kItemQ queries of one cell.
 //   count    k_ball_count: one wave = one work item.  Every query's cube half-width is ball_ring (pct_ball_plan.h).  Where
 //            the cube of the item's largest ring has at most 64 (y, z) rows (ring <= kBallStageRing) and at most kBallCap
 //            candidates it is staged into LDS once for all queries of the item; otherwise every query streams its own
@@ -107,11 +107,8 @@ __device__ __forceinline__ void ball_items(const BallArgs& a, float4* __restrict
     row.dist = a.dist;
 
     for (int item = (int)blockIdx.x * kWavesPerBlock + w; item < total; item += nwaves) {
-        const int4 it = a.items[item];
-        const int cell = __builtin_amdgcn_readfirstlane(it.x);
-        const int qs = __builtin_amdgcn_readfirstlane(it.y);
-        const int nq = __builtin_amdgcn_readfirstlane(it.z);
-        const int cx = cell % g.nx, cy = (cell / g.nx) % g.ny, cz = cell / (g.nx * g.ny);
+        const QueryItem it = query_item(a.items, item, g);
+        const int qs = it.qs, nq = it.nq, cx = it.cx, cy = it.cy, cz = it.cz;
         // lane j < nq: the j-th query of the item, its r*r and its ring
         int my_ring = -1;
         double my_r2 = 0.0;
@@ -119,9 +116,9 @@ __device__ __forceinline__ void ball_items(const BallArgs& a, float4* __restrict
             const int64_t qi = (int64_t)a.q_sorted[qs + lane];
             const double r = a.r[qi * a.r_stride];
             my_r2 = r * r;
-            const double gx = (a.q[3 * qi] - g.ox) * g.inv_cell - cx;
-            const double gy = (a.q[3 * qi + 1] - g.oy) * g.inv_cell - cy;
-            const double gz = (a.q[3 * qi + 2] - g.oz) * g.inv_cell - cz;
+            const double gx = query_cell_offset(a.q[3 * qi], g.ox, g.inv_cell, cx);
+            const double gy = query_cell_offset(a.q[3 * qi + 1], g.oy, g.inv_cell, cy);
+            const double gz = query_cell_offset(a.q[3 * qi + 2], g.oz, g.inv_cell, cz);
             my_ring = ball_ring(g.nx, g.ny, g.nz, g.cell, cx, cy, cz, gx, gy, gz, my_r2);
         }
         int ring_item = my_ring;
@@ -348,8 +345,7 @@ int pct_launch_ball(pct_ctx* ctx, bool grid, const double* d_q, int64_t m, const
     PCT_HIP(ctx, hipMemsetAsync(a.stat, 0, sizeof(BallWords), ctx->stream));
     PCT_HIP(ctx, hipMemsetAsync(a.counts + m, 0, sizeof(int64_t), ctx->stream));
 
-    const int64_t want = (m + kWavesPerBlock - 1) / kWavesPerBlock;
-    const dim3 block(64 * kWavesPerBlock), blocks((unsigned)(want < 16384 ? want : 16384));
+    const dim3 block(64 * kWavesPerBlock), blocks(query_blocks(m));
     if (grid) PCT_LAUNCH(k_ball_count, blocks, block, 0, ctx->stream, a);
     else PCT_LAUNCH(k_ball_count_all, blocks, block, 0, ctx->stream, a);
     PCT_HIP(ctx, hipGetLastError());

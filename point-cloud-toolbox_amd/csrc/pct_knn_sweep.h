@@ -5,6 +5,7 @@
 // translation unit of its own so that the hot kernels' file does not pay their compile time.
 #pragma once
 #include "pct_internal.h"
+#include "pct_query_plan.h"
 #include "pct_sweep_plan.h"
 
 #include <math.h>
@@ -392,20 +393,10 @@ struct ShellIter {
     }
 };
 
-// squared radius (cell units folded in) inside which the cube of radius `ring`
-// around the query's cell is known to contain every point; +inf once the cube
-// covers the grid.  gx,gy,gz = position of the query inside its cell in cell units.
+// squared radius inside which the cube of radius `ring` around the query's cell is known to contain every point: the one
+// expression of pct_query_plan.h, which tests/test_query_plan.py checks against brute force
 __device__ __forceinline__ double guaranteed_r2(const pct_grid& g, int cx, int cy, int cz, double gx, double gy, double gz, int ring) {
-    const double inf = INFINITY;
-    double gmin = inf;
-    gmin = fmin(gmin, cx - ring <= 0 ? inf : gx + ring);
-    gmin = fmin(gmin, cx + ring >= g.nx - 1 ? inf : (1.0 - gx) + ring);
-    gmin = fmin(gmin, cy - ring <= 0 ? inf : gy + ring);
-    gmin = fmin(gmin, cy + ring >= g.ny - 1 ? inf : (1.0 - gy) + ring);
-    gmin = fmin(gmin, cz - ring <= 0 ? inf : gz + ring);
-    gmin = fmin(gmin, cz + ring >= g.nz - 1 ? inf : (1.0 - gz) + ring);
-    const double rr = gmin * g.cell * (1.0 - 1e-6);
-    return rr * rr;
+    return query_guaranteed_r2(g.nx, g.ny, g.nz, g.cell, cx, cy, cz, gx, gy, gz, ring);
 }
 
 // Squared distance from the query to the nearest face beyond which points were left out of the grid

@@ -7,8 +7,9 @@
 // strict, padding is index n and +inf.  Every comparison is on exact fp64 keys (Sweep<R>, pct_knn_sweep.h): no float32
 // pre-selection here.
 //
-//   stage 1  pct_query_stage1 (pct_query_items.h, shared with pct_ball.hip): the cell of every query, the query indices
-//            sorted by cell, work items {cell, first sorted query, <= kItemQ queries}.
+//   stage 1  pct_query_stage1 (pct_query_items.h, shared with pct_ball.hip, as are the item decode and the launch
+//            geometry below): the cell of every query, the query indices sorted by cell, work items {cell, first
+//            sorted query, <= kItemQ queries}.
 //   stage 2  k_query_cells: one wave = one work item.  The item's 27-cell stencil is staged into LDS once (16-byte
 //            records {x, y, z, sorted position}, PCT_STAGE_CAP2 of them per wave), Sweep<R> runs over the staged
 //            candidates for each query of the item; a row is stored only if the 27 cells vouch for it
@@ -77,11 +78,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_query_cells(QueryArgs a
     sw.pend_p = s_pend_p[w];
 
     for (int item = (int)blockIdx.x * kWavesPerBlock + w; item < total; item += nwaves) {
-        const int4 it = a.items[item];
-        const int cell = __builtin_amdgcn_readfirstlane(it.x);
-        const int qs = __builtin_amdgcn_readfirstlane(it.y);
-        const int nq = __builtin_amdgcn_readfirstlane(it.z);
-        const int cx = cell % g.nx, cy = (cell / g.nx) % g.ny, cz = cell / (g.nx * g.ny);
+        const QueryItem it = query_item(a.items, item, g);
+        const int qs = it.qs, nq = it.nq, cx = it.cx, cy = it.cy, cz = it.cz;
         // bounds of the 9 x-runs of the 27-cell stencil, lanes 0..8 (centre row first); at the rim of the grid a run
         // is clamped to the row, rows outside the grid stay empty
         int run_s = 0, run_len = 0;
@@ -139,9 +137,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_query_cells(QueryArgs a
                 if (sw.npend > 0 || sw.empty) sw.flush();
                 if (!have) break;
             }
-            const double gx = (sw.qx - g.ox) * g.inv_cell - cx;
-            const double gy = (sw.qy - g.oy) * g.inv_cell - cy;
-            const double gz = (sw.qz - g.oz) * g.inv_cell - cz;
+            const double gx = query_cell_offset(sw.qx, g.ox, g.inv_cell, cx);
+            const double gy = query_cell_offset(sw.qy, g.oy, g.inv_cell, cy);
+            const double gz = query_cell_offset(sw.qz, g.oz, g.inv_cell, cz);
             if (fmin(sw.tau_d, sw.eps2) <= query_guaranteed_r2(g.nx, g.ny, g.nz, g.cell, cx, cy, cz, gx, gy, gz, 1)) {
                 store_query_row<R>(sw, a, qi, lane);
             } else {
@@ -187,9 +185,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_query_exact(QueryArgs a
         const int cy = __builtin_amdgcn_readfirstlane(query_cell_coord(sw.qy, g.oy, g.inv_cell, g.ny));
         const int cz = __builtin_amdgcn_readfirstlane(query_cell_coord(sw.qz, g.oz, g.inv_cell, g.nz));
         sw.reset();
-        const double gx = (sw.qx - g.ox) * g.inv_cell - cx;
-        const double gy = (sw.qy - g.oy) * g.inv_cell - cy;
-        const double gz = (sw.qz - g.oz) * g.inv_cell - cz;
+        const double gx = query_cell_offset(sw.qx, g.ox, g.inv_cell, cx);
+        const double gy = query_cell_offset(sw.qy, g.oy, g.inv_cell, cy);
+        const double gz = query_cell_offset(sw.qz, g.oz, g.inv_cell, cz);
         const bool inside = query_inside_cell(gx) && query_inside_cell(gy) && query_inside_cell(gz);
         ShellIter sh;
         sh.start(g, cy, cz, -1, 1);
@@ -254,9 +252,7 @@ int pct_launch_query_grid(pct_ctx* ctx, const double* d_q, int64_t m, int32_t k,
     a.idx_out = d_idx;
     a.dist_out = d_dist;
     // device-side counts, fixed grids: at most m items / m redone queries, one per wave
-    const int64_t want = (m + kWavesPerBlock - 1) / kWavesPerBlock;
-    const dim3 block(64 * kWavesPerBlock);
-    const dim3 cells_grid((unsigned)(want < 16384 ? want : 16384)), exact_grid((unsigned)(want < 8192 ? want : 8192));
+    const dim3 block(64 * kWavesPerBlock), cells_grid(query_blocks(m)), exact_grid(query_blocks(m, 8192));
     if (k <= 64) {
         PCT_LAUNCH(k_query_cells<1>, cells_grid, block, 0, ctx->stream, a);
         PCT_LAUNCH(k_query_exact<1>, exact_grid, block, 0, ctx->stream, a);

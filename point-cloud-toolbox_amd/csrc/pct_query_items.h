@@ -1,8 +1,16 @@
-// Stage 1 of every query of caller-supplied points through the uniform cell list (pct_query.hip: k nearest;
-// pct_ball.hip: radius search): the cell of every query (query_cell_coord, pct_query_plan.h), the query indices sorted
-// by cell, work items {cell, first sorted query, <= kItemQ queries}.
-// (The sort is the library's, as in pct_tree.hip, not a histogram over the cells: m is the small side, the grid may hold
-// 2^27 cells, and no pass here is sized by the grid.)
+// What every query of caller-supplied points through the uniform cell list shares (pct_query.hip: k nearest;
+// pct_ball.hip: radius search), kept in this header so that no other translation unit's code depends on it:
+//   stage 1       pct_query_stage1: the cell of every query (query_cell_coord, pct_query_plan.h), the query indices sorted
+//                 by cell, work items {cell, first sorted query, <= kItemQ queries}.
+//                 (The sort is the library's, as in pct_tree.hip, not a histogram over the cells: m is the small side,
+//                 the grid may hold 2^27 cells, and no pass here is sized by the grid.)
+//   query_item    a work item decoded: its cell, its queries, the cell's coordinates.
+//   query_blocks  the launch geometry of the kernels that give one wave to one item (or one query).
+// The LDS staging of the two files stays apart: k_query_cells stages nine runs nearest-first, so that tau tightens early,
+// and rewrites .w to the sorted position; ball_items stages up to 49 rows in grid order and keeps the public index -- one
+// routine for both would branch on its caller.  The prefetching cube walk (ShellIter's steps, each issued one step ahead
+// of its use) is written out in k_query_exact and in ball_items as it is in k_knn_exact: a shared cursor over ShellIter was
+// measured and cost k_query_exact 7 % of the whole call at n = m = 65 536 (tools/query_probe.py gain).
 #pragma once
 
 #include "pct_knn_sweep.h"
@@ -60,6 +68,24 @@ __global__ __launch_bounds__(256) void k_query_items(const unsigned* __restrict_
         const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
         items[base + rank] = make_int4((int)key, (int)i, nq, 0);         // at most m items: one per query
     }
+}
+
+struct QueryItem { int cell, qs, nq, cx, cy, cz; };   // wave-uniform: the cell, the first position in q_sorted, the queries
+
+__device__ __forceinline__ QueryItem query_item(const int4* __restrict__ items, int item, const pct_grid& g) {
+    const int4 it = items[item];
+    QueryItem qi;
+    qi.cell = __builtin_amdgcn_readfirstlane(it.x);
+    qi.qs = __builtin_amdgcn_readfirstlane(it.y);
+    qi.nq = __builtin_amdgcn_readfirstlane(it.z);
+    qi.cx = qi.cell % g.nx; qi.cy = (qi.cell / g.nx) % g.ny; qi.cz = qi.cell / (g.nx * g.ny);
+    return qi;
+}
+
+// one wave per item, kWavesPerBlock of them per block; the kernels stride over what the grid does not cover
+unsigned query_blocks(int64_t m, int64_t most = 16384) {
+    const int64_t want = (m + kWavesPerBlock - 1) / kWavesPerBlock;
+    return (unsigned)(want < most ? want : most);
 }
 
 size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }

@@ -1,8 +1,9 @@
-// The pure rules of pct_query_points_algo (pct_api.hip, pct_query.hip): which path answers a set of caller-supplied
-// query points, the cell a query is filed in, and the radius a searched cube of cells vouches for around a query that
-// may lie outside the grid box.  Nothing here knows a handle, a device or the environment; the cell and the radius are
-// also what the kernels evaluate (QP_HD) -- tests/test_query_plan.py compiles this header alone with the host compiler
-// and checks the radius against brute force.
+// The pure rules of the queries of caller-supplied points (pct_api.hip, pct_query.hip, pct_ball.hip): which path answers a
+// set of query points, the cell a query is filed in, its position inside that cell, and the radius a searched cube of
+// cells vouches for.  That radius is the guarantee of EVERY sweep over the cell list: guaranteed_r2 (pct_knn_sweep.h)
+// forwards here, for the cloud's own points as for a caller's, which may lie outside the grid box.  Nothing here knows a
+// handle, a device or the environment; the cell, the position and the radius are what the kernels evaluate (QP_HD) --
+// tests/test_query_plan.py compiles this header alone with the host compiler and checks the radius against brute force.
 #pragma once
 
 #include <math.h>
@@ -69,24 +70,27 @@ QP_HD inline int query_cell_coord(double x, double o, double inv, int n) {
     return (int)c;
 }
 
+// the query's position relative to the low corner of its cell c, in cell units
+QP_HD inline double query_cell_offset(double x, double o, double inv, int c) { return (x - o) * inv - c; }
+
 // a query inside the grid box has every in-cell offset in [0, 1); a clamped one (or an overflowed offset) has not
 QP_HD inline bool query_inside_cell(double g) { return g >= 0.0 && g < 1.0; }
 
 // ---- the radius a searched cube vouches for ------------------------------------------------------------------------------
 // The cube of cells within Chebyshev distance `ring` of the query's cell (cx, cy, cz), clipped to the grid, has been
-// searched.  gx, gy, gz: the query's position relative to the low corner of its cell, in cell units -- in [0, 1) for a
-// query inside the grid box; below 0 (cell 0) or at and above 1 (cell n - 1) for a query clamped into a boundary cell.
+// searched.  gx, gy, gz: query_cell_offset per axis -- in [0, 1) for a query inside the grid box (every point of the cloud
+// is one); below 0 (cell 0) or at and above 1 (cell n - 1) for a query clamped into a boundary cell.
 // Returns a lower bound, in cell units, on the distance from the query to any point filed in a cell OUTSIDE the cube;
 // +inf when the cube covers the grid.
 //
-// Why guaranteed_r2's expression (pct_knn_sweep.h) holds for a clamped query as it stands.  A point outside the cube is
-// outside it along some axis, say x, on one side.  High side: its cell index is > cx + ring, so its coordinate is at least
-// that cell's low face, cx + ring + 1 (points clamped into the last cell lie beyond its outer face: farther still);
-// the query sits at cx + gx, the gap is ring + 1 - gx for ANY gx, and it only grows for gx < 0.  Low side: the point lies
-// below the face cx - ring, the gap is gx + ring for any gx, growing for gx >= 1.  A term could only turn small or
-// negative for gx < -ring on the low side or gx > ring + 1 on the high side -- but gx < 0 happens in cell 0 alone, where
-// the low side is open (cx - ring <= 0: no cell beyond, the term is +inf), and gx >= 1 in cell n - 1 alone, where the
-// high side is open.  So every finite term is >= ring > 0 and is a true gap; the smallest one bounds the distance.
+// Why it holds, a clamped query included.  A point outside the cube is outside it along some axis, say x, on one side.
+// High side: its cell index is > cx + ring, so its coordinate is at least that cell's low face, cx + ring + 1 (points
+// clamped into the last cell lie beyond its outer face: farther still); the query sits at cx + gx, the gap is
+// ring + 1 - gx for ANY gx, and it only grows for gx < 0.  Low side: the point lies below the face cx - ring, the gap is
+// gx + ring for any gx, growing for gx >= 1.  A term could only turn small or negative for gx < -ring on the low side or
+// gx > ring + 1 on the high side -- but gx < 0 happens in cell 0 alone, where the low side is open (cx - ring <= 0: no
+// cell beyond, the term is +inf), and gx >= 1 in cell n - 1 alone, where the high side is open.  So every finite term is
+// >= ring > 0 and is a true gap; the smallest one bounds the distance.
 // An overflowing gx (+-inf for a query at 1e300 over a tiny cell) gives +inf terms, never a NaN: inf is only added to.
 QP_HD inline double query_guarantee_cells(int nx, int ny, int nz, int cx, int cy, int cz, double gx, double gy, double gz, int ring) {
     const double inf = INFINITY;
@@ -99,7 +103,7 @@ QP_HD inline double query_guarantee_cells(int nx, int ny, int nz, int cx, int cy
     gmin = fmin(gmin, cz + ring >= nz - 1 ? inf : (1.0 - gz) + ring);
     return gmin;
 }
-// ... squared, in the cloud's units, shrunk by 1e-6 as guaranteed_r2 is (the cell coordinates are rounded twice)
+// ... squared, in the cloud's units, shrunk by 1e-6 (the cell coordinates are rounded twice)
 QP_HD inline double query_guaranteed_r2(int nx, int ny, int nz, double cell, int cx, int cy, int cz, double gx, double gy, double gz, int ring) {
     const double rr = query_guarantee_cells(nx, ny, nz, cx, cy, cz, gx, gy, gz, ring) * cell * (1.0 - 1e-6);
     return rr * rr;

@@ -63,6 +63,14 @@ def _matrix_norms(points):
     return p.dtype.type(l1), p.dtype.type(l2), linf
 
 
+def _vectors3(x):
+    """SciPy's check of the points handed to a tree: float64, the last axis of length 3."""
+    x = np.asarray(x, dtype=np.float64)
+    if x.shape[-1:] != (3,):
+        raise ValueError(f"x must consist of vectors of length 3 but has shape {x.shape}")
+    return x
+
+
 class _DeviceTree:
     """``self.kdtree`` of the reference (SciPy's k-d tree of the float32 cloud, pct:74) as far as its callers use it
     (pct:625, 759, 844): ``query(x, k)`` for arbitrary points, answered on the device (``pct_query_points_algo`` with
@@ -84,9 +92,7 @@ class _DeviceTree:
     def query(self, x, k=1, eps=0, p=2, distance_upper_bound=np.inf, workers=1):
         if eps != 0 or p != 2:
             raise NotImplementedError("only exact Euclidean queries (eps=0, p=2) run on the device")
-        x = np.asarray(x, dtype=np.float64)
-        if x.shape[-1:] != (3,):
-            raise ValueError(f"x must consist of vectors of length 3 but has shape {x.shape}")
+        x = _vectors3(x)
         if not isinstance(k, (int, np.integer)) or k < 1:
             raise ValueError("k must be an integer >= 1")
         flat = x.reshape(-1, 3)
@@ -121,9 +127,7 @@ class _DeviceTree:
         return (offsets, idx, dist) if distances else (offsets, idx)
 
     def _ball_arguments(self, x, r):
-        x = np.asarray(x, dtype=np.float64)
-        if x.shape[-1:] != (3,):
-            raise ValueError(f"x must consist of vectors of length 3 but has shape {x.shape}")
+        x = _vectors3(x)
         if not np.isfinite(x).all():
             raise ValueError("'x' must be finite, check for nan or inf values")
         radii = np.empty(x.shape[:-1], np.float64)

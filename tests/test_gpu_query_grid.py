@@ -248,6 +248,22 @@ def test_resident_table_and_fit_are_untouched(bench, planted):
     assert _same(before, _snapshot(h, len(pts)))
 
 
+def test_plain_entry_leaves_the_stats_alone(bench):
+    """pct_query_points shares its body with pct_query_points_algo: it still answers from the sweep, builds nothing and
+    leaves query_stats those of the last pct_query_points_algo call."""
+    h, capi = bench["h"], bench["capi"]
+    pts, q = bench["cloud"]("lattice"), np.ascontiguousarray(we.lattice_queries()[38:43])
+    h.set_points(pts)
+    _check(bench, pts, q, 5, route=BUILD, where="before the plain entry")
+    before = h.query_stats()
+    lib = capi.load()
+    idx = np.empty((len(q), 5), np.int32)
+    dist = np.empty((len(q), 5), np.float64)
+    h._check(lib.pct_query_points(h._h, capi._ptr(q, capi._f64p), len(q), 5, 0.0, capi._ptr(idx, capi._i32p), capi._ptr(dist, capi._f64p)))
+    _assert_rows((idx, dist), we.rows(pts, 5, queries=q)[:2], "plain entry")
+    assert h.query_stats() == before
+
+
 def test_curvature_after_a_grid_query_equals_a_fresh_handle(bench):
     h, capi = bench["h"], bench["capi"]
     pts = bench["cloud"]("torus")

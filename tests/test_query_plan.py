@@ -8,7 +8,8 @@ second -- compiled with -fsanitize=undefined, so that a conversion of an out-of-
 cells of queries at, inside and outside every face and up to +-1e300, and checks the radius against brute force: with
 every cell outside the searched cube filled with its nearest possible point (a boundary cell holds the points clamped
 into it: it reaches to infinity on its outer side), the true minimum distance to an excluded point is never below what
-the header vouches for."""
+the header vouches for.  guaranteed_r2 (csrc/pct_knn_sweep.h) forwards to that one expression, so this pins the
+guarantee of every sweep over the cell list, the cloud's own included."""
 import os
 import shutil
 import subprocess
