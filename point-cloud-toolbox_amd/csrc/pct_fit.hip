@@ -9,7 +9,7 @@
 // workgroup stages its 64 neighbour-index rows into LDS with coalesced loads
 // (odd row pitch -> conflict-free column reads; letting every lane stream its
 // own row from global instead was measured 2x slower), then every lane walks
-// its own row twice, gathers issued eight neighbours ahead of their use:
+// its own row twice, gathers issued kFitAhead neighbours ahead of their use:
 //   pass 1  centred neighbours (native dtype, pct:641) -> fp64 sums about the
 //           first neighbour -> 3x3 covariance, ddof=1 (pct:277) -> normal =
 //           eigenvector of the smallest eigenvalue (== Vt[-1], pct:283;
@@ -29,6 +29,17 @@
 namespace {
 
 constexpr int kFitBlock = 64;
+
+// Gathers a lane issues together in the two neighbour loops, before it uses the first of them: a lane waits out one
+// memory latency per group and one per neighbour behind the last full group.  Measured on the 1 M-point torus and on
+// C4 / C5 (profiles/r06_a_fit_keep_ab.txt): 10 beats 8 at k = 30, 45, 50, 64, 80 and 100 (k_fit 179 against 185 us at
+// k = 50); 12 (162 registers) and 16 (186, two waves per SIMD) lose, and so does every way tried of grouping the
+// neighbours behind the last full group, which moves the register allocation of the loops themselves.
+// -DPCT_FIT_AHEAD=<n> on this file: a developer's A/B build (tools/build_variant.py).
+#ifndef PCT_FIT_AHEAD
+#define PCT_FIT_AHEAD 10
+#endif
+constexpr int kFitAhead = PCT_FIT_AHEAD;
 
 struct FitArgs {
     const float4* pts;       // records {x,y,z,public index}
@@ -63,6 +74,8 @@ struct FitArgs {
     int force_jacobi;        // PCT_FIT_JACOBI=1: every row's normal through the cyclic Jacobi (A/B runs, route-against-route tests)
     int blocks_per_xcd;      // blocks are dealt to the 8 XCDs in turn: block b takes rows of block (b % 8) * blocks_per_xcd + b / 8, so
                              // that one XCD's L2 serves neighbouring rows (table rows are in cell order: their neighbours overlap)
+    int keep;                // the KEEP of the instantiation the launch takes (fit_keep_depth(): PCT_FIT_KEEP=<depth>, A/B runs and
+                             // depth-against-depth tests); the kernels do not read it
 };
 
 // Smallest Cholesky pivot ratio d_j / g_jj (= sin^2 of the angle between design column j and the span of the columns
@@ -260,8 +273,12 @@ __device__ __forceinline__ void plane_rotation(int m, double sx, double sy, doub
 // get here: the resident one of the wide sweeps (k = 256 .. 511: sorted-space positions, the table's pitch, float64
 // clouds, eps counts) and caller-supplied rows (pct_fit_indices takes any k the reference's fit would).
 // MASKED: a compile-time variant, so that the row test leaves the hot instantiation's register allocation alone.
-template <bool F64, bool OUT64 = false, bool STAGED = true, bool MASKED = false>
+// KEEP: the centred float32 coordinates of a row's first min(m, KEEP) neighbours stay in registers from pass 1 to pass 2,
+// which then gathers only the neighbours behind them (float32 clouds; 3 registers per kept neighbour).  Where an
+// operand comes from is all that changes: every operation and its order are those of KEEP = 0, and so is every bit.
+template <bool F64, bool OUT64 = false, bool STAGED = true, bool MASKED = false, int KEEP = 0>
 __global__ __launch_bounds__(kFitBlock) void k_fit(FitArgs a) {
+    static_assert(KEEP == 0 || !F64, "the stash holds float32 coordinates");
     extern __shared__ int s_idx[];   // 64 rows x kp
     const int lane = threadIdx.x;
     if (blockIdx.x == 0) {
@@ -277,18 +294,26 @@ __global__ __launch_bounds__(kFitBlock) void k_fit(FitArgs a) {
     const int nrow = (int)min((int64_t)kFitBlock, a.rows - row0);
     if constexpr (STAGED) {
         const int sub = lane >> 4, c4 = (lane & 15) << 2;
+        // Every load of a 64-column chunk is issued before the first store: a lane outside the tile reads the tile's
+        // last row or the row's last int4 instead (inside the table, never stored), so no load sits behind a branch --
+        // with the loads under the row and column tests each one was waited for before the next was issued, sixteen
+        // memory latencies in a row per block.
         for (int cb = 0; cb < k; cb += 64) {
             const int c = cb + c4;
-#pragma unroll 4
-            for (int r0 = 0; r0 < kFitBlock; r0 += 4) {
-                const int r = r0 + sub;
+            const int cl = min(c, a.pitch - 4);
+            int4 v[kFitBlock / 4];
+#pragma unroll
+            for (int i = 0; i < kFitBlock / 4; ++i)
+                v[i] = *(const int4*)(a.table + (row0 + min(i * 4 + sub, nrow - 1)) * a.pitch + cl);
+#pragma unroll
+            for (int i = 0; i < kFitBlock / 4; ++i) {
+                const int r = i * 4 + sub;
                 if (r < nrow && c < a.pitch) {
-                    const int4 v = *(const int4*)(a.table + (row0 + r) * a.pitch + c);
                     int* dst = s_idx + r * kp + c;
-                    if (c + 0 < k) dst[0] = v.x;
-                    if (c + 1 < k) dst[1] = v.y;
-                    if (c + 2 < k) dst[2] = v.z;
-                    if (c + 3 < k) dst[3] = v.w;
+                    if (c + 0 < k) dst[0] = v[i].x;
+                    if (c + 1 < k) dst[1] = v[i].y;
+                    if (c + 2 < k) dst[2] = v[i].z;
+                    if (c + 3 < k) dst[3] = v[i].w;
                 }
             }
         }
@@ -339,7 +364,7 @@ __global__ __launch_bounds__(kFitBlock) void k_fit(FitArgs a) {
     // ---- pass 1: moments of the centred neighbourhood ---------------------
     double sx = 0, sy = 0, sz = 0, sxx = 0, sxy = 0, sxz = 0, syy = 0, syz = 0, szz = 0;
     double fx = 0, fy = 0, fz = 0, lx = 0, ly = 0, lz = 0;
-    // gathers are issued four neighbours ahead of their use (the row walk is latency-bound otherwise)
+    // gathers are issued kFitAhead neighbours ahead of their use (the row walk is latency-bound otherwise)
     // The moments are taken about the FIRST neighbour, not about the query: the covariance does not care, and a query far
     // from its neighbourhood (caller-supplied rows with a foreign query, far outliers) no longer costs sxx - sx * mx its
     // digits -- about the query, 1 000 neighbourhood radii away, the rotation moved by 1e-10, enough to round the
@@ -359,16 +384,47 @@ __global__ __launch_bounds__(kFitBlock) void k_fit(FitArgs a) {
         bad_id |= (unsigned)id >= a.n_pts;
         return (int)min((unsigned)id, a.n_pts - 1u);
     };
+    float kx[KEEP ? KEEP : 1], ky[KEEP ? KEEP : 1], kz[KEEP ? KEEP : 1];      // the stash: statically indexed, so registers
     {
         int j = 0;
-        for (; j + 8 <= m; j += 8) {
-            double x[8], y[8], z[8];
+        if constexpr (KEEP > 0) {
+            // the kept prefix, unrolled in groups of eight gathers.  A group the row ends in loads its last neighbour
+            // again in the places behind it (the same record: no index read past the row) and accumulates up to m.
 #pragma unroll
-            for (int u = 0; u < 8; ++u) load_centred<F64>(a, checked(my[j + u]), qx, qy, qz, qp.x, qp.y, qp.z, x[u], y[u], z[u]);
+            for (int g = 0; g < KEEP; g += 8) {
+                if (g < m) {
+#pragma unroll
+                    for (int t = 0; t < 8; ++t) {
+                        const int u = g + t;
+                        if (u < KEEP) {
+                            const float4 p = a.pts[checked(my[min(u, m - 1)])];
+                            kx[u] = p.x - qp.x; ky[u] = p.y - qp.y; kz[u] = p.z - qp.z;       // as load_centred
+                        }
+                    }
+                    if (g == 0) { fx = (double)kx[0]; fy = (double)ky[0]; fz = (double)kz[0]; }
+#pragma unroll
+                    for (int t = 0; t < 8; ++t) {
+                        const int u = g + t;
+                        if (u < KEEP) {
+                            if (u < m) {
+                                const double x = (double)kx[u], y = (double)ky[u], z = (double)kz[u];
+                                PASS1_ACC(x, y, z);
+                                lx = x; ly = y; lz = z;
+                            }
+                        }
+                    }
+                }
+            }
+            j = min(m, KEEP);
+        }
+        for (; j + kFitAhead <= m; j += kFitAhead) {
+            double x[kFitAhead], y[kFitAhead], z[kFitAhead];
+#pragma unroll
+            for (int u = 0; u < kFitAhead; ++u) load_centred<F64>(a, checked(my[j + u]), qx, qy, qz, qp.x, qp.y, qp.z, x[u], y[u], z[u]);
             if (j == 0) { fx = x[0]; fy = y[0]; fz = z[0]; }
 #pragma unroll
-            for (int u = 0; u < 8; ++u) PASS1_ACC(x[u], y[u], z[u]);
-            lx = x[7]; ly = y[7]; lz = z[7];
+            for (int u = 0; u < kFitAhead; ++u) PASS1_ACC(x[u], y[u], z[u]);
+            lx = x[kFitAhead - 1]; ly = y[kFitAhead - 1]; lz = z[kFitAhead - 1];
         }
         for (; j < m; ++j) {
             double x, y, z;
@@ -424,12 +480,22 @@ __global__ __launch_bounds__(kFitBlock) void k_fit(FitArgs a) {
     } while (0)
     {
         int j = 0;
-        for (; j + 8 <= m; j += 8) {
-            double x[8], y[8], z[8];
+        if constexpr (KEEP > 0) {
 #pragma unroll
-            for (int u = 0; u < 8; ++u) load_centred<F64>(a, my[j + u], qx, qy, qz, qp.x, qp.y, qp.z, x[u], y[u], z[u]);
+            for (int u = 0; u < KEEP; ++u) {
+                if (u < m) {
+                    const double x = (double)kx[u], y = (double)ky[u], z = (double)kz[u];
+                    PASS2_ACC(x, y, z);
+                }
+            }
+            j = min(m, KEEP);
+        }
+        for (; j + kFitAhead <= m; j += kFitAhead) {
+            double x[kFitAhead], y[kFitAhead], z[kFitAhead];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) PASS2_ACC(x[u], y[u], z[u]);
+            for (int u = 0; u < kFitAhead; ++u) load_centred<F64>(a, my[j + u], qx, qy, qz, qp.x, qp.y, qp.z, x[u], y[u], z[u]);
+#pragma unroll
+            for (int u = 0; u < kFitAhead; ++u) PASS2_ACC(x[u], y[u], z[u]);
         }
         for (; j < m; ++j) {
             double x, y, z;
@@ -804,6 +870,26 @@ int fit_jacobi_forced() {
     return e && e[0] == '1' ? 1 : 0;
 }
 
+// The stash depths k_fit<false, false, true, false, KEEP> is built at, ascending (registers and time of each).
+// The default is the depth with the lowest median step time on the bench shape, and that is none: every depth measured
+// slower than 0 (profiles/r06_a_fit_keep_ab.txt) -- the kernel waits for memory, and fewer gathers do not shorten a wait.
+constexpr int kFitKeepBuilt[] = {8, 10, 16, 25, 50};
+constexpr int kFitKeepDefault = 0;
+
+// The KEEP a launch takes.  Only the headline instantiation (float32 cloud, float32 results, rows staged in LDS, no row
+// mask) is built with a stash; every other launch keeps nothing.  PCT_FIT_KEEP=<depth> (read per call) asks for the
+// largest built depth not above <depth>, whatever the row length: A/B runs, depth-against-depth tests.
+int fit_keep_depth(const FitArgs& a, bool f64, bool staged) {
+    if (f64 || a.coefs64 || a.row_mask || !staged) return 0;
+    int want = kFitKeepDefault;
+    const char* e = pct_getenv("PCT_FIT_KEEP");
+    if (e && e[0] >= '0' && e[0] <= '9') want = atoi(e);
+    int depth = 0;
+    for (const int d : kFitKeepBuilt)
+        if (d <= want) depth = d;
+    return depth;
+}
+
 // slot: the pinned slots of the call (FitSlot); *mirrored (may be null): the fit kernel mirrors the statistics words
 int launch(pct_ctx* ctx, const FitArgs& a0, bool f64, FitSlot slot, bool* mirrored) {
     FitArgs a = a0;
@@ -817,6 +903,7 @@ int launch(pct_ctx* ctx, const FitArgs& a0, bool f64, FitSlot slot, bool* mirror
     if (blocks <= 0) return PCT_OK;
     a.blocks_per_xcd = pct_getenv("PCT_NO_XCD_MAP") ? 0 : (blocks + 7) / 8;
     a.force_jacobi = fit_jacobi_forced();
+    a.keep = fit_keep_depth(a, f64, staged);
     if (a.blocks_per_xcd) blocks = a.blocks_per_xcd * 8;
     // rows for k_fit_svd: list + its length (first word of the buffer's 64-byte head)
     // two counts used in turn: a launch counts in one and clears the other for the launch after it (both cleared once per
@@ -845,11 +932,23 @@ int launch(pct_ctx* ctx, const FitArgs& a0, bool f64, FitSlot slot, bool* mirror
         else if (staged) PCT_LAUNCH((k_fit<F_, O_, true>), dim3(blocks), dim3(kFitBlock), lds, ctx->stream, a);  \
         else PCT_LAUNCH((k_fit<F_, O_, false>), dim3(blocks), dim3(kFitBlock), 0, ctx->stream, a);          \
     } while (0)
-    if (a.coefs64) {
+#define PCT_FIT_LAUNCH_KEEP(D_) \
+    case D_: PCT_LAUNCH((k_fit<false, false, true, false, D_>), dim3(blocks), dim3(kFitBlock), lds, ctx->stream, a); break
+    if (a.keep) {
+        switch (a.keep) {
+            PCT_FIT_LAUNCH_KEEP(8);
+            PCT_FIT_LAUNCH_KEEP(10);
+            PCT_FIT_LAUNCH_KEEP(16);
+            PCT_FIT_LAUNCH_KEEP(25);
+            PCT_FIT_LAUNCH_KEEP(50);
+            default: return pct_fail(ctx, PCT_ERR_INVALID, "fit: no kernel keeps %d neighbours", a.keep);
+        }
+    } else if (a.coefs64) {
         if (f64) PCT_FIT_LAUNCH(true, true);
         else PCT_FIT_LAUNCH(false, true);
     } else if (f64) PCT_FIT_LAUNCH(true, false);
     else PCT_FIT_LAUNCH(false, false);
+#undef PCT_FIT_LAUNCH_KEEP
 #undef PCT_FIT_LAUNCH
     PCT_HIP(ctx, hipGetLastError());
     // the rows handed over: fixed grid, the list length is read on the device
