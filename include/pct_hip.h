@@ -254,6 +254,33 @@ int pct_get_ball(pct_ctx* ctx, int64_t row_begin, int64_t row_end, int32_t* idx,
  * Zeros behind the route after the exhaustive path. */
 int pct_ball_stats(pct_ctx* ctx, int64_t out[4]);
 
+/* Curvature over radius neighbourhoods: the quadric fit (pct:635-647, 657-674) of the m resident rows of the last
+ * pct_query_ball, row i about the cloud point c = self_rows[i] (a public index in [0, n)) -- "every point within r", at any
+ * row length, where pct_fit / pct_fit_indices take a rectangular table of at most 511 neighbours.
+ * Members of row i: its entries e != c.  Only the centre's own index is skipped: a coinciding twin of the centre is a
+ * member.  An entry outside [0, n) is never dereferenced; the row reads NaN.
+ * Key: key(e) = (d2(e), e) with d2 = (dx*dx + dy*dy) + dz*dz in float64, three separate operations, nothing fused, dx = the
+ * float32-rounded record of e widened to float64 minus the centre's coordinate -- native float64 for float64 clouds, else
+ * the float32 value widened: pct_query_ball's expression with the centre as the query.  near / far = the member with the
+ * smallest / largest key.
+ * Result: get_best_fit_plane_and_rotate, fit_quadratic_surface and calculate_explicit_quadratic_curvatures (pct:270-321,
+ * 331-360, 398-431) applied to the block points[ranked] - points[c], centred in the cloud's native dtype (pct:641), ranked =
+ * the members ascending by key: pct:286's points[-1] - points[0] is far - near in the native dtype, every other step is a
+ * sum over the members and does not depend on their order (up to the rounding of fp64 sums).
+ * Fewer than 2 members: NaN coefficients, K, H and H^2 (np.cov of one point).  Fewer than 6 members, or normal equations
+ * whose Cholesky pivot ratio falls below the fit's threshold: numpy.linalg.lstsq's minimum-norm (gelsd) answer, by the
+ * solver pct_fit uses for such rows.
+ * Outputs: coefficients (m,6), K, H, H^2 row-aligned; they replace the results of an earlier fit exactly as
+ * pct_fit_indices' do and are read with pct_get_fit(ctx, 0, m, ...).  used (host, m entries, may be NULL): members fitted
+ * per row.  The resident ball rows, the resident neighbour table, PCA results and the cell list are untouched;
+ * pct_timings.fit_ms and fit_svd_rows describe this call.  Works on sorted and unsorted rows, with or without
+ * PCT_BALL_DISTANCES; the same rows in the same order give the same bytes.  Under pct_set_async it first waits for a
+ * pending call, like every blocking entry point.
+ * PCT_ERR_NO_NEIGHBORS without resident rows (none queried, a PCT_BALL_COUNT_ONLY or capped query, a new cloud since);
+ * PCT_ERR_INVALID when m is not the row count of the last query, for a centre outside [0, n), for a slab handle.
+ * Environment, read per call: PCT_FIT_BALL_ROUTE=wave|table forces one of the two device routes (A/B runs). */
+int pct_fit_ball(pct_ctx* ctx, const int64_t* self_rows, int64_t m, int32_t* used);
+
 /* explicit_quadratic_neighbor_study (pct:732-800), the numeric part: for every sample row s and every
  * neighbour count n in [n_lo, n_hi], the Gaussian curvature of the quadric fitted to the point itself plus
  * its n nearest neighbours (pct:759-761).  Needs a resident plain k-NN table with k >= n_hi.

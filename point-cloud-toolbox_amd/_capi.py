@@ -95,6 +95,7 @@ SIGNATURES = {
     "pct_query_ball": (C.c_int, [_p, _f64p, C.c_int64, _f64p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, _i64p]),
     "pct_get_ball": (C.c_int, [_p, C.c_int64, C.c_int64, _i32p, _f64p]),
     "pct_ball_stats": (C.c_int, [_p, _i64p]),
+    "pct_fit_ball": (C.c_int, [_p, _i64p, C.c_int64, _i32p]),
     "pct_mesh_energies": (C.c_int, [_p, _f64p, C.c_int64, _i32p, C.c_int64, _p, _p, C.c_int32, _f64p]),
     "pct_voxel_downsample": (C.c_int, [_p, _f64p, C.c_int64, C.c_double, _i64p, _i64p]),
     "pct_voxel_downsample_f32": (C.c_int, [_p, _f32p, C.c_int64, C.c_double, _i64p, _i64p]),
@@ -426,6 +427,17 @@ class Handle:
         out = np.zeros(4, np.int64)
         self._check(self._lib.pct_ball_stats(self._h, _ptr(out, _i64p)))
         return {"route": int(out[0]), "staged": int(out[1]), "streamed": int(out[2]), "max_ring": int(out[3])}
+
+    def fit_ball(self, self_rows):
+        """``pct_fit_ball``: the quadric fit of the resident rows of the last ``query_ball``, row i about the cloud point
+        ``self_rows[i]`` (its own index is no member of its row).  Returns ``used`` (m,) int32, the members fitted per row;
+        coefficients and curvatures are row-aligned, read with ``get_fit(0, m)``."""
+        rows = np.ascontiguousarray(self_rows, dtype=np.int64)
+        if rows.ndim != 1:
+            raise ValueError("centres must have shape (m,)")
+        used = np.empty(len(rows), np.int32)
+        self._check(self._lib.pct_fit_ball(self._h, _ptr(rows, _i64p), len(rows), _ptr(used, _i32p)))
+        return used
 
     def query_stats(self):
         """Of the last ``query_points``: {route (0 sweep, 1 resident cell list, 2 cell list built), stencil, redone, max_ring}."""

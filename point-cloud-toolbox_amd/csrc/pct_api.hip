@@ -1016,6 +1016,50 @@ int pct_get_ball(pct_ctx* ctx, int64_t row_begin, int64_t row_end, int32_t* idx,
     return PCT_OK;
 }
 
+// Fit of the resident ball rows about their centres (pct_fit_ball.hip).  Like pct_fit_indices it replaces the results of an
+// earlier fit and nothing else: the rows, a resident neighbour table, PCA results and the cell list stay as they are.
+int pct_fit_ball(pct_ctx* ctx, const int64_t* self_rows, int64_t m, int32_t* used) {
+    PCT_TRY(begin_call(ctx));
+    PCT_TRY(refuse_in_slab_mode(ctx, "pct_fit_ball"));
+    if (!ctx->ball_valid) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "pct_fit_ball: no ball rows on this handle (pct_query_ball)");
+    if (m != ctx->ball_m) return pct_fail(ctx, PCT_ERR_INVALID, "pct_fit_ball: %lld centres for the %lld rows of the last query", (long long)m, (long long)ctx->ball_m);
+    if (m > 0 && !self_rows) return pct_fail(ctx, PCT_ERR_INVALID, "pct_fit_ball: null centres");
+    for (int64_t i = 0; i < m; ++i)
+        if (self_rows[i] < 0 || self_rows[i] >= ctx->n)
+            return pct_fail(ctx, PCT_ERR_INVALID, "pct_fit_ball: row %lld: centre %lld outside the cloud", (long long)i, (long long)self_rows[i]);
+    ctx->tm.fit_ms = 0;
+    ctx->tm.fit_svd_rows = 0;
+    ctx->fit_rows = m;
+    ctx->fit_row_order = false;
+    ctx->fit_valid = true;
+    ctx->fit_cloud_aligned = false;
+    if (m == 0) return PCT_OK;
+    PCT_TRY(pct_reserve(ctx, &ctx->coefs, (size_t)m * 6 * sizeof(float)));
+    PCT_TRY(pct_reserve(ctx, &ctx->K, (size_t)m * sizeof(float)));
+    PCT_TRY(pct_reserve(ctx, &ctx->H, (size_t)m * sizeof(float)));
+    PCT_TRY(pct_reserve(ctx, &ctx->H2, (size_t)m * sizeof(float)));
+    PCT_TRY(pct_reserve(ctx, &ctx->stage_c, (size_t)m * sizeof(int)));
+    PCT_TRY(pct_reserve(ctx, &ctx->stage_d, (size_t)m * sizeof(int)));
+    ctx->fit_valid = false;                    // until the kernels have run
+    {
+        int* self32 = (int*)malloc((size_t)m * sizeof(int));
+        if (!self32) return pct_fail(ctx, PCT_ERR_OOM, "pct_fit_ball: %lld centres", (long long)m);
+        for (int64_t i = 0; i < m; ++i) self32[i] = (int)self_rows[i];
+        const hipError_t e = hipMemcpy(ctx->stage_c.p, self32, (size_t)m * sizeof(int), hipMemcpyHostToDevice);
+        free(self32);
+        PCT_HIP(ctx, e);
+    }
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_BEGIN], ctx->stream));
+    PCT_TRY(pct_launch_fit_ball(ctx, (const int*)ctx->stage_c.p, m, (int*)ctx->stage_d.p));
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_END], ctx->stream));
+    if (used) PCT_HIP(ctx, hipMemcpyAsync(used, ctx->stage_d.p, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->tm.fit_ms = ev_ms(ctx, PCT_EV_FIT_BEGIN, PCT_EV_FIT_END);
+    ctx->tm.fit_svd_rows = ctx->pin->svd_rows[0];
+    ctx->fit_valid = true;
+    return PCT_OK;
+}
+
 int pct_ball_stats(pct_ctx* ctx, int64_t out[4]) {
     if (!ctx || !out) return PCT_ERR_INVALID;
     for (int i = 0; i < 4; ++i) out[i] = ctx->ball_stats[i];

@@ -437,6 +437,11 @@ int pct_launch_fit_pass(pct_ctx* ctx, int64_t rows, int par);
 int pct_launch_fit_rows(pct_ctx* ctx, const int32_t* d_idx, const int32_t* d_cnt,
                         const int64_t* d_query, int64_t rows, int32_t k, int32_t pitch,
                         float* d_coefs, float* d_K, float* d_H, float* d_H2, bool sorted_space);
+int pct_launch_fit_rows32(pct_ctx* ctx, const int32_t* d_idx, const int32_t* d_cnt, const int32_t* d_query32, int64_t rows,
+                          int32_t k, int32_t pitch, float* d_coefs, float* d_K, float* d_H, float* d_H2);
+// pct_fit_ball.hip: the resident CSR rows of the last pct_query_ball fitted about the centres d_self32 (rows); d_used (rows)
+// receives the members per row; results row-aligned in ctx->coefs / K / H / H2, SVD row count in pinned slot 0
+int pct_launch_fit_ball(pct_ctx* ctx, const int* d_self32, int64_t rows, int* d_used);
 int pct_launch_prefix_rows(pct_ctx* ctx, const int* d_sample_pos, int64_t n_samples, int n_lo, int n_hi, int* d_table,
                            int pitch, int* d_cnt, int64_t* d_row_query);
 int pct_launch_gather_fit(pct_ctx* ctx, int64_t first, int64_t rows, float* d_coefs, float* d_K, float* d_H, float* d_H2);

@@ -183,6 +183,7 @@ class PointCloud:
         self._uploaded_fp = None        # fingerprint of the points array the device cloud was uploaded from
         self._n_dev = 0                 # rows of the device cloud
         self._nbr_cache = None
+        self._ball_counts = None        # members per row of the last compute_curvature_ball, until the next planting
         self._user_neighbors = None
         self._fit_on_device = False
         self._coefs_cache = None
@@ -291,6 +292,7 @@ class PointCloud:
         self._table_on_device = True
         self.kdtree = _DeviceTree(self)                     # pct:74-75: the tree object later methods query
         self._nbr_cache = None
+        self._ball_counts = None
         self._user_neighbors = None
         self._fit_on_device = False
         self._plant_token += 1
@@ -322,6 +324,8 @@ class PointCloud:
 
     @property
     def neighbor_counts(self):
+        if self._ball_counts is not None:
+            return self._ball_counts
         return self._download_neighbors()[2]
 
     # ------------------------------------------------------------------ A4
@@ -438,12 +442,63 @@ class PointCloud:
         h.curvature(k_neighbors, eps or 0.0, algo)
         self._table_on_device = True
         self._nbr_cache = None
+        self._ball_counts = None
         self._user_neighbors = None
         _, K, H, H2 = h.get_fit(0, self._n_dev, coefs=False)
         self.K_quadratic, self.H_quadratic, self.K_H_sq_quadratic = K, H, H2
         self._plant_token += 1
         self._fit_token = self._plant_token
         self._fit_on_device, self._user_coefs, self._coefs_cache, self._device_curv = True, None, None, (K, H, H2)
+        self.last_timings = h.timings()
+        return K, H
+
+    # curvature over radius neighbourhoods: every point within r of each centre (the usual scan-processing form; the
+    # hybrid form "at most k within eps" is plant_kdtree(k, eps))
+    def compute_curvature_ball(self, radius, rows=None, max_entries=1 << 28):
+        """Quadric-fit curvature of the neighbourhoods ``{p : |p - points[c]| <= radius}`` (inclusive, ``c`` itself left
+        out) of the centres ``c`` in ``rows`` (default: every point), on the device: ``pct_query_ball`` with the centres'
+        own native-dtype coordinates as queries, then ``pct_fit_ball`` on the resident rows, at any row length.
+        ``radius``: a scalar, or one radius per centre.  The centres are chunked where one query would hold more than
+        ``max_entries`` entries (cut by the count pass's offsets).  Returns ``(K, H)`` float32 and sets ``K_quadratic``,
+        ``H_quadratic``, ``K_H_sq_quadratic``, ``quadratic_coefficients`` and ``neighbor_counts`` for the given rows."""
+        h = self._upload()                                 # the cloud of the moment, as plant_kdtree (pct:74)
+        pts = np.asarray(self.points)
+        centres = np.arange(len(pts), dtype=np.int64) if rows is None else np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        if len(centres) and (centres.min() < 0 or centres.max() >= len(pts)):
+            raise ValueError("rows outside the cloud")
+        radii = np.empty(len(centres), np.float64)
+        radii[...] = radius                                # a scalar, or one per centre (NumPy's broadcast and its error)
+        flat = np.ascontiguousarray(pts[centres], dtype=np.float64)     # float32 coordinates widened, float64 as they are
+        one = len(radii) > 0 and bool((radii == radii[0]).all())
+        max_entries = int(max_entries)
+        m = len(centres)
+        coefs, K, H, H2 = np.empty((m, 6), np.float32), np.empty(m, np.float32), np.empty(m, np.float32), np.empty(m, np.float32)
+        used = np.empty(m, np.int32)
+
+        def fit(begin, end):                               # the rows [begin, end) are resident
+            used[begin:end] = h.fit_ball(centres[begin:end])
+            coefs[begin:end], K[begin:end], H[begin:end], H2[begin:end] = h.get_fit(0, end - begin)
+
+        st, offsets = h.query_ball(flat, radii[:1] if one else radii, 0, _capi.QUERY_AUTO, max_entries)
+        if st == _capi.PCT_OK:
+            fit(0, m)
+        else:                                              # PCT_ERR_LIMIT: the same cut as _DeviceTree._ball_csr
+            begin = 0
+            while begin < m:
+                end = max(int(np.searchsorted(offsets, offsets[begin] + max_entries, side="right")) - 1, begin + 1)
+                h.query_ball(flat[begin:end], radii[:1] if one else radii[begin:end], 0, _capi.QUERY_AUTO, 0)
+                fit(begin, end)
+                begin = end
+        # the fit results on the device are those of the last chunk, and the neighbour table (if any) went with the upload
+        self._table_on_device = False
+        self._fit_on_device = False
+        self._device_curv = None
+        self._coefs_cache = None
+        self._user_coefs = coefs
+        self._user_neighbors = None
+        self._nbr_cache = None
+        self._ball_counts = used
+        self.K_quadratic, self.H_quadratic, self.K_H_sq_quadratic = K, H, H2
         self.last_timings = h.timings()
         return K, H
 
