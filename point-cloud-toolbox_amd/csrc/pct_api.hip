@@ -68,6 +68,14 @@ int pct_reserve(pct_ctx* ctx, pct_buf* b, size_t bytes) {
     return PCT_OK;
 }
 
+int pct_reserve_fit(pct_ctx* ctx, int64_t rows) {
+    PCT_TRY(pct_reserve(ctx, &ctx->coefs, (size_t)rows * 6 * sizeof(float)));
+    PCT_TRY(pct_reserve(ctx, &ctx->K, (size_t)rows * sizeof(float)));
+    PCT_TRY(pct_reserve(ctx, &ctx->H, (size_t)rows * sizeof(float)));
+    PCT_TRY(pct_reserve(ctx, &ctx->H2, (size_t)rows * sizeof(float)));
+    return PCT_OK;
+}
+
 static float ev_ms(const hipEvent_t* ev, int a, int b) {
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, ev[a], ev[b]) != hipSuccess) ms = 0.f;
@@ -819,10 +827,7 @@ int pct_fit_indices(pct_ctx* ctx, const int32_t* idx, const int32_t* count, cons
     PCT_TRY(begin_call(ctx));
     int32_t pitch = 0;
     PCT_TRY(stage_neighbour_rows(ctx, idx, count, query, rows, k, &pitch, true));
-    PCT_TRY(pct_reserve(ctx, &ctx->coefs, (size_t)rows * 6 * sizeof(float)));
-    PCT_TRY(pct_reserve(ctx, &ctx->K, (size_t)rows * sizeof(float)));
-    PCT_TRY(pct_reserve(ctx, &ctx->H, (size_t)rows * sizeof(float)));
-    PCT_TRY(pct_reserve(ctx, &ctx->H2, (size_t)rows * sizeof(float)));
+    PCT_TRY(pct_reserve_fit(ctx, rows));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_BEGIN], ctx->stream));
     PCT_TRY(pct_launch_fit_rows(ctx, (const int*)ctx->stage_a.p, count ? (const int*)ctx->stage_c.p : nullptr,
                                 query ? (const int64_t*)ctx->stage_d.p : nullptr, rows, k, pitch, (float*)ctx->coefs.p,
@@ -1034,10 +1039,7 @@ int pct_fit_ball(pct_ctx* ctx, const int64_t* self_rows, int64_t m, int32_t* use
     ctx->fit_valid = true;
     ctx->fit_cloud_aligned = false;
     if (m == 0) return PCT_OK;
-    PCT_TRY(pct_reserve(ctx, &ctx->coefs, (size_t)m * 6 * sizeof(float)));
-    PCT_TRY(pct_reserve(ctx, &ctx->K, (size_t)m * sizeof(float)));
-    PCT_TRY(pct_reserve(ctx, &ctx->H, (size_t)m * sizeof(float)));
-    PCT_TRY(pct_reserve(ctx, &ctx->H2, (size_t)m * sizeof(float)));
+    PCT_TRY(pct_reserve_fit(ctx, m));
     PCT_TRY(pct_reserve(ctx, &ctx->stage_c, (size_t)m * sizeof(int)));
     PCT_TRY(pct_reserve(ctx, &ctx->stage_d, (size_t)m * sizeof(int)));
     ctx->fit_valid = false;                    // until the kernels have run

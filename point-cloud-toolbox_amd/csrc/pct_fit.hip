@@ -43,12 +43,8 @@ constexpr int kFitAhead = PCT_FIT_AHEAD;
 // get here: the resident one of the wide sweeps (k = 256 .. 511: sorted-space positions, the table's pitch, float64
 // clouds, eps counts) and caller-supplied rows (pct_fit_indices takes any k the reference's fit would).
 // MASKED: a compile-time variant, so that the row test leaves the hot instantiation's register allocation alone.
-// KEEP: the centred float32 coordinates of a row's first min(m, KEEP) neighbours stay in registers from pass 1 to pass 2,
-// which then gathers only the neighbours behind them (float32 clouds; 3 registers per kept neighbour).  Where an
-// operand comes from is all that changes: every operation and its order are those of KEEP = 0, and so is every bit.
-template <bool F64, bool OUT64 = false, bool STAGED = true, bool MASKED = false, int KEEP = 0>
+template <bool F64, bool OUT64 = false, bool STAGED = true, bool MASKED = false>
 __global__ __launch_bounds__(kFitBlock) void k_fit(FitArgs a) {
-    static_assert(KEEP == 0 || !F64, "the stash holds float32 coordinates");
     extern __shared__ int s_idx[];   // 64 rows x kp
     const int lane = threadIdx.x;
     if (blockIdx.x == 0) {
@@ -110,6 +106,15 @@ __global__ __launch_bounds__(kFitBlock) void k_fit(FitArgs a) {
     const int* my = STAGED ? s_idx + lane * kp : a.table + row * a.pitch;
     const float nanf_ = __int_as_float(0x7fc00000);
 
+    const auto store_nan = [&]() {      // rows without an answer here: fewer than six neighbours, an entry outside the cloud
+        if constexpr (OUT64) {
+            for (int j = 0; j < 6; ++j) a.coefs64[out * 6 + j] = (double)nanf_;
+            a.K64[out] = (double)nanf_; a.H64[out] = (double)nanf_;
+        } else {
+            for (int j = 0; j < 6; ++j) a.coefs[out * 6 + j] = nanf_;
+            a.K[out] = nanf_; a.H[out] = nanf_; a.H2[out] = nanf_;
+        }
+    };
     // rows this kernel does not finish go to k_fit_svd: one counter increment per wave
     const auto hand_over = [&]() {
         const unsigned long long fm = __ballot(1);                  // the lanes that are here together
@@ -120,13 +125,7 @@ __global__ __launch_bounds__(kFitBlock) void k_fit(FitArgs a) {
         a.flag_list[base + (int)__popcll(fm & ((1ull << lane) - 1ull))] = (int)row;
     };
     if (m < 6) {   // under-determined quadric (eps bound, neighbour study): lstsq's minimum-norm answer, k_fit_svd
-        if constexpr (OUT64) {
-            for (int j = 0; j < 6; ++j) a.coefs64[out * 6 + j] = (double)nanf_;
-            a.K64[out] = (double)nanf_; a.H64[out] = (double)nanf_;
-        } else {
-            for (int j = 0; j < 6; ++j) a.coefs[out * 6 + j] = nanf_;
-            a.K[out] = nanf_; a.H[out] = nanf_; a.H2[out] = nanf_;
-        }
+        store_nan();
         if (m >= 2) hand_over();       // (np.cov of fewer than two points is NaN in the reference as well)
         return;
     }
@@ -154,39 +153,8 @@ __global__ __launch_bounds__(kFitBlock) void k_fit(FitArgs a) {
         bad_id |= (unsigned)id >= a.n_pts;
         return (int)min((unsigned)id, a.n_pts - 1u);
     };
-    float kx[KEEP ? KEEP : 1], ky[KEEP ? KEEP : 1], kz[KEEP ? KEEP : 1];      // the stash: statically indexed, so registers
     {
         int j = 0;
-        if constexpr (KEEP > 0) {
-            // the kept prefix, unrolled in groups of eight gathers.  A group the row ends in loads its last neighbour
-            // again in the places behind it (the same record: no index read past the row) and accumulates up to m.
-#pragma unroll
-            for (int g = 0; g < KEEP; g += 8) {
-                if (g < m) {
-#pragma unroll
-                    for (int t = 0; t < 8; ++t) {
-                        const int u = g + t;
-                        if (u < KEEP) {
-                            const float4 p = a.pts[checked(my[min(u, m - 1)])];
-                            kx[u] = p.x - qp.x; ky[u] = p.y - qp.y; kz[u] = p.z - qp.z;       // as load_centred
-                        }
-                    }
-                    if (g == 0) { fx = (double)kx[0]; fy = (double)ky[0]; fz = (double)kz[0]; }
-#pragma unroll
-                    for (int t = 0; t < 8; ++t) {
-                        const int u = g + t;
-                        if (u < KEEP) {
-                            if (u < m) {
-                                const double x = (double)kx[u], y = (double)ky[u], z = (double)kz[u];
-                                PASS1_ACC(x, y, z);
-                                lx = x; ly = y; lz = z;
-                            }
-                        }
-                    }
-                }
-            }
-            j = min(m, KEEP);
-        }
         for (; j + kFitAhead <= m; j += kFitAhead) {
             double x[kFitAhead], y[kFitAhead], z[kFitAhead];
 #pragma unroll
@@ -206,13 +174,7 @@ __global__ __launch_bounds__(kFitBlock) void k_fit(FitArgs a) {
     }
 #undef PASS1_ACC
     if (bad_id) {
-        if constexpr (OUT64) {
-            for (int j = 0; j < 6; ++j) a.coefs64[out * 6 + j] = (double)nanf_;
-            a.K64[out] = (double)nanf_; a.H64[out] = (double)nanf_;
-        } else {
-            for (int j = 0; j < 6; ++j) a.coefs[out * 6 + j] = nanf_;
-            a.K[out] = nanf_; a.H[out] = nanf_; a.H2[out] = nanf_;
-        }
+        store_nan();
         return;
     }
     double rot[9];
@@ -250,16 +212,6 @@ __global__ __launch_bounds__(kFitBlock) void k_fit(FitArgs a) {
     } while (0)
     {
         int j = 0;
-        if constexpr (KEEP > 0) {
-#pragma unroll
-            for (int u = 0; u < KEEP; ++u) {
-                if (u < m) {
-                    const double x = (double)kx[u], y = (double)ky[u], z = (double)kz[u];
-                    PASS2_ACC(x, y, z);
-                }
-            }
-            j = min(m, KEEP);
-        }
         for (; j + kFitAhead <= m; j += kFitAhead) {
             double x[kFitAhead], y[kFitAhead], z[kFitAhead];
 #pragma unroll
@@ -451,30 +403,20 @@ __global__ __launch_bounds__(256) void k_gather_fit(const int* __restrict__ row_
     if (o_H2) o_H2[i] = H2[r];
 }
 
-// PCT_FIT_JACOBI=1 (read per call): the normal of every row through the cyclic Jacobi, the route before direct_normal()
-int fit_jacobi_forced() {
-    const char* e = pct_getenv("PCT_FIT_JACOBI");
-    return e && e[0] == '1' ? 1 : 0;
-}
-
-// The stash depths k_fit<false, false, true, false, KEEP> is built at, ascending (registers and time of each).
-// The default is the depth with the lowest median step time on the bench shape, and that is none: every depth measured
-// slower than 0 (profiles/r06_a_fit_keep_ab.txt) -- the kernel waits for memory, and fewer gathers do not shorten a wait.
-constexpr int kFitKeepBuilt[] = {8, 10, 16, 25, 50};
-constexpr int kFitKeepDefault = 0;
-
-// The KEEP a launch takes.  Only the headline instantiation (float32 cloud, float32 results, rows staged in LDS, no row
-// mask) is built with a stash; every other launch keeps nothing.  PCT_FIT_KEEP=<depth> (read per call) asks for the
-// largest built depth not above <depth>, whatever the row length: A/B runs, depth-against-depth tests.
-int fit_keep_depth(const FitArgs& a, bool f64, bool staged) {
-    if (f64 || a.coefs64 || a.row_mask || !staged) return 0;
-    int want = kFitKeepDefault;
-    const char* e = pct_getenv("PCT_FIT_KEEP");
-    if (e && e[0] >= '0' && e[0] <= '9') want = atoi(e);
-    int depth = 0;
-    for (const int d : kFitKeepBuilt)
-        if (d <= want) depth = d;
-    return depth;
+// k_fit and the k_fit_svd behind it, for one cloud dtype and one output width.  The masked kernel exists for float32 outputs
+// only (launch() has refused a masked fit with float64 outputs or rows too long to stage).
+template <bool F64, bool OUT64>
+int launch_kernels(pct_ctx* ctx, const FitArgs& a, bool staged, int blocks, size_t lds, long long* note) {
+    const dim3 grid(blocks), block(kFitBlock);
+    if (!OUT64 && a.row_mask && staged) PCT_LAUNCH_T((k_fit<F64, false, true, true>), grid, block, lds, ctx->stream, a);
+    else if (staged) PCT_LAUNCH_T((k_fit<F64, OUT64, true>), grid, block, lds, ctx->stream, a);
+    else PCT_LAUNCH_T((k_fit<F64, OUT64, false>), grid, block, 0, ctx->stream, a);
+    PCT_HIP(ctx, hipGetLastError());
+    // the rows handed over: fixed grid, the list length is read on the device
+    const int sblocks = blocks < 1024 ? blocks : 1024;
+    PCT_LAUNCH_T((k_fit_svd<F64, OUT64>), dim3(sblocks), dim3(64), 0, ctx->stream, a, a.flag_list, a.flag_count, note);
+    PCT_HIP(ctx, hipGetLastError());
+    return PCT_OK;
 }
 
 // slot: the pinned slots of the call (FitSlot); *mirrored (may be null): the fit kernel mirrors the statistics words
@@ -490,7 +432,6 @@ int launch(pct_ctx* ctx, const FitArgs& a0, bool f64, FitSlot slot, bool* mirror
     if (blocks <= 0) return PCT_OK;
     a.blocks_per_xcd = pct_getenv("PCT_NO_XCD_MAP") ? 0 : (blocks + 7) / 8;
     a.force_jacobi = fit_jacobi_forced();
-    a.keep = fit_keep_depth(a, f64, staged);
     if (a.blocks_per_xcd) blocks = a.blocks_per_xcd * 8;
     // rows for k_fit_svd: list + its length (first word of the buffer's 64-byte head)
     // two counts used in turn: a launch counts in one and clears the other for the launch after it (both cleared once per
@@ -513,44 +454,26 @@ int launch(pct_ctx* ctx, const FitArgs& a0, bool f64, FitSlot slot, bool* mirror
     a.flag_next = (int*)ctx->fit_flag.p + (ctx->fit_parity ^ 1);
     ctx->fit_parity ^= 1;
     a.flag_list = (int*)ctx->fit_flag.p + 16;
-#define PCT_FIT_LAUNCH(F_, O_)                                                                                      \
-    do {                                                                                                            \
-        if (a.row_mask && staged && !O_) PCT_LAUNCH((k_fit<F_, false, true, true>), dim3(blocks), dim3(kFitBlock), lds, ctx->stream, a); \
-        else if (staged) PCT_LAUNCH((k_fit<F_, O_, true>), dim3(blocks), dim3(kFitBlock), lds, ctx->stream, a);  \
-        else PCT_LAUNCH((k_fit<F_, O_, false>), dim3(blocks), dim3(kFitBlock), 0, ctx->stream, a);          \
-    } while (0)
-#define PCT_FIT_LAUNCH_KEEP(D_) \
-    case D_: PCT_LAUNCH((k_fit<false, false, true, false, D_>), dim3(blocks), dim3(kFitBlock), lds, ctx->stream, a); break
-    if (a.keep) {
-        switch (a.keep) {
-            PCT_FIT_LAUNCH_KEEP(8);
-            PCT_FIT_LAUNCH_KEEP(10);
-            PCT_FIT_LAUNCH_KEEP(16);
-            PCT_FIT_LAUNCH_KEEP(25);
-            PCT_FIT_LAUNCH_KEEP(50);
-            default: return pct_fail(ctx, PCT_ERR_INVALID, "fit: no kernel keeps %d neighbours", a.keep);
-        }
-    } else if (a.coefs64) {
-        if (f64) PCT_FIT_LAUNCH(true, true);
-        else PCT_FIT_LAUNCH(false, true);
-    } else if (f64) PCT_FIT_LAUNCH(true, false);
-    else PCT_FIT_LAUNCH(false, false);
-#undef PCT_FIT_LAUNCH_KEEP
-#undef PCT_FIT_LAUNCH
-    PCT_HIP(ctx, hipGetLastError());
-    // the rows handed over: fixed grid, the list length is read on the device
-    const int sblocks = blocks < 1024 ? blocks : 1024;
     long long* note = &ctx->pin->svd_rows[slot.par];
-    if (a.coefs64) {
-        if (f64)
-            PCT_LAUNCH((k_fit_svd<true, true>), dim3(sblocks), dim3(64), 0, ctx->stream, a, a.flag_list, a.flag_count, note);
-        else
-            PCT_LAUNCH((k_fit_svd<false, true>), dim3(sblocks), dim3(64), 0, ctx->stream, a, a.flag_list, a.flag_count, note);
-    } else if (f64)
-        PCT_LAUNCH((k_fit_svd<true, false>), dim3(sblocks), dim3(64), 0, ctx->stream, a, a.flag_list, a.flag_count, note);
-    else
-        PCT_LAUNCH((k_fit_svd<false, false>), dim3(sblocks), dim3(64), 0, ctx->stream, a, a.flag_list, a.flag_count, note);
-    PCT_HIP(ctx, hipGetLastError());
+    if (a.coefs64) return f64 ? launch_kernels<true, true>(ctx, a, staged, blocks, lds, note) : launch_kernels<false, true>(ctx, a, staged, blocks, lds, note);
+    return f64 ? launch_kernels<true, false>(ctx, a, staged, blocks, lds, note) : launch_kernels<false, false>(ctx, a, staged, blocks, lds, note);
+}
+
+// What the two fits of the resident table share: the handle's result buffers for the owned range, the table's own counts
+// and the owned public range.
+int table_args(pct_ctx* ctx, FitSpace space, FitArgs* a) {
+    PCT_TRY(pct_reserve_fit(ctx, ctx->q_end - ctx->q_begin));
+    PCT_TRY(fit_source(ctx, space, a));
+    a->table = (const int*)ctx->nbr_pos.p;
+    a->cnt = ctx->eps > 0 ? (const int*)ctx->nbr_cnt.p : nullptr;
+    a->k = ctx->k;
+    a->out_base = ctx->q_begin;
+    a->q_begin = (int)ctx->q_begin;
+    a->q_end = (int)ctx->q_end;
+    a->coefs = (float*)ctx->coefs.p;
+    a->K = (float*)ctx->K.p;
+    a->H = (float*)ctx->H.p;
+    a->H2 = (float*)ctx->H2.p;
     return PCT_OK;
 }
 
@@ -560,29 +483,12 @@ int launch(pct_ctx* ctx, const FitArgs& a0, bool f64, FitSlot slot, bool* mirror
 // still in ITS cell order -- gathers stay local; results go to public order.  The merged public-space table is fitted
 // only when a caller asks for the table first and the fit later (1.3 ms instead of 0.25 at 1 M points).
 int pct_launch_fit_pass(pct_ctx* ctx, int64_t rows, int par) {
-    const int64_t nq = ctx->q_end - ctx->q_begin;
-    PCT_TRY(pct_reserve(ctx, &ctx->coefs, (size_t)nq * 6 * sizeof(float)));
-    PCT_TRY(pct_reserve(ctx, &ctx->K, (size_t)nq * sizeof(float)));
-    PCT_TRY(pct_reserve(ctx, &ctx->H, (size_t)nq * sizeof(float)));
-    PCT_TRY(pct_reserve(ctx, &ctx->H2, (size_t)nq * sizeof(float)));
     FitArgs a = {};
-    a.pts = (const float4*)ctx->sorted4.p;
-    a.ptsd = ctx->has_f64 ? (const double4*)ctx->sorted4d.p : nullptr;
-    a.table = (const int*)ctx->nbr_pos.p;
-    a.cnt = ctx->eps > 0 ? (const int*)ctx->nbr_cnt.p : nullptr;
+    PCT_TRY(table_args(ctx, FitSpace::Sorted, &a));
     a.row_query32 = (const int*)ctx->owned_pos.p;
     a.rows = rows;
-    a.k = ctx->k;
     a.pitch = (ctx->k + 3) & ~3;
     a.out_by_row = 0;
-    a.out_base = ctx->q_begin;
-    a.q_begin = (int)ctx->q_begin;
-    a.q_end = (int)ctx->q_end;
-    a.coefs = (float*)ctx->coefs.p;
-    a.K = (float*)ctx->K.p;
-    a.H = (float*)ctx->H.p;
-    a.H2 = (float*)ctx->H2.p;
-    a.n_pts = (unsigned)ctx->n_grid;
     a.row_mask = (const int*)ctx->row_done.p;
     a.svd_accumulate = 1;                      // (pct_knn_levels zeroes the host word before the first pass)
     return launch(ctx, a, ctx->has_f64, FitSlot{par, false}, nullptr);      // (a pass mirrors nothing: the sweep goes on behind it)
@@ -590,36 +496,18 @@ int pct_launch_fit_pass(pct_ctx* ctx, int64_t rows, int par) {
 
 // fit from the device-resident neighbour table left by the sweep
 int pct_launch_fit_table(pct_ctx* ctx, FitSlot slot, bool* mirrored) {
-    const int64_t nq = ctx->q_end - ctx->q_begin;
-    PCT_TRY(pct_reserve(ctx, &ctx->coefs, (size_t)nq * 6 * sizeof(float)));
-    PCT_TRY(pct_reserve(ctx, &ctx->K, (size_t)nq * sizeof(float)));
-    PCT_TRY(pct_reserve(ctx, &ctx->H, (size_t)nq * sizeof(float)));
-    PCT_TRY(pct_reserve(ctx, &ctx->H2, (size_t)nq * sizeof(float)));
     FitArgs a = {};
     const bool sorted = ctx->knn_sorted_space;
-    a.pts = (const float4*)(sorted ? ctx->sorted4.p : ctx->pts4.p);
-    a.ptsd = ctx->has_f64 ? (const double4*)(sorted ? ctx->sorted4d.p : ctx->pts4d.p) : nullptr;
-    a.table = (const int*)ctx->nbr_pos.p;
-    a.cnt = ctx->eps > 0 ? (const int*)ctx->nbr_cnt.p : nullptr;
-    a.row_query = nullptr;
+    PCT_TRY(table_args(ctx, sorted ? FitSpace::Sorted : FitSpace::Packed, &a));
     a.row_query32 = sorted ? (const int*)ctx->owned_pos.p : nullptr;    // table row -> sorted position of its query
     a.row_offset = sorted ? 0 : ctx->q_begin;                           // exhaustive sweep: row = public index - q_begin
-    a.rows = nq;
-    a.k = ctx->k;
+    a.rows = ctx->q_end - ctx->q_begin;
     a.pitch = ctx->nbr_pitch;
     // Grid sweep: results stay in TABLE-ROW (cell) order -- a wave's 64 rows are consecutive, so the stores
     // coalesce; written in public order they were 36 B scattered per point and cost 4x the bytes at the HBM
     // (WRITE_SIZE 145 MB vs 36 MB).  pct_get_fit gathers public rows on request (pct_launch_gather_fit).
     a.out_by_row = sorted ? 1 : 0;
     ctx->fit_row_order = sorted;
-    a.out_base = ctx->q_begin;
-    a.q_begin = (int)ctx->q_begin;
-    a.q_end = (int)ctx->q_end;
-    a.coefs = (float*)ctx->coefs.p;
-    a.K = (float*)ctx->K.p;
-    a.H = (float*)ctx->H.p;
-    a.H2 = (float*)ctx->H2.p;
-    a.n_pts = (unsigned)(sorted ? ctx->n_grid : ctx->n);
     return launch(ctx, a, ctx->has_f64, slot, mirrored);
 }
 
@@ -632,41 +520,17 @@ int pct_launch_gather_fit(pct_ctx* ctx, int64_t first, int64_t rows, float* d_co
     return PCT_OK;
 }
 
-// fit from explicit neighbour rows, outputs row-aligned.  sorted_space: ids refer to the cell-sorted arrays.
-int pct_launch_fit_rows(pct_ctx* ctx, const int32_t* d_idx, const int32_t* d_cnt, const int64_t* d_query,
-                        int64_t rows, int32_t k, int32_t pitch, float* d_coefs, float* d_K, float* d_H, float* d_H2,
-                        bool sorted_space) {
+// Fit from explicit neighbour rows, outputs row-aligned: the one body of the three entries below.  The query of a row is
+// d_query32[row], else d_query[row], else the row's own number; the results are the float32 four or the float64 three.
+// (rows with fewer than 6 points get lstsq's minimum-norm answer from k_fit_svd, as in every launch)
+static int fit_rows(pct_ctx* ctx, FitSpace space, const int32_t* d_idx, const int32_t* d_cnt, const int64_t* d_query,
+                    const int32_t* d_query32, int64_t rows, int32_t k, int32_t pitch, float* d_coefs, float* d_K, float* d_H,
+                    float* d_H2, double* d_coefs64, double* d_K64, double* d_H64) {
     FitArgs a = {};
-    a.pts = (const float4*)(sorted_space ? ctx->sorted4.p : ctx->pts4.p);
-    a.ptsd = ctx->has_f64 ? (const double4*)(sorted_space ? ctx->sorted4d.p : ctx->pts4d.p) : nullptr;
+    PCT_TRY(fit_source(ctx, space, &a));
     a.table = d_idx;
     a.cnt = d_cnt;
     a.row_query = d_query;
-    a.rows = rows;
-    a.k = k;
-    a.pitch = pitch;
-    a.out_by_row = 1;
-    a.out_base = 0;
-    a.q_begin = 0;
-    a.q_end = (int)ctx->n;
-    a.coefs = d_coefs;
-    a.K = d_K;
-    a.H = d_H;
-    a.H2 = d_H2;
-    a.n_pts = (unsigned)(sorted_space ? ctx->n_grid : ctx->n);
-    // (rows with fewer than 6 points get lstsq's minimum-norm answer from k_fit_svd, as in every launch)
-    return launch(ctx, a, ctx->has_f64, FitSlot{0, false}, nullptr);       // (a blocking entry point: slot 0, no fused tail behind it)
-}
-
-// the same for rows built on the device (pct_fit_ball.hip): public-space ids into the plain records, int32 query ids
-int pct_launch_fit_rows32(pct_ctx* ctx, const int32_t* d_idx, const int32_t* d_cnt, const int32_t* d_query32, int64_t rows,
-                          int32_t k, int32_t pitch, float* d_coefs, float* d_K, float* d_H, float* d_H2) {
-    PCT_TRY(pct_ensure_plain_records(ctx));
-    FitArgs a = {};
-    a.pts = (const float4*)ctx->qpts4.p;
-    a.ptsd = ctx->has_f64 ? (const double4*)ctx->pts4d.p : nullptr;
-    a.table = d_idx;
-    a.cnt = d_cnt;
     a.row_query32 = d_query32;
     a.rows = rows;
     a.k = k;
@@ -678,31 +542,32 @@ int pct_launch_fit_rows32(pct_ctx* ctx, const int32_t* d_idx, const int32_t* d_c
     a.K = d_K;
     a.H = d_H;
     a.H2 = d_H2;
-    a.n_pts = (unsigned)ctx->n;
+    a.coefs64 = d_coefs64;
+    a.K64 = d_K64;
+    a.H64 = d_H64;
     return launch(ctx, a, ctx->has_f64, FitSlot{0, false}, nullptr);       // (a blocking entry point: slot 0, no fused tail behind it)
+}
+
+// sorted_space: ids refer to the cell-sorted arrays, else to the packed ones
+int pct_launch_fit_rows(pct_ctx* ctx, const int32_t* d_idx, const int32_t* d_cnt, const int64_t* d_query,
+                        int64_t rows, int32_t k, int32_t pitch, float* d_coefs, float* d_K, float* d_H, float* d_H2,
+                        bool sorted_space) {
+    return fit_rows(ctx, sorted_space ? FitSpace::Sorted : FitSpace::Packed, d_idx, d_cnt, d_query, nullptr, rows, k, pitch,
+                    d_coefs, d_K, d_H, d_H2, nullptr, nullptr, nullptr);
+}
+
+// the same for rows built on the device (pct_fit_ball.hip): public-space ids into the plain records, int32 query ids
+int pct_launch_fit_rows32(pct_ctx* ctx, const int32_t* d_idx, const int32_t* d_cnt, const int32_t* d_query32, int64_t rows,
+                          int32_t k, int32_t pitch, float* d_coefs, float* d_K, float* d_H, float* d_H2) {
+    return fit_rows(ctx, FitSpace::Public, d_idx, d_cnt, nullptr, d_query32, rows, k, pitch, d_coefs, d_K, d_H, d_H2, nullptr,
+                    nullptr, nullptr);
 }
 
 // the diagnostics variant of pct_launch_fit_rows: float64 coefficients and curvatures, public-space ids
 int pct_launch_fit_rows_f64(pct_ctx* ctx, const int32_t* d_idx, const int32_t* d_cnt, const int64_t* d_query, int64_t rows,
                             int32_t k, int32_t pitch, double* d_coefs, double* d_K, double* d_H) {
-    PCT_TRY(pct_ensure_plain_records(ctx));
-    FitArgs a = {};
-    a.pts = (const float4*)ctx->qpts4.p;
-    a.ptsd = ctx->has_f64 ? (const double4*)ctx->pts4d.p : nullptr;
-    a.table = d_idx;
-    a.cnt = d_cnt;
-    a.row_query = d_query;
-    a.rows = rows;
-    a.k = k;
-    a.pitch = pitch;
-    a.out_by_row = 1;
-    a.q_begin = 0;
-    a.q_end = (int)ctx->n;
-    a.coefs64 = d_coefs;
-    a.K64 = d_K;
-    a.H64 = d_H;
-    a.n_pts = (unsigned)ctx->n;
-    return launch(ctx, a, ctx->has_f64, FitSlot{0, false}, nullptr);       // (a blocking entry point: slot 0, no fused tail behind it)
+    return fit_rows(ctx, FitSpace::Public, d_idx, d_cnt, d_query, nullptr, rows, k, pitch, nullptr, nullptr, nullptr, nullptr,
+                    d_coefs, d_K, d_H);
 }
 
 int pct_launch_prefix_rows(pct_ctx* ctx, const int* d_sample_row, int64_t n_samples, int n_lo, int n_hi, int* d_table,

@@ -321,7 +321,8 @@ int ball_fit_short_max() {                    // PCT_FIT_BALL_SHORT=<members>: a
 // ctx->coefs / K / H / H2 (reserved by the caller).  The pinned SVD row count of slot 0 is complete at the next
 // synchronisation.
 int pct_launch_fit_ball(pct_ctx* ctx, const int* d_self32, int64_t rows, int* d_used) {
-    PCT_TRY(pct_ensure_plain_records(ctx));
+    BallFitArgs b = {};
+    PCT_TRY(fit_source(ctx, FitSpace::Public, &b.f));
     const bool f64 = ctx->has_f64;
     const int short_max = ball_fit_short_max(), pitch = ball_fit_pitch(short_max);
     const bool with_table = ball_fit_table_allowed(rows, short_max, ball_fit_route_knob());
@@ -340,10 +341,6 @@ int pct_launch_fit_ball(pct_ctx* ctx, const int* d_self32, int64_t rows, int* d_
     }
     PCT_HIP(ctx, hipMemsetAsync(words, 0, 64, ctx->stream));
 
-    BallFitArgs b = {};
-    b.f.pts = (const float4*)ctx->qpts4.p;
-    b.f.ptsd = f64 ? (const double4*)ctx->pts4d.p : nullptr;
-    b.f.n_pts = (unsigned)ctx->n;
     b.f.out_by_row = 1;
     b.f.coefs = (float*)ctx->coefs.p;
     b.f.K = (float*)ctx->K.p;
@@ -351,7 +348,7 @@ int pct_launch_fit_ball(pct_ctx* ctx, const int* d_self32, int64_t rows, int* d_
     b.f.H2 = (float*)ctx->H2.p;
     b.f.flag_list = flag_list;
     b.f.flag_count = words + 2;
-    b.f.force_jacobi = pct_getenv("PCT_FIT_JACOBI") && pct_getenv("PCT_FIT_JACOBI")[0] == '1' ? 1 : 0;
+    b.f.force_jacobi = fit_jacobi_forced();
     b.off = (const int64_t*)ctx->ball_off.p;
     b.idx = (const int*)ctx->ball_idx.p;
     b.self32 = d_self32;

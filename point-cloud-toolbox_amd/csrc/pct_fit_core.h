@@ -1,5 +1,6 @@
 // What the fit kernels share (pct_fit.hip: k_fit, k_fit_svd and the batched staticmethods; pct_fit_ball.hip: the fit of
-// CSR rows): the launch arguments, the tangent-plane stage, the curvature formulas and the gelsd-semantics solver.
+// CSR rows): the launch arguments and the two host helpers that fill them, the tangent-plane stage, the curvature formulas
+// and the gelsd-semantics solver.
 // Everything is internal to the translation unit that includes it (anonymous namespace), exactly as when it lived in
 // pct_fit.hip: the move changed no token of these functions, and k_fit compiles to the same code.
 #pragma once
@@ -42,9 +43,27 @@ struct FitArgs {
     int force_jacobi;        // PCT_FIT_JACOBI=1: every row's normal through the cyclic Jacobi (A/B runs, route-against-route tests)
     int blocks_per_xcd;      // blocks are dealt to the 8 XCDs in turn: block b takes rows of block (b % 8) * blocks_per_xcd + b / 8, so
                              // that one XCD's L2 serves neighbouring rows (table rows are in cell order: their neighbours overlap)
-    int keep;                // the KEEP of the instantiation the launch takes (fit_keep_depth(): PCT_FIT_KEEP=<depth>, A/B runs and
-                             // depth-against-depth tests); the kernels do not read it
 };
+
+// The three orders of the cloud's records that the neighbour ids of a fit refer to: the cell-sorted records (ctx->sorted4 /
+// sorted4d, n_grid of them), the packed ones (pts4 / pts4d, n) and the public-order records (qpts4 / pts4d, n).
+enum class FitSpace { Sorted, Packed, Public };
+
+// pts, ptsd and n_pts of a launch: set here together, and nowhere else
+int fit_source(pct_ctx* ctx, FitSpace space, FitArgs* a) {
+    if (space == FitSpace::Public) PCT_TRY(pct_ensure_plain_records(ctx));
+    const bool sorted = space == FitSpace::Sorted;
+    a->pts = (const float4*)(sorted ? ctx->sorted4.p : space == FitSpace::Packed ? ctx->pts4.p : ctx->qpts4.p);
+    a->ptsd = ctx->has_f64 ? (const double4*)(sorted ? ctx->sorted4d.p : ctx->pts4d.p) : nullptr;
+    a->n_pts = (unsigned)(sorted ? ctx->n_grid : ctx->n);
+    return PCT_OK;
+}
+
+// PCT_FIT_JACOBI=1 (read per call): the normal of every row through the cyclic Jacobi, the route before direct_normal()
+int fit_jacobi_forced() {
+    const char* e = pct_getenv("PCT_FIT_JACOBI");
+    return e && e[0] == '1' ? 1 : 0;
+}
 
 // Smallest Cholesky pivot ratio d_j / g_jj (= sin^2 of the angle between design column j and the span of the columns
 // before it; invariant under column scaling) below which the normal equations are not trusted.  Their error grows like

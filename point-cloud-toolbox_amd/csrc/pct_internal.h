@@ -338,6 +338,7 @@ inline double pct_default_factor(int k) {
     return n <= 85 ? 0.52 : n <= 101 ? 0.52 - 0.07 * (n - 85) / 16.0 : 0.45 - 0.05 * (n - 101) / 27.0;
 }
 int pct_reserve(pct_ctx* ctx, pct_buf* b, size_t bytes);
+int pct_reserve_fit(pct_ctx* ctx, int64_t rows);     // the handle's fit results (ctx->coefs, K, H, H2) for `rows` rows
 inline pct_dev_words* pct_dev(pct_ctx* ctx) { return (pct_dev_words*)ctx->counters.p; }     // after pct_reserve(&ctx->counters, sizeof(pct_dev_words))
 void pct_release(pct_buf* b);
 

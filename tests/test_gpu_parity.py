@@ -469,6 +469,48 @@ def test_hybrid_eps_query(gpu):
     assert_curvature(K, H, ref["K"], ref["H"])
 
 
+def test_eps_bound_that_leaves_rows_shorter_than_the_quadric(gpu):
+    """The fused call under a bound that leaves rows of 0 to 24 neighbours (2 000-point torus, k = 30, the median row
+    holds 8): six and more against oracle.curvature_batched; three to five against the reference loop, i.e. lstsq's
+    minimum-norm answer (three points lie IN their plane, the orientation test's dot product is rounding noise: either
+    order of first and last neighbour; two points have no normal at all in the reference -- finite, no more); none and
+    one read NaN and nothing else does.  The rows handed to k_fit_svd are the under-determined ones and, of the others,
+    those the pivot test sends: all whose normal equations are hopeless, none whose are comfortable."""
+    import fit_exact as fe
+    k = 30
+    pts = gpu["shapes"].torus_random(2000, seed=78)
+    p = pts.astype(np.float64)
+    d = np.sqrt(((p[:, None, :] - p[None, :, :]) ** 2).sum(-1))
+    eps = float(np.median(np.sort(d, axis=1)[:, 9]))          # about nine points inside the bound, self included
+    idx, _, cnt = oracle.knn(pts, k, eps=eps)
+    assert cnt.min() == 0 and (cnt == 1).any() and all((cnt == m).sum() >= 20 for m in range(2, 12)) and cnt.max() < k
+    h = gpu["capi"].Handle(0)
+    h.set_points(pts)
+    h.curvature(k, eps, gpu["capi"].KNN_GRID)
+    co, K, H, H2 = h.get_fit(0, len(pts))
+    got_idx, _, got_cnt = h.get_neighbors(0, len(pts), want_count=True)
+    svd_rows = h.timings()["fit_svd_rows"]
+    h.close()
+    valid = np.arange(k)[None, :] < cnt[:, None]
+    assert np.array_equal(got_cnt, cnt) and np.array_equal(got_idx[valid], idx[valid])
+
+    none = cnt < 2
+    for a in (co, K, H, H2):
+        assert np.isnan(a[none]).all() and np.isfinite(a[~none]).all()
+    full = np.flatnonzero(cnt >= 6)
+    _, rK, rH, _ = oracle.curvature_batched(pts, idx[full], full, cnt[full])
+    assert_curvature(K[full], H[full], rK, rH)
+    for r in np.flatnonzero((cnt >= 3) & (cnt < 6)):
+        orders = [np.arange(cnt[r])] + ([np.arange(3)[::-1]] if cnt[r] == 3 else [])
+        cands = [oracle.curvature_loop(pts, idx[r, :cnt[r]][o][None, :], [r])[0][0] for o in orders]
+        assert any(np.allclose(co[r], c, rtol=1e-5, atol=1e-6 * np.abs(c).max()) for c in cands), (r, cnt[r], co[r], cands)
+
+    pivot = np.array([fe.pivot_ratios(fe.design(oracle.plane_align(pts[idx[r, :cnt[r]]] - pts[r]))[0]).min() for r in full])
+    short = int(((cnt >= 2) & (cnt < 6)).sum())
+    assert short + (pivot <= 1e-10).sum() <= svd_rows <= short + len(full) - (pivot >= 1e-3).sum(), (svd_rows, short)
+    print(f"eps rows: {int(none.sum())} NaN, {short} under-determined, {len(full)} full, {svd_rows} to k_fit_svd")
+
+
 def test_density_contrast_forces_ring_fallback_and_lds_overflow(gpu):
     rng = np.random.default_rng(5)
     dense = rng.normal(scale=0.002, size=(6000, 3))
@@ -839,6 +881,29 @@ def test_fused_entry_matches_stepwise(gpu):
     ref = oracle.knn(p64, 50)
     assert np.array_equal(e.neighbor_indices, ref[0]) and np.array_equal(e.dists, ref[1])
     assert np.array_equal(f.neighbor_indices, ref[0]) and np.array_equal(f.dists, ref[1])
+
+
+def test_fused_call_against_the_oracle(gpu):
+    """pct_curvature itself (sweep and fit in one call, results in cell order until they are read) on a 20 000-point
+    torus at k = 50, against the oracle.  No row goes to k_fit_svd: the smallest Cholesky pivot ratio over the oracle's
+    20 000 neighbourhoods is 0.094 (fit_exact.pivot_ratios of every row; every tenth row is recomputed here), five
+    decades above where the normal equations are handed over."""
+    import fit_exact as fe
+    pts = gpu["shapes"].torus_random(20_000, seed=1234)
+    ref = oracle.pipeline_batched(pts, 50)
+    h = gpu["capi"].Handle(0)
+    h.set_points(pts)
+    h.curvature(50)
+    idx, dists, _ = h.get_neighbors(0, len(pts))
+    co, K, H, H2 = h.get_fit(0, len(pts))
+    svd_rows = h.timings()["fit_svd_rows"]
+    h.close()
+    assert np.array_equal(idx, ref["idx"]) and np.array_equal(dists, ref["dists"])
+    assert_curvature(K, H, ref["K"], ref["H"])
+    assert np.array_equal(H2, H * H)
+    rows = range(0, len(pts), 10)
+    assert min(fe.pivot_ratios(fe.design(oracle.plane_align(pts[ref["idx"][r]] - pts[r]))[0]).min() for r in rows) >= 1e-3
+    assert svd_rows == 0, svd_rows
 
 
 def test_host_supplied_indices_and_validation(gpu, golden):
