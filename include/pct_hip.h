@@ -301,6 +301,40 @@ int pct_mesh_energies(pct_ctx* ctx, const double* vertices, int64_t n_vertices, 
                       int64_t n_triangles, const void* gaussian, const void* mean, int32_t curvature_is_f64,
                       double* out3);
 
+/* Mesh-free energies.  calculate_energies(voronoi_areas, gaussian_curvature, mean_curvature) (pct:650-655) sums
+ * (h ** 2) * area and k * area over per-point areas that nothing in the reference produces.  pct_point_areas produces
+ * them from the rows of the resident neighbour table (pct_knn / pct_curvature; owned rows, eps counts and rows of up to
+ * 511 neighbours included): the area of every point's Voronoi cell in its own tangent plane.  Row i, count_i neighbours:
+ *   block   Q_j = p_j - p_i, centred in the cloud's dtype (pct:641), float64 from there on;
+ *   frame   R = the rotation pct_fit takes for this row (pct:270-312); (a_j, b_j) = the first two components of R Q_j;
+ *   bound   L^2 = max_j |Q_j|^2;
+ *   cell    the square [-L, L]^2 cut by the half-plane a_j x + b_j y <= rho_j^2 / 2 of every neighbour with
+ *           rho_j^2 = a_j^2 + b_j^2 > 0, in row order (rho_j^2 == 0 -- a coinciding point, or one straight along the
+ *           normal -- cuts nothing: each of two twins keeps its full cell);
+ *   area    (float64) the shoelace area of the polygon left; nverts (int32) its vertex count; closed (uint8) 1 iff it has
+ *           at least 3 vertices and every one of them has x^2 + y^2 < L^2 (independent of the in-plane basis).  A row that
+ *           is not closed is open -- the rim of an open surface, k too small, fewer than 3 neighbours -- and reports the
+ *           area of the square as far as it was cut;
+ *   NaN     count_i < 2, a frame that is not finite: area NaN, closed 0, nverts 0 -- the rows whose fit is NaN.
+ * PCT_ERR_NO_NEIGHBORS without a resident table, as pct_fit.  A new cloud, owned range or planting drops the areas, as it
+ * drops the fit.  pct_timings is untouched (its size is part of the ABI): pct_point_area_profile has the time. */
+int pct_point_areas(pct_ctx* ctx);
+/* Cloud rows [begin, end) of the owned range; any pointer may be NULL.  PCT_ERR_INVALID without areas. */
+int pct_get_point_areas(pct_ctx* ctx, int64_t begin, int64_t end, double* area, uint8_t* closed, int32_t* nverts);
+/* Of the last pct_point_areas: out = {rows, closed rows, NaN rows, rows whose polygon outgrew the fast kernel's vertex
+ * capacity and were redone with room for k + 4 vertices (the same code, the same result)}. */
+int pct_point_area_stats(pct_ctx* ctx, int64_t out[4]);
+/* ... and out = {device milliseconds of its kernels (hipEvent), neighbours that passed the rejection test, summed over
+ * the rows -- the cuts that were actually examined}. */
+int pct_point_area_profile(pct_ctx* ctx, double out[2]);
+/* calculate_energies (pct:650-655) on the device: out = {bending = sum (double)H2_i * A_i with H2 the fit's float32
+ * h ** 2 (pct:652), stretching = sum (double)K_i * A_i (pct:653), area = sum A_i, rows used}, over the owned rows whose
+ * area, K and H are no NaN -- closed_only != 0: and whose cell is closed.  float64 sums in a fixed order over the table's rows (per-
+ * block partials, then one block): the same bytes for the same resident table; another planting may order the rows of a
+ * cell differently, and the sums then differ in their last bits.  Needs the fit (pct_fit / pct_curvature) and the areas of the
+ * table in place: PCT_ERR_INVALID "no fit results" / "no point areas" otherwise. */
+int pct_point_energies(pct_ctx* ctx, int32_t closed_only, double out[4]);
+
 /* ---- scan preparation (next row N4) ---------------------------------------- */
 /* Voxel-grid down-sampling of convert_asc_to_ply.py:20-51: voxel = floor(coordinate / voxel_size) evaluated in the
  * coordinates' own dtype as NumPy does (the _f32 form divides by (float)voxel_size in float32), the

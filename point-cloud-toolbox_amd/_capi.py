@@ -56,6 +56,7 @@ _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
 _f32p = C.POINTER(C.c_float)
 _f64p = C.POINTER(C.c_double)
+_u8p = C.POINTER(C.c_uint8)
 
 # name -> (restype, argtypes); every symbol declared in include/pct_hip.h
 SIGNATURES = {
@@ -97,6 +98,11 @@ SIGNATURES = {
     "pct_ball_stats": (C.c_int, [_p, _i64p]),
     "pct_fit_ball": (C.c_int, [_p, _i64p, C.c_int64, _i32p]),
     "pct_mesh_energies": (C.c_int, [_p, _f64p, C.c_int64, _i32p, C.c_int64, _p, _p, C.c_int32, _f64p]),
+    "pct_point_areas": (C.c_int, [_p]),
+    "pct_get_point_areas": (C.c_int, [_p, C.c_int64, C.c_int64, _f64p, _u8p, _i32p]),
+    "pct_point_area_stats": (C.c_int, [_p, _i64p]),
+    "pct_point_area_profile": (C.c_int, [_p, _f64p]),
+    "pct_point_energies": (C.c_int, [_p, C.c_int32, _f64p]),
     "pct_voxel_downsample": (C.c_int, [_p, _f64p, C.c_int64, C.c_double, _i64p, _i64p]),
     "pct_voxel_downsample_f32": (C.c_int, [_p, _f32p, C.c_int64, C.c_double, _i64p, _i64p]),
     "pct_surface_variation": (C.c_int, [_p, C.c_int32, _f32p]),
@@ -540,6 +546,38 @@ class Handle:
         self._check(self._lib.pct_mesh_energies(self._h, _ptr(v, _f64p), len(v), _ptr(t, _i32p), len(t), g.ctypes.data_as(_p),
                                                m.ctypes.data_as(_p), kind, _ptr(out, _f64p)))
         return float(out[0]), float(out[1]), float(out[2])
+
+    # -- mesh-free energies: tangent-plane Voronoi areas of the resident table's rows (pct:650-655) ------------------
+    def point_areas(self):
+        """``pct_point_areas``: the area of every owned point's Voronoi cell in its own tangent plane, from the rows of
+        the resident neighbour table; kept on the device (``get_point_areas``, ``point_energies``)."""
+        self._check(self._lib.pct_point_areas(self._h))
+
+    def get_point_areas(self, begin, end, area=True, closed=True, nverts=True):
+        """(area float64, closed uint8, nverts int32) of cloud rows [begin, end); ``None`` for what was not asked for."""
+        rows = int(end) - int(begin)
+        a = np.empty(rows, np.float64) if area else None
+        c = np.empty(rows, np.uint8) if closed else None
+        n = np.empty(rows, np.int32) if nverts else None
+        self._check(self._lib.pct_get_point_areas(self._h, int(begin), int(end), _ptr(a, _f64p), _ptr(c, _u8p), _ptr(n, _i32p)))
+        return a, c, n
+
+    def point_area_stats(self):
+        """Of the last ``point_areas``: {rows, closed, nan, overflow (rows redone with room for k + 4 vertices), ms (device
+        time of its kernels), survivors (neighbours that passed the rejection test, summed over the rows)}."""
+        out = np.zeros(4, np.int64)
+        self._check(self._lib.pct_point_area_stats(self._h, _ptr(out, _i64p)))
+        prof = np.zeros(2, np.float64)
+        self._check(self._lib.pct_point_area_profile(self._h, _ptr(prof, _f64p)))
+        return {"rows": int(out[0]), "closed": int(out[1]), "nan": int(out[2]), "overflow": int(out[3]),
+                "ms": float(prof[0]), "survivors": int(prof[1])}
+
+    def point_energies(self, closed_only=False):
+        """``pct_point_energies``: (bending, stretching, area, n_used) over the owned rows -- the closed ones only with
+        ``closed_only``; needs the fit and the areas of the table in place."""
+        out = np.zeros(4, np.float64)
+        self._check(self._lib.pct_point_energies(self._h, int(bool(closed_only)), _ptr(out, _f64p)))
+        return float(out[0]), float(out[1]), float(out[2]), int(out[3])
 
     def voxel_downsample(self, xyz, voxel_size):
         """Indices of the first point of every voxel.  float32 coordinates are binned in float32, everything else in

@@ -240,7 +240,8 @@ void pct_destroy(pct_ctx* ctx) {
                       &ctx->stage_a, &ctx->stage_b, &ctx->stage_c, &ctx->stage_d, &ctx->row_done, &ctx->redo_m, &ctx->flag_buf, &ctx->dens_buf, &ctx->pub_pos, &ctx->pub_dist, &ctx->pub_cnt, &ctx->qpts4, &ctx->qry, &ctx->ball_off, &ctx->ball_idx, &ctx->ball_alt, &ctx->ball_dist, &ctx->fit_flag, &ctx->lvl_src,
                       &ctx->tree_codes, &ctx->tree_vals, &ctx->tree_lvl, &ctx->tree_head, &ctx->tree_marks, &ctx->tree_seg, &ctx->tree_runs, &ctx->tree_range, &ctx->tree_bucket, &ctx->tree_tmp,
                       &ctx->pca, &ctx->pca_aux, &ctx->pca_nbr, &ctx->pca_orig,
-                      &ctx->bin_rec, &ctx->bin_mat, &ctx->bin_plan, &ctx->bin_base};
+                      &ctx->bin_rec, &ctx->bin_mat, &ctx->bin_plan, &ctx->bin_base,
+                      &ctx->area, &ctx->area_closed, &ctx->area_nverts, &ctx->area_over};
     for (pct_buf* b : all) pct_release(b);
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     for (auto& e : ctx->ev)
@@ -271,6 +272,7 @@ static int new_cloud(pct_ctx* ctx, int64_t n) {
     ctx->grid_valid = ctx->knn_valid = ctx->fit_valid = ctx->pts4_valid = ctx->qpts4_valid = false;
     ctx->pca_valid = false;
     ctx->ball_valid = false;
+    ctx->area_valid = false;
     ctx->has_f64 = false;
     ctx->no_cull = ctx->culled = false;
     ctx->retries = 0;
@@ -339,7 +341,7 @@ int pct_set_query_range(pct_ctx* ctx, int64_t begin, int64_t end) {
     ctx->q_end = end;
     ctx->slab_parts = ctx->slab_part = 0;
     ctx->slab_split_valid = false;
-    ctx->knn_valid = ctx->fit_valid = ctx->grid_valid = false;   // the cell order depends on the owned range
+    ctx->knn_valid = ctx->fit_valid = ctx->area_valid = ctx->grid_valid = false;   // the cell order depends on the owned range
     ctx->no_cull = false;
     ctx->retries = 0;
     return PCT_OK;
@@ -357,7 +359,7 @@ int pct_set_query_slab(pct_ctx* ctx, int32_t part, int32_t parts) {
     ctx->slab_parts = parts >= 1 ? parts : 0;     // (one part: the whole cloud as one slab -- the same code path, for a world of one rank)
     ctx->slab_part = parts >= 1 ? part : 0;
     ctx->slab_split_valid = false;
-    ctx->knn_valid = ctx->fit_valid = ctx->grid_valid = false;
+    ctx->knn_valid = ctx->fit_valid = ctx->area_valid = ctx->grid_valid = false;
     ctx->no_cull = false;
     ctx->retries = 0;
     return PCT_OK;
@@ -545,7 +547,7 @@ static int run_knn(pct_ctx* ctx, int32_t k, double eps, int32_t asked, const int
     const int32_t algo = rq.algo;
     RouteSwitches sw = {false, false};             // (they matter to PCT_KNN_AUTO only)
     if (rq.auto_req) sw = RouteSwitches{pct_getenv("PCT_NO_TREE") != nullptr, pct_getenv("PCT_NO_AUTO_LEVELS") != nullptr};
-    ctx->knn_valid = ctx->fit_valid = false;
+    ctx->knn_valid = ctx->fit_valid = ctx->area_valid = false;     // a new planting drops the fit and the areas
     ctx->k = k;
     ctx->eps = eps;
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_CALL_BEGIN], ctx->stream));
@@ -1100,6 +1102,87 @@ int pct_get_fit(pct_ctx* ctx, int64_t begin, int64_t end, float* coefs, float* K
     if (K) PCT_HIP(ctx, hipMemcpyAsync(K, (float*)ctx->K.p + off, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     if (H) PCT_HIP(ctx, hipMemcpyAsync(H, (float*)ctx->H.p + off, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     if (H2) PCT_HIP(ctx, hipMemcpyAsync(H2, (float*)ctx->H2.p + off, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PCT_OK;
+}
+
+// ---- per-point tangent-plane Voronoi areas and the energies over them (pct_area.hip) --------------------------------------
+int pct_point_areas(pct_ctx* ctx) {
+    PCT_TRY(begin_call(ctx));
+    PCT_TRY(refuse_in_slab_mode(ctx, "pct_point_areas"));
+    if (!ctx->knn_valid) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "plant the neighbour table first (pct_knn)");
+    ctx->area_valid = false;
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_AREA_BEGIN], ctx->stream));
+    PCT_TRY(pct_launch_point_areas(ctx));
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_AREA_END], ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));              // the call's one wait: results, statistics words, events
+    const unsigned long long* w = ctx->pin->area_words;
+    ctx->area_rows = ctx->q_end - ctx->q_begin;
+    ctx->area_stats[0] = ctx->area_rows;
+    ctx->area_stats[1] = (int64_t)w[1];
+    ctx->area_stats[2] = (int64_t)w[2];
+    ctx->area_stats[3] = (int64_t)w[0];
+    ctx->area_profile[0] = ev_ms(ctx, PCT_EV_AREA_BEGIN, PCT_EV_AREA_END);
+    ctx->area_profile[1] = (double)w[3];
+    ctx->area_valid = true;
+    return PCT_OK;
+}
+
+// areas in table-row order refer to the table they were taken from
+static bool areas_resident(const pct_ctx* ctx) { return ctx->area_valid && (!ctx->area_row_order || ctx->knn_valid); }
+
+int pct_get_point_areas(pct_ctx* ctx, int64_t begin, int64_t end, double* area, uint8_t* closed, int32_t* nverts) {
+    PCT_TRY(begin_call(ctx));
+    PCT_TRY(refuse_in_slab_mode(ctx, "pct_get_point_areas"));
+    if (!areas_resident(ctx)) return pct_fail(ctx, PCT_ERR_INVALID, "no point areas (pct_point_areas)");
+    if (begin < ctx->q_begin || end > ctx->q_begin + ctx->area_rows || begin > end)
+        return pct_fail(ctx, PCT_ERR_INVALID, "rows [%lld,%lld) outside the owned range", (long long)begin, (long long)end);
+    const int64_t rows = end - begin, off = begin - ctx->q_begin;
+    if (rows == 0) return PCT_OK;
+    const double* d_a = (const double*)ctx->area.p + off;
+    const unsigned char* d_c = (const unsigned char*)ctx->area_closed.p + off;
+    const int* d_n = (const int*)ctx->area_nverts.p + off;
+    if (ctx->area_row_order) {          // table-row order: gather the requested public rows first
+        PCT_TRY(pct_reserve(ctx, &ctx->stage_a, (size_t)rows * sizeof(double)));
+        PCT_TRY(pct_reserve(ctx, &ctx->stage_b, (size_t)rows * sizeof(int)));
+        PCT_TRY(pct_reserve(ctx, &ctx->stage_c, (size_t)rows));
+        PCT_TRY(pct_launch_gather_areas(ctx, off, rows, area ? (double*)ctx->stage_a.p : nullptr, closed ? (unsigned char*)ctx->stage_c.p : nullptr,
+                                        nverts ? (int*)ctx->stage_b.p : nullptr));
+        d_a = (const double*)ctx->stage_a.p;
+        d_n = (const int*)ctx->stage_b.p;
+        d_c = (const unsigned char*)ctx->stage_c.p;
+    }
+    if (area) PCT_HIP(ctx, hipMemcpyAsync(area, d_a, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (closed) PCT_HIP(ctx, hipMemcpyAsync(closed, d_c, (size_t)rows, hipMemcpyDeviceToHost, ctx->stream));
+    if (nverts) PCT_HIP(ctx, hipMemcpyAsync(nverts, d_n, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PCT_OK;
+}
+
+int pct_point_area_stats(pct_ctx* ctx, int64_t out[4]) {
+    if (!ctx || !out) return PCT_ERR_INVALID;
+    for (int i = 0; i < 4; ++i) out[i] = ctx->area_valid ? ctx->area_stats[i] : 0;
+    return PCT_OK;
+}
+
+int pct_point_area_profile(pct_ctx* ctx, double out[2]) {
+    if (!ctx || !out) return PCT_ERR_INVALID;
+    for (int i = 0; i < 2; ++i) out[i] = ctx->area_valid ? ctx->area_profile[i] : 0.0;
+    return PCT_OK;
+}
+
+int pct_point_energies(pct_ctx* ctx, int32_t closed_only, double out[4]) {
+    PCT_TRY(begin_call(ctx));
+    PCT_TRY(refuse_in_slab_mode(ctx, "pct_point_energies"));
+    if (!out) return pct_fail(ctx, PCT_ERR_INVALID, "null result");
+    const int64_t rows = ctx->q_end - ctx->q_begin;
+    if (!ctx->fit_valid || !ctx->fit_cloud_aligned || ctx->fit_rows != rows) return pct_fail(ctx, PCT_ERR_INVALID, "no fit results");
+    if (!areas_resident(ctx) || ctx->area_rows != rows) return pct_fail(ctx, PCT_ERR_INVALID, "no point areas (pct_point_areas)");
+    const int nblk = 1024;
+    PCT_TRY(pct_reserve(ctx, &ctx->stage_d, ((size_t)nblk * 4 + 4) * sizeof(double)));
+    double* d_part = (double*)ctx->stage_d.p;
+    PCT_TRY(pct_launch_point_energies(ctx, closed_only != 0, d_part, d_part + (size_t)nblk * 4));
+    PCT_HIP(ctx, hipMemcpyAsync(out, d_part + (size_t)nblk * 4, 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PCT_OK;
 }

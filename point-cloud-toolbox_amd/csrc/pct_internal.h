@@ -113,6 +113,7 @@ struct pct_pinned {
     alignas(32) int tree_counts[26];                 // ... its counts and level histogram
     alignas(512) int slab_cut[PCT_SLAB_PARTS_MAX + 1];
     alignas(512) long long slab_counts[PCT_SLAB_PARTS_MAX];
+    alignas(64) unsigned long long area_words[8];    // pct_point_areas (pct_area.hip): overflow rows, closed rows, NaN rows, neighbours past the rejection test
 };
 static_assert(sizeof(pct_pinned) <= 4096, "pct_create allocates 4096 bytes");
 
@@ -122,6 +123,7 @@ enum pct_event {                           // ctx->ev
     PCT_EV_FIT_BEGIN, PCT_EV_FIT_END,      // a fit (a fused call records its end only)
     PCT_EV_FAST_END,                       // end of the fast sweep, the dominant kernel
     PCT_EV_SCAN_TOTALS,                    // the cell list's scan totals are in pinned memory (pct_build_grid)
+    PCT_EV_AREA_BEGIN, PCT_EV_AREA_END,    // pct_point_areas
     PCT_EV_COUNT
 };
 
@@ -303,6 +305,17 @@ struct pct_ctx {
     int64_t pca_rows = 0;
 
     pct_timings tm = {};
+
+    // per-point tangent-plane Voronoi areas (pct_area.hip) of the owned rows of the resident table
+    pct_buf area;          // double (owned)
+    pct_buf area_closed;   // uint8 (owned)
+    pct_buf area_nverts;   // int32 (owned)
+    pct_buf area_over;     // eight statistics words, then int32 (owned): the rows redone with room for k + 4 vertices
+    bool area_valid = false;
+    bool area_row_order = false;   // in neighbour-table row order (as fit_row_order), else public order from q_begin
+    int64_t area_rows = 0;
+    int64_t area_stats[4] = {0, 0, 0, 0};   // rows, closed rows, NaN rows, overflow rows
+    double area_profile[2] = {0, 0};        // device milliseconds of the two kernels, neighbours past the rejection test
 };
 
 int pct_fail(pct_ctx* ctx, int code, const char* fmt, ...);
@@ -467,6 +480,11 @@ int pct_ensure_row_of(pct_ctx* ctx);     // before any read of ctx->row_of
 int pct_launch_export_rows(pct_ctx* ctx, const int64_t* d_rows, int64_t n_rows, int32_t* d_idx, float* d_dist, int32_t* d_cnt);
 int pct_launch_mesh_energies(pct_ctx* ctx, const double* d_v, const int* d_tri, int64_t n_tri, const void* d_K, const void* d_H,
                              bool k_f64, bool h_f64, double* d_partial, int nblk, double* d_out);
+// pct_area.hip: areas of the owned rows of the resident table (statistics words to ctx->pin->area_words), their public
+// rows gathered out of table-row order, and the energies over them: d_out4 = {bending, stretching, area, rows used}
+int pct_launch_point_areas(pct_ctx* ctx);
+int pct_launch_gather_areas(pct_ctx* ctx, int64_t first, int64_t rows, double* d_area, unsigned char* d_closed, int* d_nverts);
+int pct_launch_point_energies(pct_ctx* ctx, bool closed_only, double* d_partial, double* d_out4);
 int pct_voxel_downsample_device(pct_ctx* ctx, const void* d_xyz, bool f64, int64_t n, double voxel, int64_t* d_out, int64_t* count);
 int pct_launch_surface_variation(pct_ctx* ctx, float* d_out);
 // PCA principal curvatures (pct_pca.hip).  The sweep fetches up to PCT_PCA_EXTRA candidates beyond k per point, re-ranked

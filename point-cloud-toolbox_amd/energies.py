@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _capi
 
-__all__ = ["mesh_energies", "load_mesh_compute_energies"]
+__all__ = ["mesh_energies", "point_energies", "load_mesh_compute_energies"]
 
 
 def mesh_energies(vertices, triangles, gaussian_curvature, mean_curvature, device=0):
@@ -20,6 +20,22 @@ def mesh_energies(vertices, triangles, gaussian_curvature, mean_curvature, devic
     h = _capi.Handle(device)
     try:
         return h.mesh_energies(vertices, triangles, gaussian_curvature, mean_curvature)
+    finally:
+        h.close()
+
+
+def point_energies(points, k, eps=None, closed_only=False, device=0):
+    """(bending_energy, stretching_energy, total_area) of a point cloud without a mesh: k-NN, quadric fit and per-point
+    tangent-plane Voronoi areas on the device, then ``calculate_energies`` (pointCloudToolbox.py:650-655) over them
+    (``pct_point_energies``).  ``closed_only``: the cells bounded by their own neighbourhood only -- on an open surface
+    the rim's cells are not."""
+    pts = np.asarray(points)
+    h = _capi.Handle(device)
+    try:
+        h.set_points(pts if pts.dtype == np.float64 else pts.astype(np.float32, copy=False))
+        h.curvature(int(k), eps or 0.0)
+        h.point_areas()
+        return h.point_energies(closed_only)[:3]
     finally:
         h.close()
 

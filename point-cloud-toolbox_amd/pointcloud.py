@@ -191,6 +191,8 @@ class PointCloud:
         self._device_curv = None
         self._plant_token = 0
         self._fit_token = -1
+        self._area_token = -1           # the planting whose per-point areas are on the device
+        self._area_cache = None
         self.eps = None
         self.collect_stats = False      # sweep statistics in last_timings (costs atomics)
 
@@ -389,6 +391,65 @@ class PointCloud:
         self.fit_explicit_quadratic_surfaces_to_neighborhoods()
         K, H = self.calculate_curvatures_of_explicit_quadratic_surfaces_for_all_points()
         return np.array(K), np.array(H)
+
+    # ------------------------------------------------ mesh-free energies: the voronoi_areas of pct:650-655
+    def _planted_table(self):
+        """The handle, where the table of the last ``plant_kdtree`` is resident and is the one a fit would read."""
+        if self._handle is None or not self._table_on_device:
+            raise AttributeError("'PointCloud' object has no attribute 'neighbor_indices'")      # plant_kdtree first
+        if self._user_neighbors is not None:
+            raise ValueError("per-point areas are taken from the planted neighbour table, not from assigned neighbor_indices")
+        return self._handle
+
+    def _areas_on_device(self):
+        return self._handle is not None and self._table_on_device and getattr(self, "_area_token", -1) == self._plant_token
+
+    def compute_voronoi_areas(self):
+        """Per-point area weights without a mesh: the area of every point's Voronoi cell in its own tangent plane, from the
+        neighbourhoods of the last ``plant_kdtree`` and the device cloud of that planting (``pct_point_areas``,
+        include/pct_hip.h) -- the ``voronoi_areas`` the reference's ``calculate_energies`` (pct:650-655) takes and nothing
+        in it produces.  Returns (N,) float64; NaN for rows of fewer than two neighbours.  ``cells_closed`` tells the
+        cells that the neighbourhood bounds on every side from those it leaves open (the rim of an open surface, k too small)."""
+        h = self._planted_table()
+        h.point_areas()
+        self._area_token = self._plant_token
+        self._area_cache = None
+        self.last_area_stats = h.point_area_stats()
+        return self.voronoi_areas
+
+    def _download_areas(self):
+        if not self._areas_on_device():
+            self.compute_voronoi_areas()
+        if self._area_cache is None:
+            self._area_cache = self._handle.get_point_areas(0, self._n_dev, nverts=False)[:2]
+        return self._area_cache
+
+    @property
+    def voronoi_areas(self):
+        """(N,) float64, computed on first access after a planting and kept until the next one."""
+        return self._download_areas()[0]
+
+    @property
+    def cells_closed(self):
+        """(N,) bool: the cell is bounded by the point's own neighbours."""
+        return self._download_areas()[1].astype(bool)
+
+    def compute_point_energies(self, closed_only=False):
+        """``(bending, stretching, area)`` of the cloud without a mesh: sum (h ** 2) * area and sum k * area (pct:652-653)
+        over the per-point areas, and their sum, in float64 on the device -- over the rows whose area, K and H are no NaN,
+        the closed cells only with ``closed_only``.  Runs the fit and the areas where they are not resident for the
+        planted table; three doubles come back."""
+        h = self._planted_table()
+        if not (self._fit_on_device and self._fit_token == self._plant_token and self._user_coefs is None):
+            self.fit_explicit_quadratic_surfaces_to_neighborhoods()
+            h = self._planted_table()
+        if not self._areas_on_device():
+            h.point_areas()
+            self._area_token = self._plant_token
+            self._area_cache = None
+            self.last_area_stats = h.point_area_stats()
+        bending, stretching, area, _ = h.point_energies(closed_only)
+        return bending, stretching, area
 
     def export_ply_with_curvatures(self, filename='output_with_curvatures.ply'):
         """The ASCII PLY validate_shape writes after the curvature step (utils.py:538-551), same bytes."""
