@@ -47,15 +47,18 @@ enum pct_knn_algo {
                                  spans a decade or more                                  */
 };
 
-/* Per-stage device times of the most recent call, hipEvent milliseconds. */
+/* Per-stage device times of the most recent call in milliseconds, from device clock stamps or events: the stages of an
+ * explicit PCT_KNN_GRID / PCT_KNN_GRID_EXACT sweep or fused call are stamped by its own kernels (the device's wall clock
+ * at the entry of the first kernel of every stage and at the end of the last), everything else is bracketed by hipEvents
+ * (PCT_TIME_EVENTS=1: every call). */
 typedef struct pct_timings {
     float upload_ms;          /* H2D of coordinates (0 when device-resident)            */
-    float grid_ms;            /* bounding box + cell sizing + counting sort             */
-    float knn_ms;             /* neighbour sweep kernel(s) only (fast + exact redo)     */
-    float knn_fast_ms;        /* of which the fast sweep alone: k_knn_pair, k_knn_duo or k_knn_fast, see sweep_variant */
-    float fit_ms;             /* fused plane-align + quadric fit + curvature kernel     */
+    float grid_ms;            /* bounding box + cell sizing + counting sort (device clock stamps or events) */
+    float knn_ms;             /* neighbour sweep kernel(s) only (fast + exact redo) (device clock stamps or events) */
+    float knn_fast_ms;        /* of which the fast sweep alone: k_knn_pair, k_knn_duo or k_knn_fast, see sweep_variant (device clock stamps or events) */
+    float fit_ms;             /* fused plane-align + quadric fit + curvature kernel (device clock stamps or events) */
     float export_ms;          /* sorted-space -> public index translation               */
-    float total_ms;
+    float total_ms;           /* the stages above, first to last (device clock stamps or events) */
     int32_t knn_launches;
     int32_t grid_iters;       /* cell-size refinement passes                            */
     int64_t cells;            /* grid cells                                             */

@@ -92,15 +92,29 @@ static void read_sweep_stats(const pct_sweep_words& w, pct_timings* t) {
     t->redone_queries = (int64_t)w.redone_queries;
 }
 
-// bookkeeping of the pending fused call, whose kernels have finished: timings from its event set, statistics
+// the stage times of a finished sweep or fused call from the pinned stamps of its parity (fit_ms = 0 behind a sweep on its own)
+static void stamp_times(const pct_ctx* ctx, int par, bool sorted, pct_timings* t) {
+    const pct_stage_ms m = pct_stamps_ms(&ctx->pin->stamps[par], ctx->clock_khz);
+    t->grid_ms = m.grid;
+    t->knn_ms = m.knn;
+    t->knn_fast_ms = sorted ? m.knn_fast : 0.f;
+    t->fit_ms = m.fit;
+    t->total_ms = m.total;
+}
+
+// bookkeeping of the pending fused call, whose kernels have finished: timings from its stamps or its event set, statistics
 static void finish_pending(pct_ctx* ctx, const hipEvent_t* ev) {
     pct_timings t = ctx->tm_snap;
     read_sweep_stats(ctx->pin->stats[ctx->pend_par], &t);
-    t.grid_ms = ev_ms(ev, PCT_EV_CALL_BEGIN, PCT_EV_GRID_END);
-    t.knn_ms = ev_ms(ev, PCT_EV_GRID_END, PCT_EV_SWEEP_END);
-    t.knn_fast_ms = ctx->pend_sorted ? ev_ms(ev, PCT_EV_GRID_END, PCT_EV_FAST_END) : 0.f;
-    t.fit_ms = ev_ms(ev, PCT_EV_SWEEP_END, PCT_EV_FIT_END);
-    t.total_ms = ev_ms(ev, PCT_EV_CALL_BEGIN, PCT_EV_FIT_END);
+    if (ctx->pend_stamped) {
+        stamp_times(ctx, ctx->pend_par, ctx->pend_sorted, &t);
+    } else {
+        t.grid_ms = ev_ms(ev, PCT_EV_CALL_BEGIN, PCT_EV_GRID_END);
+        t.knn_ms = ev_ms(ev, PCT_EV_GRID_END, PCT_EV_SWEEP_END);
+        t.knn_fast_ms = ctx->pend_sorted ? ev_ms(ev, PCT_EV_GRID_END, PCT_EV_FAST_END) : 0.f;
+        t.fit_ms = ev_ms(ev, PCT_EV_SWEEP_END, PCT_EV_FIT_END);
+        t.total_ms = ev_ms(ev, PCT_EV_CALL_BEGIN, PCT_EV_FIT_END);
+    }
     t.fit_svd_rows = ctx->pin->svd_rows[ctx->pend_par];
     ctx->tm_done = t;
     ctx->pending = false;
@@ -225,6 +239,9 @@ int pct_create(int device, pct_ctx** out) {
         return PCT_ERR_OOM;
     }
     memset(ctx->pin, 0, 4096);
+    // ticks of the device's wall clock per millisecond, for the calls timed by stamps (unknown: every call keeps its events)
+    if (hipDeviceGetAttribute(&ctx->clock_khz, hipDeviceAttributeWallClockRate, device) != hipSuccess || ctx->clock_khz < 0) ctx->clock_khz = 0;
+    (void)hipGetLastError();
     *out = ctx;
     return PCT_OK;
 }
@@ -241,7 +258,7 @@ void pct_destroy(pct_ctx* ctx) {
                       &ctx->tree_codes, &ctx->tree_vals, &ctx->tree_lvl, &ctx->tree_head, &ctx->tree_marks, &ctx->tree_seg, &ctx->tree_runs, &ctx->tree_range, &ctx->tree_bucket, &ctx->tree_tmp,
                       &ctx->pca, &ctx->pca_aux, &ctx->pca_nbr, &ctx->pca_orig,
                       &ctx->bin_rec, &ctx->bin_mat, &ctx->bin_plan, &ctx->bin_base,
-                      &ctx->area, &ctx->area_closed, &ctx->area_nverts, &ctx->area_over};
+                      &ctx->area, &ctx->area_closed, &ctx->area_nverts, &ctx->area_over, &ctx->stamp_tickets};
     for (pct_buf* b : all) pct_release(b);
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     for (auto& e : ctx->ev)
@@ -525,12 +542,25 @@ static int examine_uniform_list(pct_ctx* ctx, int32_t k, bool tree_reachable, Ro
     return PCT_OK;
 }
 
-// Neighbour sweep without timing bookkeeping; events CALL_BEGIN | GRID_END | SWEEP_END bracket cell list and sweep.
+// A sweep on its own, timed by stamps, has no fit kernel behind it to end the call: one thread, whose start is the end of the sweep.
+__global__ void k_stamp_end(const unsigned long long* __restrict__ dev, unsigned long long* __restrict__ pin) {
+    const unsigned long long now = wall_clock64();
+    for (int i = 0; i < PCT_ST_SWEEP_END; ++i) pin[i] = dev[i];
+    pin[PCT_ST_SWEEP_END] = now;
+    __hip_atomic_store(&pin[PCT_ST_CALL_END], now, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// Neighbour sweep without timing bookkeeping; events CALL_BEGIN | GRID_END | SWEEP_END bracket cell list and sweep --
+// or, *stamped, none does: the route was certain before the first launch (an explicit PCT_KNN_GRID / PCT_KNN_GRID_EXACT
+// request, no slab) and the build's first launch took the begin stamp, so the kernels stamp the device words of parity
+// par and whatever follows the sweep (fused_tail, pct_knn) ends the call into the pinned ones (pct_stamp.h).
+// PCT_TIME_EVENTS=1 keeps the events (A/B runs); stamped = null: the caller reads events.
 // fuse_par: the fused call -- its fit reads no distances, and the passes of a chained sweep fit their rows into the pinned slots of this parity.
-static int run_knn(pct_ctx* ctx, int32_t k, double eps, int32_t asked, const int* fuse_par = nullptr, SweepDone* done = nullptr) {
+static int run_knn(pct_ctx* ctx, int32_t k, double eps, int32_t asked, bool* stamped, const int* fuse_par = nullptr, SweepDone* done = nullptr) {
     SweepDone unread;
     if (!done) done = &unread;
     *done = SweepDone{};
+    if (stamped) *stamped = false;
     const bool want_dist = fuse_par == nullptr;
     // 1. the request
     if (ctx->n <= 0) return pct_fail(ctx, PCT_ERR_INVALID, "no cloud loaded");
@@ -550,7 +580,21 @@ static int run_knn(pct_ctx* ctx, int32_t k, double eps, int32_t asked, const int
     ctx->knn_valid = ctx->fit_valid = ctx->area_valid = false;     // a new planting drops the fit and the areas
     ctx->k = k;
     ctx->eps = eps;
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_CALL_BEGIN], ctx->stream));
+    const int par = fuse_par ? *fuse_par : 0;
+    bool stamps = stamped && pct_stamps_apply(rq.auto_req, algo == PCT_KNN_GRID || algo == PCT_KNN_GRID_EXACT, ctx->slab_parts >= 1,
+                                              ctx->q_end - ctx->q_begin, ctx->clock_khz, pct_getenv("PCT_TIME_EVENTS") != nullptr);
+    CallBegin begin = {};
+    if (stamps) {
+        PCT_TRY(pct_reserve(ctx, &ctx->counters, sizeof(pct_dev_words)));
+        PCT_TRY(pct_reserve(ctx, &ctx->stamp_tickets, (size_t)kStampTicketLines * kStampTicketStride * sizeof(unsigned)));
+        if (ctx->stamp_tickets.p != ctx->stamp_tickets_seen) {        // (once per allocation: the last block out leaves the tickets at zero)
+            PCT_HIP(ctx, hipMemsetAsync(ctx->stamp_tickets.p, 0, (size_t)kStampTicketLines * kStampTicketStride * sizeof(unsigned), ctx->stream));
+            ctx->stamp_tickets_seen = ctx->stamp_tickets.p;
+        }
+        ctx->pin->stamps[par].t[PCT_ST_CALL_END] = 0ull;        // "finished" is this word non-zero
+        begin = CallBegin{&pct_dev(ctx)->stamps[par].t[PCT_ST_CALL_BEGIN], ctx->ev[PCT_EV_CALL_BEGIN], false, false};
+    }
+    if (!stamps) PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_CALL_BEGIN], ctx->stream));
     ctx->tm.levels = 0;
     ctx->tm.sweep_variant = 0;         // (set by the fast sweep's launch, pct_knn.hip)
     ctx->tm.algo = algo;
@@ -569,7 +613,8 @@ static int run_knn(pct_ctx* ctx, int32_t k, double eps, int32_t asked, const int
     // 3. the uniform list (PCT_KNN_GRID, PCT_KNN_GRID_EXACT) -- and whether PCT_KNN_AUTO keeps it
     const bool tree_reachable = may_give_up(rq, ctx->n, sw);
     GridVerdict built;
-    PCT_TRY(pct_build_grid(ctx, k, eps, tree_reachable, &built));
+    PCT_TRY(pct_build_grid(ctx, k, eps, tree_reachable, &built, stamps ? &begin : nullptr));
+    stamps = stamps && begin.stamped;          // (else the build has recorded PCT_EV_CALL_BEGIN in front of its first launch)
     Route route = built == GridVerdict::GaveUp ? Route::Tree : Route::Stay;      // (not built: far too many cells per point)
     if (built == GridVerdict::Built && skew_gate(rq, whole, ctx->n, ctx->nonempty_cells, sw)) {
         PCT_TRY(examine_uniform_list(ctx, k, tree_reachable, &route));
@@ -585,9 +630,10 @@ static int run_knn(pct_ctx* ctx, int32_t k, double eps, int32_t asked, const int
     }
     if (route == Route::Levels) return sweep_levels(ctx, k, eps, fuse_par, done);
     // 4. the sweep
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_GRID_END], ctx->stream));
-    PCT_TRY(pct_launch_knn_grid(ctx, k, eps, algo == PCT_KNN_GRID_EXACT, 0, want_dist));
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_SWEEP_END], ctx->stream));
+    if (!stamps) PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_GRID_END], ctx->stream));
+    PCT_TRY(pct_launch_knn_grid(ctx, k, eps, algo == PCT_KNN_GRID_EXACT, 0, want_dist, stamps ? pct_dev(ctx)->stamps[par].t : nullptr));
+    if (!stamps) PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_SWEEP_END], ctx->stream));
+    if (stamped) *stamped = stamps;
     ctx->tm.knn_launches = 1;
     ctx->knn_valid = true;
     ctx->knn_hier = false;
@@ -595,20 +641,23 @@ static int run_knn(pct_ctx* ctx, int32_t k, double eps, int32_t asked, const int
 }
 
 // The fused call's tail behind its sweep: the fit (where the passes of a chained sweep have not fitted their rows), its end
-// event, and the sweep's statistics words into pinned slot `par` -- mirrored by the fit kernel, else copied.
-// (no event of its own for the start of the fit: it starts where the sweep's last event, PCT_EV_SWEEP_END, was recorded --
-// every event record is a marker packet between two kernels, ~3 us of dispatch gap)
-static int fused_tail(pct_ctx* ctx, int par, const SweepDone& swept) {
+// -- stamped: by the last block out of k_fit_svd, else an event --, and the sweep's statistics words into pinned slot `par`
+// -- mirrored by the fit kernel, else copied.
+// (a call timed by events has none for the start of the fit: it starts where the sweep's last event, PCT_EV_SWEEP_END, was
+// recorded -- every event record is a marker packet between two kernels, ~3 us of dispatch gap; a stamped call has no marker
+// on its chain at all)
+static int fused_tail(pct_ctx* ctx, int par, const SweepDone& swept, bool stamped) {
     bool mirrored = false;
-    if (!swept.rows_fitted) PCT_TRY(pct_launch_fit_table(ctx, FitSlot{par, true}, &mirrored));
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_END], ctx->stream));
+    if (!swept.rows_fitted) PCT_TRY(pct_launch_fit_table(ctx, FitSlot{par, true, stamped}, &mirrored));
+    if (!stamped) PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_END], ctx->stream));
     if (!mirrored)                // (no fit kernel ran: the chained sweep fitted its passes itself, or there are no rows)
         PCT_HIP(ctx, hipMemcpyAsync(&ctx->pin->stats[par], ctx->counters.p, sizeof(pct_sweep_words), hipMemcpyDeviceToHost, ctx->stream));
     return PCT_OK;
 }
 
 // words_enqueued: the fused tail has sent the statistics words to pinned slot 0 already
-static int finish_knn_stats(pct_ctx* ctx, bool words_enqueued, bool* beyond_limits) {
+// stamped: the call's times come from the pinned stamps of parity 0 (fit_ms and total_ms with them)
+static int finish_knn_stats(pct_ctx* ctx, bool words_enqueued, bool stamped, bool* beyond_limits) {
     pct_sweep_words& w = ctx->pin->stats[0];                             // pinned: a plain DMA, no staging
     if (!words_enqueued) PCT_HIP(ctx, hipMemcpyAsync(&w, ctx->counters.p, sizeof(w), hipMemcpyDeviceToHost, ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -616,9 +665,13 @@ static int finish_knn_stats(pct_ctx* ctx, bool words_enqueued, bool* beyond_limi
     if (pct_getenv("PCT_TREE_DEBUG") && ctx->collect_stats)
         fprintf(stderr, "[tree] redone %llu, up-levelled %llu, candidate steps %llu, costliest exact query: %llu steps (row %llu)\n", w.redone_queries,
                 w.ring_fallbacks, w.candidate_steps, w.costliest >> 32, w.costliest & 0xffffffffull);
-    ctx->tm.grid_ms = ev_ms(ctx, PCT_EV_CALL_BEGIN, PCT_EV_GRID_END);
-    ctx->tm.knn_ms = ev_ms(ctx, PCT_EV_GRID_END, PCT_EV_SWEEP_END);
-    ctx->tm.knn_fast_ms = ctx->knn_sorted_space ? ev_ms(ctx, PCT_EV_GRID_END, PCT_EV_FAST_END) : 0.f;
+    if (stamped) {
+        stamp_times(ctx, 0, ctx->knn_sorted_space, &ctx->tm);
+    } else {
+        ctx->tm.grid_ms = ev_ms(ctx, PCT_EV_CALL_BEGIN, PCT_EV_GRID_END);
+        ctx->tm.knn_ms = ev_ms(ctx, PCT_EV_GRID_END, PCT_EV_SWEEP_END);
+        ctx->tm.knn_fast_ms = ctx->knn_sorted_space ? ev_ms(ctx, PCT_EV_GRID_END, PCT_EV_FAST_END) : 0.f;
+    }
     // a sharded handle that left far points out of its grid met a query those points could matter to
     *beyond_limits = ctx->knn_sorted_space && ctx->culled && w.beyond_limits > 0;
     ctx->tm.limit_retries = ctx->retries;
@@ -634,16 +687,19 @@ static void retry_without_cull(pct_ctx* ctx) {
 
 int pct_knn(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
     PCT_TRY(begin_call(ctx));
-    bool again = false;
-    PCT_TRY(run_knn(ctx, k, eps, algo));
-    PCT_TRY(finish_knn_stats(ctx, false, &again));
-    if (again) {
+    bool again = false, stamped = false;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        PCT_TRY(run_knn(ctx, k, eps, algo, &stamped));
+        if (stamped) {
+            PCT_LAUNCH(k_stamp_end, dim3(1), dim3(1), 0, ctx->stream, (const unsigned long long*)pct_dev(ctx)->stamps[0].t, ctx->pin->stamps[0].t);
+            PCT_HIP(ctx, hipGetLastError());
+        }
+        PCT_TRY(finish_knn_stats(ctx, false, stamped, &again));
+        if (!again) break;
         retry_without_cull(ctx);
-        PCT_TRY(run_knn(ctx, k, eps, algo));
-        PCT_TRY(finish_knn_stats(ctx, false, &again));
     }
     ctx->tm.fit_ms = 0;
-    ctx->tm.total_ms = ev_ms(ctx, PCT_EV_CALL_BEGIN, PCT_EV_SWEEP_END);
+    if (!stamped) ctx->tm.total_ms = ev_ms(ctx, PCT_EV_CALL_BEGIN, PCT_EV_SWEEP_END);
     return PCT_OK;
 }
 
@@ -680,11 +736,12 @@ static void swap_event_sets(pct_ctx* ctx) {
 static int curvature_async(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
     const bool had = ctx->pending;
     if (had) swap_event_sets(ctx);          // the pending call keeps its timing events; this one records into the other set
-    const int par = had ? ctx->pend_par ^ 1 : 0;
+    const int par = pct_next_parity(had, ctx->pend_par);
     ctx->retries = 0;
     SweepDone swept;
-    int st = run_knn(ctx, k, eps, algo, &par, &swept);
-    if (st == PCT_OK) st = fused_tail(ctx, par, swept);
+    bool stamped = false;
+    int st = run_knn(ctx, k, eps, algo, &stamped, &par, &swept);
+    if (st == PCT_OK) st = fused_tail(ctx, par, swept, stamped);
     if (st != PCT_OK) {            // leave the handle in the plain state: nothing pending, events where they were
         (void)hipStreamSynchronize(ctx->stream);
         if (had) {
@@ -694,8 +751,13 @@ static int curvature_async(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
         return st;
     }
     if (had) {
-        // its kernels lie in front of this call's mid-build wait on the stream: normally long finished (checked, not assumed)
-        if (hipEventQuery(ctx->ev_prev[PCT_EV_FIT_END]) != hipSuccess) (void)hipEventSynchronize(ctx->ev_prev[PCT_EV_FIT_END]);
+        // its kernels lie in front of this call's mid-build wait on the stream: normally long finished (checked, not assumed:
+        // its end stamp is in pinned memory, or its end event has been passed)
+        if (ctx->pend_stamped) {
+            if (!pct_stamps_finished(&ctx->pin->stamps[ctx->pend_par])) (void)hipStreamSynchronize(ctx->stream);
+        } else if (hipEventQuery(ctx->ev_prev[PCT_EV_FIT_END]) != hipSuccess) {
+            (void)hipEventSynchronize(ctx->ev_prev[PCT_EV_FIT_END]);
+        }
         (void)hipGetLastError();
         finish_pending(ctx, ctx->ev_prev);
     }
@@ -703,6 +765,7 @@ static int curvature_async(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
     ctx->tm_snap = ctx->tm;
     ctx->pend_par = par;
     ctx->pend_sorted = ctx->knn_sorted_space;
+    ctx->pend_stamped = stamped;
     ctx->pending = true;
     ctx->fit_rows = ctx->q_end - ctx->q_begin;
     ctx->fit_valid = true;
@@ -717,19 +780,22 @@ int pct_curvature(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
                        !ctx->collect_stats;
     PCT_TRY(begin_call(ctx, !async));
     if (async) return curvature_async(ctx, k, eps, algo);
+    bool stamped = false;
     for (int attempt = 0; attempt < 2; ++attempt) {
         bool again = false;
         const int par = 0;
         SweepDone swept;
-        PCT_TRY(run_knn(ctx, k, eps, algo, &par, &swept));
-        PCT_TRY(fused_tail(ctx, par, swept));
-        PCT_TRY(finish_knn_stats(ctx, true, &again));
+        PCT_TRY(run_knn(ctx, k, eps, algo, &stamped, &par, &swept));
+        PCT_TRY(fused_tail(ctx, par, swept, stamped));
+        PCT_TRY(finish_knn_stats(ctx, true, stamped, &again));
         if (!again) break;
         retry_without_cull(ctx);
     }
-    ctx->tm.fit_ms = ev_ms(ctx, PCT_EV_SWEEP_END, PCT_EV_FIT_END);            // (the fit starts where the sweep's last event was recorded)
+    if (!stamped) {
+        ctx->tm.fit_ms = ev_ms(ctx, PCT_EV_SWEEP_END, PCT_EV_FIT_END);        // (the fit starts where the sweep's last event was recorded)
+        ctx->tm.total_ms = ev_ms(ctx, PCT_EV_CALL_BEGIN, PCT_EV_FIT_END);
+    }
     ctx->tm.fit_svd_rows = ctx->pin->svd_rows[0];
-    ctx->tm.total_ms = ev_ms(ctx, PCT_EV_CALL_BEGIN, PCT_EV_FIT_END);
     ctx->tm_done = ctx->tm;
     ctx->fit_rows = ctx->q_end - ctx->q_begin;
     ctx->fit_valid = true;
@@ -1347,11 +1413,11 @@ int pct_surface_variation(pct_ctx* ctx, int32_t k_total, float* out) {
     const int64_t rows = ctx->q_end - ctx->q_begin;
     for (int attempt = 0; attempt < 2; ++attempt) {
         bool again = false;
-        PCT_TRY(run_knn(ctx, k_total - 1, 0.0, PCT_KNN_AUTO));        // k-1 neighbours + the point itself (utils.py:812-814)
+        PCT_TRY(run_knn(ctx, k_total - 1, 0.0, PCT_KNN_AUTO, nullptr));        // k-1 neighbours + the point itself (utils.py:812-814)
         PCT_TRY(pct_reserve(ctx, &ctx->K, (size_t)rows * sizeof(float)));
         PCT_TRY(pct_launch_surface_variation(ctx, (float*)ctx->K.p));
         PCT_HIP(ctx, hipMemcpyAsync(out, ctx->K.p, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        PCT_TRY(finish_knn_stats(ctx, false, &again));
+        PCT_TRY(finish_knn_stats(ctx, false, false, &again));
         if (!again) break;
         retry_without_cull(ctx);
     }
@@ -1381,8 +1447,8 @@ int pct_pca_curvatures(pct_ctx* ctx, int32_t k, int32_t algo, int32_t keep_neigh
     const int64_t room = (PCT_K_MAX < ctx->n - 1 ? PCT_K_MAX : ctx->n - 1) - kk;
     const int32_t kc = (int32_t)(kk + (room < PCT_PCA_EXTRA ? room : PCT_PCA_EXTRA));
     bool again = false;
-    if (st == PCT_OK) st = run_knn(ctx, kc, 0.0, algo);
-    if (st == PCT_OK) st = finish_knn_stats(ctx, false, &again);     // (whole clouds: nothing was left out of the cell list)
+    if (st == PCT_OK) st = run_knn(ctx, kc, 0.0, algo, nullptr);      // (timed by events: the PCA kernels follow)
+    if (st == PCT_OK) st = finish_knn_stats(ctx, false, false, &again);     // (whole clouds: nothing was left out of the cell list)
     const int rs = pct_pca_restore(ctx);
     PCT_TRY(st);
     PCT_TRY(rs);

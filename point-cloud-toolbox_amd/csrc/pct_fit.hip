@@ -47,6 +47,7 @@ template <bool F64, bool OUT64 = false, bool STAGED = true, bool MASKED = false>
 __global__ __launch_bounds__(kFitBlock) void k_fit(FitArgs a) {
     extern __shared__ int s_idx[];   // 64 rows x kp
     const int lane = threadIdx.x;
+    if (a.stamps) pct_stamp(&a.stamps[PCT_ST_SWEEP_END]);
     if (blockIdx.x == 0) {
         if (lane == 0 && a.flag_next) *a.flag_next = 0;
         if (a.stat_dst && lane < 8) ((unsigned long long*)a.stat_dst)[lane] = ((const unsigned long long*)a.stat_src)[lane];
@@ -307,6 +308,9 @@ template <bool F64, bool OUT64>
 __global__ __launch_bounds__(64) void k_fit_svd(FitArgs a, const int* __restrict__ list, const int* __restrict__ list_count,
                                                 long long* __restrict__ host_count) {
     fit_svd_rows<F64, OUT64>(a, TableRows{}, list, list_count, host_count);
+    // behind the rows redone here: fit_ms covers them.  (The row count block 0 has sent to the host is stored again by the
+    // block that ends the call, in front of the end stamp: a host that sees the stamp reads this call's count.)
+    pct_stamp_last_out(a.stamps, a.stamps_pin, a.stamp_ticket, host_count, (long long)*list_count);
 }
 
 // ---------------------------------------------------------------------------
@@ -449,6 +453,13 @@ int launch(pct_ctx* ctx, const FitArgs& a0, bool f64, FitSlot slot, bool* mirror
         a.stat_src = &pct_dev(ctx)->sweep;
         a.stat_dst = &ctx->pin->stats[slot.par];
         if (mirrored) *mirrored = true;
+    }
+    a.stamps = a.stamps_pin = nullptr;
+    a.stamp_ticket = nullptr;
+    if (slot.stamped) {            // (run_knn has reserved the words and zeroed the ticket)
+        a.stamps = pct_dev(ctx)->stamps[slot.par].t;
+        a.stamps_pin = ctx->pin->stamps[slot.par].t;
+        a.stamp_ticket = (unsigned*)ctx->stamp_tickets.p;
     }
     a.flag_count = (int*)ctx->fit_flag.p + ctx->fit_parity;
     a.flag_next = (int*)ctx->fit_flag.p + (ctx->fit_parity ^ 1);

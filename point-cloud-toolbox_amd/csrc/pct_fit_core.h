@@ -41,6 +41,11 @@ struct FitArgs {
     const int* row_mask;     // MASKED instantiation: only the rows with a non-zero entry are fitted (passes of the density-adaptive sweep)
     int svd_accumulate;      // the count of rows handed to k_fit_svd is ADDED to the host word (the passes of one fused call)
     int force_jacobi;        // PCT_FIT_JACOBI=1: every row's normal through the cyclic Jacobi (A/B runs, route-against-route tests)
+    // a call timed by the device clock (pct_stamp.h), else null: the call's device stamps -- k_fit stamps the end of the
+    // sweep at its entry --, and their pinned mirror and the ticket k_fit_svd's last block out ends the call with
+    unsigned long long* stamps;
+    unsigned long long* stamps_pin;
+    unsigned* stamp_ticket;  // ctx->stamp_tickets
     int blocks_per_xcd;      // blocks are dealt to the 8 XCDs in turn: block b takes rows of block (b % 8) * blocks_per_xcd + b / 8, so
                              // that one XCD's L2 serves neighbouring rows (table rows are in cell order: their neighbours overlap)
 };

@@ -228,7 +228,9 @@ __device__ __forceinline__ int load_four_points(const float* __restrict__ xyz, i
 // (one point per lane and trip: the float4 stores of a wave are 1 KB contiguous; the four-points-per-lane form of the
 // cull / slab passes reads better but scatters these stores over 64 lines per instruction -- 16.7 against 12.7 us)
 __global__ __launch_bounds__(kBlock) void k_pack(const float* __restrict__ xyz, int64_t n,
-                                                 float4* __restrict__ pts4, PackRed* __restrict__ parts) {
+                                                 float4* __restrict__ pts4, PackRed* __restrict__ parts,
+                                                 unsigned long long* __restrict__ begin_stamp) {
+    pct_stamp(begin_stamp);
     const float sh[3] = {0.f, 0.f, 0.f};
     PackAcc acc;
     acc.init();
@@ -830,7 +832,9 @@ __device__ __forceinline__ float4 bin_load(const float* __restrict__ xyz, const 
 template <bool RAW>
 __global__ __launch_bounds__(kBinWide) void k_bin_count(const float* __restrict__ xyz, const float4* __restrict__ pts4, int64_t n,
                                                          int tile_rows, pct_grid g, int shift, int nb,
-                                                         unsigned* __restrict__ mat, PackRed* __restrict__ parts) {
+                                                         unsigned* __restrict__ mat, PackRed* __restrict__ parts,
+                                                         unsigned long long* __restrict__ begin_stamp) {
+    pct_stamp(begin_stamp);
     __shared__ unsigned s_cnt[kBinMaxBuckets];
     for (int b = threadIdx.x; b < nb; b += kBinWide) s_cnt[b] = 0;
     __syncthreads();
@@ -1121,12 +1125,12 @@ static int red_read(pct_ctx* ctx, int n_parts, PackRed* out, float* bbox, bool c
 // every point, public order
 // defer: do not wait for the result (the caller builds on the previous call's box and checks at its next
 // synchronisation, pct_build_grid)
-static int pack_all(pct_ctx* ctx, float* bbox, PackRed* red, bool defer = false) {
+static int pack_all(pct_ctx* ctx, float* bbox, PackRed* red, bool defer = false, unsigned long long* begin_stamp = nullptr) {
     const int64_t n = ctx->n;
     PCT_TRY(pct_reserve(ctx, &ctx->pts4, (size_t)n * sizeof(float4)));
     const int nb = grid_1d(n, kBlock * 4, 512);
     PCT_TRY(red_reset(ctx, nb, false));
-    PCT_LAUNCH(k_pack, dim3(nb), dim3(kBlock), 0, ctx->stream, ctx->xyz_view, n, (float4*)ctx->pts4.p, red_parts(ctx));
+    PCT_LAUNCH(k_pack, dim3(nb), dim3(kBlock), 0, ctx->stream, ctx->xyz_view, n, (float4*)ctx->pts4.p, red_parts(ctx), begin_stamp);
     PCT_HIP(ctx, hipGetLastError());
     if (defer) {
         PCT_TRY(red_fold(ctx, nb, false));
@@ -1359,7 +1363,9 @@ struct GridPoints {
 
 // Decides the source from ctx and runs its pack pass.  *restart: the kept part cannot fill a row; culling is ruled out
 // on the handle and the caller starts over.
-static int select_source(pct_ctx* ctx, int32_t k, double target, bool slab, int64_t n_owned, bool sharded, GridPoints* s, bool* restart) {
+// begin (may be null): the call's start -- stamped by the full pack's kernel, recorded as an event in front of every other pack pass.
+static int select_source(pct_ctx* ctx, int32_t k, double target, bool slab, int64_t n_owned, bool sharded, GridPoints* s, bool* restart,
+                         CallBegin* begin) {
     const bool own_flag = ctx->own_flag != nullptr;
     // (a slab's owned points are found by the pack itself: it always runs, with an open box after a limit retry)
     const bool try_cull = slab ? n_owned > 0
@@ -1373,6 +1379,7 @@ static int select_source(pct_ctx* ctx, int32_t k, double target, bool slab, int6
     *s = GridPoints{};
     s->src = own_flag && ctx->lvl_src_valid ? GridSource::LevelBase : try_cull ? GridSource::CulledPack : spec ? GridSource::CallerRows
                                                                                                                : GridSource::FullPack;
+    if (begin && s->src != GridSource::CallerRows && s->src != GridSource::FullPack) PCT_HIP(ctx, begin->fall_back(ctx->stream));
     switch (s->src) {
     case GridSource::LevelBase:
         for (int a = 0; a < 6; ++a) s->bbox[a] = ctx->lvl_bbox[a];
@@ -1403,7 +1410,7 @@ static int select_source(pct_ctx* ctx, int32_t k, double target, bool slab, int6
         for (int a = 0; a < 6; ++a) s->bbox[a] = ctx->spec_bbox[a];
         break;
     case GridSource::FullPack:
-        PCT_TRY(pack_all(ctx, s->bbox, &s->red));
+        PCT_TRY(pack_all(ctx, s->bbox, &s->red, false, begin ? begin->take() : nullptr));
         PCT_TRY(trim_box(ctx, s->red, s->bbox));
         break;
     }
@@ -1534,9 +1541,9 @@ struct GridPass {
 
 // the two passes over the input tiles, from the caller's rows (RAW) or from packed records
 template <bool RAW>
-static void launch_bin_count(pct_ctx* ctx, int64_t n, const GridPass& p, PackRed* parts) {
+static void launch_bin_count(pct_ctx* ctx, int64_t n, const GridPass& p, PackRed* parts, unsigned long long* begin_stamp) {
     PCT_LAUNCH_T(k_bin_count<RAW>, dim3(p.bs.ntiles), dim3(kBinWide), 0, ctx->stream, ctx->xyz_view, p.src, n, p.bs.tile_rows, p.g, p.bs.shift,
-                 p.bs.nb, (unsigned*)ctx->bin_mat.p, parts);
+                 p.bs.nb, (unsigned*)ctx->bin_mat.p, parts, begin_stamp);
 }
 template <bool RAW>
 static void launch_bin_scatter(pct_ctx* ctx, int64_t n, const GridPass& p, int* cell_oth) {
@@ -1545,13 +1552,15 @@ static void launch_bin_scatter(pct_ctx* ctx, int64_t n, const GridPass& p, int* 
 }
 
 // First half of a pass: per-cell counts of owned / other points in cell_own / cell_oth (and, while the box is deferred,
-// the cloud's PackRed record on its way to pinned memory).
-static int launch_count(pct_ctx* ctx, const GridPoints& s, GridPass& p) {
+// the cloud's PackRed record on its way to pinned memory).  begin (may be null): a call's start that has not been marked
+// yet is stamped by k_bin_count where that is the first launch, else recorded in front of the clearing fills.
+static int launch_count(pct_ctx* ctx, const GridPoints& s, GridPass& p, CallBegin* begin) {
     const pct_grid& g = p.g;
     const int64_t n = s.n;
     const float* own_flag = (const float*)ctx->own_flag;
     const bool bin = p.build == GridBuild::Bin;            // (writes every counter itself: no clearing fill)
     PCT_TRY(pct_reserve(ctx, &ctx->cell_own, (size_t)g.ncell * sizeof(int)));
+    if (begin && !bin) PCT_HIP(ctx, begin->fall_back(ctx->stream));
     if (!bin) PCT_HIP(ctx, hipMemsetAsync(ctx->cell_own.p, 0, (size_t)g.ncell * sizeof(int), ctx->stream));
     if (p.sharded) {
         PCT_TRY(pct_reserve(ctx, &ctx->cell_oth, (size_t)g.ncell * sizeof(int)));
@@ -1563,7 +1572,8 @@ static int launch_count(pct_ctx* ctx, const GridPoints& s, GridPass& p) {
     const int nhb = grid_1d(n, kBlock, 0);
     if (bin) {
         const BinShape& bs = p.bs;
-        s.raw ? launch_bin_count<true>(ctx, n, p, parts) : launch_bin_count<false>(ctx, n, p, parts);
+        unsigned long long* begin_stamp = begin ? begin->take() : nullptr;
+        s.raw ? launch_bin_count<true>(ctx, n, p, parts, begin_stamp) : launch_bin_count<false>(ctx, n, p, parts, begin_stamp);
         PCT_LAUNCH(k_bin_colscan, dim3((bs.nb + kBinScanCols - 1) / kBinScanCols), dim3(kBinScanCols * kBinScanGroups), 0, ctx->stream,
                    (unsigned*)ctx->bin_mat.p, bs.ntiles, bs.nb, p.bin.tot);
         PCT_LAUNCH(k_bin_plan, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned*)p.bin.tot, bs.nb, bs.chunk, p.bin.plan, p.bin.items);
@@ -1709,7 +1719,7 @@ static int commit_grid(pct_ctx* ctx, const GridPoints& s, pct_grid g, const Edge
 // 27-cell stencil (guaranteed radius = one cell edge) contains the k+1 nearest
 // points for nearly every query of a surface-like cloud; the sweep kernel
 // widens ring by ring for the rest.
-int pct_build_grid(pct_ctx* ctx, int32_t k, double eps, bool may_give_up, GridVerdict* out) {
+int pct_build_grid(pct_ctx* ctx, int32_t k, double eps, bool may_give_up, GridVerdict* out, CallBegin* begin) {
     *out = GridVerdict::Built;
     ctx->grid_valid = false;       // (the lists are being rewritten: valid again once a build is committed)
     // measured optima on surface clouds (tools/tune_factor.py): larger cells cost candidates, smaller ones cost
@@ -1743,7 +1753,7 @@ int pct_build_grid(pct_ctx* ctx, int32_t k, double eps, bool may_give_up, GridVe
         const bool sharded = own_flag || ctx->q_begin > 0 || ctx->q_end < ctx->n || slab;   // some points are candidates only
         GridPoints s;
         bool restart = false;
-        PCT_TRY(select_source(ctx, k, target, slab, n_owned, sharded, &s, &restart));
+        PCT_TRY(select_source(ctx, k, target, slab, n_owned, sharded, &s, &restart, begin));
         if (restart) continue;
         const int64_t n = s.n;
         ctx->items_q = items_q;
@@ -1787,7 +1797,7 @@ int pct_build_grid(pct_ctx* ctx, int32_t k, double eps, bool may_give_up, GridVe
             p.bs = bin_allowed ? bin_shape(n, g.ncell, sharded) : BinShape{};
             p.build = choose_build(bin_allowed, p.bs, s);
             const bool bin = p.build == GridBuild::Bin;
-            PCT_TRY(launch_count(ctx, s, p));
+            PCT_TRY(launch_count(ctx, s, p, begin));
             const int nblk = (int)((g.ncell + kScanTile - 1) / kScanTile);
             if (pct_getenv("PCT_GRID_DEBUG"))
                 fprintf(stderr, "[grid] pass %d: n %lld owned %lld edge %g dims %d x %d x %d = %lld cells (%d scan tiles), box [%g %g %g]-[%g %g %g]\n", it,

@@ -8,6 +8,7 @@
 #include <stdlib.h>
 
 #include "../../include/pct_hip.h"
+#include "pct_stamp.h"
 
 #define PCT_WAVE 64
 #define PCT_K_MAX 511           // longest neighbour row: k + 1 <= 512 = 64 lanes x 8 list registers (wave-per-query sweeps, pct_knn_wide.hip)
@@ -89,7 +90,8 @@ struct pct_dev_words {                     // ctx->counters: 512 bytes of device
         pct_sweep_words sweep;
         unsigned long long census[4];      // pct_item_census, between a cell-list build and its sweep
     };
-    unsigned long long unused[24];
+    pct_stamp_block stamps[2];             // by parity of the call: the stage boundaries its kernels stamp (pct_stamp.h)
+    unsigned long long unused[8];
     unsigned long long scatter_hits;       // pct_scatter_records: records that fell into the asked rows
     unsigned long long tail[31];
 };
@@ -97,7 +99,7 @@ static_assert(sizeof(pct_dev_words) == 512, "what every user reserves");
 // ctx->pin: 4 KiB of pinned, device-visible host memory.  Kernels and small copies drop their few result words here, so
 // that a read-back is one stream synchronisation.  One field per read-back; no two share bytes.  A record type that
 // belongs to one file is aligned bytes here, whose size that file asserts.  The fields a kernel stores to directly
-// (scan_totals, stats, svd_rows, tree_totals, slab_cut, slab_counts) are aligned as they always were.
+// (scan_totals, stats, svd_rows, tree_totals, slab_cut, slab_counts, stamps) are aligned as they always were.
 struct pct_pinned {
     alignas(128) unsigned char pack_red[128];        // PackRed, the pack reduction (pct_grid.hip)
     alignas(128) unsigned char scan_totals[32];      // ScanTotals (pct_grid.hip)
@@ -114,9 +116,15 @@ struct pct_pinned {
     alignas(512) int slab_cut[PCT_SLAB_PARTS_MAX + 1];
     alignas(512) long long slab_counts[PCT_SLAB_PARTS_MAX];
     alignas(64) unsigned long long area_words[8];    // pct_point_areas (pct_area.hip): overflow rows, closed rows, NaN rows, neighbours past the rejection test
+    // by parity: the stamps of a call timed by the device clock, mirrored whole by the step's last kernel; the host clears
+    // the end stamp before it enqueues the call and reads the block once that word is non-zero (pct_stamp.h)
+    alignas(64) pct_stamp_block stamps[2];
 };
 static_assert(sizeof(pct_pinned) <= 4096, "pct_create allocates 4096 bytes");
 
+// The five between CALL_BEGIN and FAST_END time the stages of a sweep or a fused call whose route is open when it starts
+// (PCT_KNN_AUTO, the tree, the chained sweep, brute force, slab handles, a build that starts with a pass of its own) or that
+// PCT_TIME_EVENTS=1 asks for; every other PCT_KNN_GRID / PCT_KNN_GRID_EXACT call records none of them (pct_stamp.h).
 enum pct_event {                           // ctx->ev
     PCT_EV_IO_BEGIN, PCT_EV_IO_END,        // an upload or an export
     PCT_EV_CALL_BEGIN, PCT_EV_GRID_END, PCT_EV_SWEEP_END,     // a sweep or a fused call: cell list | sweep | (fused) fit
@@ -143,6 +151,10 @@ struct pct_ctx {
     bool pending = false;          // a fused call has been enqueued and its bookkeeping has not been done
     int pend_par = 0;              // parity of the pending call: which pinned slots its kernels write
     bool pend_sorted = false;      // its table is in a sorted space: knn_fast_ms applies
+    bool pend_stamped = false;     // its times come from the stamps of its parity, not from its event set
+    int clock_khz = 0;             // hipDeviceAttributeWallClockRate: ticks of a stamp per millisecond (0: unknown, calls are timed by events)
+    pct_buf stamp_tickets;         // unsigned (kStampTicketLines lines): blocks of the step's last kernel that have finished (pct_stamp_last_out;
+    void* stamp_tickets_seen = nullptr;   // zero between launches: cleared once per allocation)
     pct_timings tm_snap = {};      // the host-side fields of the pending call's timings
     pct_timings tm_done = {};      // timings of the last call whose bookkeeping has been done
     char err[512] = {0};
@@ -422,7 +434,28 @@ __device__ inline int64_t pct_code_lower_bound(const unsigned long long* __restr
 // What one call asks of another, and what it answers, travels in arguments and results -- never parked on the handle.
 // Which pinned parity slot (statistics mirror, SVD row count) the fits of a call write, and whether its fit kernel may
 // mirror the sweep's statistics words there (the fused call: one copy less in the step's tail).
-struct FitSlot { int par; bool mirror_stats; };
+// stamped: the call is timed by the device clock (pct_stamp.h) -- k_fit stamps the end of the sweep, k_fit_svd the end of the call.
+struct FitSlot { int par; bool mirror_stats; bool stamped; };
+// The start of a call that would rather be timed by device stamps.  The cell-list build hands `slot` to its first launch
+// where that is a kernel with a stamp argument (k_pack, k_bin_count); where it is not -- a cull pass, a level pass, a build
+// with per-point atomics, whose first launch is a memset -- it records `fallback` in front of that launch instead and the
+// call goes on with events.  Used once: a later pass of the cell-size search or a restarted attempt finds it spent.
+struct CallBegin {
+    unsigned long long* slot;      // device word PCT_ST_CALL_BEGIN of the call's parity
+    hipEvent_t fallback;           // PCT_EV_CALL_BEGIN
+    bool spent, stamped;
+    unsigned long long* take() {
+        if (spent) return nullptr;
+        spent = stamped = true;
+        return slot;
+    }
+    hipError_t fall_back(hipStream_t stream) {
+        if (spent) return hipSuccess;
+        spent = true;
+        stamped = false;
+        return hipEventRecord(fallback, stream);
+    }
+};
 enum class GridVerdict { Built, GaveUp };                  // GaveUp: more than 16 cells per point wanted, nothing built
 enum class TreeVerdict { Built, Unusable, OtherCloud };    // Unusable: not a cloud for it; OtherCloud: not the expected box; nothing built
 
@@ -430,9 +463,12 @@ enum class TreeVerdict { Built, Unusable, OtherCloud };    // Unusable: not a cl
 int pct_pack_points(pct_ctx* ctx, float* bbox6);
 int pct_pack_points_f64(pct_ctx* ctx, const double* d_xyz64);
 // may_give_up: PCT_KNN_AUTO on a cloud the hierarchical list could take (pct_auto_route.h)
-int pct_build_grid(pct_ctx* ctx, int32_t k, double eps, bool may_give_up, GridVerdict* out);
-// neighbour sweeps (pct_knn.hip); want_dist = false: the caller reads no distances from the table (the fused call)
-int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, int phase, bool want_dist);
+// begin (may be null): how the call's start is marked (CallBegin)
+int pct_build_grid(pct_ctx* ctx, int32_t k, double eps, bool may_give_up, GridVerdict* out, CallBegin* begin = nullptr);
+// neighbour sweeps (pct_knn.hip); want_dist = false: the caller reads no distances from the table (the fused call);
+// stamps: the device stamp block of a call timed by the device clock (its kernels stamp PCT_ST_GRID_END and PCT_ST_FAST_END;
+// no event is recorded), null: PCT_EV_FAST_END is recorded behind the fast sweep
+int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, int phase, bool want_dist, unsigned long long* stamps = nullptr);
 int pct_launch_knn_brute(pct_ctx* ctx, int32_t k, double eps);
 // census of the work items of the cell list in place: out4 = {queries, queries whose stencil overflows the staging
 // area, queries whose stencil holds fewer than 2.5 (k+1) points (too few to vouch for k+1 within one cell edge), sum over the other queries of the non-empty cells in their

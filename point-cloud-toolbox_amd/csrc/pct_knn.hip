@@ -253,7 +253,7 @@ int launch_sweep(pct_ctx* ctx, const SweepPlan& p, const KnnArgs& a, int* redo, 
 
 // phase 0: fast sweep + exact sweep of what it flagged (or, exact_only, the exact sweep of every query);
 // phase 1: fast sweep only, the flagged rows stay in ctx->redo (level passes); phase 2: exact sweep of ctx->redo
-int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, int phase, bool want_dist) {
+int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, int phase, bool want_dist, unsigned long long* stamps) {
     const int64_t n_rows = ctx->own_flag ? ctx->own_count : ctx->q_end - ctx->q_begin;
     const SweepPlan plan = plan_for(ctx, k, eps, false, exact_only, phase, want_dist);
     if (phase != 2) {
@@ -266,8 +266,14 @@ int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, in
     int* redo_count = &pct_dev(ctx)->sweep.redo_count;
     int* redo = (int*)ctx->redo.p;
     const dim3 block(64 * kWavesPerBlock);
+    if (stamps) {                  // the first kernel launched here stamps the end of the cell list; no fast sweep: knn_fast_ms = 0
+        const bool fast = plan.family != kNoSweep;
+        a.stamp_sweep = &stamps[PCT_ST_GRID_END];
+        a.stamp_exact = &stamps[fast ? PCT_ST_FAST_END : PCT_ST_GRID_END];
+        a.stamp_exact_also = fast ? nullptr : &stamps[PCT_ST_FAST_END];
+    }
     PCT_TRY(launch_sweep(ctx, plan, a, redo, redo_count));
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FAST_END], ctx->stream));      // end of the dominant kernel
+    if (!stamps) PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FAST_END], ctx->stream));      // end of the dominant kernel
     // exact pass: the flagged queries (device-side count, fixed grid) or, for testing, every query
     if (phase != 1) {
         const int64_t waves = exact_only ? n_rows : 32768;   // one query per wave for typical redo counts

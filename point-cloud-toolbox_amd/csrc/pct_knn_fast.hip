@@ -146,6 +146,7 @@ __global__ __launch_bounds__(64 * kFastWaves<R>, (TREE ? (R == 1 ? (PCT_TREE_CAP
     }
     int my_pre, m;
     run_prefix<NRUNS>(run_len, lane, my_pre, m);
+    pct_stamp(a.stamp_sweep);      // (behind the prologue's loads; block 0 takes neither return above on a uniform list: pct_stamp.h)
     unsigned long long n_flush = 0, n_step = 0, n_redo = 0;
     // rows of this item that go to the redo list: collected here (bit = query of the item, two bits of reason) and
     // appended with ONE counter increment when the item is done -- a counter increment per query serialises at the

@@ -37,6 +37,7 @@ struct PairArgs {
     const int4* tree_seg;     // per segment {level, cx, cy, cz}
     const int2* tree_runs;    // per segment 27 x {first position, points}, centre cell first
     int tree_bits;
+    unsigned long long* stamp;       // a call timed by the device clock: the sweep's entry (pct_stamp.h), else null
 };
 
 PairArgs make_pair_args(const pct_ctx* ctx, const KnnArgs& a, bool tree, int* redo, int* redo_count) {
@@ -47,6 +48,7 @@ PairArgs make_pair_args(const pct_ctx* ctx, const KnnArgs& a, bool tree, int* re
     pa.redo = redo; pa.redo_count = redo_count; pa.counters = a.counters;
     pa.n_items = (int)ctx->n_items; pa.items_q = ctx->items_q;
     pa.k = a.k; pa.pitch = a.pitch; pa.stats = a.stats; pa.eps2 = a.eps2; pa.g = a.g;
+    pa.stamp = a.stamp_sweep;
     pa.items_per_xcd = pct_getenv("PCT_NO_XCD_MAP") ? 0 : (int)((ctx->n_items + 7) / 8);
     if (tree) {
         pa.tree_seg = a.tree_seg; pa.tree_runs = a.tree_runs; pa.tree_bits = a.tree_bits;

@@ -95,6 +95,7 @@ __global__ __launch_bounds__(64 * kPairWaves, (TREE ? 4 : Q64 ? 5 : 6)) void k_k
     load_queries<Q64>(a.pts, a.ptsd, qs, nq, lane, my_q, my_qx, my_qy, my_qz, my_eq);
     int my_pre, m;
     run_prefix<NRUNS>(run_len, lane, my_pre, m);
+    pct_stamp(a.stamp);            // (behind the prologue's loads; block 0 takes neither return above on a uniform list: pct_stamp.h)
     if (item_overflows<TREE, NRUNS>(m, CAP, run_len, lane)) {
         hand_item_to_redo(a.redo, a.redo_count, a.counters, a.stats, row0, nq, lane, true);
         return;

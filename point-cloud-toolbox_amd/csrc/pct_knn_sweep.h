@@ -42,6 +42,11 @@ struct KnnArgs {
     const int* tree_bucket;                 // first position of every 18-bit code prefix
     int stats;                // collect the counters below (off by default)
     pct_sweep_words* counters;
+    // a call timed by the device clock (pct_stamp.h), else null: the word the fast sweep stamps at its entry, and the
+    // word(s) the exact kernel behind it stamps
+    unsigned long long* stamp_sweep;
+    unsigned long long* stamp_exact;
+    unsigned long long* stamp_exact_also;
 };
 
 // rows of 128 .. PCT_K_MAX neighbours (pct_knn_wide.hip): list registers R = 4 | 8
@@ -424,6 +429,7 @@ __device__ __forceinline__ int cell_coord_d(double x, double o, double inv, int 
 template <int R>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void k_knn_exact(KnnArgs a, const int* __restrict__ list,
                                                                    const int* __restrict__ list_count) {
+    pct_stamp(a.stamp_exact, a.stamp_exact_also);
     __shared__ double s_pend_d[kWavesPerBlock][64 * R + 64];
     __shared__ int s_pend_p[kWavesPerBlock][64 * R + 64];
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
