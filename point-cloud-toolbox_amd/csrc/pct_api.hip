@@ -76,12 +76,7 @@ int pct_reserve_fit(pct_ctx* ctx, int64_t rows) {
     return PCT_OK;
 }
 
-static float ev_ms(const hipEvent_t* ev, int a, int b) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, ev[a], ev[b]) != hipSuccess) ms = 0.f;
-    return ms;
-}
-static float ev_ms(pct_ctx* ctx, int a, int b) { return ev_ms(ctx->ev, a, b); }
+static float ev_ms(pct_ctx* ctx, int a, int b) { return pct_event_ms(ctx->ev[a], ctx->ev[b]); }
 
 // the statistics a sweep left, as the timings report them
 static void read_sweep_stats(const pct_sweep_words& w, pct_timings* t) {
@@ -92,39 +87,22 @@ static void read_sweep_stats(const pct_sweep_words& w, pct_timings* t) {
     t->redone_queries = (int64_t)w.redone_queries;
 }
 
-// the stage times of a finished sweep or fused call from the pinned stamps of its parity (fit_ms = 0 behind a sweep on its own)
-static void stamp_times(const pct_ctx* ctx, int par, bool sorted, pct_timings* t) {
-    const pct_stage_ms m = pct_stamps_ms(&ctx->pin->stamps[par], ctx->clock_khz);
-    t->grid_ms = m.grid;
-    t->knn_ms = m.knn;
-    t->knn_fast_ms = sorted ? m.knn_fast : 0.f;
-    t->fit_ms = m.fit;
-    t->total_ms = m.total;
-}
-
-// bookkeeping of the pending fused call, whose kernels have finished: timings from its stamps or its event set, statistics
-static void finish_pending(pct_ctx* ctx, const hipEvent_t* ev) {
-    pct_timings t = ctx->tm_snap;
-    read_sweep_stats(ctx->pin->stats[ctx->pend_par], &t);
-    if (ctx->pend_stamped) {
-        stamp_times(ctx, ctx->pend_par, ctx->pend_sorted, &t);
-    } else {
-        t.grid_ms = ev_ms(ev, PCT_EV_CALL_BEGIN, PCT_EV_GRID_END);
-        t.knn_ms = ev_ms(ev, PCT_EV_GRID_END, PCT_EV_SWEEP_END);
-        t.knn_fast_ms = ctx->pend_sorted ? ev_ms(ev, PCT_EV_GRID_END, PCT_EV_FAST_END) : 0.f;
-        t.fit_ms = ev_ms(ev, PCT_EV_SWEEP_END, PCT_EV_FIT_END);
-        t.total_ms = ev_ms(ev, PCT_EV_CALL_BEGIN, PCT_EV_FIT_END);
-    }
-    t.fit_svd_rows = ctx->pin->svd_rows[ctx->pend_par];
+// bookkeeping of the pending fused call, whose kernels have finished: timings from its clock, statistics
+static void finish_pending(pct_ctx* ctx) {
+    const int par = ctx->pend.par;
+    pct_timings t = ctx->pend.tm;
+    read_sweep_stats(ctx->pin->stats[par], &t);
+    ctx->clock[par].read(ctx->pend.sorted, &t);
+    t.fit_svd_rows = ctx->pin->svd_rows[par];
     ctx->tm_done = t;
-    ctx->pending = false;
+    ctx->pend.on = false;
 }
 
 // every entry point but an asynchronous pct_curvature: wait for the pending call and do its bookkeeping first
 static int drain(pct_ctx* ctx) {
-    if (!ctx->pending) return PCT_OK;
+    if (!ctx->pend.on) return PCT_OK;
     const hipError_t e = hipStreamSynchronize(ctx->stream);
-    finish_pending(ctx, ctx->ev);
+    finish_pending(ctx);
     ctx->tm = ctx->tm_done;
     PCT_HIP(ctx, e);
     return PCT_OK;
@@ -224,24 +202,28 @@ int pct_create(int device, pct_ctx** out) {
         delete ctx;
         return PCT_ERR_HIP;
     }
-    for (auto& e : ctx->ev)
-        if (hipEventCreate(&e) != hipSuccess) {
-            delete ctx;
-            return PCT_ERR_HIP;
-        }
-    for (int i = PCT_EV_CALL_BEGIN; i <= PCT_EV_FAST_END; ++i)     // the second set of timing events (pct_set_async)
-        if (hipEventCreate(&ctx->ev_prev[i]) != hipSuccess) {
-            delete ctx;
-            return PCT_ERR_HIP;
-        }
+    bool events = true;           // the handle's stopwatch pairs and the boundaries of its two call clocks
+    for (auto& e : ctx->ev) events = events && hipEventCreate(&e) == hipSuccess;
+    for (auto& c : ctx->clock)
+        for (auto& e : c.ev) events = events && hipEventCreate(&e) == hipSuccess;
+    if (!events) {
+        delete ctx;
+        return PCT_ERR_HIP;
+    }
     if (hipHostMalloc((void**)&ctx->pin, 4096, hipHostMallocMapped) != hipSuccess) {
         delete ctx;
         return PCT_ERR_OOM;
     }
     memset(ctx->pin, 0, 4096);
-    // ticks of the device's wall clock per millisecond, for the calls timed by stamps (unknown: every call keeps its events)
-    if (hipDeviceGetAttribute(&ctx->clock_khz, hipDeviceAttributeWallClockRate, device) != hipSuccess || ctx->clock_khz < 0) ctx->clock_khz = 0;
+    // the call clocks' pinned stamps, by parity, and the ticks of the device's wall clock per millisecond (unknown: every call keeps its events)
+    int khz = 0;
+    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) != hipSuccess || khz < 0) khz = 0;
     (void)hipGetLastError();
+    for (int par = 0; par < 2; ++par) {
+        ctx->clock[par].par = par;
+        ctx->clock[par].pin = &ctx->pin->stamps[par];
+        ctx->clock[par].rate_khz = khz;
+    }
     *out = ctx;
     return PCT_OK;
 }
@@ -263,8 +245,9 @@ void pct_destroy(pct_ctx* ctx) {
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     for (auto& e : ctx->ev)
         if (e) (void)hipEventDestroy(e);
-    for (auto& e : ctx->ev_prev)
-        if (e) (void)hipEventDestroy(e);
+    for (auto& c : ctx->clock)
+        for (auto& e : c.ev)
+            if (e) (void)hipEventDestroy(e);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -478,12 +461,12 @@ int pct_set_stats(pct_ctx* ctx, int32_t enable) {
 struct SweepDone { bool rows_fitted = false; };     // the passes of a chained sweep fitted the rows they answered: no fit is left to launch
 
 // The chain of cell lists.  fuse_par: every pass fits its rows, into the pinned slots of this parity (null: no fits).
-static int sweep_levels(pct_ctx* ctx, int32_t k, double eps, const int* fuse_par, SweepDone* done) {
+static int sweep_levels(pct_ctx* ctx, int32_t k, double eps, const int* fuse_par, pct_call_clock& clock, SweepDone* done) {
     ctx->tm.algo = PCT_KNN_GRID_LEVELS;
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_GRID_END], ctx->stream));
-    PCT_TRY(pct_knn_levels(ctx, k, eps, fuse_par));
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FAST_END], ctx->stream));
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_SWEEP_END], ctx->stream));
+    PCT_HIP(ctx, clock.boundary(PCT_ST_GRID_END, ctx->stream));
+    PCT_TRY(pct_knn_levels(ctx, k, eps, fuse_par, &clock));
+    PCT_HIP(ctx, clock.boundary(PCT_ST_FAST_END, ctx->stream));
+    PCT_HIP(ctx, clock.boundary(PCT_ST_SWEEP_END, ctx->stream));
     ctx->tm.knn_launches = ctx->tm.levels;
     ctx->knn_valid = true;
     ctx->knn_hier = true;
@@ -494,15 +477,15 @@ static int sweep_levels(pct_ctx* ctx, int32_t k, double eps, const int* fuse_par
 // The hierarchical cell list of a whole cloud.  *verdict: Built -- swept; Unusable (extents or eps outside what the float32
 // pre-selection can square) -- the chain of cell lists swept instead; OtherCloud (expect_bbox: the box a remembered
 // verdict was given for, null: any cloud) -- nothing built or swept, the caller goes on.
-static int sweep_tree(pct_ctx* ctx, int32_t k, double eps, bool want_dist, const float* expect_bbox, const int* fuse_par, SweepDone* done,
-                      TreeVerdict* verdict) {
+static int sweep_tree(pct_ctx* ctx, int32_t k, double eps, bool want_dist, const float* expect_bbox, const int* fuse_par, pct_call_clock& clock,
+                      SweepDone* done, TreeVerdict* verdict) {
     ctx->tm.algo = PCT_KNN_TREE;
     PCT_TRY(pct_build_tree(ctx, k, eps, expect_bbox, verdict));
     if (*verdict == TreeVerdict::OtherCloud) return PCT_OK;
-    if (*verdict == TreeVerdict::Unusable) return sweep_levels(ctx, k, eps, fuse_par, done);
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_GRID_END], ctx->stream));
-    PCT_TRY(pct_launch_knn_tree(ctx, k, eps, want_dist));
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_SWEEP_END], ctx->stream));
+    if (*verdict == TreeVerdict::Unusable) return sweep_levels(ctx, k, eps, fuse_par, clock, done);
+    PCT_HIP(ctx, clock.boundary(PCT_ST_GRID_END, ctx->stream));
+    PCT_TRY(pct_launch_knn_tree(ctx, k, eps, want_dist, &clock));
+    PCT_HIP(ctx, clock.boundary(PCT_ST_SWEEP_END, ctx->stream));
     ctx->tm.knn_launches = 1;
     ctx->knn_valid = true;
     ctx->knn_hier = true;
@@ -510,16 +493,16 @@ static int sweep_tree(pct_ctx* ctx, int32_t k, double eps, bool want_dist, const
 }
 
 // The exhaustive sweep: no cell list, the packed cloud
-static int sweep_brute(pct_ctx* ctx, int32_t k, double eps) {
+static int sweep_brute(pct_ctx* ctx, int32_t k, double eps, pct_call_clock& clock) {
     float bbox[6];
     PCT_TRY(pct_pack_points(ctx, bbox));
     ctx->tm.grid_iters = 0;
     ctx->tm.cells = ctx->tm.occupied_cells = 0;
     ctx->tm.grid_points = ctx->n;
     ctx->tm.cell_size = 0;
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_GRID_END], ctx->stream));
+    PCT_HIP(ctx, clock.boundary(PCT_ST_GRID_END, ctx->stream));
     PCT_TRY(pct_launch_knn_brute(ctx, k, eps));
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_SWEEP_END], ctx->stream));
+    PCT_HIP(ctx, clock.boundary(PCT_ST_SWEEP_END, ctx->stream));
     ctx->tm.knn_launches = 1;
     ctx->knn_valid = true;
     ctx->knn_hier = false;
@@ -542,25 +525,15 @@ static int examine_uniform_list(pct_ctx* ctx, int32_t k, bool tree_reachable, Ro
     return PCT_OK;
 }
 
-// A sweep on its own, timed by stamps, has no fit kernel behind it to end the call: one thread, whose start is the end of the sweep.
-__global__ void k_stamp_end(const unsigned long long* __restrict__ dev, unsigned long long* __restrict__ pin) {
-    const unsigned long long now = wall_clock64();
-    for (int i = 0; i < PCT_ST_SWEEP_END; ++i) pin[i] = dev[i];
-    pin[PCT_ST_SWEEP_END] = now;
-    __hip_atomic_store(&pin[PCT_ST_CALL_END], now, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// Neighbour sweep without timing bookkeeping; events CALL_BEGIN | GRID_END | SWEEP_END bracket cell list and sweep --
-// or, *stamped, none does: the route was certain before the first launch (an explicit PCT_KNN_GRID / PCT_KNN_GRID_EXACT
-// request, no slab) and the build's first launch took the begin stamp, so the kernels stamp the device words of parity
-// par and whatever follows the sweep (fused_tail, pct_knn) ends the call into the pinned ones (pct_stamp.h).
-// PCT_TIME_EVENTS=1 keeps the events (A/B runs); stamped = null: the caller reads events.
-// fuse_par: the fused call -- its fit reads no distances, and the passes of a chained sweep fit their rows into the pinned slots of this parity.
-static int run_knn(pct_ctx* ctx, int32_t k, double eps, int32_t asked, bool* stamped, const int* fuse_par = nullptr, SweepDone* done = nullptr) {
+// Neighbour sweep without timing bookkeeping.  clock: the call's, opened here once the request is known and told where
+// the call begins, where the cell list ends and where the sweep ends; whatever follows the sweep (fused_call, pct_knn)
+// ends it.  kind == PCT_CALL_FUSED: the fit reads no distances, and the passes of a chained sweep fit their rows into
+// the pinned slots of the clock's parity.
+static int run_knn(pct_ctx* ctx, int32_t k, double eps, int32_t asked, pct_call_clock& clock, pct_call_kind kind, SweepDone* done = nullptr) {
     SweepDone unread;
     if (!done) done = &unread;
     *done = SweepDone{};
-    if (stamped) *stamped = false;
+    const int* fuse_par = kind == PCT_CALL_FUSED ? &clock.par : nullptr;
     const bool want_dist = fuse_par == nullptr;
     // 1. the request
     if (ctx->n <= 0) return pct_fail(ctx, PCT_ERR_INVALID, "no cloud loaded");
@@ -580,84 +553,68 @@ static int run_knn(pct_ctx* ctx, int32_t k, double eps, int32_t asked, bool* sta
     ctx->knn_valid = ctx->fit_valid = ctx->area_valid = false;     // a new planting drops the fit and the areas
     ctx->k = k;
     ctx->eps = eps;
-    const int par = fuse_par ? *fuse_par : 0;
-    bool stamps = stamped && pct_stamps_apply(rq.auto_req, algo == PCT_KNN_GRID || algo == PCT_KNN_GRID_EXACT, ctx->slab_parts >= 1,
-                                              ctx->q_end - ctx->q_begin, ctx->clock_khz, pct_getenv("PCT_TIME_EVENTS") != nullptr);
-    CallBegin begin = {};
-    if (stamps) {
-        PCT_TRY(pct_reserve(ctx, &ctx->counters, sizeof(pct_dev_words)));
-        PCT_TRY(pct_reserve(ctx, &ctx->stamp_tickets, (size_t)kStampTicketLines * kStampTicketStride * sizeof(unsigned)));
-        if (ctx->stamp_tickets.p != ctx->stamp_tickets_seen) {        // (once per allocation: the last block out leaves the tickets at zero)
-            PCT_HIP(ctx, hipMemsetAsync(ctx->stamp_tickets.p, 0, (size_t)kStampTicketLines * kStampTicketStride * sizeof(unsigned), ctx->stream));
-            ctx->stamp_tickets_seen = ctx->stamp_tickets.p;
-        }
-        ctx->pin->stamps[par].t[PCT_ST_CALL_END] = 0ull;        // "finished" is this word non-zero
-        begin = CallBegin{&pct_dev(ctx)->stamps[par].t[PCT_ST_CALL_BEGIN], ctx->ev[PCT_EV_CALL_BEGIN], false, false};
-    }
-    if (!stamps) PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_CALL_BEGIN], ctx->stream));
+    PCT_TRY(clock.open(ctx, rq.auto_req, algo == PCT_KNN_GRID || algo == PCT_KNN_GRID_EXACT, kind));
+    PCT_HIP(ctx, clock.start(ctx->stream));
     ctx->tm.levels = 0;
     ctx->tm.sweep_variant = 0;         // (set by the fast sweep's launch, pct_knn.hip)
     ctx->tm.algo = algo;
     TreeVerdict tree;
     if (algo == PCT_KNN_TREE)
-        return rq.tree_ok ? sweep_tree(ctx, k, eps, want_dist, nullptr, fuse_par, done, &tree) : sweep_levels(ctx, k, eps, fuse_par, done);
+        return rq.tree_ok ? sweep_tree(ctx, k, eps, want_dist, nullptr, fuse_par, clock, done, &tree) : sweep_levels(ctx, k, eps, fuse_par, clock, done);
     // 2. the remembered hierarchical list
     if (remembered_applies(rq, ctx->n, ctx->auto_tree_n, &ctx->auto_tree_calls, sw)) {
-        PCT_TRY(sweep_tree(ctx, k, eps, want_dist, ctx->auto_tree_bbox, fuse_par, done, &tree));
+        PCT_TRY(sweep_tree(ctx, k, eps, want_dist, ctx->auto_tree_bbox, fuse_par, clock, done, &tree));
         if (tree != TreeVerdict::OtherCloud) return PCT_OK;
         ctx->auto_tree_n = 0;
         ctx->tm.algo = algo;
     }
-    if (algo == PCT_KNN_GRID_LEVELS) return sweep_levels(ctx, k, eps, fuse_par, done);
-    if (algo == PCT_KNN_BRUTE) return sweep_brute(ctx, k, eps);
+    if (algo == PCT_KNN_GRID_LEVELS) return sweep_levels(ctx, k, eps, fuse_par, clock, done);
+    if (algo == PCT_KNN_BRUTE) return sweep_brute(ctx, k, eps, clock);
     // 3. the uniform list (PCT_KNN_GRID, PCT_KNN_GRID_EXACT) -- and whether PCT_KNN_AUTO keeps it
     const bool tree_reachable = may_give_up(rq, ctx->n, sw);
     GridVerdict built;
-    PCT_TRY(pct_build_grid(ctx, k, eps, tree_reachable, &built, stamps ? &begin : nullptr));
-    stamps = stamps && begin.stamped;          // (else the build has recorded PCT_EV_CALL_BEGIN in front of its first launch)
+    PCT_TRY(pct_build_grid(ctx, k, eps, tree_reachable, &built, &clock));
     Route route = built == GridVerdict::GaveUp ? Route::Tree : Route::Stay;      // (not built: far too many cells per point)
     if (built == GridVerdict::Built && skew_gate(rq, whole, ctx->n, ctx->nonempty_cells, sw)) {
         PCT_TRY(examine_uniform_list(ctx, k, tree_reachable, &route));
         if (route == Route::Stay) ctx->auto_tree_n = 0;
     }
     if (route == Route::Tree) {
-        PCT_TRY(sweep_tree(ctx, k, eps, want_dist, nullptr, fuse_par, done, &tree));
+        PCT_TRY(sweep_tree(ctx, k, eps, want_dist, nullptr, fuse_par, clock, done, &tree));
         if (tree == TreeVerdict::Built) {          // the next cloud of this size and box goes there directly
             ctx->auto_tree_n = ctx->n;
             memcpy(ctx->auto_tree_bbox, ctx->tree_bbox, sizeof(ctx->tree_bbox));
         }
         return PCT_OK;
     }
-    if (route == Route::Levels) return sweep_levels(ctx, k, eps, fuse_par, done);
+    if (route == Route::Levels) return sweep_levels(ctx, k, eps, fuse_par, clock, done);
     // 4. the sweep
-    if (!stamps) PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_GRID_END], ctx->stream));
-    PCT_TRY(pct_launch_knn_grid(ctx, k, eps, algo == PCT_KNN_GRID_EXACT, 0, want_dist, stamps ? pct_dev(ctx)->stamps[par].t : nullptr));
-    if (!stamps) PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_SWEEP_END], ctx->stream));
-    if (stamped) *stamped = stamps;
+    PCT_HIP(ctx, clock.boundary(PCT_ST_GRID_END, ctx->stream));
+    PCT_TRY(pct_launch_knn_grid(ctx, k, eps, algo == PCT_KNN_GRID_EXACT, 0, want_dist, &clock));
+    PCT_HIP(ctx, clock.boundary(PCT_ST_SWEEP_END, ctx->stream));
     ctx->tm.knn_launches = 1;
     ctx->knn_valid = true;
     ctx->knn_hier = false;
     return PCT_OK;
 }
 
-// The fused call's tail behind its sweep: the fit (where the passes of a chained sweep have not fitted their rows), its end
-// -- stamped: by the last block out of k_fit_svd, else an event --, and the sweep's statistics words into pinned slot `par`
-// -- mirrored by the fit kernel, else copied.
-// (a call timed by events has none for the start of the fit: it starts where the sweep's last event, PCT_EV_SWEEP_END, was
-// recorded -- every event record is a marker packet between two kernels, ~3 us of dispatch gap; a stamped call has no marker
-// on its chain at all)
-static int fused_tail(pct_ctx* ctx, int par, const SweepDone& swept, bool stamped) {
+// The fused call, enqueued: the sweep and its tail -- the fit (where the passes of a chained sweep have not fitted their
+// rows), the call's end on its clock, and the sweep's statistics words into the pinned slot of the clock's parity,
+// mirrored by the fit kernel, else copied.
+// (the fit stage has no boundary of its own: it starts where the sweep ends)
+static int fused_call(pct_ctx* ctx, int32_t k, double eps, int32_t algo, pct_call_clock& clock) {
+    SweepDone swept;
+    PCT_TRY(run_knn(ctx, k, eps, algo, clock, PCT_CALL_FUSED, &swept));
     bool mirrored = false;
-    if (!swept.rows_fitted) PCT_TRY(pct_launch_fit_table(ctx, FitSlot{par, true, stamped}, &mirrored));
-    if (!stamped) PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_END], ctx->stream));
+    if (!swept.rows_fitted) PCT_TRY(pct_launch_fit_table(ctx, FitSlot{clock.par, true, &clock}, &mirrored));
+    PCT_HIP(ctx, clock.end(ctx->stream));
     if (!mirrored)                // (no fit kernel ran: the chained sweep fitted its passes itself, or there are no rows)
-        PCT_HIP(ctx, hipMemcpyAsync(&ctx->pin->stats[par], ctx->counters.p, sizeof(pct_sweep_words), hipMemcpyDeviceToHost, ctx->stream));
+        PCT_HIP(ctx, hipMemcpyAsync(&ctx->pin->stats[clock.par],ctx->counters.p, sizeof(pct_sweep_words), hipMemcpyDeviceToHost, ctx->stream));
     return PCT_OK;
 }
 
 // words_enqueued: the fused tail has sent the statistics words to pinned slot 0 already
-// stamped: the call's times come from the pinned stamps of parity 0 (fit_ms and total_ms with them)
-static int finish_knn_stats(pct_ctx* ctx, bool words_enqueued, bool stamped, bool* beyond_limits) {
+static int finish_knn_stats(pct_ctx* ctx, const pct_call_clock& clock, bool words_enqueued, bool* beyond_limits) {
     pct_sweep_words& w = ctx->pin->stats[0];                             // pinned: a plain DMA, no staging
     if (!words_enqueued) PCT_HIP(ctx, hipMemcpyAsync(&w, ctx->counters.p, sizeof(w), hipMemcpyDeviceToHost, ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -665,13 +622,7 @@ static int finish_knn_stats(pct_ctx* ctx, bool words_enqueued, bool stamped, boo
     if (pct_getenv("PCT_TREE_DEBUG") && ctx->collect_stats)
         fprintf(stderr, "[tree] redone %llu, up-levelled %llu, candidate steps %llu, costliest exact query: %llu steps (row %llu)\n", w.redone_queries,
                 w.ring_fallbacks, w.candidate_steps, w.costliest >> 32, w.costliest & 0xffffffffull);
-    if (stamped) {
-        stamp_times(ctx, 0, ctx->knn_sorted_space, &ctx->tm);
-    } else {
-        ctx->tm.grid_ms = ev_ms(ctx, PCT_EV_CALL_BEGIN, PCT_EV_GRID_END);
-        ctx->tm.knn_ms = ev_ms(ctx, PCT_EV_GRID_END, PCT_EV_SWEEP_END);
-        ctx->tm.knn_fast_ms = ctx->knn_sorted_space ? ev_ms(ctx, PCT_EV_GRID_END, PCT_EV_FAST_END) : 0.f;
-    }
+    clock.read(ctx->knn_sorted_space, &ctx->tm);
     // a sharded handle that left far points out of its grid met a query those points could matter to
     *beyond_limits = ctx->knn_sorted_space && ctx->culled && w.beyond_limits > 0;
     ctx->tm.limit_retries = ctx->retries;
@@ -687,19 +638,14 @@ static void retry_without_cull(pct_ctx* ctx) {
 
 int pct_knn(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
     PCT_TRY(begin_call(ctx));
-    bool again = false, stamped = false;
+    bool again = false;
     for (int attempt = 0; attempt < 2; ++attempt) {
-        PCT_TRY(run_knn(ctx, k, eps, algo, &stamped));
-        if (stamped) {
-            PCT_LAUNCH(k_stamp_end, dim3(1), dim3(1), 0, ctx->stream, (const unsigned long long*)pct_dev(ctx)->stamps[0].t, ctx->pin->stamps[0].t);
-            PCT_HIP(ctx, hipGetLastError());
-        }
-        PCT_TRY(finish_knn_stats(ctx, false, stamped, &again));
+        PCT_TRY(run_knn(ctx, k, eps, algo, ctx->clock[0], PCT_CALL_SWEEP));
+        PCT_HIP(ctx, ctx->clock[0].end(ctx->stream));
+        PCT_TRY(finish_knn_stats(ctx, ctx->clock[0], false, &again));
         if (!again) break;
         retry_without_cull(ctx);
     }
-    ctx->tm.fit_ms = 0;
-    if (!stamped) ctx->tm.total_ms = ev_ms(ctx, PCT_EV_CALL_BEGIN, PCT_EV_SWEEP_END);
     return PCT_OK;
 }
 
@@ -708,7 +654,7 @@ int pct_fit(pct_ctx* ctx) {
     PCT_TRY(refuse_in_slab_mode(ctx, "pct_fit"));
     if (!ctx->knn_valid) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "plant the neighbour table first (pct_knn)");
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_BEGIN], ctx->stream));
-    PCT_TRY(pct_launch_fit_table(ctx, FitSlot{0, false}, nullptr));
+    PCT_TRY(pct_launch_fit_table(ctx, FitSlot{0, false, nullptr}, nullptr));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_END], ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->tm.fit_ms = ev_ms(ctx, PCT_EV_FIT_BEGIN, PCT_EV_FIT_END);
@@ -725,48 +671,32 @@ int pct_set_async(pct_ctx* ctx, int32_t enable) {
     return PCT_OK;
 }
 
-// the timing events of the pending call <-> the set the next call records into
-static void swap_event_sets(pct_ctx* ctx) {
-    for (int i = PCT_EV_CALL_BEGIN; i <= PCT_EV_FAST_END; ++i) { hipEvent_t t = ctx->ev[i]; ctx->ev[i] = ctx->ev_prev[i]; ctx->ev_prev[i] = t; }
-}
-
 // pct_curvature of a stream of clouds (pct_set_async): enqueue and return.  The previous call's bookkeeping is done here,
 // after the cell list's mid-build wait -- which lies behind all of that call's kernels on the stream --, without a wait
 // of its own.
 static int curvature_async(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
-    const bool had = ctx->pending;
-    if (had) swap_event_sets(ctx);          // the pending call keeps its timing events; this one records into the other set
-    const int par = pct_next_parity(had, ctx->pend_par);
+    const bool had = ctx->pend.on;
+    const int par = pct_next_parity(had, ctx->pend.par);        // (the pending call keeps its clock and its pinned slots)
+    pct_call_clock& clock = ctx->clock[par];
     ctx->retries = 0;
-    SweepDone swept;
-    bool stamped = false;
-    int st = run_knn(ctx, k, eps, algo, &stamped, &par, &swept);
-    if (st == PCT_OK) st = fused_tail(ctx, par, swept, stamped);
-    if (st != PCT_OK) {            // leave the handle in the plain state: nothing pending, events where they were
+    const int st = fused_call(ctx, k, eps, algo, clock);
+    if (st != PCT_OK) {            // leave the handle in the plain state: nothing pending
         (void)hipStreamSynchronize(ctx->stream);
-        if (had) {
-            swap_event_sets(ctx);
-            finish_pending(ctx, ctx->ev);
-        }
+        if (had) finish_pending(ctx);
         return st;
     }
     if (had) {
-        // its kernels lie in front of this call's mid-build wait on the stream: normally long finished (checked, not assumed:
-        // its end stamp is in pinned memory, or its end event has been passed)
-        if (ctx->pend_stamped) {
-            if (!pct_stamps_finished(&ctx->pin->stamps[ctx->pend_par])) (void)hipStreamSynchronize(ctx->stream);
-        } else if (hipEventQuery(ctx->ev_prev[PCT_EV_FIT_END]) != hipSuccess) {
-            (void)hipEventSynchronize(ctx->ev_prev[PCT_EV_FIT_END]);
-        }
+        // its kernels lie in front of this call's mid-build wait on the stream: normally long finished (checked, not assumed)
+        const pct_call_clock& prev = ctx->clock[ctx->pend.par];
+        if (!prev.finished()) (void)prev.wait(ctx->stream);
         (void)hipGetLastError();
-        finish_pending(ctx, ctx->ev_prev);
+        finish_pending(ctx);
     }
     ctx->tm.limit_retries = 0;
-    ctx->tm_snap = ctx->tm;
-    ctx->pend_par = par;
-    ctx->pend_sorted = ctx->knn_sorted_space;
-    ctx->pend_stamped = stamped;
-    ctx->pending = true;
+    ctx->pend.tm = ctx->tm;
+    ctx->pend.par = par;
+    ctx->pend.sorted = ctx->knn_sorted_space;
+    ctx->pend.on = true;
     ctx->fit_rows = ctx->q_end - ctx->q_begin;
     ctx->fit_valid = true;
     ctx->fit_cloud_aligned = true;
@@ -780,20 +710,12 @@ int pct_curvature(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
                        !ctx->collect_stats;
     PCT_TRY(begin_call(ctx, !async));
     if (async) return curvature_async(ctx, k, eps, algo);
-    bool stamped = false;
     for (int attempt = 0; attempt < 2; ++attempt) {
         bool again = false;
-        const int par = 0;
-        SweepDone swept;
-        PCT_TRY(run_knn(ctx, k, eps, algo, &stamped, &par, &swept));
-        PCT_TRY(fused_tail(ctx, par, swept, stamped));
-        PCT_TRY(finish_knn_stats(ctx, true, stamped, &again));
+        PCT_TRY(fused_call(ctx, k, eps, algo, ctx->clock[0]));
+        PCT_TRY(finish_knn_stats(ctx, ctx->clock[0], true, &again));
         if (!again) break;
         retry_without_cull(ctx);
-    }
-    if (!stamped) {
-        ctx->tm.fit_ms = ev_ms(ctx, PCT_EV_SWEEP_END, PCT_EV_FIT_END);        // (the fit starts where the sweep's last event was recorded)
-        ctx->tm.total_ms = ev_ms(ctx, PCT_EV_CALL_BEGIN, PCT_EV_FIT_END);
     }
     ctx->tm.fit_svd_rows = ctx->pin->svd_rows[0];
     ctx->tm_done = ctx->tm;
@@ -1413,11 +1335,11 @@ int pct_surface_variation(pct_ctx* ctx, int32_t k_total, float* out) {
     const int64_t rows = ctx->q_end - ctx->q_begin;
     for (int attempt = 0; attempt < 2; ++attempt) {
         bool again = false;
-        PCT_TRY(run_knn(ctx, k_total - 1, 0.0, PCT_KNN_AUTO, nullptr));        // k-1 neighbours + the point itself (utils.py:812-814)
+        PCT_TRY(run_knn(ctx, k_total - 1, 0.0, PCT_KNN_AUTO, ctx->clock[0], PCT_CALL_SWEEP_HEAD));        // k-1 neighbours + the point itself (utils.py:812-814)
         PCT_TRY(pct_reserve(ctx, &ctx->K, (size_t)rows * sizeof(float)));
         PCT_TRY(pct_launch_surface_variation(ctx, (float*)ctx->K.p));
         PCT_HIP(ctx, hipMemcpyAsync(out, ctx->K.p, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        PCT_TRY(finish_knn_stats(ctx, false, false, &again));
+        PCT_TRY(finish_knn_stats(ctx, ctx->clock[0], false, &again));
         if (!again) break;
         retry_without_cull(ctx);
     }
@@ -1447,8 +1369,8 @@ int pct_pca_curvatures(pct_ctx* ctx, int32_t k, int32_t algo, int32_t keep_neigh
     const int64_t room = (PCT_K_MAX < ctx->n - 1 ? PCT_K_MAX : ctx->n - 1) - kk;
     const int32_t kc = (int32_t)(kk + (room < PCT_PCA_EXTRA ? room : PCT_PCA_EXTRA));
     bool again = false;
-    if (st == PCT_OK) st = run_knn(ctx, kc, 0.0, algo, nullptr);      // (timed by events: the PCA kernels follow)
-    if (st == PCT_OK) st = finish_knn_stats(ctx, false, false, &again);     // (whole clouds: nothing was left out of the cell list)
+    if (st == PCT_OK) st = run_knn(ctx, kc, 0.0, algo, ctx->clock[0], PCT_CALL_SWEEP_HEAD);      // (the PCA kernels follow)
+    if (st == PCT_OK) st = finish_knn_stats(ctx, ctx->clock[0], false, &again);     // (whole clouds: nothing was left out of the cell list)
     const int rs = pct_pca_restore(ctx);
     PCT_TRY(st);
     PCT_TRY(rs);
@@ -1461,7 +1383,7 @@ int pct_pca_curvatures(pct_ctx* ctx, int32_t k, int32_t algo, int32_t keep_neigh
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_END], ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->tm.fit_ms = ev_ms(ctx, PCT_EV_FIT_BEGIN, PCT_EV_FIT_END);
-    ctx->tm.total_ms = ev_ms(ctx, PCT_EV_CALL_BEGIN, PCT_EV_FIT_END);
+    ctx->tm.total_ms = ctx->clock[0].since_begin(ctx->ev[PCT_EV_FIT_END]);
     ctx->pca_valid = true;
     ctx->pca_has_nbr = keep_neighbors != 0;
     ctx->pca_k = (int32_t)kk;
@@ -1498,7 +1420,7 @@ int pct_timings_size(void) { return (int)sizeof(pct_timings); }
 
 int pct_get_timings(const pct_ctx* ctx, pct_timings* out) {
     if (!ctx || !out) return PCT_ERR_INVALID;
-    if (ctx->pending) {                    // (an asynchronous call: its times exist once its kernels have finished)
+    if (ctx->pend.on) {                    // (an asynchronous call: its times exist once its kernels have finished)
         pct_ctx* c = const_cast<pct_ctx*>(ctx);
         PCT_TRY(begin_call(c));
     }
@@ -1508,7 +1430,7 @@ int pct_get_timings(const pct_ctx* ctx, pct_timings* out) {
 
 int pct_get_timings_done(const pct_ctx* ctx, pct_timings* out) {
     if (!ctx || !out) return PCT_ERR_INVALID;
-    *out = ctx->pending ? ctx->tm_done : ctx->tm;
+    *out = ctx->pend.on ? ctx->tm_done : ctx->tm;
     return PCT_OK;
 }
 

@@ -454,13 +454,7 @@ int launch(pct_ctx* ctx, const FitArgs& a0, bool f64, FitSlot slot, bool* mirror
         a.stat_dst = &ctx->pin->stats[slot.par];
         if (mirrored) *mirrored = true;
     }
-    a.stamps = a.stamps_pin = nullptr;
-    a.stamp_ticket = nullptr;
-    if (slot.stamped) {            // (run_knn has reserved the words and zeroed the ticket)
-        a.stamps = pct_dev(ctx)->stamps[slot.par].t;
-        a.stamps_pin = ctx->pin->stamps[slot.par].t;
-        a.stamp_ticket = (unsigned*)ctx->stamp_tickets.p;
-    }
+    if (slot.clock) slot.clock->end_words(&a.stamps, &a.stamps_pin, &a.stamp_ticket);
     a.flag_count = (int*)ctx->fit_flag.p + ctx->fit_parity;
     a.flag_next = (int*)ctx->fit_flag.p + (ctx->fit_parity ^ 1);
     ctx->fit_parity ^= 1;

@@ -1363,9 +1363,9 @@ struct GridPoints {
 
 // Decides the source from ctx and runs its pack pass.  *restart: the kept part cannot fill a row; culling is ruled out
 // on the handle and the caller starts over.
-// begin (may be null): the call's start -- stamped by the full pack's kernel, recorded as an event in front of every other pack pass.
+// clock (may be null): the call's begin -- the full pack's kernel takes its word; every other pack pass has its event in front.
 static int select_source(pct_ctx* ctx, int32_t k, double target, bool slab, int64_t n_owned, bool sharded, GridPoints* s, bool* restart,
-                         CallBegin* begin) {
+                         pct_call_clock* clock) {
     const bool own_flag = ctx->own_flag != nullptr;
     // (a slab's owned points are found by the pack itself: it always runs, with an open box after a limit retry)
     const bool try_cull = slab ? n_owned > 0
@@ -1379,7 +1379,7 @@ static int select_source(pct_ctx* ctx, int32_t k, double target, bool slab, int6
     *s = GridPoints{};
     s->src = own_flag && ctx->lvl_src_valid ? GridSource::LevelBase : try_cull ? GridSource::CulledPack : spec ? GridSource::CallerRows
                                                                                                                : GridSource::FullPack;
-    if (begin && s->src != GridSource::CallerRows && s->src != GridSource::FullPack) PCT_HIP(ctx, begin->fall_back(ctx->stream));
+    if (clock && s->src != GridSource::CallerRows && s->src != GridSource::FullPack) PCT_HIP(ctx, clock->begin_event(ctx->stream));
     switch (s->src) {
     case GridSource::LevelBase:
         for (int a = 0; a < 6; ++a) s->bbox[a] = ctx->lvl_bbox[a];
@@ -1410,7 +1410,7 @@ static int select_source(pct_ctx* ctx, int32_t k, double target, bool slab, int6
         for (int a = 0; a < 6; ++a) s->bbox[a] = ctx->spec_bbox[a];
         break;
     case GridSource::FullPack:
-        PCT_TRY(pack_all(ctx, s->bbox, &s->red, false, begin ? begin->take() : nullptr));
+        PCT_TRY(pack_all(ctx, s->bbox, &s->red, false, clock ? clock->begin_word() : nullptr));
         PCT_TRY(trim_box(ctx, s->red, s->bbox));
         break;
     }
@@ -1552,15 +1552,15 @@ static void launch_bin_scatter(pct_ctx* ctx, int64_t n, const GridPass& p, int* 
 }
 
 // First half of a pass: per-cell counts of owned / other points in cell_own / cell_oth (and, while the box is deferred,
-// the cloud's PackRed record on its way to pinned memory).  begin (may be null): a call's start that has not been marked
-// yet is stamped by k_bin_count where that is the first launch, else recorded in front of the clearing fills.
-static int launch_count(pct_ctx* ctx, const GridPoints& s, GridPass& p, CallBegin* begin) {
+// the cloud's PackRed record on its way to pinned memory).  clock (may be null): a call's begin that has not been marked
+// yet goes to k_bin_count as its word where that is the first launch, else in front of the clearing fills as its event.
+static int launch_count(pct_ctx* ctx, const GridPoints& s, GridPass& p, pct_call_clock* clock) {
     const pct_grid& g = p.g;
     const int64_t n = s.n;
     const float* own_flag = (const float*)ctx->own_flag;
     const bool bin = p.build == GridBuild::Bin;            // (writes every counter itself: no clearing fill)
     PCT_TRY(pct_reserve(ctx, &ctx->cell_own, (size_t)g.ncell * sizeof(int)));
-    if (begin && !bin) PCT_HIP(ctx, begin->fall_back(ctx->stream));
+    if (clock && !bin) PCT_HIP(ctx, clock->begin_event(ctx->stream));
     if (!bin) PCT_HIP(ctx, hipMemsetAsync(ctx->cell_own.p, 0, (size_t)g.ncell * sizeof(int), ctx->stream));
     if (p.sharded) {
         PCT_TRY(pct_reserve(ctx, &ctx->cell_oth, (size_t)g.ncell * sizeof(int)));
@@ -1572,7 +1572,7 @@ static int launch_count(pct_ctx* ctx, const GridPoints& s, GridPass& p, CallBegi
     const int nhb = grid_1d(n, kBlock, 0);
     if (bin) {
         const BinShape& bs = p.bs;
-        unsigned long long* begin_stamp = begin ? begin->take() : nullptr;
+        unsigned long long* begin_stamp = clock ? clock->begin_word() : nullptr;
         s.raw ? launch_bin_count<true>(ctx, n, p, parts, begin_stamp) : launch_bin_count<false>(ctx, n, p, parts, begin_stamp);
         PCT_LAUNCH(k_bin_colscan, dim3((bs.nb + kBinScanCols - 1) / kBinScanCols), dim3(kBinScanCols * kBinScanGroups), 0, ctx->stream,
                    (unsigned*)ctx->bin_mat.p, bs.ntiles, bs.nb, p.bin.tot);
@@ -1719,7 +1719,7 @@ static int commit_grid(pct_ctx* ctx, const GridPoints& s, pct_grid g, const Edge
 // 27-cell stencil (guaranteed radius = one cell edge) contains the k+1 nearest
 // points for nearly every query of a surface-like cloud; the sweep kernel
 // widens ring by ring for the rest.
-int pct_build_grid(pct_ctx* ctx, int32_t k, double eps, bool may_give_up, GridVerdict* out, CallBegin* begin) {
+int pct_build_grid(pct_ctx* ctx, int32_t k, double eps, bool may_give_up, GridVerdict* out, pct_call_clock* clock) {
     *out = GridVerdict::Built;
     ctx->grid_valid = false;       // (the lists are being rewritten: valid again once a build is committed)
     // measured optima on surface clouds (tools/tune_factor.py): larger cells cost candidates, smaller ones cost
@@ -1753,7 +1753,7 @@ int pct_build_grid(pct_ctx* ctx, int32_t k, double eps, bool may_give_up, GridVe
         const bool sharded = own_flag || ctx->q_begin > 0 || ctx->q_end < ctx->n || slab;   // some points are candidates only
         GridPoints s;
         bool restart = false;
-        PCT_TRY(select_source(ctx, k, target, slab, n_owned, sharded, &s, &restart, begin));
+        PCT_TRY(select_source(ctx, k, target, slab, n_owned, sharded, &s, &restart, clock));
         if (restart) continue;
         const int64_t n = s.n;
         ctx->items_q = items_q;
@@ -1797,7 +1797,7 @@ int pct_build_grid(pct_ctx* ctx, int32_t k, double eps, bool may_give_up, GridVe
             p.bs = bin_allowed ? bin_shape(n, g.ncell, sharded) : BinShape{};
             p.build = choose_build(bin_allowed, p.bs, s);
             const bool bin = p.build == GridBuild::Bin;
-            PCT_TRY(launch_count(ctx, s, p, begin));
+            PCT_TRY(launch_count(ctx, s, p, clock));
             const int nblk = (int)((g.ncell + kScanTile - 1) / kScanTile);
             if (pct_getenv("PCT_GRID_DEBUG"))
                 fprintf(stderr, "[grid] pass %d: n %lld owned %lld edge %g dims %d x %d x %d = %lld cells (%d scan tiles), box [%g %g %g]-[%g %g %g]\n", it,

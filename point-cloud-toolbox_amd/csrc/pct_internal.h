@@ -9,6 +9,7 @@
 
 #include "../../include/pct_hip.h"
 #include "pct_stamp.h"
+#include "pct_clock.h"
 
 #define PCT_WAVE 64
 #define PCT_K_MAX 511           // longest neighbour row: k + 1 <= 512 = 64 lanes x 8 list registers (wave-per-query sweeps, pct_knn_wide.hip)
@@ -122,14 +123,11 @@ struct pct_pinned {
 };
 static_assert(sizeof(pct_pinned) <= 4096, "pct_create allocates 4096 bytes");
 
-// The five between CALL_BEGIN and FAST_END time the stages of a sweep or a fused call whose route is open when it starts
-// (PCT_KNN_AUTO, the tree, the chained sweep, brute force, slab handles, a build that starts with a pass of its own) or that
-// PCT_TIME_EVENTS=1 asks for; every other PCT_KNN_GRID / PCT_KNN_GRID_EXACT call records none of them (pct_stamp.h).
+// The handle's stopwatch pairs.  The stages of a sweep or a fused call are not among them: they are timed by the call's
+// clock (pct_clock.h), which owns the events of its boundaries.
 enum pct_event {                           // ctx->ev
     PCT_EV_IO_BEGIN, PCT_EV_IO_END,        // an upload or an export
-    PCT_EV_CALL_BEGIN, PCT_EV_GRID_END, PCT_EV_SWEEP_END,     // a sweep or a fused call: cell list | sweep | (fused) fit
-    PCT_EV_FIT_BEGIN, PCT_EV_FIT_END,      // a fit (a fused call records its end only)
-    PCT_EV_FAST_END,                       // end of the fast sweep, the dominant kernel
+    PCT_EV_FIT_BEGIN, PCT_EV_FIT_END,      // a fit on its own (pct_fit and its siblings)
     PCT_EV_SCAN_TOTALS,                    // the cell list's scan totals are in pinned memory (pct_build_grid)
     PCT_EV_AREA_BEGIN, PCT_EV_AREA_END,    // pct_point_areas
     PCT_EV_COUNT
@@ -142,20 +140,18 @@ struct pct_ctx {
     pct_comm* comm = nullptr;
     hipStream_t stream = nullptr;
     hipEvent_t ev[PCT_EV_COUNT] = {};
-    // Streams of clouds (pct_set_async): a fused call returns once its kernels are enqueued; its timing events, its
-    // statistics words and its SVD row count wait in the set of the call's parity until the NEXT fused call has passed
-    // its mid-build wait (everything of the previous call has completed by then) or until anything else is asked of the
+    pct_call_clock clock[2];       // stage timing of a sweep or a fused call, by parity of the call (blocking calls: 0)
+    // Streams of clouds (pct_set_async): a fused call returns once its kernels are enqueued; its clock, its statistics
+    // words and its SVD row count wait in the slots of the call's parity until the NEXT fused call has passed its
+    // mid-build wait (everything of the previous call has completed by then) or until anything else is asked of the
     // handle (which first waits for the stream).  The host prepares step i + 1 while the device fits step i.
-    hipEvent_t ev_prev[PCT_EV_COUNT] = {};    // the timing events of the pending call while a new one records into ev
     bool async_mode = false;
-    bool pending = false;          // a fused call has been enqueued and its bookkeeping has not been done
-    int pend_par = 0;              // parity of the pending call: which pinned slots its kernels write
-    bool pend_sorted = false;      // its table is in a sorted space: knn_fast_ms applies
-    bool pend_stamped = false;     // its times come from the stamps of its parity, not from its event set
-    int clock_khz = 0;             // hipDeviceAttributeWallClockRate: ticks of a stamp per millisecond (0: unknown, calls are timed by events)
+    // the pending call -- on: a fused call has been enqueued and its bookkeeping has not been done; par: its parity (which
+    // clock times it, which pinned slots its kernels write); sorted: its table is in a sorted space, knn_fast_ms applies;
+    // tm: the host-side fields of its timings
+    struct { bool on = false; int par = 0; bool sorted = false; pct_timings tm = {}; } pend;
     pct_buf stamp_tickets;         // unsigned (kStampTicketLines lines): blocks of the step's last kernel that have finished (pct_stamp_last_out;
-    void* stamp_tickets_seen = nullptr;   // zero between launches: cleared once per allocation)
-    pct_timings tm_snap = {};      // the host-side fields of the pending call's timings
+                                   // zero between launches: cleared when allocated, by the first call that opens on stamps)
     pct_timings tm_done = {};      // timings of the last call whose bookkeeping has been done
     char err[512] = {0};
 
@@ -434,28 +430,8 @@ __device__ inline int64_t pct_code_lower_bound(const unsigned long long* __restr
 // What one call asks of another, and what it answers, travels in arguments and results -- never parked on the handle.
 // Which pinned parity slot (statistics mirror, SVD row count) the fits of a call write, and whether its fit kernel may
 // mirror the sweep's statistics words there (the fused call: one copy less in the step's tail).
-// stamped: the call is timed by the device clock (pct_stamp.h) -- k_fit stamps the end of the sweep, k_fit_svd the end of the call.
-struct FitSlot { int par; bool mirror_stats; bool stamped; };
-// The start of a call that would rather be timed by device stamps.  The cell-list build hands `slot` to its first launch
-// where that is a kernel with a stamp argument (k_pack, k_bin_count); where it is not -- a cull pass, a level pass, a build
-// with per-point atomics, whose first launch is a memset -- it records `fallback` in front of that launch instead and the
-// call goes on with events.  Used once: a later pass of the cell-size search or a restarted attempt finds it spent.
-struct CallBegin {
-    unsigned long long* slot;      // device word PCT_ST_CALL_BEGIN of the call's parity
-    hipEvent_t fallback;           // PCT_EV_CALL_BEGIN
-    bool spent, stamped;
-    unsigned long long* take() {
-        if (spent) return nullptr;
-        spent = stamped = true;
-        return slot;
-    }
-    hipError_t fall_back(hipStream_t stream) {
-        if (spent) return hipSuccess;
-        spent = true;
-        stamped = false;
-        return hipEventRecord(fallback, stream);
-    }
-};
+// clock (may be null): the fused call's, whose end the fit kernels may be asked to stamp (pct_call_clock::end_words).
+struct FitSlot { int par; bool mirror_stats; pct_call_clock* clock; };
 enum class GridVerdict { Built, GaveUp };                  // GaveUp: more than 16 cells per point wanted, nothing built
 enum class TreeVerdict { Built, Unusable, OtherCloud };    // Unusable: not a cloud for it; OtherCloud: not the expected box; nothing built
 
@@ -463,22 +439,21 @@ enum class TreeVerdict { Built, Unusable, OtherCloud };    // Unusable: not a cl
 int pct_pack_points(pct_ctx* ctx, float* bbox6);
 int pct_pack_points_f64(pct_ctx* ctx, const double* d_xyz64);
 // may_give_up: PCT_KNN_AUTO on a cloud the hierarchical list could take (pct_auto_route.h)
-// begin (may be null): how the call's start is marked (CallBegin)
-int pct_build_grid(pct_ctx* ctx, int32_t k, double eps, bool may_give_up, GridVerdict* out, CallBegin* begin = nullptr);
+// clock (may be null: a build outside a timed call): the call's, whose begin the build's first launch marks
+int pct_build_grid(pct_ctx* ctx, int32_t k, double eps, bool may_give_up, GridVerdict* out, pct_call_clock* clock = nullptr);
 // neighbour sweeps (pct_knn.hip); want_dist = false: the caller reads no distances from the table (the fused call);
-// stamps: the device stamp block of a call timed by the device clock (its kernels stamp PCT_ST_GRID_END and PCT_ST_FAST_END;
-// no event is recorded), null: PCT_EV_FAST_END is recorded behind the fast sweep
-int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, int phase, bool want_dist, unsigned long long* stamps = nullptr);
+// clock: the call's -- the end of the fast sweep is a boundary of its sweep stage
+int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, int phase, bool want_dist, pct_call_clock* clock);
 int pct_launch_knn_brute(pct_ctx* ctx, int32_t k, double eps);
 // census of the work items of the cell list in place: out4 = {queries, queries whose stencil overflows the staging
 // area, queries whose stencil holds fewer than 2.5 (k+1) points (too few to vouch for k+1 within one cell edge), sum over the other queries of the non-empty cells in their
 // 27-cell stencil} -- what decides between the plain and the density-adaptive sweep before anything is swept
 int pct_item_census(pct_ctx* ctx, int32_t k, unsigned long long out4[4]);
 // pct_levels.hip; fuse_par: every pass fits the rows it answered, into the pinned slots of this parity (null: no fits)
-int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps, const int* fuse_par);
+int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps, const int* fuse_par, pct_call_clock* clock);
 // pct_tree.hip; expect_bbox: the box a remembered verdict of PCT_KNN_AUTO was given for (null: any cloud)
 int pct_build_tree(pct_ctx* ctx, int32_t k, double eps, const float* expect_bbox, TreeVerdict* out);
-int pct_launch_knn_tree(pct_ctx* ctx, int32_t k, double eps, bool want_dist);
+int pct_launch_knn_tree(pct_ctx* ctx, int32_t k, double eps, bool want_dist, pct_call_clock* clock);
 int pct_launch_export_neighbors(pct_ctx* ctx, int64_t begin, int64_t end,
                                 int32_t* d_idx, float* d_dist, int32_t* d_cnt);
 // fit (pct_fit.hip)

@@ -253,7 +253,7 @@ int launch_sweep(pct_ctx* ctx, const SweepPlan& p, const KnnArgs& a, int* redo, 
 
 // phase 0: fast sweep + exact sweep of what it flagged (or, exact_only, the exact sweep of every query);
 // phase 1: fast sweep only, the flagged rows stay in ctx->redo (level passes); phase 2: exact sweep of ctx->redo
-int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, int phase, bool want_dist, unsigned long long* stamps) {
+int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, int phase, bool want_dist, pct_call_clock* clock) {
     const int64_t n_rows = ctx->own_flag ? ctx->own_count : ctx->q_end - ctx->q_begin;
     const SweepPlan plan = plan_for(ctx, k, eps, false, exact_only, phase, want_dist);
     if (phase != 2) {
@@ -266,14 +266,14 @@ int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, in
     int* redo_count = &pct_dev(ctx)->sweep.redo_count;
     int* redo = (int*)ctx->redo.p;
     const dim3 block(64 * kWavesPerBlock);
-    if (stamps) {                  // the first kernel launched here stamps the end of the cell list; no fast sweep: knn_fast_ms = 0
-        const bool fast = plan.family != kNoSweep;
-        a.stamp_sweep = &stamps[PCT_ST_GRID_END];
-        a.stamp_exact = &stamps[fast ? PCT_ST_FAST_END : PCT_ST_GRID_END];
-        a.stamp_exact_also = fast ? nullptr : &stamps[PCT_ST_FAST_END];
-    }
+    // the words of the clock's boundaries (null: it records them): the first kernel launched here stamps the end of the cell
+    // list; no fast sweep: one reading for both, knn_fast_ms = 0
+    const bool fast = plan.family != kNoSweep;
+    a.stamp_sweep = clock->word(PCT_ST_GRID_END);
+    a.stamp_exact = clock->word(fast ? PCT_ST_FAST_END : PCT_ST_GRID_END);
+    a.stamp_exact_also = fast ? nullptr : clock->word(PCT_ST_FAST_END);
     PCT_TRY(launch_sweep(ctx, plan, a, redo, redo_count));
-    if (!stamps) PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FAST_END], ctx->stream));      // end of the dominant kernel
+    PCT_HIP(ctx, clock->boundary(PCT_ST_FAST_END, ctx->stream));      // end of the dominant kernel
     // exact pass: the flagged queries (device-side count, fixed grid) or, for testing, every query
     if (phase != 1) {
         const int64_t waves = exact_only ? n_rows : 32768;   // one query per wave for typical redo counts
@@ -294,7 +294,7 @@ int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, in
 // Neighbour sweep on the hierarchical cell list (pct_build_tree): fast sweep over its work items, then the exact sweep
 // on the same structure for what the fast one flagged.  The table is in Morton order (a sorted space like the uniform
 // list's: sorted4, owned_pos = identity, row_of).
-int pct_launch_knn_tree(pct_ctx* ctx, int32_t k, double eps, bool want_dist) {
+int pct_launch_knn_tree(pct_ctx* ctx, int32_t k, double eps, bool want_dist, pct_call_clock* clock) {
     if (ctx->level_mode || ctx->own_flag || ctx->q_begin != 0 || ctx->q_end != ctx->n)
         return pct_fail(ctx, PCT_ERR_INVALID, "the tree sweep takes whole clouds");
     const int64_t n_rows = ctx->n;
@@ -313,7 +313,7 @@ int pct_launch_knn_tree(pct_ctx* ctx, int32_t k, double eps, bool want_dist) {
     int* redo_count = &pct_dev(ctx)->sweep.redo_count;
     int* redo = (int*)ctx->redo.p;
     PCT_TRY(launch_sweep(ctx, plan, a, redo, redo_count));
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FAST_END], ctx->stream));
+    PCT_HIP(ctx, clock->boundary(PCT_ST_FAST_END, ctx->stream));
     const int blocks = (32768 + kWavesPerBlock - 1) / kWavesPerBlock;        // device-side count, fixed grid
     const int* list = exact_only ? nullptr : redo;
     if (k + 1 <= 64)

@@ -186,7 +186,7 @@ void swap_buf(T& a, T& b) { T t = a; a = b; b = t; }
 
 }  // namespace
 
-int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps, const int* fuse_par) {
+int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps, const int* fuse_par, pct_call_clock* clock) {
     ctx->pin->svd_rows[fuse_par ? *fuse_par : 0] = 0;                   // rows the passes' fits hand to k_fit_svd: summed over the passes of this call
     const int64_t nq = ctx->q_end - ctx->q_begin;
     if (ctx->n >= ((int64_t)1 << 29)) return pct_fail(ctx, PCT_ERR_INVALID, "the chained sweep handles clouds below 2^29 points");
@@ -219,7 +219,7 @@ int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps, const int* fuse_par) {
         const double t1 = debug ? tick() : 0;
         PCT_TRY(pct_reserve(ctx, &ctx->row_done, (size_t)owned * sizeof(int)));
         PCT_HIP(ctx, hipMemsetAsync(ctx->row_done.p, 0, (size_t)owned * sizeof(int), ctx->stream));
-        PCT_TRY(pct_launch_knn_grid(ctx, k, eps, exact, exact ? 0 : 1, true));      // (k_merge_rows below reads the distances)
+        PCT_TRY(pct_launch_knn_grid(ctx, k, eps, exact, exact ? 0 : 1, true, clock));      // (k_merge_rows below reads the distances)
         if (!exact) {
             // the stencil of a well-sized pass holds about 11 cells' worth of points on a surface
             PCT_LAUNCH(k_classify, dim3(1024), dim3(256), 0, ctx->stream, (const int*)ctx->row_done.p, (const int*)ctx->redo_m.p,

@@ -3,7 +3,9 @@
 // marker packet between two kernels that depend on each other anyway.  Instead the first kernel of every stage stores
 // the device's wall clock at its entry -- a marker, too, is processed when the previous kernel has retired -- and the
 // last block out of the step's last kernel stores the end.  This header holds the layout of a call's stamps, the device
-// helper (HIP compilations only) and the host's arithmetic on a stamp block, which tests/host/ compiles on its own.
+// helpers (HIP compilations only) and the host's arithmetic on a stamp block, which tests/host/ compiles on its own.
+// Which calls take stamps, who hands the words to the kernels and who reads them back is the call clock's business
+// (pct_clock.h): the host functions below are called from there and from nowhere else in the library.
 #pragma once
 
 #include <stdint.h>
@@ -69,8 +71,8 @@ inline pct_stage_ms pct_stamps_ms(const pct_stamp_block* b, int rate_khz) {
 // the two returns that precede the prologue's end -- it made the compiler load the work item, its cell's bounds and its
 // first row with vector loads where it had used scalar loads, for every block and whether or not a stamp was asked for:
 // k_knn_duo 1.1 % and k_knn_pair 0.5 - 1 % slower (profiles/r08_a_stage_stamps_ab.txt, block 3).  Behind the prologue the
-// kernels keep the loads and registers the parent's had; the grid's end is stamped two or three dependent load latencies
-// into block 0.  Block 0 never takes either of the two earlier returns in a stamped call: it holds work item 0, which is
+// kernels keep the loads and registers the parent's had; the grid's end gets its stamp two or three dependent load latencies
+// into block 0.  Block 0 never takes either of the two earlier returns in a call timed by stamps: it holds work item 0, which is
 // out of range only when there are no items (no owned rows: pct_stamps_apply), and split segments exist on the hierarchical
 // list alone, which is timed by events.
 __device__ __forceinline__ void pct_stamp(unsigned long long* slot, unsigned long long* also = nullptr) {

@@ -71,28 +71,53 @@ def torus(gpu):
     return gpu["shapes"].torus_random(20_000, seed=3)
 
 
+def stepwise_twice(capi, pts, k, algo, fast=True):
+    """Two sweeps on their own, each followed by its fit, on one handle: the sweep's call ends where the sweep does."""
+    h = capi.Handle(0)
+    try:
+        h.set_points(pts)
+        for call in ("first", "second"):
+            t0 = time.perf_counter()
+            h.knn(k, 0.0, algo)
+            t = h.timings()
+            h.fit()
+            wall = 1e3 * (time.perf_counter() - t0)
+            f = h.timings()
+            print("stepwise", call, t["grid_ms"], t["knn_ms"], t["knn_fast_ms"], t["total_ms"], f["fit_ms"], "wall %.4f" % wall)
+            assert t["grid_ms"] > 0 and t["knn_ms"] > 0 and f["fit_ms"] > 0
+            if fast:
+                assert 0 < t["knn_fast_ms"] <= t["knn_ms"]
+            else:
+                assert t["knn_fast_ms"] == 0
+            assert t["fit_ms"] == 0
+            assert abs(t["grid_ms"] + t["knn_ms"] - t["total_ms"]) <= REL * t["total_ms"]
+            assert t["total_ms"] + f["fit_ms"] <= wall
+    finally:
+        h.close()
+
+
 def test_bracket_fused_and_stepwise(gpu, torus):
     capi = gpu["capi"]
     saved = _without_event_switch()
     try:
         fused_twice(capi, torus, K, what="fused")
-        h = capi.Handle(0)
-        try:
-            h.set_points(torus)
-            for call in ("first", "second"):
-                t0 = time.perf_counter()
-                h.knn(K, 0.0, capi.KNN_GRID)
-                t = h.timings()
-                h.fit()
-                wall = 1e3 * (time.perf_counter() - t0)
-                f = h.timings()
-                print("stepwise", call, t["grid_ms"], t["knn_ms"], t["knn_fast_ms"], t["total_ms"], f["fit_ms"], "wall %.4f" % wall)
-                assert t["grid_ms"] > 0 and t["knn_ms"] > 0 and 0 < t["knn_fast_ms"] <= t["knn_ms"] and f["fit_ms"] > 0
-                assert t["fit_ms"] == 0
-                assert abs(t["grid_ms"] + t["knn_ms"] - t["total_ms"]) <= REL * t["total_ms"]
-                assert t["total_ms"] + f["fit_ms"] <= wall
-        finally:
-            h.close()
+        stepwise_twice(capi, torus, K, capi.KNN_GRID)
+    finally:
+        _restore(saved)
+
+
+@pytest.mark.parametrize("route", ["grid", "brute"])
+def test_sweep_on_its_own_under_events(gpu, torus, route):
+    """PCT_TIME_EVENTS=1: the sweep's call ends at its sweep-end event -- fit_ms = 0, grid + knn = total; the exhaustive
+    sweep (2 000 points) has no fast sweep."""
+    capi = gpu["capi"]
+    saved = _without_event_switch()
+    os.environ["PCT_TIME_EVENTS"] = "1"
+    try:
+        if route == "grid":
+            stepwise_twice(capi, torus, K, capi.KNN_GRID)
+        else:
+            stepwise_twice(capi, gpu["shapes"].torus_random(2000, seed=6), K, capi.KNN_BRUTE, fast=False)
     finally:
         _restore(saved)
 
@@ -264,3 +289,110 @@ def test_other_routes_keep_their_events(gpu):
             assert t["grid_ms"] > 0 and t["knn_ms"] > 0 and t["fit_ms"] > 0
     finally:
         h.close()
+
+
+def _owned_fit_bits(capi, pts, begin, end, events, what, env=None):
+    """Two fused PCT_KNN_GRID calls on a handle that owns rows [begin, end), each inside its bracket, with the stamps or
+    (events) with PCT_TIME_EVENTS=1; the fit of the owned rows."""
+    saved = _without_event_switch()
+    saved_env = {name: os.environ.pop(name, None) for name in (env or {})}
+    try:
+        os.environ.update(env or {})
+        if events:
+            os.environ["PCT_TIME_EVENTS"] = "1"
+        h = capi.Handle(0)
+        try:
+            h.set_points(pts)
+            if (begin, end) != (0, len(pts)):
+                h.set_query_range(begin, end)
+            for call in ("first", "second"):
+                t0 = time.perf_counter()
+                h.curvature(K, 0.0, capi.KNN_GRID)
+                wall = 1e3 * (time.perf_counter() - t0)
+                bracket(h.timings(), wall, f"{what} {'events' if events else 'stamps'} {call}")
+            return h.get_fit(begin, end)
+        finally:
+            h.close()
+    finally:
+        for name, value in saved_env.items():
+            os.environ.pop(name, None)
+            if value is not None:
+                os.environ[name] = value
+        _restore(saved)
+
+
+def test_begin_falls_back_behind_a_cull_pass(gpu, torus):
+    """A handle that owns the first quarter of a float32 cloud: its build starts with the cull pass, which takes no stamp,
+    so the call that opened on stamps marks its begin with an event and goes on with events."""
+    capi = gpu["capi"]
+    got = [_owned_fit_bits(capi, torus, 0, len(torus) // 4, events, "cull") for events in (False, True)]
+    for x, y in zip(*got):
+        assert x.shape == y.shape and np.array_equal(x, y, equal_nan=True)
+
+
+def test_begin_falls_back_behind_a_clearing_fill(gpu, torus):
+    """PCT_GRID_ATOMIC=1: the second call builds from the caller's rows with per-point atomics, so its first launch is a
+    clearing fill (the first call's is k_pack, which takes the begin stamp)."""
+    _owned_fit_bits(gpu["capi"], torus, 0, len(torus), False, "atomic build", env={"PCT_GRID_ATOMIC": "1"})
+
+
+@pytest.mark.parametrize("route", ["tree", "levels", "brute"])
+def test_routes_that_never_take_stamps(gpu, torus, route):
+    """The hierarchical list, the chained sweep (which fits inside its passes: its fit stage may be empty) and the
+    exhaustive sweep (2 000 points, no fast sweep) are timed by events whatever was asked."""
+    capi = gpu["capi"]
+    algo = {"tree": capi.KNN_TREE, "levels": capi.KNN_GRID_LEVELS, "brute": capi.KNN_BRUTE}[route]
+    pts = gpu["shapes"].torus_random(2000, seed=6) if route == "brute" else torus
+    saved = _without_event_switch()
+    h = capi.Handle(0)
+    try:
+        h.set_points(pts)
+        for call in ("first", "second"):
+            t0 = time.perf_counter()
+            h.curvature(K, 0.0, algo)
+            wall = 1e3 * (time.perf_counter() - t0)
+            t = h.timings()
+            print(route, call, {f: t[f] for f in ("algo", "grid_ms", "knn_ms", "knn_fast_ms", "fit_ms", "total_ms")}, "wall %.4f" % wall)
+            assert t["grid_ms"] > 0 and t["knn_ms"] > 0 and t["fit_ms"] >= 0
+            assert abs(t["grid_ms"] + t["knn_ms"] + t["fit_ms"] - t["total_ms"]) <= REL * t["total_ms"]
+            assert t["total_ms"] <= wall
+            if route == "brute":
+                assert t["knn_fast_ms"] == 0
+            elif route == "tree":       # (the chained sweep's table is in public space: no knn_fast_ms is reported for it)
+                assert 0 < t["knn_fast_ms"] <= t["knn_ms"]
+    finally:
+        h.close()
+        _restore(saved)
+
+
+K_MAX = 511     # PCT_K_MAX (csrc/pct_internal.h)
+
+
+def test_refused_call_behind_a_pending_one(gpu, torus):
+    """Async mode: a call the library refuses before it enqueues anything (k out of range) finds nothing to undo: the
+    record on the handle is still the good call's and the handle goes on as a blocking one's would.  (The stage fields of
+    that record are not checked: after a refusal the handle reports its current record, whose times are the last drained
+    call's -- none on this handle.)"""
+    capi = gpu["capi"]
+    saved = _without_event_switch()
+    h, ref = capi.Handle(0), capi.Handle(0)
+    try:
+        ref.set_points(torus)
+        ref.curvature(K, 0.0, capi.KNN_GRID)
+        want = ref.get_fit(0, len(torus))
+        h.set_async(True)
+        h.set_points(torus)
+        h.curvature(K, 0.0, capi.KNN_GRID)
+        with pytest.raises(ValueError):
+            h.curvature(K_MAX + 1, 0.0, capi.KNN_GRID)
+        t = h.stage_times_done().as_dict()
+        print({f: t[f] for f in ("grid_points", "grid_ms", "knn_ms", "knn_fast_ms", "fit_ms", "total_ms")})
+        assert t["grid_points"] == len(torus)
+        h.curvature(K, 0.0, capi.KNN_GRID)
+        h.synchronize()
+        for x, y in zip(h.get_fit(0, len(torus)), want):
+            assert x.shape == y.shape and np.array_equal(x, y, equal_nan=True)
+    finally:
+        h.close()
+        ref.close()
+        _restore(saved)
