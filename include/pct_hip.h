@@ -338,6 +338,49 @@ int pct_point_area_profile(pct_ctx* ctx, double out[2]);
  * table in place: PCT_ERR_INVALID "no fit results" / "no point areas" otherwise. */
 int pct_point_energies(pct_ctx* ctx, int32_t closed_only, double out[4]);
 
+/* Per-point surface frames from the quadric fit.  The fit builds, for every row, a tangent-plane rotation R and a patch
+ * z = A a^2 + B b^2 + C ab + D a + E b + F, and keeps K and H.  pct_point_frames keeps the rest: the fitted normal, the
+ * principal curvatures k1 >= k2 (calculate_explicit_quadratic_curvatures returns them per call, pct:425-431) and their
+ * directions, and -- with a viewpoint -- one side of the surface for all rows.  It needs the resident table (else
+ * PCT_ERR_NO_NEIGHBORS) and the fit of that table (pct_fit / pct_curvature; else PCT_ERR_INVALID "no fit results", the
+ * condition of pct_point_energies).  Row i of the table, count_i = m valid neighbours:
+ *   block   Q_j = p_j - p_i, centred in the cloud's dtype (pct:641), float64 from there on;
+ *   R       the rotation pct_fit takes for this row (pct:270-312), from the same moments in the same order (PCT_FIT_JACOBI
+ *           applies as in the fit);
+ *   coefs   (A, B, C, D, E) = the row's float32 fit coefficients, widened to float64; nothing is fitted again;
+ *   patch normal   w = sqrt((1 + D D) + E E), m = (-D, -E, 1) / w: the unit normal of the patch at a = b = 0, on the +z
+ *           side of the rotated frame;
+ *   tangent basis  g2 = 1 + D D, g = sqrt(g2), e1 = (1, 0, D) / g, e2 = m x e1 = (-D E, g2, E) / (g w);
+ *   second fundamental form   for tangent vectors given by their first two components,
+ *           II(x, y) = ((2A xa ya + C (xa yb + xb ya)) + 2B xb yb) / w;
+ *   shape operator   the symmetric S = [[s11, s12], [s12, s22]], s11 = II(e1, e1), s12 = II(e1, e2), s22 = II(e2, e2); in
+ *           exact arithmetic tr S = 2H and det S = K of pct:416-419;
+ *   principal curvatures   h = (s11 + s22) / 2, d = (s11 - s22) / 2, r = sqrt(d d + s12 s12): k1 = h + r, k2 = h - r;
+ *   principal directions in the rotated frame   the rotation that annihilates s12, Jacobi's small root, no atan2:
+ *           t = s12 / (|d| + r), cj = 1 / sqrt(t t + 1), sj = t cj, (c, s) = (cj, sj) where d > 0 and (sj, cj) otherwise;
+ *           t1 = c e1 + s e2 belongs to k1, t2 = -s e1 + c e2 to k2.  r == 0 exactly (umbilic): t1 = e1, t2 = e2; such
+ *           rows are counted;
+ *   world frame   n = R^T m, d1 = R^T t1, d2 = R^T t2 (component i: (R[0][i] v0 + R[1][i] v1) + R[2][i] v2); d1 and d2
+ *           under the sign rule of pct_get_pca: the component of largest magnitude is positive, the first among equals;
+ *   viewpoint (optional)   v, three doubles in the cloud's own coordinates.  Where
+ *           ((vx - px) n0 + (vy - py) n1) + (vz - pz) n2 < 0, p = p_i in the cloud's native dtype widened:
+ *           n <- -n, (k1, k2) <- (-k2, -k1), (d1, d2) <- (d2, d1), flipped = 1;
+ *   without a viewpoint   n stays on the side the fit's own far-minus-near rule chose (pct:286-297) -- the side the fit's
+ *           H is signed against, which jumps from point to point -- and flipped = 0.  Either way H and k1, k2 are signed
+ *           relative to n: with a viewpoint, H_signed = flipped ? -H : H;
+ *   NaN rows   m < 2, a table entry outside the cloud, a non-finite R or coefficient: every output of the row is NaN and
+ *           flipped = 0.  Such rows are counted.
+ * A non-finite viewpoint: PCT_ERR_INVALID.  A new cloud, owned range, planting or fit drops the frames.  pct_timings is
+ * untouched: pct_point_frame_stats has the time. */
+int pct_point_frames(pct_ctx* ctx, const double* viewpoint /* 3 doubles or NULL */);
+/* Cloud rows [begin, end) of the owned range, float64 host arrays: normal (rows, 3), k12 (rows, 2) = [k1, k2], dirs
+ * (rows, 3, 2) C order with d1, d2 as columns (as pct_get_pca delivers its frame), flipped (rows) uint8; any pointer may
+ * be NULL.  PCT_ERR_INVALID without frames. */
+int pct_get_point_frames(pct_ctx* ctx, int64_t begin, int64_t end, double* normal, double* k12, double* dirs, uint8_t* flipped);
+/* Of the last pct_point_frames: out = {rows, NaN rows, flipped rows, umbilic rows}; *ms (may be NULL) the device
+ * milliseconds of its kernel (hipEvent). */
+int pct_point_frame_stats(pct_ctx* ctx, int64_t out[4], double* ms);
+
 /* ---- scan preparation (next row N4) ---------------------------------------- */
 /* Voxel-grid down-sampling of convert_asc_to_ply.py:20-51: voxel = floor(coordinate / voxel_size) evaluated in the
  * coordinates' own dtype as NumPy does (the _f32 form divides by (float)voxel_size in float32), the
@@ -392,6 +435,10 @@ int pct_format_float(double x, char* out32);
 /* The ASCII PLY of utils.py:538-551: header + one line 'x y z K H' per vertex, numbers as the reference's f-string
  * prints them. */
 int pct_write_ply_ascii(const char* path, const float* xyz, const float* gaussian, const float* mean, int64_t n);
+/* export_ply_with_curvature_and_normals (pct:699-726) without faces: header + one line 'x y z nx ny nz K H' per vertex
+ * (normals (n, 3) float32), numbers in pct_write_ply_ascii's format. */
+int pct_write_ply_ascii_normals(const char* path, const float* xyz, const float* normals, const float* gaussian,
+                                const float* mean, int64_t n);
 
 /* ---- multi-GPU exchange --------------------------------------------------------------------------
  * The reference is one process; here the cloud shards by point-index range over up to 8 GPUs, one process per GPU,

@@ -103,6 +103,9 @@ SIGNATURES = {
     "pct_point_area_stats": (C.c_int, [_p, _i64p]),
     "pct_point_area_profile": (C.c_int, [_p, _f64p]),
     "pct_point_energies": (C.c_int, [_p, C.c_int32, _f64p]),
+    "pct_point_frames": (C.c_int, [_p, _f64p]),
+    "pct_get_point_frames": (C.c_int, [_p, C.c_int64, C.c_int64, _f64p, _f64p, _f64p, _u8p]),
+    "pct_point_frame_stats": (C.c_int, [_p, _i64p, _f64p]),
     "pct_voxel_downsample": (C.c_int, [_p, _f64p, C.c_int64, C.c_double, _i64p, _i64p]),
     "pct_voxel_downsample_f32": (C.c_int, [_p, _f32p, C.c_int64, C.c_double, _i64p, _i64p]),
     "pct_surface_variation": (C.c_int, [_p, C.c_int32, _f32p]),
@@ -114,6 +117,7 @@ SIGNATURES = {
     "pct_matrix_norms_f32": (C.c_int, [_f32p, C.c_int64, _f64p]),
     "pct_matrix_norms_f64": (C.c_int, [_f64p, C.c_int64, _f64p]),
     "pct_write_ply_ascii": (C.c_int, [C.c_char_p, _f32p, _f32p, _f32p, C.c_int64]),
+    "pct_write_ply_ascii_normals": (C.c_int, [C.c_char_p, _f32p, _f32p, _f32p, _f32p, C.c_int64]),
     "pct_comm_unique_id": (C.c_int, [_p]),
     "pct_comm_init": (C.c_int, [_p, C.c_int32, C.c_int32, _p]),
     "pct_comm_destroy": (C.c_int, [_p]),
@@ -206,6 +210,19 @@ def write_ply_ascii(path, points, gaussian, mean):
     if len(g) != len(p) or len(m) != len(p):
         raise ValueError("one curvature value per point is required")
     if load().pct_write_ply_ascii(os.fsencode(path), _ptr(p, _f32p), _ptr(g, _f32p), _ptr(m, _f32p), len(p)) != PCT_OK:
+        raise OSError(f"cannot write {path!r}")
+
+
+def write_ply_ascii_normals(path, points, normals, gaussian, mean):
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    nr = np.ascontiguousarray(normals, dtype=np.float32)
+    g = np.ascontiguousarray(gaussian, dtype=np.float32)
+    m = np.ascontiguousarray(mean, dtype=np.float32)
+    if nr.shape != p.shape:
+        raise ValueError("one normal per point is required")
+    if len(g) != len(p) or len(m) != len(p):
+        raise ValueError("one curvature value per point is required")
+    if load().pct_write_ply_ascii_normals(os.fsencode(path), _ptr(p, _f32p), _ptr(nr, _f32p), _ptr(g, _f32p), _ptr(m, _f32p), len(p)) != PCT_OK:
         raise OSError(f"cannot write {path!r}")
 
 
@@ -571,6 +588,32 @@ class Handle:
         self._check(self._lib.pct_point_area_profile(self._h, _ptr(prof, _f64p)))
         return {"rows": int(out[0]), "closed": int(out[1]), "nan": int(out[2]), "overflow": int(out[3]),
                 "ms": float(prof[0]), "survivors": int(prof[1])}
+
+    # -- surface frames from the resident fit: fitted normals, k1 / k2 and their directions ---------------------------
+    def point_frames(self, viewpoint=None):
+        """``pct_point_frames``: normal, k1 >= k2 and the principal directions of every owned row, from the resident table
+        and its fit; with ``viewpoint`` (three numbers in the cloud's coordinates) every normal is turned to its side.
+        Kept on the device (``get_point_frames``)."""
+        v = None if viewpoint is None else np.ascontiguousarray(viewpoint, dtype=np.float64).reshape(3)
+        self._check(self._lib.pct_point_frames(self._h, _ptr(v, _f64p)))
+
+    def get_point_frames(self, begin, end, normal=True, k=True, dirs=True, flipped=True):
+        """(normal (rows, 3), k (rows, 2) = [k1, k2], dirs (rows, 3, 2), flipped (rows,) uint8) of cloud rows [begin, end);
+        ``None`` for what was not asked for."""
+        rows = int(end) - int(begin)
+        n = np.empty((rows, 3), np.float64) if normal else None
+        kk = np.empty((rows, 2), np.float64) if k else None
+        d = np.empty((rows, 3, 2), np.float64) if dirs else None
+        f = np.empty(rows, np.uint8) if flipped else None
+        self._check(self._lib.pct_get_point_frames(self._h, int(begin), int(end), _ptr(n, _f64p), _ptr(kk, _f64p), _ptr(d, _f64p), _ptr(f, _u8p)))
+        return n, kk, d, f
+
+    def point_frame_stats(self):
+        """Of the last ``point_frames``: {rows, nan, flipped, umbilic, ms (device time of its kernel)}."""
+        out = np.zeros(4, np.int64)
+        ms = np.zeros(1, np.float64)
+        self._check(self._lib.pct_point_frame_stats(self._h, _ptr(out, _i64p), _ptr(ms, _f64p)))
+        return {"rows": int(out[0]), "nan": int(out[1]), "flipped": int(out[2]), "umbilic": int(out[3]), "ms": float(ms[0])}
 
     def point_energies(self, closed_only=False):
         """``pct_point_energies``: (bending, stretching, area, n_used) over the owned rows -- the closed ones only with

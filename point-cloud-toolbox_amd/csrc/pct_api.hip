@@ -240,7 +240,7 @@ void pct_destroy(pct_ctx* ctx) {
                       &ctx->tree_codes, &ctx->tree_vals, &ctx->tree_lvl, &ctx->tree_head, &ctx->tree_marks, &ctx->tree_seg, &ctx->tree_runs, &ctx->tree_range, &ctx->tree_bucket, &ctx->tree_tmp,
                       &ctx->pca, &ctx->pca_aux, &ctx->pca_nbr, &ctx->pca_orig,
                       &ctx->bin_rec, &ctx->bin_mat, &ctx->bin_plan, &ctx->bin_base,
-                      &ctx->area, &ctx->area_closed, &ctx->area_nverts, &ctx->area_over, &ctx->stamp_tickets};
+                      &ctx->area, &ctx->area_closed, &ctx->area_nverts, &ctx->area_over, &ctx->frame, &ctx->frame_flip, &ctx->stamp_tickets};
     for (pct_buf* b : all) pct_release(b);
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     for (auto& e : ctx->ev)
@@ -273,6 +273,7 @@ static int new_cloud(pct_ctx* ctx, int64_t n) {
     ctx->pca_valid = false;
     ctx->ball_valid = false;
     ctx->area_valid = false;
+    ctx->frame_valid = false;
     ctx->has_f64 = false;
     ctx->no_cull = ctx->culled = false;
     ctx->retries = 0;
@@ -341,7 +342,7 @@ int pct_set_query_range(pct_ctx* ctx, int64_t begin, int64_t end) {
     ctx->q_end = end;
     ctx->slab_parts = ctx->slab_part = 0;
     ctx->slab_split_valid = false;
-    ctx->knn_valid = ctx->fit_valid = ctx->area_valid = ctx->grid_valid = false;   // the cell order depends on the owned range
+    ctx->knn_valid = ctx->fit_valid = ctx->area_valid = ctx->frame_valid = ctx->grid_valid = false;   // the cell order depends on the owned range
     ctx->no_cull = false;
     ctx->retries = 0;
     return PCT_OK;
@@ -359,7 +360,7 @@ int pct_set_query_slab(pct_ctx* ctx, int32_t part, int32_t parts) {
     ctx->slab_parts = parts >= 1 ? parts : 0;     // (one part: the whole cloud as one slab -- the same code path, for a world of one rank)
     ctx->slab_part = parts >= 1 ? part : 0;
     ctx->slab_split_valid = false;
-    ctx->knn_valid = ctx->fit_valid = ctx->area_valid = ctx->grid_valid = false;
+    ctx->knn_valid = ctx->fit_valid = ctx->area_valid = ctx->frame_valid = ctx->grid_valid = false;
     ctx->no_cull = false;
     ctx->retries = 0;
     return PCT_OK;
@@ -550,7 +551,7 @@ static int run_knn(pct_ctx* ctx, int32_t k, double eps, int32_t asked, pct_call_
     const int32_t algo = rq.algo;
     RouteSwitches sw = {false, false};             // (they matter to PCT_KNN_AUTO only)
     if (rq.auto_req) sw = RouteSwitches{pct_getenv("PCT_NO_TREE") != nullptr, pct_getenv("PCT_NO_AUTO_LEVELS") != nullptr};
-    ctx->knn_valid = ctx->fit_valid = ctx->area_valid = false;     // a new planting drops the fit and the areas
+    ctx->knn_valid = ctx->fit_valid = ctx->area_valid = ctx->frame_valid = false;     // a new planting drops the fit and the areas
     ctx->k = k;
     ctx->eps = eps;
     PCT_TRY(clock.open(ctx, rq.auto_req, algo == PCT_KNN_GRID || algo == PCT_KNN_GRID_EXACT, kind));
@@ -661,6 +662,7 @@ int pct_fit(pct_ctx* ctx) {
     ctx->tm.fit_svd_rows = ctx->pin->svd_rows[0];
     ctx->fit_rows = ctx->q_end - ctx->q_begin;
     ctx->fit_valid = true;
+    ctx->frame_valid = false;          // (frames hold what the fit before this one left)
     ctx->fit_cloud_aligned = true;
     return PCT_OK;
 }
@@ -699,6 +701,7 @@ static int curvature_async(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
     ctx->pend.on = true;
     ctx->fit_rows = ctx->q_end - ctx->q_begin;
     ctx->fit_valid = true;
+    ctx->frame_valid = false;          // (frames hold what the fit before this one left)
     ctx->fit_cloud_aligned = true;
     return PCT_OK;
 }
@@ -721,6 +724,7 @@ int pct_curvature(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
     ctx->tm_done = ctx->tm;
     ctx->fit_rows = ctx->q_end - ctx->q_begin;
     ctx->fit_valid = true;
+    ctx->frame_valid = false;          // (frames hold what the fit before this one left)
     ctx->fit_cloud_aligned = true;
     return PCT_OK;
 }
@@ -829,6 +833,7 @@ int pct_fit_indices(pct_ctx* ctx, const int32_t* idx, const int32_t* count, cons
     ctx->fit_rows = rows;
     ctx->fit_row_order = false;
     ctx->fit_valid = true;
+    ctx->frame_valid = false;          // (frames hold what the fit before this one left)
     ctx->fit_cloud_aligned = false;   // (a resident neighbour table is untouched and stays valid)
     return PCT_OK;
 }
@@ -1027,6 +1032,7 @@ int pct_fit_ball(pct_ctx* ctx, const int64_t* self_rows, int64_t m, int32_t* use
     ctx->fit_rows = m;
     ctx->fit_row_order = false;
     ctx->fit_valid = true;
+    ctx->frame_valid = false;          // (frames hold what the fit before this one left)
     ctx->fit_cloud_aligned = false;
     if (m == 0) return PCT_OK;
     PCT_TRY(pct_reserve_fit(ctx, m));
@@ -1049,6 +1055,7 @@ int pct_fit_ball(pct_ctx* ctx, const int64_t* self_rows, int64_t m, int32_t* use
     ctx->tm.fit_ms = ev_ms(ctx, PCT_EV_FIT_BEGIN, PCT_EV_FIT_END);
     ctx->tm.fit_svd_rows = ctx->pin->svd_rows[0];
     ctx->fit_valid = true;
+    ctx->frame_valid = false;          // (frames hold what the fit before this one left)
     return PCT_OK;
 }
 
@@ -1172,6 +1179,71 @@ int pct_point_energies(pct_ctx* ctx, int32_t closed_only, double out[4]) {
     PCT_TRY(pct_launch_point_energies(ctx, closed_only != 0, d_part, d_part + (size_t)nblk * 4));
     PCT_HIP(ctx, hipMemcpyAsync(out, d_part + (size_t)nblk * 4, 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PCT_OK;
+}
+
+// ---- per-point surface frames from the resident fit (pct_frame.hip) ----------------------------------------------------
+int pct_point_frames(pct_ctx* ctx, const double* viewpoint) {
+    PCT_TRY(begin_call(ctx));
+    PCT_TRY(refuse_in_slab_mode(ctx, "pct_point_frames"));
+    if (!ctx->knn_valid) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "plant the neighbour table first (pct_knn)");
+    const int64_t rows = ctx->q_end - ctx->q_begin;
+    if (!ctx->fit_valid || !ctx->fit_cloud_aligned || ctx->fit_rows != rows) return pct_fail(ctx, PCT_ERR_INVALID, "no fit results");
+    if (viewpoint && !(isfinite(viewpoint[0]) && isfinite(viewpoint[1]) && isfinite(viewpoint[2])))
+        return pct_fail(ctx, PCT_ERR_INVALID, "pct_point_frames: the viewpoint is not finite");
+    ctx->frame_valid = false;
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FRAME_BEGIN], ctx->stream));
+    PCT_TRY(pct_launch_point_frames(ctx, viewpoint));
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FRAME_END], ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));              // the call's one wait: results, statistics words, events
+    const unsigned long long* w = ctx->pin->frame_words;
+    ctx->frame_rows = rows;
+    ctx->frame_stats[0] = rows;
+    for (int i = 0; i < 3; ++i) ctx->frame_stats[1 + i] = (int64_t)w[i];
+    ctx->frame_ms = ev_ms(ctx, PCT_EV_FRAME_BEGIN, PCT_EV_FRAME_END);
+    ctx->frame_valid = true;
+    return PCT_OK;
+}
+
+// frames in table-row order refer to the table they were taken from
+static bool frames_resident(const pct_ctx* ctx) { return ctx->frame_valid && (!ctx->frame_row_order || ctx->knn_valid); }
+
+int pct_get_point_frames(pct_ctx* ctx, int64_t begin, int64_t end, double* normal, double* k12, double* dirs, uint8_t* flipped) {
+    PCT_TRY(begin_call(ctx));
+    PCT_TRY(refuse_in_slab_mode(ctx, "pct_get_point_frames"));
+    if (!frames_resident(ctx)) return pct_fail(ctx, PCT_ERR_INVALID, "no point frames (pct_point_frames)");
+    if (begin < ctx->q_begin || end > ctx->q_begin + ctx->frame_rows || begin > end)
+        return pct_fail(ctx, PCT_ERR_INVALID, "rows [%lld,%lld) outside the owned range", (long long)begin, (long long)end);
+    const int64_t rows = end - begin, off = begin - ctx->q_begin, all = ctx->frame_rows;
+    if (rows == 0) return PCT_OK;
+    const double* d_n = (const double*)ctx->frame.p + off * 3;
+    const double* d_k = (const double*)ctx->frame.p + all * 3 + off * 2;
+    const double* d_d = (const double*)ctx->frame.p + all * 5 + off * 6;
+    const unsigned char* d_f = (const unsigned char*)ctx->frame_flip.p + 64 + off;
+    if (ctx->frame_row_order) {         // table-row order: gather the requested public rows first
+        PCT_TRY(pct_reserve(ctx, &ctx->stage_a, (size_t)rows * 3 * sizeof(double)));
+        PCT_TRY(pct_reserve(ctx, &ctx->stage_b, (size_t)rows * 2 * sizeof(double)));
+        PCT_TRY(pct_reserve(ctx, &ctx->stage_d, (size_t)rows * 6 * sizeof(double)));
+        PCT_TRY(pct_reserve(ctx, &ctx->stage_c, (size_t)rows));
+        PCT_TRY(pct_launch_gather_frames(ctx, off, rows, normal ? (double*)ctx->stage_a.p : nullptr, k12 ? (double*)ctx->stage_b.p : nullptr,
+                                         dirs ? (double*)ctx->stage_d.p : nullptr, flipped ? (unsigned char*)ctx->stage_c.p : nullptr));
+        d_n = (const double*)ctx->stage_a.p;
+        d_k = (const double*)ctx->stage_b.p;
+        d_d = (const double*)ctx->stage_d.p;
+        d_f = (const unsigned char*)ctx->stage_c.p;
+    }
+    if (normal) PCT_HIP(ctx, hipMemcpyAsync(normal, d_n, (size_t)rows * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (k12) PCT_HIP(ctx, hipMemcpyAsync(k12, d_k, (size_t)rows * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (dirs) PCT_HIP(ctx, hipMemcpyAsync(dirs, d_d, (size_t)rows * 6 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (flipped) PCT_HIP(ctx, hipMemcpyAsync(flipped, d_f, (size_t)rows, hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PCT_OK;
+}
+
+int pct_point_frame_stats(pct_ctx* ctx, int64_t out[4], double* ms) {
+    if (!ctx || !out) return PCT_ERR_INVALID;
+    for (int i = 0; i < 4; ++i) out[i] = ctx->frame_valid ? ctx->frame_stats[i] : 0;
+    if (ms) *ms = ctx->frame_valid ? ctx->frame_ms : 0.0;
     return PCT_OK;
 }
 

@@ -120,6 +120,7 @@ struct pct_pinned {
     // by parity: the stamps of a call timed by the device clock, mirrored whole by the step's last kernel; the host clears
     // the end stamp before it enqueues the call and reads the block once that word is non-zero (pct_stamp.h)
     alignas(64) pct_stamp_block stamps[2];
+    alignas(64) unsigned long long frame_words[8];   // pct_point_frames (pct_frame.hip): NaN rows, flipped rows, umbilic rows
 };
 static_assert(sizeof(pct_pinned) <= 4096, "pct_create allocates 4096 bytes");
 
@@ -130,6 +131,7 @@ enum pct_event {                           // ctx->ev
     PCT_EV_FIT_BEGIN, PCT_EV_FIT_END,      // a fit on its own (pct_fit and its siblings)
     PCT_EV_SCAN_TOTALS,                    // the cell list's scan totals are in pinned memory (pct_build_grid)
     PCT_EV_AREA_BEGIN, PCT_EV_AREA_END,    // pct_point_areas
+    PCT_EV_FRAME_BEGIN, PCT_EV_FRAME_END,  // pct_point_frames
     PCT_EV_COUNT
 };
 
@@ -324,6 +326,15 @@ struct pct_ctx {
     int64_t area_rows = 0;
     int64_t area_stats[4] = {0, 0, 0, 0};   // rows, closed rows, NaN rows, overflow rows
     double area_profile[2] = {0, 0};        // device milliseconds of the two kernels, neighbours past the rejection test
+
+    // per-point surface frames (pct_frame.hip) of the owned rows of the resident table and its fit
+    pct_buf frame;         // double (owned): normal (rows, 3) | k1 k2 (rows, 2) | directions (rows, 3, 2)
+    pct_buf frame_flip;    // eight statistics words, then uint8 (owned): the viewpoint turned the row's normal
+    bool frame_valid = false;
+    bool frame_row_order = false;  // in neighbour-table row order (as fit_row_order), else public order from q_begin
+    int64_t frame_rows = 0;
+    int64_t frame_stats[4] = {0, 0, 0, 0};  // rows, NaN rows, flipped rows, umbilic rows
+    double frame_ms = 0;                    // device milliseconds of its kernel
 };
 
 int pct_fail(pct_ctx* ctx, int code, const char* fmt, ...);
@@ -496,6 +507,11 @@ int pct_launch_mesh_energies(pct_ctx* ctx, const double* d_v, const int* d_tri, 
 int pct_launch_point_areas(pct_ctx* ctx);
 int pct_launch_gather_areas(pct_ctx* ctx, int64_t first, int64_t rows, double* d_area, unsigned char* d_closed, int* d_nverts);
 int pct_launch_point_energies(pct_ctx* ctx, bool closed_only, double* d_partial, double* d_out4);
+// pct_frame.hip: surface frames of the owned rows of the resident table from its resident fit (statistics words to
+// ctx->pin->frame_words; viewpoint: three finite doubles or null), and their public rows gathered out of table-row order
+int pct_launch_point_frames(pct_ctx* ctx, const double* viewpoint);
+int pct_launch_gather_frames(pct_ctx* ctx, int64_t first, int64_t rows, double* d_normal, double* d_k12, double* d_dirs,
+                             unsigned char* d_flipped);
 int pct_voxel_downsample_device(pct_ctx* ctx, const void* d_xyz, bool f64, int64_t n, double voxel, int64_t* d_out, int64_t* count);
 int pct_launch_surface_variation(pct_ctx* ctx, float* d_out);
 // PCA principal curvatures (pct_pca.hip).  The sweep fetches up to PCT_PCA_EXTRA candidates beyond k per point, re-ranked

@@ -6,6 +6,7 @@
 //   pct_write_ply_ascii            : the ASCII PLY with K/H the reference writes one f-string per vertex
 //                                    (/root/reference/utils.py:538-551); numbers formatted exactly as the f-string
 //                                    does: repr(float(np.float32 value))
+//   pct_write_ply_ascii_normals    : the same with nx ny nz between the coordinates and the curvatures
 // Pure C++17 (no device code); lives in the same shared library so the ctypes shim has one ABI.
 #include <charconv>
 #include <cmath>
@@ -263,12 +264,15 @@ int pct_text_load(const char* path, int64_t rows, int32_t cols, double* out) {
 
 int pct_format_float(double x, char* out32) { return out32 ? format_py_float(x, out32) : 0; }
 
-int pct_write_ply_ascii(const char* path, const float* xyz, const float* gaussian, const float* mean, int64_t n) {
+// One vertex per line: the coordinates, `normals` (n, 3; null: none), K and H, numbers as the reference's f-string prints them
+static int write_ply_vertices(const char* path, const float* xyz, const float* normals, const float* gaussian, const float* mean,
+                              int64_t n) {
     if (!path || !xyz || !gaussian || !mean || n < 0) return PCT_ERR_INVALID;
     FILE* f = fopen(path, "wb");
     if (!f) return PCT_ERR_INVALID;
-    fprintf(f, "ply\nformat ascii 1.0\nelement vertex %lld\nproperty float x\nproperty float y\nproperty float z\n"
-               "property float gaussian_curvature\nproperty float mean_curvature\nend_header\n", (long long)n);   // utils.py:539-547
+    fprintf(f, "ply\nformat ascii 1.0\nelement vertex %lld\nproperty float x\nproperty float y\nproperty float z\n%s"
+               "property float gaussian_curvature\nproperty float mean_curvature\nend_header\n", (long long)n,
+            normals ? "property float nx\nproperty float ny\nproperty float nz\n" : "");   // utils.py:539-547
     int threads = (int)std::thread::hardware_concurrency();
     if (threads < 1) threads = 1;
     if (threads > 32) threads = 32;
@@ -279,13 +283,18 @@ int pct_write_ply_ascii(const char* path, const float* xyz, const float* gaussia
         th.emplace_back([&, t] {
             const int64_t lo = n * t / threads, hi = n * (t + 1) / threads;
             std::string& s = parts[t];
-            s.reserve((size_t)(hi - lo) * 64);
+            s.reserve((size_t)(hi - lo) * (normals ? 104 : 64));
             char buf[40];
             for (int64_t i = lo; i < hi; ++i) {
-                const float v[5] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], gaussian[i], mean[i]};
-                for (int j = 0; j < 5; ++j) {
+                float v[8] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+                int cols = 3;
+                if (normals)
+                    for (int j = 0; j < 3; ++j) v[cols++] = normals[3 * i + j];
+                v[cols++] = gaussian[i];
+                v[cols++] = mean[i];
+                for (int j = 0; j < cols; ++j) {
                     s.append(buf, (size_t)format_py_float((double)v[j], buf));
-                    s.push_back(j == 4 ? '\n' : ' ');
+                    s.push_back(j == cols - 1 ? '\n' : ' ');
                 }
             }
         });
@@ -294,6 +303,16 @@ int pct_write_ply_ascii(const char* path, const float* xyz, const float* gaussia
     for (auto& s : parts) ok = ok && fwrite(s.data(), 1, s.size(), f) == s.size();
     ok = fclose(f) == 0 && ok;
     return ok ? PCT_OK : PCT_ERR_INVALID;
+}
+
+int pct_write_ply_ascii(const char* path, const float* xyz, const float* gaussian, const float* mean, int64_t n) {
+    return write_ply_vertices(path, xyz, nullptr, gaussian, mean, n);
+}
+
+int pct_write_ply_ascii_normals(const char* path, const float* xyz, const float* normals, const float* gaussian,
+                                const float* mean, int64_t n) {
+    if (!normals) return PCT_ERR_INVALID;
+    return write_ply_vertices(path, xyz, normals, gaussian, mean, n);
 }
 
 }  // extern "C"

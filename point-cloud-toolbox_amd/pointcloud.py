@@ -191,8 +191,11 @@ class PointCloud:
         self._device_curv = None
         self._plant_token = 0
         self._fit_token = -1
+        self._fit_serial = 0            # counts the fits of this object: frames belong to one of them
         self._area_token = -1           # the planting whose per-point areas are on the device
         self._area_cache = None
+        self._frame_key = None          # (planting, fit, viewpoint) whose surface frames are on the device
+        self._frame_cache = None
         self.eps = None
         self.collect_stats = False      # sweep statistics in last_timings (costs atomics)
 
@@ -354,6 +357,7 @@ class PointCloud:
         self._device_curv = None
         self._fit_on_device = True
         self._fit_token = self._plant_token
+        self._fit_serial += 1
         self.last_timings = h.timings()
 
     @property
@@ -450,6 +454,55 @@ class PointCloud:
             self.last_area_stats = h.point_area_stats()
         bending, stretching, area, _ = h.point_energies(closed_only)
         return bending, stretching, area
+
+    # ------------------------------------------------ surface frames: what the quadric fit knows beyond K and H
+    def _frames_on_device(self, key):
+        return self._handle is not None and self._table_on_device and self._fit_on_device and self._frame_key == key
+
+    def compute_surface_frames(self, viewpoint=None):
+        """Per-point frames of the fitted patches (``pct_point_frames``, include/pct_hip.h): the unit normal, the principal
+        curvatures k1 >= k2 (what ``calculate_explicit_quadratic_curvatures`` returns per call, pct:425-431) and their
+        directions.  ``viewpoint`` -- three numbers in the cloud's coordinates, a scanner position -- turns every normal
+        to its side; H and k1, k2 are signed relative to the normal, so ``H_signed_quadratic`` then has one sign
+        convention over the whole cloud, which ``H_quadratic`` (signed by each row's far-minus-near rule, pct:286-297)
+        does not.  Without it the normals stay on the side the fit chose.  Runs the fit first where it is not resident for
+        the planted table.  Returns ``(normals (N, 3), k1 (N,), k2 (N,), directions (N, 3, 2))``, float64, and sets
+        ``normals``, ``k1_quadratic``, ``k2_quadratic``, ``principal_directions_quadratic``, ``normals_flipped``,
+        ``H_signed_quadratic`` and ``last_frame_stats``."""
+        h = self._planted_table()
+        if not (self._fit_on_device and self._fit_token == self._plant_token and self._user_coefs is None):
+            self.fit_explicit_quadratic_surfaces_to_neighborhoods()
+            h = self._planted_table()
+        view = None if viewpoint is None else tuple(float(x) for x in np.asarray(viewpoint, np.float64).reshape(3))
+        key = (self._plant_token, self._fit_serial, view)
+        if not self._frames_on_device(key) or self._frame_cache is None:
+            h.point_frames(view)
+            self._frame_key = key
+            self.last_frame_stats = h.point_frame_stats()
+            normal, k12, dirs, flipped = h.get_point_frames(0, self._n_dev)
+            H = h.get_fit(0, self._n_dev, coefs=False, K=False, H2=False)[2]
+            self._frame_cache = (normal, np.ascontiguousarray(k12[:, 0]), np.ascontiguousarray(k12[:, 1]), dirs,
+                                 flipped.astype(bool), np.where(flipped.astype(bool), -H, H).astype(np.float32))
+        normal, k1, k2, dirs, flipped, H_signed = self._frame_cache
+        self.normals = normal
+        self.k1_quadratic, self.k2_quadratic = k1, k2
+        self.principal_directions_quadratic = dirs
+        self.normals_flipped = flipped
+        self.H_signed_quadratic = H_signed
+        return normal, k1, k2, dirs
+
+    def compute_normals(self):
+        """pct:691-697 -- there through PyVista and a Delaunay mesh; here the normals of the fitted patches
+        (``compute_surface_frames`` without a viewpoint).  Sets ``self.normals``."""
+        self.compute_surface_frames()
+
+    def export_ply_with_curvature_and_normals(self, filename):
+        """pct:699-726 without faces: ASCII PLY vertices ``x y z nx ny nz gaussian_curvature mean_curvature``.  Computes
+        the normals first when ``self.normals`` is missing or is not one normal per point (pct:701-702)."""
+        normals = getattr(self, "normals", None)
+        if normals is None or np.shape(normals) != (len(self.points), 3):
+            self.compute_normals()
+        _capi.write_ply_ascii_normals(filename, np.asarray(self.points), self.normals, self.K_quadratic, self.H_quadratic)
 
     def export_ply_with_curvatures(self, filename='output_with_curvatures.ply'):
         """The ASCII PLY validate_shape writes after the curvature step (utils.py:538-551), same bytes."""
