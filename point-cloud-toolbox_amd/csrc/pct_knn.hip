@@ -272,6 +272,10 @@ int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, in
     a.stamp_sweep = clock->word(PCT_ST_GRID_END);
     a.stamp_exact = clock->word(fast ? PCT_ST_FAST_END : PCT_ST_GRID_END);
     a.stamp_exact_also = fast ? nullptr : clock->word(PCT_ST_FAST_END);
+    // k_knn_pair / k_knn_duo leave their lists in the rows they could not prove, and the exact sweep starts from them
+    // (PCT_REDO_SEED=0, read per call: neither; an A/B aid)
+    const char* seed_env = pct_getenv("PCT_REDO_SEED");
+    a.redo_seed = plan.lean() && !plan.tree && phase == 0 && !(seed_env && seed_env[0] == '0' && seed_env[1] == 0);
     PCT_TRY(launch_sweep(ctx, plan, a, redo, redo_count));
     PCT_HIP(ctx, clock->boundary(PCT_ST_FAST_END, ctx->stream));      // end of the dominant kernel
     // exact pass: the flagged queries (device-side count, fixed grid) or, for testing, every query

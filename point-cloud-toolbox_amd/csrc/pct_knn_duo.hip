@@ -71,9 +71,16 @@ __global__ __launch_bounds__(64, ((TREE ? PCT_TREE_CAP2 : PCT_DUO_CAP) <= 768 ? 
     int my_pre, m;
     run_prefix<NRUNS>(run_len, lane, my_pre, m);
     pct_stamp(a.stamp);            // (behind the prologue's loads; block 0 takes neither return above on a uniform list: pct_stamp.h)
+    unsigned long long redo_mask = 0ull;
     if (item_overflows<TREE, NRUNS>(m, CAP, run_len, lane)) {
-        hand_item_to_redo(a.redo, a.redo_count, a.counters, a.stats, row0, nq, lane, true);
-        return;
+        if (TREE || !a.seed) {
+            hand_item_to_redo(a.redo, a.redo_count, a.counters, a.stats, row0, nq, lane, true, a.nbr_pos, a.pitch);
+            return;
+        }
+        // the item runs on the first CAP flat slots of its stencil and all its queries go to the redo list (k_knn_pair)
+        redo_mask = nq >= 64 ? ~0ull : (1ull << nq) - 1ull;
+        if (a.stats && lane == 0) atomicAdd(&a.counters->lds_overflows, 1ull);
+        m = CAP;
     }
     unsigned slotx[CAP / 64];
     {
@@ -81,7 +88,7 @@ __global__ __launch_bounds__(64, ((TREE ? PCT_TREE_CAP2 : PCT_DUO_CAP) <= 768 ? 
         static_assert(sizeof(L.pend) >= CAP / 8, "the run-start bit string lives in the survivor list");
         if (lane < CAP / 32) bits[lane] = 0u;
         wave_lds_sync();
-        const bool nonempty = lane < NRUNS && run_len > 0;
+        const bool nonempty = lane < NRUNS && run_len > 0 && my_pre < CAP;      // (a truncated item: the runs that begin inside)
         const unsigned long long ne = __builtin_amdgcn_ballot_w64(nonempty);
         if (nonempty) {
             atomicOr(&bits[my_pre >> 5], 1u << (my_pre & 31));
@@ -132,7 +139,6 @@ __global__ __launch_bounds__(64, ((TREE ? PCT_TREE_CAP2 : PCT_DUO_CAP) <= 768 ? 
     const float eps2a = EPS ? keys.eps2a : INFINITY;
     const double eps1 = EPS ? keys.eps1 : 0.0;
     float t_prev_f = 0.f;
-    unsigned long long redo_mask = 0ull;
 
     char* const pos_item = (char*)(a.nbr_pos + (int64_t)row0 * a.pitch);
     char* const dist_item = DIST ? (char*)(a.nbr_dist + (int64_t)row0 * a.pitch) : nullptr;
@@ -207,16 +213,23 @@ __global__ __launch_bounds__(64, ((TREE ? PCT_TREE_CAP2 : PCT_DUO_CAP) <= 768 ? 
                     if (__builtin_amdgcn_ballot_w64(!(nt > lo && nt < hi)) != 0ull) break;      // no float left between: a pile of equal distances
                     t = nt;
                 }
-                if (!found || __builtin_amdgcn_ballot_w64(!(T >= 1e-30f)) != 0ull) { redo_mask |= 1ull << qi; continue; }
-                t_prev_f = T;
-                // smallest exact key a candidate cut by the float32 threshold can have (k_knn_pair)
-                double lo2 = (double)T * (1.0 - 0x1p-20);
-                if constexpr (Q64) {
-                    // (sqrt(L) - eq)^2 >= L - 2 eq sqrt(L); an upper bound of the root is enough: float32 root, rounded up
-                    const double root_up = (double)__builtin_sqrtf(T) * (1.0 + 0x1p-21);
-                    lo2 = fmax(lo2 - 2.0 * (double)eq * root_up, 0.0);
+                if (!found || __builtin_amdgcn_ballot_w64(!(T >= 1e-30f)) != 0ull) {
+                    // no threshold: nothing passes, the list is all padding and the row stored below starts with -1 -- the
+                    // mark of a redo row without candidates (Sweep::seed)
+                    redo_mask |= 1ull << qi;
+                    T = 0.f;
+                    cnt = 0;
+                } else {
+                    t_prev_f = T;
+                    // smallest exact key a candidate cut by the float32 threshold can have (k_knn_pair)
+                    double lo2 = (double)T * (1.0 - 0x1p-20);
+                    if constexpr (Q64) {
+                        // (sqrt(L) - eq)^2 >= L - 2 eq sqrt(L); an upper bound of the root is enough: float32 root, rounded up
+                        const double root_up = (double)__builtin_sqrtf(T) * (1.0 + 0x1p-21);
+                        lo2 = fmax(lo2 - 2.0 * (double)eq * root_up, 0.0);
+                    }
+                    bkey = (unsigned)fmin(lo2 * scale, 4294967294.0);
                 }
-                bkey = (unsigned)fmin(lo2 * scale, 4294967294.0);
             }
             // ---- compact the staged slots of the survivors, two batches per block of instructions (k_knn_pair's
             // hand-placed sequence; here both batches append to the same list)
@@ -279,7 +292,9 @@ __global__ __launch_bounds__(64, ((TREE ? PCT_TREE_CAP2 : PCT_DUO_CAP) <= 768 ? 
             const unsigned gk = (unsigned)__builtin_amdgcn_readlane((int)my_gkey, qi);
             const unsigned tk = tau >> SLOT_BITS;
             const unsigned need_k = min(tau == kPadElem ? 0xFFFFFFFFu : tk + 1u, eps_key);
-            if (need_k > min(gk, bkey) || (tau != kPadElem && tk >= key_max - 1u)) { redo_mask |= 1ull << qi; continue; }
+            // (a query whose proof fails stores its row like any other -- ordered or not, these are k real candidates: the
+            // exact sweep starts from the distance of the farthest, Sweep::seed -- and is on the redo list all the same)
+            if (need_k > min(gk, bkey) || (tau != kPadElem && tk >= key_max - 1u)) redo_mask |= 1ull << qi;
             // equal keys among the first k + 2 entries: ordered here by the exact values (order_equal_keys).  Detection:
             // element i ^ element i + 1 below 2^SLOT_BITS <=> same key
             {
@@ -293,7 +308,7 @@ __global__ __launch_bounds__(64, ((TREE ? PCT_TREE_CAP2 : PCT_DUO_CAP) <= 768 ? 
                 const bool same0 = ((e[0] ^ n0) >> SLOT_BITS) == 0u && e[0] != kPadElem && n0 != kPadElem;
                 const bool same1 = ((e[1] ^ n1) >> SLOT_BITS) == 0u && e[1] != kPadElem && n1 != kPadElem && lane < 63;
                 const unsigned long long cm = (__builtin_amdgcn_ballot_w64(same0) & order_lo) | (__builtin_amdgcn_ballot_w64(same1) & order_hi);
-                if (__builtin_expect(cm != 0ull, 0)) {
+                if (__builtin_expect(cm != 0ull && ((redo_mask >> qi) & 1ull) == 0ull, 0)) {
                     const bool done = order_equal_keys<2, SLOT_BITS>(e, a.pts,
                         [&](unsigned at) {
                             const int j = min((int)L.pend[at] & 1023, CAP - 1);
@@ -301,7 +316,7 @@ __global__ __launch_bounds__(64, ((TREE ? PCT_TREE_CAP2 : PCT_DUO_CAP) <= 768 ? 
                             return (dx * dx + dy * dy) + dz * dz;
                         },
                         [&](unsigned at) { return L.pay_p[at]; });
-                    if (!done) { redo_mask |= 1ull << qi; continue; }
+                    if (!done) redo_mask |= 1ull << qi;
                 }
             }
             // ---- store: the lane that holds list entry i looks up position (and distance) of survivor e & 127 --------

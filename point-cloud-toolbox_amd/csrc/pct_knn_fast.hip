@@ -172,7 +172,7 @@ __global__ __launch_bounds__(64 * kFastWaves<R>, (TREE ? (R == 1 ? (PCT_TREE_CAP
             if (lane < nq) a.redo_m[row0 + lane] = ((hopeless ? 1 : 2) << 29) | min(m, (1 << 29) - 1);
             return;
         }
-        hand_item_to_redo(redo, redo_count, a.counters, a.stats, row0, nq, lane, !hopeless);
+        hand_item_to_redo(redo, redo_count, a.counters, a.stats, row0, nq, lane, !hopeless, a.nbr_pos, a.pitch);
         return;
     }
 

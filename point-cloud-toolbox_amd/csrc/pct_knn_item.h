@@ -29,6 +29,7 @@ struct PairArgs {
                               // the items one XCD's L2 serves at a time are neighbours in cell order (they share most of their stencils)
     int k, pitch;
     int stats;
+    int seed;                 // KnnArgs::redo_seed: an item whose stencil overflows the staging area runs on its first CAP slots
     unsigned magic_x, magic_xy;      // cell -> (cx, cy, cz) by multiplication: q = (x * magic) >> shift, exact for x < 2^30
     int shift_x, shift_xy;
     double eps2;
@@ -48,6 +49,7 @@ PairArgs make_pair_args(const pct_ctx* ctx, const KnnArgs& a, bool tree, int* re
     pa.redo = redo; pa.redo_count = redo_count; pa.counters = a.counters;
     pa.n_items = (int)ctx->n_items; pa.items_q = ctx->items_q;
     pa.k = a.k; pa.pitch = a.pitch; pa.stats = a.stats; pa.eps2 = a.eps2; pa.g = a.g;
+    pa.seed = a.redo_seed;
     pa.stamp = a.stamp_sweep;
     pa.items_per_xcd = pct_getenv("PCT_NO_XCD_MAP") ? 0 : (int)((ctx->n_items + 7) / 8);
     if (tree) {
@@ -190,12 +192,18 @@ __device__ __forceinline__ bool item_overflows(const int m, const int cap, const
 
 // The exact sweep takes the whole item: its rows are appended to the redo list with ONE counter increment (an increment
 // per query serialises at the memory side).  overflow: the item counts as a staging overflow in the statistics.
+// No query of the item has run: every row gets -1 in its first column, so that whoever reads a redo row for the list the
+// fast sweep left there (k_knn_exact, Sweep::seed) never takes what an earlier call wrote for one.
 __device__ __forceinline__ void hand_item_to_redo(int* __restrict__ redo, int* __restrict__ redo_count, pct_sweep_words* counters,
-                                                  const int stats, const int row0, const int nq, const int lane, const bool overflow) {
+                                                  const int stats, const int row0, const int nq, const int lane, const bool overflow,
+                                                  int* __restrict__ nbr_pos, const int pitch) {
     int base = 0;
     if (lane == 0) base = atomicAdd(redo_count, nq);
     base = __builtin_amdgcn_readfirstlane(base);
-    if (lane < nq) redo[base + lane] = row0 + lane;
+    if (lane < nq) {
+        redo[base + lane] = row0 + lane;
+        nbr_pos[(int64_t)(row0 + lane) * pitch] = -1;
+    }
     if (stats && lane == 0) {
         if (overflow) atomicAdd(&counters->lds_overflows, 1ull);
         atomicAdd(&counters->redone_queries, (unsigned long long)nq);

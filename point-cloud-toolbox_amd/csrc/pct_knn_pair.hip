@@ -96,9 +96,18 @@ __global__ __launch_bounds__(64 * kPairWaves, (TREE ? 4 : Q64 ? 5 : 6)) void k_k
     int my_pre, m;
     run_prefix<NRUNS>(run_len, lane, my_pre, m);
     pct_stamp(a.stamp);            // (behind the prologue's loads; block 0 takes neither return above on a uniform list: pct_stamp.h)
+    unsigned long long redo_mask = 0ull;                  // queries of this item the exact sweep has to take
     if (item_overflows<TREE, NRUNS>(m, CAP, run_len, lane)) {
-        hand_item_to_redo(a.redo, a.redo_count, a.counters, a.stats, row0, nq, lane, true);
-        return;
+        if (TREE || !a.seed) {
+            hand_item_to_redo(a.redo, a.redo_count, a.counters, a.stats, row0, nq, lane, true, a.nbr_pos, a.pitch);
+            return;
+        }
+        // The item runs on the first CAP flat slots of its stencil: every list it stores is k real candidates, which is
+        // all the exact sweep asks of a redo row (Sweep::seed) -- the proofs below assume the whole stencil, so every
+        // query of the item is on the redo list from here on, whatever they say.
+        redo_mask = nq >= 64 ? ~0ull : (1ull << nq) - 1ull;
+        if (a.stats && lane == 0) atomicAdd(&a.counters->lds_overflows, 1ull);
+        m = CAP;
     }
 
     // ---- copy the runs as one flat range (see k_knn_fast): run starts as a bit string in the list area; the run index
@@ -109,7 +118,7 @@ __global__ __launch_bounds__(64 * kPairWaves, (TREE ? 4 : Q64 ? 5 : 6)) void k_k
         unsigned* bits = L.pend;
         if (lane < CAP / 32) bits[lane] = 0u;
         wave_lds_sync();
-        const bool nonempty = lane < NRUNS && run_len > 0;
+        const bool nonempty = lane < NRUNS && run_len > 0 && my_pre < CAP;      // (a truncated item: the runs that begin inside)
         const unsigned long long ne = __builtin_amdgcn_ballot_w64(nonempty);
         if (nonempty) {
             atomicOr(&bits[my_pre >> 5], 1u << (my_pre & 31));
@@ -160,7 +169,6 @@ __global__ __launch_bounds__(64 * kPairWaves, (TREE ? 4 : Q64 ? 5 : 6)) void k_k
     const float eps2a = EPS ? keys.eps2a : INFINITY;
     const double eps1 = EPS ? keys.eps1 : 0.0;
     float t_prev_f = 0.f;                                 // threshold of the previous query of this item (0 = none yet)
-    unsigned long long redo_mask = 0ull;                  // queries of this item the exact sweep has to take
 
     // table rows of this item: one 64-bit base per item, 32-bit offsets per query and lane (list entry i -> column i - 1)
     char* const pos_item = (char*)(a.nbr_pos + (int64_t)row0 * a.pitch);
@@ -299,9 +307,10 @@ __global__ __launch_bounds__(64 * kPairWaves, (TREE ? 4 : Q64 ? 5 : 6)) void k_k
                 ok_b = live_b && (fm & 2u) != 0u && (!need_b || T_b >= 1e-30f);
                 if (need_a && ok_a) { t_prev_f = T_a; bkey_a = (unsigned)__builtin_amdgcn_readlane((int)v_bkey, 0); }
                 if (need_b && ok_b) { t_prev_f = T_b; bkey_b = (unsigned)__builtin_amdgcn_readlane((int)v_bkey, 1); }
-                if (!ok_a) { redo_mask |= 1ull << qi; T_a = 0.f; cnt_a = 0; }        // nothing passes, nothing is stored
+                // no threshold: nothing passes, the list is all padding and the row stored below starts with -1 -- the mark
+                // of a redo row without candidates (Sweep::seed)
+                if (!ok_a) { redo_mask |= 1ull << qi; T_a = 0.f; cnt_a = 0; }
                 if (!ok_b) { if (live_b) redo_mask |= 1ull << qj; T_b = 0.f; cnt_b = 0; }
-                if (!ok_a && !ok_b) continue;
             }
             if (!live_b) { T_b = 0.f; cnt_b = 0; }
             // ---- compact the slots of the survivors of both queries.  Per batch and query: one compare (the pass mask
@@ -431,7 +440,9 @@ __global__ __launch_bounds__(64 * kPairWaves, (TREE ? 4 : Q64 ? 5 : 6)) void k_k
                     }
                 }
             }
-            // ---- store: the lane that holds list entry i fetches position (and distance) of survivor e & 63 ----------
+            // ---- store: the lane that holds list entry i fetches position (and distance) of survivor e & 63.  A query whose
+            // proof failed stores its row like any other (ordered or not, these are k real candidates: the exact sweep
+            // starts from the distance of the farthest, Sweep::seed) and is on the redo list all the same.
             {
                 const unsigned off_a = lane_off + (unsigned)qi * pitch4, off_b = lane_off + (unsigned)qj * pitch4;
                 const bool real_a = e_a != kPadElem, real_b = e_b != kPadElem;
@@ -445,14 +456,14 @@ __global__ __launch_bounds__(64 * kPairWaves, (TREE ? 4 : Q64 ? 5 : 6)) void k_k
 #ifdef PCT_ABL_NO_STORE
                 if (pos_a == 0x7fffffff && pos_b == 0x7ffffff1)
 #endif
-                if (ok_a && col_lane) {
+                if (col_lane) {
                     *(int*)(pos_item + off_a) = real_a ? pos_a : -1;
                     if constexpr (DIST) *(float*)(dist_item + off_a) = real_a ? dist_a : INFINITY;
                 }
 #ifdef PCT_ABL_NO_STORE
                 if (pos_a == 0x7fffffff && pos_b == 0x7ffffff1)
 #endif
-                if (ok_b && col_lane) {
+                if (live_b && col_lane) {
                     *(int*)(pos_item + off_b) = real_b ? pos_b : -1;
                     if constexpr (DIST) *(float*)(dist_item + off_b) = real_b ? dist_b : INFINITY;
                 }

@@ -47,6 +47,10 @@ struct KnnArgs {
     unsigned long long* stamp_sweep;
     unsigned long long* stamp_exact;
     unsigned long long* stamp_exact_also;
+    // the launch in front was k_knn_pair or k_knn_duo on the uniform cell list: every row of the redo list holds the k
+    // candidates that launch found for it, or -1 in its first column (k_knn_exact reads its starting bound from them).
+    // Never set for exact_only, level passes or the hierarchical list.
+    int redo_seed;
 };
 
 // rows of 128 .. PCT_K_MAX neighbours (pct_knn_wide.hip): list registers R = 4 | 8
@@ -217,8 +221,61 @@ struct Sweep {
 #pragma unroll
         for (int r = 1; r < R; ++r)
             if (slot == r) { d = best.d[r]; p = best.p[r]; }
-        tau_d = __shfl(d, src);
-        tau_p = __shfl(p, src);
+        d = __shfl(d, src);
+        p = __shfl(p, src);
+        // fewer than k+1 real entries so far: the bound stays what it was (+inf, or the seed) -- it never rises
+        if (p != INT_MAX) { tau_d = d; tau_p = p; }
+    }
+
+    // fp64 ((dx^2 + dy^2) + dz^2), no FMA: SciPy's value
+    __device__ __forceinline__ double dist2(const float4 c) const {
+        const double dx = (double)c.x - qx, dy = (double)c.y - qy, dz = (double)c.z - qz;
+        return (dx * dx + dy * dy) + dz * dz;
+    }
+
+    // Start from a bound somebody else found (after reset()).  The row's k columns are read as k claimed positions and
+    // nothing else is believed of them: if they are k distinct positions inside the cloud, none of them the query's own
+    // record `self`, then these and `self` are k+1 distinct points, and the largest of their exact squared distances
+    // B is an upper bound of the (k+1)-th smallest.  The running bound becomes (B, INT_MAX): a candidate at exactly
+    // B passes (consider), whatever its index.  Returns B, or +inf when the row gives no bound (a marker, padding,
+    // anything out of range or repeated): the sweep then starts as it always did.
+    __device__ __forceinline__ double seed(const int* __restrict__ cols, const int self, const int n) {
+        const int lane = lane_id();
+        int p[R];
+        bool bad = false;
+        double B = dist2(pts[self]);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int col = lane + 64 * r;
+            p[r] = col < k ? cols[col] : -1;
+            if (col < k) {
+                const bool in = (unsigned)p[r] < (unsigned)n && p[r] != self;
+                bad = bad || !in;
+                const double d2 = dist2(pts[in ? p[r] : self]);
+                bad = bad || !(d2 < INFINITY);
+                B = fmax(B, d2);
+            }
+        }
+        if (__ballot(bad) != 0ull) return INFINITY;
+        // distinct: column i differs from every later column
+        for (int i = 0; i + 1 < k; ++i) {
+            int v = p[0];
+#pragma unroll
+            for (int r = 1; r < R; ++r)
+                if ((i >> 6) == r) v = p[r];
+            v = __builtin_amdgcn_readlane(v, i & 63);      // (i is wave-uniform: no LDS round trip per column)
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int col = lane + 64 * r;
+                bad = bad || (col > i && col < k && p[r] == v);
+            }
+        }
+        if (__ballot(bad) != 0ull) return INFINITY;
+        for (int o = 32; o > 0; o >>= 1) B = fmax(B, __shfl_xor(B, o));
+        if (!(B < INFINITY)) return INFINITY;
+        tau_d = B;
+        tau_p = INT_MAX;
+        return B;
     }
 
     // take up to 64*R pending survivors into the running list
@@ -255,8 +312,7 @@ struct Sweep {
 
     // one candidate per lane; survivors are compacted into the pending buffer
     __device__ __forceinline__ void consider(float4 c, int pos, bool valid) {
-        const double dx = (double)c.x - qx, dy = (double)c.y - qy, dz = (double)c.z - qz;
-        const double d2 = (dx * dx + dy * dy) + dz * dz;
+        const double d2 = dist2(c);
         // Every lane takes part (wave ballot inside) -- but a lane without a candidate must not take part in the
         // tie-break: its registers hold the coordinates of an EARLIER batch (or zeros), whose d2 can equal the running
         // (k+1)-th distance exactly (that earlier candidate may BE the (k+1)-th), and the tie-break reads the public
@@ -264,7 +320,9 @@ struct Sweep {
         // below ~380 points that is beyond the head-room of the allocation: the GPU memory fault that aborted a test
         // run once in a while for two rounds.  The padding position never enters a tie-break.
         const bool closer = key_less(d2, valid ? pos : INT_MAX, tau_d, tau_p, pts);
-        const bool pass = valid && d2 < eps2 && closer;
+        // a finite bound without a position is a seed (seed()): k+1 points lie within it, not necessarily below it
+        const bool at_seed = tau_p == INT_MAX && d2 == tau_d && d2 < INFINITY;
+        const bool pass = valid && d2 < eps2 && (closer || at_seed);
         const unsigned long long m = __ballot(pass);
         if (pass) {
             const int slot = npend + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
@@ -464,8 +522,11 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_knn_exact(KnnArgs a, co
         const double gx = (sw.qx - g.ox) * g.inv_cell - cx;
         const double gy = (sw.qy - g.oy) * g.inv_cell - cy;
         const double gz = (sw.qz - g.oz) * g.inv_cell - cz;
+        // the fast sweep in front left what it found in the row: the bound starts there, not at +inf, the first flush
+        // takes about k+1 survivors instead of the cube's population, and the cube loses the cells beyond the bound
+        const double seed_d2 = a.redo_seed && list ? sw.seed(a.nbr_pos + (int64_t)row * a.pitch, q, (int)a.n) : (double)INFINITY;
         ShellIter it;
-        it.start(g, cy, cz, -1, 1);
+        it.start(g, cy, cz, -1, 1, seed_d2, gx, gy, gz);
         // candidate loads run one step ahead of their use (a shell is many short runs, each a dependent load)
         int nbase = 0, nlim = 0;
         bool have_next = it.next(g, cs, cx, cy, cz, nbase, nlim);
