@@ -381,6 +381,51 @@ int pct_get_point_frames(pct_ctx* ctx, int64_t begin, int64_t end, double* norma
  * milliseconds of its kernel (hipEvent). */
 int pct_point_frame_stats(pct_ctx* ctx, int64_t out[4], double* ms);
 
+/* Consistent normal orientation.  The fit picks a side per row (pct:286-297), and one viewpoint orients only what is seen
+ * from it; pct_orient_frames turns the resident frames of a whole-cloud handle so that neighbouring rows agree, by a
+ * level-synchronous flood over the resident neighbour table (the role of Open3D's
+ * orient_normals_consistent_tangent_plane in the reference's pipeline, utils:80).  Every choice is a keyed 64-bit maximum:
+ * the result is a pure function of the normals as they stand before the call and of the table, whatever order either is
+ * stored in.  tests/orient_exact.py states it again in NumPy.
+ *   valid     a row whose normal holds no NaN.  Invalid rows are never labelled, never parents, and keep every output;
+ *   entries   of row i: its table entries before its eps count that are records of the cloud.  The graph is undirected:
+ *             i ~ j when j is an entry of row i or i one of row j;
+ *   claim     a labelled row p on an unlabelled valid row c: dot = (n_p0 n_c0 + n_p1 n_c1) + n_p2 n_c2 in float64, nothing
+ *             fused; key = (uint64(bits of (float)|dot|) << 32) | (0xFFFFFFFF - public index of p).  The largest key wins
+ *             (the best aligned parent, the lowest index among equals); c takes toggle[c] = toggle[p] XOR (dot < 0),
+ *             parent p, level[p] + 1 and p's component;
+ *   flood     until no unlabelled valid row is left or max_components components exist:
+ *               seed   the unlabelled valid row of lowest public index: toggle 0, level 0, parent -1, the next component
+ *                      id (ids count up from 0);
+ *               push   every row labelled in the previous level claims the unlabelled valid entries of its own row; all
+ *                      claims of a level are in before any is decided; until a level labels nothing;
+ *               pull   once: every unlabelled valid row claims for itself from the entries of its own row that carry this
+ *                      component's id, the entry as parent.  Rows labelled: they are the next frontier, push again; none:
+ *                      the component is complete.  This reaches an outlier that lists the surface while nothing lists it;
+ *   anchor    each component may be turned as a whole.  PCT_ORIENT_SEED: as flooded.  PCT_ORIENT_TOP (Hoppe's rule): the
+ *             component's row of largest z of its float32 record (-0 = +0), lowest public index among equals; its oriented
+ *             normal has n_z < 0: every toggle of the component is inverted.  PCT_ORIENT_VIEW: with the oriented normal,
+ *             s = ((vx - px) n0 + (vy - py) n1) + (vz - pz) n2 (pct_point_frames' expression, p in the cloud's dtype); rows
+ *             with s < 0 face away, rows with s > 0 face the viewpoint; more away than facing: inverted; a tie leaves it;
+ *   apply     every row with toggle 1, exactly as pct_point_frames' flip: n <- -n, (k1, k2) <- (-k2, -k1), (d1, d2) <-
+ *             (d2, d1), flipped ^= 1; H_signed = flipped ? -H : H keeps holding.  Rows beyond max_components stay
+ *             untouched with component -1.
+ * PCT_ERR_INVALID "no point frames" without resident frames; PCT_ERR_INVALID for an owned range or slab handle, an unknown
+ * anchor, or PCT_ORIENT_VIEW without a finite viewpoint.  max_components <= 0: 65536.  A new cloud, owned range, planting,
+ * fit or pct_point_frames call drops the orientation.  pct_get_point_frames serves the turned frames; pct_point_frame_stats
+ * keeps describing the pct_point_frames call.  pct_timings is untouched. */
+#define PCT_ORIENT_SEED 0
+#define PCT_ORIENT_TOP  1
+#define PCT_ORIENT_VIEW 2
+int pct_orient_frames(pct_ctx* ctx, int32_t anchor, const double* viewpoint /* 3 doubles or NULL */, int32_t max_components);
+/* Cloud rows [begin, end): component, parent, level int32 (-1 where unlabelled; a seed's parent is -1), toggled uint8 (the
+ * row was turned by the call, the anchor included); any pointer may be NULL.  PCT_ERR_INVALID without an orientation. */
+int pct_get_orientation(pct_ctx* ctx, int64_t begin, int64_t end, int32_t* component, int32_t* parent, int32_t* level, uint8_t* toggled);
+/* Of the last pct_orient_frames: out = {valid rows, components, rows left unlabelled, toggled rows, push levels that labelled
+ * a row (summed over the components), pull rounds that labelled a row, kernel launches, host waits}; *ms (may be NULL) the
+ * device milliseconds between two events around the call's work. */
+int pct_orient_stats(pct_ctx* ctx, int64_t out[8], double* ms);
+
 /* ---- scan preparation (next row N4) ---------------------------------------- */
 /* Voxel-grid down-sampling of convert_asc_to_ply.py:20-51: voxel = floor(coordinate / voxel_size) evaluated in the
  * coordinates' own dtype as NumPy does (the _f32 form divides by (float)voxel_size in float32), the

@@ -28,6 +28,8 @@ PCT_ERR_LIMIT = 8
 MESH_F32, MESH_F64, MESH_K64_H32, MESH_K32_H64 = 0, 1, 2, 3      # pct_mesh_energies' curvature_is_f64
 
 KNN_AUTO, KNN_BRUTE, KNN_GRID, KNN_GRID_EXACT, KNN_GRID_LEVELS, KNN_TREE = 0, 1, 2, 3, 4, 5
+ORIENT_SEED, ORIENT_TOP, ORIENT_VIEW = 0, 1, 2          # pct_orient_frames' anchors
+ORIENT_ANCHORS = {"seed": ORIENT_SEED, "top": ORIENT_TOP, "view": ORIENT_VIEW}
 QUERY_AUTO, QUERY_SWEEP, QUERY_GRID = 0, 1, 2                    # pct_query_points_algo, pct_query_ball
 BALL_SORTED, BALL_DISTANCES, BALL_COUNT_ONLY = 1, 2, 4           # pct_query_ball's flags
 
@@ -106,6 +108,9 @@ SIGNATURES = {
     "pct_point_frames": (C.c_int, [_p, _f64p]),
     "pct_get_point_frames": (C.c_int, [_p, C.c_int64, C.c_int64, _f64p, _f64p, _f64p, _u8p]),
     "pct_point_frame_stats": (C.c_int, [_p, _i64p, _f64p]),
+    "pct_orient_frames": (C.c_int, [_p, C.c_int32, _f64p, C.c_int32]),
+    "pct_get_orientation": (C.c_int, [_p, C.c_int64, C.c_int64, _i32p, _i32p, _i32p, _u8p]),
+    "pct_orient_stats": (C.c_int, [_p, _i64p, _f64p]),
     "pct_voxel_downsample": (C.c_int, [_p, _f64p, C.c_int64, C.c_double, _i64p, _i64p]),
     "pct_voxel_downsample_f32": (C.c_int, [_p, _f32p, C.c_int64, C.c_double, _i64p, _i64p]),
     "pct_surface_variation": (C.c_int, [_p, C.c_int32, _f32p]),
@@ -614,6 +619,34 @@ class Handle:
         ms = np.zeros(1, np.float64)
         self._check(self._lib.pct_point_frame_stats(self._h, _ptr(out, _i64p), _ptr(ms, _f64p)))
         return {"rows": int(out[0]), "nan": int(out[1]), "flipped": int(out[2]), "umbilic": int(out[3]), "ms": float(ms[0])}
+
+    # -- consistent orientation of those frames: a flood over the resident table --------------------------------------------
+    def orient_frames(self, anchor="top", viewpoint=None, max_components=None):
+        """``pct_orient_frames``: turns the resident frames so that neighbouring rows agree.  ``anchor``: "seed", "top" or
+        "view" (or the ORIENT_* value); "view" needs ``viewpoint``.  The frames stay on the device (``get_point_frames``
+        serves them turned), and so do the component, parent, level and toggle of every row (``get_orientation``)."""
+        a = ORIENT_ANCHORS.get(anchor, anchor)
+        if not isinstance(a, (int, np.integer)):
+            raise ValueError(f"unknown anchor {anchor!r}")
+        v = None if viewpoint is None else np.ascontiguousarray(viewpoint, dtype=np.float64).reshape(3)
+        self._check(self._lib.pct_orient_frames(self._h, int(a), _ptr(v, _f64p), int(max_components or 0)))
+
+    def get_orientation(self, begin, end):
+        """(component, parent, level int32, toggled uint8) of cloud rows [begin, end); -1 where a row was not labelled."""
+        rows = int(end) - int(begin)
+        comp, parent, level = (np.empty(rows, np.int32) for _ in range(3))
+        toggled = np.empty(rows, np.uint8)
+        self._check(self._lib.pct_get_orientation(self._h, int(begin), int(end), _ptr(comp, _i32p), _ptr(parent, _i32p),
+                                                  _ptr(level, _i32p), _ptr(toggled, _u8p)))
+        return comp, parent, level, toggled
+
+    def orient_stats(self):
+        """Of the last ``orient_frames``: {valid, components, unlabelled, toggled, levels, pulls, launches, waits, ms}."""
+        out = np.zeros(8, np.int64)
+        ms = np.zeros(1, np.float64)
+        self._check(self._lib.pct_orient_stats(self._h, _ptr(out, _i64p), _ptr(ms, _f64p)))
+        names = ("valid", "components", "unlabelled", "toggled", "levels", "pulls", "launches", "waits")
+        return {**{k: int(v) for k, v in zip(names, out)}, "ms": float(ms[0])}
 
     def point_energies(self, closed_only=False):
         """``pct_point_energies``: (bending, stretching, area, n_used) over the owned rows -- the closed ones only with

@@ -240,7 +240,7 @@ void pct_destroy(pct_ctx* ctx) {
                       &ctx->tree_codes, &ctx->tree_vals, &ctx->tree_lvl, &ctx->tree_head, &ctx->tree_marks, &ctx->tree_seg, &ctx->tree_runs, &ctx->tree_range, &ctx->tree_bucket, &ctx->tree_tmp,
                       &ctx->pca, &ctx->pca_aux, &ctx->pca_nbr, &ctx->pca_orig,
                       &ctx->bin_rec, &ctx->bin_mat, &ctx->bin_plan, &ctx->bin_base,
-                      &ctx->area, &ctx->area_closed, &ctx->area_nverts, &ctx->area_over, &ctx->frame, &ctx->frame_flip, &ctx->stamp_tickets};
+                      &ctx->area, &ctx->area_closed, &ctx->area_nverts, &ctx->area_over, &ctx->frame, &ctx->frame_flip, &ctx->orient, &ctx->stamp_tickets};
     for (pct_buf* b : all) pct_release(b);
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     for (auto& e : ctx->ev)
@@ -1191,7 +1191,7 @@ int pct_point_frames(pct_ctx* ctx, const double* viewpoint) {
     if (!ctx->fit_valid || !ctx->fit_cloud_aligned || ctx->fit_rows != rows) return pct_fail(ctx, PCT_ERR_INVALID, "no fit results");
     if (viewpoint && !(isfinite(viewpoint[0]) && isfinite(viewpoint[1]) && isfinite(viewpoint[2])))
         return pct_fail(ctx, PCT_ERR_INVALID, "pct_point_frames: the viewpoint is not finite");
-    ctx->frame_valid = false;
+    ctx->frame_valid = ctx->orient_valid = false;
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FRAME_BEGIN], ctx->stream));
     PCT_TRY(pct_launch_point_frames(ctx, viewpoint));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FRAME_END], ctx->stream));
@@ -1244,6 +1244,70 @@ int pct_point_frame_stats(pct_ctx* ctx, int64_t out[4], double* ms) {
     if (!ctx || !out) return PCT_ERR_INVALID;
     for (int i = 0; i < 4; ++i) out[i] = ctx->frame_valid ? ctx->frame_stats[i] : 0;
     if (ms) *ms = ctx->frame_valid ? ctx->frame_ms : 0.0;
+    return PCT_OK;
+}
+
+// ---- consistent orientation of the resident frames (pct_orient.hip) ------------------------------------------------------
+// the orientation belongs to the frames it turned: whatever drops them (a new cloud, owned range, planting or fit) drops it
+static bool orientation_resident(const pct_ctx* ctx) { return ctx->orient_valid && frames_resident(ctx); }
+
+int pct_orient_frames(pct_ctx* ctx, int32_t anchor, const double* viewpoint, int32_t max_components) {
+    PCT_TRY(begin_call(ctx));
+    PCT_TRY(refuse_in_slab_mode(ctx, "pct_orient_frames"));
+    ctx->orient_valid = false;
+    if (!frames_resident(ctx) || !ctx->knn_valid) return pct_fail(ctx, PCT_ERR_INVALID, "no point frames (pct_point_frames)");
+    const int64_t rows = ctx->q_end - ctx->q_begin;
+    if (ctx->q_begin != 0 || ctx->q_end != ctx->n || ctx->culled || ctx->frame_rows != rows)
+        return pct_fail(ctx, PCT_ERR_INVALID, "pct_orient_frames: the handle owns rows [%lld,%lld) of %lld: the flood needs the whole cloud",
+                        (long long)ctx->q_begin, (long long)ctx->q_end, (long long)ctx->n);
+    if (anchor != PCT_ORIENT_SEED && anchor != PCT_ORIENT_TOP && anchor != PCT_ORIENT_VIEW)
+        return pct_fail(ctx, PCT_ERR_INVALID, "pct_orient_frames: unknown anchor %d", anchor);
+    if (anchor == PCT_ORIENT_VIEW && !(viewpoint && isfinite(viewpoint[0]) && isfinite(viewpoint[1]) && isfinite(viewpoint[2])))
+        return pct_fail(ctx, PCT_ERR_INVALID, "pct_orient_frames: PCT_ORIENT_VIEW needs a finite viewpoint");
+    const int max_comp = max_components <= 0 ? 65536 : max_components;
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_ORIENT_BEGIN], ctx->stream));
+    const int status = pct_run_orient(ctx, anchor, anchor == PCT_ORIENT_VIEW ? viewpoint : nullptr, max_comp, ctx->orient_stats);
+    if (status != PCT_OK) {
+        (void)hipStreamSynchronize(ctx->stream);           // (nothing of a failed flood stays in flight)
+        return status;
+    }
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_ORIENT_END], ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const int* w = ctx->pin->orient_words;
+    const int64_t valid = w[OW_VALID], labelled = w[OW_LABELLED];
+    ctx->orient_stats[0] = valid;
+    ctx->orient_stats[1] = w[OW_NCOMP];
+    ctx->orient_stats[2] = valid - labelled;
+    ctx->orient_stats[3] = w[OW_TOGGLED];
+    ctx->orient_stats[4] = w[OW_LEVELS];
+    ctx->orient_stats[5] = w[OW_PULLS];
+    ctx->orient_ms = ev_ms(ctx, PCT_EV_ORIENT_BEGIN, PCT_EV_ORIENT_END);
+    ctx->orient_rows = rows;
+    ctx->orient_valid = true;
+    return PCT_OK;
+}
+
+int pct_get_orientation(pct_ctx* ctx, int64_t begin, int64_t end, int32_t* component, int32_t* parent, int32_t* level, uint8_t* toggled) {
+    PCT_TRY(begin_call(ctx));
+    PCT_TRY(refuse_in_slab_mode(ctx, "pct_get_orientation"));
+    if (!orientation_resident(ctx)) return pct_fail(ctx, PCT_ERR_INVALID, "no orientation (pct_orient_frames)");
+    if (begin < 0 || end > ctx->orient_rows || begin > end)
+        return pct_fail(ctx, PCT_ERR_INVALID, "rows [%lld,%lld) outside the cloud", (long long)begin, (long long)end);
+    const size_t rows = (size_t)(end - begin);
+    if (rows == 0) return PCT_OK;
+    if (component) PCT_HIP(ctx, hipMemcpyAsync(component, ctx->orient_comp + begin, rows * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (parent) PCT_HIP(ctx, hipMemcpyAsync(parent, ctx->orient_parent + begin, rows * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (level) PCT_HIP(ctx, hipMemcpyAsync(level, ctx->orient_level + begin, rows * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (toggled) PCT_HIP(ctx, hipMemcpyAsync(toggled, ctx->orient_toggle + begin, rows, hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PCT_OK;
+}
+
+int pct_orient_stats(pct_ctx* ctx, int64_t out[8], double* ms) {
+    if (!ctx || !out) return PCT_ERR_INVALID;
+    const bool live = orientation_resident(ctx);
+    for (int i = 0; i < 8; ++i) out[i] = live ? ctx->orient_stats[i] : 0;
+    if (ms) *ms = live ? ctx->orient_ms : 0.0;
     return PCT_OK;
 }
 

@@ -121,6 +121,7 @@ struct pct_pinned {
     // the end stamp before it enqueues the call and reads the block once that word is non-zero (pct_stamp.h)
     alignas(64) pct_stamp_block stamps[2];
     alignas(64) unsigned long long frame_words[8];   // pct_point_frames (pct_frame.hip): NaN rows, flipped rows, umbilic rows
+    alignas(64) int orient_words[16];                // pct_orient_frames (pct_orient.hip): its control words, OrientWord
 };
 static_assert(sizeof(pct_pinned) <= 4096, "pct_create allocates 4096 bytes");
 
@@ -132,8 +133,15 @@ enum pct_event {                           // ctx->ev
     PCT_EV_SCAN_TOTALS,                    // the cell list's scan totals are in pinned memory (pct_build_grid)
     PCT_EV_AREA_BEGIN, PCT_EV_AREA_END,    // pct_point_areas
     PCT_EV_FRAME_BEGIN, PCT_EV_FRAME_END,  // pct_point_frames
+    PCT_EV_ORIENT_BEGIN, PCT_EV_ORIENT_END,// pct_orient_frames
     PCT_EV_COUNT
 };
+
+enum OrientWord {                          // int words of pct_orient.hip's control block, mirrored to pct_pinned::orient_words
+    OW_CNT_A = 0, OW_CNT_B, OW_UCNT0, OW_UCNT1, OW_UPAR, OW_SEED_BEST, OW_NCOMP, OW_RUNNING, OW_FINISHED, OW_LEVELS,
+    OW_PULLS, OW_LABELLED, OW_VALID, OW_TOGGLED, OW_PUSH_DONE, OW_COUNT
+};
+static_assert(OW_COUNT <= 16, "pct_pinned::orient_words");
 
 struct pct_comm;            // RCCL communicator + exchange stream (pct_comm.hip); null on a single-GPU handle
 
@@ -335,6 +343,18 @@ struct pct_ctx {
     int64_t frame_rows = 0;
     int64_t frame_stats[4] = {0, 0, 0, 0};  // rows, NaN rows, flipped rows, umbilic rows
     double frame_ms = 0;                    // device milliseconds of its kernel
+
+    // consistent orientation of those frames (pct_orient.hip): one allocation, carved up per call; the four results in
+    // public order, int32 / uint8 (owned), live while orient_valid and the frames they turned are resident
+    pct_buf orient;
+    const int* orient_comp = nullptr;
+    const int* orient_parent = nullptr;
+    const int* orient_level = nullptr;
+    const unsigned char* orient_toggle = nullptr;
+    bool orient_valid = false;
+    int64_t orient_rows = 0;
+    int64_t orient_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // valid rows, components, unlabelled, toggled, levels, pull rounds, launches, waits
+    double orient_ms = 0;
 };
 
 int pct_fail(pct_ctx* ctx, int code, const char* fmt, ...);
@@ -512,6 +532,10 @@ int pct_launch_point_energies(pct_ctx* ctx, bool closed_only, double* d_partial,
 int pct_launch_point_frames(pct_ctx* ctx, const double* viewpoint);
 int pct_launch_gather_frames(pct_ctx* ctx, int64_t first, int64_t rows, double* d_normal, double* d_k12, double* d_dirs,
                              unsigned char* d_flipped);
+// pct_orient.hip: the flood over the resident table, the anchor and the apply pass on the resident frames of a whole-cloud
+// handle; the control words are on their way to ctx->pin->orient_words on return (complete after the stream's next wait),
+// stats8[6] and [7] (kernel launches, host waits) are filled here
+int pct_run_orient(pct_ctx* ctx, int anchor, const double* viewpoint, int max_comp, int64_t stats8[8]);
 int pct_voxel_downsample_device(pct_ctx* ctx, const void* d_xyz, bool f64, int64_t n, double voxel, int64_t* d_out, int64_t* count);
 int pct_launch_surface_variation(pct_ctx* ctx, float* d_out);
 // PCA principal curvatures (pct_pca.hip).  The sweep fetches up to PCT_PCA_EXTRA candidates beyond k per point, re-ranked

@@ -491,6 +491,32 @@ class PointCloud:
         self.H_signed_quadratic = H_signed
         return normal, k1, k2, dirs
 
+    def orient_normals_consistently(self, anchor="top", viewpoint=None, max_components=None):
+        """Turns the normals of the fitted patches so that neighbouring points agree (``pct_orient_frames``,
+        include/pct_hip.h): a flood over the planted neighbour table -- the step the reference's pipeline takes from Open3D
+        (``orient_normals_consistent_tangent_plane``, utils:80) and its README promises as "consistency in curvature
+        signs".  ``anchor`` decides the side of each connected component as a whole: "top" (the highest point's normal
+        points up: outward on a closed surface), "view" (to the side of ``viewpoint``) or "seed" (as flooded).  Computes the
+        frames first (``compute_surface_frames``) where none are cached.  Refreshes ``normals``, ``k1_quadratic``,
+        ``k2_quadratic``, ``principal_directions_quadratic``, ``normals_flipped`` and ``H_signed_quadratic`` from the
+        device, sets ``normal_components`` (int32, -1: not reached) and ``last_orientation_stats``, and returns the
+        normals.  ``compute_surface_frames`` with the same arguments, ``compute_normals`` and the PLY export serve the
+        oriented values until the next planting or fit."""
+        if self._frame_key is None or self._frame_key[:2] != (self._plant_token, self._fit_serial) or \
+                not self._frames_on_device(self._frame_key) or self._frame_cache is None:
+            self.compute_surface_frames()
+        h = self._planted_table()
+        h.orient_frames(anchor, viewpoint, max_components)
+        self.last_orientation_stats = h.orient_stats()
+        normal, k12, dirs, flipped = h.get_point_frames(0, self._n_dev)
+        H = h.get_fit(0, self._n_dev, coefs=False, K=False, H2=False)[2]
+        self._frame_cache = (normal, np.ascontiguousarray(k12[:, 0]), np.ascontiguousarray(k12[:, 1]), dirs,
+                             flipped.astype(bool), np.where(flipped.astype(bool), -H, H).astype(np.float32))
+        self.normal_components = h.get_orientation(0, self._n_dev)[0]
+        self.normals, self.k1_quadratic, self.k2_quadratic, self.principal_directions_quadratic, self.normals_flipped, \
+            self.H_signed_quadratic = self._frame_cache
+        return self.normals
+
     def compute_normals(self):
         """pct:691-697 -- there through PyVista and a Delaunay mesh; here the normals of the fitted patches
         (``compute_surface_frames`` without a viewpoint).  Sets ``self.normals``."""
