@@ -628,6 +628,12 @@ __device__ __forceinline__ int4 cell_counts(const int* __restrict__ own, const i
     return make_int4(t, (o + items_q - 1) / items_q, o, t > 0 ? 1 : 0);
 }
 
+// ... of a cell with o owned and x other points (the counting sort holds the counters in LDS)
+__device__ __forceinline__ int4 count_record(int o, int x, int items_q) {
+    const int t = o + x;
+    return make_int4(t, (o + items_q - 1) / items_q, o, t > 0 ? 1 : 0);
+}
+
 // first pass: per-tile sums; also accumulates sum_c owned_c * count_c (= sum over the owned points of the
 // population of their own cell), the statistic the cell-size loop steers on
 __global__ __launch_bounds__(kBlock) void k_scan_sums(const int* __restrict__ own, const int* __restrict__ oth, int64_t ncell, int items_q,
@@ -804,11 +810,16 @@ __global__ __launch_bounds__(kBlock) void k_scatter_raw(const float* __restrict_
 //                  bucket's range of bin_rec (runs of one tile and bucket are adjacent: the L2 combines the stores)
 //   k_bin_cells    per item: per-cell, per-class counts in LDS -> cell_own / cell_oth.  The only item of a bucket stores
 //                  all its cells (zeros too: no clearing fill); the items of a shared bucket add their non-zero counts
-//                  (one atomic per non-empty (item, cell, class)) and keep the value returned, their run's offset
-//   (k_scan_sums, k_scan_tiles, event, k_scan_apply as for every build)
-//   k_bin_place    per item: LDS cursors from cell_start (+ cell_own for the other class, + the run offset), every
-//                  record to its place in sorted4; owned_pos / sorted4d along; row_of on first need (k_bin_row_of)
-// Kernel boundaries are the only ordering between blocks.
+//                  (one atomic per non-empty (item, cell, class)) and keep the value returned, their run's offset.
+//                  Also the bucket's scan record (k_scan_sums' work: a bucket is a scan tile): by the only item from its
+//                  LDS counters, by the item of a shared bucket that takes the bucket's last ticket from the final counts
+//   (k_scan_tiles over the per-bucket records, event: as for every build)
+//   k_bin_place    per item: the triple scan inside its bucket (k_scan_apply's work) from cell_own / cell_oth and the
+//                  bucket's bases -> LDS cursors (+ the run offset in a shared bucket); the first item of a bucket writes
+//                  cell_start / own_start / occ for its cells; every record to its place in sorted4; owned_pos / sorted4d
+//                  along; row_of on first need (k_bin_row_of)
+// Kernel boundaries are the only ordering between blocks, but for one last-block-out ticket per shared bucket in
+// k_bin_cells (nobody waits: the block that finds itself last does the bucket's reduction).
 constexpr int kBinBlock = 256;        // fine level: one block per work item
 constexpr int kBinWide = 1024;        // coarse level: one block per tile, four rows per thread in flight
 // (kBinTileRows, kBinMaxTiles, kBinMaxBuckets, kBinMaxCounters, kBinMinChunk, BinShape and bin_shape: pct_grid_edge.h)
@@ -938,7 +949,8 @@ template <bool RAW>
 __global__ __launch_bounds__(kBinWide) void k_bin_scatter(const float* __restrict__ xyz, const float4* __restrict__ pts4, int64_t n,
                                                            int tile_rows, pct_grid g, int shift, int nb, int chunk,
                                                            const unsigned* __restrict__ mat, const int* __restrict__ plan,
-                                                           float4* __restrict__ rec, int* __restrict__ cell_own, int* __restrict__ cell_oth) {
+                                                           float4* __restrict__ rec, int* __restrict__ cell_own, int* __restrict__ cell_oth,
+                                                           unsigned* __restrict__ tickets) {
     __shared__ unsigned s_cur[kBinMaxBuckets];
     const int* bstart = plan + 16;
     for (int b = threadIdx.x; b < nb; b += kBinWide) s_cur[b] = (unsigned)bstart[b] + mat[(size_t)blockIdx.x * nb + b];
@@ -956,10 +968,12 @@ __global__ __launch_bounds__(kBinWide) void k_bin_scatter(const float* __restric
             if (pos < (unsigned)n) rec[pos] = p[j];   // (guard: the caller's rows must not change between the two passes)
         }
     }
-    // the counters of the shared buckets are added to by k_bin_cells: cleared here, a kernel boundary ahead of it
+    // the counters of the shared buckets are added to by k_bin_cells, and their items take a ticket there: cleared here,
+    // a kernel boundary ahead of it
     if (plan[2] > 0) {
         for (int b = blockIdx.x; b < nb; b += gridDim.x) {
             if (bstart[b + 1] - bstart[b] <= chunk) continue;
+            if (threadIdx.x == 0) tickets[b] = 0u;
             const int64_t c0 = (int64_t)b << shift, c1 = min(g.ncell, c0 + ((int64_t)1 << shift));
             for (int64_t c = c0 + threadIdx.x; c < c1; c += kBinWide) {
                 cell_own[c] = 0;
@@ -969,12 +983,30 @@ __global__ __launch_bounds__(kBinWide) void k_bin_scatter(const float* __restric
     }
 }
 
+// 64 consecutive values, one per lane: inclusive sums.  Six data-parallel-primitive adds (shifts by 1, 2, 4, 8 inside the
+// rows of 16 lanes, then lane 15 of a row to the next row, lane 31 to the upper half): the scan stands on the latency
+// chain of every block of k_bin_place, where six cross-lane LDS permutes per value cost 1 us of the kernel.
+__device__ __forceinline__ int wave_incl_sum(int v) {
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);      // row_shr:1
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);      // row_shr:2
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);      // row_shr:4
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);      // row_shr:8
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);      // row_bcast:15 into rows 1 and 3
+    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);      // row_bcast:31 into rows 2 and 3
+    return v;
+}
+
 __global__ __launch_bounds__(kBinBlock) void k_bin_cells(const float4* __restrict__ rec, const int* __restrict__ plan,
                                                          const int4* __restrict__ items, pct_grid g, int shift, int q_begin, int q_end,
                                                          int* __restrict__ cell_own, int* __restrict__ cell_oth, int* __restrict__ base,
                                                          const PackRed* __restrict__ parts, int n_parts, PackRed* __restrict__ red,
-                                                         PackRed* __restrict__ red_host) {
+                                                         PackRed* __restrict__ red_host, int items_q, int chunk,
+                                                         int4* __restrict__ brec, unsigned long long* __restrict__ bsq,
+                                                         unsigned* __restrict__ tickets) {
     extern __shared__ int s_c[];                    // cells per bucket x classes counters
+    __shared__ int4 s_rec[kBinBlock / 64];
+    __shared__ unsigned long long s_sq[kBinBlock / 64];
+    __shared__ int s_last;
     // the grid's last block is not an item's: it folds the tiles' PackAcc records of a speculative build beside the
     // others (k_pack_final's work, off the chain: a one-block kernel of its own cost 5 us there)
     if (blockIdx.x == gridDim.x - 1) {
@@ -1012,39 +1044,137 @@ __global__ __launch_bounds__(kBinBlock) void k_bin_cells(const float4* __restric
         if (slot < 0) arr[c0 + l] = v;
         else base[(size_t)slot * nc + k] = v ? atomicAdd(&arr[c0 + l], v) : 0;
     }
+    // The bucket's scan record.  A shared bucket's counts are final when all its items have added theirs: every item
+    // takes a ticket of the bucket (cleared by k_bin_scatter) and the one that finds itself last reads the counts back.
+    // No release fence in front of the ticket: all an item publishes are the device-scope atomics above, performed at
+    // the memory side like the ticket itself, and each has returned before its wave passes the barrier (its value is the
+    // operand of a store in front of it).  A fence there writes the L2's dirty lines back, in the longest blocks of the
+    // launch (0.6 us of the kernel).  The last item out takes an agent-scope acquire and reads the counts with
+    // agent-scope loads.
+    if (slot >= 0) {
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int* bstart = plan + 16;
+            const int ni = (bstart[it.x + 1] - bstart[it.x] + chunk - 1) / chunk;
+            const bool last = atomicAdd(&tickets[it.x], 1u) == (unsigned)(ni - 1);
+            if (last) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            s_last = last;
+        }
+        __syncthreads();
+        if (!s_last) return;
+    }
+    int4 v = make_int4(0, 0, 0, 0);
+    unsigned long long sq = 0;
+    for (int l = threadIdx.x; l < ncl; l += kBinBlock) {
+        int o, x = 0;
+        if (slot < 0) {
+            o = s_c[l];
+            if (cell_oth) x = s_c[cpb + l];
+        } else {
+            o = __hip_atomic_load(&cell_own[c0 + l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (cell_oth) x = __hip_atomic_load(&cell_oth[c0 + l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        const int4 c = count_record(o, x, items_q);
+        v = add3(v, c);
+        sq += (unsigned long long)c.z * (unsigned)c.x;           // owned points x population of their cell
+    }
+    v = make_int4(wave_incl_sum(v.x), wave_incl_sum(v.y), wave_incl_sum(v.z), wave_incl_sum(v.w));     // (lane 63: the wave's)
+    for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
+    if ((threadIdx.x & 63) == 63) {
+        s_rec[threadIdx.x >> 6] = v;
+        s_sq[threadIdx.x >> 6] = sq;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int4 t = make_int4(0, 0, 0, 0);
+        unsigned long long q = 0;
+        for (int i = 0; i < kBinBlock / 64; ++i) { t = add3(t, s_rec[i]); q += s_sq[i]; }
+        brec[it.x] = t;
+        bsq[it.x] = q;
+    }
 }
 
 __global__ __launch_bounds__(kBinBlock) void k_bin_place(const float4* __restrict__ rec, const int* __restrict__ plan,
                                                          const int4* __restrict__ items, pct_grid g, int shift, int q_begin, int q_end,
-                                                         int64_t n, int64_t n_owned, const int* __restrict__ cell_start,
+                                                         int64_t n, int64_t n_owned, int nb, int items_q, const int4* __restrict__ brec,
                                                          const int* __restrict__ cell_own, const int* __restrict__ cell_oth,
-                                                         const int* __restrict__ own_start, const int* __restrict__ base,
+                                                         const int* __restrict__ base, int* __restrict__ cell_start,
+                                                         int* __restrict__ own_start, int2* __restrict__ occ, int64_t occ_cap,
                                                          float4* __restrict__ sorted4, int* __restrict__ row_of, int* __restrict__ owned_pos,
                                                          const double4* __restrict__ pts4d, double4* __restrict__ sorted4d) {
     extern __shared__ int s_cur[];                  // cells per bucket x classes cursors, then (two classes) cells per bucket words:
-    if ((int)blockIdx.x >= plan[0]) return;         // neighbour-table row minus sorted position of the cell's owned points
+                                                    // neighbour-table row minus sorted position of the cell's owned points
+    __shared__ int4 s_wave[kBinBlock / 64];         // the sums of the four waves' quarters of the bucket
+    if ((int)blockIdx.x >= plan[0]) return;
     const int4 it = items[blockIdx.x];
     const int r0 = it.y, r1 = it.z, slot = it.w;
-    if (r0 >= r1) return;
     const int cpb = 1 << shift, nc = cell_oth ? 2 * cpb : cpb;
     const int64_t c0 = (int64_t)it.x << shift;
     const int ncl = (int)min((int64_t)cpb, g.ncell - c0);
     int* s_row = s_cur + nc;
-    for (int k = threadIdx.x; k < nc; k += kBinBlock) {
-        const int l = k & (cpb - 1);
-        if (l >= ncl) continue;
-        int s = cell_start[c0 + l];
-        if (k >= cpb) s += cell_own[c0 + l];                       // owned points first inside every cell
-        else if (cell_oth) s_row[l] = own_start[c0 + l] - s;
-        if (slot >= 0) s += base[(size_t)slot * nc + k];
-        s_cur[k] = s;
+    // The triple scan inside the bucket (cells, work-item ranks, owned points: k_scan_apply's work), from the bucket's
+    // final counts and its bases in brec.  Every wave takes a quarter of the bucket's cells, 64 consecutive cells a trip,
+    // one per lane: first its sums, then, behind the sums of the waves in front of it, its cells' starts.
+    // (A lane reads back from LDS only what it has stored there itself: no barrier between the two loops.)
+    // The item's first records are on their way meanwhile.
+    float4 p[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (r0 + (int)threadIdx.x + j * kBinBlock < r1) p[j] = rec[r0 + threadIdx.x + j * kBinBlock];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int l_begin = wave * (cpb / (kBinBlock / 64)), l_end = l_begin + cpb / (kBinBlock / 64);     // (cpb >= 256: whole trips)
+    {
+        int4 v = make_int4(0, 0, 0, 0);
+        for (int l = l_begin + lane; l < l_end; l += 64) {
+            const int o = l < ncl ? cell_own[c0 + l] : 0, x = cell_oth && l < ncl ? cell_oth[c0 + l] : 0;
+            s_cur[l] = o;
+            if (cell_oth) s_cur[cpb + l] = x;
+            v = add3(v, count_record(o, x, items_q));
+        }
+        v = make_int4(wave_incl_sum(v.x), wave_incl_sum(v.y), wave_incl_sum(v.z), 0);
+        if (lane == 63) s_wave[wave] = v;
     }
     __syncthreads();
+    int4 run = brec[it.x];
+    for (int w = 0; w < wave; ++w) run = add3(run, s_wave[w]);
+    // the first item of a bucket also writes the lists the sweep and the fit read, for the bucket's cells
+    const bool first = slot < 0 || r0 == plan[16 + it.x];
+    for (int l = l_begin + lane; l < l_end; l += 64) {
+        const int o = s_cur[l], x = cell_oth ? s_cur[cpb + l] : 0;
+        const int4 c = count_record(o, x, items_q);
+        const int4 incl = make_int4(wave_incl_sum(c.x), wave_incl_sum(c.y), wave_incl_sum(c.z), 0);
+        const int s = run.x + incl.x - c.x, r = run.y + incl.y - c.y, w = run.z + incl.z - c.z;
+        run.x += __builtin_amdgcn_readlane(incl.x, 63);
+        run.y += __builtin_amdgcn_readlane(incl.y, 63);
+        run.z += __builtin_amdgcn_readlane(incl.z, 63);
+        if (l >= ncl) continue;
+        const size_t off = slot >= 0 ? (size_t)slot * nc + l : 0;
+        const int run_own = slot >= 0 ? base[off] : 0, run_oth = slot >= 0 && cell_oth ? base[off + cpb] : 0;
+        if (first) {
+            cell_start[c0 + l] = s;
+            own_start[c0 + l] = w;
+            for (int ch = 0; ch < c.y; ++ch)
+                if (r + ch < occ_cap) occ[r + ch] = make_int2((int)(c0 + l), ch);
+        }
+        s_cur[l] = s + run_own;
+        if (cell_oth) {
+            s_cur[cpb + l] = s + o + run_oth;           // owned points first inside every cell
+            s_row[l] = w - s;
+        }
+    }
+    if (first && it.x == nb - 1 && threadIdx.x == 0) {
+        const int4 tot = brec[nb];
+        cell_start[g.ncell] = tot.x;
+        own_start[g.ncell] = tot.z;
+    }
+    if (r0 >= r1) return;               // (an empty bucket's item: the lists above were its work)
+    __syncthreads();
     for (int base = r0 + threadIdx.x; base < r1; base += 4 * kBinBlock) {
-        float4 p[4];
+        if (base != r0 + (int)threadIdx.x) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (base + j * kBinBlock < r1) p[j] = rec[base + j * kBinBlock];
+            for (int j = 0; j < 4; ++j)
+                if (base + j * kBinBlock < r1) p[j] = rec[base + j * kBinBlock];
+        }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (base + j * kBinBlock >= r1) continue;
@@ -1507,11 +1637,16 @@ static GridBuild choose_build(bool bin_allowed, const BinShape& bs, const GridPo
 }
 
 // Scratch of one bin pass (sized by its grid): bucket-partitioned records (bin_rec), [tile][bucket] matrix (bin_mat),
-// plan words + bucket starts + column totals + work list (bin_plan), run offsets of the shared buckets' items (bin_base).
+// plan words + bucket starts + column totals + work list + the buckets' scan records and tickets (bin_plan), run offsets of
+// the shared buckets' items (bin_base).
 struct BinScratch {
     int* plan;
     unsigned* tot;       // column totals, inside bin_plan
     int4* items;         // work list, inside bin_plan
+    int4* brec;          // per bucket: sums of cell_counts() over its cells, then (k_scan_tiles) the sums of the buckets in
+                         // front of it; [nb] the totals.  Inside bin_plan, as are
+    unsigned long long* bsq;     // per bucket: sum of owned x total over its cells
+    unsigned* tickets;   // per shared bucket: items that have added their counts
     size_t lds;          // fine counters of one class
 };
 static int bin_scratch(pct_ctx* ctx, const BinShape& bs, int64_t n, BinScratch* b) {
@@ -1519,11 +1654,17 @@ static int bin_scratch(pct_ctx* ctx, const BinShape& bs, int64_t n, BinScratch* 
     PCT_TRY(pct_reserve(ctx, &ctx->bin_mat, (size_t)bs.ntiles * bs.nb * sizeof(unsigned)));
     const size_t plan_words = 16 + (size_t)(bs.nb + 1) + (size_t)bs.nb;
     const size_t items_at = (plan_words * sizeof(int) + 15) / 16 * 16;
-    PCT_TRY(pct_reserve(ctx, &ctx->bin_plan, items_at + (size_t)bs.max_items * sizeof(int4)));
+    const size_t brec_at = items_at + (size_t)bs.max_items * sizeof(int4);
+    const size_t bsq_at = brec_at + (size_t)(bs.nb + 1) * sizeof(int4);
+    const size_t tickets_at = bsq_at + (size_t)bs.nb * sizeof(unsigned long long);
+    PCT_TRY(pct_reserve(ctx, &ctx->bin_plan, tickets_at + (size_t)bs.nb * sizeof(unsigned)));
     PCT_TRY(pct_reserve(ctx, &ctx->bin_base, (size_t)bs.max_shared * (bs.cls << bs.shift) * sizeof(int)));
     b->plan = (int*)ctx->bin_plan.p;
     b->tot = (unsigned*)(b->plan + 16 + bs.nb + 1);
     b->items = (int4*)((char*)ctx->bin_plan.p + items_at);
+    b->brec = (int4*)((char*)ctx->bin_plan.p + brec_at);
+    b->bsq = (unsigned long long*)((char*)ctx->bin_plan.p + bsq_at);
+    b->tickets = (unsigned*)((char*)ctx->bin_plan.p + tickets_at);
     b->lds = (size_t)(bs.cls << bs.shift) * sizeof(int);
     return PCT_OK;
 }
@@ -1537,6 +1678,8 @@ struct GridPass {
     const float4* src;       // packed records (pts4 or the level base)
     int64_t n_owned;
     bool sharded, sub_box;
+    int items_q;             // queries per work item of the sweep
+    int64_t occ_cap;         // entries of the sweep's work list (occ) that are reserved
 };
 
 // the two passes over the input tiles, from the caller's rows (RAW) or from packed records
@@ -1548,7 +1691,8 @@ static void launch_bin_count(pct_ctx* ctx, int64_t n, const GridPass& p, PackRed
 template <bool RAW>
 static void launch_bin_scatter(pct_ctx* ctx, int64_t n, const GridPass& p, int* cell_oth) {
     PCT_LAUNCH_T(k_bin_scatter<RAW>, dim3(p.bs.ntiles), dim3(kBinWide), 0, ctx->stream, ctx->xyz_view, p.src, n, p.bs.tile_rows, p.g, p.bs.shift,
-                 p.bs.nb, p.bs.chunk, (const unsigned*)ctx->bin_mat.p, (const int*)p.bin.plan, (float4*)ctx->bin_rec.p, (int*)ctx->cell_own.p, cell_oth);
+                 p.bs.nb, p.bs.chunk, (const unsigned*)ctx->bin_mat.p, (const int*)p.bin.plan, (float4*)ctx->bin_rec.p, (int*)ctx->cell_own.p, cell_oth,
+                 p.bin.tickets);
 }
 
 // First half of a pass: per-cell counts of owned / other points in cell_own / cell_oth (and, while the box is deferred,
@@ -1580,7 +1724,8 @@ static int launch_count(pct_ctx* ctx, const GridPoints& s, GridPass& p, pct_call
         s.raw ? launch_bin_scatter<true>(ctx, n, p, cell_oth) : launch_bin_scatter<false>(ctx, n, p, cell_oth);
         PCT_LAUNCH(k_bin_cells, dim3(bs.max_items + 1), dim3(kBinBlock), p.bin.lds, ctx->stream, (const float4*)ctx->bin_rec.p, (const int*)p.bin.plan,
                    (const int4*)p.bin.items, g, bs.shift, (int)ctx->q_begin, (int)ctx->q_end, (int*)ctx->cell_own.p, cell_oth,
-                   (int*)ctx->bin_base.p, (const PackRed*)parts, bs.ntiles, (PackRed*)ctx->red.p, pin_red(ctx));
+                   (int*)ctx->bin_base.p, (const PackRed*)parts, bs.ntiles, (PackRed*)ctx->red.p, pin_red(ctx), p.items_q, bs.chunk,
+                   p.bin.brec, p.bin.bsq, p.bin.tickets);
     } else if (p.build == GridBuild::AtomicRaw) {
         PCT_LAUNCH(k_hist_raw, dim3(nhb), dim3(kBlock), 0, ctx->stream, ctx->xyz_view, n, g, s.g_begin, s.g_end, (int*)ctx->cell_of.p,
                    (int*)ctx->cell_fill.p, (int*)ctx->cell_own.p, cell_oth, parts);
@@ -1597,26 +1742,35 @@ static int launch_count(pct_ctx* ctx, const GridPoints& s, GridPass& p, pct_call
 
 // Between the halves: cell starts, the ordered work list (occ) and -- in pinned memory from PCT_EV_SCAN_TOTALS on -- the
 // totals and the occupancy statistic the pass is judged by.
-static int launch_scan(pct_ctx* ctx, const GridPass& p, int items_q, int nblk) {
+// The counting sort (Bin) has left one scan record per bucket (k_bin_cells) and scans inside the buckets itself
+// (k_bin_place): one launch here, over the buckets' records.  The other builds: k_scan_sums and k_scan_apply over tiles of
+// kScanTile cells.
+static int launch_scan(pct_ctx* ctx, const GridPass& p, int nblk) {
+    const bool bin = p.build == GridBuild::Bin;
+    const int items_q = p.items_q;
     const int* cell_oth = p.sharded ? (const int*)ctx->cell_oth.p : nullptr;
-    PCT_TRY(pct_reserve(ctx, &ctx->scan_tmp, (size_t)(nblk + 1) * sizeof(int4) + (size_t)nblk * sizeof(unsigned long long)));
-    unsigned long long* sq_part = (unsigned long long*)((int4*)ctx->scan_tmp.p + nblk + 1);
+    if (!bin) PCT_TRY(pct_reserve(ctx, &ctx->scan_tmp, (size_t)(nblk + 1) * sizeof(int4) + (size_t)nblk * sizeof(unsigned long long)));
+    int4* tmp = bin ? p.bin.brec : (int4*)ctx->scan_tmp.p;
+    unsigned long long* sq_part = bin ? p.bin.bsq : (unsigned long long*)((int4*)ctx->scan_tmp.p + nblk + 1);
+    if (bin) nblk = p.bs.nb;
     PCT_TRY(pct_reserve(ctx, &ctx->cell_cnt, (size_t)(p.g.ncell + 1) * sizeof(int)));
     PCT_TRY(pct_reserve(ctx, &ctx->own_start, (size_t)(p.g.ncell + 1) * sizeof(int)));
-    PCT_TRY(pct_reserve(ctx, &ctx->occ, ((size_t)(p.n_owned < p.g.ncell ? p.n_owned : p.g.ncell) + (size_t)p.n_owned / items_q + 16) * sizeof(int2)));
-    PCT_LAUNCH(k_scan_sums, dim3(nblk), dim3(kBlock), 0, ctx->stream, (const int*)ctx->cell_own.p, cell_oth, p.g.ncell, items_q,
-               (int4*)ctx->scan_tmp.p, sq_part);
+    PCT_TRY(pct_reserve(ctx, &ctx->occ, (size_t)p.occ_cap * sizeof(int2)));
+    if (!bin)
+        PCT_LAUNCH(k_scan_sums, dim3(nblk), dim3(kBlock), 0, ctx->stream, (const int*)ctx->cell_own.p, cell_oth, p.g.ncell, items_q, tmp, sq_part);
     PCT_TRY(pct_reserve(ctx, &ctx->counters, sizeof(pct_dev_words)));
-    PCT_LAUNCH(k_scan_tiles, dim3(1), dim3(1024), 0, ctx->stream, (int4*)ctx->scan_tmp.p, nblk,
+    PCT_LAUNCH(k_scan_tiles, dim3(1), dim3(1024), 0, ctx->stream, tmp, nblk,
                (const unsigned long long*)sq_part, pin_totals(ctx), (unsigned long long*)&pct_dev(ctx)->sweep);
     ctx->counters_clean = true;
     // the totals this pass is judged by (and, with a deferred pack, the cloud's box) are in pinned memory from here on:
     // the host waits for THIS point, not for the end of the stream -- while it wakes up, decides and enqueues the
-    // sweep, the device applies the scan and scatters the records (50 us at 1 M points; the read-back used to be ~25
-    // us of an idle device).  A pass that is rejected has scattered for nothing, as before.
+    // sweep, the device applies the scan and scatters the records (18 us at 1 M points in the counting sort, which does
+    // both in k_bin_place, and no gap in front of the sweep: profiles/r11_bucket_scan_ab.txt; the read-back used to be
+    // ~25 us of an idle device).  A pass that is rejected has scattered for nothing, as before.
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_SCAN_TOTALS], ctx->stream));
-    PCT_LAUNCH(k_scan_apply, dim3(nblk), dim3(kBlock), 0, ctx->stream, (const int*)ctx->cell_own.p, cell_oth, p.g.ncell, items_q,
-               (const int4*)ctx->scan_tmp.p, (int*)ctx->cell_cnt.p, (int*)ctx->own_start.p, (int2*)ctx->occ.p);
+    if (!bin)
+        PCT_LAUNCH(k_scan_apply, dim3(nblk), dim3(kBlock), 0, ctx->stream, (const int*)ctx->cell_own.p, cell_oth, p.g.ncell, items_q,
+                   (const int4*)tmp, (int*)ctx->cell_cnt.p, (int*)ctx->own_start.p, (int2*)ctx->occ.p);
     return PCT_OK;
 }
 
@@ -1635,8 +1789,9 @@ static int launch_place(pct_ctx* ctx, const GridPoints& s, const GridPass& p) {
     if (p.build == GridBuild::Bin)
         PCT_LAUNCH(k_bin_place, dim3(p.bs.max_items), dim3(kBinBlock), p.bin.lds + (p.sharded ? p.bin.lds / 2 : 0), ctx->stream,
                    (const float4*)ctx->bin_rec.p, (const int*)p.bin.plan, (const int4*)p.bin.items, g, p.bs.shift, (int)ctx->q_begin,
-                   (int)ctx->q_end, n, p.n_owned, (const int*)ctx->cell_cnt.p, (const int*)ctx->cell_own.p, cell_oth,
-                   (const int*)ctx->own_start.p, (const int*)ctx->bin_base.p, (float4*)ctx->sorted4.p,
+                   (int)ctx->q_end, n, p.n_owned, p.bs.nb, p.items_q, (const int4*)p.bin.brec, (const int*)ctx->cell_own.p, cell_oth,
+                   (const int*)ctx->bin_base.p, (int*)ctx->cell_cnt.p, (int*)ctx->own_start.p, (int2*)ctx->occ.p, p.occ_cap,
+                   (float4*)ctx->sorted4.p,
                    lazy_rows ? nullptr : (int*)ctx->row_of.p, (int*)ctx->owned_pos.p, pts4d, sorted4d);
     else if (p.build == GridBuild::AtomicRaw)
         PCT_LAUNCH(k_scatter_raw, dim3(grid_1d(n, kBlock, 0)), dim3(kBlock), 0, ctx->stream, ctx->xyz_view, (const int*)ctx->cell_of.p,
@@ -1762,7 +1917,7 @@ int pct_build_grid(pct_ctx* ctx, int32_t k, double eps, bool may_give_up, GridVe
         double a = es.first();
         GridPass p = {};
         p.src = s.from_base ? (const float4*)ctx->lvl_src.p : (const float4*)ctx->pts4.p;
-        p.n_owned = n_owned; p.sharded = sharded; p.sub_box = sub_box;
+        p.n_owned = n_owned; p.sharded = sharded; p.sub_box = sub_box; p.items_q = items_q;
         int iters = 0;
         int4 tot = make_int4(0, 0, 0, 0);
         double m_last = 0;
@@ -1797,12 +1952,13 @@ int pct_build_grid(pct_ctx* ctx, int32_t k, double eps, bool may_give_up, GridVe
             p.bs = bin_allowed ? bin_shape(n, g.ncell, sharded) : BinShape{};
             p.build = choose_build(bin_allowed, p.bs, s);
             const bool bin = p.build == GridBuild::Bin;
+            p.occ_cap = (n_owned < g.ncell ? n_owned : g.ncell) + n_owned / items_q + 16;
             PCT_TRY(launch_count(ctx, s, p, clock));
             const int nblk = (int)((g.ncell + kScanTile - 1) / kScanTile);
             if (pct_getenv("PCT_GRID_DEBUG"))
                 fprintf(stderr, "[grid] pass %d: n %lld owned %lld edge %g dims %d x %d x %d = %lld cells (%d scan tiles), box [%g %g %g]-[%g %g %g]\n", it,
                         (long long)n, (long long)n_owned, a, g.nx, g.ny, g.nz, (long long)g.ncell, nblk, s.bbox[0], s.bbox[1], s.bbox[2], s.bbox[3], s.bbox[4], s.bbox[5]);
-            PCT_TRY(launch_scan(ctx, p, items_q, nblk));
+            PCT_TRY(launch_scan(ctx, p, nblk));
             PCT_TRY(launch_place(ctx, s, p));
             PCT_HIP(ctx, hipEventSynchronize(ctx->ev[PCT_EV_SCAN_TOTALS]));
             if (s.deferred_box) {
