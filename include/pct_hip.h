@@ -84,6 +84,68 @@ typedef struct pct_timings {
                                  (k_knn_pair and k_knn_duo report PRE = PAIR = 1).  Every variant returns the same rows */
 } pct_timings;
 
+/* ---- state rules: what a call needs, what it leaves, what it drops --------------------------------------------------------
+ * One handle holds at most one of each: a cloud, an owned range or slab, a neighbour table, fit results, point areas, point
+ * frames with their orientation, PCA results, ball rows.  The entry points below say what they compute; these rules say how
+ * they meet on one handle.  tests/call_model.py states them again as a table and quotes every sentence it relies on;
+ * tests/call_driver.py runs random call sequences against them.
+ *
+ * Refusals.  A refused call changes nothing: after a call that returns an error status for its arguments or for the state
+ * of the handle, whatever was resident before it is resident still, with the same contents.  The one exception is
+ * pct_query_ball: once its arguments are accepted it drops the rows of the previous query, so a query that then ends in
+ * PCT_ERR_LIMIT, PCT_ERR_OOM or PCT_ERR_HIP leaves none; a query refused for its arguments or for the state of the handle
+ * leaves them (every PCT_ERR_INVALID and PCT_ERR_NONFINITE of it, a refusal of the cell-list build included, comes first).
+ * A state refusal is decided on the host before anything is launched.
+ *
+ * A new cloud (pct_set_points_f32, pct_set_points_f64, pct_set_points_device_f32, pct_use_points_device_f32) drops every
+ * result on the handle: the table, the fit results, the areas, the frames, the orientation, the PCA results and the ball
+ * rows.  It ends slab mode and owns the whole cloud.  What pct_set_async, pct_set_stats and pct_set_grid_param set stays.
+ *
+ * Ownership.  pct_set_query_range and pct_set_query_slab need a cloud (PCT_ERR_INVALID) and drop what is computed per
+ * owned row: the table, the fit results, the areas, the frames and the orientation -- also where the range is the one
+ * already set.  Ball rows and PCA results answer for the whole cloud and are untouched by a change of ownership.
+ * Slab mode begins with pct_set_query_slab(parts >= 1) and ends with pct_set_query_range, a new cloud or
+ * pct_set_query_slab(parts <= 0).  While a handle owns a slab these refuse with PCT_ERR_INVALID: pct_knn, pct_fit,
+ * pct_fit_indices, pct_fit_ball, pct_get_neighbors, pct_get_neighbor_rows, pct_get_fit, pct_neighbor_study_curvatures,
+ * pct_query_points, pct_query_points_algo, pct_query_ball, pct_point_areas, pct_get_point_areas, pct_point_energies,
+ * pct_point_frames, pct_get_point_frames, pct_orient_frames, pct_get_orientation, pct_surface_variation and
+ * pct_pca_curvatures; pct_curvature refuses every algo but PCT_KNN_AUTO and PCT_KNN_GRID.  pct_get_ball, pct_get_pca,
+ * pct_fit_indices_f64, pct_voxel_downsample and the stateless helpers keep working on a slab handle.
+ * pct_slab_counts and pct_slab_records refuse with PCT_ERR_INVALID until a pct_curvature has run in slab mode.
+ *
+ * Plantings.  pct_knn, pct_curvature, pct_surface_variation and pct_pca_curvatures need a cloud (PCT_ERR_INVALID) and
+ * drop the table in place, the fit results, the areas, the frames and the orientation.  Ball rows are untouched by a
+ * planting, and so are PCA results unless the planting is pct_pca_curvatures.  pct_knn leaves its table; pct_curvature
+ * leaves its table and the cloud-aligned fit of it; pct_surface_variation leaves a plain table of k_total - 1 neighbours
+ * and no fit; pct_pca_curvatures leaves no readable table (the one in place holds its over-fetched candidates:
+ * pct_get_neighbors and pct_fit answer PCT_ERR_NO_NEIGHBORS until the next planting) and no fit.
+ *
+ * Fits.  pct_fit, pct_curvature, pct_fit_indices and pct_fit_ball replace the fit results and drop the frames and the
+ * orientation; the table, the areas, the ball rows and the PCA results are untouched by a fit.  The results of pct_fit and
+ * pct_curvature are cloud-aligned (pct_get_fit takes rows of the owned range), those of pct_fit_indices and pct_fit_ball
+ * are row-aligned (pct_get_fit(ctx, 0, rows, ...)).  pct_point_frames and pct_point_energies need the cloud-aligned fit of
+ * the owned rows: PCT_ERR_INVALID "no fit results" after pct_fit_indices or pct_fit_ball.
+ *
+ * What needs the table: pct_fit, pct_get_neighbors, pct_get_neighbor_rows, pct_point_areas, pct_point_frames and
+ * pct_neighbor_study_curvatures answer PCT_ERR_NO_NEIGHBORS without one; pct_orient_frames answers PCT_ERR_INVALID.
+ * What needs results: pct_get_fit PCT_ERR_INVALID without fit results; pct_get_point_areas PCT_ERR_INVALID without areas;
+ * pct_get_point_frames and pct_orient_frames PCT_ERR_INVALID without frames; pct_get_orientation PCT_ERR_INVALID without
+ * an orientation; pct_get_pca PCT_ERR_INVALID without PCA results, and for idx unless keep_neighbors was set; pct_get_ball
+ * PCT_ERR_INVALID and pct_fit_ball PCT_ERR_NO_NEIGHBORS without ball rows.
+ * pct_point_areas replaces the areas and touches nothing else.  pct_point_frames replaces the frames, drops the
+ * orientation and touches nothing else.  pct_orient_frames turns the frames in place -- a second call starts from the
+ * frames as the first left them -- and replaces the orientation.
+ *
+ * Side calls.  pct_query_points, pct_query_points_algo, pct_fit_indices_f64, pct_neighbor_study_curvatures,
+ * pct_curvatures_from_coefficients, pct_plane_rotate, pct_fit_quadric, pct_mesh_energies, every pct_get_* and every
+ * *_stats call leave everything resident untouched, whichever path they take.  The point queries need a cloud
+ * (PCT_ERR_INVALID), and so do pct_fit_indices and pct_fit_indices_f64.
+ * pct_voxel_downsample and pct_voxel_downsample_f32 drop the table and nothing else: fit results, areas, frames, the
+ * orientation, ball rows and PCA results computed before stay readable, whichever sweep planted the table.
+ *
+ * Asynchronous steps (pct_set_async): whatever a pending pct_curvature will leave is what every later call finds; no call
+ * is served from the state before it. */
+
 /* ---- lifetime ---------------------------------------------------------- */
 int pct_device_count(int* count);
 int pct_create(int device, pct_ctx** out);
@@ -156,7 +218,8 @@ int pct_get_neighbor_rows(pct_ctx* ctx, const int64_t* rows, int64_t n_rows,
 int pct_fit(pct_ctx* ctx);
 /* From host-supplied neighbours: idx (rows,k) int32 for query points
  * query[rows] (NULL = 0..rows-1), optional per-row valid count.  The results replace those of an
- * earlier fit; a resident neighbour table stays as it is (pct_get_neighbors / pct_fit keep working). */
+ * earlier fit; a resident neighbour table stays as it is (pct_get_neighbors / pct_fit keep working), and so do the areas.
+ * Refused on a slab handle, as pct_fit is: the results of a slab pass are read as records, never replaced row by row. */
 int pct_fit_indices(pct_ctx* ctx, const int32_t* idx, const int32_t* count,
                     const int64_t* query, int64_t rows, int32_t k);
 /* Diagnostics variant of pct_fit_indices: the same neighbourhoods through the same kernel, but the
@@ -412,8 +475,10 @@ int pct_point_frame_stats(pct_ctx* ctx, int64_t out[4], double* ms);
  *             untouched with component -1.
  * PCT_ERR_INVALID "no point frames" without resident frames; PCT_ERR_INVALID for an owned range or slab handle, an unknown
  * anchor, or PCT_ORIENT_VIEW without a finite viewpoint.  max_components <= 0: 65536.  A new cloud, owned range, planting,
- * fit or pct_point_frames call drops the orientation.  pct_get_point_frames serves the turned frames; pct_point_frame_stats
- * keeps describing the pct_point_frames call.  pct_timings is untouched. */
+ * fit or pct_point_frames call drops the orientation; a refused pct_orient_frames does not (the orientation of an earlier
+ * call and the frames it turned stay as they are).  The flood reads the resident table: PCT_ERR_INVALID without one (after
+ * pct_voxel_downsample).  pct_get_point_frames serves the turned frames; pct_point_frame_stats keeps describing the
+ * pct_point_frames call.  pct_timings is untouched. */
 #define PCT_ORIENT_SEED 0
 #define PCT_ORIENT_TOP  1
 #define PCT_ORIENT_VIEW 2
@@ -432,7 +497,8 @@ int pct_orient_stats(pct_ctx* ctx, int64_t out[8], double* ms);
  * first point of every voxel is kept.  indices (caller-allocated, n entries) receives the kept input indices in
  * increasing order (= the reference's order of first occurrence), *count their number.  Works on any handle, with or
  * without a resident cloud; it borrows the cell list's scratch buffers, so a resident neighbour table is dropped
- * (plant it again before pct_fit / pct_get_neighbors); fit results already computed stay readable. */
+ * (plant it again before pct_fit / pct_get_neighbors); fit results, areas, frames and the orientation already computed
+ * stay readable, whichever sweep planted the table (state rules above). */
 int pct_voxel_downsample(pct_ctx* ctx, const double* xyz, int64_t n, double voxel_size, int64_t* indices, int64_t* count);
 int pct_voxel_downsample_f32(pct_ctx* ctx, const float* xyz, int64_t n, double voxel_size, int64_t* indices, int64_t* count);
 /* PCA surface variation as utils.py:778-829 DOCUMENTS it, for the loaded cloud: k_total neighbours including the point

@@ -418,6 +418,14 @@ class Handle:
                                                     _ptr(idx, _i32p), _ptr(dist, _f64p)))
         return idx, dist
 
+    def query_points_plain(self, q, k, eps=0.0):
+        """``pct_query_points`` itself: the exhaustive sweep whatever is resident (``query_points`` names the path)."""
+        q = _queries(q, "query points must have shape (m, 3)")
+        idx = np.empty((len(q), int(k)), np.int32)
+        dist = np.empty((len(q), int(k)), np.float64)
+        self._check(self._lib.pct_query_points(self._h, _ptr(q, _f64p), len(q), int(k), float(eps or 0.0), _ptr(idx, _i32p), _ptr(dist, _f64p)))
+        return idx, dist
+
     def query_ball(self, q, r, flags=BALL_SORTED, algo=QUERY_AUTO, max_entries=0):
         """``pct_query_ball``: every cloud point within ``r`` (one radius, or one per query; inclusive) of each (m,3)
         float64 query.  Returns ``(status, offsets)`` -- PCT_OK, or PCT_ERR_LIMIT when the rows hold more than
@@ -430,6 +438,8 @@ class Handle:
         offsets = np.zeros(len(q) + 1, np.int64)
         st = self._lib.pct_query_ball(self._h, _ptr(q, _f64p), len(q), _ptr(r, _f64p), len(r), int(flags), int(algo),
                                       int(max_entries), _ptr(offsets, _i64p))
+        if st in (PCT_ERR_INVALID, PCT_ERR_NONFINITE):
+            self._check(st)                   # refused before the library dropped anything: the rows of an earlier query stay, and their offsets here
         self._ball_offsets = offsets if st == PCT_OK and not flags & BALL_COUNT_ONLY else None
         if st != PCT_ERR_LIMIT:
             self._check(st)

@@ -819,6 +819,7 @@ static int stage_neighbour_rows(pct_ctx* ctx, const int32_t* idx, const int32_t*
 
 int pct_fit_indices(pct_ctx* ctx, const int32_t* idx, const int32_t* count, const int64_t* query, int64_t rows, int32_t k) {
     PCT_TRY(begin_call(ctx));
+    PCT_TRY(refuse_in_slab_mode(ctx, "pct_fit_indices"));
     int32_t pitch = 0;
     PCT_TRY(stage_neighbour_rows(ctx, idx, count, query, rows, k, &pitch, true));
     PCT_TRY(pct_reserve_fit(ctx, rows));
@@ -868,7 +869,8 @@ static QueryState query_state(const pct_ctx* ctx) {
     QueryState qs = {};
     qs.uniform_resident = ctx->grid_valid && ctx->grid_whole && !finite_limits;
     qs.tree_resident = ctx->knn_valid && ctx->knn_hier;
-    qs.sorted_resident = (ctx->knn_valid && ctx->knn_sorted_space) || (ctx->fit_valid && ctx->fit_row_order);
+    qs.sorted_resident = (ctx->knn_valid && ctx->knn_sorted_space) || (ctx->fit_valid && ctx->fit_row_order) ||
+                         (ctx->area_valid && ctx->area_row_order) || (ctx->frame_valid && ctx->frame_row_order);
     qs.sharded = ctx->q_begin != 0 || ctx->q_end != ctx->n;      // (a culled list in place: finite limits, not uniform_resident)
     qs.slab = ctx->slab_parts >= 1;
     return qs;
@@ -968,7 +970,9 @@ int pct_query_ball(pct_ctx* ctx, const double* q_xyz, int64_t m, const double* r
     if (flags & ~(PCT_BALL_SORTED | PCT_BALL_DISTANCES | PCT_BALL_COUNT_ONLY)) return pct_fail(ctx, PCT_ERR_INVALID, "unknown flags %d", flags);
     QueryRoute route;
     if (!ball_route(algo, ctx->n, m, query_state(ctx), &route)) return pct_fail(ctx, PCT_ERR_INVALID, "unknown query algorithm %d", algo);
-    ctx->ball_valid = false;                   // whatever was resident is the previous call's
+    PCT_TRY(check_queries_finite(ctx, q_xyz, m));
+    if (m > 0 && route == QueryRoute::GridBuild) PCT_TRY(build_query_grid(ctx, 30, "pct_query_ball"));      // (rows of 30: the cloud's usual sweep)
+    ctx->ball_valid = false;                   // the request is accepted and its cell list stands: whatever was resident is the previous call's
     for (int i = 0; i < 4; ++i) ctx->ball_stats[i] = 0;
     offsets[0] = 0;
     if (m == 0) {
@@ -977,8 +981,6 @@ int pct_query_ball(pct_ctx* ctx, const double* q_xyz, int64_t m, const double* r
         ctx->ball_m = 0;
         return PCT_OK;
     }
-    PCT_TRY(check_queries_finite(ctx, q_xyz, m));
-    if (route == QueryRoute::GridBuild) PCT_TRY(build_query_grid(ctx, 30, "pct_query_ball"));      // (rows of 30: the cloud's usual sweep)
     PCT_TRY(pct_reserve(ctx, &ctx->stage_a, (size_t)m * 3 * sizeof(double)));
     PCT_TRY(pct_reserve(ctx, &ctx->stage_b, (size_t)n_r * sizeof(double)));
     PCT_HIP(ctx, hipMemcpyAsync(ctx->stage_a.p, q_xyz, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
@@ -1123,8 +1125,9 @@ int pct_point_areas(pct_ctx* ctx) {
     return PCT_OK;
 }
 
-// areas in table-row order refer to the table they were taken from
-static bool areas_resident(const pct_ctx* ctx) { return ctx->area_valid && (!ctx->area_row_order || ctx->knn_valid); }
+// areas in table-row order are gathered through row_of, which outlives the table (pct_voxel_downsample clears knn_valid
+// alone) exactly as the fit's: whatever rewrites the cell order clears area_valid, and query_state keeps a query's build away
+static bool areas_resident(const pct_ctx* ctx) { return ctx->area_valid; }
 
 int pct_get_point_areas(pct_ctx* ctx, int64_t begin, int64_t end, double* area, uint8_t* closed, int32_t* nverts) {
     PCT_TRY(begin_call(ctx));
@@ -1205,8 +1208,8 @@ int pct_point_frames(pct_ctx* ctx, const double* viewpoint) {
     return PCT_OK;
 }
 
-// frames in table-row order refer to the table they were taken from
-static bool frames_resident(const pct_ctx* ctx) { return ctx->frame_valid && (!ctx->frame_row_order || ctx->knn_valid); }
+// frames in table-row order: as areas_resident
+static bool frames_resident(const pct_ctx* ctx) { return ctx->frame_valid; }
 
 int pct_get_point_frames(pct_ctx* ctx, int64_t begin, int64_t end, double* normal, double* k12, double* dirs, uint8_t* flipped) {
     PCT_TRY(begin_call(ctx));
@@ -1254,7 +1257,6 @@ static bool orientation_resident(const pct_ctx* ctx) { return ctx->orient_valid 
 int pct_orient_frames(pct_ctx* ctx, int32_t anchor, const double* viewpoint, int32_t max_components) {
     PCT_TRY(begin_call(ctx));
     PCT_TRY(refuse_in_slab_mode(ctx, "pct_orient_frames"));
-    ctx->orient_valid = false;
     if (!frames_resident(ctx) || !ctx->knn_valid) return pct_fail(ctx, PCT_ERR_INVALID, "no point frames (pct_point_frames)");
     const int64_t rows = ctx->q_end - ctx->q_begin;
     if (ctx->q_begin != 0 || ctx->q_end != ctx->n || ctx->culled || ctx->frame_rows != rows)
@@ -1265,6 +1267,7 @@ int pct_orient_frames(pct_ctx* ctx, int32_t anchor, const double* viewpoint, int
     if (anchor == PCT_ORIENT_VIEW && !(viewpoint && isfinite(viewpoint[0]) && isfinite(viewpoint[1]) && isfinite(viewpoint[2])))
         return pct_fail(ctx, PCT_ERR_INVALID, "pct_orient_frames: PCT_ORIENT_VIEW needs a finite viewpoint");
     const int max_comp = max_components <= 0 ? 65536 : max_components;
+    ctx->orient_valid = false;         // (behind every refusal: a refused call leaves the orientation of an earlier one)
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_ORIENT_BEGIN], ctx->stream));
     const int status = pct_run_orient(ctx, anchor, anchor == PCT_ORIENT_VIEW ? viewpoint : nullptr, max_comp, ctx->orient_stats);
     if (status != PCT_OK) {
