@@ -29,6 +29,7 @@ MESH_F32, MESH_F64, MESH_K64_H32, MESH_K32_H64 = 0, 1, 2, 3      # pct_mesh_ener
 
 KNN_AUTO, KNN_BRUTE, KNN_GRID, KNN_GRID_EXACT, KNN_GRID_LEVELS, KNN_TREE = 0, 1, 2, 3, 4, 5
 ORIENT_SEED, ORIENT_TOP, ORIENT_VIEW = 0, 1, 2          # pct_orient_frames' anchors
+TRI_WIND_FRAMES = 1                                     # pct_point_triangles' flag (include/pct_hip_surface.h)
 ORIENT_ANCHORS = {"seed": ORIENT_SEED, "top": ORIENT_TOP, "view": ORIENT_VIEW}
 QUERY_AUTO, QUERY_SWEEP, QUERY_GRID = 0, 1, 2                    # pct_query_points_algo, pct_query_ball
 BALL_SORTED, BALL_DISTANCES, BALL_COUNT_ONLY = 1, 2, 4           # pct_query_ball's flags
@@ -141,6 +142,16 @@ SIGNATURES = {
     "pct_selftest": (C.c_int, [_p, _i32p]),
 }
 
+# ... and every symbol declared in include/pct_hip_surface.h
+SURFACE_SIGNATURES = {
+    "pct_point_triangles": (C.c_int, [_p, C.c_int32]),
+    "pct_get_point_fans": (C.c_int, [_p, C.c_int64, C.c_int64, _i64p, _i32p]),
+    "pct_get_triangles": (C.c_int, [_p, C.c_int64, C.c_int64, _i32p]),
+    "pct_point_triangle_stats": (C.c_int, [_p, _i64p, _f64p]),
+    "pct_point_triangle_profile": (C.c_int, [_p, _f64p]),
+    "pct_write_ply_ascii_faces": (C.c_int, [C.c_char_p, _f32p, _f32p, _f32p, _f32p, C.c_int64, _i32p, C.c_int64]),
+}
+
 _lib = None
 
 
@@ -161,7 +172,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as exc:  # pragma: no cover - depends on the machine
         raise HipExtensionError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(SURFACE_SIGNATURES.items()):
         fn = getattr(lib, name)      # AttributeError if the ABI and this table diverge
         fn.restype = res
         fn.argtypes = args
@@ -228,6 +239,21 @@ def write_ply_ascii_normals(path, points, normals, gaussian, mean):
     if len(g) != len(p) or len(m) != len(p):
         raise ValueError("one curvature value per point is required")
     if load().pct_write_ply_ascii_normals(os.fsencode(path), _ptr(p, _f32p), _ptr(nr, _f32p), _ptr(g, _f32p), _ptr(m, _f32p), len(p)) != PCT_OK:
+        raise OSError(f"cannot write {path!r}")
+
+
+def write_ply_ascii_faces(path, points, normals, gaussian, mean, faces):
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    nr = np.ascontiguousarray(normals, dtype=np.float32)
+    g = np.ascontiguousarray(gaussian, dtype=np.float32)
+    m = np.ascontiguousarray(mean, dtype=np.float32)
+    t = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+    if nr.shape != p.shape:
+        raise ValueError("one normal per point is required")
+    if len(g) != len(p) or len(m) != len(p):
+        raise ValueError("one curvature value per point is required")
+    if load().pct_write_ply_ascii_faces(os.fsencode(path), _ptr(p, _f32p), _ptr(nr, _f32p), _ptr(g, _f32p), _ptr(m, _f32p), len(p),
+                                        _ptr(t, _i32p), len(t)) != PCT_OK:
         raise OSError(f"cannot write {path!r}")
 
 
@@ -657,6 +683,43 @@ class Handle:
         self._check(self._lib.pct_orient_stats(self._h, _ptr(out, _i64p), _ptr(ms, _f64p)))
         names = ("valid", "components", "unlabelled", "toggled", "levels", "pulls", "launches", "waits")
         return {**{k: int(v) for k, v in zip(names, out)}, "ms": float(ms[0])}
+
+    # -- faces from the tangent-plane Voronoi cells (include/pct_hip_surface.h) ----------------------------------------------
+    def point_triangles(self, wind_frames=False):
+        """``pct_point_triangles``: fans, corners and triangles of the resident table of a whole-cloud handle;
+        ``wind_frames``: wound about the resident frames' normals (PCT_TRI_WIND_FRAMES).  Kept on the device
+        (``get_triangles``, ``get_point_fans``)."""
+        self._check(self._lib.pct_point_triangles(self._h, TRI_WIND_FRAMES if wind_frames else 0))
+
+    def get_point_fans(self, begin, end):
+        """(offsets (rows + 1,) int64, indices int32): the natural neighbours of cloud rows [begin, end) as CSR, public
+        indices in polygon order."""
+        rows = int(end) - int(begin)
+        off = np.zeros(max(rows, 0) + 1, np.int64)
+        self._check(self._lib.pct_get_point_fans(self._h, int(begin), int(end), _ptr(off, _i64p), None))
+        nbr = np.empty(int(off[-1]), np.int32)
+        if len(nbr):
+            self._check(self._lib.pct_get_point_fans(self._h, int(begin), int(end), _ptr(off, _i64p), _ptr(nbr, _i32p)))
+        return off, nbr
+
+    def point_triangle_stats(self):
+        """Of the last ``point_triangles``: {rows, rows_with_corner, corners, triangles, wide_rows, largest_fan,
+        boundary_edges, ms, fan_ms, agree_ms (device times: the call, its fan kernels, agreement and emission)}."""
+        out = np.zeros(8, np.int64)
+        ms = np.zeros(1, np.float64)
+        self._check(self._lib.pct_point_triangle_stats(self._h, _ptr(out, _i64p), _ptr(ms, _f64p)))
+        prof = np.zeros(2, np.float64)
+        self._check(self._lib.pct_point_triangle_profile(self._h, _ptr(prof, _f64p)))
+        names = ("rows", "rows_with_corner", "corners", "triangles", "wide_rows", "largest_fan", "boundary_edges")
+        return {**{k: int(v) for k, v in zip(names, out)}, "ms": float(ms[0]), "fan_ms": float(prof[0]), "agree_ms": float(prof[1])}
+
+    def get_triangles(self, first=0, count=None):
+        """(count, 3) int32 public indices, ascending by (v0, v1, v2); by default all of them."""
+        if count is None:
+            count = self.point_triangle_stats()["triangles"] - int(first)
+        tri = np.empty((max(int(count), 0), 3), np.int32)
+        self._check(self._lib.pct_get_triangles(self._h, int(first), int(count), _ptr(tri, _i32p)))
+        return tri
 
     def point_energies(self, closed_only=False):
         """``pct_point_energies``: (bending, stretching, area, n_used) over the owned rows -- the closed ones only with

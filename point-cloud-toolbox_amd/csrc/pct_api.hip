@@ -240,7 +240,9 @@ void pct_destroy(pct_ctx* ctx) {
                       &ctx->tree_codes, &ctx->tree_vals, &ctx->tree_lvl, &ctx->tree_head, &ctx->tree_marks, &ctx->tree_seg, &ctx->tree_runs, &ctx->tree_range, &ctx->tree_bucket, &ctx->tree_tmp,
                       &ctx->pca, &ctx->pca_aux, &ctx->pca_nbr, &ctx->pca_orig,
                       &ctx->bin_rec, &ctx->bin_mat, &ctx->bin_plan, &ctx->bin_base,
-                      &ctx->area, &ctx->area_closed, &ctx->area_nverts, &ctx->area_over, &ctx->frame, &ctx->frame_flip, &ctx->orient, &ctx->stamp_tickets};
+                      &ctx->area, &ctx->area_closed, &ctx->area_nverts, &ctx->area_over, &ctx->frame, &ctx->frame_flip, &ctx->orient, &ctx->stamp_tickets,
+                      &ctx->fan_head, &ctx->fan_fast, &ctx->fan_wide, &ctx->fan_side, &ctx->fan_over, &ctx->tri_mask, &ctx->tri_count, &ctx->tri_off,
+                      &ctx->tri_tmp, &ctx->tri_part, &ctx->tri};
     for (pct_buf* b : all) pct_release(b);
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     for (auto& e : ctx->ev)
@@ -274,6 +276,7 @@ static int new_cloud(pct_ctx* ctx, int64_t n) {
     ctx->ball_valid = false;
     ctx->area_valid = false;
     ctx->frame_valid = false;
+    ctx->tri_valid = false;
     ctx->has_f64 = false;
     ctx->no_cull = ctx->culled = false;
     ctx->retries = 0;
@@ -343,6 +346,7 @@ int pct_set_query_range(pct_ctx* ctx, int64_t begin, int64_t end) {
     ctx->slab_parts = ctx->slab_part = 0;
     ctx->slab_split_valid = false;
     ctx->knn_valid = ctx->fit_valid = ctx->area_valid = ctx->frame_valid = ctx->grid_valid = false;   // the cell order depends on the owned range
+    ctx->tri_valid = false;
     ctx->no_cull = false;
     ctx->retries = 0;
     return PCT_OK;
@@ -361,6 +365,7 @@ int pct_set_query_slab(pct_ctx* ctx, int32_t part, int32_t parts) {
     ctx->slab_part = parts >= 1 ? part : 0;
     ctx->slab_split_valid = false;
     ctx->knn_valid = ctx->fit_valid = ctx->area_valid = ctx->frame_valid = ctx->grid_valid = false;
+    ctx->tri_valid = false;
     ctx->no_cull = false;
     ctx->retries = 0;
     return PCT_OK;
@@ -552,6 +557,7 @@ static int run_knn(pct_ctx* ctx, int32_t k, double eps, int32_t asked, pct_call_
     RouteSwitches sw = {false, false};             // (they matter to PCT_KNN_AUTO only)
     if (rq.auto_req) sw = RouteSwitches{pct_getenv("PCT_NO_TREE") != nullptr, pct_getenv("PCT_NO_AUTO_LEVELS") != nullptr};
     ctx->knn_valid = ctx->fit_valid = ctx->area_valid = ctx->frame_valid = false;     // a new planting drops the fit and the areas
+    ctx->tri_valid = false;            // ... and the fans and triangles
     ctx->k = k;
     ctx->eps = eps;
     PCT_TRY(clock.open(ctx, rq.auto_req, algo == PCT_KNN_GRID || algo == PCT_KNN_GRID_EXACT, kind));
@@ -1311,6 +1317,84 @@ int pct_orient_stats(pct_ctx* ctx, int64_t out[8], double* ms) {
     const bool live = orientation_resident(ctx);
     for (int i = 0; i < 8; ++i) out[i] = live ? ctx->orient_stats[i] : 0;
     if (ms) *ms = live ? ctx->orient_ms : 0.0;
+    return PCT_OK;
+}
+
+// ---- faces from the tangent-plane Voronoi cells (pct_fan.hip, include/pct_hip_surface.h) -----------------------------------
+int pct_point_triangles(pct_ctx* ctx, int32_t flags) {
+    PCT_TRY(begin_call(ctx));
+    PCT_TRY(refuse_in_slab_mode(ctx, "pct_point_triangles"));
+    if (!ctx->knn_valid) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "plant the neighbour table first (pct_knn)");
+    if (ctx->q_begin != 0 || ctx->q_end != ctx->n || ctx->culled)
+        return pct_fail(ctx, PCT_ERR_INVALID, "pct_point_triangles: the handle owns rows [%lld,%lld) of %lld: agreement needs the whole cloud",
+                        (long long)ctx->q_begin, (long long)ctx->q_end, (long long)ctx->n);
+    if (flags & ~PCT_TRI_WIND_FRAMES) return pct_fail(ctx, PCT_ERR_INVALID, "pct_point_triangles: unknown flags %d", flags);
+    const bool wind = (flags & PCT_TRI_WIND_FRAMES) != 0;
+    if (wind && !(ctx->frame_valid && ctx->frame_rows == ctx->n)) return pct_fail(ctx, PCT_ERR_INVALID, "no point frames (pct_point_frames)");
+    ctx->tri_valid = false;            // (behind every refusal: a refused call leaves the triangles of an earlier one)
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_TRI_BEGIN], ctx->stream));
+    const int status = pct_launch_point_triangles(ctx, wind, ctx->ev[PCT_EV_TRI_MID]);
+    if (status != PCT_OK) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return status;
+    }
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_TRI_END], ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const unsigned long long* w = ctx->pin->tri_words;
+    ctx->tri_rows = ctx->n;
+    ctx->tri_total = (int64_t)w[7];
+    const int64_t st[8] = {ctx->n, (int64_t)w[1], (int64_t)w[2], ctx->tri_total, (int64_t)w[0], (int64_t)w[3], (int64_t)w[4], 0};
+    for (int i = 0; i < 8; ++i) ctx->tri_stats[i] = st[i];
+    ctx->tri_ms[0] = ev_ms(ctx, PCT_EV_TRI_BEGIN, PCT_EV_TRI_END);
+    ctx->tri_ms[1] = ev_ms(ctx, PCT_EV_TRI_BEGIN, PCT_EV_TRI_MID);
+    ctx->tri_ms[2] = ev_ms(ctx, PCT_EV_TRI_MID, PCT_EV_TRI_END);
+    ctx->tri_valid = true;
+    return PCT_OK;
+}
+
+int pct_get_point_fans(pct_ctx* ctx, int64_t begin, int64_t end, int64_t* offsets, int32_t* nbr) {
+    PCT_TRY(begin_call(ctx));
+    if (!ctx->tri_valid) return pct_fail(ctx, PCT_ERR_INVALID, "no triangles (pct_point_triangles)");
+    if (begin < 0 || end > ctx->tri_rows || begin > end || !offsets)
+        return pct_fail(ctx, PCT_ERR_INVALID, "rows [%lld,%lld) outside the cloud", (long long)begin, (long long)end);
+    const int64_t rows = end - begin;
+    PCT_TRY(pct_reserve(ctx, &ctx->stage_a, (size_t)(rows + 1) * sizeof(int64_t)));
+    PCT_TRY(pct_reserve(ctx, &ctx->stage_b, (size_t)(rows + 1) * sizeof(int64_t)));
+    int64_t* d_off = (int64_t*)ctx->stage_b.p;
+    PCT_TRY(pct_launch_point_fans(ctx, begin, rows, (int64_t*)ctx->stage_a.p, d_off, nullptr));
+    PCT_HIP(ctx, hipMemcpyAsync(offsets, d_off, (size_t)(rows + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const int64_t total = offsets[rows];
+    if (!nbr || total == 0) return PCT_OK;
+    PCT_TRY(pct_reserve(ctx, &ctx->stage_d, (size_t)total * sizeof(int)));
+    PCT_TRY(pct_launch_point_fans(ctx, begin, rows, (int64_t*)ctx->stage_a.p, d_off, (int*)ctx->stage_d.p));
+    PCT_HIP(ctx, hipMemcpyAsync(nbr, ctx->stage_d.p, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PCT_OK;
+}
+
+int pct_get_triangles(pct_ctx* ctx, int64_t first, int64_t count, int32_t* tri) {
+    PCT_TRY(begin_call(ctx));
+    if (!ctx->tri_valid) return pct_fail(ctx, PCT_ERR_INVALID, "no triangles (pct_point_triangles)");
+    if (first < 0 || count < 0 || first + count > ctx->tri_total || (count > 0 && !tri))
+        return pct_fail(ctx, PCT_ERR_INVALID, "triangles [%lld,%lld) outside the %lld resident", (long long)first, (long long)(first + count),
+                        (long long)ctx->tri_total);
+    if (count == 0) return PCT_OK;
+    PCT_HIP(ctx, hipMemcpyAsync(tri, (const int*)ctx->tri.p + first * 3, (size_t)count * 3 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PCT_OK;
+}
+
+int pct_point_triangle_stats(pct_ctx* ctx, int64_t out[8], double* ms) {
+    if (!ctx || !out) return PCT_ERR_INVALID;
+    for (int i = 0; i < 8; ++i) out[i] = ctx->tri_valid ? ctx->tri_stats[i] : 0;
+    if (ms) *ms = ctx->tri_valid ? ctx->tri_ms[0] : 0.0;
+    return PCT_OK;
+}
+
+int pct_point_triangle_profile(pct_ctx* ctx, double out[2]) {
+    if (!ctx || !out) return PCT_ERR_INVALID;
+    for (int i = 0; i < 2; ++i) out[i] = ctx->tri_valid ? ctx->tri_ms[1 + i] : 0.0;
     return PCT_OK;
 }
 

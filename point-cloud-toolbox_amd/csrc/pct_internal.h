@@ -8,6 +8,7 @@
 #include <stdlib.h>
 
 #include "../../include/pct_hip.h"
+#include "../../include/pct_hip_surface.h"
 #include "pct_stamp.h"
 #include "pct_clock.h"
 
@@ -122,6 +123,7 @@ struct pct_pinned {
     alignas(64) pct_stamp_block stamps[2];
     alignas(64) unsigned long long frame_words[8];   // pct_point_frames (pct_frame.hip): NaN rows, flipped rows, umbilic rows
     alignas(64) int orient_words[16];                // pct_orient_frames (pct_orient.hip): its control words, OrientWord
+    alignas(64) unsigned long long tri_words[8];     // pct_point_triangles (pct_fan.hip): FanWord; [7] the triangle count
 };
 static_assert(sizeof(pct_pinned) <= 4096, "pct_create allocates 4096 bytes");
 
@@ -134,6 +136,7 @@ enum pct_event {                           // ctx->ev
     PCT_EV_AREA_BEGIN, PCT_EV_AREA_END,    // pct_point_areas
     PCT_EV_FRAME_BEGIN, PCT_EV_FRAME_END,  // pct_point_frames
     PCT_EV_ORIENT_BEGIN, PCT_EV_ORIENT_END,// pct_orient_frames
+    PCT_EV_TRI_BEGIN, PCT_EV_TRI_MID, PCT_EV_TRI_END,   // pct_point_triangles: the fan kernels | agreement and emission
     PCT_EV_COUNT
 };
 
@@ -355,6 +358,22 @@ struct pct_ctx {
     int64_t orient_rows = 0;
     int64_t orient_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // valid rows, components, unlabelled, toggled, levels, pull rounds, launches, waits
     double orient_ms = 0;
+
+    // fans and triangles of the resident table of a whole-cloud handle (pct_fan.hip), everything by public index: they
+    // depend on neither the table nor row_of once computed
+    pct_buf fan_head;      // int2 (n): {vertices of the row's cell, slot in fan_wide or -1}
+    pct_buf fan_fast;      // int32 (n, kAreaCap): the fan codes of the rows the fast kernel finished
+    pct_buf fan_wide;      // int32 (overflow rows, k + 4): ... of the rows redone with room for k + 4 vertices
+    pct_buf fan_side;      // uint8 (n): the frames' flipped bits as the call found them
+    pct_buf fan_over;      // eight statistics words, then int32 (n): the overflow list
+    pct_buf tri_mask, tri_count, tri_off, tri_tmp;   // agreed corners per row, triangles per row, their scan, scan scratch
+    pct_buf tri_part;      // u64 (blocks, 4): the statistics' per-block partial sums
+    pct_buf tri;           // int32 (triangles, 3), ascending
+    bool tri_valid = false;
+    int32_t tri_wpitch = 0;
+    int64_t tri_rows = 0, tri_total = 0;
+    int64_t tri_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double tri_ms[3] = {0, 0, 0};           // device milliseconds: the call, its fan kernels, agreement and emission
 };
 
 int pct_fail(pct_ctx* ctx, int code, const char* fmt, ...);
@@ -536,6 +555,11 @@ int pct_launch_gather_frames(pct_ctx* ctx, int64_t first, int64_t rows, double* 
 // handle; the control words are on their way to ctx->pin->orient_words on return (complete after the stream's next wait),
 // stats8[6] and [7] (kernel launches, host waits) are filled here
 int pct_run_orient(pct_ctx* ctx, int anchor, const double* viewpoint, int max_comp, int64_t stats8[8]);
+// pct_fan.hip: fans and triangles of the resident table of a whole-cloud handle (mid: recorded between the fan kernels and
+// the agreement; the statistics words are on their way to ctx->pin->tri_words on return, the triangle count is in [7]),
+// and the natural neighbours of public rows [first, first + rows) as CSR (d_count: rows + 1 words of scratch)
+int pct_launch_point_triangles(pct_ctx* ctx, bool wind_frames, hipEvent_t mid);
+int pct_launch_point_fans(pct_ctx* ctx, int64_t first, int64_t rows, int64_t* d_count, int64_t* d_off, int* d_nbr);
 int pct_voxel_downsample_device(pct_ctx* ctx, const void* d_xyz, bool f64, int64_t n, double voxel, int64_t* d_out, int64_t* count);
 int pct_launch_surface_variation(pct_ctx* ctx, float* d_out);
 // PCA principal curvatures (pct_pca.hip).  The sweep fetches up to PCT_PCA_EXTRA candidates beyond k per point, re-ranked

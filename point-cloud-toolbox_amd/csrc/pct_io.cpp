@@ -7,6 +7,7 @@
 //                                    (/root/reference/utils.py:538-551); numbers formatted exactly as the f-string
 //                                    does: repr(float(np.float32 value))
 //   pct_write_ply_ascii_normals    : the same with nx ny nz between the coordinates and the curvatures
+//   pct_write_ply_ascii_faces      : ... and the triangles behind the vertices (include/pct_hip_surface.h)
 // Pure C++17 (no device code); lives in the same shared library so the ctypes shim has one ABI.
 #include <charconv>
 #include <cmath>
@@ -24,6 +25,7 @@
 #include <unistd.h>
 
 #include "../../include/pct_hip.h"
+#include "../../include/pct_hip_surface.h"
 
 namespace {
 
@@ -264,15 +266,18 @@ int pct_text_load(const char* path, int64_t rows, int32_t cols, double* out) {
 
 int pct_format_float(double x, char* out32) { return out32 ? format_py_float(x, out32) : 0; }
 
-// One vertex per line: the coordinates, `normals` (n, 3; null: none), K and H, numbers as the reference's f-string prints them
+// One vertex per line: the coordinates, `normals` (n, 3; null: none), K and H, numbers as the reference's f-string prints them;
+// tri (null: no face element): one "3 a b c" line per triangle behind the vertices
 static int write_ply_vertices(const char* path, const float* xyz, const float* normals, const float* gaussian, const float* mean,
-                              int64_t n) {
+                              int64_t n, const int32_t* tri = nullptr, int64_t n_tri = 0) {
     if (!path || !xyz || !gaussian || !mean || n < 0) return PCT_ERR_INVALID;
     FILE* f = fopen(path, "wb");
     if (!f) return PCT_ERR_INVALID;
+    char faces[96] = "";
+    if (tri) snprintf(faces, sizeof faces, "element face %lld\nproperty list uchar int vertex_indices\n", (long long)n_tri);
     fprintf(f, "ply\nformat ascii 1.0\nelement vertex %lld\nproperty float x\nproperty float y\nproperty float z\n%s"
-               "property float gaussian_curvature\nproperty float mean_curvature\nend_header\n", (long long)n,
-            normals ? "property float nx\nproperty float ny\nproperty float nz\n" : "");   // utils.py:539-547
+               "property float gaussian_curvature\nproperty float mean_curvature\n%send_header\n", (long long)n,
+            normals ? "property float nx\nproperty float ny\nproperty float nz\n" : "", faces);   // utils.py:539-547
     int threads = (int)std::thread::hardware_concurrency();
     if (threads < 1) threads = 1;
     if (threads > 32) threads = 32;
@@ -301,6 +306,14 @@ static int write_ply_vertices(const char* path, const float* xyz, const float* n
     for (auto& x : th) x.join();
     bool ok = true;
     for (auto& s : parts) ok = ok && fwrite(s.data(), 1, s.size(), f) == s.size();
+    if (tri) {
+        std::string s;
+        s.reserve((size_t)n_tri * 24);
+        char buf[64];
+        for (int64_t i = 0; i < n_tri; ++i)
+            s.append(buf, (size_t)snprintf(buf, sizeof buf, "3 %d %d %d\n", tri[3 * i], tri[3 * i + 1], tri[3 * i + 2]));
+        ok = ok && fwrite(s.data(), 1, s.size(), f) == s.size();
+    }
     ok = fclose(f) == 0 && ok;
     return ok ? PCT_OK : PCT_ERR_INVALID;
 }
@@ -313,6 +326,15 @@ int pct_write_ply_ascii_normals(const char* path, const float* xyz, const float*
                                 const float* mean, int64_t n) {
     if (!normals) return PCT_ERR_INVALID;
     return write_ply_vertices(path, xyz, normals, gaussian, mean, n);
+}
+
+int pct_write_ply_ascii_faces(const char* path, const float* xyz, const float* normals, const float* gaussian, const float* mean,
+                              int64_t n, const int32_t* tri, int64_t n_tri) {
+    if (!normals || n_tri < 0 || (n_tri > 0 && !tri)) return PCT_ERR_INVALID;
+    for (int64_t i = 0; i < 3 * n_tri; ++i)
+        if (tri[i] < 0 || tri[i] >= n) return PCT_ERR_INVALID;
+    static const int32_t none[3] = {0, 0, 0};
+    return write_ply_vertices(path, xyz, normals, gaussian, mean, n, tri ? tri : none, n_tri);
 }
 
 }  // extern "C"

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _capi
 
-__all__ = ["mesh_energies", "point_energies", "load_mesh_compute_energies"]
+__all__ = ["mesh_energies", "point_energies", "triangulated_energies", "load_mesh_compute_energies"]
 
 
 def mesh_energies(vertices, triangles, gaussian_curvature, mean_curvature, device=0):
@@ -36,6 +36,24 @@ def point_energies(points, k, eps=None, closed_only=False, device=0):
         h.curvature(int(k), eps or 0.0)
         h.point_areas()
         return h.point_energies(closed_only)[:3]
+    finally:
+        h.close()
+
+
+def triangulated_energies(points, k, eps=None, device=0):
+    """(bending_energy, stretching_energy, total_area) of a point cloud over its own triangles: k-NN, quadric fit and the
+    faces of the tangent-plane Voronoi cells on the device (``pct_point_triangles``, include/pct_hip_surface.h), then the
+    mesh integral of ``load_mesh_compute_energies`` over them (``pct_mesh_energies``) -- the reference's pipeline from scan
+    to energies (utils:92-96, utils:702-765) without a host mesher."""
+    pts = np.asarray(points)
+    pts = pts if pts.dtype == np.float64 else pts.astype(np.float32, copy=False)
+    h = _capi.Handle(device)
+    try:
+        h.set_points(pts)
+        h.curvature(int(k), eps or 0.0)
+        h.point_triangles()
+        _, K, H, _ = h.get_fit(0, len(pts), coefs=False)
+        return h.mesh_energies(pts, h.get_triangles(), K, H)
     finally:
         h.close()
 

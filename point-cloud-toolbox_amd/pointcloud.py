@@ -196,6 +196,7 @@ class PointCloud:
         self._area_cache = None
         self._frame_key = None          # (planting, fit, viewpoint) whose surface frames are on the device
         self._frame_cache = None
+        self._faces_token = -1          # the planting whose faces are in ``faces`` / ``natural_neighbors``
         self.eps = None
         self.collect_stats = False      # sweep statistics in last_timings (costs atomics)
 
@@ -522,13 +523,53 @@ class PointCloud:
         (``compute_surface_frames`` without a viewpoint).  Sets ``self.normals``."""
         self.compute_surface_frames()
 
+    # ------------------------------------------------ faces: triangles from the tangent-plane Voronoi cells
+    def compute_surface_triangles(self, use_frames=None):
+        """Triangles of the surface without leaving the device (``pct_point_triangles``, include/pct_hip_surface.h): every
+        point's Voronoi cell in its own tangent plane gives its natural neighbours in order, two consecutive ones propose a
+        triangle, and the triangles all three of their corners propose are kept -- the role ball pivoting plays in the
+        reference's pipeline (utils:92-96).  ``use_frames``: wind every face counter-clockwise about the normal of its
+        lowest corner as the resident frames hold it (after ``orient_normals_consistently``: one side per component);
+        default: where frames of this planting and fit are resident.  Without them the winding follows the fit's own side.
+        Sets ``faces`` (T, 3) int32 -- the attribute the reference's export reads (pct:711) --, ``natural_neighbors``
+        ((N + 1,) int64 offsets, int32 indices) and ``last_triangle_stats``; returns ``faces``."""
+        h = self._planted_table()
+        resident = self._frame_key is not None and self._frame_key[:2] == (self._plant_token, self._fit_serial) and \
+            self._frames_on_device(self._frame_key)
+        if use_frames is None:
+            use_frames = resident
+        if use_frames and not resident:
+            raise ValueError("no surface frames of this planting and fit on the device (compute_surface_frames)")
+        h.point_triangles(bool(use_frames))
+        self.last_triangle_stats = h.point_triangle_stats()
+        self.faces = h.get_triangles(0, self.last_triangle_stats["triangles"])
+        self.natural_neighbors = h.get_point_fans(0, self._n_dev)
+        self._faces_token = self._plant_token
+        return self.faces
+
+    def compute_mesh_energies(self):
+        """``(bending, stretching, area)`` over ``faces`` (utils.py:702-765 on this cloud's own triangles): the cloud,
+        ``faces``, ``K_quadratic`` and ``H_quadratic`` through ``pct_mesh_energies``.  Computes the faces and the
+        curvatures of the planted table where they are missing."""
+        if getattr(self, "faces", None) is None or self._faces_token != self._plant_token:
+            self.compute_surface_triangles()
+        if not hasattr(self, "K_quadratic"):
+            self.compute_pointwise_explicit_quadratic_curvature()
+        from . import energies
+        return energies.mesh_energies(np.asarray(self.points), self.faces, self.K_quadratic, self.H_quadratic, self._device)
+
     def export_ply_with_curvature_and_normals(self, filename):
-        """pct:699-726 without faces: ASCII PLY vertices ``x y z nx ny nz gaussian_curvature mean_curvature``.  Computes
-        the normals first when ``self.normals`` is missing or is not one normal per point (pct:701-702)."""
+        """pct:699-726: ASCII PLY vertices ``x y z nx ny nz gaussian_curvature mean_curvature`` and, once ``faces`` has been
+        computed (``compute_surface_triangles``; pct:711), the face element behind them.  Computes the normals first when
+        ``self.normals`` is missing or is not one normal per point (pct:701-702)."""
         normals = getattr(self, "normals", None)
         if normals is None or np.shape(normals) != (len(self.points), 3):
             self.compute_normals()
-        _capi.write_ply_ascii_normals(filename, np.asarray(self.points), self.normals, self.K_quadratic, self.H_quadratic)
+        faces = getattr(self, "faces", None)
+        if faces is not None and len(faces) > 0:
+            _capi.write_ply_ascii_faces(filename, np.asarray(self.points), self.normals, self.K_quadratic, self.H_quadratic, faces)
+        else:
+            _capi.write_ply_ascii_normals(filename, np.asarray(self.points), self.normals, self.K_quadratic, self.H_quadratic)
 
     def export_ply_with_curvatures(self, filename='output_with_curvatures.ply'):
         """The ASCII PLY validate_shape writes after the curvature step (utils.py:538-551), same bytes."""
