@@ -86,8 +86,10 @@ typedef struct pct_timings {
 
 /* ---- state rules: what a call needs, what it leaves, what it drops --------------------------------------------------------
  * One handle holds at most one of each: a cloud, an owned range or slab, a neighbour table, fit results, point areas, point
- * frames with their orientation, PCA results, ball rows.  The entry points below say what they compute; these rules say how
- * they meet on one handle.  tests/call_model.py states them again as a table and quotes every sentence it relies on;
+ * frames with their orientation, fans and triangles, PCA results, ball rows.  The entry points below and in
+ * pct_hip_surface.h say what they compute; these rules say how they meet on one handle.  The library keeps them as one
+ * table, csrc/pct_residents.h: which event drops which results, and what a result is derived from.  tests/call_model.py
+ * states them again as a table and quotes every sentence it relies on (tests/test_residents.py holds the two tables equal);
  * tests/call_driver.py runs random call sequences against them.
  *
  * Refusals.  A refused call changes nothing: after a call that returns an error status for its arguments or for the state
@@ -99,35 +101,35 @@ typedef struct pct_timings {
  *
  * A new cloud (pct_set_points_f32, pct_set_points_f64, pct_set_points_device_f32, pct_use_points_device_f32) drops every
  * result on the handle: the table, the fit results, the areas, the frames, the orientation, the PCA results and the ball
- * rows.  It ends slab mode and owns the whole cloud.  What pct_set_async, pct_set_stats and pct_set_grid_param set stays.
+ * rows, and the triangles with them.  It ends slab mode and owns the whole cloud.  What pct_set_async, pct_set_stats and pct_set_grid_param set stays.
  *
  * Ownership.  pct_set_query_range and pct_set_query_slab need a cloud (PCT_ERR_INVALID) and drop what is computed per
- * owned row: the table, the fit results, the areas, the frames and the orientation -- also where the range is the one
- * already set.  Ball rows and PCA results answer for the whole cloud and are untouched by a change of ownership.
+ * owned row: the table, the fit results, the areas, the frames and the orientation, and the triangles -- also where the
+ * range is the one already set.  Ball rows and PCA results answer for the whole cloud and are untouched by a change of ownership.
  * Slab mode begins with pct_set_query_slab(parts >= 1) and ends with pct_set_query_range, a new cloud or
  * pct_set_query_slab(parts <= 0).  While a handle owns a slab these refuse with PCT_ERR_INVALID: pct_knn, pct_fit,
  * pct_fit_indices, pct_fit_ball, pct_get_neighbors, pct_get_neighbor_rows, pct_get_fit, pct_neighbor_study_curvatures,
  * pct_query_points, pct_query_points_algo, pct_query_ball, pct_point_areas, pct_get_point_areas, pct_point_energies,
- * pct_point_frames, pct_get_point_frames, pct_orient_frames, pct_get_orientation, pct_surface_variation and
- * pct_pca_curvatures; pct_curvature refuses every algo but PCT_KNN_AUTO and PCT_KNN_GRID.  pct_get_ball, pct_get_pca,
+ * pct_point_frames, pct_get_point_frames, pct_orient_frames, pct_get_orientation, pct_point_triangles,
+ * pct_surface_variation and pct_pca_curvatures; pct_curvature refuses every algo but PCT_KNN_AUTO and PCT_KNN_GRID.  pct_get_ball, pct_get_pca,
  * pct_fit_indices_f64, pct_voxel_downsample and the stateless helpers keep working on a slab handle.
  * pct_slab_counts and pct_slab_records refuse with PCT_ERR_INVALID until a pct_curvature has run in slab mode.
  *
  * Plantings.  pct_knn, pct_curvature, pct_surface_variation and pct_pca_curvatures need a cloud (PCT_ERR_INVALID) and
- * drop the table in place, the fit results, the areas, the frames and the orientation.  Ball rows are untouched by a
+ * drop the table in place, the fit results, the areas, the frames and the orientation, and the triangles.  Ball rows are untouched by a
  * planting, and so are PCA results unless the planting is pct_pca_curvatures.  pct_knn leaves its table; pct_curvature
  * leaves its table and the cloud-aligned fit of it; pct_surface_variation leaves a plain table of k_total - 1 neighbours
  * and no fit; pct_pca_curvatures leaves no readable table (the one in place holds its over-fetched candidates:
  * pct_get_neighbors and pct_fit answer PCT_ERR_NO_NEIGHBORS until the next planting) and no fit.
  *
  * Fits.  pct_fit, pct_curvature, pct_fit_indices and pct_fit_ball replace the fit results and drop the frames and the
- * orientation; the table, the areas, the ball rows and the PCA results are untouched by a fit.  The results of pct_fit and
+ * orientation; the table, the areas, the ball rows and the PCA results are untouched by a fit, and so are the triangles.  The results of pct_fit and
  * pct_curvature are cloud-aligned (pct_get_fit takes rows of the owned range), those of pct_fit_indices and pct_fit_ball
  * are row-aligned (pct_get_fit(ctx, 0, rows, ...)).  pct_point_frames and pct_point_energies need the cloud-aligned fit of
  * the owned rows: PCT_ERR_INVALID "no fit results" after pct_fit_indices or pct_fit_ball.
  *
- * What needs the table: pct_fit, pct_get_neighbors, pct_get_neighbor_rows, pct_point_areas, pct_point_frames and
- * pct_neighbor_study_curvatures answer PCT_ERR_NO_NEIGHBORS without one; pct_orient_frames answers PCT_ERR_INVALID.
+ * What needs the table: pct_fit, pct_get_neighbors, pct_get_neighbor_rows, pct_point_areas, pct_point_frames,
+ * pct_point_triangles and pct_neighbor_study_curvatures answer PCT_ERR_NO_NEIGHBORS without one; pct_orient_frames answers PCT_ERR_INVALID.
  * What needs results: pct_get_fit PCT_ERR_INVALID without fit results; pct_get_point_areas PCT_ERR_INVALID without areas;
  * pct_get_point_frames and pct_orient_frames PCT_ERR_INVALID without frames; pct_get_orientation PCT_ERR_INVALID without
  * an orientation; pct_get_pca PCT_ERR_INVALID without PCA results, and for idx unless keep_neighbors was set; pct_get_ball
@@ -136,12 +138,22 @@ typedef struct pct_timings {
  * orientation and touches nothing else.  pct_orient_frames turns the frames in place -- a second call starts from the
  * frames as the first left them -- and replaces the orientation.
  *
+ * Triangles (pct_hip_surface.h).  pct_point_triangles needs the table and a whole-cloud handle, because agreement reads other
+ * rows' corners: PCT_ERR_INVALID for an owned range, as pct_orient_frames.  Unknown flag bits: PCT_ERR_INVALID.
+ * PCT_TRI_WIND_FRAMES without resident frames: PCT_ERR_INVALID "no point frames"; without the flag no frames are needed.
+ * pct_point_triangles replaces the fans and triangles and touches nothing else: table, fit results, areas, frames,
+ * orientation, PCA results, ball rows and pct_timings keep their bytes.  A new cloud, a change of ownership and every
+ * planting drop the triangles; a fit, pct_point_frames, pct_orient_frames and pct_voxel_downsample do not: they are kept by
+ * public index, and the winding is a snapshot of the flipped bits at the call.  pct_get_point_fans and pct_get_triangles
+ * PCT_ERR_INVALID without triangles.
+ *
  * Side calls.  pct_query_points, pct_query_points_algo, pct_fit_indices_f64, pct_neighbor_study_curvatures,
  * pct_curvatures_from_coefficients, pct_plane_rotate, pct_fit_quadric, pct_mesh_energies, every pct_get_* and every
  * *_stats call leave everything resident untouched, whichever path they take.  The point queries need a cloud
  * (PCT_ERR_INVALID), and so do pct_fit_indices and pct_fit_indices_f64.
  * pct_voxel_downsample and pct_voxel_downsample_f32 drop the table and nothing else: fit results, areas, frames, the
- * orientation, ball rows and PCA results computed before stay readable, whichever sweep planted the table.
+ * orientation, ball rows and PCA results computed before stay readable, whichever sweep planted the table; so do the
+ * triangles.
  *
  * Asynchronous steps (pct_set_async): whatever a pending pct_curvature will leave is what every later call finds; no call
  * is served from the state before it. */

@@ -1,7 +1,7 @@
 /*
  * pct_hip_surface.h -- the connectivity of the surface: natural neighbours and triangles from the tangent-plane Voronoi
- * cells of the resident neighbour table.  Same handle, same status codes and same conventions as pct_hip.h, which this
- * header includes; its entry points are bound by their own table of the ctypes shim.
+ * cells of the resident neighbour table.  Same handle, same status codes, same conventions and same state rules as
+ * pct_hip.h, which this header includes; the ctypes shim binds both headers' entry points from one table.
  *
  * The reference's pipeline builds a triangle mesh on the host before anything else (ball pivoting, utils:92-96), writes
  * self.faces into its PLY (pct:710-715) and integrates its energies over triangles (load_mesh_compute_energies).  Here the
@@ -42,16 +42,10 @@ extern "C" {
  * (PCT_KNN_BRUTE and PCT_KNN_GRID plantings give the same bytes), and two calls on the same state give the same bytes (no
  * atomics on the output).
  *
- * State.  Needs a cloud and the resident table: PCT_ERR_NO_NEIGHBORS without one, as pct_point_areas.  Needs a whole-cloud
- * handle, because agreement reads other rows' corners: PCT_ERR_INVALID for an owned range or a slab, as pct_orient_frames.
- * PCT_TRI_WIND_FRAMES without resident frames: PCT_ERR_INVALID "no point frames"; without the flag no frames are needed
- * and the winding follows the fit's own side.  Unknown flag bits: PCT_ERR_INVALID.  eps counts and rows of up to 511
- * neighbours work as in pct_point_areas.  A refused call changes nothing (the triangles of an earlier call stay).  The
- * call touches nothing else on the handle: table, fit, areas, frames, orientation, PCA results, ball rows and pct_timings
- * keep their bytes.  A new cloud, a change of ownership (pct_set_query_range, pct_set_query_slab) or a planting (pct_knn,
- * pct_curvature) drops the triangles and fans; a fit, pct_point_frames, pct_orient_frames and pct_voxel_downsample do not:
- * they are kept by public index, and the winding is a snapshot of the flipped bits at the call.  Under pct_set_async the
- * call first waits for a pending call, like every blocking entry point. */
+ * State: the rules are in pct_hip.h ("Triangles", and the paragraphs on refusals, new clouds, ownership and plantings) --
+ * what the call needs, that it touches nothing else, what drops the triangles and what does not.  Without
+ * PCT_TRI_WIND_FRAMES the winding follows the fit's own side.  eps counts and rows of up to 511 neighbours work as in
+ * pct_point_areas. */
 #define PCT_TRI_WIND_FRAMES 1
 int pct_point_triangles(pct_ctx* ctx, int32_t flags);
 /* The natural neighbours of cloud rows [begin, end) as CSR: offsets (end - begin + 1, int64, from 0), nbr public indices

@@ -61,7 +61,7 @@ _f32p = C.POINTER(C.c_float)
 _f64p = C.POINTER(C.c_double)
 _u8p = C.POINTER(C.c_uint8)
 
-# name -> (restype, argtypes); every symbol declared in include/pct_hip.h
+# name -> (restype, argtypes); every symbol declared in include/pct_hip.h and include/pct_hip_surface.h
 SIGNATURES = {
     "pct_device_count": (C.c_int, [C.POINTER(C.c_int)]),
     "pct_create": (C.c_int, [C.c_int, C.POINTER(_p)]),
@@ -140,10 +140,7 @@ SIGNATURES = {
     "pct_device_download": (C.c_int, [_p, _p, _p, C.c_int64]),
     "pct_synchronize": (C.c_int, [_p]),
     "pct_selftest": (C.c_int, [_p, _i32p]),
-}
-
-# ... and every symbol declared in include/pct_hip_surface.h
-SURFACE_SIGNATURES = {
+    # include/pct_hip_surface.h
     "pct_point_triangles": (C.c_int, [_p, C.c_int32]),
     "pct_get_point_fans": (C.c_int, [_p, C.c_int64, C.c_int64, _i64p, _i32p]),
     "pct_get_triangles": (C.c_int, [_p, C.c_int64, C.c_int64, _i32p]),
@@ -172,7 +169,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as exc:  # pragma: no cover - depends on the machine
         raise HipExtensionError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, (res, args) in list(SIGNATURES.items()) + list(SURFACE_SIGNATURES.items()):
+    for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)      # AttributeError if the ABI and this table diverge
         fn.restype = res
         fn.argtypes = args
@@ -685,11 +682,11 @@ class Handle:
         return {**{k: int(v) for k, v in zip(names, out)}, "ms": float(ms[0])}
 
     # -- faces from the tangent-plane Voronoi cells (include/pct_hip_surface.h) ----------------------------------------------
-    def point_triangles(self, wind_frames=False):
+    def point_triangles(self, wind_frames=False, flags=0):
         """``pct_point_triangles``: fans, corners and triangles of the resident table of a whole-cloud handle;
-        ``wind_frames``: wound about the resident frames' normals (PCT_TRI_WIND_FRAMES).  Kept on the device
-        (``get_triangles``, ``get_point_fans``)."""
-        self._check(self._lib.pct_point_triangles(self._h, TRI_WIND_FRAMES if wind_frames else 0))
+        ``wind_frames``: wound about the resident frames' normals (PCT_TRI_WIND_FRAMES); ``flags``: further flag bits,
+        passed as they are.  Kept on the device (``get_triangles``, ``get_point_fans``)."""
+        self._check(self._lib.pct_point_triangles(self._h, (TRI_WIND_FRAMES if wind_frames else 0) | int(flags)))
 
     def get_point_fans(self, begin, end):
         """(offsets (rows + 1,) int64, indices int32): the natural neighbours of cloud rows [begin, end) as CSR, public

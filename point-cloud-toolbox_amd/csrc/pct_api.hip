@@ -264,22 +264,25 @@ static int begin_call(pct_ctx* ctx, bool wait_for_pending = true) {
     return PCT_OK;
 }
 
+// a change of ownership -- rows [begin, end), or (parts >= 1) a slab, whose rows the build cuts: the cell order depends on it
+static void own_rows(pct_ctx* ctx, int64_t begin, int64_t end, int32_t part, int32_t parts) {
+    ctx->q_begin = begin;
+    ctx->q_end = end;
+    ctx->slab_parts = parts;
+    ctx->slab_part = part;
+    ctx->slab_split_valid = ctx->grid_valid = false;
+    ctx->res.drop(PCT_OWNERSHIP);
+    ctx->no_cull = false;
+    ctx->retries = 0;
+}
+
 static int new_cloud(pct_ctx* ctx, int64_t n) {
     if (n <= 0 || n > (int64_t)INT32_MAX - 1024) return pct_fail(ctx, PCT_ERR_INVALID, "cloud size %lld out of range", (long long)n);
     ctx->n = n;
-    ctx->q_begin = 0;
-    ctx->q_end = n;
-    ctx->slab_parts = ctx->slab_part = 0;
-    ctx->slab_split_valid = false;
-    ctx->grid_valid = ctx->knn_valid = ctx->fit_valid = ctx->pts4_valid = ctx->qpts4_valid = false;
-    ctx->pca_valid = false;
-    ctx->ball_valid = false;
-    ctx->area_valid = false;
-    ctx->frame_valid = false;
-    ctx->tri_valid = false;
-    ctx->has_f64 = false;
-    ctx->no_cull = ctx->culled = false;
-    ctx->retries = 0;
+    own_rows(ctx, 0, n, 0, 0);
+    ctx->res.drop(PCT_NEW_CLOUD);
+    ctx->pts4_valid = ctx->qpts4_valid = false;
+    ctx->has_f64 = ctx->culled = false;
     ctx->tm = pct_timings{};
     return PCT_OK;
 }
@@ -341,14 +344,7 @@ int pct_set_query_range(pct_ctx* ctx, int64_t begin, int64_t end) {
     PCT_TRY(begin_call(ctx));
     if (ctx->n <= 0) return pct_fail(ctx, PCT_ERR_INVALID, "no cloud loaded");
     if (begin < 0 || end > ctx->n || begin > end) return pct_fail(ctx, PCT_ERR_INVALID, "bad query range [%lld,%lld)", (long long)begin, (long long)end);
-    ctx->q_begin = begin;
-    ctx->q_end = end;
-    ctx->slab_parts = ctx->slab_part = 0;
-    ctx->slab_split_valid = false;
-    ctx->knn_valid = ctx->fit_valid = ctx->area_valid = ctx->frame_valid = ctx->grid_valid = false;   // the cell order depends on the owned range
-    ctx->tri_valid = false;
-    ctx->no_cull = false;
-    ctx->retries = 0;
+    own_rows(ctx, begin, end, 0, 0);
     return PCT_OK;
 }
 
@@ -359,20 +355,15 @@ int pct_set_query_slab(pct_ctx* ctx, int32_t part, int32_t parts) {
         return pct_fail(ctx, PCT_ERR_INVALID, "bad slab %d of %d (at most %d parts)", part, parts, PCT_SLAB_PARTS_MAX);
     if (parts >= 1 && (ctx->has_f64 || ctx->n < 4096))
         return pct_fail(ctx, PCT_ERR_INVALID, "slab ownership serves float32 clouds of at least 4096 points (use index ranges)");
-    ctx->q_begin = 0;
-    ctx->q_end = ctx->n;                 // until the build has cut the cloud
-    ctx->slab_parts = parts >= 1 ? parts : 0;     // (one part: the whole cloud as one slab -- the same code path, for a world of one rank)
-    ctx->slab_part = parts >= 1 ? part : 0;
-    ctx->slab_split_valid = false;
-    ctx->knn_valid = ctx->fit_valid = ctx->area_valid = ctx->frame_valid = ctx->grid_valid = false;
-    ctx->tri_valid = false;
-    ctx->no_cull = false;
-    ctx->retries = 0;
+    // the whole cloud until the build has cut it (one part: the whole cloud as one slab -- the same code path, for a world of one rank)
+    own_rows(ctx, 0, ctx->n, parts >= 1 ? part : 0, parts >= 1 ? parts : 0);
     return PCT_OK;
 }
 
-// by-index getters have no meaning while the rows are those of a slab
-static int refuse_in_slab_mode(pct_ctx* ctx, const char* what) {
+// begin_call of the entry points a slab handle refuses (the header's list under "Ownership"): rows by index have no meaning
+// while the rows are those of a slab
+static int begin_row_call(pct_ctx* ctx, const char* what) {
+    PCT_TRY(begin_call(ctx));
     if (ctx->slab_parts >= 1)
         return pct_fail(ctx, PCT_ERR_INVALID, "%s: this handle owns a slab, not an index range (pct_slab_records / pct_scatter_records)", what);
     return PCT_OK;
@@ -380,7 +371,7 @@ static int refuse_in_slab_mode(pct_ctx* ctx, const char* what) {
 
 int pct_slab_counts(pct_ctx* ctx, int64_t* counts, int32_t parts) {
     PCT_TRY(begin_call(ctx));
-    if (ctx->slab_parts < 1 || !ctx->slab_split_valid || !ctx->fit_valid)
+    if (ctx->slab_parts < 1 || !ctx->slab_split_valid || !ctx->res.has(PCT_R_FIT))
         return pct_fail(ctx, PCT_ERR_INVALID, "pct_slab_counts: no slab pass on this handle (pct_set_query_slab, pct_curvature)");
     if (!counts || parts != ctx->slab_parts) return pct_fail(ctx, PCT_ERR_INVALID, "pct_slab_counts: %d parts asked, the cloud was cut into %d", parts, ctx->slab_parts);
     for (int p = 0; p < parts; ++p) counts[p] = ctx->slab_counts[p];
@@ -418,7 +409,7 @@ __global__ __launch_bounds__(256) void k_scatter_records(const float* __restrict
 
 int pct_slab_records(pct_ctx* ctx, float* dev_records, int64_t capacity_rows, int64_t* rows_out) {
     PCT_TRY(begin_call(ctx));
-    if (ctx->slab_parts < 1 || !ctx->slab_split_valid || !ctx->fit_valid || !ctx->knn_sorted_space || !ctx->fit_row_order)
+    if (ctx->slab_parts < 1 || !ctx->slab_split_valid || !ctx->res.has(PCT_R_FIT) || !ctx->knn_sorted_space || !ctx->fit_row_order)
         return pct_fail(ctx, PCT_ERR_INVALID, "pct_slab_records: no slab pass on this handle (pct_set_query_slab, pct_curvature)");
     const int64_t rows = ctx->q_end - ctx->q_begin;
     if (rows_out) *rows_out = rows;
@@ -466,6 +457,13 @@ int pct_set_stats(pct_ctx* ctx, int32_t enable) {
 // ---- the sweep of a call: which structure serves it (the rules: pct_auto_route.h), built and swept ---------------------
 struct SweepDone { bool rows_fitted = false; };     // the passes of a chained sweep fitted the rows they answered: no fit is left to launch
 
+// a sweep has left its table; hier: from the hierarchical list or the chain of cell lists
+static void table_left(pct_ctx* ctx, bool hier) {
+    ctx->knn_hier = hier;
+    ctx->res.leave(PCT_R_TABLE, ctx->knn_sorted_space);
+}
+static bool tree_table_resident(const pct_ctx* ctx) { return ctx->res.has(PCT_R_TABLE) && ctx->knn_hier; }
+
 // The chain of cell lists.  fuse_par: every pass fits its rows, into the pinned slots of this parity (null: no fits).
 static int sweep_levels(pct_ctx* ctx, int32_t k, double eps, const int* fuse_par, pct_call_clock& clock, SweepDone* done) {
     ctx->tm.algo = PCT_KNN_GRID_LEVELS;
@@ -474,8 +472,7 @@ static int sweep_levels(pct_ctx* ctx, int32_t k, double eps, const int* fuse_par
     PCT_HIP(ctx, clock.boundary(PCT_ST_FAST_END, ctx->stream));
     PCT_HIP(ctx, clock.boundary(PCT_ST_SWEEP_END, ctx->stream));
     ctx->tm.knn_launches = ctx->tm.levels;
-    ctx->knn_valid = true;
-    ctx->knn_hier = true;
+    table_left(ctx, true);
     done->rows_fitted = fuse_par != nullptr;
     return PCT_OK;
 }
@@ -493,8 +490,7 @@ static int sweep_tree(pct_ctx* ctx, int32_t k, double eps, bool want_dist, const
     PCT_TRY(pct_launch_knn_tree(ctx, k, eps, want_dist, &clock));
     PCT_HIP(ctx, clock.boundary(PCT_ST_SWEEP_END, ctx->stream));
     ctx->tm.knn_launches = 1;
-    ctx->knn_valid = true;
-    ctx->knn_hier = true;
+    table_left(ctx, true);
     return PCT_OK;
 }
 
@@ -510,8 +506,7 @@ static int sweep_brute(pct_ctx* ctx, int32_t k, double eps, pct_call_clock& cloc
     PCT_TRY(pct_launch_knn_brute(ctx, k, eps));
     PCT_HIP(ctx, clock.boundary(PCT_ST_SWEEP_END, ctx->stream));
     ctx->tm.knn_launches = 1;
-    ctx->knn_valid = true;
-    ctx->knn_hier = false;
+    table_left(ctx, false);
     return PCT_OK;
 }
 
@@ -556,8 +551,7 @@ static int run_knn(pct_ctx* ctx, int32_t k, double eps, int32_t asked, pct_call_
     const int32_t algo = rq.algo;
     RouteSwitches sw = {false, false};             // (they matter to PCT_KNN_AUTO only)
     if (rq.auto_req) sw = RouteSwitches{pct_getenv("PCT_NO_TREE") != nullptr, pct_getenv("PCT_NO_AUTO_LEVELS") != nullptr};
-    ctx->knn_valid = ctx->fit_valid = ctx->area_valid = ctx->frame_valid = false;     // a new planting drops the fit and the areas
-    ctx->tri_valid = false;            // ... and the fans and triangles
+    ctx->res.drop(PCT_PLANTING);       // the request is resolved: nothing refuses it from here on
     ctx->k = k;
     ctx->eps = eps;
     PCT_TRY(clock.open(ctx, rq.auto_req, algo == PCT_KNN_GRID || algo == PCT_KNN_GRID_EXACT, kind));
@@ -600,8 +594,7 @@ static int run_knn(pct_ctx* ctx, int32_t k, double eps, int32_t asked, pct_call_
     PCT_TRY(pct_launch_knn_grid(ctx, k, eps, algo == PCT_KNN_GRID_EXACT, 0, want_dist, &clock));
     PCT_HIP(ctx, clock.boundary(PCT_ST_SWEEP_END, ctx->stream));
     ctx->tm.knn_launches = 1;
-    ctx->knn_valid = true;
-    ctx->knn_hier = false;
+    table_left(ctx, false);
     return PCT_OK;
 }
 
@@ -656,21 +649,26 @@ int pct_knn(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
     return PCT_OK;
 }
 
+// The end of every fit: results for `rows` rows -- cloud-aligned (rows [q_begin, q_end), in the order their launcher stored
+// them) or the rows of the call in the call's order.  They replace the fit before them and whatever was made from it.
+static int fit_left(pct_ctx* ctx, int64_t rows, bool cloud_aligned) {
+    ctx->fit_rows = rows;
+    ctx->fit_cloud_aligned = cloud_aligned;
+    if (!cloud_aligned) ctx->fit_row_order = false;
+    ctx->res.leave(PCT_R_FIT, ctx->fit_row_order);
+    return PCT_OK;
+}
+
 int pct_fit(pct_ctx* ctx) {
-    PCT_TRY(begin_call(ctx));
-    PCT_TRY(refuse_in_slab_mode(ctx, "pct_fit"));
-    if (!ctx->knn_valid) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "plant the neighbour table first (pct_knn)");
+    PCT_TRY(begin_row_call(ctx, "pct_fit"));
+    if (!ctx->res.has(PCT_R_TABLE)) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "plant the neighbour table first (pct_knn)");
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_BEGIN], ctx->stream));
     PCT_TRY(pct_launch_fit_table(ctx, FitSlot{0, false, nullptr}, nullptr));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_END], ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->tm.fit_ms = ev_ms(ctx, PCT_EV_FIT_BEGIN, PCT_EV_FIT_END);
     ctx->tm.fit_svd_rows = ctx->pin->svd_rows[0];
-    ctx->fit_rows = ctx->q_end - ctx->q_begin;
-    ctx->fit_valid = true;
-    ctx->frame_valid = false;          // (frames hold what the fit before this one left)
-    ctx->fit_cloud_aligned = true;
-    return PCT_OK;
+    return fit_left(ctx, ctx->q_end - ctx->q_begin, true);
 }
 
 int pct_set_async(pct_ctx* ctx, int32_t enable) {
@@ -705,11 +703,7 @@ static int curvature_async(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
     ctx->pend.par = par;
     ctx->pend.sorted = ctx->knn_sorted_space;
     ctx->pend.on = true;
-    ctx->fit_rows = ctx->q_end - ctx->q_begin;
-    ctx->fit_valid = true;
-    ctx->frame_valid = false;          // (frames hold what the fit before this one left)
-    ctx->fit_cloud_aligned = true;
-    return PCT_OK;
+    return fit_left(ctx, ctx->q_end - ctx->q_begin, true);
 }
 
 int pct_curvature(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
@@ -728,17 +722,12 @@ int pct_curvature(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
     }
     ctx->tm.fit_svd_rows = ctx->pin->svd_rows[0];
     ctx->tm_done = ctx->tm;
-    ctx->fit_rows = ctx->q_end - ctx->q_begin;
-    ctx->fit_valid = true;
-    ctx->frame_valid = false;          // (frames hold what the fit before this one left)
-    ctx->fit_cloud_aligned = true;
-    return PCT_OK;
+    return fit_left(ctx, ctx->q_end - ctx->q_begin, true);
 }
 
 int pct_get_neighbors(pct_ctx* ctx, int64_t begin, int64_t end, int32_t* idx, float* dist, int32_t* count) {
-    PCT_TRY(begin_call(ctx));
-    PCT_TRY(refuse_in_slab_mode(ctx, "pct_get_neighbors"));
-    if (!ctx->knn_valid) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "no neighbour table");
+    PCT_TRY(begin_row_call(ctx, "pct_get_neighbors"));
+    if (!ctx->res.has(PCT_R_TABLE)) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "no neighbour table");
     if (begin < ctx->q_begin || end > ctx->q_end || begin > end)
         return pct_fail(ctx, PCT_ERR_INVALID, "rows [%lld,%lld) outside the owned range [%lld,%lld)", (long long)begin,
                         (long long)end, (long long)ctx->q_begin, (long long)ctx->q_end);
@@ -761,9 +750,8 @@ int pct_get_neighbors(pct_ctx* ctx, int64_t begin, int64_t end, int32_t* idx, fl
 }
 
 int pct_get_neighbor_rows(pct_ctx* ctx, const int64_t* rows, int64_t n_rows, int32_t* idx, float* dist, int32_t* count) {
-    PCT_TRY(begin_call(ctx));
-    PCT_TRY(refuse_in_slab_mode(ctx, "pct_get_neighbor_rows"));
-    if (!ctx->knn_valid) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "no neighbour table");
+    PCT_TRY(begin_row_call(ctx, "pct_get_neighbor_rows"));
+    if (!ctx->res.has(PCT_R_TABLE)) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "no neighbour table");
     if (!rows || n_rows <= 0) return pct_fail(ctx, PCT_ERR_INVALID, "bad row list");
     for (int64_t i = 0; i < n_rows; ++i)
         if (rows[i] < ctx->q_begin || rows[i] >= ctx->q_end)
@@ -824,8 +812,7 @@ static int stage_neighbour_rows(pct_ctx* ctx, const int32_t* idx, const int32_t*
 }
 
 int pct_fit_indices(pct_ctx* ctx, const int32_t* idx, const int32_t* count, const int64_t* query, int64_t rows, int32_t k) {
-    PCT_TRY(begin_call(ctx));
-    PCT_TRY(refuse_in_slab_mode(ctx, "pct_fit_indices"));
+    PCT_TRY(begin_row_call(ctx, "pct_fit_indices"));
     int32_t pitch = 0;
     PCT_TRY(stage_neighbour_rows(ctx, idx, count, query, rows, k, &pitch, true));
     PCT_TRY(pct_reserve_fit(ctx, rows));
@@ -837,12 +824,7 @@ int pct_fit_indices(pct_ctx* ctx, const int32_t* idx, const int32_t* count, cons
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->tm.fit_ms = ev_ms(ctx, PCT_EV_FIT_BEGIN, PCT_EV_FIT_END);
     ctx->tm.fit_svd_rows = ctx->pin->svd_rows[0];
-    ctx->fit_rows = rows;
-    ctx->fit_row_order = false;
-    ctx->fit_valid = true;
-    ctx->frame_valid = false;          // (frames hold what the fit before this one left)
-    ctx->fit_cloud_aligned = false;   // (a resident neighbour table is untouched and stays valid)
-    return PCT_OK;
+    return fit_left(ctx, rows, false);         // (a resident neighbour table is untouched and stays valid)
 }
 
 int pct_fit_indices_f64(pct_ctx* ctx, const int32_t* idx, const int32_t* count, const int64_t* query, int64_t rows, int32_t k,
@@ -866,17 +848,16 @@ int pct_fit_indices_f64(pct_ctx* ctx, const int32_t* idx, const int32_t* count, 
 
 // ---- queries of caller-supplied points: what pct_query_points, pct_query_points_algo and pct_query_ball share ----------------
 // What query_route and ball_route (pct_query_plan.h, pct_ball_plan.h) are told of the handle.  The only place that reads
-// these fields for routing: a residency flag missed here reroutes a call, and a wrong reroute is a rebuild that
-// invalidates a resident table.
+// these fields for routing: a wrong reroute is a rebuild that invalidates what is resident in the cell order -- which
+// results those are is kept where they are left (pct_residents::leave), not listed here.
 static QueryState query_state(const pct_ctx* ctx) {
     const pct_grid& g = ctx->grid;
     bool finite_limits = false;
     for (int a = 0; a < 3; ++a) finite_limits = finite_limits || isfinite(g.lim_lo[a]) || isfinite(g.lim_hi[a]);
     QueryState qs = {};
     qs.uniform_resident = ctx->grid_valid && ctx->grid_whole && !finite_limits;
-    qs.tree_resident = ctx->knn_valid && ctx->knn_hier;
-    qs.sorted_resident = (ctx->knn_valid && ctx->knn_sorted_space) || (ctx->fit_valid && ctx->fit_row_order) ||
-                         (ctx->area_valid && ctx->area_row_order) || (ctx->frame_valid && ctx->frame_row_order);
+    qs.tree_resident = tree_table_resident(ctx);
+    qs.sorted_resident = ctx->res.any_in_cell_order();
     qs.sharded = ctx->q_begin != 0 || ctx->q_end != ctx->n;      // (a culled list in place: finite limits, not uniform_resident)
     qs.slab = ctx->slab_parts >= 1;
     return qs;
@@ -917,8 +898,7 @@ static int build_query_grid(pct_ctx* ctx, int32_t kb, const char* who) {
 // never a list built, and query_stats stay those of the last pct_query_points_algo call.
 static int query_points(pct_ctx* ctx, const char* who, const double* q_xyz, int64_t m, int32_t k, double eps, const int32_t* algo,
                         int32_t* idx, double* dist) {
-    PCT_TRY(begin_call(ctx));
-    PCT_TRY(refuse_in_slab_mode(ctx, who));
+    PCT_TRY(begin_row_call(ctx, who));
     PCT_TRY(check_query_arrays(ctx, q_xyz, m, m == 0 || (idx && dist)));
     if (k < 1 || k > 128) return pct_fail(ctx, PCT_ERR_INVALID, "k=%d outside [1,128]", k);
     QueryRoute route = QueryRoute::Sweep;
@@ -969,8 +949,7 @@ int pct_query_stats(pct_ctx* ctx, int64_t out[4]) {
 // Radius search (pct_ball.hip).  The route is ball_route's (pct_ball_plan.h), from the same state query_points reads.
 int pct_query_ball(pct_ctx* ctx, const double* q_xyz, int64_t m, const double* r, int64_t n_r, int32_t flags, int32_t algo,
                    int64_t max_entries, int64_t* offsets) {
-    PCT_TRY(begin_call(ctx));
-    PCT_TRY(refuse_in_slab_mode(ctx, "pct_query_ball"));
+    PCT_TRY(begin_row_call(ctx, "pct_query_ball"));
     PCT_TRY(check_query_arrays(ctx, q_xyz, m, offsets && (m == 0 || r)));
     if (m > 0 && n_r != 1 && n_r != m) return pct_fail(ctx, PCT_ERR_INVALID, "%lld radii for %lld queries (one, or one per query)", (long long)n_r, (long long)m);
     if (flags & ~(PCT_BALL_SORTED | PCT_BALL_DISTANCES | PCT_BALL_COUNT_ONLY)) return pct_fail(ctx, PCT_ERR_INVALID, "unknown flags %d", flags);
@@ -978,34 +957,28 @@ int pct_query_ball(pct_ctx* ctx, const double* q_xyz, int64_t m, const double* r
     if (!ball_route(algo, ctx->n, m, query_state(ctx), &route)) return pct_fail(ctx, PCT_ERR_INVALID, "unknown query algorithm %d", algo);
     PCT_TRY(check_queries_finite(ctx, q_xyz, m));
     if (m > 0 && route == QueryRoute::GridBuild) PCT_TRY(build_query_grid(ctx, 30, "pct_query_ball"));      // (rows of 30: the cloud's usual sweep)
-    ctx->ball_valid = false;                   // the request is accepted and its cell list stands: whatever was resident is the previous call's
+    ctx->res.drop(pct_replacing(PCT_R_BALL));  // the request is accepted and its cell list stands: whatever was resident is the previous call's
     for (int i = 0; i < 4; ++i) ctx->ball_stats[i] = 0;
     offsets[0] = 0;
-    if (m == 0) {
-        ctx->ball_valid = !(flags & PCT_BALL_COUNT_ONLY);
-        ctx->ball_has_dist = (flags & PCT_BALL_DISTANCES) != 0;
-        ctx->ball_m = 0;
-        return PCT_OK;
+    if (m > 0) {
+        PCT_TRY(pct_reserve(ctx, &ctx->stage_a, (size_t)m * 3 * sizeof(double)));
+        PCT_TRY(pct_reserve(ctx, &ctx->stage_b, (size_t)n_r * sizeof(double)));
+        PCT_HIP(ctx, hipMemcpyAsync(ctx->stage_a.p, q_xyz, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        PCT_HIP(ctx, hipMemcpyAsync(ctx->stage_b.p, r, (size_t)n_r * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        ctx->ball_stats[0] = (int64_t)route;
+        PCT_TRY(pct_launch_ball(ctx, route != QueryRoute::Sweep, (const double*)ctx->stage_a.p, m, (const double*)ctx->stage_b.p,
+                                n_r == m && m > 1 ? 1 : 0, flags, max_entries, offsets, ctx->ball_stats + 1));
     }
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_a, (size_t)m * 3 * sizeof(double)));
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_b, (size_t)n_r * sizeof(double)));
-    PCT_HIP(ctx, hipMemcpyAsync(ctx->stage_a.p, q_xyz, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(ctx->stage_b.p, r, (size_t)n_r * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    ctx->ball_stats[0] = (int64_t)route;
-    const int st = pct_launch_ball(ctx, route != QueryRoute::Sweep, (const double*)ctx->stage_a.p, m, (const double*)ctx->stage_b.p,
-                                   n_r == m && m > 1 ? 1 : 0, flags, max_entries, offsets, ctx->ball_stats + 1);
-    if (st != PCT_OK) return st;
-    if (!(flags & PCT_BALL_COUNT_ONLY)) {
-        ctx->ball_valid = true;
-        ctx->ball_has_dist = (flags & PCT_BALL_DISTANCES) != 0;
-        ctx->ball_m = m;
-    }
+    if (flags & PCT_BALL_COUNT_ONLY) return PCT_OK;        // (nothing is kept)
+    ctx->ball_has_dist = (flags & PCT_BALL_DISTANCES) != 0;
+    ctx->ball_m = m;
+    ctx->res.leave(PCT_R_BALL, false);
     return PCT_OK;
 }
 
 int pct_get_ball(pct_ctx* ctx, int64_t row_begin, int64_t row_end, int32_t* idx, double* dist) {
     PCT_TRY(begin_call(ctx));
-    if (!ctx->ball_valid) return pct_fail(ctx, PCT_ERR_INVALID, "no ball rows on this handle (pct_query_ball)");
+    if (!ctx->res.has(PCT_R_BALL)) return pct_fail(ctx, PCT_ERR_INVALID, "no ball rows on this handle (pct_query_ball)");
     if (row_begin < 0 || row_end > ctx->ball_m || row_begin > row_end)
         return pct_fail(ctx, PCT_ERR_INVALID, "bad row range [%lld,%lld) of %lld", (long long)row_begin, (long long)row_end, (long long)ctx->ball_m);
     if (dist && !ctx->ball_has_dist) return pct_fail(ctx, PCT_ERR_INVALID, "pct_get_ball: no distances were asked for (PCT_BALL_DISTANCES)");
@@ -1027,9 +1000,8 @@ int pct_get_ball(pct_ctx* ctx, int64_t row_begin, int64_t row_end, int32_t* idx,
 // Fit of the resident ball rows about their centres (pct_fit_ball.hip).  Like pct_fit_indices it replaces the results of an
 // earlier fit and nothing else: the rows, a resident neighbour table, PCA results and the cell list stay as they are.
 int pct_fit_ball(pct_ctx* ctx, const int64_t* self_rows, int64_t m, int32_t* used) {
-    PCT_TRY(begin_call(ctx));
-    PCT_TRY(refuse_in_slab_mode(ctx, "pct_fit_ball"));
-    if (!ctx->ball_valid) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "pct_fit_ball: no ball rows on this handle (pct_query_ball)");
+    PCT_TRY(begin_row_call(ctx, "pct_fit_ball"));
+    if (!ctx->res.has(PCT_R_BALL)) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "pct_fit_ball: no ball rows on this handle (pct_query_ball)");
     if (m != ctx->ball_m) return pct_fail(ctx, PCT_ERR_INVALID, "pct_fit_ball: %lld centres for the %lld rows of the last query", (long long)m, (long long)ctx->ball_m);
     if (m > 0 && !self_rows) return pct_fail(ctx, PCT_ERR_INVALID, "pct_fit_ball: null centres");
     for (int64_t i = 0; i < m; ++i)
@@ -1037,16 +1009,11 @@ int pct_fit_ball(pct_ctx* ctx, const int64_t* self_rows, int64_t m, int32_t* use
             return pct_fail(ctx, PCT_ERR_INVALID, "pct_fit_ball: row %lld: centre %lld outside the cloud", (long long)i, (long long)self_rows[i]);
     ctx->tm.fit_ms = 0;
     ctx->tm.fit_svd_rows = 0;
-    ctx->fit_rows = m;
-    ctx->fit_row_order = false;
-    ctx->fit_valid = true;
-    ctx->frame_valid = false;          // (frames hold what the fit before this one left)
-    ctx->fit_cloud_aligned = false;
-    if (m == 0) return PCT_OK;
+    if (m == 0) return fit_left(ctx, 0, false);
+    ctx->res.drop(pct_replacing(PCT_R_FIT));   // accepted: the fit before this one is gone, the new one is there once the kernels have run
     PCT_TRY(pct_reserve_fit(ctx, m));
     PCT_TRY(pct_reserve(ctx, &ctx->stage_c, (size_t)m * sizeof(int)));
     PCT_TRY(pct_reserve(ctx, &ctx->stage_d, (size_t)m * sizeof(int)));
-    ctx->fit_valid = false;                    // until the kernels have run
     {
         int* self32 = (int*)malloc((size_t)m * sizeof(int));
         if (!self32) return pct_fail(ctx, PCT_ERR_OOM, "pct_fit_ball: %lld centres", (long long)m);
@@ -1062,9 +1029,7 @@ int pct_fit_ball(pct_ctx* ctx, const int64_t* self_rows, int64_t m, int32_t* use
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->tm.fit_ms = ev_ms(ctx, PCT_EV_FIT_BEGIN, PCT_EV_FIT_END);
     ctx->tm.fit_svd_rows = ctx->pin->svd_rows[0];
-    ctx->fit_valid = true;
-    ctx->frame_valid = false;          // (frames hold what the fit before this one left)
-    return PCT_OK;
+    return fit_left(ctx, m, false);
 }
 
 int pct_ball_stats(pct_ctx* ctx, int64_t out[4]) {
@@ -1074,9 +1039,8 @@ int pct_ball_stats(pct_ctx* ctx, int64_t out[4]) {
 }
 
 int pct_get_fit(pct_ctx* ctx, int64_t begin, int64_t end, float* coefs, float* K, float* H, float* H2) {
-    PCT_TRY(begin_call(ctx));
-    PCT_TRY(refuse_in_slab_mode(ctx, "pct_get_fit"));
-    if (!ctx->fit_valid) return pct_fail(ctx, PCT_ERR_INVALID, "no fit results");
+    PCT_TRY(begin_row_call(ctx, "pct_get_fit"));
+    if (!ctx->res.has(PCT_R_FIT)) return pct_fail(ctx, PCT_ERR_INVALID, "no fit results");
     const int64_t base = ctx->fit_cloud_aligned ? ctx->q_begin : 0;   // cloud-aligned vs row-aligned results
     if (begin < base || end > base + ctx->fit_rows || begin > end)
         return pct_fail(ctx, PCT_ERR_INVALID, "rows [%lld,%lld) outside the fitted range", (long long)begin, (long long)end);
@@ -1111,10 +1075,9 @@ int pct_get_fit(pct_ctx* ctx, int64_t begin, int64_t end, float* coefs, float* K
 
 // ---- per-point tangent-plane Voronoi areas and the energies over them (pct_area.hip) --------------------------------------
 int pct_point_areas(pct_ctx* ctx) {
-    PCT_TRY(begin_call(ctx));
-    PCT_TRY(refuse_in_slab_mode(ctx, "pct_point_areas"));
-    if (!ctx->knn_valid) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "plant the neighbour table first (pct_knn)");
-    ctx->area_valid = false;
+    PCT_TRY(begin_row_call(ctx, "pct_point_areas"));
+    if (!ctx->res.has(PCT_R_TABLE)) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "plant the neighbour table first (pct_knn)");
+    ctx->res.drop(pct_replacing(PCT_R_AREAS));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_AREA_BEGIN], ctx->stream));
     PCT_TRY(pct_launch_point_areas(ctx));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_AREA_END], ctx->stream));
@@ -1127,18 +1090,15 @@ int pct_point_areas(pct_ctx* ctx) {
     ctx->area_stats[3] = (int64_t)w[0];
     ctx->area_profile[0] = ev_ms(ctx, PCT_EV_AREA_BEGIN, PCT_EV_AREA_END);
     ctx->area_profile[1] = (double)w[3];
-    ctx->area_valid = true;
+    ctx->res.leave(PCT_R_AREAS, ctx->area_row_order);
     return PCT_OK;
 }
 
-// areas in table-row order are gathered through row_of, which outlives the table (pct_voxel_downsample clears knn_valid
-// alone) exactly as the fit's: whatever rewrites the cell order clears area_valid, and query_state keeps a query's build away
-static bool areas_resident(const pct_ctx* ctx) { return ctx->area_valid; }
-
+// areas in table-row order are gathered through row_of, which outlives the table (PCT_TABLE_LOST) exactly as the fit's:
+// whatever rewrites the cell order drops the areas, and query_state keeps a query's build away
 int pct_get_point_areas(pct_ctx* ctx, int64_t begin, int64_t end, double* area, uint8_t* closed, int32_t* nverts) {
-    PCT_TRY(begin_call(ctx));
-    PCT_TRY(refuse_in_slab_mode(ctx, "pct_get_point_areas"));
-    if (!areas_resident(ctx)) return pct_fail(ctx, PCT_ERR_INVALID, "no point areas (pct_point_areas)");
+    PCT_TRY(begin_row_call(ctx, "pct_get_point_areas"));
+    if (!ctx->res.has(PCT_R_AREAS)) return pct_fail(ctx, PCT_ERR_INVALID, "no point areas (pct_point_areas)");
     if (begin < ctx->q_begin || end > ctx->q_begin + ctx->area_rows || begin > end)
         return pct_fail(ctx, PCT_ERR_INVALID, "rows [%lld,%lld) outside the owned range", (long long)begin, (long long)end);
     const int64_t rows = end - begin, off = begin - ctx->q_begin;
@@ -1165,23 +1125,22 @@ int pct_get_point_areas(pct_ctx* ctx, int64_t begin, int64_t end, double* area, 
 
 int pct_point_area_stats(pct_ctx* ctx, int64_t out[4]) {
     if (!ctx || !out) return PCT_ERR_INVALID;
-    for (int i = 0; i < 4; ++i) out[i] = ctx->area_valid ? ctx->area_stats[i] : 0;
+    for (int i = 0; i < 4; ++i) out[i] = ctx->res.has(PCT_R_AREAS) ? ctx->area_stats[i] : 0;
     return PCT_OK;
 }
 
 int pct_point_area_profile(pct_ctx* ctx, double out[2]) {
     if (!ctx || !out) return PCT_ERR_INVALID;
-    for (int i = 0; i < 2; ++i) out[i] = ctx->area_valid ? ctx->area_profile[i] : 0.0;
+    for (int i = 0; i < 2; ++i) out[i] = ctx->res.has(PCT_R_AREAS) ? ctx->area_profile[i] : 0.0;
     return PCT_OK;
 }
 
 int pct_point_energies(pct_ctx* ctx, int32_t closed_only, double out[4]) {
-    PCT_TRY(begin_call(ctx));
-    PCT_TRY(refuse_in_slab_mode(ctx, "pct_point_energies"));
+    PCT_TRY(begin_row_call(ctx, "pct_point_energies"));
     if (!out) return pct_fail(ctx, PCT_ERR_INVALID, "null result");
     const int64_t rows = ctx->q_end - ctx->q_begin;
-    if (!ctx->fit_valid || !ctx->fit_cloud_aligned || ctx->fit_rows != rows) return pct_fail(ctx, PCT_ERR_INVALID, "no fit results");
-    if (!areas_resident(ctx) || ctx->area_rows != rows) return pct_fail(ctx, PCT_ERR_INVALID, "no point areas (pct_point_areas)");
+    if (!ctx->res.has(PCT_R_FIT) || !ctx->fit_cloud_aligned || ctx->fit_rows != rows) return pct_fail(ctx, PCT_ERR_INVALID, "no fit results");
+    if (!ctx->res.has(PCT_R_AREAS) || ctx->area_rows != rows) return pct_fail(ctx, PCT_ERR_INVALID, "no point areas (pct_point_areas)");
     const int nblk = 1024;
     PCT_TRY(pct_reserve(ctx, &ctx->stage_d, ((size_t)nblk * 4 + 4) * sizeof(double)));
     double* d_part = (double*)ctx->stage_d.p;
@@ -1193,14 +1152,13 @@ int pct_point_energies(pct_ctx* ctx, int32_t closed_only, double out[4]) {
 
 // ---- per-point surface frames from the resident fit (pct_frame.hip) ----------------------------------------------------
 int pct_point_frames(pct_ctx* ctx, const double* viewpoint) {
-    PCT_TRY(begin_call(ctx));
-    PCT_TRY(refuse_in_slab_mode(ctx, "pct_point_frames"));
-    if (!ctx->knn_valid) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "plant the neighbour table first (pct_knn)");
+    PCT_TRY(begin_row_call(ctx, "pct_point_frames"));
+    if (!ctx->res.has(PCT_R_TABLE)) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "plant the neighbour table first (pct_knn)");
     const int64_t rows = ctx->q_end - ctx->q_begin;
-    if (!ctx->fit_valid || !ctx->fit_cloud_aligned || ctx->fit_rows != rows) return pct_fail(ctx, PCT_ERR_INVALID, "no fit results");
+    if (!ctx->res.has(PCT_R_FIT) || !ctx->fit_cloud_aligned || ctx->fit_rows != rows) return pct_fail(ctx, PCT_ERR_INVALID, "no fit results");
     if (viewpoint && !(isfinite(viewpoint[0]) && isfinite(viewpoint[1]) && isfinite(viewpoint[2])))
         return pct_fail(ctx, PCT_ERR_INVALID, "pct_point_frames: the viewpoint is not finite");
-    ctx->frame_valid = ctx->orient_valid = false;
+    ctx->res.drop(pct_replacing(PCT_R_FRAMES));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FRAME_BEGIN], ctx->stream));
     PCT_TRY(pct_launch_point_frames(ctx, viewpoint));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FRAME_END], ctx->stream));
@@ -1210,17 +1168,14 @@ int pct_point_frames(pct_ctx* ctx, const double* viewpoint) {
     ctx->frame_stats[0] = rows;
     for (int i = 0; i < 3; ++i) ctx->frame_stats[1 + i] = (int64_t)w[i];
     ctx->frame_ms = ev_ms(ctx, PCT_EV_FRAME_BEGIN, PCT_EV_FRAME_END);
-    ctx->frame_valid = true;
+    ctx->res.leave(PCT_R_FRAMES, ctx->frame_row_order);
     return PCT_OK;
 }
 
-// frames in table-row order: as areas_resident
-static bool frames_resident(const pct_ctx* ctx) { return ctx->frame_valid; }
-
+// frames in table-row order: as the areas
 int pct_get_point_frames(pct_ctx* ctx, int64_t begin, int64_t end, double* normal, double* k12, double* dirs, uint8_t* flipped) {
-    PCT_TRY(begin_call(ctx));
-    PCT_TRY(refuse_in_slab_mode(ctx, "pct_get_point_frames"));
-    if (!frames_resident(ctx)) return pct_fail(ctx, PCT_ERR_INVALID, "no point frames (pct_point_frames)");
+    PCT_TRY(begin_row_call(ctx, "pct_get_point_frames"));
+    if (!ctx->res.has(PCT_R_FRAMES)) return pct_fail(ctx, PCT_ERR_INVALID, "no point frames (pct_point_frames)");
     if (begin < ctx->q_begin || end > ctx->q_begin + ctx->frame_rows || begin > end)
         return pct_fail(ctx, PCT_ERR_INVALID, "rows [%lld,%lld) outside the owned range", (long long)begin, (long long)end);
     const int64_t rows = end - begin, off = begin - ctx->q_begin, all = ctx->frame_rows;
@@ -1251,19 +1206,16 @@ int pct_get_point_frames(pct_ctx* ctx, int64_t begin, int64_t end, double* norma
 
 int pct_point_frame_stats(pct_ctx* ctx, int64_t out[4], double* ms) {
     if (!ctx || !out) return PCT_ERR_INVALID;
-    for (int i = 0; i < 4; ++i) out[i] = ctx->frame_valid ? ctx->frame_stats[i] : 0;
-    if (ms) *ms = ctx->frame_valid ? ctx->frame_ms : 0.0;
+    for (int i = 0; i < 4; ++i) out[i] = ctx->res.has(PCT_R_FRAMES) ? ctx->frame_stats[i] : 0;
+    if (ms) *ms = ctx->res.has(PCT_R_FRAMES) ? ctx->frame_ms : 0.0;
     return PCT_OK;
 }
 
 // ---- consistent orientation of the resident frames (pct_orient.hip) ------------------------------------------------------
-// the orientation belongs to the frames it turned: whatever drops them (a new cloud, owned range, planting or fit) drops it
-static bool orientation_resident(const pct_ctx* ctx) { return ctx->orient_valid && frames_resident(ctx); }
-
+// the orientation belongs to the frames it turned: whatever drops or replaces them drops it (pct_residents.h)
 int pct_orient_frames(pct_ctx* ctx, int32_t anchor, const double* viewpoint, int32_t max_components) {
-    PCT_TRY(begin_call(ctx));
-    PCT_TRY(refuse_in_slab_mode(ctx, "pct_orient_frames"));
-    if (!frames_resident(ctx) || !ctx->knn_valid) return pct_fail(ctx, PCT_ERR_INVALID, "no point frames (pct_point_frames)");
+    PCT_TRY(begin_row_call(ctx, "pct_orient_frames"));
+    if (!ctx->res.has(PCT_R_FRAMES) || !ctx->res.has(PCT_R_TABLE)) return pct_fail(ctx, PCT_ERR_INVALID, "no point frames (pct_point_frames)");
     const int64_t rows = ctx->q_end - ctx->q_begin;
     if (ctx->q_begin != 0 || ctx->q_end != ctx->n || ctx->culled || ctx->frame_rows != rows)
         return pct_fail(ctx, PCT_ERR_INVALID, "pct_orient_frames: the handle owns rows [%lld,%lld) of %lld: the flood needs the whole cloud",
@@ -1273,7 +1225,7 @@ int pct_orient_frames(pct_ctx* ctx, int32_t anchor, const double* viewpoint, int
     if (anchor == PCT_ORIENT_VIEW && !(viewpoint && isfinite(viewpoint[0]) && isfinite(viewpoint[1]) && isfinite(viewpoint[2])))
         return pct_fail(ctx, PCT_ERR_INVALID, "pct_orient_frames: PCT_ORIENT_VIEW needs a finite viewpoint");
     const int max_comp = max_components <= 0 ? 65536 : max_components;
-    ctx->orient_valid = false;         // (behind every refusal: a refused call leaves the orientation of an earlier one)
+    ctx->res.drop(pct_replacing(PCT_R_ORIENT));        // (behind every refusal: a refused call leaves the orientation of an earlier one)
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_ORIENT_BEGIN], ctx->stream));
     const int status = pct_run_orient(ctx, anchor, anchor == PCT_ORIENT_VIEW ? viewpoint : nullptr, max_comp, ctx->orient_stats);
     if (status != PCT_OK) {
@@ -1292,14 +1244,13 @@ int pct_orient_frames(pct_ctx* ctx, int32_t anchor, const double* viewpoint, int
     ctx->orient_stats[5] = w[OW_PULLS];
     ctx->orient_ms = ev_ms(ctx, PCT_EV_ORIENT_BEGIN, PCT_EV_ORIENT_END);
     ctx->orient_rows = rows;
-    ctx->orient_valid = true;
+    ctx->res.leave(PCT_R_ORIENT, false);
     return PCT_OK;
 }
 
 int pct_get_orientation(pct_ctx* ctx, int64_t begin, int64_t end, int32_t* component, int32_t* parent, int32_t* level, uint8_t* toggled) {
-    PCT_TRY(begin_call(ctx));
-    PCT_TRY(refuse_in_slab_mode(ctx, "pct_get_orientation"));
-    if (!orientation_resident(ctx)) return pct_fail(ctx, PCT_ERR_INVALID, "no orientation (pct_orient_frames)");
+    PCT_TRY(begin_row_call(ctx, "pct_get_orientation"));
+    if (!ctx->res.has(PCT_R_ORIENT)) return pct_fail(ctx, PCT_ERR_INVALID, "no orientation (pct_orient_frames)");
     if (begin < 0 || end > ctx->orient_rows || begin > end)
         return pct_fail(ctx, PCT_ERR_INVALID, "rows [%lld,%lld) outside the cloud", (long long)begin, (long long)end);
     const size_t rows = (size_t)(end - begin);
@@ -1314,7 +1265,7 @@ int pct_get_orientation(pct_ctx* ctx, int64_t begin, int64_t end, int32_t* compo
 
 int pct_orient_stats(pct_ctx* ctx, int64_t out[8], double* ms) {
     if (!ctx || !out) return PCT_ERR_INVALID;
-    const bool live = orientation_resident(ctx);
+    const bool live = ctx->res.has(PCT_R_ORIENT);
     for (int i = 0; i < 8; ++i) out[i] = live ? ctx->orient_stats[i] : 0;
     if (ms) *ms = live ? ctx->orient_ms : 0.0;
     return PCT_OK;
@@ -1322,16 +1273,15 @@ int pct_orient_stats(pct_ctx* ctx, int64_t out[8], double* ms) {
 
 // ---- faces from the tangent-plane Voronoi cells (pct_fan.hip, include/pct_hip_surface.h) -----------------------------------
 int pct_point_triangles(pct_ctx* ctx, int32_t flags) {
-    PCT_TRY(begin_call(ctx));
-    PCT_TRY(refuse_in_slab_mode(ctx, "pct_point_triangles"));
-    if (!ctx->knn_valid) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "plant the neighbour table first (pct_knn)");
+    PCT_TRY(begin_row_call(ctx, "pct_point_triangles"));
+    if (!ctx->res.has(PCT_R_TABLE)) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "plant the neighbour table first (pct_knn)");
     if (ctx->q_begin != 0 || ctx->q_end != ctx->n || ctx->culled)
         return pct_fail(ctx, PCT_ERR_INVALID, "pct_point_triangles: the handle owns rows [%lld,%lld) of %lld: agreement needs the whole cloud",
                         (long long)ctx->q_begin, (long long)ctx->q_end, (long long)ctx->n);
     if (flags & ~PCT_TRI_WIND_FRAMES) return pct_fail(ctx, PCT_ERR_INVALID, "pct_point_triangles: unknown flags %d", flags);
     const bool wind = (flags & PCT_TRI_WIND_FRAMES) != 0;
-    if (wind && !(ctx->frame_valid && ctx->frame_rows == ctx->n)) return pct_fail(ctx, PCT_ERR_INVALID, "no point frames (pct_point_frames)");
-    ctx->tri_valid = false;            // (behind every refusal: a refused call leaves the triangles of an earlier one)
+    if (wind && !(ctx->res.has(PCT_R_FRAMES) && ctx->frame_rows == ctx->n)) return pct_fail(ctx, PCT_ERR_INVALID, "no point frames (pct_point_frames)");
+    ctx->res.drop(pct_replacing(PCT_R_TRIANGLES));     // (behind every refusal: a refused call leaves the triangles of an earlier one)
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_TRI_BEGIN], ctx->stream));
     const int status = pct_launch_point_triangles(ctx, wind, ctx->ev[PCT_EV_TRI_MID]);
     if (status != PCT_OK) {
@@ -1348,13 +1298,13 @@ int pct_point_triangles(pct_ctx* ctx, int32_t flags) {
     ctx->tri_ms[0] = ev_ms(ctx, PCT_EV_TRI_BEGIN, PCT_EV_TRI_END);
     ctx->tri_ms[1] = ev_ms(ctx, PCT_EV_TRI_BEGIN, PCT_EV_TRI_MID);
     ctx->tri_ms[2] = ev_ms(ctx, PCT_EV_TRI_MID, PCT_EV_TRI_END);
-    ctx->tri_valid = true;
+    ctx->res.leave(PCT_R_TRIANGLES, false);            // (kept by public index)
     return PCT_OK;
 }
 
 int pct_get_point_fans(pct_ctx* ctx, int64_t begin, int64_t end, int64_t* offsets, int32_t* nbr) {
     PCT_TRY(begin_call(ctx));
-    if (!ctx->tri_valid) return pct_fail(ctx, PCT_ERR_INVALID, "no triangles (pct_point_triangles)");
+    if (!ctx->res.has(PCT_R_TRIANGLES)) return pct_fail(ctx, PCT_ERR_INVALID, "no triangles (pct_point_triangles)");
     if (begin < 0 || end > ctx->tri_rows || begin > end || !offsets)
         return pct_fail(ctx, PCT_ERR_INVALID, "rows [%lld,%lld) outside the cloud", (long long)begin, (long long)end);
     const int64_t rows = end - begin;
@@ -1375,7 +1325,7 @@ int pct_get_point_fans(pct_ctx* ctx, int64_t begin, int64_t end, int64_t* offset
 
 int pct_get_triangles(pct_ctx* ctx, int64_t first, int64_t count, int32_t* tri) {
     PCT_TRY(begin_call(ctx));
-    if (!ctx->tri_valid) return pct_fail(ctx, PCT_ERR_INVALID, "no triangles (pct_point_triangles)");
+    if (!ctx->res.has(PCT_R_TRIANGLES)) return pct_fail(ctx, PCT_ERR_INVALID, "no triangles (pct_point_triangles)");
     if (first < 0 || count < 0 || first + count > ctx->tri_total || (count > 0 && !tri))
         return pct_fail(ctx, PCT_ERR_INVALID, "triangles [%lld,%lld) outside the %lld resident", (long long)first, (long long)(first + count),
                         (long long)ctx->tri_total);
@@ -1387,14 +1337,14 @@ int pct_get_triangles(pct_ctx* ctx, int64_t first, int64_t count, int32_t* tri) 
 
 int pct_point_triangle_stats(pct_ctx* ctx, int64_t out[8], double* ms) {
     if (!ctx || !out) return PCT_ERR_INVALID;
-    for (int i = 0; i < 8; ++i) out[i] = ctx->tri_valid ? ctx->tri_stats[i] : 0;
-    if (ms) *ms = ctx->tri_valid ? ctx->tri_ms[0] : 0.0;
+    for (int i = 0; i < 8; ++i) out[i] = ctx->res.has(PCT_R_TRIANGLES) ? ctx->tri_stats[i] : 0;
+    if (ms) *ms = ctx->res.has(PCT_R_TRIANGLES) ? ctx->tri_ms[0] : 0.0;
     return PCT_OK;
 }
 
 int pct_point_triangle_profile(pct_ctx* ctx, double out[2]) {
     if (!ctx || !out) return PCT_ERR_INVALID;
-    for (int i = 0; i < 2; ++i) out[i] = ctx->tri_valid ? ctx->tri_ms[1 + i] : 0.0;
+    for (int i = 0; i < 2; ++i) out[i] = ctx->res.has(PCT_R_TRIANGLES) ? ctx->tri_ms[1 + i] : 0.0;
     return PCT_OK;
 }
 
@@ -1445,9 +1395,8 @@ int pct_fit_quadric(pct_ctx* ctx, const float* pts, int64_t batch, int32_t m, fl
 
 int pct_neighbor_study_curvatures(pct_ctx* ctx, const int64_t* sample_rows, int64_t n_samples, int32_t n_lo, int32_t n_hi,
                                    float* K_out) {
-    PCT_TRY(begin_call(ctx));
-    PCT_TRY(refuse_in_slab_mode(ctx, "pct_neighbor_study_curvatures"));
-    if (!ctx->knn_valid) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "plant the neighbour table first (pct_knn)");
+    PCT_TRY(begin_row_call(ctx, "pct_neighbor_study_curvatures"));
+    if (!ctx->res.has(PCT_R_TABLE)) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "plant the neighbour table first (pct_knn)");
     if (!sample_rows || !K_out || n_samples <= 0 || n_lo < 1 || n_hi < n_lo) return pct_fail(ctx, PCT_ERR_INVALID, "bad study arguments");
     if (n_hi > ctx->k) return pct_fail(ctx, PCT_ERR_INVALID, "the study needs %d neighbours per point, the table holds %d", n_hi, ctx->k);
     if (ctx->eps > 0) return pct_fail(ctx, PCT_ERR_INVALID, "the study needs a plain k-NN table (no eps bound)");
@@ -1552,8 +1501,7 @@ int pct_voxel_downsample_f32(pct_ctx* ctx, const float* xyz, int64_t n, double v
 }
 
 int pct_surface_variation(pct_ctx* ctx, int32_t k_total, float* out) {
-    PCT_TRY(begin_call(ctx));
-    PCT_TRY(refuse_in_slab_mode(ctx, "pct_surface_variation"));
+    PCT_TRY(begin_row_call(ctx, "pct_surface_variation"));
     if (!out || k_total < 2) return pct_fail(ctx, PCT_ERR_INVALID, "bad surface-variation arguments");
     const int64_t rows = ctx->q_end - ctx->q_begin;
     for (int attempt = 0; attempt < 2; ++attempt) {
@@ -1566,13 +1514,11 @@ int pct_surface_variation(pct_ctx* ctx, int32_t k_total, float* out) {
         if (!again) break;
         retry_without_cull(ctx);
     }
-    ctx->fit_valid = false;
-    return PCT_OK;
+    return PCT_OK;                     // (no fit: the planting dropped it, ctx->K holds the variation)
 }
 
 int pct_pca_curvatures(pct_ctx* ctx, int32_t k, int32_t algo, int32_t keep_neighbors, int64_t* exact_rows) {
-    PCT_TRY(begin_call(ctx));
-    PCT_TRY(refuse_in_slab_mode(ctx, "pct_pca_curvatures"));
+    PCT_TRY(begin_row_call(ctx, "pct_pca_curvatures"));
     if (ctx->n <= 0) return pct_fail(ctx, PCT_ERR_INVALID, "no cloud loaded");
     if (ctx->q_begin != 0 || ctx->q_end != ctx->n)
         return pct_fail(ctx, PCT_ERR_INVALID, "pct_pca_curvatures answers whole clouds (query range [%lld,%lld) of %lld points)",
@@ -1583,7 +1529,7 @@ int pct_pca_curvatures(pct_ctx* ctx, int32_t k, int32_t algo, int32_t keep_neigh
     if (kk < 2)      // np.cov of fewer than two points is NaN, and scipy.linalg.eigh refuses it
         return pct_fail(ctx, PCT_ERR_INVALID, "k=%d on %lld points leaves %lld neighbours: array must not contain infs or NaNs",
                         k, (long long)ctx->n, (long long)kk);
-    ctx->pca_valid = false;
+    ctx->res.drop(pct_replacing(PCT_R_PCA));
     double R = 0.0, origin[3] = {0, 0, 0};
     bool bad = false;
     // float64 clouds: from here until pct_pca_restore the handle's cloud is the recentred one the sweep ranks
@@ -1601,13 +1547,13 @@ int pct_pca_curvatures(pct_ctx* ctx, int32_t k, int32_t algo, int32_t keep_neigh
     int64_t exact = 0;
     st = pct_launch_pca(ctx, (int32_t)kk, 2.0 * R * (1.0 + 1e-9), origin, keep_neighbors != 0, &exact);
     if (ctx->has_f64) ctx->grid_valid = false;        // (the cell list holds the recentred float32 cloud)
-    ctx->knn_valid = ctx->fit_valid = false;           // (the table in place holds the over-fetched candidates)
+    ctx->res.drop(PCT_TABLE_AND_FIT_LOST);            // (the table in place holds the over-fetched candidates)
     PCT_TRY(st);
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_END], ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->tm.fit_ms = ev_ms(ctx, PCT_EV_FIT_BEGIN, PCT_EV_FIT_END);
     ctx->tm.total_ms = ctx->clock[0].since_begin(ctx->ev[PCT_EV_FIT_END]);
-    ctx->pca_valid = true;
+    ctx->res.leave(PCT_R_PCA, false);
     ctx->pca_has_nbr = keep_neighbors != 0;
     ctx->pca_k = (int32_t)kk;
     ctx->pca_rows = ctx->n;
@@ -1618,7 +1564,7 @@ int pct_pca_curvatures(pct_ctx* ctx, int32_t k, int32_t algo, int32_t keep_neigh
 int pct_get_pca(pct_ctx* ctx, int64_t begin, int64_t end, double* l1, double* l2, double* dirs, double* K, double* H,
                 int32_t* idx) {
     PCT_TRY(begin_call(ctx));
-    if (!ctx->pca_valid) return pct_fail(ctx, PCT_ERR_INVALID, "no PCA frame on this handle (pct_pca_curvatures)");
+    if (!ctx->res.has(PCT_R_PCA)) return pct_fail(ctx, PCT_ERR_INVALID, "no PCA frame on this handle (pct_pca_curvatures)");
     if (begin < 0 || end > ctx->pca_rows || begin > end)
         return pct_fail(ctx, PCT_ERR_INVALID, "bad row range [%lld,%lld) of %lld", (long long)begin, (long long)end, (long long)ctx->pca_rows);
     if (idx && !ctx->pca_has_nbr)

@@ -216,7 +216,8 @@ int pct_voxel_downsample_device(pct_ctx* ctx, const void* d_xyz, bool f64, int64
     PCT_HIP(ctx, hipMemcpyAsync(&total, (int*)ctx->scan_tmp.p + blocks, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *count = total;
-    ctx->grid_valid = ctx->knn_valid = false;      // scratch buffers of the cell list were reused
+    ctx->grid_valid = false;                       // scratch buffers of the cell list were reused
+    ctx->res.drop(PCT_TABLE_LOST);
     return PCT_OK;
 }
 

@@ -11,6 +11,7 @@
 #include "../../include/pct_hip_surface.h"
 #include "pct_stamp.h"
 #include "pct_clock.h"
+#include "pct_residents.h"
 
 #define PCT_WAVE 64
 #define PCT_K_MAX 511           // longest neighbour row: k + 1 <= 512 = 64 lanes x 8 list registers (wave-per-query sweeps, pct_knn_wide.hip)
@@ -159,6 +160,7 @@ struct pct_ctx {
     // mid-build wait (everything of the previous call has completed by then) or until anything else is asked of the
     // handle (which first waits for the stream).  The host prepares step i + 1 while the device fits step i.
     bool async_mode = false;
+    pct_residents res;             // which results are in place (the state rules of include/pct_hip.h: pct_residents.h)
     // the pending call -- on: a fused call has been enqueued and its bookkeeping has not been done; par: its parity (which
     // clock times it, which pinned slots its kernels write); sorted: its table is in a sorted space, knn_fast_ms applies;
     // tm: the host-side fields of its timings
@@ -281,9 +283,8 @@ struct pct_ctx {
     int fit_parity = 0;            // which of the two counts of fit_flag the next fit launch uses (the launch zeroes the other one)
     void* fit_flag_seen = nullptr; // the fit_flag allocation (pointer and capacity) whose head has been zeroed
     size_t fit_flag_cap_seen = 0;
-    bool knn_valid = false;
     bool knn_hier = false;         // the table in place came from the hierarchical list or the chain of cell lists (run_knn)
-    bool knn_sorted_space = false; // false: rows/ids are public indices (brute force)
+    bool knn_sorted_space = false; // the table's rows are in cell order, its entries sorted positions; false: public indices (brute force)
     bool dist_valid = true;        // nbr_dist holds the distances of the table in place (else: derived on demand)
     pct_buf counters;   // pct_dev_words: the sweep's statistics words, the census, the scatter hit count
 
@@ -291,10 +292,9 @@ struct pct_ctx {
     pct_buf coefs;      // float (n,6)
     pct_buf K, H, H2;   // float (n)
     int64_t fit_rows = 0;
-    bool fit_valid = false;
     bool fit_row_order = false;    // results are in neighbour-table row order (grid sweep), not public order
     bool fit_cloud_aligned = false;// results belong to cloud rows [q_begin, q_end) (pct_fit / pct_curvature) rather than to the
-                                   // rows of a pct_fit_indices call; kept apart from knn_valid, which helpers may clear
+                                   // rows of a pct_fit_indices call; kept apart from the table, which helpers may drop
 
     pct_buf fit_flag;   // int: [0] number of rows k_fit handed to k_fit_svd, [16..] the rows
     // staging for downloads / host-index fits
@@ -312,7 +312,7 @@ struct pct_ctx {
     pct_buf ball_idx;   // int32 (entries) public indices
     pct_buf ball_alt;   // ... the other buffer of the library's segmented sort (rows longer than k_ball_sort takes)
     pct_buf ball_dist;  // double (entries), when asked for
-    bool ball_valid = false, ball_has_dist = false;
+    bool ball_has_dist = false;
     int64_t ball_m = 0;
     int64_t ball_stats[4] = {0, 0, 0, 0};
 
@@ -321,7 +321,7 @@ struct pct_ctx {
     pct_buf pca_aux;    // float32 rounding offset, flags, rows handed to the exact pass and their bounds
     pct_buf pca_nbr;    // int32 (n,k): the neighbourhoods used (pct_pca_curvatures with keep_neighbors)
     pct_buf pca_orig;   // double4 (n): float64 clouds' uploaded records while the sweep sees them recentred
-    bool pca_valid = false, pca_has_nbr = false, pca_recentred = false;
+    bool pca_has_nbr = false, pca_recentred = false;
     int32_t pca_k = 0;
     int64_t pca_rows = 0;
 
@@ -332,7 +332,6 @@ struct pct_ctx {
     pct_buf area_closed;   // uint8 (owned)
     pct_buf area_nverts;   // int32 (owned)
     pct_buf area_over;     // eight statistics words, then int32 (owned): the rows redone with room for k + 4 vertices
-    bool area_valid = false;
     bool area_row_order = false;   // in neighbour-table row order (as fit_row_order), else public order from q_begin
     int64_t area_rows = 0;
     int64_t area_stats[4] = {0, 0, 0, 0};   // rows, closed rows, NaN rows, overflow rows
@@ -341,20 +340,18 @@ struct pct_ctx {
     // per-point surface frames (pct_frame.hip) of the owned rows of the resident table and its fit
     pct_buf frame;         // double (owned): normal (rows, 3) | k1 k2 (rows, 2) | directions (rows, 3, 2)
     pct_buf frame_flip;    // eight statistics words, then uint8 (owned): the viewpoint turned the row's normal
-    bool frame_valid = false;
     bool frame_row_order = false;  // in neighbour-table row order (as fit_row_order), else public order from q_begin
     int64_t frame_rows = 0;
     int64_t frame_stats[4] = {0, 0, 0, 0};  // rows, NaN rows, flipped rows, umbilic rows
     double frame_ms = 0;                    // device milliseconds of its kernel
 
     // consistent orientation of those frames (pct_orient.hip): one allocation, carved up per call; the four results in
-    // public order, int32 / uint8 (owned), live while orient_valid and the frames they turned are resident
+    // public order, int32 / uint8 (owned)
     pct_buf orient;
     const int* orient_comp = nullptr;
     const int* orient_parent = nullptr;
     const int* orient_level = nullptr;
     const unsigned char* orient_toggle = nullptr;
-    bool orient_valid = false;
     int64_t orient_rows = 0;
     int64_t orient_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // valid rows, components, unlabelled, toggled, levels, pull rounds, launches, waits
     double orient_ms = 0;
@@ -369,7 +366,6 @@ struct pct_ctx {
     pct_buf tri_mask, tri_count, tri_off, tri_tmp;   // agreed corners per row, triangles per row, their scan, scan scratch
     pct_buf tri_part;      // u64 (blocks, 4): the statistics' per-block partial sums
     pct_buf tri;           // int32 (triangles, 3), ascending
-    bool tri_valid = false;
     int32_t tri_wpitch = 0;
     int64_t tri_rows = 0, tri_total = 0;
     int64_t tri_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};

@@ -330,7 +330,8 @@ int pct_pca_prep(pct_ctx* ctx, double* round_off, bool* nonfinite, double origin
         PCT_HIP(ctx, hipMemcpyAsync(ctx->pca_orig.p, ctx->pts4d.p, (size_t)n * sizeof(double4), hipMemcpyDeviceToDevice, ctx->stream));
         PCT_HIP(ctx, hipMemcpyAsync(c, ctx->pca_orig.p, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
         ctx->pca_recentred = true;
-        ctx->grid_valid = ctx->knn_valid = ctx->fit_valid = ctx->pts4_valid = ctx->qpts4_valid = false;
+        ctx->grid_valid = ctx->pts4_valid = ctx->qpts4_valid = false;
+        ctx->res.drop(PCT_TABLE_AND_FIT_LOST);
     }
     PCT_LAUNCH(k_pca_prep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (float*)ctx->xyz_view,
                ctx->has_f64 ? (const double4*)ctx->pca_orig.p : nullptr, ctx->has_f64 ? (double4*)ctx->pts4d.p : nullptr, n,
@@ -348,7 +349,7 @@ int pct_pca_prep(pct_ctx* ctx, double* round_off, bool* nonfinite, double origin
 int pct_pca_restore(pct_ctx* ctx) {
     if (!ctx->pca_recentred) return PCT_OK;
     const int64_t n = ctx->n;
-    const bool sorted = ctx->knn_valid && ctx->knn_sorted_space;
+    const bool sorted = ctx->res.has(PCT_R_TABLE) && ctx->knn_sorted_space;
     PCT_LAUNCH(k_pca_restore, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const double4*)ctx->pca_orig.p, n,
                (double4*)ctx->pts4d.p, (float*)ctx->xyz_view, sorted ? (double4*)ctx->sorted4d.p : nullptr);
     PCT_HIP(ctx, hipGetLastError());

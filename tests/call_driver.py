@@ -1,6 +1,6 @@
 """Random call sequences over every modelled entry point, held to include/pct_hip.h (tests/call_model.py).
 
-`plan(seed, profile, steps)` draws a sequence from what the model allows -- about one step in six (768 of the 4800 committed
+`plan(seed, profile, steps)` draws a sequence from what the model allows -- about one step in six (911 of the 5400 committed
 steps; tests/test_call_model.py holds it between one in seven and one in five) an operation whose precondition the model says
 is unmet, for which the documented refusal is expected: after a call that dropped a result its getters are asked, a refusal the
 plan has not drawn yet is drawn where the state allows it, so that every (operation, precondition) pair is refused.  The choice depends on the seed and
@@ -32,7 +32,7 @@ K_SET = [3, 8, 30, 63, 64, 100, 127, 128, 200, 400]
 # possible, and otherwise.  Over the committed cases this comes to the share tests/test_call_model.py asserts.
 P_PROBE, P_NOVEL, P_ANY = 0.4, 0.3, 0.01
 _PROBES = {"get_neighbors": "table", "get_fit": "fit", "get_point_areas": "areas", "get_point_frames": "frames", "get_orientation": "orient",
-           "get_pca": "pca", "get_ball": "ball", "slab_counts": "slab_pass"}
+           "get_triangles": "triangles", "get_point_fans": "triangles", "get_pca": "pca", "get_ball": "ball", "slab_counts": "slab_pass"}
 
 # ---- the committed cases: (seed, profile, steps) -------------------------------------------------------------------------
 CASES = [
@@ -44,6 +44,7 @@ CASES = [
     (7, "stream", 600),      # consecutive clouds of equal size and box, asynchronous steps
     (2, "wide", 600),        # rows of 128-511 neighbours
     (1, "device", 600),      # device-resident input
+    (2, "surface", 600),     # fans and triangles among frames, orientation, voxel down-sampling and plantings
 ]
 
 _BASE = {
@@ -56,7 +57,11 @@ _BASE = {
     "get_pca": 0.3, "voxel_downsample": 0.08, "voxel_downsample_f32": 0.08, "mesh_energies": 0.08, "plane_rotate": 0.08, "fit_quadric": 0.08,
     "curvatures_from_coefficients": 0.08, "slab_counts": 1.5, "slab_records": 1.5, "scatter_records": 1.5,
     "get_timings": 0.08, "get_timings_done": 0.08, "synchronize": 0.1,
+    "point_triangles": 1.0, "get_point_fans": 0.6, "get_triangles": 0.8, "point_triangle_stats": 0.15,
 }
+# operations only the profiles that name them draw, in state or out of it: the plans of the others are what they were
+# before these operations existed
+_NAMED_ONLY = ("point_triangles", "get_point_fans", "get_triangles", "point_triangle_stats")
 # profile -> (multipliers, cloud loaders with weights, cloud-size classes with weights, share of new clouds among the steps)
 PROFILES = {
     "core": ({}, {"set_points_f32": 1.0}, (0.35, 0.35, 0.3), 0.03),
@@ -77,6 +82,10 @@ PROFILES = {
              {"set_points_f32": 0.8, "set_points_f64": 0.2}, (0.15, 0.45, 0.4), 0.03),
     "device": ({"voxel_downsample_f32": 4, "pca_curvatures": 4, "get_pca": 2, "query_ball": 2, "get_ball": 2, "set_query_range": 3, "set_query_slab": 25},
                {"set_points_device": 0.5, "use_points_device": 0.5}, (0.3, 0.3, 0.4), 0.1),
+    "surface": ({"point_triangles": 2.5, "get_point_fans": 4, "get_triangles": 1.5, "point_triangle_stats": 1, "point_frames": 2, "orient_frames": 2,
+                 "voxel_downsample": 5, "voxel_downsample_f32": 5, "surface_variation": 4, "pca_curvatures": 4, "set_query_range": 3, "set_query_slab": 25,
+                 "fit": 1.5, "point_areas": 0.4, "get_point_areas": 0.4, "get_fit": 0.5},
+                {"set_points_f32": 0.85, "set_points_f64": 0.15}, (0.3, 0.3, 0.4), 0.05),
 }
 _SIZES = ((40, 300), (1000, 3000), (4500, 6000))
 _CLOUD_OPS = ("set_points_f32", "set_points_f64", "set_points_device", "use_points_device")
@@ -92,10 +101,12 @@ def _follow(s, name):
     favoured, one that would drop it is held back -- a function of the model state, as every choice is."""
     if name in ("knn", "curvature"):
         return 0.4 if s.table is not None or s.slab_pass is not None else 1.0
-    if name in ("set_query_range", "set_query_slab", "pca_curvatures", "surface_variation") and (s.areas is not None or s.frames is not None):
+    if name in ("set_query_range", "set_query_slab", "pca_curvatures", "surface_variation") and (s.areas is not None or s.frames is not None or s.triangles is not None):
         return 2.0                      # (what they must drop is there to be dropped)
     if name in ("voxel_downsample", "voxel_downsample_f32") and s.table is not None and (s.frames is not None or s.areas is not None):
         return 10.0 if s.orient is not None else 4.0                      # (the table goes, what was computed from it must stay)
+    if s.triangles is not None and name in ("fit", "point_frames", "orient_frames", "voxel_downsample", "voxel_downsample_f32"):
+        return 3.0                      # (the triangles must stay)
     after_change = s.last is not None and bool(M.OPS[s.last].drops or M.OPS[s.last].creates)
     if after_change and M.OPS[name].pre and not (M.OPS[name].drops or M.OPS[name].creates):
         return 3.0                      # a getter right after a call that changes state: what it should have left is read
@@ -104,7 +115,7 @@ def _follow(s, name):
 
 
 _GETTERS = {"table": "get_neighbors", "fit": "get_fit", "areas": "get_point_areas", "frames": "get_point_frames", "orient": "get_orientation",
-            "pca": "get_pca", "ball": "get_ball"}
+            "triangles": "get_triangles", "pca": "get_pca", "ball": "get_ball"}
 
 
 # ---- clouds (NumPy only: a sequence is generated without the package) ----------------------------------------------------
@@ -160,6 +171,7 @@ class Plan:
         self.rng = np.random.default_rng([int(seed), 20260])
         self.profile = profile
         self.mult, self.loaders, self.sizes, self.cloud_w = PROFILES[profile]
+        self.mult = {**{n: 0.0 for n in _NAMED_ONLY if n not in self.mult}, **self.mult}
         self.state = M.State()
         self.pts = None
         self.serial = 0
@@ -183,7 +195,7 @@ class Plan:
         elif self._out_of_state():
             name, variant = self._pick_unmet()
         else:
-            names = [n for n in _BASE if M.check(s, n, {})[0] == M.OK and _WHEN.get(n, lambda s: True)(s)]
+            names = [n for n in _BASE if self.mult.get(n, 1.0) > 0 and M.check(s, n, {})[0] == M.OK and _WHEN.get(n, lambda s: True)(s)]
             w = np.array([_BASE[n] * self.mult.get(n, 1.0) * _follow(s, n) for n in names])
             name, variant = names[int(rng.choice(len(w), p=w / w.sum()))], None
         args = getattr(self, "_a_" + name, self._a_none)(variant or {})
@@ -194,7 +206,8 @@ class Plan:
         if name in _CLOUD_OPS: self.pts = args["pts"]
         if want != M.OK:                  # after a refusal one resident result, chosen by the seed, is read again
             have = [g for r, g in _GETTERS.items() if getattr(self.state, r) is not None and M.check(self.state, g, {})[0] == M.OK]
-            if have: self.queue.append(have[int(rng.integers(len(have)))])
+            if name == "point_triangles" and "get_triangles" in have: self.queue.append("get_triangles")      # (the result a refused call of it could take along)
+            elif have: self.queue.append(have[int(rng.integers(len(have)))])
         return name, args, want
 
     def _pick_loader(self):
@@ -206,10 +219,10 @@ class Plan:
         the model state and the plan's own count of what it has refused so far: a call has just dropped a result (its
         getter must now refuse), a refusal this plan has not drawn yet is possible, and a small constant share."""
         s, rng = self.state, self.rng
-        cands = M.unmet(s)
+        cands = [c for c in M.unmet(s) if self.mult.get(c[0], 1.0) > 0]
         count = lambda c: self.refused.get(M.refusal_key(s, c[0], c[1] or {}), 0)
         probe = [c for c in cands if c[1] is None and _PROBES.get(c[0]) in s.just and M.first_unmet(s, c[0], {}).startswith(_PROBES[c[0]])]
-        novel = [c for c in cands if count(c) == 0]
+        novel = [c for c in cands if count(c) < (2 if c[0] in _NAMED_ONLY else 1)]      # (what one profile alone draws is refused twice there)
         u = rng.random()
         if probe and u < (1.0 if s.last in ("set_points_device", "use_points_device", "set_query_slab") else P_PROBE):                 # every getter of what was just dropped, one after the other
             order = [probe[i] for i in rng.permutation(len(probe))]
@@ -224,7 +237,7 @@ class Plan:
         return True
 
     def _pick_unmet(self):
-        if self.state.cloud is None: self.pool = M.unmet(self.state)
+        if self.state.cloud is None: self.pool = [c for c in M.unmet(self.state) if self.mult.get(c[0], 1.0) > 0]
         return self.pool[int(self.rng.integers(len(self.pool)))]
 
     # -- arguments --------------------------------------------------------------------------------------------------------
@@ -345,6 +358,18 @@ class Plan:
         if v: return {"anchor": 2, "view": None, "max_components": 0}
         anchor = int(self.rng.integers(0, 3))
         return {"anchor": anchor, "view": self._view() if anchor == 2 else None, "max_components": int(self.rng.choice([0, 0, 0, 1, 3]))}
+
+    def _a_point_triangles(self, v):
+        if v: return dict(v)
+        return {"flags": M.TRI_WIND_FRAMES if self.state.frames is not None and self.rng.random() < 0.6 else 0}
+
+    def _a_get_point_fans(self, v):
+        b, e = self._span(0, max(self.state.n, 1))
+        return {"b": b, "e": e}
+
+    def _a_get_triangles(self, v):
+        lo, hi = np.sort(self.rng.random(2))              # (the plan does not know how many there are: a share of them)
+        return {"share": (0.0, 1.0) if self.rng.random() < 0.3 else (float(lo), float(hi))}
 
     def _queries(self, m_far, m_on):
         rng, pts = self.rng, self.pts
@@ -500,6 +525,20 @@ class Reference:
             out = (f.get_point_frames(0, self.n), stats)
             return out + ((f.get_orientation(0, self.n), f.orient_stats()) if calls else ())
         return self._fresh(("frames", k, eps, view, calls), work)
+
+    def triangles(self, t):
+        """(triangles, (fan offsets, fan members), statistics) for a resident's provenance: the table, the flag and -- with
+        the flag -- the frames and the orient calls that had turned them when pct_point_triangles ran."""
+        view, calls = (t["frames"]["view"], t["orient"]["calls"] if t["orient"] else ()) if t["wind"] else (None, ())
+        def work(f):
+            if t["wind"]:
+                f.curvature(t["k"], t["eps"], KNN_BRUTE); f.point_frames(view)
+                for anchor, v, maxc in calls: f.orient_frames(anchor, v, maxc)
+            else: f.knn(t["k"], t["eps"], KNN_BRUTE)
+            f.point_triangles(t["wind"])
+            stats = f.point_triangle_stats()
+            return f.get_triangles(0, stats["triangles"]), f.get_point_fans(0, self.n), stats
+        return self._fresh(("triangles", t["k"], t["eps"], t["wind"], view, calls), work)
 
     def study(self, k, rows, n_lo, n_hi):
         def work(f):
@@ -779,6 +818,35 @@ class Runner:
         want = self._frames(state)[3]
         keys = ("valid", "components", "unlabelled", "toggled", "levels", "pulls")
         if any(out[k] != want[k] for k in keys): return f"{out}, a fresh handle counts {want}"
+
+    # -- fans and triangles -----------------------------------------------------------------------------------------------
+    def do_point_triangles(self, a, s): self.h.point_triangles(bool(a["flags"] & M.TRI_WIND_FRAMES), flags=a["flags"] & ~M.TRI_WIND_FRAMES)
+    def do_get_point_fans(self, a, s): return self.h.get_point_fans(a["b"], a["e"])
+
+    def ck_get_point_fans(self, a, out, state, before):
+        off, nbr = self.ref.triangles(state.triangles)[1]
+        b, e = a["b"], a["e"]
+        if not same(out, (off[b:e + 1] - off[b], nbr[off[b]:off[e]])): return f"fans of rows [{b},{e}) of {M._brief(state.triangles)} differ from a fresh handle's"
+
+    def _triangle_span(self, a, s):
+        total = len(self.ref.triangles(s.triangles)[0]) if s.triangles is not None else 0
+        first = int(a["share"][0] * total)
+        return first, max(int(a["share"][1] * total) - first, 0)
+
+    def do_get_triangles(self, a, s): return self.h.get_triangles(*self._triangle_span(a, s))
+
+    def ck_get_triangles(self, a, out, state, before):
+        first, count = self._triangle_span(a, state)
+        if not same(out, self.ref.triangles(state.triangles)[0][first:first + count]):
+            return f"triangles [{first},{first + count}) of {M._brief(state.triangles)} differ from a fresh handle's"
+
+    def do_point_triangle_stats(self, a, s): return self.h.point_triangle_stats()
+
+    def ck_point_triangle_stats(self, a, out, state, before):
+        counts = {k: v for k, v in out.items() if not k.endswith("ms")}
+        if state.triangles is None: return None if not any(counts.values()) else f"{out} without triangles"
+        want = {k: v for k, v in self.ref.triangles(state.triangles)[2].items() if not k.endswith("ms")}
+        if counts != want: return f"{counts}, a fresh handle counts {want}"
 
     # -- queries of caller-supplied points, ball rows ---------------------------------------------------------------------
     def do_query_points(self, a, s): return _plain_query(self.h, a["q"], a["k"], a["eps"])

@@ -15,7 +15,8 @@ OK, INVALID, NO_NEIGHBORS, K_TOO_LARGE, LIMIT = "ok", "invalid", "no_neighbors",
 # a refusal as _capi.Handle._check raises it (PCT_ERR_LIMIT is returned by Handle.query_ball, not raised)
 RAISES = {INVALID: ValueError, NO_NEIGHBORS: AttributeError, K_TOO_LARGE: IndexError}
 
-RESIDENTS = ("table", "fit", "areas", "frames", "orient", "pca", "ball", "slab_pass")
+RESIDENTS = ("table", "fit", "areas", "frames", "orient", "triangles", "pca", "ball", "slab_pass")      # (the library's eight, csrc/pct_residents.h, and the slab pass)
+TRI_WIND_FRAMES = 1            # pct_point_triangles' flag
 SLAB_MIN_N = 4096              # pct_set_query_slab: float32 clouds of >= 4096 points
 
 
@@ -31,6 +32,7 @@ class State:
         self.areas = None        # {k, eps, lo, hi}
         self.frames = None       # {k, eps, lo, hi, view}
         self.orient = None       # {calls: ((anchor, view, max_components), ...)} since the frames were made
+        self.triangles = None    # {k, eps, lo, hi, wind, frames, orient}: the table's provenance, the flag and -- with the flag -- the frames' and the orientation's at the call
         self.pca = None          # {k, keep}
         self.ball = None         # {id, m, flags, centres}: the query's serial, its rows and flags, the cloud points its queries sit on
         self.slab_pass = None    # {k, eps, part, parts}: a pct_curvature has run in slab mode
@@ -90,6 +92,9 @@ COND = {
     "areas": lambda s, a: s.areas is not None,
     "frames": lambda s, a: s.frames is not None,
     "orient": lambda s, a: s.orient is not None,
+    "triangles": lambda s, a: s.triangles is not None,
+    "tri_flags": lambda s, a: not a.get("flags", 0) & ~TRI_WIND_FRAMES,
+    "tri_frames": lambda s, a: not a.get("flags", 0) & TRI_WIND_FRAMES or s.frames is not None,
     "pca": lambda s, a: s.pca is not None,
     "pca_idx": lambda s, a: not a.get("want_idx") or (s.pca is not None and s.pca["keep"]),
     "ball": lambda s, a: s.ball is not None,
@@ -118,10 +123,11 @@ class Op:
         self.folds = folds                     # waits for a pending asynchronous call first (almost everything)
 
 
-_PER_ROW = ("table", "fit", "areas", "frames", "orient", "slab_pass")
+_PER_ROW = ("table", "fit", "areas", "frames", "orient", "triangles", "slab_pass")
 _ALL = RESIDENTS
 _Q_NEW = "drops every result on the handle: the table, the fit results, the areas, the frames, the orientation, the PCA results and the ball rows"
 _Q_OWN = "drop what is computed per owned row: the table, the fit results, the areas, the frames and the orientation"
+_Q_TRI = "A new cloud, a change of ownership and every planting drop the triangles"
 _Q_OWN_KEEPS = "Ball rows and PCA results answer for the whole cloud and are untouched by a change of ownership"
 _Q_PLANT = "drop the table in place, the fit results, the areas, the frames and the orientation"
 _Q_PLANT_KEEPS = "Ball rows are untouched by a planting, and so are PCA results unless the planting is pct_pca_curvatures"
@@ -191,6 +197,11 @@ def _c_orient(s, a):
     s.orient = {"calls": before + ((a["anchor"], a.get("view"), a.get("max_components", 0)),)}
 
 
+def _c_triangles(s, a):
+    wind = bool(a.get("flags", 0) & TRI_WIND_FRAMES)            # (the winding is a snapshot of the flipped bits at the call)
+    s.triangles = dict(s.table, wind=wind, frames=s.frames if wind else None, orient=s.orient if wind else None)
+
+
 def _c_ball(s, a):
     if a.get("max_entries", 0) == 1 or a["flags"] & 4:      # capped, or PCT_BALL_COUNT_ONLY: nothing is kept
         return
@@ -218,7 +229,7 @@ _getter = dict(header=(_Q_SIDE,))
 
 OPS = {
     # ---- clouds --------------------------------------------------------------------------------------------------------
-    "set_points_f32": Op(["pct_set_points_f32"], drops=_ALL, creates=_new_cloud("host", "f32"), header=(_Q_NEW, "It ends slab mode and owns the whole cloud", _Q_SETTINGS)),
+    "set_points_f32": Op(["pct_set_points_f32"], drops=_ALL, creates=_new_cloud("host", "f32"), header=(_Q_NEW, _Q_TRI, "It ends slab mode and owns the whole cloud", _Q_SETTINGS)),
     "set_points_f64": Op(["pct_set_points_f64"], drops=_ALL, creates=_new_cloud("host", "f64"), header=(_Q_NEW,)),
     "set_points_device": Op(["pct_device_alloc", "pct_device_upload", "pct_set_points_device_f32", "pct_device_free"], drops=_ALL,
                             creates=_new_cloud("device_copy", "f32"), header=(_Q_NEW,)),
@@ -227,7 +238,7 @@ OPS = {
                             header=(_Q_NEW, "The buffer must stay allocated and unchanged until the next pct_set_points_* / pct_use_points_* call")),
     # ---- ownership -----------------------------------------------------------------------------------------------------
     "set_query_range": Op(["pct_set_query_range"], pre=[("cloud", INVALID, "pct_set_query_range and pct_set_query_slab need a cloud (PCT_ERR_INVALID)")],
-                          drops=_PER_ROW, creates=_c_range, header=(_Q_OWN, _Q_OWN_KEEPS, "also where the range is the one already set",
+                          drops=_PER_ROW, creates=_c_range, header=(_Q_OWN, _Q_TRI, _Q_OWN_KEEPS, "also where the range is the one already set",
                                                                     "ends with pct_set_query_range, a new cloud or pct_set_query_slab(parts <= 0)")),
     "set_query_slab": Op(["pct_set_query_slab"], pre=[("cloud", INVALID, "pct_set_query_range and pct_set_query_slab need a cloud (PCT_ERR_INVALID)"),
                                                       ("slab_cloud", INVALID, "float32 clouds of >= 4096 points")],
@@ -238,7 +249,7 @@ OPS = {
     "set_async": Op(["pct_set_async"], creates=_setting("async_on"), header=(_Q_SETTINGS, _Q_ASYNC)),
     # ---- plantings and fits --------------------------------------------------------------------------------------------
     "knn": Op(["pct_knn"], pre=[("cloud", INVALID, _Q_PLANT_CLOUD), _slab], drops=_PER_ROW, creates=_c_knn,
-              header=(_Q_PLANT, _Q_PLANT_KEEPS, "pct_knn leaves its table")),
+              header=(_Q_PLANT, _Q_TRI, _Q_PLANT_KEEPS, "pct_knn leaves its table")),
     "curvature": Op(["pct_curvature"], pre=[("cloud", INVALID, _Q_PLANT_CLOUD), ("slab_algo", INVALID, "pct_curvature refuses every algo but PCT_KNN_AUTO and PCT_KNN_GRID")],
                     drops=_PER_ROW, creates=_c_curvature, header=(_Q_PLANT, _Q_PLANT_KEEPS, "pct_curvature leaves its table and the cloud-aligned fit of it", _Q_FIT, _Q_ASYNC),
                     variants=(None, {"algo": 1})),
@@ -279,6 +290,17 @@ OPS = {
                                 "a refused pct_orient_frames does not", _Q_REFUSED)),
     "get_orientation": Op(["pct_get_orientation"], pre=[_slab, ("orient", INVALID, "pct_get_orientation PCT_ERR_INVALID without an orientation")], **_getter),
     "orient_stats": Op(["pct_orient_stats"], folds=False, **_getter),
+    # ---- fans and triangles (include/pct_hip_surface.h) ----------------------------------------------------------------
+    "point_triangles": Op(["pct_point_triangles"],
+                          pre=[_slab, ("table", NO_NEIGHBORS, _Q_TABLE), ("whole", INVALID, "PCT_ERR_INVALID for an owned range, as pct_orient_frames"),
+                               ("tri_flags", INVALID, "Unknown flag bits: PCT_ERR_INVALID"),
+                               ("tri_frames", INVALID, 'PCT_TRI_WIND_FRAMES without resident frames: PCT_ERR_INVALID "no point frames"')],
+                          drops=("triangles",), creates=_c_triangles, variants=(None, {"flags": 64}, {"flags": TRI_WIND_FRAMES}),
+                          header=("pct_point_triangles replaces the fans and triangles and touches nothing else", _Q_TRI,
+                                  "a fit, pct_point_frames, pct_orient_frames and pct_voxel_downsample do not", "the winding is a snapshot of the flipped bits at the call", _Q_REFUSED)),
+    "get_point_fans": Op(["pct_get_point_fans"], pre=[("triangles", INVALID, "pct_get_point_fans and pct_get_triangles PCT_ERR_INVALID without triangles")], **_getter),
+    "get_triangles": Op(["pct_get_triangles"], pre=[("triangles", INVALID, "pct_get_point_fans and pct_get_triangles PCT_ERR_INVALID without triangles")], **_getter),
+    "point_triangle_stats": Op(["pct_point_triangle_stats"], folds=False, **_getter),
     # ---- queries of caller-supplied points, ball rows ------------------------------------------------------------------
     "query_points": Op(["pct_query_points"], pre=[_slab, _cloud], **_getter),
     "query_points_algo": Op(["pct_query_points_algo"], pre=[_slab, _cloud],
@@ -327,6 +349,8 @@ EXCLUDED = {
     "pct_text_load": "host text parser: no handle, no state (tests/test_io.py)",
     "pct_write_ply_ascii": "host PLY writer: no handle, no state (tests/test_io.py)",
     "pct_write_ply_ascii_normals": "host PLY writer: no handle, no state (tests/test_io.py)",
+    "pct_write_ply_ascii_faces": "host PLY writer: no handle, no state (tests/test_gpu_triangles.py)",
+    "pct_point_triangle_profile": "two device times of the last pct_point_triangles: nothing the model can hold a value to (tests/test_gpu_triangles.py)",
     "pct_matrix_norms_f32": "host pass over an array: no handle, no state",
     "pct_matrix_norms_f64": "host pass over an array: no handle, no state",
     "pct_format_float": "pure host function",
@@ -359,9 +383,11 @@ def first_unmet(state, name, args):
 
 def refusal_key(state, name, args):
     """What a refusal exercises: the operation and the precondition that refuses it -- for pct_orient_frames also whether
-    an orientation is resident, the one result a refused call of it could take along."""
+    an orientation is resident, for pct_point_triangles whether triangles are: the one result a refused call of either
+    could take along."""
     key = (name, first_unmet(state, name, args))
-    return key + ("orientation resident",) if name == "orient_frames" and state.orient is not None else key
+    if name == "orient_frames" and state.orient is not None: return key + ("orientation resident",)
+    return key + ("triangles resident",) if name == "point_triangles" and state.triangles is not None else key
 
 
 def unmet(state):

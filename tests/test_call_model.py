@@ -44,7 +44,7 @@ def _crc(a):
 
 # what an operation makes anew: keeping the one before cannot show
 _MAKES = {"knn": ("table",), "curvature": ("table", "fit"), "surface_variation": ("table",), "fit": ("fit",), "fit_indices": ("fit",), "fit_ball": ("fit",),
-          "point_areas": ("areas",), "point_frames": ("frames",), "pca_curvatures": ("pca",), "query_ball": ("ball",)}
+          "point_areas": ("areas",), "point_frames": ("frames",), "point_triangles": ("triangles",), "pca_curvatures": ("pca",), "query_ball": ("ball",)}
 # one defect per operation and per result its "drops" clause names: defect -> (operations, residents wrongly kept).  (An
 # orientation goes with its frames: kept alone it is probed where the frames are made anew, by pct_point_frames.)
 EVERY_KEEP = {f"{op} keeps the {r}": ((op,), (r,)) for op, o in M.OPS.items() for r in o.drops
@@ -62,6 +62,9 @@ KEEPS = {
     "the table readable after voxel_downsample": (("voxel_downsample", "voxel_downsample_f32"), ("table",)),
     "surface_variation keeps the fit": (("surface_variation",), ("fit",)),
     "pct_pca_curvatures keeps the areas": (("pca_curvatures",), ("areas",)),
+    "a planting keeps the triangles": (("knn", "curvature", "surface_variation", "pca_curvatures"), ("triangles",)),
+    "a change of ownership keeps the triangles": (("set_query_range", "set_query_slab"), ("triangles",)),
+    "a new cloud keeps the triangles": (D._CLOUD_OPS, ("triangles",)),
 }
 # defect -> (operations, residents the operation wrongly drops)
 DROPS = {
@@ -71,9 +74,14 @@ DROPS = {
     "a planting drops the PCA results": (("knn", "curvature"), ("pca",)),
     "pct_fit_indices drops the areas": (("fit_indices",), ("areas",)),
     "pct_point_areas drops the frames": (("point_areas",), ("frames", "orient")),
+    "a fit drops the triangles": (("fit", "fit_indices", "fit_ball"), ("triangles",)),
+    "pct_point_frames drops the triangles": (("point_frames",), ("triangles",)),
+    "pct_orient_frames drops the triangles": (("orient_frames",), ("triangles",)),
+    "voxel_downsample drops the triangles": (("voxel_downsample", "voxel_downsample_f32"), ("triangles",)),
 }
 SPECIAL = ["fit_indices results served as cloud-aligned", "PCA leaves its over-fetched table valid", "query_points through the cell list disturbs the table",
-           "fit_ball disturbs the ball rows", "a refused call changes state", "an async read served before the pending call is folded in"]
+           "fit_ball disturbs the ball rows", "a refused call changes state", "an async read served before the pending call is folded in",
+           "a refused pct_point_triangles drops the triangles", "triangles wound by the frames as they are now, not as the call found them"]
 KEEPS.update(EVERY_KEEP)
 DEFECTS = list(KEEPS) + list(DROPS) + SPECIAL
 
@@ -114,6 +122,8 @@ class FakeHandle:
                 new.ball = dict(new.ball, disturbed=True)
         elif d == "a refused call changes state" and status != M.LIMIT:
             new.fit = new.orient = None
+        elif d == "a refused pct_point_triangles drops the triangles" and name == "point_triangles":
+            new.triangles = None
         if M.OPS[name].folds and not new.pending:
             if not (d == "an async read served before the pending call is folded in" and name in ("get_fit", "get_neighbors")): self.stale = None
         self.s = new
@@ -335,6 +345,42 @@ class FakeHandle:
         if self.s.orient is None: return {**{k: 0 for k in names}, "ms": 0.0}
         return {**{k: (self._frame_seed() >> i) % 97 for i, k in enumerate(names)}, "ms": 0.1}
 
+    # -- fans and triangles -----------------------------------------------------------------------------------------------
+    def point_triangles(self, wind_frames=False, flags=0):
+        self._call("point_triangles", {"flags": (M.TRI_WIND_FRAMES if wind_frames else 0) | int(flags)})
+
+    def _triangles(self):
+        """(triangles, fan offsets, fan members) hashed from the resident's provenance: 0-3 fan members and 0-2 triangles per row."""
+        t, n = self.s.triangles, self.s.n
+        side = (t["frames"], t["orient"])
+        if self.defect == "triangles wound by the frames as they are now, not as the call found them" and t["wind"]: side = (self.s.frames, self.s.orient)
+        sd = _seed("triangles", self._key(), t["k"], t["eps"], t["wind"], side)
+        if ("triangles", sd) not in self.memo:
+            rows = np.arange(n)
+            off = np.concatenate([[0], np.cumsum((_mix(sd, rows) % np.uint64(4)).astype(np.int64))])
+            nbr = (_mix(sd + 1, np.arange(off[-1])) % np.uint64(n)).astype(np.int32)
+            v0 = np.repeat(rows, (_mix(sd + 2, rows) % np.uint64(3)).astype(np.int64))
+            tri = np.stack([v0, _mix(sd + 3, np.arange(len(v0))) % np.uint64(n), _mix(sd + 4, np.arange(len(v0))) % np.uint64(n)], axis=1).astype(np.int32)
+            self.memo["triangles", sd] = tri, off, nbr
+        return self.memo["triangles", sd]
+
+    def get_triangles(self, first=0, count=None):
+        self._call("get_triangles", {})
+        tri = self._triangles()[0]
+        return tri[first:] if count is None else tri[first:first + count]
+
+    def get_point_fans(self, b, e):
+        self._call("get_point_fans", {"b": b, "e": e})
+        _, off, nbr = self._triangles()
+        return off[b:e + 1] - off[b], nbr[off[b]:off[e]]
+
+    def point_triangle_stats(self):
+        self._call("point_triangle_stats", {})
+        names = ("rows", "rows_with_corner", "corners", "triangles", "wide_rows", "largest_fan", "boundary_edges")
+        if self.s.triangles is None: return {**{k: 0 for k in names}, "ms": 0.0, "fan_ms": 0.0, "agree_ms": 0.0}
+        tri, off, _ = self._triangles()
+        return {**{k: 1 for k in names}, "rows": self.s.n, "triangles": len(tri), "largest_fan": int(np.diff(off).max()), "ms": 0.1, "fan_ms": 0.05, "agree_ms": 0.05}
+
     # -- queries ----------------------------------------------------------------------------------------------------------
     def _query(self, name, q, k, eps, algo):
         self._call(name, {"algo": algo})
@@ -507,7 +553,8 @@ def test_every_entry_point_is_issued_and_every_precondition_refused():
     assert not few, f"issued successfully fewer than five times over the committed seeds: {few}"
     # every precondition of every operation, not only every operation: (operation, the condition that refuses it)
     pairs = [(n, cond) for n, op in M.OPS.items() for cond, _, _ in op.pre] + [("orient_frames", c, "orientation resident") for c in ("table", "view_given")]
-    rare = {k: refused.get(k, 0) + (refused.get(k + ("orientation resident",), 0) if len(k) == 2 else 0) for k in pairs}
+    pairs += [("point_triangles", c, "triangles resident") for c in ("tri_flags", "tri_frames")]
+    rare = {k: refused.get(k, 0) + (sum(refused.get(k + (r,), 0) for r in ("orientation resident", "triangles resident")) if len(k) == 2 else 0) for k in pairs}
     rare = {k: v for k, v in rare.items() if v < 2}
     assert not rare, f"refused fewer than twice over the committed seeds: {rare}"
     # the share of steps that expect a refusal, as tests/call_driver.py and DESIGN.md state it

@@ -1,4 +1,4 @@
-"""The C-ABI library loads and exports every symbol include/pct_hip.h declares (no compute)."""
+"""The C-ABI library loads and exports every symbol include/pct_hip.h and include/pct_hip_surface.h declare (no compute)."""
 import ctypes
 import os
 import re
@@ -10,7 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "pct_hip.h")).read()
+    text = "".join(open(os.path.join(ROOT, "include", h)).read() for h in ("pct_hip.h", "pct_hip_surface.h"))
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     return sorted(set(re.findall(r"\b(pct_[a-z0-9_]+)\s*\(", text)))
 

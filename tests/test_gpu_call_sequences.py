@@ -147,3 +147,77 @@ def test_fit_indices_is_refused_on_a_slab_handle(gpu):
             h.device_free(rec)
     finally:
         h.close()
+
+
+# ---- fans and triangles: the header's sentences a drawn sequence meets only by luck ----------------------------------------
+_TRI_CLOUDS = [(300, 8), (300, 30), (5000, 8), (5000, 30)]       # (the driver's small and large size classes: 5000 points take the cell-list path)
+
+
+def _triangles(h, n):
+    stats = {k: v for k, v in h.point_triangle_stats().items() if not k.endswith("ms")}
+    return (h.get_triangles(0, stats["triangles"]),) + h.get_point_fans(0, n), stats
+
+
+def _no_triangles(h):
+    for read in (lambda: h.get_triangles(0, 1), lambda: h.get_point_fans(0, 1)):
+        with pytest.raises(ValueError, match="no triangles"):
+            read()
+    assert not any(v for k, v in h.point_triangle_stats().items())
+
+
+@pytest.mark.parametrize("n,k", _TRI_CLOUDS)
+def test_triangles_outlive_a_fit_new_frames_an_orientation_and_voxel_downsample(gpu, n, k):
+    """The header: a fit, pct_point_frames, pct_orient_frames and pct_voxel_downsample do not drop the triangles -- they
+    are kept by public index, and the winding is a snapshot of the flipped bits at the call."""
+    capi = gpu["capi"]
+    pts = gpu["shapes"].torus_random(n, seed=21)
+    h = capi.Handle(0)
+    try:
+        h.set_points(pts); h.curvature(k); h.point_frames(); h.point_triangles(True)
+        before, stats = _triangles(h, n)
+        assert stats["rows"] == n and len(before[0]) == stats["triangles"] > 0 and before[1][-1] == len(before[2]) > 0
+        for change in (h.fit, lambda: h.point_frames((0.0, 0.0, 9.0)), lambda: h.orient_frames("top"), lambda: h.voxel_downsample(pts, 0.1)):
+            change()
+            after = _triangles(h, n)
+            assert _same(after[0], before) and after[1] == stats
+        with pytest.raises(AttributeError):
+            h.get_neighbors(0, 1)                             # (the table went with pct_voxel_downsample, the triangles did not)
+    finally:
+        h.close()
+
+
+@pytest.mark.parametrize("n,k", _TRI_CLOUDS)
+def test_triangles_go_with_every_planting_and_with_the_range_set_again(gpu, n, k):
+    """The header: a new cloud, a change of ownership and every planting drop the triangles -- all four plantings, and
+    pct_set_query_range also where the range is the one already set."""
+    capi = gpu["capi"]
+    pts = gpu["shapes"].torus_random(n, seed=22)
+    h = capi.Handle(0)
+    try:
+        h.set_points(pts)
+        for drop in (lambda: h.knn(k), lambda: h.curvature(k), lambda: h.surface_variation(k + 1), lambda: h.pca_curvatures(k), lambda: h.set_query_range(0, n)):
+            h.knn(k); h.point_triangles()
+            assert h.point_triangle_stats()["triangles"] > 0 and len(h.get_triangles(0, 1)) == 1
+            drop()
+            _no_triangles(h)
+    finally:
+        h.close()
+
+
+@pytest.mark.parametrize("n,k", _TRI_CLOUDS)
+def test_refused_point_triangles_keeps_the_triangles(gpu, n, k):
+    """The header: a refused call changes nothing -- pct_point_triangles drops the triangles of an earlier call behind
+    its last refusal, so an unknown flag bit or PCT_TRI_WIND_FRAMES without frames leaves them."""
+    capi = gpu["capi"]
+    pts = gpu["shapes"].torus_random(n, seed=23)
+    h = capi.Handle(0)
+    try:
+        h.set_points(pts); h.knn(k); h.point_triangles()
+        before, stats = _triangles(h, n)
+        for refused, why in ((lambda: h.point_triangles(False, flags=64), "unknown flags"), (lambda: h.point_triangles(True), "no point frames")):
+            with pytest.raises(ValueError, match=why):
+                refused()
+            after = _triangles(h, n)
+            assert _same(after[0], before) and after[1] == stats
+    finally:
+        h.close()
