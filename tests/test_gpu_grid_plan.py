@@ -89,6 +89,7 @@ EXPECTED = {
     "warm_A": (1, 300, "0x1.2cb9435ffee0ap-2", 4000, 352, "0x1.d4a5e353f7ceep+4"),
     "warm_A_no_spec": (1, 300, "0x1.20b9e519d607bp-2", 4000, 360, "0x1.b326e978d4fdfp+4"),
     "auto_scan_grid": (4, 1156896, "0x1.1694cf3ace62fp-7", 20000, 9120, "0x1.b3c63f141205cp+4"),
+    # (the one row of the hierarchical list: also DERIVED, by tests/tree_exact.py -- test_tree_exact.py: test_recorded_row_of_the_scan)
     "auto_scan": (1, 1068, "0x1.530afdc2aa400p-20", 20000, 2220, "0x1.2ba01eae807acp+4"),
     "auto_torus": (1, 2646, "0x1.0d2759bd94b65p-3", 20000, 1776, "0x1.b396bb98c7e28p+4"),
 }
