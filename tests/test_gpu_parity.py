@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import ownership_exact
 import pct_oracle as oracle
 
 pytestmark = pytest.mark.gpu
@@ -675,8 +676,11 @@ def test_slab_shards_of_an_unsorted_cloud_are_bit_identical(gpu, parts):
     _, K0, H0, _ = h.get_fit(0, n, coefs=False, H2=False)
     K, H, tms = _slab_pass(h, pts, k, parts)
     assert np.array_equal(K.view(np.uint32), K0.view(np.uint32)) and np.array_equal(H.view(np.uint32), H0.view(np.uint32))
+    largest_bin = int(ownership_exact.Split(pts, parts).hist.max())
+    assert largest_bin + 1 < 0.001 * n
     for t in tms:
-        assert abs(t["rows"] - n / parts) < 0.01 * n, tms                        # equal populations (4096 bins)
+        # equal populations: cum[cut[p]] lies in [floor(p n / parts), floor(p n / parts) + largest bin), tests/ownership_exact.py
+        assert abs(t["rows"] - n / parts) <= largest_bin + 1, tms
         assert t["rows"] <= t["grid_points"] <= n / parts + 0.25 * n, t          # the slab and its margin, not the cloud
         assert t["limit_retries"] == 0
     # by-index getters have no meaning for a slab; an index range (or a new cloud) brings them back
