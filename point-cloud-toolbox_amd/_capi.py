@@ -149,6 +149,17 @@ SIGNATURES = {
     "pct_write_ply_ascii_faces": (C.c_int, [C.c_char_p, _f32p, _f32p, _f32p, _f32p, C.c_int64, _i32p, C.c_int64]),
 }
 
+# include/pct_hip_holes.h: a table of its own -- SIGNATURES stays the boundary of pct_hip.h and pct_hip_surface.h
+HOLE_SIGNATURES = {
+    "pct_fill_holes": (C.c_int, [_p, C.c_int32, C.c_double, C.c_int32]),
+    "pct_get_hole_triangles": (C.c_int, [_p, C.c_int64, C.c_int64, _i32p]),
+    "pct_get_filled_triangles": (C.c_int, [_p, C.c_int64, C.c_int64, _i32p]),
+    "pct_get_boundary_loops": (C.c_int, [_p, _i64p, _i32p, C.POINTER(C.c_uint8)]),
+    "pct_fill_hole_stats": (C.c_int, [_p, _i64p, _f64p]),
+}
+HOLE_MAX_VERTICES = 32                                  # PCT_HOLE_MAX_VERTICES
+HOLE_STATUS = ("filled", "perimeter", "blocked")        # pct_get_boundary_loops' status bytes
+
 _lib = None
 
 
@@ -169,8 +180,8 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as exc:  # pragma: no cover - depends on the machine
         raise HipExtensionError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)      # AttributeError if the ABI and this table diverge
+    for name, (res, args) in (*SIGNATURES.items(), *HOLE_SIGNATURES.items()):
+        fn = getattr(lib, name)      # AttributeError if the ABI and these tables diverge
         fn.restype = res
         fn.argtypes = args
     if lib.pct_timings_size() != C.sizeof(Timings):
@@ -717,6 +728,51 @@ class Handle:
         tri = np.empty((max(int(count), 0), 3), np.int32)
         self._check(self._lib.pct_get_triangles(self._h, int(first), int(count), _ptr(tri, _i32p)))
         return tri
+
+    # -- boundary loops and small-hole filling (include/pct_hip_holes.h) -----------------------------------------------------
+    def fill_holes(self, max_vertices=HOLE_MAX_VERTICES, max_perimeter=float("inf"), flags=0):
+        """``pct_fill_holes``: the boundary loops of the resident triangles, those of at most ``max_vertices`` vertices and
+        a perimeter below ``max_perimeter`` filled.  Kept on the device beside the triangles (``get_hole_triangles``,
+        ``get_filled_triangles``, ``get_boundary_loops``)."""
+        self._check(self._lib.pct_fill_holes(self._h, int(max_vertices), float(max_perimeter), int(flags)))
+
+    def fill_hole_stats(self):
+        """Of the last ``fill_holes``: {boundary_edges (before), gaps, odd_gaps, loops, filled, perimeter, blocked,
+        patch_triangles, ms (device time of the call)}."""
+        out = np.zeros(8, np.int64)
+        ms = np.zeros(1, np.float64)
+        self._check(self._lib.pct_fill_hole_stats(self._h, _ptr(out, _i64p), _ptr(ms, _f64p)))
+        names = ("boundary_edges", "gaps", "odd_gaps", "loops", "filled", "perimeter", "blocked", "patch_triangles")
+        return {**{k: int(v) for k, v in zip(names, out)}, "ms": float(ms[0])}
+
+    def get_hole_triangles(self, first=0, count=None):
+        """(count, 3) int32: the patch triangles, ascending; by default all of them."""
+        if count is None:
+            count = self.fill_hole_stats()["patch_triangles"] - int(first)
+        tri = np.empty((max(int(count), 0), 3), np.int32)
+        self._check(self._lib.pct_get_hole_triangles(self._h, int(first), int(count), _ptr(tri, _i32p)))
+        return tri
+
+    def get_filled_triangles(self, first=0, count=None):
+        """(count, 3) int32: the resident triangles merged with the patches, ascending; by default all of them."""
+        if count is None:
+            count = self.point_triangle_stats()["triangles"] + self.fill_hole_stats()["patch_triangles"] - int(first)
+        tri = np.empty((max(int(count), 0), 3), np.int32)
+        self._check(self._lib.pct_get_filled_triangles(self._h, int(first), int(count), _ptr(tri, _i32p)))
+        return tri
+
+    def get_boundary_loops(self):
+        """(offsets (loops + 1,) int64, vertices int32, status (loops,) uint8): every owned loop in canonical order; status
+        0 filled, 1 left for its perimeter, 2 blocked."""
+        loops = self.fill_hole_stats()["loops"]
+        off = np.zeros(loops + 1, np.int64)
+        status = np.zeros(loops, np.uint8)
+        u8p = C.POINTER(C.c_uint8)
+        self._check(self._lib.pct_get_boundary_loops(self._h, _ptr(off, _i64p), None, _ptr(status, u8p)))
+        verts = np.empty(int(off[-1]), np.int32)
+        if len(verts):
+            self._check(self._lib.pct_get_boundary_loops(self._h, _ptr(off, _i64p), _ptr(verts, _i32p), _ptr(status, u8p)))
+        return off, verts, status
 
     def point_energies(self, closed_only=False):
         """``pct_point_energies``: (bending, stretching, area, n_used) over the owned rows -- the closed ones only with

@@ -242,7 +242,9 @@ void pct_destroy(pct_ctx* ctx) {
                       &ctx->bin_rec, &ctx->bin_mat, &ctx->bin_plan, &ctx->bin_base,
                       &ctx->area, &ctx->area_closed, &ctx->area_nverts, &ctx->area_over, &ctx->frame, &ctx->frame_flip, &ctx->orient, &ctx->stamp_tickets,
                       &ctx->fan_head, &ctx->fan_fast, &ctx->fan_wide, &ctx->fan_side, &ctx->fan_over, &ctx->tri_mask, &ctx->tri_count, &ctx->tri_off,
-                      &ctx->tri_tmp, &ctx->tri_part, &ctx->tri};
+                      &ctx->tri_tmp, &ctx->tri_part, &ctx->tri,
+                      &ctx->hole_cnt, &ctx->hole_off, &ctx->hole_part, &ctx->hole_gap, &ctx->hole_slot, &ctx->hole_scan, &ctx->hole_loop, &ctx->hole_tri,
+                      &ctx->hole_alt, &ctx->hole_filled, &ctx->hole_tmp};
     for (pct_buf* b : all) pct_release(b);
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     for (auto& e : ctx->ev)
@@ -1345,6 +1347,77 @@ int pct_point_triangle_stats(pct_ctx* ctx, int64_t out[8], double* ms) {
 int pct_point_triangle_profile(pct_ctx* ctx, double out[2]) {
     if (!ctx || !out) return PCT_ERR_INVALID;
     for (int i = 0; i < 2; ++i) out[i] = ctx->res.has(PCT_R_TRIANGLES) ? ctx->tri_ms[1 + i] : 0.0;
+    return PCT_OK;
+}
+
+// ---- boundary loops and small-hole filling (pct_hole.hip, include/pct_hip_holes.h): an appendix of the triangles -------------
+static bool hole_results(const pct_ctx* ctx) { return ctx->res.has(PCT_R_TRIANGLES) && ctx->hole_valid; }
+
+int pct_fill_holes(pct_ctx* ctx, int32_t max_vertices, double max_perimeter, int32_t flags) {
+    PCT_TRY(begin_row_call(ctx, "pct_fill_holes"));
+    if (ctx->n > 0 && (ctx->q_begin != 0 || ctx->q_end != ctx->n || ctx->culled))
+        return pct_fail(ctx, PCT_ERR_INVALID, "pct_fill_holes: the handle owns rows [%lld,%lld) of %lld: a loop may cross into other rows",
+                        (long long)ctx->q_begin, (long long)ctx->q_end, (long long)ctx->n);
+    if (!ctx->res.has(PCT_R_TRIANGLES)) return pct_fail(ctx, PCT_ERR_INVALID, "no triangles (pct_point_triangles)");
+    if (max_vertices < 3 || max_vertices > PCT_HOLE_MAX_VERTICES)
+        return pct_fail(ctx, PCT_ERR_INVALID, "pct_fill_holes: max_vertices=%d outside [3,%d]", max_vertices, PCT_HOLE_MAX_VERTICES);
+    if (!(max_perimeter > 0.0)) return pct_fail(ctx, PCT_ERR_INVALID, "pct_fill_holes: max_perimeter must be positive (+inf: no cap)");
+    if (flags != 0) return pct_fail(ctx, PCT_ERR_INVALID, "pct_fill_holes: unknown flags %d", flags);
+    ctx->hole_valid = false;                           // (behind every refusal: a refused call leaves the results of an earlier one)
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_HOLE_BEGIN], ctx->stream));
+    int64_t st[8];
+    const int status = pct_launch_fill_holes(ctx, max_vertices, max_perimeter, st);
+    if (status != PCT_OK) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return status;
+    }
+    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_HOLE_END], ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < 8; ++i) ctx->hole_stats[i] = st[i];
+    ctx->hole_ms = ev_ms(ctx, PCT_EV_HOLE_BEGIN, PCT_EV_HOLE_END);
+    ctx->hole_valid = true;
+    return PCT_OK;
+}
+
+static int get_triangle_rows(pct_ctx* ctx, const pct_buf& src, int64_t have, int64_t first, int64_t count, int32_t* tri) {
+    PCT_TRY(begin_call(ctx));
+    if (!hole_results(ctx)) return pct_fail(ctx, PCT_ERR_INVALID, "no hole results (pct_fill_holes)");
+    if (first < 0 || count < 0 || first + count > have || (count > 0 && !tri))
+        return pct_fail(ctx, PCT_ERR_INVALID, "triangles [%lld,%lld) outside the %lld resident", (long long)first, (long long)(first + count), (long long)have);
+    if (count == 0) return PCT_OK;
+    PCT_HIP(ctx, hipMemcpyAsync(tri, (const int*)src.p + first * 3, (size_t)count * 3 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PCT_OK;
+}
+
+int pct_get_hole_triangles(pct_ctx* ctx, int64_t first, int64_t count, int32_t* tri) {
+    if (!ctx) return PCT_ERR_INVALID;
+    return get_triangle_rows(ctx, ctx->hole_tri, ctx->hole_patches, first, count, tri);
+}
+
+int pct_get_filled_triangles(pct_ctx* ctx, int64_t first, int64_t count, int32_t* tri) {
+    if (!ctx) return PCT_ERR_INVALID;
+    return get_triangle_rows(ctx, ctx->hole_filled, ctx->tri_total + ctx->hole_patches, first, count, tri);
+}
+
+int pct_get_boundary_loops(pct_ctx* ctx, int64_t* offsets, int32_t* vertices, uint8_t* status) {
+    PCT_TRY(begin_call(ctx));
+    if (!hole_results(ctx)) return pct_fail(ctx, PCT_ERR_INVALID, "no hole results (pct_fill_holes)");
+    if (!offsets) return pct_fail(ctx, PCT_ERR_INVALID, "null offsets");
+    const int64_t loops = ctx->hole_loops, verts = ctx->hole_loop_verts;
+    const char* base = (const char*)ctx->hole_loop.p;
+    const size_t off_bytes = (size_t)(loops + 1) * sizeof(int64_t), vert_bytes = (size_t)verts * sizeof(int);
+    PCT_HIP(ctx, hipMemcpyAsync(offsets, base, off_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (status && loops > 0) PCT_HIP(ctx, hipMemcpyAsync(status, base + off_bytes + vert_bytes, (size_t)loops, hipMemcpyDeviceToHost, ctx->stream));
+    if (vertices && verts > 0) PCT_HIP(ctx, hipMemcpyAsync(vertices, base + off_bytes, vert_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PCT_OK;
+}
+
+int pct_fill_hole_stats(pct_ctx* ctx, int64_t out[8], double* ms) {
+    if (!ctx || !out) return PCT_ERR_INVALID;
+    for (int i = 0; i < 8; ++i) out[i] = hole_results(ctx) ? ctx->hole_stats[i] : 0;
+    if (ms) *ms = hole_results(ctx) ? ctx->hole_ms : 0.0;
     return PCT_OK;
 }
 

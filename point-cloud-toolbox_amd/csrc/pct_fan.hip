@@ -18,7 +18,7 @@
 // and counted for the row.  rocprim::exclusive_scan.  k_tri_fill: writes the row's triangles wound about its normal, sorted
 // among themselves, and counts the edges with one face from the row's own mask.  No atomics on the output: the same bytes
 // for the same state.
-#include "pct_area_row.h"
+#include "pct_fan_row.h"
 
 #include <rocprim/device/device_scan.hpp>
 
@@ -134,23 +134,8 @@ struct TriArgs {
     unsigned long long* part;       // (blocks, 4): every block's {rows with a corner, corners, largest fan, edges with one face}
 };
 
-// a block's share of one statistic into its slot of TriArgs::part (no same-address atomics: k_tri_stats adds the slots up)
-__device__ __forceinline__ void block_partial(unsigned long long v, bool is_max, unsigned long long* __restrict__ slot) {
-    __shared__ unsigned long long sh[4];
-    for (int s = 32; s > 0; s >>= 1) {
-        const unsigned long long other = __shfl_xor(v, s);
-        v = is_max ? (other > v ? other : v) : v + other;
-    }
-    __syncthreads();                              // (the slot array is used once per statistic)
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long r = sh[0];
-        for (int w = 1; w < 4; ++w) r = is_max ? (sh[w] > r ? sh[w] : r) : r + sh[w];
-        *slot = r;
-    }
-}
-
+// (a block's share of one statistic goes into its slot of TriArgs::part through block_partial, pct_fan_row.h: k_tri_stats
+// adds the slots up)
 __global__ __launch_bounds__(256) void k_tri_stats(const unsigned long long* __restrict__ part, int blocks, unsigned long long* __restrict__ words) {
     __shared__ unsigned long long sh[4][256];
     unsigned long long v[4] = {0, 0, 0, 0};
@@ -169,13 +154,6 @@ __global__ __launch_bounds__(256) void k_tri_stats(const unsigned long long* __r
     }
 }
 
-__device__ __forceinline__ const int* fan_codes(const int2* __restrict__ head, const int* __restrict__ fast, const int* __restrict__ wide,
-                                                int wpitch, int64_t i, int& n) {
-    const int2 h = head[i];
-    n = h.x;
-    return h.y < 0 ? fast + i * kAreaCap : wide + (int64_t)h.y * wpitch;
-}
-__device__ __forceinline__ int code_record(int c) { return c >= 0 ? c : -2 - c; }          // (-1 stays -1)
 // vertex v of the fan: a proper corner of two different records?
 __device__ __forceinline__ bool fan_corner(const int* __restrict__ codes, int n, int v, int& a, int& b) {
     const int cv = codes[v];
@@ -363,6 +341,7 @@ int scan_counts(pct_ctx* ctx, const int64_t* d_count, int64_t* d_off, int64_t en
 int pct_launch_point_triangles(pct_ctx* ctx, bool wind_frames, hipEvent_t mid) {
     const int64_t n = ctx->n;
     const bool sorted = ctx->knn_sorted_space;
+    ctx->hole_valid = false;        // the boundary loops and patches of the triangles about to be replaced (pct_hole.hip)
     FitArgs a = {};
     PCT_TRY(fit_source(ctx, sorted ? FitSpace::Sorted : FitSpace::Packed, &a));
     a.table = (const int*)ctx->nbr_pos.p;

@@ -9,6 +9,7 @@
 
 #include "../../include/pct_hip.h"
 #include "../../include/pct_hip_surface.h"
+#include "../../include/pct_hip_holes.h"
 #include "pct_stamp.h"
 #include "pct_clock.h"
 #include "pct_residents.h"
@@ -125,6 +126,7 @@ struct pct_pinned {
     alignas(64) unsigned long long frame_words[8];   // pct_point_frames (pct_frame.hip): NaN rows, flipped rows, umbilic rows
     alignas(64) int orient_words[16];                // pct_orient_frames (pct_orient.hip): its control words, OrientWord
     alignas(64) unsigned long long tri_words[8];     // pct_point_triangles (pct_fan.hip): FanWord; [7] the triangle count
+    alignas(64) long long hole_words[8];             // pct_fill_holes (pct_hole.hip): HoleWord
 };
 static_assert(sizeof(pct_pinned) <= 4096, "pct_create allocates 4096 bytes");
 
@@ -138,6 +140,7 @@ enum pct_event {                           // ctx->ev
     PCT_EV_FRAME_BEGIN, PCT_EV_FRAME_END,  // pct_point_frames
     PCT_EV_ORIENT_BEGIN, PCT_EV_ORIENT_END,// pct_orient_frames
     PCT_EV_TRI_BEGIN, PCT_EV_TRI_MID, PCT_EV_TRI_END,   // pct_point_triangles: the fan kernels | agreement and emission
+    PCT_EV_HOLE_BEGIN, PCT_EV_HOLE_END,    // pct_fill_holes
     PCT_EV_COUNT
 };
 
@@ -370,6 +373,22 @@ struct pct_ctx {
     int64_t tri_rows = 0, tri_total = 0;
     int64_t tri_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     double tri_ms[3] = {0, 0, 0};           // device milliseconds: the call, its fan kernels, agreement and emission
+
+    // boundary loops and patches of those triangles (pct_hole.hip, include/pct_hip_holes.h): an appendix of the triangles
+    // resident -- read only while res.has(PCT_R_TRIANGLES) && hole_valid; pct_launch_point_triangles clears the flag
+    bool hole_valid = false;
+    pct_buf hole_cnt, hole_off;     // int64 (n + 1): gaps per row, their scan
+    pct_buf hole_part;              // u64 (blocks, 4): the statistics' per-block partial sums
+    pct_buf hole_gap;               // int2 (gaps): the gaps' members {a, b}; int (gaps): their rows
+    pct_buf hole_slot;              // per gap: HoleSlot, PCT_HOLE_MAX_VERTICES loop vertices, 3 (PCT_HOLE_MAX_VERTICES - 2) patch indices
+    pct_buf hole_scan;              // HoleSum (gaps + 1): loops, loop vertices and patch triangles before every gap
+    pct_buf hole_loop;              // the owned loops packed: int64 offsets (loops + 1) | int32 vertices | uint8 status
+    pct_buf hole_tri, hole_alt;     // int32 (patches, 3) ascending; the sort's other buffer
+    pct_buf hole_filled;            // int32 (triangles + patches, 3) ascending
+    pct_buf hole_tmp;               // scan, sort and merge scratch
+    int64_t hole_loops = 0, hole_loop_verts = 0, hole_patches = 0;
+    int64_t hole_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double hole_ms = 0;
 };
 
 int pct_fail(pct_ctx* ctx, int code, const char* fmt, ...);
@@ -556,6 +575,10 @@ int pct_run_orient(pct_ctx* ctx, int anchor, const double* viewpoint, int max_co
 // and the natural neighbours of public rows [first, first + rows) as CSR (d_count: rows + 1 words of scratch)
 int pct_launch_point_triangles(pct_ctx* ctx, bool wind_frames, hipEvent_t mid);
 int pct_launch_point_fans(pct_ctx* ctx, int64_t first, int64_t rows, int64_t* d_count, int64_t* d_off, int* d_nbr);
+// pct_hole.hip: gaps, loops, patches and the filled array of the resident fans and triangles; waits for the stream three
+// times (the gap count, the loop and patch counts, the end) and leaves ctx->hole_loops / hole_loop_verts / hole_patches and
+// stats8 = {boundary edges, gaps, odd gaps, loops, filled, left for the perimeter, blocked, patch triangles}
+int pct_launch_fill_holes(pct_ctx* ctx, int max_vertices, double max_perimeter, int64_t stats8[8]);
 int pct_voxel_downsample_device(pct_ctx* ctx, const void* d_xyz, bool f64, int64_t n, double voxel, int64_t* d_out, int64_t* count);
 int pct_launch_surface_variation(pct_ctx* ctx, float* d_out);
 // PCA principal curvatures (pct_pca.hip).  The sweep fetches up to PCT_PCA_EXTRA candidates beyond k per point, re-ranked

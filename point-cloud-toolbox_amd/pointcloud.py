@@ -547,6 +547,33 @@ class PointCloud:
         self._faces_token = self._plant_token
         return self.faces
 
+    def fill_surface_holes(self, max_vertices=32, max_perimeter=None, update_faces=True):
+        """Close the small gaps ``compute_surface_triangles`` leaves, without leaving the device (``pct_fill_holes``,
+        include/pct_hip_holes.h): the boundary loops of the faces are read off the fans, and every loop of at most
+        ``max_vertices`` (3 .. 32) vertices whose perimeter is below ``max_perimeter`` gets the triangulation of least total
+        squared area -- the step behind ball pivoting in the reference's pipeline (utils:150-206).  ``max_perimeter=None``:
+        half the mean extent of the bounding box (utils:173, utils:338-339); ``float("inf")``: no cap.  Computes the faces
+        first where they are missing.  Sets ``hole_faces`` (P, 3) int32, ``boundary_loops`` ((loops + 1,) int64 offsets,
+        int32 vertices in canonical order, uint8 status: 0 filled, 1 left for its perimeter, 2 blocked) and
+        ``last_hole_stats``; with ``update_faces`` also ``faces``, to the filled array, which the PLY export and
+        ``compute_mesh_energies`` then read.  A later ``compute_surface_triangles`` restores the unfilled faces.
+        Returns the filled array."""
+        h = self._planted_table()
+        if getattr(self, "faces", None) is None or self._faces_token != self._plant_token or h.point_triangle_stats()["rows"] == 0:
+            self.compute_surface_triangles()
+        if max_perimeter is None:
+            p = np.asarray(self.points, np.float64)
+            ext = p.max(0) - p.min(0)
+            max_perimeter = 0.5 * (((ext[0] + ext[1]) + ext[2]) / 3.0)
+        h.fill_holes(max_vertices, max_perimeter)
+        self.last_hole_stats = h.fill_hole_stats()
+        self.hole_faces = h.get_hole_triangles(0, self.last_hole_stats["patch_triangles"])
+        self.boundary_loops = h.get_boundary_loops()
+        filled = h.get_filled_triangles(0, self.last_triangle_stats["triangles"] + self.last_hole_stats["patch_triangles"])
+        if update_faces:
+            self.faces = filled
+        return filled
+
     def compute_mesh_energies(self):
         """``(bending, stretching, area)`` over ``faces`` (utils.py:702-765 on this cloud's own triangles): the cloud,
         ``faces``, ``K_quadratic`` and ``H_quadratic`` through ``pct_mesh_energies``.  Computes the faces and the
