@@ -60,14 +60,14 @@ typedef struct pct_timings {
     float export_ms;          /* sorted-space -> public index translation               */
     float total_ms;           /* the stages above, first to last (device clock stamps or events) */
     int32_t knn_launches;
-    int32_t grid_iters;       /* cell-size refinement passes                            */
+    int32_t grid_iters;       /* builds of the cell-size search, plus the passes that trimmed the grid box to 6 sigma */
     int64_t cells;            /* grid cells                                             */
     int64_t occupied_cells;   /* work items of the sweep (cells split into query chunks) */
-    int64_t ring_fallbacks;   /* queries that needed more than the 27-cell stencil      */
-    int64_t lds_overflows;    /* cells whose stencil exceeded the LDS staging capacity  */
+    int64_t ring_fallbacks;   /* rows the exact sweep answered beyond the 27-cell stencil (of the rows it ran over) */
+    int64_t lds_overflows;    /* work items whose stencil exceeded the LDS staging capacity (handed over whole) */
     int64_t flushes;          /* wave-wide sort/merge passes of the sweep               */
     int64_t candidate_steps;  /* 64-candidate distance steps of the sweep               */
-    int64_t redone_queries;   /* queries re-done by the exact sweep (float-key collisions) */
+    int64_t redone_queries;   /* queries re-done by the exact sweep (overflowing items, rows the stencil cannot vouch for, float-key collisions) */
     double cell_size;
     int64_t grid_points;      /* points held by the cell list: the cloud, or (sharded handles) the part of it
                                  near the owned range                                    */

@@ -20,6 +20,7 @@ struct EdgeSearch {
     int max_iter;
     // state
     double emax = 1.0;             // longest extent (1 for a point)
+    bool no_extent = false;        // the box is a point: one cell at every edge, no step changes the occupancy
     double first_guess = 0;        // this cloud's own first guess, before the warm start and the clamps
     bool hinted = false;           // the first edge came from the previous cloud on this handle
     double a_prev = 0, m_prev = 0, d_last = 2.0;
@@ -30,7 +31,8 @@ struct EdgeSearch {
 
     double first() {
         emax = fmax(ex, fmax(ey, ez));
-        if (!(emax > 0)) emax = 1.0;
+        no_extent = !(emax > 0);
+        if (no_extent) emax = 1.0;
         // first guess: the cloud is a surface whose area is about the bbox's half-surface * 1.2
         double area = 1.2 * (ex * ey + ey * ez + ex * ez);
         if (!(area > 0)) area = emax * emax;
@@ -62,7 +64,8 @@ struct EdgeSearch {
         const bool eps_bound = eps > 0 && a >= eps;            // cannot grow past eps
         const bool capped = ncell * 2 > cell_cap && m < target;
         return (m >= kWinLo * target && m <= kWinHi * target) || it == max_iter - 1 || (eps_bound && m < target) ||
-               capped || (a >= emax && m < target) || (hit_cap && m > target);      // (cannot refine past the cell budget)
+               capped || (a >= emax && m < target) || (hit_cap && m > target) ||      // (cannot refine past the cell budget)
+               no_extent;             // (identical points: the same one-cell grid whatever the edge)
     }
 
     // secant step on the measured dimension d (m ~ a^d; 2 for a surface, until two passes have measured it)

@@ -84,6 +84,9 @@ int main() {
         printf("window_lo_%g %d\n", target, (int)box.accept(0.89 * target, 0.5, 1, cap, false, 0));
         printf("window_hi_%g %d\n", target, (int)box.accept(1.13 * target, 0.5, 1, cap, false, 0));
         printf("hint_after_%g %.17g\n", target, box.hint_after(0.05, 30.0));
+        const EdgeSearch point = search(target, 0, 0);        // a box without extent: emax = 1 stands in
+        printf("point_%g %d\n", target, (int)point.accept(100 * target, 0.5, 1, cap, false, 0));
+        printf("point_emax_%g %.17g\n", target, point.emax);
     }
     warm("r075", 0.75, 27, 0);
     warm("r15_other_target", 1.5, 29.5, 0);
@@ -175,6 +178,9 @@ def test_accept_conditions(out, t):
     assert out[f"last_pass_{t}"] == 1 and out[f"not_last_pass_{t}"] == 0         # it == max_iter - 1, whatever m
     assert out[f"window_lo_{t}"] == 1 and out[f"window_hi_{t}"] == 0             # 0.88 .. 1.12 of target
     assert close(out[f"hint_after_{t}"], 0.05 * math.sqrt(float(t) / 30.0))      # no step taken: d = 2
+    # a box without extent is one cell at every edge: the first pass is the last, whatever it measured (not_last_pass above
+    # is the same call on a box with an extent)
+    assert out[f"point_{t}"] == 1 and out[f"point_emax_{t}"] == 1.0
 
 
 def test_warm_start(out):
