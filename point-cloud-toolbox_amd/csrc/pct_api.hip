@@ -78,6 +78,12 @@ int pct_reserve_fit(pct_ctx* ctx, int64_t rows) {
 
 static float ev_ms(pct_ctx* ctx, int a, int b) { return pct_event_ms(ctx->ev[a], ctx->ev[b]); }
 
+// what a statistics getter answers: the numbers stored with the result while it is in place, zeros otherwise
+template <typename T>
+static void stats_or_zero(bool live, const T* src, int n, T* out) {
+    for (int i = 0; i < n; ++i) out[i] = live ? src[i] : T(0);
+}
+
 // the statistics a sweep left, as the timings report them
 static void read_sweep_stats(const pct_sweep_words& w, pct_timings* t) {
     t->ring_fallbacks = (int64_t)w.ring_fallbacks;
@@ -411,7 +417,7 @@ __global__ __launch_bounds__(256) void k_scatter_records(const float* __restrict
 
 int pct_slab_records(pct_ctx* ctx, float* dev_records, int64_t capacity_rows, int64_t* rows_out) {
     PCT_TRY(begin_call(ctx));
-    if (ctx->slab_parts < 1 || !ctx->slab_split_valid || !ctx->res.has(PCT_R_FIT) || !ctx->knn_sorted_space || !ctx->fit_row_order)
+    if (ctx->slab_parts < 1 || !ctx->slab_split_valid || !ctx->res.has(PCT_R_FIT) || !ctx->knn_sorted_space || !ctx->res.in_row_order(PCT_R_FIT))
         return pct_fail(ctx, PCT_ERR_INVALID, "pct_slab_records: no slab pass on this handle (pct_set_query_slab, pct_curvature)");
     const int64_t rows = ctx->q_end - ctx->q_begin;
     if (rows_out) *rows_out = rows;
@@ -462,7 +468,7 @@ struct SweepDone { bool rows_fitted = false; };     // the passes of a chained s
 // a sweep has left its table; hier: from the hierarchical list or the chain of cell lists
 static void table_left(pct_ctx* ctx, bool hier) {
     ctx->knn_hier = hier;
-    ctx->res.leave(PCT_R_TABLE, ctx->knn_sorted_space);
+    ctx->res.leave(PCT_R_TABLE, ctx->knn_sorted_space, ctx->q_end - ctx->q_begin);
 }
 static bool tree_table_resident(const pct_ctx* ctx) { return ctx->res.has(PCT_R_TABLE) && ctx->knn_hier; }
 
@@ -604,11 +610,13 @@ static int run_knn(pct_ctx* ctx, int32_t k, double eps, int32_t asked, pct_call_
 // rows), the call's end on its clock, and the sweep's statistics words into the pinned slot of the clock's parity,
 // mirrored by the fit kernel, else copied.
 // (the fit stage has no boundary of its own: it starts where the sweep ends)
-static int fused_call(pct_ctx* ctx, int32_t k, double eps, int32_t algo, pct_call_clock& clock) {
+// *fit_by_row: the order the fit results are stored in, for the caller's fit_left
+static int fused_call(pct_ctx* ctx, int32_t k, double eps, int32_t algo, pct_call_clock& clock, bool* fit_by_row) {
     SweepDone swept;
     PCT_TRY(run_knn(ctx, k, eps, algo, clock, PCT_CALL_FUSED, &swept));
     bool mirrored = false;
-    if (!swept.rows_fitted) PCT_TRY(pct_launch_fit_table(ctx, FitSlot{clock.par, true, &clock}, &mirrored));
+    *fit_by_row = false;          // (the passes fitted their rows: public order)
+    if (!swept.rows_fitted) PCT_TRY(pct_launch_fit_table(ctx, FitSlot{clock.par, true, &clock}, &mirrored, fit_by_row));
     PCT_HIP(ctx, clock.end(ctx->stream));
     if (!mirrored)                // (no fit kernel ran: the chained sweep fitted its passes itself, or there are no rows)
         PCT_HIP(ctx, hipMemcpyAsync(&ctx->pin->stats[clock.par],ctx->counters.p, sizeof(pct_sweep_words), hipMemcpyDeviceToHost, ctx->stream));
@@ -651,13 +659,11 @@ int pct_knn(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
     return PCT_OK;
 }
 
-// The end of every fit: results for `rows` rows -- cloud-aligned (rows [q_begin, q_end), in the order their launcher stored
+// The end of every fit: results for `rows` rows -- cloud-aligned (rows [q_begin, q_end), by_row: as their launcher stored
 // them) or the rows of the call in the call's order.  They replace the fit before them and whatever was made from it.
-static int fit_left(pct_ctx* ctx, int64_t rows, bool cloud_aligned) {
-    ctx->fit_rows = rows;
+static int fit_left(pct_ctx* ctx, int64_t rows, bool cloud_aligned, bool by_row) {
     ctx->fit_cloud_aligned = cloud_aligned;
-    if (!cloud_aligned) ctx->fit_row_order = false;
-    ctx->res.leave(PCT_R_FIT, ctx->fit_row_order);
+    ctx->res.leave(PCT_R_FIT, by_row, rows);
     return PCT_OK;
 }
 
@@ -665,12 +671,13 @@ int pct_fit(pct_ctx* ctx) {
     PCT_TRY(begin_row_call(ctx, "pct_fit"));
     if (!ctx->res.has(PCT_R_TABLE)) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "plant the neighbour table first (pct_knn)");
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_BEGIN], ctx->stream));
-    PCT_TRY(pct_launch_fit_table(ctx, FitSlot{0, false, nullptr}, nullptr));
+    bool by_row = false;
+    PCT_TRY(pct_launch_fit_table(ctx, FitSlot{0, false, nullptr}, nullptr, &by_row));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_END], ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->tm.fit_ms = ev_ms(ctx, PCT_EV_FIT_BEGIN, PCT_EV_FIT_END);
     ctx->tm.fit_svd_rows = ctx->pin->svd_rows[0];
-    return fit_left(ctx, ctx->q_end - ctx->q_begin, true);
+    return fit_left(ctx, ctx->q_end - ctx->q_begin, true, by_row);
 }
 
 int pct_set_async(pct_ctx* ctx, int32_t enable) {
@@ -687,7 +694,8 @@ static int curvature_async(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
     const int par = pct_next_parity(had, ctx->pend.par);        // (the pending call keeps its clock and its pinned slots)
     pct_call_clock& clock = ctx->clock[par];
     ctx->retries = 0;
-    const int st = fused_call(ctx, k, eps, algo, clock);
+    bool fit_by_row = false;
+    const int st = fused_call(ctx, k, eps, algo, clock, &fit_by_row);
     if (st != PCT_OK) {            // leave the handle in the plain state: nothing pending
         (void)hipStreamSynchronize(ctx->stream);
         if (had) finish_pending(ctx);
@@ -705,7 +713,7 @@ static int curvature_async(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
     ctx->pend.par = par;
     ctx->pend.sorted = ctx->knn_sorted_space;
     ctx->pend.on = true;
-    return fit_left(ctx, ctx->q_end - ctx->q_begin, true);
+    return fit_left(ctx, ctx->q_end - ctx->q_begin, true, fit_by_row);
 }
 
 int pct_curvature(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
@@ -715,16 +723,17 @@ int pct_curvature(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
                        !ctx->collect_stats;
     PCT_TRY(begin_call(ctx, !async));
     if (async) return curvature_async(ctx, k, eps, algo);
+    bool fit_by_row = false;
     for (int attempt = 0; attempt < 2; ++attempt) {
         bool again = false;
-        PCT_TRY(fused_call(ctx, k, eps, algo, ctx->clock[0]));
+        PCT_TRY(fused_call(ctx, k, eps, algo, ctx->clock[0], &fit_by_row));
         PCT_TRY(finish_knn_stats(ctx, ctx->clock[0], true, &again));
         if (!again) break;
         retry_without_cull(ctx);
     }
     ctx->tm.fit_svd_rows = ctx->pin->svd_rows[0];
     ctx->tm_done = ctx->tm;
-    return fit_left(ctx, ctx->q_end - ctx->q_begin, true);
+    return fit_left(ctx, ctx->q_end - ctx->q_begin, true, fit_by_row);
 }
 
 int pct_get_neighbors(pct_ctx* ctx, int64_t begin, int64_t end, int32_t* idx, float* dist, int32_t* count) {
@@ -826,7 +835,7 @@ int pct_fit_indices(pct_ctx* ctx, const int32_t* idx, const int32_t* count, cons
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->tm.fit_ms = ev_ms(ctx, PCT_EV_FIT_BEGIN, PCT_EV_FIT_END);
     ctx->tm.fit_svd_rows = ctx->pin->svd_rows[0];
-    return fit_left(ctx, rows, false);         // (a resident neighbour table is untouched and stays valid)
+    return fit_left(ctx, rows, false, false);         // (a resident neighbour table is untouched and stays valid)
 }
 
 int pct_fit_indices_f64(pct_ctx* ctx, const int32_t* idx, const int32_t* count, const int64_t* query, int64_t rows, int32_t k,
@@ -973,16 +982,16 @@ int pct_query_ball(pct_ctx* ctx, const double* q_xyz, int64_t m, const double* r
     }
     if (flags & PCT_BALL_COUNT_ONLY) return PCT_OK;        // (nothing is kept)
     ctx->ball_has_dist = (flags & PCT_BALL_DISTANCES) != 0;
-    ctx->ball_m = m;
-    ctx->res.leave(PCT_R_BALL, false);
+    ctx->res.leave(PCT_R_BALL, false, m);
     return PCT_OK;
 }
 
 int pct_get_ball(pct_ctx* ctx, int64_t row_begin, int64_t row_end, int32_t* idx, double* dist) {
     PCT_TRY(begin_call(ctx));
     if (!ctx->res.has(PCT_R_BALL)) return pct_fail(ctx, PCT_ERR_INVALID, "no ball rows on this handle (pct_query_ball)");
-    if (row_begin < 0 || row_end > ctx->ball_m || row_begin > row_end)
-        return pct_fail(ctx, PCT_ERR_INVALID, "bad row range [%lld,%lld) of %lld", (long long)row_begin, (long long)row_end, (long long)ctx->ball_m);
+    const int64_t have = ctx->res.rows_of(PCT_R_BALL);
+    if (row_begin < 0 || row_end > have || row_begin > row_end)
+        return pct_fail(ctx, PCT_ERR_INVALID, "bad row range [%lld,%lld) of %lld", (long long)row_begin, (long long)row_end, (long long)have);
     if (dist && !ctx->ball_has_dist) return pct_fail(ctx, PCT_ERR_INVALID, "pct_get_ball: no distances were asked for (PCT_BALL_DISTANCES)");
     if (row_begin == row_end) return PCT_OK;
     int64_t ends[2] = {0, 0};
@@ -1004,14 +1013,15 @@ int pct_get_ball(pct_ctx* ctx, int64_t row_begin, int64_t row_end, int32_t* idx,
 int pct_fit_ball(pct_ctx* ctx, const int64_t* self_rows, int64_t m, int32_t* used) {
     PCT_TRY(begin_row_call(ctx, "pct_fit_ball"));
     if (!ctx->res.has(PCT_R_BALL)) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "pct_fit_ball: no ball rows on this handle (pct_query_ball)");
-    if (m != ctx->ball_m) return pct_fail(ctx, PCT_ERR_INVALID, "pct_fit_ball: %lld centres for the %lld rows of the last query", (long long)m, (long long)ctx->ball_m);
+    if (m != ctx->res.rows_of(PCT_R_BALL))
+        return pct_fail(ctx, PCT_ERR_INVALID, "pct_fit_ball: %lld centres for the %lld rows of the last query", (long long)m, (long long)ctx->res.rows_of(PCT_R_BALL));
     if (m > 0 && !self_rows) return pct_fail(ctx, PCT_ERR_INVALID, "pct_fit_ball: null centres");
     for (int64_t i = 0; i < m; ++i)
         if (self_rows[i] < 0 || self_rows[i] >= ctx->n)
             return pct_fail(ctx, PCT_ERR_INVALID, "pct_fit_ball: row %lld: centre %lld outside the cloud", (long long)i, (long long)self_rows[i]);
     ctx->tm.fit_ms = 0;
     ctx->tm.fit_svd_rows = 0;
-    if (m == 0) return fit_left(ctx, 0, false);
+    if (m == 0) return fit_left(ctx, 0, false, false);
     ctx->res.drop(pct_replacing(PCT_R_FIT));   // accepted: the fit before this one is gone, the new one is there once the kernels have run
     PCT_TRY(pct_reserve_fit(ctx, m));
     PCT_TRY(pct_reserve(ctx, &ctx->stage_c, (size_t)m * sizeof(int)));
@@ -1031,7 +1041,7 @@ int pct_fit_ball(pct_ctx* ctx, const int64_t* self_rows, int64_t m, int32_t* use
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->tm.fit_ms = ev_ms(ctx, PCT_EV_FIT_BEGIN, PCT_EV_FIT_END);
     ctx->tm.fit_svd_rows = ctx->pin->svd_rows[0];
-    return fit_left(ctx, m, false);
+    return fit_left(ctx, m, false, false);
 }
 
 int pct_ball_stats(pct_ctx* ctx, int64_t out[4]) {
@@ -1040,39 +1050,40 @@ int pct_ball_stats(pct_ctx* ctx, int64_t out[4]) {
     return PCT_OK;
 }
 
+// ---- what the row getters, the statistics getters and the calls that build on a resident share ---------------------------
+// the range error of a row getter: rows [begin, end) within the rows r covers, which start at base; what: "the owned range", ...
+static int check_owned_span(pct_ctx* ctx, const char* what, pct_resident r, int64_t begin, int64_t end, int64_t base) {
+    if (begin < base || end > base + ctx->res.rows_of(r) || begin > end)
+        return pct_fail(ctx, PCT_ERR_INVALID, "rows [%lld,%lld) outside %s", (long long)begin, (long long)end, what);
+    return PCT_OK;
+}
+
+// rows [first, first + rows) of r's columns to the caller: through row_of where r is stored in table-row order (row_of
+// outlives the table, PCT_TABLE_LOST: whatever rewrites the cell order drops r, and query_state keeps a query's build away)
+static int get_rows(pct_ctx* ctx, pct_resident r, const pct_column* cols, int ncol, int64_t first, int64_t rows) {
+    if (rows == 0) return PCT_OK;
+    const int* map = nullptr;
+    if (ctx->res.in_row_order(r)) {
+        PCT_TRY(pct_ensure_row_of(ctx));
+        map = (const int*)ctx->row_of.p;
+    }
+    return pct_download_columns(ctx, cols, ncol, first, rows, map);
+}
+
+// r is in place for every owned row (the fit: the cloud-aligned one), else PCT_ERR_INVALID with `missing`
+static int need_for_owned_rows(pct_ctx* ctx, pct_resident r, const char* missing) {
+    if (ctx->res.covers(r, ctx->q_end - ctx->q_begin) && (r != PCT_R_FIT || ctx->fit_cloud_aligned)) return PCT_OK;
+    return pct_fail(ctx, PCT_ERR_INVALID, "%s", missing);
+}
+
 int pct_get_fit(pct_ctx* ctx, int64_t begin, int64_t end, float* coefs, float* K, float* H, float* H2) {
     PCT_TRY(begin_row_call(ctx, "pct_get_fit"));
     if (!ctx->res.has(PCT_R_FIT)) return pct_fail(ctx, PCT_ERR_INVALID, "no fit results");
     const int64_t base = ctx->fit_cloud_aligned ? ctx->q_begin : 0;   // cloud-aligned vs row-aligned results
-    if (begin < base || end > base + ctx->fit_rows || begin > end)
-        return pct_fail(ctx, PCT_ERR_INVALID, "rows [%lld,%lld) outside the fitted range", (long long)begin, (long long)end);
-    const int64_t rows = end - begin, off = begin - base;
-    if (rows == 0) return PCT_OK;
-    if (ctx->fit_row_order) {          // results live in table-row order: gather the requested public rows first
-        float *d_c = nullptr, *d_s = nullptr;
-        if (coefs) { PCT_TRY(pct_reserve(ctx, &ctx->stage_a, (size_t)rows * 6 * sizeof(float))); d_c = (float*)ctx->stage_a.p; }
-        PCT_TRY(pct_reserve(ctx, &ctx->stage_b, (size_t)rows * 3 * sizeof(float)));
-        d_s = (float*)ctx->stage_b.p;
-        PCT_TRY(pct_launch_gather_fit(ctx, off, rows, d_c, K ? d_s : nullptr, H ? d_s + rows : nullptr, H2 ? d_s + 2 * rows : nullptr));
-        if (coefs) PCT_HIP(ctx, hipMemcpyAsync(coefs, d_c, (size_t)rows * 6 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        // the three arrays lie back to back on the device; where the caller's do too, one copy moves the run
-        float* host[3] = {K, H, H2};
-        for (int i = 0; i < 3;) {
-            if (!host[i]) { ++i; continue; }
-            int j = i + 1;
-            while (j < 3 && host[j] == host[j - 1] + rows) ++j;
-            PCT_HIP(ctx, hipMemcpyAsync(host[i], d_s + (size_t)i * rows, (size_t)(j - i) * rows * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-            i = j;
-        }
-        PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return PCT_OK;
-    }
-    if (coefs) PCT_HIP(ctx, hipMemcpyAsync(coefs, (float*)ctx->coefs.p + off * 6, (size_t)rows * 6 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (K) PCT_HIP(ctx, hipMemcpyAsync(K, (float*)ctx->K.p + off, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (H) PCT_HIP(ctx, hipMemcpyAsync(H, (float*)ctx->H.p + off, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (H2) PCT_HIP(ctx, hipMemcpyAsync(H2, (float*)ctx->H2.p + off, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PCT_OK;
+    PCT_TRY(check_owned_span(ctx, "the fitted range", PCT_R_FIT, begin, end, base));
+    const pct_column cols[] = {{ctx->coefs.p, 6 * sizeof(float), coefs}, {ctx->K.p, sizeof(float), K}, {ctx->H.p, sizeof(float), H},
+                               {ctx->H2.p, sizeof(float), H2}};
+    return get_rows(ctx, PCT_R_FIT, cols, 4, begin - base, end - begin);
 }
 
 // ---- per-point tangent-plane Voronoi areas and the energies over them (pct_area.hip) --------------------------------------
@@ -1081,68 +1092,47 @@ int pct_point_areas(pct_ctx* ctx) {
     if (!ctx->res.has(PCT_R_TABLE)) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "plant the neighbour table first (pct_knn)");
     ctx->res.drop(pct_replacing(PCT_R_AREAS));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_AREA_BEGIN], ctx->stream));
-    PCT_TRY(pct_launch_point_areas(ctx));
+    bool by_row = false;
+    PCT_TRY(pct_launch_point_areas(ctx, &by_row));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_AREA_END], ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));              // the call's one wait: results, statistics words, events
     const unsigned long long* w = ctx->pin->area_words;
-    ctx->area_rows = ctx->q_end - ctx->q_begin;
-    ctx->area_stats[0] = ctx->area_rows;
+    const int64_t rows = ctx->q_end - ctx->q_begin;
+    ctx->area_stats[0] = rows;
     ctx->area_stats[1] = (int64_t)w[1];
     ctx->area_stats[2] = (int64_t)w[2];
     ctx->area_stats[3] = (int64_t)w[0];
     ctx->area_profile[0] = ev_ms(ctx, PCT_EV_AREA_BEGIN, PCT_EV_AREA_END);
     ctx->area_profile[1] = (double)w[3];
-    ctx->res.leave(PCT_R_AREAS, ctx->area_row_order);
+    ctx->res.leave(PCT_R_AREAS, by_row, rows);
     return PCT_OK;
 }
 
-// areas in table-row order are gathered through row_of, which outlives the table (PCT_TABLE_LOST) exactly as the fit's:
-// whatever rewrites the cell order drops the areas, and query_state keeps a query's build away
 int pct_get_point_areas(pct_ctx* ctx, int64_t begin, int64_t end, double* area, uint8_t* closed, int32_t* nverts) {
     PCT_TRY(begin_row_call(ctx, "pct_get_point_areas"));
     if (!ctx->res.has(PCT_R_AREAS)) return pct_fail(ctx, PCT_ERR_INVALID, "no point areas (pct_point_areas)");
-    if (begin < ctx->q_begin || end > ctx->q_begin + ctx->area_rows || begin > end)
-        return pct_fail(ctx, PCT_ERR_INVALID, "rows [%lld,%lld) outside the owned range", (long long)begin, (long long)end);
-    const int64_t rows = end - begin, off = begin - ctx->q_begin;
-    if (rows == 0) return PCT_OK;
-    const double* d_a = (const double*)ctx->area.p + off;
-    const unsigned char* d_c = (const unsigned char*)ctx->area_closed.p + off;
-    const int* d_n = (const int*)ctx->area_nverts.p + off;
-    if (ctx->area_row_order) {          // table-row order: gather the requested public rows first
-        PCT_TRY(pct_reserve(ctx, &ctx->stage_a, (size_t)rows * sizeof(double)));
-        PCT_TRY(pct_reserve(ctx, &ctx->stage_b, (size_t)rows * sizeof(int)));
-        PCT_TRY(pct_reserve(ctx, &ctx->stage_c, (size_t)rows));
-        PCT_TRY(pct_launch_gather_areas(ctx, off, rows, area ? (double*)ctx->stage_a.p : nullptr, closed ? (unsigned char*)ctx->stage_c.p : nullptr,
-                                        nverts ? (int*)ctx->stage_b.p : nullptr));
-        d_a = (const double*)ctx->stage_a.p;
-        d_n = (const int*)ctx->stage_b.p;
-        d_c = (const unsigned char*)ctx->stage_c.p;
-    }
-    if (area) PCT_HIP(ctx, hipMemcpyAsync(area, d_a, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (closed) PCT_HIP(ctx, hipMemcpyAsync(closed, d_c, (size_t)rows, hipMemcpyDeviceToHost, ctx->stream));
-    if (nverts) PCT_HIP(ctx, hipMemcpyAsync(nverts, d_n, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PCT_OK;
+    PCT_TRY(check_owned_span(ctx, "the owned range", PCT_R_AREAS, begin, end, ctx->q_begin));
+    const pct_column cols[] = {{ctx->area.p, sizeof(double), area}, {ctx->area_closed.p, 1, closed}, {ctx->area_nverts.p, sizeof(int), nverts}};
+    return get_rows(ctx, PCT_R_AREAS, cols, 3, begin - ctx->q_begin, end - begin);
 }
 
 int pct_point_area_stats(pct_ctx* ctx, int64_t out[4]) {
     if (!ctx || !out) return PCT_ERR_INVALID;
-    for (int i = 0; i < 4; ++i) out[i] = ctx->res.has(PCT_R_AREAS) ? ctx->area_stats[i] : 0;
+    stats_or_zero(ctx->res.has(PCT_R_AREAS), ctx->area_stats, 4, out);
     return PCT_OK;
 }
 
 int pct_point_area_profile(pct_ctx* ctx, double out[2]) {
     if (!ctx || !out) return PCT_ERR_INVALID;
-    for (int i = 0; i < 2; ++i) out[i] = ctx->res.has(PCT_R_AREAS) ? ctx->area_profile[i] : 0.0;
+    stats_or_zero(ctx->res.has(PCT_R_AREAS), ctx->area_profile, 2, out);
     return PCT_OK;
 }
 
 int pct_point_energies(pct_ctx* ctx, int32_t closed_only, double out[4]) {
     PCT_TRY(begin_row_call(ctx, "pct_point_energies"));
     if (!out) return pct_fail(ctx, PCT_ERR_INVALID, "null result");
-    const int64_t rows = ctx->q_end - ctx->q_begin;
-    if (!ctx->res.has(PCT_R_FIT) || !ctx->fit_cloud_aligned || ctx->fit_rows != rows) return pct_fail(ctx, PCT_ERR_INVALID, "no fit results");
-    if (!ctx->res.has(PCT_R_AREAS) || ctx->area_rows != rows) return pct_fail(ctx, PCT_ERR_INVALID, "no point areas (pct_point_areas)");
+    PCT_TRY(need_for_owned_rows(ctx, PCT_R_FIT, "no fit results"));
+    PCT_TRY(need_for_owned_rows(ctx, PCT_R_AREAS, "no point areas (pct_point_areas)"));
     const int nblk = 1024;
     PCT_TRY(pct_reserve(ctx, &ctx->stage_d, ((size_t)nblk * 4 + 4) * sizeof(double)));
     double* d_part = (double*)ctx->stage_d.p;
@@ -1156,60 +1146,39 @@ int pct_point_energies(pct_ctx* ctx, int32_t closed_only, double out[4]) {
 int pct_point_frames(pct_ctx* ctx, const double* viewpoint) {
     PCT_TRY(begin_row_call(ctx, "pct_point_frames"));
     if (!ctx->res.has(PCT_R_TABLE)) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "plant the neighbour table first (pct_knn)");
-    const int64_t rows = ctx->q_end - ctx->q_begin;
-    if (!ctx->res.has(PCT_R_FIT) || !ctx->fit_cloud_aligned || ctx->fit_rows != rows) return pct_fail(ctx, PCT_ERR_INVALID, "no fit results");
+    PCT_TRY(need_for_owned_rows(ctx, PCT_R_FIT, "no fit results"));
     if (viewpoint && !(isfinite(viewpoint[0]) && isfinite(viewpoint[1]) && isfinite(viewpoint[2])))
         return pct_fail(ctx, PCT_ERR_INVALID, "pct_point_frames: the viewpoint is not finite");
     ctx->res.drop(pct_replacing(PCT_R_FRAMES));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FRAME_BEGIN], ctx->stream));
-    PCT_TRY(pct_launch_point_frames(ctx, viewpoint));
+    bool by_row = false;
+    PCT_TRY(pct_launch_point_frames(ctx, viewpoint, &by_row));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FRAME_END], ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));              // the call's one wait: results, statistics words, events
     const unsigned long long* w = ctx->pin->frame_words;
-    ctx->frame_rows = rows;
+    const int64_t rows = ctx->q_end - ctx->q_begin;
     ctx->frame_stats[0] = rows;
     for (int i = 0; i < 3; ++i) ctx->frame_stats[1 + i] = (int64_t)w[i];
     ctx->frame_ms = ev_ms(ctx, PCT_EV_FRAME_BEGIN, PCT_EV_FRAME_END);
-    ctx->res.leave(PCT_R_FRAMES, ctx->frame_row_order);
+    ctx->res.leave(PCT_R_FRAMES, by_row, rows);
     return PCT_OK;
 }
 
-// frames in table-row order: as the areas
 int pct_get_point_frames(pct_ctx* ctx, int64_t begin, int64_t end, double* normal, double* k12, double* dirs, uint8_t* flipped) {
     PCT_TRY(begin_row_call(ctx, "pct_get_point_frames"));
     if (!ctx->res.has(PCT_R_FRAMES)) return pct_fail(ctx, PCT_ERR_INVALID, "no point frames (pct_point_frames)");
-    if (begin < ctx->q_begin || end > ctx->q_begin + ctx->frame_rows || begin > end)
-        return pct_fail(ctx, PCT_ERR_INVALID, "rows [%lld,%lld) outside the owned range", (long long)begin, (long long)end);
-    const int64_t rows = end - begin, off = begin - ctx->q_begin, all = ctx->frame_rows;
-    if (rows == 0) return PCT_OK;
-    const double* d_n = (const double*)ctx->frame.p + off * 3;
-    const double* d_k = (const double*)ctx->frame.p + all * 3 + off * 2;
-    const double* d_d = (const double*)ctx->frame.p + all * 5 + off * 6;
-    const unsigned char* d_f = (const unsigned char*)ctx->frame_flip.p + 64 + off;
-    if (ctx->frame_row_order) {         // table-row order: gather the requested public rows first
-        PCT_TRY(pct_reserve(ctx, &ctx->stage_a, (size_t)rows * 3 * sizeof(double)));
-        PCT_TRY(pct_reserve(ctx, &ctx->stage_b, (size_t)rows * 2 * sizeof(double)));
-        PCT_TRY(pct_reserve(ctx, &ctx->stage_d, (size_t)rows * 6 * sizeof(double)));
-        PCT_TRY(pct_reserve(ctx, &ctx->stage_c, (size_t)rows));
-        PCT_TRY(pct_launch_gather_frames(ctx, off, rows, normal ? (double*)ctx->stage_a.p : nullptr, k12 ? (double*)ctx->stage_b.p : nullptr,
-                                         dirs ? (double*)ctx->stage_d.p : nullptr, flipped ? (unsigned char*)ctx->stage_c.p : nullptr));
-        d_n = (const double*)ctx->stage_a.p;
-        d_k = (const double*)ctx->stage_b.p;
-        d_d = (const double*)ctx->stage_d.p;
-        d_f = (const unsigned char*)ctx->stage_c.p;
-    }
-    if (normal) PCT_HIP(ctx, hipMemcpyAsync(normal, d_n, (size_t)rows * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (k12) PCT_HIP(ctx, hipMemcpyAsync(k12, d_k, (size_t)rows * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (dirs) PCT_HIP(ctx, hipMemcpyAsync(dirs, d_d, (size_t)rows * 6 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (flipped) PCT_HIP(ctx, hipMemcpyAsync(flipped, d_f, (size_t)rows, hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PCT_OK;
+    PCT_TRY(check_owned_span(ctx, "the owned range", PCT_R_FRAMES, begin, end, ctx->q_begin));
+    const int64_t all = ctx->res.rows_of(PCT_R_FRAMES);
+    const double* f = (const double*)ctx->frame.p;
+    const pct_column cols[] = {{f, 3 * sizeof(double), normal}, {f + all * 3, 2 * sizeof(double), k12}, {f + all * 5, 6 * sizeof(double), dirs},
+                               {(const unsigned char*)ctx->frame_flip.p + 64, 1, flipped}};
+    return get_rows(ctx, PCT_R_FRAMES, cols, 4, begin - ctx->q_begin, end - begin);
 }
 
 int pct_point_frame_stats(pct_ctx* ctx, int64_t out[4], double* ms) {
     if (!ctx || !out) return PCT_ERR_INVALID;
-    for (int i = 0; i < 4; ++i) out[i] = ctx->res.has(PCT_R_FRAMES) ? ctx->frame_stats[i] : 0;
-    if (ms) *ms = ctx->res.has(PCT_R_FRAMES) ? ctx->frame_ms : 0.0;
+    stats_or_zero(ctx->res.has(PCT_R_FRAMES), ctx->frame_stats, 4, out);
+    if (ms) stats_or_zero(ctx->res.has(PCT_R_FRAMES), &ctx->frame_ms, 1, ms);
     return PCT_OK;
 }
 
@@ -1219,7 +1188,7 @@ int pct_orient_frames(pct_ctx* ctx, int32_t anchor, const double* viewpoint, int
     PCT_TRY(begin_row_call(ctx, "pct_orient_frames"));
     if (!ctx->res.has(PCT_R_FRAMES) || !ctx->res.has(PCT_R_TABLE)) return pct_fail(ctx, PCT_ERR_INVALID, "no point frames (pct_point_frames)");
     const int64_t rows = ctx->q_end - ctx->q_begin;
-    if (ctx->q_begin != 0 || ctx->q_end != ctx->n || ctx->culled || ctx->frame_rows != rows)
+    if (ctx->q_begin != 0 || ctx->q_end != ctx->n || ctx->culled || !ctx->res.covers(PCT_R_FRAMES, rows))
         return pct_fail(ctx, PCT_ERR_INVALID, "pct_orient_frames: the handle owns rows [%lld,%lld) of %lld: the flood needs the whole cloud",
                         (long long)ctx->q_begin, (long long)ctx->q_end, (long long)ctx->n);
     if (anchor != PCT_ORIENT_SEED && anchor != PCT_ORIENT_TOP && anchor != PCT_ORIENT_VIEW)
@@ -1245,31 +1214,23 @@ int pct_orient_frames(pct_ctx* ctx, int32_t anchor, const double* viewpoint, int
     ctx->orient_stats[4] = w[OW_LEVELS];
     ctx->orient_stats[5] = w[OW_PULLS];
     ctx->orient_ms = ev_ms(ctx, PCT_EV_ORIENT_BEGIN, PCT_EV_ORIENT_END);
-    ctx->orient_rows = rows;
-    ctx->res.leave(PCT_R_ORIENT, false);
+    ctx->res.leave(PCT_R_ORIENT, false, rows);
     return PCT_OK;
 }
 
 int pct_get_orientation(pct_ctx* ctx, int64_t begin, int64_t end, int32_t* component, int32_t* parent, int32_t* level, uint8_t* toggled) {
     PCT_TRY(begin_row_call(ctx, "pct_get_orientation"));
     if (!ctx->res.has(PCT_R_ORIENT)) return pct_fail(ctx, PCT_ERR_INVALID, "no orientation (pct_orient_frames)");
-    if (begin < 0 || end > ctx->orient_rows || begin > end)
-        return pct_fail(ctx, PCT_ERR_INVALID, "rows [%lld,%lld) outside the cloud", (long long)begin, (long long)end);
-    const size_t rows = (size_t)(end - begin);
-    if (rows == 0) return PCT_OK;
-    if (component) PCT_HIP(ctx, hipMemcpyAsync(component, ctx->orient_comp + begin, rows * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    if (parent) PCT_HIP(ctx, hipMemcpyAsync(parent, ctx->orient_parent + begin, rows * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    if (level) PCT_HIP(ctx, hipMemcpyAsync(level, ctx->orient_level + begin, rows * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    if (toggled) PCT_HIP(ctx, hipMemcpyAsync(toggled, ctx->orient_toggle + begin, rows, hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PCT_OK;
+    PCT_TRY(check_owned_span(ctx, "the cloud", PCT_R_ORIENT, begin, end, 0));
+    const pct_column cols[] = {{ctx->orient_comp, sizeof(int), component}, {ctx->orient_parent, sizeof(int), parent},
+                               {ctx->orient_level, sizeof(int), level}, {ctx->orient_toggle, 1, toggled}};
+    return pct_download_columns(ctx, cols, 4, begin, end - begin, nullptr);
 }
 
 int pct_orient_stats(pct_ctx* ctx, int64_t out[8], double* ms) {
     if (!ctx || !out) return PCT_ERR_INVALID;
-    const bool live = ctx->res.has(PCT_R_ORIENT);
-    for (int i = 0; i < 8; ++i) out[i] = live ? ctx->orient_stats[i] : 0;
-    if (ms) *ms = live ? ctx->orient_ms : 0.0;
+    stats_or_zero(ctx->res.has(PCT_R_ORIENT), ctx->orient_stats, 8, out);
+    if (ms) stats_or_zero(ctx->res.has(PCT_R_ORIENT), &ctx->orient_ms, 1, ms);
     return PCT_OK;
 }
 
@@ -1282,7 +1243,7 @@ int pct_point_triangles(pct_ctx* ctx, int32_t flags) {
                         (long long)ctx->q_begin, (long long)ctx->q_end, (long long)ctx->n);
     if (flags & ~PCT_TRI_WIND_FRAMES) return pct_fail(ctx, PCT_ERR_INVALID, "pct_point_triangles: unknown flags %d", flags);
     const bool wind = (flags & PCT_TRI_WIND_FRAMES) != 0;
-    if (wind && !(ctx->res.has(PCT_R_FRAMES) && ctx->frame_rows == ctx->n)) return pct_fail(ctx, PCT_ERR_INVALID, "no point frames (pct_point_frames)");
+    if (wind) PCT_TRY(need_for_owned_rows(ctx, PCT_R_FRAMES, "no point frames (pct_point_frames)"));
     ctx->res.drop(pct_replacing(PCT_R_TRIANGLES));     // (behind every refusal: a refused call leaves the triangles of an earlier one)
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_TRI_BEGIN], ctx->stream));
     const int status = pct_launch_point_triangles(ctx, wind, ctx->ev[PCT_EV_TRI_MID]);
@@ -1293,21 +1254,20 @@ int pct_point_triangles(pct_ctx* ctx, int32_t flags) {
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_TRI_END], ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const unsigned long long* w = ctx->pin->tri_words;
-    ctx->tri_rows = ctx->n;
     ctx->tri_total = (int64_t)w[7];
     const int64_t st[8] = {ctx->n, (int64_t)w[1], (int64_t)w[2], ctx->tri_total, (int64_t)w[0], (int64_t)w[3], (int64_t)w[4], 0};
     for (int i = 0; i < 8; ++i) ctx->tri_stats[i] = st[i];
     ctx->tri_ms[0] = ev_ms(ctx, PCT_EV_TRI_BEGIN, PCT_EV_TRI_END);
     ctx->tri_ms[1] = ev_ms(ctx, PCT_EV_TRI_BEGIN, PCT_EV_TRI_MID);
     ctx->tri_ms[2] = ev_ms(ctx, PCT_EV_TRI_MID, PCT_EV_TRI_END);
-    ctx->res.leave(PCT_R_TRIANGLES, false);            // (kept by public index)
+    ctx->res.leave(PCT_R_TRIANGLES, false, ctx->n);    // (kept by public index)
     return PCT_OK;
 }
 
 int pct_get_point_fans(pct_ctx* ctx, int64_t begin, int64_t end, int64_t* offsets, int32_t* nbr) {
     PCT_TRY(begin_call(ctx));
     if (!ctx->res.has(PCT_R_TRIANGLES)) return pct_fail(ctx, PCT_ERR_INVALID, "no triangles (pct_point_triangles)");
-    if (begin < 0 || end > ctx->tri_rows || begin > end || !offsets)
+    if (begin < 0 || end > ctx->res.rows_of(PCT_R_TRIANGLES) || begin > end || !offsets)
         return pct_fail(ctx, PCT_ERR_INVALID, "rows [%lld,%lld) outside the cloud", (long long)begin, (long long)end);
     const int64_t rows = end - begin;
     PCT_TRY(pct_reserve(ctx, &ctx->stage_a, (size_t)(rows + 1) * sizeof(int64_t)));
@@ -1325,34 +1285,34 @@ int pct_get_point_fans(pct_ctx* ctx, int64_t begin, int64_t end, int64_t* offset
     return PCT_OK;
 }
 
+// triangles [first, first + count) of an ascending (have, 3) array
+static int download_triangles(pct_ctx* ctx, const pct_buf& src, int64_t have, int64_t first, int64_t count, int32_t* tri) {
+    if (first < 0 || count < 0 || first + count > have || (count > 0 && !tri))
+        return pct_fail(ctx, PCT_ERR_INVALID, "triangles [%lld,%lld) outside the %lld resident", (long long)first, (long long)(first + count), (long long)have);
+    const pct_column col = {src.p, 3 * sizeof(int), tri};
+    return pct_download_columns(ctx, &col, 1, first, count, nullptr);
+}
+
 int pct_get_triangles(pct_ctx* ctx, int64_t first, int64_t count, int32_t* tri) {
     PCT_TRY(begin_call(ctx));
     if (!ctx->res.has(PCT_R_TRIANGLES)) return pct_fail(ctx, PCT_ERR_INVALID, "no triangles (pct_point_triangles)");
-    if (first < 0 || count < 0 || first + count > ctx->tri_total || (count > 0 && !tri))
-        return pct_fail(ctx, PCT_ERR_INVALID, "triangles [%lld,%lld) outside the %lld resident", (long long)first, (long long)(first + count),
-                        (long long)ctx->tri_total);
-    if (count == 0) return PCT_OK;
-    PCT_HIP(ctx, hipMemcpyAsync(tri, (const int*)ctx->tri.p + first * 3, (size_t)count * 3 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PCT_OK;
+    return download_triangles(ctx, ctx->tri, ctx->tri_total, first, count, tri);
 }
 
 int pct_point_triangle_stats(pct_ctx* ctx, int64_t out[8], double* ms) {
     if (!ctx || !out) return PCT_ERR_INVALID;
-    for (int i = 0; i < 8; ++i) out[i] = ctx->res.has(PCT_R_TRIANGLES) ? ctx->tri_stats[i] : 0;
-    if (ms) *ms = ctx->res.has(PCT_R_TRIANGLES) ? ctx->tri_ms[0] : 0.0;
+    stats_or_zero(ctx->res.has(PCT_R_TRIANGLES), ctx->tri_stats, 8, out);
+    if (ms) stats_or_zero(ctx->res.has(PCT_R_TRIANGLES), &ctx->tri_ms[0], 1, ms);
     return PCT_OK;
 }
 
 int pct_point_triangle_profile(pct_ctx* ctx, double out[2]) {
     if (!ctx || !out) return PCT_ERR_INVALID;
-    for (int i = 0; i < 2; ++i) out[i] = ctx->res.has(PCT_R_TRIANGLES) ? ctx->tri_ms[1 + i] : 0.0;
+    stats_or_zero(ctx->res.has(PCT_R_TRIANGLES), &ctx->tri_ms[1], 2, out);
     return PCT_OK;
 }
 
-// ---- boundary loops and small-hole filling (pct_hole.hip, include/pct_hip_holes.h): an appendix of the triangles -------------
-static bool hole_results(const pct_ctx* ctx) { return ctx->res.has(PCT_R_TRIANGLES) && ctx->hole_valid; }
-
+// ---- boundary loops and small-hole filling (pct_hole.hip, include/pct_hip_holes.h): PCT_R_HOLES, made from the triangles ------
 int pct_fill_holes(pct_ctx* ctx, int32_t max_vertices, double max_perimeter, int32_t flags) {
     PCT_TRY(begin_row_call(ctx, "pct_fill_holes"));
     if (ctx->n > 0 && (ctx->q_begin != 0 || ctx->q_end != ctx->n || ctx->culled))
@@ -1363,7 +1323,7 @@ int pct_fill_holes(pct_ctx* ctx, int32_t max_vertices, double max_perimeter, int
         return pct_fail(ctx, PCT_ERR_INVALID, "pct_fill_holes: max_vertices=%d outside [3,%d]", max_vertices, PCT_HOLE_MAX_VERTICES);
     if (!(max_perimeter > 0.0)) return pct_fail(ctx, PCT_ERR_INVALID, "pct_fill_holes: max_perimeter must be positive (+inf: no cap)");
     if (flags != 0) return pct_fail(ctx, PCT_ERR_INVALID, "pct_fill_holes: unknown flags %d", flags);
-    ctx->hole_valid = false;                           // (behind every refusal: a refused call leaves the results of an earlier one)
+    ctx->res.drop(pct_replacing(PCT_R_HOLES));         // (behind every refusal: a refused call leaves the results of an earlier one)
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_HOLE_BEGIN], ctx->stream));
     int64_t st[8];
     const int status = pct_launch_fill_holes(ctx, max_vertices, max_perimeter, st);
@@ -1375,19 +1335,14 @@ int pct_fill_holes(pct_ctx* ctx, int32_t max_vertices, double max_perimeter, int
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (int i = 0; i < 8; ++i) ctx->hole_stats[i] = st[i];
     ctx->hole_ms = ev_ms(ctx, PCT_EV_HOLE_BEGIN, PCT_EV_HOLE_END);
-    ctx->hole_valid = true;
+    ctx->res.leave(PCT_R_HOLES, false, ctx->n);
     return PCT_OK;
 }
 
 static int get_triangle_rows(pct_ctx* ctx, const pct_buf& src, int64_t have, int64_t first, int64_t count, int32_t* tri) {
     PCT_TRY(begin_call(ctx));
-    if (!hole_results(ctx)) return pct_fail(ctx, PCT_ERR_INVALID, "no hole results (pct_fill_holes)");
-    if (first < 0 || count < 0 || first + count > have || (count > 0 && !tri))
-        return pct_fail(ctx, PCT_ERR_INVALID, "triangles [%lld,%lld) outside the %lld resident", (long long)first, (long long)(first + count), (long long)have);
-    if (count == 0) return PCT_OK;
-    PCT_HIP(ctx, hipMemcpyAsync(tri, (const int*)src.p + first * 3, (size_t)count * 3 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PCT_OK;
+    if (!ctx->res.has(PCT_R_HOLES)) return pct_fail(ctx, PCT_ERR_INVALID, "no hole results (pct_fill_holes)");
+    return download_triangles(ctx, src, have, first, count, tri);
 }
 
 int pct_get_hole_triangles(pct_ctx* ctx, int64_t first, int64_t count, int32_t* tri) {
@@ -1402,7 +1357,7 @@ int pct_get_filled_triangles(pct_ctx* ctx, int64_t first, int64_t count, int32_t
 
 int pct_get_boundary_loops(pct_ctx* ctx, int64_t* offsets, int32_t* vertices, uint8_t* status) {
     PCT_TRY(begin_call(ctx));
-    if (!hole_results(ctx)) return pct_fail(ctx, PCT_ERR_INVALID, "no hole results (pct_fill_holes)");
+    if (!ctx->res.has(PCT_R_HOLES)) return pct_fail(ctx, PCT_ERR_INVALID, "no hole results (pct_fill_holes)");
     if (!offsets) return pct_fail(ctx, PCT_ERR_INVALID, "null offsets");
     const int64_t loops = ctx->hole_loops, verts = ctx->hole_loop_verts;
     const char* base = (const char*)ctx->hole_loop.p;
@@ -1416,8 +1371,8 @@ int pct_get_boundary_loops(pct_ctx* ctx, int64_t* offsets, int32_t* vertices, ui
 
 int pct_fill_hole_stats(pct_ctx* ctx, int64_t out[8], double* ms) {
     if (!ctx || !out) return PCT_ERR_INVALID;
-    for (int i = 0; i < 8; ++i) out[i] = hole_results(ctx) ? ctx->hole_stats[i] : 0;
-    if (ms) *ms = hole_results(ctx) ? ctx->hole_ms : 0.0;
+    stats_or_zero(ctx->res.has(PCT_R_HOLES), ctx->hole_stats, 8, out);
+    if (ms) stats_or_zero(ctx->res.has(PCT_R_HOLES), &ctx->hole_ms, 1, ms);
     return PCT_OK;
 }
 
@@ -1626,10 +1581,9 @@ int pct_pca_curvatures(pct_ctx* ctx, int32_t k, int32_t algo, int32_t keep_neigh
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->tm.fit_ms = ev_ms(ctx, PCT_EV_FIT_BEGIN, PCT_EV_FIT_END);
     ctx->tm.total_ms = ctx->clock[0].since_begin(ctx->ev[PCT_EV_FIT_END]);
-    ctx->res.leave(PCT_R_PCA, false);
+    ctx->res.leave(PCT_R_PCA, false, ctx->n);
     ctx->pca_has_nbr = keep_neighbors != 0;
     ctx->pca_k = (int32_t)kk;
-    ctx->pca_rows = ctx->n;
     if (exact_rows) *exact_rows = exact;
     return PCT_OK;
 }
@@ -1638,20 +1592,17 @@ int pct_get_pca(pct_ctx* ctx, int64_t begin, int64_t end, double* l1, double* l2
                 int32_t* idx) {
     PCT_TRY(begin_call(ctx));
     if (!ctx->res.has(PCT_R_PCA)) return pct_fail(ctx, PCT_ERR_INVALID, "no PCA frame on this handle (pct_pca_curvatures)");
-    if (begin < 0 || end > ctx->pca_rows || begin > end)
-        return pct_fail(ctx, PCT_ERR_INVALID, "bad row range [%lld,%lld) of %lld", (long long)begin, (long long)end, (long long)ctx->pca_rows);
+    const int64_t n = ctx->res.rows_of(PCT_R_PCA), rows = end - begin;
+    if (begin < 0 || end > n || begin > end)
+        return pct_fail(ctx, PCT_ERR_INVALID, "bad row range [%lld,%lld) of %lld", (long long)begin, (long long)end, (long long)n);
     if (idx && !ctx->pca_has_nbr)
         return pct_fail(ctx, PCT_ERR_INVALID, "pct_get_pca: the neighbourhoods were not kept (pct_pca_curvatures keep_neighbors)");
-    const int64_t n = ctx->pca_rows, rows = end - begin;
     if (rows == 0) return PCT_OK;
     const double* o = (const double*)ctx->pca.p;
+    const pct_column cols[] = {{o, sizeof(double), l1}, {o + n, sizeof(double), l2}, {o + 2 * n, sizeof(double), K}, {o + 3 * n, sizeof(double), H},
+                               {o + 4 * n, 6 * sizeof(double), dirs}, {ctx->pca_nbr.p, ctx->pca_k * (int)sizeof(int32_t), idx}};
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_IO_BEGIN], ctx->stream));
-    double* outs[4] = {l1, l2, K, H};
-    for (int i = 0; i < 4; ++i)
-        if (outs[i]) PCT_HIP(ctx, hipMemcpyAsync(outs[i], o + (int64_t)i * n + begin, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (dirs) PCT_HIP(ctx, hipMemcpyAsync(dirs, o + 4 * n + 6 * begin, (size_t)rows * 6 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (idx) PCT_HIP(ctx, hipMemcpyAsync(idx, (const int32_t*)ctx->pca_nbr.p + begin * ctx->pca_k, (size_t)rows * ctx->pca_k * sizeof(int32_t),
-                                         hipMemcpyDeviceToHost, ctx->stream));
+    PCT_TRY(pct_enqueue_columns(ctx, cols, 6, begin, rows, nullptr));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_IO_END], ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->tm.export_ms = ev_ms(ctx, PCT_EV_IO_BEGIN, PCT_EV_IO_END);

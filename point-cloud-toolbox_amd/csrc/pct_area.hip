@@ -101,19 +101,6 @@ __global__ __launch_bounds__(kAreaBlock) void k_area_wide(FitArgs a, AreaOut o) 
     }
 }
 
-// public rows [first, first + rows) of the owned range out of row-ordered results
-__global__ __launch_bounds__(256) void k_gather_area(const int* __restrict__ row_of, int64_t first, int64_t rows,
-                                                     const double* __restrict__ area, const unsigned char* __restrict__ closed,
-                                                     const int* __restrict__ nverts, double* __restrict__ o_area,
-                                                     unsigned char* __restrict__ o_closed, int* __restrict__ o_nverts) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= rows) return;
-    const int64_t r = row_of[first + i];
-    if (o_area) o_area[i] = area[r];
-    if (o_closed) o_closed[i] = closed[r];
-    if (o_nverts) o_nverts[i] = nverts[r];
-}
-
 // calculate_energies (pct:650-655) over per-point areas: bending = sum double(H2_i) A_i (H2 = the fit's float32 h ** 2),
 // stretching = sum double(K_i) A_i, area = sum A_i, over the owned rows i whose area, K and H2 are no NaN -- and whose cell
 // is closed, with closed_only.  area_map / fit_map (nullable): where row i of the sum lies in the areas / in the fit.
@@ -166,7 +153,7 @@ __global__ __launch_bounds__(64) void k_point_final(const double* __restrict__ p
 // Areas of the owned rows of the resident table, in the order pct_launch_fit_table leaves its results in (table-row order
 // behind a sweep of a cell list, public order otherwise).  The statistics words go to ctx->pin->area_words; both are
 // complete once the stream has been waited for.
-int pct_launch_point_areas(pct_ctx* ctx) {
+int pct_launch_point_areas(pct_ctx* ctx, bool* by_row) {
     const int64_t rows = ctx->q_end - ctx->q_begin;
     const bool sorted = ctx->knn_sorted_space;
     FitArgs a = {};
@@ -206,16 +193,7 @@ int pct_launch_point_areas(pct_ctx* ctx) {
         PCT_HIP(ctx, hipGetLastError());
     }
     PCT_HIP(ctx, hipMemcpyAsync(ctx->pin->area_words, ctx->area_over.p, sizeof(ctx->pin->area_words), hipMemcpyDeviceToHost, ctx->stream));
-    ctx->area_row_order = sorted;
-    return PCT_OK;
-}
-
-int pct_launch_gather_areas(pct_ctx* ctx, int64_t first, int64_t rows, double* d_area, unsigned char* d_closed, int* d_nverts) {
-    PCT_TRY(pct_ensure_row_of(ctx));
-    PCT_LAUNCH(k_gather_area, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, ctx->stream, (const int*)ctx->row_of.p, first, rows,
-               (const double*)ctx->area.p, (const unsigned char*)ctx->area_closed.p, (const int*)ctx->area_nverts.p, d_area, d_closed,
-               d_nverts);
-    PCT_HIP(ctx, hipGetLastError());
+    *by_row = sorted;
     return PCT_OK;
 }
 
@@ -224,9 +202,10 @@ int pct_launch_point_energies(pct_ctx* ctx, bool closed_only, double* d_partial,
     const int64_t rows = ctx->q_end - ctx->q_begin;
     const int nblk = (int)((rows + kEnergyBlock - 1) / kEnergyBlock < 1024 ? (rows + kEnergyBlock - 1) / kEnergyBlock : 1024);
     const int *area_map = nullptr, *fit_map = nullptr;
-    if (ctx->area_row_order != ctx->fit_row_order) {      // one of the two in table-row order, the other in public order
+    const bool area_by_row = ctx->res.in_row_order(PCT_R_AREAS);
+    if (area_by_row != ctx->res.in_row_order(PCT_R_FIT)) {      // one of the two in table-row order, the other in public order
         PCT_TRY(pct_ensure_row_of(ctx));
-        (ctx->area_row_order ? area_map : fit_map) = (const int*)ctx->row_of.p;
+        (area_by_row ? area_map : fit_map) = (const int*)ctx->row_of.p;
     }
     PCT_LAUNCH(k_point_energy, dim3(nblk > 0 ? nblk : 1), dim3(kEnergyBlock), 0, ctx->stream, (const double*)ctx->area.p,
                (const unsigned char*)ctx->area_closed.p, (const float*)ctx->K.p, (const float*)ctx->H2.p, area_map, fit_map, rows,

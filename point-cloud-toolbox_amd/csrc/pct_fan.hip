@@ -341,7 +341,6 @@ int scan_counts(pct_ctx* ctx, const int64_t* d_count, int64_t* d_off, int64_t en
 int pct_launch_point_triangles(pct_ctx* ctx, bool wind_frames, hipEvent_t mid) {
     const int64_t n = ctx->n;
     const bool sorted = ctx->knn_sorted_space;
-    ctx->hole_valid = false;        // the boundary loops and patches of the triangles about to be replaced (pct_hole.hip)
     FitArgs a = {};
     PCT_TRY(fit_source(ctx, sorted ? FitSpace::Sorted : FitSpace::Packed, &a));
     a.table = (const int*)ctx->nbr_pos.p;
@@ -361,7 +360,7 @@ int pct_launch_point_triangles(pct_ctx* ctx, bool wind_frames, hipEvent_t mid) {
     o.fast = (int*)ctx->fan_fast.p;
     o.side = (unsigned char*)ctx->fan_side.p;
     o.flipped = wind_frames ? (const unsigned char*)ctx->frame_flip.p + 64 : nullptr;
-    o.flipped_by_row = ctx->frame_row_order ? 1 : 0;
+    o.flipped_by_row = ctx->res.in_row_order(PCT_R_FRAMES) ? 1 : 0;
     o.words = (unsigned long long*)ctx->fan_over.p;
     o.over_list = (int*)ctx->fan_over.p + 16;
     PCT_HIP(ctx, hipMemsetAsync(ctx->fan_over.p, 0, 64, ctx->stream));

@@ -231,30 +231,12 @@ __global__ __launch_bounds__(kFrameBlock) void k_frame(FitArgs a, FrameOut o) {
     }
 }
 
-// public rows [first, first + rows) of the owned range out of row-ordered results
-__global__ __launch_bounds__(256) void k_gather_frame(const int* __restrict__ row_of, int64_t first, int64_t rows,
-                                                      const double* __restrict__ normal, const double* __restrict__ k12,
-                                                      const double* __restrict__ dirs, const unsigned char* __restrict__ flipped,
-                                                      double* __restrict__ o_normal, double* __restrict__ o_k12,
-                                                      double* __restrict__ o_dirs, unsigned char* __restrict__ o_flipped) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= rows) return;
-    const int64_t r = row_of[first + i];
-    if (o_normal)
-        for (int j = 0; j < 3; ++j) o_normal[i * 3 + j] = normal[r * 3 + j];
-    if (o_k12)
-        for (int j = 0; j < 2; ++j) o_k12[i * 2 + j] = k12[r * 2 + j];
-    if (o_dirs)
-        for (int j = 0; j < 6; ++j) o_dirs[i * 6 + j] = dirs[r * 6 + j];
-    if (o_flipped) o_flipped[i] = flipped[r];
-}
-
 }  // namespace
 
 // Frames of the owned rows of the resident table, in the order pct_launch_fit_table leaves its results in (table-row order
 // behind a sweep of a cell list, public order otherwise).  The statistics words go to ctx->pin->frame_words; both are
 // complete once the stream has been waited for.  viewpoint: three finite doubles, or null.
-int pct_launch_point_frames(pct_ctx* ctx, const double* viewpoint) {
+int pct_launch_point_frames(pct_ctx* ctx, const double* viewpoint, bool* by_row) {
     const int64_t rows = ctx->q_end - ctx->q_begin;
     const bool sorted = ctx->knn_sorted_space;
     FitArgs a = {};
@@ -280,8 +262,9 @@ int pct_launch_point_frames(pct_ctx* ctx, const double* viewpoint) {
     o.words = (unsigned long long*)ctx->frame_flip.p;
     o.flipped = (unsigned char*)ctx->frame_flip.p + 64;
     o.coefs = (const float*)ctx->coefs.p;
-    o.coef_by_row = ctx->fit_row_order ? 1 : 0;
-    if (ctx->fit_row_order && !sorted) {                 // the fit in table-row order, the frames in public order
+    const bool fit_by_row = ctx->res.in_row_order(PCT_R_FIT);
+    o.coef_by_row = fit_by_row ? 1 : 0;
+    if (fit_by_row && !sorted) {                 // the fit in table-row order, the frames in public order
         PCT_TRY(pct_ensure_row_of(ctx));
         o.row_of = (const int*)ctx->row_of.p;
     }
@@ -299,17 +282,6 @@ int pct_launch_point_frames(pct_ctx* ctx, const double* viewpoint) {
         PCT_HIP(ctx, hipGetLastError());
     }
     PCT_HIP(ctx, hipMemcpyAsync(ctx->pin->frame_words, ctx->frame_flip.p, sizeof(ctx->pin->frame_words), hipMemcpyDeviceToHost, ctx->stream));
-    ctx->frame_row_order = sorted;
-    return PCT_OK;
-}
-
-int pct_launch_gather_frames(pct_ctx* ctx, int64_t first, int64_t rows, double* d_normal, double* d_k12, double* d_dirs,
-                             unsigned char* d_flipped) {
-    const int64_t all = ctx->frame_rows;
-    const double* normal = (const double*)ctx->frame.p;
-    PCT_TRY(pct_ensure_row_of(ctx));
-    PCT_LAUNCH(k_gather_frame, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, ctx->stream, (const int*)ctx->row_of.p, first, rows,
-               normal, normal + all * 3, normal + all * 5, (const unsigned char*)ctx->frame_flip.p + 64, d_normal, d_k12, d_dirs, d_flipped);
-    PCT_HIP(ctx, hipGetLastError());
+    *by_row = sorted;
     return PCT_OK;
 }

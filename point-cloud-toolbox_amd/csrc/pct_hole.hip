@@ -389,7 +389,7 @@ __global__ __launch_bounds__(256) void k_hole_pack(int64_t gaps, HoleSlots o, co
 }  // namespace
 
 int pct_launch_fill_holes(pct_ctx* ctx, int max_vertices, double max_perimeter, int64_t stats8[8]) {
-    const int64_t n = ctx->tri_rows, total = ctx->tri_total;
+    const int64_t n = ctx->res.rows_of(PCT_R_TRIANGLES), total = ctx->tri_total;
     hipStream_t st = ctx->stream;
     HoleView h = {};
     h.head = (const int2*)ctx->fan_head.p;

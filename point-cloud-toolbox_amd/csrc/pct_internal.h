@@ -163,7 +163,8 @@ struct pct_ctx {
     // mid-build wait (everything of the previous call has completed by then) or until anything else is asked of the
     // handle (which first waits for the stream).  The host prepares step i + 1 while the device fits step i.
     bool async_mode = false;
-    pct_residents res;             // which results are in place (the state rules of include/pct_hip.h: pct_residents.h)
+    pct_residents res;             // which results are in place, each one's order (table-row or public) and the rows it covers
+                                   // -- recorded there alone (the state rules of include/pct_hip.h: pct_residents.h)
     // the pending call -- on: a fused call has been enqueued and its bookkeeping has not been done; par: its parity (which
     // clock times it, which pinned slots its kernels write); sorted: its table is in a sorted space, knn_fast_ms applies;
     // tm: the host-side fields of its timings
@@ -291,11 +292,9 @@ struct pct_ctx {
     bool dist_valid = true;        // nbr_dist holds the distances of the table in place (else: derived on demand)
     pct_buf counters;   // pct_dev_words: the sweep's statistics words, the census, the scatter hit count
 
-    // results, public order
+    // fit results (PCT_R_FIT; in table-row order behind a sweep of a cell list: res.in_row_order)
     pct_buf coefs;      // float (n,6)
     pct_buf K, H, H2;   // float (n)
-    int64_t fit_rows = 0;
-    bool fit_row_order = false;    // results are in neighbour-table row order (grid sweep), not public order
     bool fit_cloud_aligned = false;// results belong to cloud rows [q_begin, q_end) (pct_fit / pct_curvature) rather than to the
                                    // rows of a pct_fit_indices call; kept apart from the table, which helpers may drop
 
@@ -316,7 +315,6 @@ struct pct_ctx {
     pct_buf ball_alt;   // ... the other buffer of the library's segmented sort (rows longer than k_ball_sort takes)
     pct_buf ball_dist;  // double (entries), when asked for
     bool ball_has_dist = false;
-    int64_t ball_m = 0;
     int64_t ball_stats[4] = {0, 0, 0, 0};
 
     // PCA principal curvatures (pct_pca.hip), public order: double [lambda_1 | lambda_2 | K | H | frame (n,3,2)]
@@ -326,25 +324,21 @@ struct pct_ctx {
     pct_buf pca_orig;   // double4 (n): float64 clouds' uploaded records while the sweep sees them recentred
     bool pca_has_nbr = false, pca_recentred = false;
     int32_t pca_k = 0;
-    int64_t pca_rows = 0;
 
     pct_timings tm = {};
 
-    // per-point tangent-plane Voronoi areas (pct_area.hip) of the owned rows of the resident table
+    // per-point tangent-plane Voronoi areas (pct_area.hip) of the owned rows of the resident table (PCT_R_AREAS: in the order
+    // and for the rows res records, as the fit)
     pct_buf area;          // double (owned)
     pct_buf area_closed;   // uint8 (owned)
     pct_buf area_nverts;   // int32 (owned)
     pct_buf area_over;     // eight statistics words, then int32 (owned): the rows redone with room for k + 4 vertices
-    bool area_row_order = false;   // in neighbour-table row order (as fit_row_order), else public order from q_begin
-    int64_t area_rows = 0;
     int64_t area_stats[4] = {0, 0, 0, 0};   // rows, closed rows, NaN rows, overflow rows
     double area_profile[2] = {0, 0};        // device milliseconds of the two kernels, neighbours past the rejection test
 
-    // per-point surface frames (pct_frame.hip) of the owned rows of the resident table and its fit
+    // per-point surface frames (pct_frame.hip) of the owned rows of the resident table and its fit (PCT_R_FRAMES: as the areas)
     pct_buf frame;         // double (owned): normal (rows, 3) | k1 k2 (rows, 2) | directions (rows, 3, 2)
     pct_buf frame_flip;    // eight statistics words, then uint8 (owned): the viewpoint turned the row's normal
-    bool frame_row_order = false;  // in neighbour-table row order (as fit_row_order), else public order from q_begin
-    int64_t frame_rows = 0;
     int64_t frame_stats[4] = {0, 0, 0, 0};  // rows, NaN rows, flipped rows, umbilic rows
     double frame_ms = 0;                    // device milliseconds of its kernel
 
@@ -355,7 +349,6 @@ struct pct_ctx {
     const int* orient_parent = nullptr;
     const int* orient_level = nullptr;
     const unsigned char* orient_toggle = nullptr;
-    int64_t orient_rows = 0;
     int64_t orient_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // valid rows, components, unlabelled, toggled, levels, pull rounds, launches, waits
     double orient_ms = 0;
 
@@ -370,13 +363,12 @@ struct pct_ctx {
     pct_buf tri_part;      // u64 (blocks, 4): the statistics' per-block partial sums
     pct_buf tri;           // int32 (triangles, 3), ascending
     int32_t tri_wpitch = 0;
-    int64_t tri_rows = 0, tri_total = 0;
+    int64_t tri_total = 0;
     int64_t tri_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     double tri_ms[3] = {0, 0, 0};           // device milliseconds: the call, its fan kernels, agreement and emission
 
-    // boundary loops and patches of those triangles (pct_hole.hip, include/pct_hip_holes.h): an appendix of the triangles
-    // resident -- read only while res.has(PCT_R_TRIANGLES) && hole_valid; pct_launch_point_triangles clears the flag
-    bool hole_valid = false;
+    // boundary loops and patches of those triangles (pct_hole.hip, include/pct_hip_holes.h): PCT_R_HOLES, made from the
+    // triangles -- whatever drops or replaces them drops these
     pct_buf hole_cnt, hole_off;     // int64 (n + 1): gaps per row, their scan
     pct_buf hole_part;              // u64 (blocks, 4): the statistics' per-block partial sums
     pct_buf hole_gap;               // int2 (gaps): the gaps' members {a, b}; int (gaps): their rows
@@ -522,7 +514,8 @@ int pct_launch_knn_tree(pct_ctx* ctx, int32_t k, double eps, bool want_dist, pct
 int pct_launch_export_neighbors(pct_ctx* ctx, int64_t begin, int64_t end,
                                 int32_t* d_idx, float* d_dist, int32_t* d_cnt);
 // fit (pct_fit.hip)
-int pct_launch_fit_table(pct_ctx* ctx, FitSlot slot, bool* mirrored);     // *mirrored (may be null): a fit kernel mirrored the statistics words
+// *mirrored (may be null): a fit kernel mirrored the statistics words; *by_row: the results are stored in table-row order
+int pct_launch_fit_table(pct_ctx* ctx, FitSlot slot, bool* mirrored, bool* by_row);
 int pct_launch_fit_pass(pct_ctx* ctx, int64_t rows, int par);
 int pct_launch_fit_rows(pct_ctx* ctx, const int32_t* d_idx, const int32_t* d_cnt,
                         const int64_t* d_query, int64_t rows, int32_t k, int32_t pitch,
@@ -534,7 +527,6 @@ int pct_launch_fit_rows32(pct_ctx* ctx, const int32_t* d_idx, const int32_t* d_c
 int pct_launch_fit_ball(pct_ctx* ctx, const int* d_self32, int64_t rows, int* d_used);
 int pct_launch_prefix_rows(pct_ctx* ctx, const int* d_sample_pos, int64_t n_samples, int n_lo, int n_hi, int* d_table,
                            int pitch, int* d_cnt, int64_t* d_row_query);
-int pct_launch_gather_fit(pct_ctx* ctx, int64_t first, int64_t rows, float* d_coefs, float* d_K, float* d_H, float* d_H2);
 int pct_launch_curvatures(pct_ctx* ctx, const float* d_coefs, int64_t rows, float* d_K, float* d_H, float* d_H2);
 int pct_launch_plane_rotate(pct_ctx* ctx, const void* d_nbrs, bool f64, int64_t batch, int32_t m, double* d_out);
 int pct_launch_quadric_rows(pct_ctx* ctx, const float* d_pts, int64_t batch, int32_t m, float* d_coefs);
@@ -552,20 +544,26 @@ int pct_launch_query_grid(pct_ctx* ctx, const double* d_q, int64_t m, int32_t k,
 int pct_launch_ball(pct_ctx* ctx, bool grid, const double* d_q, int64_t m, const double* d_r, int r_stride, int32_t flags,
                     int64_t max_entries, int64_t* h_offsets, int64_t stat3[3]);
 int pct_launch_gather_int(pct_ctx* ctx, const int* d_map, int* d_inout, int64_t n);
+// pct_rows.hip.  One column of a per-row result on its way to the host: where row 0 lies on the device, the bytes of a row,
+// the caller's array (null: not asked for).  pct_download_columns: rows [first, first + rows) of every column asked for,
+// one copy each (one for a run of columns adjacent on both sides) and one wait; map (null: the rows lie in the order asked
+// for) names the stored row of every row -- then at most kPctRowColumns columns, gathered by one kernel into stage_a first.
+// pct_enqueue_columns: without the wait.
+struct pct_column { const void* base; int bytes; void* host; };
+constexpr int kPctRowColumns = 4;
+int pct_enqueue_columns(pct_ctx* ctx, const pct_column* cols, int ncol, int64_t first, int64_t rows, const int* map);
+int pct_download_columns(pct_ctx* ctx, const pct_column* cols, int ncol, int64_t first, int64_t rows, const int* map);
 int pct_ensure_row_of(pct_ctx* ctx);     // before any read of ctx->row_of
 int pct_launch_export_rows(pct_ctx* ctx, const int64_t* d_rows, int64_t n_rows, int32_t* d_idx, float* d_dist, int32_t* d_cnt);
 int pct_launch_mesh_energies(pct_ctx* ctx, const double* d_v, const int* d_tri, int64_t n_tri, const void* d_K, const void* d_H,
                              bool k_f64, bool h_f64, double* d_partial, int nblk, double* d_out);
-// pct_area.hip: areas of the owned rows of the resident table (statistics words to ctx->pin->area_words), their public
-// rows gathered out of table-row order, and the energies over them: d_out4 = {bending, stretching, area, rows used}
-int pct_launch_point_areas(pct_ctx* ctx);
-int pct_launch_gather_areas(pct_ctx* ctx, int64_t first, int64_t rows, double* d_area, unsigned char* d_closed, int* d_nverts);
+// pct_area.hip: areas of the owned rows of the resident table (statistics words to ctx->pin->area_words; *by_row: stored in
+// table-row order), and the energies over them: d_out4 = {bending, stretching, area, rows used}
+int pct_launch_point_areas(pct_ctx* ctx, bool* by_row);
 int pct_launch_point_energies(pct_ctx* ctx, bool closed_only, double* d_partial, double* d_out4);
 // pct_frame.hip: surface frames of the owned rows of the resident table from its resident fit (statistics words to
-// ctx->pin->frame_words; viewpoint: three finite doubles or null), and their public rows gathered out of table-row order
-int pct_launch_point_frames(pct_ctx* ctx, const double* viewpoint);
-int pct_launch_gather_frames(pct_ctx* ctx, int64_t first, int64_t rows, double* d_normal, double* d_k12, double* d_dirs,
-                             unsigned char* d_flipped);
+// ctx->pin->frame_words; viewpoint: three finite doubles or null; *by_row: stored in table-row order)
+int pct_launch_point_frames(pct_ctx* ctx, const double* viewpoint, bool* by_row);
 // pct_orient.hip: the flood over the resident table, the anchor and the apply pass on the resident frames of a whole-cloud
 // handle; the control words are on their way to ctx->pin->orient_words on return (complete after the stream's next wait),
 // stats8[6] and [7] (kernel launches, host waits) are filled here

@@ -344,6 +344,5 @@ int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps, const int* fuse_par, pct
     ctx->nbr_pitch = pitch;
     ctx->knn_sorted_space = false;
     ctx->tm.levels = passes;
-    if (fuse_par) ctx->fit_row_order = false;      // the passes fitted their rows: results in public order
     return PCT_OK;
 }

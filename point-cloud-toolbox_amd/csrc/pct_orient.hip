@@ -415,7 +415,7 @@ int pct_run_orient(pct_ctx* ctx, int anchor, const double* viewpoint, int max_co
     s.rows = rows;
     s.k = ctx->k;
     s.pitch = ctx->nbr_pitch;
-    s.frame_by_row = ctx->frame_row_order ? 1 : 0;
+    s.frame_by_row = ctx->res.in_row_order(PCT_R_FRAMES) ? 1 : 0;
     s.normal = (double*)ctx->frame.p;
     s.k12 = s.normal + rows64 * 3;
     s.dirs = s.k12 + rows64 * 2;

@@ -1,6 +1,6 @@
-"""Random call sequences over every modelled entry point, held to include/pct_hip.h (tests/call_model.py).
+"""Random call sequences over every modelled entry point, held to include/pct_hip.h and include/pct_hip_holes.h (tests/call_model.py).
 
-`plan(seed, profile, steps)` draws a sequence from what the model allows -- about one step in six (911 of the 5400 committed
+`plan(seed, profile, steps)` draws a sequence from what the model allows -- about one step in six (930 of the 5400 committed
 steps; tests/test_call_model.py holds it between one in seven and one in five) an operation whose precondition the model says
 is unmet, for which the documented refusal is expected: after a call that dropped a result its getters are asked, a refusal the
 plan has not drawn yet is drawn where the state allows it, so that every (operation, precondition) pair is refused.  The choice depends on the seed and
@@ -31,8 +31,11 @@ K_SET = [3, 8, 30, 63, 64, 100, 127, 128, 200, 400]
 # a step is drawn out of state with these chances: after a call that dropped a result, while a refusal not yet drawn is
 # possible, and otherwise.  Over the committed cases this comes to the share tests/test_call_model.py asserts.
 P_PROBE, P_NOVEL, P_ANY = 0.4, 0.3, 0.01
+# how much the hole getters are favoured while hole results are in place, and pct_fill_holes while they are not (_follow)
+HOLE_FOLLOW, FILL_FOLLOW = 4.0, 4.0
 _PROBES = {"get_neighbors": "table", "get_fit": "fit", "get_point_areas": "areas", "get_point_frames": "frames", "get_orientation": "orient",
-           "get_triangles": "triangles", "get_point_fans": "triangles", "get_pca": "pca", "get_ball": "ball", "slab_counts": "slab_pass"}
+           "get_triangles": "triangles", "get_point_fans": "triangles", "get_pca": "pca", "get_ball": "ball", "slab_counts": "slab_pass",
+           "get_hole_triangles": "holes", "get_filled_triangles": "holes", "get_boundary_loops": "holes"}
 
 # ---- the committed cases: (seed, profile, steps) -------------------------------------------------------------------------
 CASES = [
@@ -44,7 +47,7 @@ CASES = [
     (7, "stream", 600),      # consecutive clouds of equal size and box, asynchronous steps
     (2, "wide", 600),        # rows of 128-511 neighbours
     (1, "device", 600),      # device-resident input
-    (2, "surface", 600),     # fans and triangles among frames, orientation, voxel down-sampling and plantings
+    (1, "surface", 600),     # fans, triangles and their filled holes among frames, orientation, voxel down-sampling and plantings
 ]
 
 _BASE = {
@@ -58,10 +61,12 @@ _BASE = {
     "curvatures_from_coefficients": 0.08, "slab_counts": 1.5, "slab_records": 1.5, "scatter_records": 1.5,
     "get_timings": 0.08, "get_timings_done": 0.08, "synchronize": 0.1,
     "point_triangles": 1.0, "get_point_fans": 0.6, "get_triangles": 0.8, "point_triangle_stats": 0.15,
+    "fill_holes": 1.0, "get_hole_triangles": 0.6, "get_filled_triangles": 0.6, "get_boundary_loops": 0.6, "fill_hole_stats": 0.15,
 }
 # operations only the profiles that name them draw, in state or out of it: the plans of the others are what they were
 # before these operations existed
-_NAMED_ONLY = ("point_triangles", "get_point_fans", "get_triangles", "point_triangle_stats")
+_NAMED_ONLY = ("point_triangles", "get_point_fans", "get_triangles", "point_triangle_stats",
+               "fill_holes", "get_hole_triangles", "get_filled_triangles", "get_boundary_loops", "fill_hole_stats")
 # profile -> (multipliers, cloud loaders with weights, cloud-size classes with weights, share of new clouds among the steps)
 PROFILES = {
     "core": ({}, {"set_points_f32": 1.0}, (0.35, 0.35, 0.3), 0.03),
@@ -82,7 +87,8 @@ PROFILES = {
              {"set_points_f32": 0.8, "set_points_f64": 0.2}, (0.15, 0.45, 0.4), 0.03),
     "device": ({"voxel_downsample_f32": 4, "pca_curvatures": 4, "get_pca": 2, "query_ball": 2, "get_ball": 2, "set_query_range": 3, "set_query_slab": 25},
                {"set_points_device": 0.5, "use_points_device": 0.5}, (0.3, 0.3, 0.4), 0.1),
-    "surface": ({"point_triangles": 2.5, "get_point_fans": 4, "get_triangles": 1.5, "point_triangle_stats": 1, "point_frames": 2, "orient_frames": 2,
+    "surface": ({"point_triangles": 2.5, "get_point_fans": 4, "get_triangles": 1.5, "point_triangle_stats": 2, "point_frames": 2, "orient_frames": 2,
+                 "fill_holes": 5, "get_hole_triangles": 3, "get_filled_triangles": 3, "get_boundary_loops": 3, "fill_hole_stats": 2,
                  "voxel_downsample": 5, "voxel_downsample_f32": 5, "surface_variation": 4, "pca_curvatures": 4, "set_query_range": 3, "set_query_slab": 25,
                  "fit": 1.5, "point_areas": 0.4, "get_point_areas": 0.4, "get_fit": 0.5},
                 {"set_points_f32": 0.85, "set_points_f64": 0.15}, (0.3, 0.3, 0.4), 0.05),
@@ -100,6 +106,7 @@ def _follow(s, name):
     """Random draws seldom finish a chain (table, fit, frames, orientation): a step that builds on what is resident is
     favoured, one that would drop it is held back -- a function of the model state, as every choice is."""
     if name in ("knn", "curvature"):
+        if s.holes is not None: return 1.0                      # (the hole results are there to be dropped with the triangles)
         return 0.4 if s.table is not None or s.slab_pass is not None else 1.0
     if name in ("set_query_range", "set_query_slab", "pca_curvatures", "surface_variation") and (s.areas is not None or s.frames is not None or s.triangles is not None):
         return 2.0                      # (what they must drop is there to be dropped)
@@ -107,6 +114,10 @@ def _follow(s, name):
         return 10.0 if s.orient is not None else 4.0                      # (the table goes, what was computed from it must stay)
     if s.triangles is not None and name in ("fit", "point_frames", "orient_frames", "voxel_downsample", "voxel_downsample_f32"):
         return 3.0                      # (the triangles must stay)
+    if name == "fill_holes" and s.holes is None:
+        return FILL_FOLLOW              # (the triangles are there: the chain table, triangles, holes is seldom finished otherwise)
+    if s.holes is not None and _PROBES.get(name) == "holes":
+        return HOLE_FOLLOW              # (short-lived: a planting or new triangles take them along)
     after_change = s.last is not None and bool(M.OPS[s.last].drops or M.OPS[s.last].creates)
     if after_change and M.OPS[name].pre and not (M.OPS[name].drops or M.OPS[name].creates):
         return 3.0                      # a getter right after a call that changes state: what it should have left is read
@@ -114,8 +125,10 @@ def _follow(s, name):
             "slab_counts": 3.0, "slab_records": 3.0, "scatter_records": 3.0}.get(name, 1.0)
 
 
+# calls that must leave the triangles and their hole results as they are: where the profile draws those, they are read next
+_KEEPS_FACES = ("fit", "fit_indices", "fit_ball", "point_frames", "orient_frames", "voxel_downsample", "voxel_downsample_f32", "point_areas")
 _GETTERS = {"table": "get_neighbors", "fit": "get_fit", "areas": "get_point_areas", "frames": "get_point_frames", "orient": "get_orientation",
-            "triangles": "get_triangles", "pca": "get_pca", "ball": "get_ball"}
+            "triangles": "get_triangles", "pca": "get_pca", "ball": "get_ball", "holes": "get_filled_triangles"}
 
 
 # ---- clouds (NumPy only: a sequence is generated without the package) ----------------------------------------------------
@@ -208,6 +221,8 @@ class Plan:
             have = [g for r, g in _GETTERS.items() if getattr(self.state, r) is not None and M.check(self.state, g, {})[0] == M.OK]
             if name == "point_triangles" and "get_triangles" in have: self.queue.append("get_triangles")      # (the result a refused call of it could take along)
             elif have: self.queue.append(have[int(rng.integers(len(have)))])
+        elif name in _KEEPS_FACES and self.mult.get("get_triangles", 1.0) > 0 and self.state.triangles is not None:
+            self.queue.append("get_filled_triangles" if self.state.holes is not None else "get_triangles")      # (what the call must have left as it was)
         return name, args, want
 
     def _pick_loader(self):
@@ -224,7 +239,7 @@ class Plan:
         probe = [c for c in cands if c[1] is None and _PROBES.get(c[0]) in s.just and M.first_unmet(s, c[0], {}).startswith(_PROBES[c[0]])]
         novel = [c for c in cands if count(c) < (2 if c[0] in _NAMED_ONLY else 1)]      # (what one profile alone draws is refused twice there)
         u = rng.random()
-        if probe and u < (1.0 if s.last in ("set_points_device", "use_points_device", "set_query_slab") else P_PROBE):                 # every getter of what was just dropped, one after the other
+        if probe and u < (1.0 if s.last in ("set_points_device", "use_points_device", "set_query_slab") or "holes" in s.just else P_PROBE):                 # every getter of what was just dropped, one after the other
             order = [probe[i] for i in rng.permutation(len(probe))]
             self.pool, self.queue = order[:1], [c[0] for c in order[1:]] + self.queue
         elif novel and u < (0.7 if s.slab else P_NOVEL): self.pool = novel
@@ -370,6 +385,13 @@ class Plan:
     def _a_get_triangles(self, v):
         lo, hi = np.sort(self.rng.random(2))              # (the plan does not know how many there are: a share of them)
         return {"share": (0.0, 1.0) if self.rng.random() < 0.3 else (float(lo), float(hi))}
+
+    def _a_fill_holes(self, v):
+        ext = float(np.ptp(self.pts, axis=0).max()) if self.pts is not None else 1.0
+        perimeter = float("inf") if self.rng.random() < 0.5 else ext * 10.0 ** self.rng.uniform(-1.5, 0.0)
+        return {"max_vertices": int(self.rng.choice([3, 4, 8, 32])), "max_perimeter": perimeter}
+
+    _a_get_hole_triangles = _a_get_filled_triangles = _a_get_triangles
 
     def _queries(self, m_far, m_on):
         rng, pts = self.rng, self.pts
@@ -539,6 +561,22 @@ class Reference:
             stats = f.point_triangle_stats()
             return f.get_triangles(0, stats["triangles"]), f.get_point_fans(0, self.n), stats
         return self._fresh(("triangles", t["k"], t["eps"], t["wind"], view, calls), work)
+
+    def holes(self, h):
+        """(patch triangles, filled triangles, boundary loops, statistics) for a resident's provenance: the triangles' and
+        the two caps of pct_fill_holes."""
+        t = h["triangles"]
+        view, calls = (t["frames"]["view"], t["orient"]["calls"] if t["orient"] else ()) if t["wind"] else (None, ())
+        def work(f):
+            if t["wind"]:
+                f.curvature(t["k"], t["eps"], KNN_BRUTE); f.point_frames(view)
+                for anchor, v, maxc in calls: f.orient_frames(anchor, v, maxc)
+            else: f.knn(t["k"], t["eps"], KNN_BRUTE)
+            f.point_triangles(t["wind"]); f.fill_holes(h["max_vertices"], h["max_perimeter"])
+            stats = f.fill_hole_stats()
+            total = f.point_triangle_stats()["triangles"] + stats["patch_triangles"]
+            return f.get_hole_triangles(0, stats["patch_triangles"]), f.get_filled_triangles(0, total), f.get_boundary_loops(), stats
+        return self._fresh(("holes", t["k"], t["eps"], t["wind"], view, calls, h["max_vertices"], h["max_perimeter"]), work)
 
     def study(self, k, rows, n_lo, n_hi):
         def work(f):
@@ -846,6 +884,37 @@ class Runner:
         counts = {k: v for k, v in out.items() if not k.endswith("ms")}
         if state.triangles is None: return None if not any(counts.values()) else f"{out} without triangles"
         want = {k: v for k, v in self.ref.triangles(state.triangles)[2].items() if not k.endswith("ms")}
+        if counts != want: return f"{counts}, a fresh handle counts {want}"
+
+    # -- boundary loops and small-hole filling ----------------------------------------------------------------------------
+    def do_fill_holes(self, a, s): self.h.fill_holes(a["max_vertices"], a["max_perimeter"])
+
+    def _hole_span(self, a, s, which):
+        total = len(self.ref.holes(s.holes)[which]) if s.holes is not None else 0
+        first = int(a["share"][0] * total)
+        return first, max(int(a["share"][1] * total) - first, 0)
+
+    def do_get_hole_triangles(self, a, s): return self.h.get_hole_triangles(*self._hole_span(a, s, 0))
+    def do_get_filled_triangles(self, a, s): return self.h.get_filled_triangles(*self._hole_span(a, s, 1))
+
+    def ck_get_hole_triangles(self, a, out, state, before, which=0):
+        first, count = self._hole_span(a, state, which)
+        if not same(out, self.ref.holes(state.holes)[which][first:first + count]):
+            return f"triangles [{first},{first + count}) of {M._brief(state.holes)} differ from a fresh handle's"
+
+    def ck_get_filled_triangles(self, a, out, state, before): return self.ck_get_hole_triangles(a, out, state, before, 1)
+
+    def do_get_boundary_loops(self, a, s): return self.h.get_boundary_loops()
+
+    def ck_get_boundary_loops(self, a, out, state, before):
+        if not same(out, self.ref.holes(state.holes)[2]): return f"loops of {M._brief(state.holes)} differ from a fresh handle's"
+
+    def do_fill_hole_stats(self, a, s): return self.h.fill_hole_stats()
+
+    def ck_fill_hole_stats(self, a, out, state, before):
+        counts = {k: v for k, v in out.items() if k != "ms"}
+        if state.holes is None: return None if not any(counts.values()) and out["ms"] == 0.0 else f"{out} without hole results"
+        want = {k: v for k, v in self.ref.holes(state.holes)[3].items() if k != "ms"}
         if counts != want: return f"{counts}, a fresh handle counts {want}"
 
     # -- queries of caller-supplied points, ball rows ---------------------------------------------------------------------

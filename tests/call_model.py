@@ -1,4 +1,4 @@
-"""The state rules of include/pct_hip.h as one table (pure Python, no GPU).
+"""The state rules of include/pct_hip.h and include/pct_hip_holes.h as one table (pure Python, no GPU).
 
 A `State` is what one handle holds -- the cloud, the owned range or slab, and the provenance of every resident result --
 and `OPS` says for every stateful entry point of `_capi.SIGNATURES` what it needs (`pre`: the conditions, in the
@@ -15,7 +15,7 @@ OK, INVALID, NO_NEIGHBORS, K_TOO_LARGE, LIMIT = "ok", "invalid", "no_neighbors",
 # a refusal as _capi.Handle._check raises it (PCT_ERR_LIMIT is returned by Handle.query_ball, not raised)
 RAISES = {INVALID: ValueError, NO_NEIGHBORS: AttributeError, K_TOO_LARGE: IndexError}
 
-RESIDENTS = ("table", "fit", "areas", "frames", "orient", "triangles", "pca", "ball", "slab_pass")      # (the library's eight, csrc/pct_residents.h, and the slab pass)
+RESIDENTS = ("table", "fit", "areas", "frames", "orient", "triangles", "pca", "ball", "holes", "slab_pass")      # (the library's nine, csrc/pct_residents.h, and the slab pass)
 TRI_WIND_FRAMES = 1            # pct_point_triangles' flag
 SLAB_MIN_N = 4096              # pct_set_query_slab: float32 clouds of >= 4096 points
 
@@ -35,6 +35,7 @@ class State:
         self.triangles = None    # {k, eps, lo, hi, wind, frames, orient}: the table's provenance, the flag and -- with the flag -- the frames' and the orientation's at the call
         self.pca = None          # {k, keep}
         self.ball = None         # {id, m, flags, centres}: the query's serial, its rows and flags, the cloud points its queries sit on
+        self.holes = None        # {triangles, max_vertices, max_perimeter}: the provenance of the triangles they were read off, and the two caps
         self.slab_pass = None    # {k, eps, part, parts}: a pct_curvature has run in slab mode
         self.async_on = False
         self.pending = False     # an asynchronous pct_curvature has been enqueued and not yet folded in
@@ -93,6 +94,7 @@ COND = {
     "frames": lambda s, a: s.frames is not None,
     "orient": lambda s, a: s.orient is not None,
     "triangles": lambda s, a: s.triangles is not None,
+    "holes": lambda s, a: s.holes is not None,
     "tri_flags": lambda s, a: not a.get("flags", 0) & ~TRI_WIND_FRAMES,
     "tri_frames": lambda s, a: not a.get("flags", 0) & TRI_WIND_FRAMES or s.frames is not None,
     "pca": lambda s, a: s.pca is not None,
@@ -123,11 +125,16 @@ class Op:
         self.folds = folds                     # waits for a pending asynchronous call first (almost everything)
 
 
-_PER_ROW = ("table", "fit", "areas", "frames", "orient", "triangles", "slab_pass")
+_PER_ROW = ("table", "fit", "areas", "frames", "orient", "triangles", "holes", "slab_pass")
 _ALL = RESIDENTS
 _Q_NEW = "drops every result on the handle: the table, the fit results, the areas, the frames, the orientation, the PCA results and the ball rows"
 _Q_OWN = "drop what is computed per owned row: the table, the fit results, the areas, the frames and the orientation"
 _Q_TRI = "A new cloud, a change of ownership and every planting drop the triangles"
+# (include/pct_hip_holes.h, "State")
+_Q_HOLES = "Whatever drops the triangles -- a new cloud, a change of ownership, a planting -- drops them, and so does a new pct_point_triangles"
+_Q_HOLES_KEPT = "a fit, pct_point_frames, pct_orient_frames and pct_voxel_downsample drop neither"
+_Q_NO_HOLES = "PCT_ERR_INVALID without hole results"
+_Q_HOLES_WHOLE = "PCT_ERR_INVALID without triangles, as pct_get_triangles, and on a handle that owns a slab or a proper sub-range"
 _Q_OWN_KEEPS = "Ball rows and PCA results answer for the whole cloud and are untouched by a change of ownership"
 _Q_PLANT = "drop the table in place, the fit results, the areas, the frames and the orientation"
 _Q_PLANT_KEEPS = "Ball rows are untouched by a planting, and so are PCA results unless the planting is pct_pca_curvatures"
@@ -202,6 +209,10 @@ def _c_triangles(s, a):
     s.triangles = dict(s.table, wind=wind, frames=s.frames if wind else None, orient=s.orient if wind else None)
 
 
+def _c_holes(s, a):
+    s.holes = {"triangles": s.triangles, "max_vertices": a["max_vertices"], "max_perimeter": a["max_perimeter"]}
+
+
 def _c_ball(s, a):
     if a.get("max_entries", 0) == 1 or a["flags"] & 4:      # capped, or PCT_BALL_COUNT_ONLY: nothing is kept
         return
@@ -229,7 +240,7 @@ _getter = dict(header=(_Q_SIDE,))
 
 OPS = {
     # ---- clouds --------------------------------------------------------------------------------------------------------
-    "set_points_f32": Op(["pct_set_points_f32"], drops=_ALL, creates=_new_cloud("host", "f32"), header=(_Q_NEW, _Q_TRI, "It ends slab mode and owns the whole cloud", _Q_SETTINGS)),
+    "set_points_f32": Op(["pct_set_points_f32"], drops=_ALL, creates=_new_cloud("host", "f32"), header=(_Q_NEW, _Q_TRI, _Q_HOLES, "It ends slab mode and owns the whole cloud", _Q_SETTINGS)),
     "set_points_f64": Op(["pct_set_points_f64"], drops=_ALL, creates=_new_cloud("host", "f64"), header=(_Q_NEW,)),
     "set_points_device": Op(["pct_device_alloc", "pct_device_upload", "pct_set_points_device_f32", "pct_device_free"], drops=_ALL,
                             creates=_new_cloud("device_copy", "f32"), header=(_Q_NEW,)),
@@ -238,7 +249,7 @@ OPS = {
                             header=(_Q_NEW, "The buffer must stay allocated and unchanged until the next pct_set_points_* / pct_use_points_* call")),
     # ---- ownership -----------------------------------------------------------------------------------------------------
     "set_query_range": Op(["pct_set_query_range"], pre=[("cloud", INVALID, "pct_set_query_range and pct_set_query_slab need a cloud (PCT_ERR_INVALID)")],
-                          drops=_PER_ROW, creates=_c_range, header=(_Q_OWN, _Q_TRI, _Q_OWN_KEEPS, "also where the range is the one already set",
+                          drops=_PER_ROW, creates=_c_range, header=(_Q_OWN, _Q_TRI, _Q_HOLES, _Q_OWN_KEEPS, "also where the range is the one already set",
                                                                     "ends with pct_set_query_range, a new cloud or pct_set_query_slab(parts <= 0)")),
     "set_query_slab": Op(["pct_set_query_slab"], pre=[("cloud", INVALID, "pct_set_query_range and pct_set_query_slab need a cloud (PCT_ERR_INVALID)"),
                                                       ("slab_cloud", INVALID, "float32 clouds of >= 4096 points")],
@@ -249,7 +260,7 @@ OPS = {
     "set_async": Op(["pct_set_async"], creates=_setting("async_on"), header=(_Q_SETTINGS, _Q_ASYNC)),
     # ---- plantings and fits --------------------------------------------------------------------------------------------
     "knn": Op(["pct_knn"], pre=[("cloud", INVALID, _Q_PLANT_CLOUD), _slab], drops=_PER_ROW, creates=_c_knn,
-              header=(_Q_PLANT, _Q_TRI, _Q_PLANT_KEEPS, "pct_knn leaves its table")),
+              header=(_Q_PLANT, _Q_TRI, _Q_HOLES, _Q_PLANT_KEEPS, "pct_knn leaves its table")),
     "curvature": Op(["pct_curvature"], pre=[("cloud", INVALID, _Q_PLANT_CLOUD), ("slab_algo", INVALID, "pct_curvature refuses every algo but PCT_KNN_AUTO and PCT_KNN_GRID")],
                     drops=_PER_ROW, creates=_c_curvature, header=(_Q_PLANT, _Q_PLANT_KEEPS, "pct_curvature leaves its table and the cloud-aligned fit of it", _Q_FIT, _Q_ASYNC),
                     variants=(None, {"algo": 1})),
@@ -295,12 +306,20 @@ OPS = {
                           pre=[_slab, ("table", NO_NEIGHBORS, _Q_TABLE), ("whole", INVALID, "PCT_ERR_INVALID for an owned range, as pct_orient_frames"),
                                ("tri_flags", INVALID, "Unknown flag bits: PCT_ERR_INVALID"),
                                ("tri_frames", INVALID, 'PCT_TRI_WIND_FRAMES without resident frames: PCT_ERR_INVALID "no point frames"')],
-                          drops=("triangles",), creates=_c_triangles, variants=(None, {"flags": 64}, {"flags": TRI_WIND_FRAMES}),
-                          header=("pct_point_triangles replaces the fans and triangles and touches nothing else", _Q_TRI,
+                          drops=("triangles", "holes"), creates=_c_triangles, variants=(None, {"flags": 64}, {"flags": TRI_WIND_FRAMES}),
+                          header=("pct_point_triangles replaces the fans and triangles and touches nothing else", _Q_TRI, _Q_HOLES,
                                   "a fit, pct_point_frames, pct_orient_frames and pct_voxel_downsample do not", "the winding is a snapshot of the flipped bits at the call", _Q_REFUSED)),
     "get_point_fans": Op(["pct_get_point_fans"], pre=[("triangles", INVALID, "pct_get_point_fans and pct_get_triangles PCT_ERR_INVALID without triangles")], **_getter),
     "get_triangles": Op(["pct_get_triangles"], pre=[("triangles", INVALID, "pct_get_point_fans and pct_get_triangles PCT_ERR_INVALID without triangles")], **_getter),
     "point_triangle_stats": Op(["pct_point_triangle_stats"], folds=False, **_getter),
+    # ---- boundary loops and small-hole filling (include/pct_hip_holes.h): made from the triangles ----------------------------
+    "fill_holes": Op(["pct_fill_holes"], pre=[("not_slab", INVALID, _Q_HOLES_WHOLE), ("whole", INVALID, _Q_HOLES_WHOLE), ("triangles", INVALID, _Q_HOLES_WHOLE)],
+                     drops=("holes",), creates=_c_holes,
+                     header=("pct_fill_holes touches nothing else on the handle", _Q_HOLES_KEPT, "A refused call changes nothing: the hole results of an earlier call stay")),
+    "get_hole_triangles": Op(["pct_get_hole_triangles"], pre=[("holes", INVALID, _Q_NO_HOLES)], header=(_Q_HOLES,)),
+    "get_filled_triangles": Op(["pct_get_filled_triangles"], pre=[("holes", INVALID, _Q_NO_HOLES)], header=(_Q_HOLES,)),
+    "get_boundary_loops": Op(["pct_get_boundary_loops"], pre=[("holes", INVALID, _Q_NO_HOLES)], header=(_Q_HOLES,)),
+    "fill_hole_stats": Op(["pct_fill_hole_stats"], folds=False, header=("Zeros without hole results",)),
     # ---- queries of caller-supplied points, ball rows ------------------------------------------------------------------
     "query_points": Op(["pct_query_points"], pre=[_slab, _cloud], **_getter),
     "query_points_algo": Op(["pct_query_points_algo"], pre=[_slab, _cloud],

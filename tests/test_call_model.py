@@ -65,6 +65,9 @@ KEEPS = {
     "a planting keeps the triangles": (("knn", "curvature", "surface_variation", "pca_curvatures"), ("triangles",)),
     "a change of ownership keeps the triangles": (("set_query_range", "set_query_slab"), ("triangles",)),
     "a new cloud keeps the triangles": (D._CLOUD_OPS, ("triangles",)),
+    "a new pct_point_triangles keeps the hole results": (("point_triangles",), ("holes",)),
+    "a planting keeps the hole results": (("knn", "curvature", "surface_variation", "pca_curvatures"), ("holes",)),
+    "a change of ownership keeps the hole results": (("set_query_range", "set_query_slab"), ("holes",)),
 }
 # defect -> (operations, residents the operation wrongly drops)
 DROPS = {
@@ -78,6 +81,9 @@ DROPS = {
     "pct_point_frames drops the triangles": (("point_frames",), ("triangles",)),
     "pct_orient_frames drops the triangles": (("orient_frames",), ("triangles",)),
     "voxel_downsample drops the triangles": (("voxel_downsample", "voxel_downsample_f32"), ("triangles",)),
+    "a fit drops the hole results": (("fit", "fit_indices", "fit_ball"), ("holes",)),
+    "pct_point_frames drops the hole results": (("point_frames",), ("holes",)),
+    "voxel_downsample drops the hole results": (("voxel_downsample", "voxel_downsample_f32"), ("holes",)),
 }
 SPECIAL = ["fit_indices results served as cloud-aligned", "PCA leaves its over-fetched table valid", "query_points through the cell list disturbs the table",
            "fit_ball disturbs the ball rows", "a refused call changes state", "an async read served before the pending call is folded in",
@@ -381,6 +387,42 @@ class FakeHandle:
         tri, off, _ = self._triangles()
         return {**{k: 1 for k in names}, "rows": self.s.n, "triangles": len(tri), "largest_fan": int(np.diff(off).max()), "ms": 0.1, "fan_ms": 0.05, "agree_ms": 0.05}
 
+    # -- boundary loops and small-hole filling ----------------------------------------------------------------------------
+    def fill_holes(self, max_vertices=32, max_perimeter=float("inf"), flags=0):
+        self._call("fill_holes", {"max_vertices": int(max_vertices), "max_perimeter": float(max_perimeter)})
+
+    def _holes(self):
+        """(patches, filled, (loop offsets, vertices, status)) hashed from the provenance: 0-2 patches and 0-1 loops per row."""
+        h, n = self.s.holes, self.s.n
+        t = h["triangles"]
+        sd = _seed("holes", self._key(), t["k"], t["eps"], t["wind"], t["frames"], t["orient"], h["max_vertices"], h["max_perimeter"])
+        if ("holes", sd) not in self.memo:
+            rows = np.arange(n)
+            v0 = np.repeat(rows, (_mix(sd, rows) % np.uint64(3)).astype(np.int64))
+            patch = np.stack([v0, _mix(sd + 1, np.arange(len(v0))) % np.uint64(n), _mix(sd + 2, np.arange(len(v0))) % np.uint64(n)], axis=1).astype(np.int32)
+            filled = np.concatenate([patch, (patch + 1) % n]).astype(np.int32)
+            loops = int(_mix(sd + 3, 0) % np.uint64(min(n, 7)))
+            off = 3 * np.arange(loops + 1, dtype=np.int64)
+            verts = (_mix(sd + 4, np.arange(3 * loops)) % np.uint64(n)).astype(np.int32)
+            self.memo["holes", sd] = patch, filled, (off, verts, (_mix(sd + 5, np.arange(loops)) % np.uint64(3)).astype(np.uint8))
+        return self.memo["holes", sd]
+
+    def _hole_rows(self, name, which, first, count):
+        self._call(name, {})
+        tri = self._holes()[which]
+        return tri[first:] if count is None else tri[first:first + count]
+
+    def get_hole_triangles(self, first=0, count=None): return self._hole_rows("get_hole_triangles", 0, first, count)
+    def get_filled_triangles(self, first=0, count=None): return self._hole_rows("get_filled_triangles", 1, first, count)
+    def get_boundary_loops(self): self._call("get_boundary_loops", {}); return self._holes()[2]
+
+    def fill_hole_stats(self):
+        self._call("fill_hole_stats", {})
+        names = ("boundary_edges", "gaps", "odd_gaps", "loops", "filled", "perimeter", "blocked", "patch_triangles")
+        if self.s.holes is None: return {**{k: 0 for k in names}, "ms": 0.0}
+        patch, _, (off, _, status) = self._holes()
+        return {**{k: 1 for k in names}, "loops": len(off) - 1, "filled": int((status == 0).sum()), "patch_triangles": len(patch), "ms": 0.1}
+
     # -- queries ----------------------------------------------------------------------------------------------------------
     def _query(self, name, q, k, eps, algo):
         self._call(name, {"algo": algo})
@@ -477,7 +519,7 @@ class FakeHandle:
 
 # ---- the tests -----------------------------------------------------------------------------------------------------------
 def _header():
-    text = open(os.path.join(ROOT, "include", "pct_hip.h")).read()
+    text = "".join(open(os.path.join(ROOT, "include", h)).read() for h in ("pct_hip.h", "pct_hip_holes.h"))
     return " ".join(" ".join(re.sub(r"^\s*/?\*+/?\s?", "", line) for line in text.splitlines()).split())
 
 
@@ -489,7 +531,7 @@ def test_every_model_rule_quotes_a_sentence_of_the_header():
 
 
 def test_every_entry_point_is_modelled_or_excluded(built):
-    names = set(built["capi"].SIGNATURES)
+    names = set(built["capi"].SIGNATURES) | set(built["capi"].HOLE_SIGNATURES)
     modelled, excluded = set(M.modelled_entry_points()), set(M.EXCLUDED)
     assert not modelled & excluded, sorted(modelled & excluded)
     assert names - modelled - excluded == set(), f"decide where these belong (tests/call_model.py): {sorted(names - modelled - excluded)}"

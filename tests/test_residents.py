@@ -1,7 +1,8 @@
 """The library's table of resident results (csrc/pct_residents.h) against the header's state rules and tests/call_model.py, on the CPU.
 
 A stand-alone program that includes nothing but that header prints, for every event, the residents it drops; for every
-`leave`, the residents it replaces (the one left and what was derived from it); and three short histories of a handle.
+`leave`, the residents it replaces (the one left and what was derived from it); three short histories of a handle; and the
+rows and the order the table records for the fit through a fourth.
 The expected sets are written out by hand from the sentences of include/pct_hip.h, and each is then held equal to the
 `drops` of every operation of `call_model.OPS` that stands for it -- the mapping is written out below, one line per operation."""
 import os
@@ -40,7 +41,7 @@ int main() {
     for (int b = 0; b < kPctResidents; ++b) {          // a handle that holds everything: what is gone after leave(r), r itself made anew
         pct_residents all;
         all.live = kPctEveryResident;
-        all.leave((pct_resident)(1u << b), false);
+        all.leave((pct_resident)(1u << b), false, 1);
         char what[64];
         snprintf(what, sizeof(what), "leave %s", kPctResidentNames[b]);
         show(what, (kPctEveryResident & ~all.live) | 1u << b);
@@ -48,36 +49,44 @@ int main() {
     }
 
     pct_residents h;                                   // pct_curvature, pct_point_frames, pct_orient_frames, then pct_fit
-    h.leave(PCT_R_TABLE, true);
-    h.leave(PCT_R_FIT, true);
-    h.leave(PCT_R_FRAMES, true);
-    h.leave(PCT_R_ORIENT, false);
+    h.leave(PCT_R_TABLE, true, 10);
+    h.leave(PCT_R_FIT, true, 10);
+    h.leave(PCT_R_FRAMES, true, 10);
+    h.leave(PCT_R_ORIENT, false, 10);
     show_handle("oriented", h);
-    h.leave(PCT_R_FIT, true);
+    h.leave(PCT_R_FIT, true, 10);
     show_handle("fit_again", h);
 
     pct_residents g;                                   // everything in place, then pct_point_frames again
     g.live = kPctEveryResident;
-    g.leave(PCT_R_FRAMES, false);
+    g.leave(PCT_R_FRAMES, false, 10);
     show_handle("frames_again", g);
 
     pct_residents a;                                   // pct_knn through a cell list, pct_point_areas, pct_voxel_downsample, a new planting by the exhaustive sweep
-    a.leave(PCT_R_TABLE, true);
-    a.leave(PCT_R_AREAS, true);
-    a.leave(PCT_R_BALL, false);
+    a.leave(PCT_R_TABLE, true, 10);
+    a.leave(PCT_R_AREAS, true, 10);
+    a.leave(PCT_R_BALL, false, 10);
     show_handle("areas_by_row", a);
     a.drop(PCT_TABLE_LOST);
     show_handle("table_lost", a);
     a.drop(PCT_PLANTING);
     show_handle("planted", a);
-    a.leave(PCT_R_TABLE, false);
+    a.leave(PCT_R_TABLE, false, 10);
     show_handle("brute_table", a);
+
+    pct_residents f;                                   // a fit in table-row order, a planting, a fit of seven caller rows
+    f.leave(PCT_R_FIT, true, 100);
+    printf("fit_by_row: %lld %d\n", (long long)f.rows_of(PCT_R_FIT), (int)f.in_row_order(PCT_R_FIT));
+    f.drop(PCT_PLANTING);
+    printf("fit_dropped: %lld %d\n", (long long)f.rows_of(PCT_R_FIT), (int)f.in_row_order(PCT_R_FIT));
+    f.leave(PCT_R_FIT, false, 7);
+    printf("fit_public: %lld %d\n", (long long)f.rows_of(PCT_R_FIT), (int)f.in_row_order(PCT_R_FIT));
     return 0;
 }
 """
 
-ALL = {"table", "fit", "areas", "frames", "orient", "triangles", "pca", "ball"}
-PER_ROW = {"table", "fit", "areas", "frames", "orient", "triangles"}
+ALL = {"table", "fit", "areas", "frames", "orient", "triangles", "pca", "ball", "holes"}
+PER_ROW = {"table", "fit", "areas", "frames", "orient", "triangles", "holes"}
 # by the header: "A new cloud ... drops every result on the handle"; "Ownership ... drop what is computed per owned row: the
 # table, the fit results, the areas, the frames and the orientation, and the triangles"; "Plantings ... drop the table in
 # place, the fit results, the areas, the frames and the orientation, and the triangles"; "pct_voxel_downsample ... drop the
@@ -85,9 +94,11 @@ PER_ROW = {"table", "fit", "areas", "frames", "orient", "triangles"}
 DROPS = {"new_cloud": ALL, "ownership": PER_ROW, "planting": PER_ROW, "table_lost": {"table"}, "table_and_fit_lost": {"table", "fit"}}
 # "Fits ... replace the fit results and drop the frames and the orientation"; "pct_point_areas replaces the areas and touches
 # nothing else"; "pct_point_frames replaces the frames, drops the orientation and touches nothing else"; "pct_orient_frames
-# ... replaces the orientation"; "pct_point_triangles replaces the fans and triangles and touches nothing else"
+# ... replaces the orientation"; "pct_point_triangles replaces the fans and triangles and touches nothing else"; and by
+# include/pct_hip_holes.h: "Whatever drops the triangles ... drops them, and so does a new pct_point_triangles";
+# "pct_fill_holes touches nothing else on the handle"
 LEAVES = {"table": {"table"}, "fit": {"fit", "frames", "orient"}, "areas": {"areas"}, "frames": {"frames", "orient"}, "orient": {"orient"},
-          "triangles": {"triangles"}, "pca": {"pca"}, "ball": {"ball"}}
+          "triangles": {"triangles", "holes"}, "pca": {"pca"}, "ball": {"ball"}, "holes": {"holes"}}
 # operation of call_model.OPS -> the events and leaves one successful call of it goes through in the library
 STANDS_FOR = {
     "set_points_f32": ("drop new_cloud",),
@@ -106,6 +117,7 @@ STANDS_FOR = {
     "point_areas": ("leave areas",),
     "point_frames": ("leave frames",),
     "point_triangles": ("leave triangles",),
+    "fill_holes": ("leave holes",),
     "query_ball": ("leave ball",),
     "voxel_downsample": ("drop table_lost",),
     "voxel_downsample_f32": ("drop table_lost",),
@@ -163,6 +175,13 @@ def test_a_fit_over_frames_and_an_orientation_leaves_neither(out):
 
 def test_frames_again_drop_the_orientation_and_nothing_else(out):
     assert set(out["frames_again"]) == ALL - {"orient"}
+
+
+def test_rows_and_order_leave_with_the_result(out):
+    """What a flag beside the table allowed: the order of a dropped fit read as that of the next."""
+    assert out["fit_by_row"] == ["100", "1"]
+    assert out["fit_dropped"] == ["0", "0"]
+    assert out["fit_public"] == ["7", "0"]
 
 
 def test_nothing_is_in_cell_order_once_the_only_row_ordered_resident_is_dropped(out):
