@@ -582,7 +582,7 @@ static int run_knn(pct_ctx* ctx, int32_t k, double eps, int32_t asked, pct_call_
     // 3. the uniform list (PCT_KNN_GRID, PCT_KNN_GRID_EXACT) -- and whether PCT_KNN_AUTO keeps it
     const bool tree_reachable = may_give_up(rq, ctx->n, sw);
     GridVerdict built;
-    PCT_TRY(pct_build_grid(ctx, k, eps, tree_reachable, &built, &clock));
+    PCT_TRY(pct_build_grid(ctx, k, eps, tree_reachable, &built, &clock, nullptr));
     Route route = built == GridVerdict::GaveUp ? Route::Tree : Route::Stay;      // (not built: far too many cells per point)
     if (built == GridVerdict::Built && skew_gate(rq, whole, ctx->n, ctx->nonempty_cells, sw)) {
         PCT_TRY(examine_uniform_list(ctx, k, tree_reachable, &route));
@@ -599,7 +599,7 @@ static int run_knn(pct_ctx* ctx, int32_t k, double eps, int32_t asked, pct_call_
     if (route == Route::Levels) return sweep_levels(ctx, k, eps, fuse_par, clock, done);
     // 4. the sweep
     PCT_HIP(ctx, clock.boundary(PCT_ST_GRID_END, ctx->stream));
-    PCT_TRY(pct_launch_knn_grid(ctx, k, eps, algo == PCT_KNN_GRID_EXACT, 0, want_dist, &clock));
+    PCT_TRY(pct_launch_knn_grid(ctx, k, eps, algo == PCT_KNN_GRID_EXACT, 0, want_dist, &clock, nullptr));
     PCT_HIP(ctx, clock.boundary(PCT_ST_SWEEP_END, ctx->stream));
     ctx->tm.knn_launches = 1;
     table_left(ctx, false);
@@ -895,7 +895,7 @@ static int build_query_grid(pct_ctx* ctx, int32_t kb, const char* who) {
     if ((int64_t)kb + 1 > ctx->n) kb = ctx->n > 1 ? (int32_t)ctx->n - 1 : 1;
     const pct_timings keep = ctx->tm;
     GridVerdict built;
-    const int st = pct_build_grid(ctx, kb, 0.0, false, &built);
+    const int st = pct_build_grid(ctx, kb, 0.0, false, &built, nullptr, nullptr);
     ctx->tm = keep;
     ctx->counters_clean = false;       // (the words the build cleared belong to no sweep of this call)
     if (st != PCT_OK) return st;       // (every refusal of the build is the caller's to see: none is turned into another route)

@@ -1471,48 +1471,33 @@ int pct_pack_points_f64(pct_ctx* ctx, const double* d_xyz64) {
     return PCT_OK;
 }
 
-// ---- where the grid's points come from ---------------------------------------------------------------------------------
-enum class GridSource {
-    LevelBase,     // later passes of the density-adaptive sweep: the points in the cell order of its first pass, and that pass's box
-    CulledPack,    // sharded handle: the owned rows and the points near them (pack_near_owned)
-    CallerRows,    // the caller's rows on the (trimmed) box of the previous similar cloud; this cloud's box is checked later
-    FullPack,      // every point, packed and measured first
-};
-
+// ---- where the grid's points come from (GridSource, choose_source: pct_grid_edge.h) --------------------------------------
 struct GridPoints {
     GridSource src;
     float bbox[6];           // grid box
     PackRed red;             // the pack pass's record (CallerRows: filled in by check_deferred_box)
     Box3 kept_box;           // CulledPack: the box that was applied
     int64_t n;               // points the grid holds
-    int g_begin, g_end;      // the owned range of the grid's records (0, 0: ownership by own_flag)
+    int g_begin, g_end;      // the owned range of the grid's records (0, 0: ownership by wanted edge)
     bool raw;                // the histogram and the placement read the caller's rows (k_bin_*<true>, k_hist_raw, k_scatter_raw)
     bool from_base;          // ... or the level base (k_hist_agg)
     bool deferred_box;       // the cloud's own box rides on the first pass and has not been checked yet
 };
 
-// Decides the source from ctx and runs its pack pass.  *restart: the kept part cannot fill a row; culling is ruled out
-// on the handle and the caller starts over.
+// Decides the source (choose_source) from ctx and the pass and runs its pack pass.  *restart: the kept part cannot fill a
+// row; culling is ruled out on the handle and the caller starts over.
 // clock (may be null): the call's begin -- the full pack's kernel takes its word; every other pack pass has its event in front.
-static int select_source(pct_ctx* ctx, int32_t k, double target, bool slab, int64_t n_owned, bool sharded, GridPoints* s, bool* restart,
-                         pct_call_clock* clock) {
-    const bool own_flag = ctx->own_flag != nullptr;
-    // (a slab's owned points are found by the pack itself: it always runs, with an open box after a limit retry)
-    const bool try_cull = slab ? n_owned > 0
-                               : !own_flag && sharded && n_owned > 0 && !ctx->has_f64 && !ctx->no_cull && !pct_getenv("PCT_NO_CULL");
-    // Speculation: a handle fed a stream of similar clouds builds the cell list over the (trimmed) box of the previous
-    // call without waiting for the new bounding box -- any box is a valid grid box, points outside are clamped into
-    // the boundary cells -- and checks the new box at the synchronisation that ends the first pass.  One host round
-    // trip less per build.
-    const bool spec = !try_cull && !own_flag && !ctx->level_mode && ctx->hint_edge > 0 && ctx->spec_valid && ctx->spec_n == ctx->n &&
-                      !pct_getenv("PCT_NO_SPEC");
+static int select_source(pct_ctx* ctx, int32_t k, double target, bool slab, int64_t n_owned, bool sharded, const LevelPass* pass,
+                         GridPoints* s, bool* restart, pct_call_clock* clock) {
+    const bool by_want = pass && pass->want;
     *s = GridPoints{};
-    s->src = own_flag && ctx->lvl_src_valid ? GridSource::LevelBase : try_cull ? GridSource::CulledPack : spec ? GridSource::CallerRows
-                                                                                                               : GridSource::FullPack;
+    s->src = choose_source({by_want, pass && pass->base, pass != nullptr, slab, sharded, n_owned, ctx->has_f64, ctx->no_cull,
+                            pct_getenv("PCT_NO_CULL") != nullptr, pct_getenv("PCT_NO_SPEC") != nullptr, ctx->hint_edge, ctx->spec_valid,
+                            ctx->spec_n, ctx->n});
     if (clock && s->src != GridSource::CallerRows && s->src != GridSource::FullPack) PCT_HIP(ctx, clock->begin_event(ctx->stream));
     switch (s->src) {
     case GridSource::LevelBase:
-        for (int a = 0; a < 6; ++a) s->bbox[a] = ctx->lvl_bbox[a];
+        for (int a = 0; a < 6; ++a) s->bbox[a] = pass->base_box[a];
         ctx->n_grid = ctx->n;
         ctx->g_begin = 0;
         ctx->culled = false;
@@ -1547,8 +1532,8 @@ static int select_source(pct_ctx* ctx, int32_t k, double target, bool slab, int6
     s->raw = s->deferred_box = s->src == GridSource::CallerRows;
     s->from_base = s->src == GridSource::LevelBase;
     s->n = ctx->n_grid;
-    s->g_begin = own_flag ? 0 : (int)ctx->g_begin;
-    s->g_end = own_flag ? 0 : (int)(ctx->g_begin + n_owned);
+    s->g_begin = by_want ? 0 : (int)ctx->g_begin;
+    s->g_end = by_want ? 0 : (int)(ctx->g_begin + n_owned);
     return PCT_OK;
 }
 
@@ -1568,13 +1553,13 @@ static BoxCheck check_deferred_box(pct_ctx* ctx, GridPoints* s) {
 }
 
 // ---- the grid of one pass ----------------------------------------------------------------------------------------------
-// The box and the dimensions for edge a.  sub_box (a fast level pass): 2.5 edges of THIS cell size around the owned
-// points (their stencils must end inside the box: the points outside it are left out of the cell list).
-static void size_grid(const pct_ctx* ctx, bool sub_box, float* bbox, double a, pct_grid* g) {
+// The box and the dimensions for edge a.  sub_box (a fast level pass: the box of its owned points, else null): 2.5 edges
+// of THIS cell size around them (their stencils must end inside the box: the points outside it are left out of the cell list).
+static void size_grid(const float* sub_box, float* bbox, double a, pct_grid* g) {
     if (sub_box)
         for (int ax = 0; ax < 3; ++ax) {
-            bbox[ax] = ctx->level_box[ax] - (float)(2.5 * a);
-            bbox[3 + ax] = ctx->level_box[3 + ax] + (float)(2.5 * a);
+            bbox[ax] = sub_box[ax] - (float)(2.5 * a);
+            bbox[3 + ax] = sub_box[3 + ax] + (float)(2.5 * a);
         }
     g->ox = bbox[0]; g->oy = bbox[1]; g->oz = bbox[2];
     g->cell = a;
@@ -1598,33 +1583,33 @@ static void size_grid(const pct_ctx* ctx, bool sub_box, float* bbox, double a, p
 }
 
 // what every pass of a build writes, sized by the points and not by the grid
-static int reserve_lists(pct_ctx* ctx, int64_t n, int64_t n_owned) {
+static int reserve_lists(pct_ctx* ctx, int64_t n, int64_t n_owned, bool by_want) {
     PCT_TRY(pct_reserve(ctx, &ctx->cell_of, (size_t)n * sizeof(int)));
     PCT_TRY(pct_reserve(ctx, &ctx->cell_fill, (size_t)n * sizeof(int)));   // in-cell arrival ranks
     PCT_TRY(pct_reserve(ctx, &ctx->sorted4, (size_t)n * sizeof(float4)));
-    PCT_TRY(pct_reserve(ctx, &ctx->row_of, (size_t)((ctx->own_flag ? n : n_owned) + 1) * sizeof(int)));
+    PCT_TRY(pct_reserve(ctx, &ctx->row_of, (size_t)((by_want ? n : n_owned) + 1) * sizeof(int)));
     PCT_TRY(pct_reserve(ctx, &ctx->owned_pos, (size_t)n_owned * sizeof(int)));
     if (ctx->has_f64) PCT_TRY(pct_reserve(ctx, &ctx->sorted4d, (size_t)n * sizeof(double4)));
     return PCT_OK;
 }
 
 // the cell-size search of one build (pct_grid_edge.h) on the box of its source and the handle's warm start
-static EdgeSearch edge_search(const pct_ctx* ctx, const GridPoints& s, double target, double eps) {
+static EdgeSearch edge_search(const pct_ctx* ctx, const GridPoints& s, double target, double eps, const LevelPass* pass) {
     EdgeSearch es = {};
     es.target = target; es.n = s.n; es.eps = eps;
     es.ex = (double)s.bbox[3] - s.bbox[0]; es.ey = (double)s.bbox[4] - s.bbox[1]; es.ez = (double)s.bbox[5] - s.bbox[2];
     es.hint_edge = ctx->hint_edge; es.hint_guess = ctx->hint_guess; es.hint_target = ctx->hint_target;
-    es.level_edge = ctx->level_edge;
+    es.level_edge = pass ? pass->edge : 0;
     // a level pass takes the edge it is given: its owned set is a mix of densities, and the mean population the search
     // steers on would be pulled to the dense minority (pct_levels.hip sizes by the geometric mean instead)
-    es.max_iter = es.level_edge > 0 ? 1 : ctx->level_mode ? 2 : 8;
+    es.max_iter = es.level_edge > 0 ? 1 : pass ? 2 : 8;
     return es;
 }
 
 // ---- which build, and its launches -------------------------------------------------------------------------------------
 // Dispatch: the two-level LDS counting sort (k_bin_*) wherever a grid point is owned or not by its public index alone and
 // every point is binned -- the caller's rows, the full pack, the range-culled pack -- and the bucket scheme covers the
-// grid (bin_shape, per pass).  The level passes (own_flag, sub_box), the slab-owned handles and larger grids keep the
+// grid (bin_shape, per pass).  The level passes (by wanted edge, sub_box), the slab-owned handles and larger grids keep the
 // per-point atomics; PCT_GRID_ATOMIC=1 forces those everywhere (A/B runs, parity tests).
 enum class GridBuild {
     Bin,             // k_bin_count, k_bin_colscan, k_bin_plan, k_bin_scatter, k_bin_cells | k_bin_place
@@ -1677,6 +1662,7 @@ struct GridPass {
     BinScratch bin;
     const float4* src;       // packed records (pts4 or the level base)
     int64_t n_owned;
+    const LevelPass* level;  // the pass of the chained sweep that asked for the build (null: a plain call)
     bool sharded, sub_box;
     int items_q;             // queries per work item of the sweep
     int64_t occ_cap;         // entries of the sweep's work list (occ) that are reserved
@@ -1701,7 +1687,7 @@ static void launch_bin_scatter(pct_ctx* ctx, int64_t n, const GridPass& p, int* 
 static int launch_count(pct_ctx* ctx, const GridPoints& s, GridPass& p, pct_call_clock* clock) {
     const pct_grid& g = p.g;
     const int64_t n = s.n;
-    const float* own_flag = (const float*)ctx->own_flag;
+    const LevelPass no_pass, &lv = p.level ? *p.level : no_pass;         // (no wanted-edge array: ownership by the records' index range)
     const bool bin = p.build == GridBuild::Bin;            // (writes every counter itself: no clearing fill)
     PCT_TRY(pct_reserve(ctx, &ctx->cell_own, (size_t)g.ncell * sizeof(int)));
     if (clock && !bin) PCT_HIP(ctx, clock->begin_event(ctx->stream));
@@ -1731,10 +1717,10 @@ static int launch_count(pct_ctx* ctx, const GridPoints& s, GridPass& p, pct_call
                    (int*)ctx->cell_fill.p, (int*)ctx->cell_own.p, cell_oth, parts);
         if (parts) PCT_TRY(red_fold(ctx, nhb, false));
     } else if (p.build == GridBuild::AtomicBase) {
-        PCT_LAUNCH(k_hist_agg, dim3(nhb), dim3(kBlock), 0, ctx->stream, p.src, n, g, own_flag, ctx->own_lo, ctx->own_hi, p.sub_box ? 1 : 0,
+        PCT_LAUNCH(k_hist_agg, dim3(nhb), dim3(kBlock), 0, ctx->stream, p.src, n, g, lv.want, lv.lo, lv.hi, p.sub_box ? 1 : 0,
                    (int*)ctx->cell_of.p, (int*)ctx->cell_fill.p, (int*)ctx->cell_own.p, (int*)ctx->cell_oth.p);
     } else {
-        PCT_LAUNCH(k_hist, dim3(nhb), dim3(kBlock), 0, ctx->stream, p.src, n, g, s.g_begin, s.g_end, own_flag, ctx->own_lo, ctx->own_hi,
+        PCT_LAUNCH(k_hist, dim3(nhb), dim3(kBlock), 0, ctx->stream, p.src, n, g, s.g_begin, s.g_end, lv.want, lv.lo, lv.hi,
                    p.sub_box ? 1 : 0, (int*)ctx->cell_of.p, (int*)ctx->cell_fill.p, (int*)ctx->cell_own.p, cell_oth);
     }
     return PCT_OK;
@@ -1779,7 +1765,7 @@ static int launch_place(pct_ctx* ctx, const GridPoints& s, const GridPass& p) {
     const pct_grid& g = p.g;
     const int64_t n = s.n;
     // (the chained sweep's passes read each other's lists: its first pass keeps row_of complete)
-    const bool lazy_rows = p.build == GridBuild::Bin && !ctx->level_mode;
+    const bool lazy_rows = p.build == GridBuild::Bin && !p.level;
     ctx->row_of_valid = !lazy_rows;
     ctx->row_of_rows = p.n_owned;
     ctx->row_of_begin = (int)ctx->q_begin;
@@ -1817,8 +1803,8 @@ static int debug_bin_plan(pct_ctx* ctx, const GridPass& p) {
 
 // ---- bookkeeping of an accepted build ------------------------------------------------------------------------------
 static int commit_grid(pct_ctx* ctx, const GridPoints& s, pct_grid g, const EdgeSearch& es, int iters, double m_last, int4 tot,
-                       int64_t n_owned, bool sub_box) {
-    const bool own_flag = ctx->own_flag != nullptr, level_pass = es.level_edge > 0;
+                       int64_t n_owned, bool plain, bool sub_box) {          // plain: no pass of the chained sweep
+    const bool level_pass = es.level_edge > 0;
     const int64_t n = s.n;
     // faces of the culling box become limits of what the grid can vouch for (cell units from the origin)
     for (int ax = 0; ax < 3; ++ax) {
@@ -1829,15 +1815,13 @@ static int commit_grid(pct_ctx* ctx, const GridPoints& s, pct_grid g, const Edge
     if (pct_getenv("PCT_GRID_DEBUG"))
         fprintf(stderr, "[grid] box [%g %g %g]-[%g %g %g] edge %g dims %d x %d x %d = %lld cells, %d passes, occupancy %.1f, items %d\n", s.bbox[0],
                 s.bbox[1], s.bbox[2], s.bbox[3], s.bbox[4], s.bbox[5], g.cell, g.nx, g.ny, g.nz, (long long)g.ncell, iters, m_last, tot.y);
-    if (ctx->level_mode && !own_flag)                    // first pass of a density-adaptive sweep: its (trimmed) box serves the later ones
-        for (int a = 0; a < 6; ++a) ctx->lvl_bbox[a] = s.bbox[a];
     ctx->grid = g;
     ctx->tm.grid_iters += iters;
     ctx->tm.cells = g.ncell;
     ctx->tm.cell_size = g.cell;
     ctx->tm.grid_points = n;
     ctx->tm.occupancy = m_last;
-    if (s.src != GridSource::CulledPack && !own_flag && !ctx->level_mode) {       // remember the box for the next similar cloud
+    if (s.src != GridSource::CulledPack && plain) {       // remember the box for the next similar cloud
         for (int a = 0; a < 6; ++a) ctx->spec_bbox[a] = s.bbox[a];
         if (s.red.cnt > 0)                // raw bounding box of this cloud (before trimming)
             for (int a = 0; a < 6; ++a) ctx->spec_raw[a] = order_float(s.red.bb[a]);
@@ -1864,7 +1848,7 @@ static int commit_grid(pct_ctx* ctx, const GridPoints& s, pct_grid g, const Edge
     ctx->tm.occupied_cells = tot.y;
     ctx->grid_valid = true;
     // what pct_query_points_algo may send caller-supplied queries through: every point filed, every point owned
-    ctx->grid_whole = !own_flag && !ctx->level_mode && !sub_box && !ctx->culled && n == ctx->n && ctx->q_begin == 0 && ctx->q_end == ctx->n &&
+    ctx->grid_whole = plain && !sub_box && !ctx->culled && n == ctx->n && ctx->q_begin == 0 && ctx->q_end == ctx->n &&
                       ctx->slab_parts == 0;
     return PCT_OK;
 }
@@ -1874,7 +1858,7 @@ static int commit_grid(pct_ctx* ctx, const GridPoints& s, pct_grid g, const Edge
 // 27-cell stencil (guaranteed radius = one cell edge) contains the k+1 nearest
 // points for nearly every query of a surface-like cloud; the sweep kernel
 // widens ring by ring for the rest.
-int pct_build_grid(pct_ctx* ctx, int32_t k, double eps, bool may_give_up, GridVerdict* out, pct_call_clock* clock) {
+int pct_build_grid(pct_ctx* ctx, int32_t k, double eps, bool may_give_up, GridVerdict* out, pct_call_clock* clock, LevelPass* pass) {
     *out = GridVerdict::Built;
     ctx->grid_valid = false;       // (the lists are being rewritten: valid again once a build is committed)
     // measured optima on surface clouds (tools/tune_factor.py): larger cells cost candidates, smaller ones cost
@@ -1886,12 +1870,12 @@ int pct_build_grid(pct_ctx* ctx, int32_t k, double eps, bool may_give_up, GridVe
     // 32 cells per point up to 2^30 (a 60 M-point torus wants 3.3e8 cells: capped at 2^27 its cells held 51 points
     // instead of 29.5, the staging area overflowed and the sweep took 235 ms instead of ~40)
     int64_t cell_cap = (int64_t)1 << 27;
-    if (ctx->level_mode) cell_cap = (int64_t)1 << 24;
+    if (pass) cell_cap = (int64_t)1 << 24;
     else if (32 * ctx->n > cell_cap) cell_cap = 32 * ctx->n < ((int64_t)1 << 30) ? 32 * ctx->n : (int64_t)1 << 30;
-    const bool own_flag = ctx->own_flag != nullptr;        // level passes: ownership by wanted-edge band
-    const bool slab = ctx->slab_parts >= 1 && !own_flag;
-    const bool sub_box = ctx->level_edge > 0 && ctx->level_box_valid;
-    const bool bin_allowed = !own_flag && !sub_box && !slab && !pct_getenv("PCT_GRID_ATOMIC");
+    const bool by_want = pass && pass->want;          // level passes: ownership by wanted-edge band
+    const bool slab = ctx->slab_parts >= 1 && !by_want;
+    const float* sub_box = pass && pass->edge > 0 ? pass->box : nullptr;
+    const bool bin_allowed = !by_want && !sub_box && !slab && !pct_getenv("PCT_GRID_ATOMIC");
     // queries per work item: 16 - 20 measured best for k_knn_pair and k_knn_duo (one staged stencil serves more queries; a
     // cell of ~28 points is one or two items; 1 M torus, k = 50: sweep 0.376 | 0.366 | 0.363 | 0.364 | 0.370 ms at 12 | 14 | 18 |
     // 20 | 24; the reference's lattice torus 0.510 | 0.489 | 0.500 at 12 | 16 | 18; k = 80: 0.597 | 0.574 | 0.583 --
@@ -1904,20 +1888,20 @@ int pct_build_grid(pct_ctx* ctx, int32_t k, double eps, bool may_give_up, GridVe
     for (int attempt = 0; attempt < 3; ++attempt) {
         ctx->tm.grid_iters = 0;
         if (slab) PCT_TRY(slab_split(ctx));                // (sets the owned count: q_begin = 0, q_end = this slab's population)
-        const int64_t n_owned = own_flag ? ctx->own_count : ctx->q_end - ctx->q_begin;
-        const bool sharded = own_flag || ctx->q_begin > 0 || ctx->q_end < ctx->n || slab;   // some points are candidates only
+        const int64_t n_owned = pct_call_rows(ctx, pass);
+        const bool sharded = by_want || ctx->q_begin > 0 || ctx->q_end < ctx->n || slab;   // some points are candidates only
         GridPoints s;
         bool restart = false;
-        PCT_TRY(select_source(ctx, k, target, slab, n_owned, sharded, &s, &restart, clock));
+        PCT_TRY(select_source(ctx, k, target, slab, n_owned, sharded, pass, &s, &restart, clock));
         if (restart) continue;
         const int64_t n = s.n;
         ctx->items_q = items_q;
-        PCT_TRY(reserve_lists(ctx, n, n_owned));
-        EdgeSearch es = edge_search(ctx, s, target, eps);
+        PCT_TRY(reserve_lists(ctx, n, n_owned, by_want));
+        EdgeSearch es = edge_search(ctx, s, target, eps, pass);
         double a = es.first();
         GridPass p = {};
-        p.src = s.from_base ? (const float4*)ctx->lvl_src.p : (const float4*)ctx->pts4.p;
-        p.n_owned = n_owned; p.sharded = sharded; p.sub_box = sub_box; p.items_q = items_q;
+        p.src = s.from_base ? pass->base : (const float4*)ctx->pts4.p;
+        p.n_owned = n_owned; p.level = pass; p.sharded = sharded; p.sub_box = sub_box != nullptr; p.items_q = items_q;
         int iters = 0;
         int4 tot = make_int4(0, 0, 0, 0);
         double m_last = 0;
@@ -1926,16 +1910,16 @@ int pct_build_grid(pct_ctx* ctx, int32_t k, double eps, bool may_give_up, GridVe
         // synchronisation instead of two; a rejected size costs a speculative scatter.
         for (int it = 0; it < es.max_iter; ++it) {
             a = es.clamp_eps(a);
-            size_grid(ctx, sub_box, s.bbox, a, &p.g);
+            size_grid(sub_box, s.bbox, a, &p.g);
             // PCT_KNN_AUTO: a surface wants about a third of a cell per point; an edge that asks for 16 cells per point was
             // steered there by a dense minority (the size-biased occupancy) -- a 1/r^2 scan wants 130 per point, 1.6 ms of
             // counters and scans that the hierarchical list does not need.  Nothing was built: the caller goes there.
-            if (!own_flag && !(es.level_edge > 0) && p.g.ncell > 16 * n && p.g.ncell > ((int64_t)1 << 20)) {
+            if (!by_want && !(es.level_edge > 0) && p.g.ncell > 16 * n && p.g.ncell > ((int64_t)1 << 20)) {
                 if (it == 0 && es.hinted) {
                     // ... unless the edge is the PREVIOUS cloud's (same size, similar box, another density -- a torus after
                     // a 1/r^2 scan inherited its 130 cells per point): this cloud's own first guess, then
                     a = es.fallback_first();
-                    size_grid(ctx, sub_box, s.bbox, a, &p.g);
+                    size_grid(sub_box, s.bbox, a, &p.g);
                 } else if (may_give_up) {
                     *out = GridVerdict::GaveUp;
                     ctx->grid_valid = false;
@@ -1945,7 +1929,7 @@ int pct_build_grid(pct_ctx* ctx, int32_t k, double eps, bool may_give_up, GridVe
             bool hit_cap = false;            // the cell budget, not the occupancy target, set this edge
             while (p.g.ncell > cell_cap) {
                 a *= cbrt((double)p.g.ncell / (double)cell_cap) * 1.01;
-                size_grid(ctx, sub_box, s.bbox, a, &p.g);
+                size_grid(sub_box, s.bbox, a, &p.g);
                 hit_cap = true;
             }
             const pct_grid& g = p.g;
@@ -1978,7 +1962,9 @@ int pct_build_grid(pct_ctx* ctx, int32_t k, double eps, bool may_give_up, GridVe
             a = es.next(m_last, a);
         }
         if (restart) continue;
-        return commit_grid(ctx, s, p.g, es, iters, m_last, tot, n_owned, sub_box);
+        PCT_TRY(commit_grid(ctx, s, p.g, es, iters, m_last, tot, n_owned, pass == nullptr, p.sub_box));
+        if (pass && !by_want) memcpy(pass->base_box, s.bbox, sizeof(s.bbox));     // first pass of a chain: its (trimmed) box serves the later ones
+        return PCT_OK;
     }
     return pct_fail(ctx, PCT_ERR_INVALID, "cell-list build: restarted more than twice");
 }

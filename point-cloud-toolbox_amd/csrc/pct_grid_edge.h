@@ -1,10 +1,37 @@
-// The pure host arithmetic of the cell-list build (pct_grid.hip): the cell-edge search and the shape of the two-level
-// counting sort.  Nothing here knows a handle, a device or the environment -- tests/test_grid_edge.py compiles this
-// header alone with the host compiler and drives it with occupancy models.
+// The pure host decisions of the cell-list build (pct_grid.hip): the source of its points, the cell-edge search and the
+// shape of the two-level counting sort.  Nothing here knows a handle, a device or the environment -- tests/test_grid_edge.py
+// compiles this header alone with the host compiler and drives it with plain values and occupancy models.
 #pragma once
 
 #include <math.h>
 #include <stdint.h>
+
+// ---- where the grid's points come from ---------------------------------------------------------------------------------
+enum class GridSource {
+    LevelBase,     // later passes of the density-adaptive sweep: the points in the cell order of its first pass, and that pass's box
+    CulledPack,    // sharded handle: the owned rows and the points near them (pack_near_owned)
+    CallerRows,    // the caller's rows on the (trimmed) box of the previous similar cloud; this cloud's box is checked later
+    FullPack,      // every point, packed and measured first
+};
+struct SourceInputs {
+    bool by_want, base_usable;     // the pass owns by wanted edge; the first pass's records hold every point
+    bool chained;                  // a pass of the chained sweep, the first included
+    bool slab, sharded;            // ownership by slab; some points are candidates only
+    int64_t n_owned;
+    bool has_f64, no_cull, env_no_cull, env_no_spec;      // of the handle; PCT_NO_CULL, PCT_NO_SPEC
+    double hint_edge; bool spec_valid; int64_t spec_n, n; // the handle's warm start, the record of its last plain build, this cloud
+};
+inline GridSource choose_source(const SourceInputs& in) {
+    // (a slab's owned points are found by the pack itself: it always runs, with an open box after a limit retry)
+    const bool try_cull = in.slab ? in.n_owned > 0
+                                  : !in.by_want && in.sharded && in.n_owned > 0 && !in.has_f64 && !in.no_cull && !in.env_no_cull;
+    // Speculation: a handle fed a stream of similar clouds builds the cell list over the (trimmed) box of the previous
+    // call without waiting for the new bounding box -- any box is a valid grid box, points outside are clamped into
+    // the boundary cells -- and checks the new box at the synchronisation that ends the first pass.  One host round
+    // trip less per build.
+    const bool spec = !try_cull && !in.by_want && !in.chained && in.hint_edge > 0 && in.spec_valid && in.spec_n == in.n && !in.env_no_spec;
+    return in.by_want && in.base_usable ? GridSource::LevelBase : try_cull ? GridSource::CulledPack : spec ? GridSource::CallerRows : GridSource::FullPack;
+}
 
 // ---- cell size ---------------------------------------------------------------------------------------------------------
 // The edge is steered until a point shares its cell with about `target` points (the occupancy m the build measures).

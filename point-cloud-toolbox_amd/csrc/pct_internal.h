@@ -200,18 +200,9 @@ struct pct_ctx {
     float spec_raw[6] = {0, 0, 0, 0, 0, 0};    // raw bounding box of that cloud
     int64_t spec_n = 0;
     bool spec_valid = false;
-    // density-adaptive sweep (pct_levels.hip): the queries one pass could not answer are re-owned by the next
-    // pass, which sizes its cells for THEM
-    const void* own_flag = nullptr; // device float (n): wanted log2 cell edge of every unanswered point (NaN = answered); null = ownership by index range
-    float own_lo = 0, own_hi = 0;   // the pass owns the points with own_lo <= wanted < own_hi
-    float level_box[6] = {0, 0, 0, 0, 0, 0};   // bbox of the owned points of a fast level pass
-    bool level_box_valid = false;
-    int64_t own_count = 0;
-    double level_edge = 0;          // > 0: first cell edge of this pass
-    bool level_mode = false;        // a density-adaptive sweep is in progress (rows answered are recorded in row_done)
+    // density-adaptive sweep (pct_levels.hip): the queries one pass could not answer are re-owned by the next pass, which
+    // sizes its cells for THEM and says so in a LevelPass (below); what lives here are the allocations the passes reuse
     pct_buf lvl_src;                // float4 (n): the points in the cell order of the first pass (input of the later passes' builds)
-    bool lvl_src_valid = false;
-    float lvl_bbox[6] = {0, 0, 0, 0, 0, 0};
     // hierarchical cell list (pct_tree.hip)
     int tree_bits = 0;
     int64_t tree_segs = 0;
@@ -491,16 +482,28 @@ __device__ inline int64_t pct_code_lower_bound(const unsigned long long* __restr
 struct FitSlot { int par; bool mirror_stats; pct_call_clock* clock; };
 enum class GridVerdict { Built, GaveUp };                  // GaveUp: more than 16 cells per point wanted, nothing built
 enum class TreeVerdict { Built, Unusable, OtherCloud };    // Unusable: not a cloud for it; OtherCloud: not the expected box; nothing built
+// What one pass of the chained sweep (pct_knn_levels) asks of the cell-list build and of the sweep over it.  A null
+// pointer to it is a plain call; the first pass of a chain carries no wanted-edge array and owns by index range.
+struct LevelPass {
+    const float* want = nullptr;   // device float (n): wanted log2 cell edge of every unanswered point (NaN = answered)
+    float lo = 0, hi = 0; int64_t owned = 0;   // the pass owns the points with lo <= wanted < hi: this many, one table row each
+    double edge = 0;               // > 0: the first cell edge is given (and, with want, is the only one tried)
+    const float* box = nullptr;    // float (6): bounding box of the owned points of a fast pass, whose grid covers only them
+    const float4* base = nullptr;  // float4 (n): the points in the cell order of the first pass, input of the later builds ...
+    float base_box[6] = {0, 0, 0, 0, 0, 0};   // ... on that pass's (trimmed) grid box: ANSWERED by the first pass's pct_build_grid
+};
+inline int64_t pct_call_rows(const pct_ctx* ctx, const LevelPass* pass) { return pass && pass->want ? pass->owned : ctx->q_end - ctx->q_begin; }   // one per owned query
 
 // grid build (pct_grid.hip)
 int pct_pack_points(pct_ctx* ctx, float* bbox6);
 int pct_pack_points_f64(pct_ctx* ctx, const double* d_xyz64);
 // may_give_up: PCT_KNN_AUTO on a cloud the hierarchical list could take (pct_auto_route.h)
 // clock (may be null: a build outside a timed call): the call's, whose begin the build's first launch marks
-int pct_build_grid(pct_ctx* ctx, int32_t k, double eps, bool may_give_up, GridVerdict* out, pct_call_clock* clock = nullptr);
+// pass (null: a plain build): the chained sweep's; its first pass gets the box of the accepted build back in base_box
+int pct_build_grid(pct_ctx* ctx, int32_t k, double eps, bool may_give_up, GridVerdict* out, pct_call_clock* clock, LevelPass* pass);
 // neighbour sweeps (pct_knn.hip); want_dist = false: the caller reads no distances from the table (the fused call);
-// clock: the call's -- the end of the fast sweep is a boundary of its sweep stage
-int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, int phase, bool want_dist, pct_call_clock* clock);
+// clock: the call's -- the end of the fast sweep is a boundary of its sweep stage; pass (null: a plain sweep): as above
+int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, int phase, bool want_dist, pct_call_clock* clock, const LevelPass* pass);
 int pct_launch_knn_brute(pct_ctx* ctx, int32_t k, double eps);
 // census of the work items of the cell list in place: out4 = {queries, queries whose stencil overflows the staging
 // area, queries whose stencil holds fewer than 2.5 (k+1) points (too few to vouch for k+1 within one cell edge), sum over the other queries of the non-empty cells in their

@@ -187,7 +187,7 @@ __global__ __launch_bounds__(256) void k_item_census(const int2* __restrict__ it
     if (threadIdx.x < 4) atomicAdd(&out->census[threadIdx.x], sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x]);
 }
 
-KnnArgs make_args(pct_ctx* ctx, int32_t k, double eps, bool grid) {
+KnnArgs make_args(pct_ctx* ctx, int32_t k, double eps, bool grid, const LevelPass* pass = nullptr) {    // pass: the chained sweep's
     KnnArgs a = {};
     a.pts = (const float4*)(grid ? ctx->sorted4.p : ctx->pts4.p);
     a.ptsd = ctx->has_f64 ? (const double4*)(grid ? ctx->sorted4d.p : ctx->pts4d.p) : nullptr;
@@ -195,7 +195,7 @@ KnnArgs make_args(pct_ctx* ctx, int32_t k, double eps, bool grid) {
     a.cell_own = (const int*)ctx->cell_own.p;
     a.own_start = (const int*)ctx->own_start.p;
     a.owned_pos = (const int*)ctx->owned_pos.p;
-    a.n_owned = ctx->own_flag ? ctx->own_count : ctx->q_end - ctx->q_begin;
+    a.n_owned = pct_call_rows(ctx, pass);
     a.occ = (const int*)ctx->occ.p;
     a.n_occ = ctx->n_occ;
     a.n = ctx->n;
@@ -208,16 +208,16 @@ KnnArgs make_args(pct_ctx* ctx, int32_t k, double eps, bool grid) {
     a.nbr_pos = (int*)ctx->nbr_pos.p;
     a.nbr_dist = (float*)ctx->nbr_dist.p;
     a.nbr_cnt = eps > 0 ? (int*)ctx->nbr_cnt.p : nullptr;
-    a.row_done = ctx->own_flag || ctx->level_mode ? (int*)ctx->row_done.p : nullptr;
+    a.row_done = pass ? (int*)ctx->row_done.p : nullptr;
     a.redo_m = a.row_done ? (int*)ctx->redo_m.p : nullptr;
     a.counters = &pct_dev(ctx)->sweep;
     a.stats = ctx->collect_stats ? 1 : 0;
     return a;
 }
 
-int reserve_table(pct_ctx* ctx, int32_t k, double eps, bool with_dist = true) {
+int reserve_table(pct_ctx* ctx, int32_t k, double eps, bool with_dist = true, const LevelPass* pass = nullptr) {
     ctx->nbr_pitch = (k + 3) & ~3;                        // 16-byte aligned rows (the fit kernel reads int4)
-    const size_t rows = (size_t)(ctx->own_flag ? ctx->own_count : ctx->q_end - ctx->q_begin);     // one row per owned query
+    const size_t rows = (size_t)pct_call_rows(ctx, pass);
     PCT_TRY(pct_reserve(ctx, &ctx->nbr_pos, rows * ctx->nbr_pitch * sizeof(int)));
     if (with_dist) PCT_TRY(pct_reserve(ctx, &ctx->nbr_dist, rows * ctx->nbr_pitch * sizeof(float)));
     ctx->dist_valid = with_dist;
@@ -230,9 +230,9 @@ int reserve_table(pct_ctx* ctx, int32_t k, double eps, bool with_dist = true) {
 
 // Which fast sweep a call takes is decided by plan_sweep (pct_sweep_plan.h) from plain values: what it reads of the
 // handle, and every tuning switch (PCT_*: A/B aids, read per call -- tests flip them), is gathered here.
-SweepPlan plan_for(const pct_ctx* ctx, int32_t k, double eps, bool tree, bool exact_only, int phase, bool want_dist) {
+SweepPlan plan_for(const pct_ctx* ctx, int32_t k, double eps, bool tree, bool exact_only, int phase, bool want_dist, const LevelPass* pass) {
     const pct_grid& g = ctx->grid;
-    const SweepInputs in = {ctx->n_items, ctx->has_f64, ctx->level_mode, ctx->own_flag != nullptr, pct_fast_r1_max(), g.cell, g.ox, g.oy, g.oz, g.nx, g.ny, g.nz};
+    const SweepInputs in = {ctx->n_items, ctx->has_f64, pass != nullptr, pass && pass->want, pct_fast_r1_max(), g.cell, g.ox, g.oy, g.oz, g.nx, g.ny, g.nz};
     const SweepSwitches sw = {pct_getenv("PCT_NO_PAIR") != nullptr, pct_getenv("PCT_NO_PAIR_KERNEL") != nullptr,
                               pct_getenv("PCT_NO_DUO_KERNEL") != nullptr, pct_getenv("PCT_KEEP_DIST") != nullptr};
     return plan_sweep(in, sw, k, eps, tree, exact_only, phase, want_dist);
@@ -253,15 +253,15 @@ int launch_sweep(pct_ctx* ctx, const SweepPlan& p, const KnnArgs& a, int* redo, 
 
 // phase 0: fast sweep + exact sweep of what it flagged (or, exact_only, the exact sweep of every query);
 // phase 1: fast sweep only, the flagged rows stay in ctx->redo (level passes); phase 2: exact sweep of ctx->redo
-int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, int phase, bool want_dist, pct_call_clock* clock) {
-    const int64_t n_rows = ctx->own_flag ? ctx->own_count : ctx->q_end - ctx->q_begin;
-    const SweepPlan plan = plan_for(ctx, k, eps, false, exact_only, phase, want_dist);
+int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, int phase, bool want_dist, pct_call_clock* clock, const LevelPass* pass) {
+    const int64_t n_rows = pct_call_rows(ctx, pass);
+    const SweepPlan plan = plan_for(ctx, k, eps, false, exact_only, phase, want_dist, pass);
     if (phase != 2) {
-        PCT_TRY(reserve_table(ctx, k, eps, plan.dist));
+        PCT_TRY(reserve_table(ctx, k, eps, plan.dist, pass));
         PCT_TRY(pct_reserve(ctx, &ctx->redo, ((size_t)n_rows + 16) * sizeof(int)));
-        if (ctx->level_mode) PCT_TRY(pct_reserve(ctx, &ctx->redo_m, ((size_t)n_rows + 16) * sizeof(int)));
+        if (pass) PCT_TRY(pct_reserve(ctx, &ctx->redo_m, ((size_t)n_rows + 16) * sizeof(int)));
     }
-    KnnArgs a = make_args(ctx, k, eps, true);
+    KnnArgs a = make_args(ctx, k, eps, true, pass);
     if (!ctx->dist_valid) a.nbr_dist = nullptr;
     int* redo_count = &pct_dev(ctx)->sweep.redo_count;
     int* redo = (int*)ctx->redo.p;
@@ -299,11 +299,10 @@ int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, in
 // on the same structure for what the fast one flagged.  The table is in Morton order (a sorted space like the uniform
 // list's: sorted4, owned_pos = identity, row_of).
 int pct_launch_knn_tree(pct_ctx* ctx, int32_t k, double eps, bool want_dist, pct_call_clock* clock) {
-    if (ctx->level_mode || ctx->own_flag || ctx->q_begin != 0 || ctx->q_end != ctx->n)
-        return pct_fail(ctx, PCT_ERR_INVALID, "the tree sweep takes whole clouds");
+    if (ctx->q_begin != 0 || ctx->q_end != ctx->n) return pct_fail(ctx, PCT_ERR_INVALID, "the tree sweep takes whole clouds");
     const int64_t n_rows = ctx->n;
     const bool exact_only = pct_getenv("PCT_TREE_EXACT_ONLY") != nullptr;        // testing: every query through the exact sweep
-    const SweepPlan plan = plan_for(ctx, k, eps, true, exact_only, 0, want_dist);
+    const SweepPlan plan = plan_for(ctx, k, eps, true, exact_only, 0, want_dist, nullptr);
     PCT_TRY(reserve_table(ctx, k, eps, plan.dist));
     PCT_TRY(pct_reserve(ctx, &ctx->redo, ((size_t)n_rows + 16) * sizeof(int)));
     KnnArgs a = make_args(ctx, k, eps, true);

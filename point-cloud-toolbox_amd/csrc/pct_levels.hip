@@ -198,11 +198,7 @@ int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps, const int* fuse_par, pct
     const bool debug = pct_getenv("PCT_LEVELS_DEBUG") != nullptr;
 
     ctx->no_cull = true;            // the merged table and the public-space fit need every point packed
-    ctx->level_mode = true;
-    ctx->own_flag = nullptr;
-    ctx->own_count = 0;
-    ctx->level_edge = 0;
-    ctx->level_box_valid = false;
+    LevelPass pass;                 // what the pass in hand asks of the build and the sweep; the first one: every owned query by index
     int passes = 0;
 
     // one pass over the owned set in place: cell list, fast sweep (or the exact one), wanted edges, merge
@@ -215,11 +211,11 @@ int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps, const int* fuse_par, pct
     const auto run_pass = [&](int64_t owned, bool exact) -> int {
         const double t0 = debug ? tick() : 0;
         GridVerdict built;                                       // (nobody to give up for: always Built)
-        PCT_TRY(pct_build_grid(ctx, k, eps, false, &built));
+        PCT_TRY(pct_build_grid(ctx, k, eps, false, &built, nullptr, &pass));
         const double t1 = debug ? tick() : 0;
         PCT_TRY(pct_reserve(ctx, &ctx->row_done, (size_t)owned * sizeof(int)));
         PCT_HIP(ctx, hipMemsetAsync(ctx->row_done.p, 0, (size_t)owned * sizeof(int), ctx->stream));
-        PCT_TRY(pct_launch_knn_grid(ctx, k, eps, exact, exact ? 0 : 1, true, clock));      // (k_merge_rows below reads the distances)
+        PCT_TRY(pct_launch_knn_grid(ctx, k, eps, exact, exact ? 0 : 1, true, clock, &pass));      // (k_merge_rows below reads the distances)
         if (!exact) {
             // the stencil of a well-sized pass holds about 11 cells' worth of points on a surface
             PCT_LAUNCH(k_classify, dim3(1024), dim3(256), 0, ctx->stream, (const int*)ctx->row_done.p, (const int*)ctx->redo_m.p,
@@ -247,96 +243,82 @@ int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps, const int* fuse_par, pct
         return PCT_OK;
     };
 
-    const auto body = [&]() -> int {
-        PCT_TRY(pct_reserve(ctx, &ctx->pub_pos, (size_t)nq * pitch * sizeof(int)));
-        PCT_TRY(pct_reserve(ctx, &ctx->pub_dist, (size_t)nq * pitch * sizeof(float)));
-        if (eps > 0) PCT_TRY(pct_reserve(ctx, &ctx->pub_cnt, (size_t)nq * sizeof(int)));
-        PCT_TRY(pct_reserve(ctx, &ctx->flag_buf, (size_t)ctx->n * sizeof(float)));
-        PCT_TRY(pct_reserve(ctx, &ctx->dens_buf, (size_t)ctx->n * sizeof(float2)));
-        PCT_TRY(pct_reserve(ctx, &ctx->stage_d, sizeof(BandStats) + 64));
-        PCT_LAUNCH(k_init_want, dim3((unsigned)((ctx->n + 255) / 256)), dim3(256), 0, ctx->stream, (float*)ctx->flag_buf.p,
-                           (float2*)ctx->dens_buf.p, ctx->n);
+    PCT_TRY(pct_reserve(ctx, &ctx->pub_pos, (size_t)nq * pitch * sizeof(int)));
+    PCT_TRY(pct_reserve(ctx, &ctx->pub_dist, (size_t)nq * pitch * sizeof(float)));
+    if (eps > 0) PCT_TRY(pct_reserve(ctx, &ctx->pub_cnt, (size_t)nq * sizeof(int)));
+    PCT_TRY(pct_reserve(ctx, &ctx->flag_buf, (size_t)ctx->n * sizeof(float)));
+    PCT_TRY(pct_reserve(ctx, &ctx->dens_buf, (size_t)ctx->n * sizeof(float2)));
+    PCT_TRY(pct_reserve(ctx, &ctx->stage_d, sizeof(BandStats) + 64));
+    PCT_LAUNCH(k_init_want, dim3((unsigned)((ctx->n + 255) / 256)), dim3(256), 0, ctx->stream, (float*)ctx->flag_buf.p,
+                       (float2*)ctx->dens_buf.p, ctx->n);
+    PCT_HIP(ctx, hipGetLastError());
+    // pass 0: every owned query, cells sized as for a plain sweep
+    PCT_TRY(run_pass(nq, false));
+    // the later passes bin the points in THIS pass's cell order (lanes of a wave then share their cells: the
+    // histogram's atomics combine, k_hist_agg) and reuse its box (pass.base_box, the build's answer)
+    PCT_TRY(pct_reserve(ctx, &ctx->lvl_src, (size_t)ctx->n * sizeof(float4)));
+    PCT_HIP(ctx, hipMemcpyAsync(ctx->lvl_src.p, ctx->sorted4.p, (size_t)ctx->n * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
+    pass.base = ctx->n_grid == ctx->n ? (const float4*)ctx->lvl_src.p : nullptr;
+    pass.want = (const float*)ctx->flag_buf.p;
+    float band_box[6];               // of the owned points of a banded pass
+    const float log_edge0 = (float)log2(ctx->grid.cell);
+    BandStats* d_st = (BandStats*)ctx->stage_d.p;
+    int* d_box = (int*)((char*)ctx->stage_d.p + sizeof(BandStats));        // 6 ints + count
+    BandStats st;
+    int64_t pending = 0;
+    for (;;) {
+        PCT_HIP(ctx, hipMemsetAsync(d_st, 0, sizeof(BandStats), ctx->stream));
+        PCT_LAUNCH(k_band_hist, dim3(512), dim3(256), 0, ctx->stream, (const float*)ctx->flag_buf.p, ctx->q_begin,
+                           ctx->q_end, log_edge0, d_st);
         PCT_HIP(ctx, hipGetLastError());
-        // pass 0: every owned query, cells sized as for a plain sweep
-        ctx->lvl_src_valid = false;
-        PCT_TRY(run_pass(nq, false));
-        // the later passes bin the points in THIS pass's cell order (lanes of a wave then share their cells: the
-        // histogram's atomics combine, k_hist_agg) and reuse its box
-        PCT_TRY(pct_reserve(ctx, &ctx->lvl_src, (size_t)ctx->n * sizeof(float4)));
-        PCT_HIP(ctx, hipMemcpyAsync(ctx->lvl_src.p, ctx->sorted4.p, (size_t)ctx->n * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
-        ctx->lvl_src_valid = ctx->n_grid == ctx->n;
-        const float log_edge0 = (float)log2(ctx->grid.cell);
-        BandStats* d_st = (BandStats*)ctx->stage_d.p;
-        int* d_box = (int*)((char*)ctx->stage_d.p + sizeof(BandStats));        // 6 ints + count
-        BandStats st;
-        int64_t pending = 0;
-        for (;;) {
-            PCT_HIP(ctx, hipMemsetAsync(d_st, 0, sizeof(BandStats), ctx->stream));
-            PCT_LAUNCH(k_band_hist, dim3(512), dim3(256), 0, ctx->stream, (const float*)ctx->flag_buf.p, ctx->q_begin,
-                               ctx->q_end, log_edge0, d_st);
-            PCT_HIP(ctx, hipGetLastError());
-            PCT_HIP(ctx, hipMemcpyAsync(ctx->pin->band_stats, d_st, sizeof(BandStats), hipMemcpyDeviceToHost, ctx->stream));
-            PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            memcpy(&st, ctx->pin->band_stats, sizeof(BandStats));
-            int64_t banded = 0;
-            for (int b = 0; b < kBins; ++b) banded += st.hist[b];
-            pending = banded + st.exact;
-            // the one-octave window (4 bins) that holds the most queries
-            int best = 0;
-            int64_t best_cnt = -1;
-            for (int b = 0; b + 4 <= kBins; ++b) {
-                const int64_t c = (int64_t)st.hist[b] + st.hist[b + 1] + st.hist[b + 2] + st.hist[b + 3];
-                if (c > best_cnt) { best_cnt = c; best = b; }
-            }
-            if (debug)
-                fprintf(stderr, "[levels] after pass %d (edge %.5g, %lld cells): pending %lld (exact-only %u), best octave at edge %.5g holds %lld\n",
-                        passes - 1, ctx->grid.cell, (long long)ctx->grid.ncell, (long long)pending, st.exact,
-                        exp2(log_edge0 + kBinLo + 0.25 * (best + 2)), (long long)best_cnt);
-            if (banded <= enough || passes >= kMaxPasses || best_cnt <= enough / 8) break;
-            const float lo = best == 0 ? -INFINITY : log_edge0 + kBinLo + 0.25f * best;
-            const float hi = best + 4 >= kBins ? 0.4f * kWantExact : log_edge0 + kBinLo + 0.25f * (best + 4);
-            const int init[7] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN, INT32_MIN, 0};
-            PCT_HIP(ctx, hipMemcpyAsync(d_box, init, sizeof(init), hipMemcpyHostToDevice, ctx->stream));
-            PCT_LAUNCH(k_band_box, dim3(512), dim3(256), 0, ctx->stream, (const float*)ctx->flag_buf.p, ctx->xyz_view,
-                               ctx->q_begin, ctx->q_end, lo, hi, d_box, (unsigned*)(d_box + 6));
-            PCT_HIP(ctx, hipGetLastError());
-            PCT_HIP(ctx, hipMemcpyAsync(ctx->pin->band_box, d_box, sizeof(init), hipMemcpyDeviceToHost, ctx->stream));
-            PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            const int* hb = ctx->pin->band_box;
-            for (int a = 0; a < 6; ++a) ctx->level_box[a] = order_to_float(hb[a]);
-            ctx->level_box_valid = true;
-            ctx->own_flag = ctx->flag_buf.p;
-            ctx->own_lo = lo;
-            ctx->own_hi = hi;
-            ctx->own_count = (int64_t)(unsigned)hb[6];
-            if (ctx->own_count <= 0) break;            // (cannot happen while histogram and window agree; never build a cell list for nobody)
-            ctx->level_edge = exp2((double)log_edge0 + kBinLo + 0.25 * (best + 2));        // centre of the window
-            PCT_TRY(run_pass(ctx->own_count, false));
+        PCT_HIP(ctx, hipMemcpyAsync(ctx->pin->band_stats, d_st, sizeof(BandStats), hipMemcpyDeviceToHost, ctx->stream));
+        PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        memcpy(&st, ctx->pin->band_stats, sizeof(BandStats));
+        int64_t banded = 0;
+        for (int b = 0; b < kBins; ++b) banded += st.hist[b];
+        pending = banded + st.exact;
+        // the one-octave window (4 bins) that holds the most queries
+        int best = 0;
+        int64_t best_cnt = -1;
+        for (int b = 0; b + 4 <= kBins; ++b) {
+            const int64_t c = (int64_t)st.hist[b] + st.hist[b + 1] + st.hist[b + 2] + st.hist[b + 3];
+            if (c > best_cnt) { best_cnt = c; best = b; }
         }
-        if (pending > 0) {               // the exact sweep answers whatever is left, over the whole box
-            ctx->own_flag = ctx->flag_buf.p;
-            ctx->own_lo = -INFINITY;
-            ctx->own_hi = INFINITY;
-            ctx->own_count = pending;
-            ctx->level_box_valid = false;
-            // cells sized for the median wanted edge of the banded leftovers (the exact sweep widens ring by ring)
-            int64_t acc = 0, banded = 0;
-            for (int b = 0; b < kBins; ++b) banded += st.hist[b];
-            int med = kBins / 2;
-            for (int b = 0; b < kBins; ++b) { acc += st.hist[b]; if (acc * 2 >= banded) { med = b; break; } }
-            ctx->level_edge = banded > 0 ? exp2((double)log_edge0 + kBinLo + 0.25 * (med + 0.5)) : exp2((double)log_edge0);
-            PCT_TRY(run_pass(pending, true));
-        }
-        return PCT_OK;
-    };
-    const int st = body();
-    ctx->own_flag = nullptr;
-    ctx->own_count = 0;
-    ctx->level_edge = 0;
-    ctx->level_box_valid = false;
-    ctx->level_mode = false;
-    ctx->lvl_src_valid = false;
-    if (st != PCT_OK) return st;
+        if (debug)
+            fprintf(stderr, "[levels] after pass %d (edge %.5g, %lld cells): pending %lld (exact-only %u), best octave at edge %.5g holds %lld\n",
+                    passes - 1, ctx->grid.cell, (long long)ctx->grid.ncell, (long long)pending, st.exact,
+                    exp2(log_edge0 + kBinLo + 0.25 * (best + 2)), (long long)best_cnt);
+        if (banded <= enough || passes >= kMaxPasses || best_cnt <= enough / 8) break;
+        pass.lo = best == 0 ? -INFINITY : log_edge0 + kBinLo + 0.25f * best;
+        pass.hi = best + 4 >= kBins ? 0.4f * kWantExact : log_edge0 + kBinLo + 0.25f * (best + 4);
+        const int init[7] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN, INT32_MIN, 0};
+        PCT_HIP(ctx, hipMemcpyAsync(d_box, init, sizeof(init), hipMemcpyHostToDevice, ctx->stream));
+        PCT_LAUNCH(k_band_box, dim3(512), dim3(256), 0, ctx->stream, (const float*)ctx->flag_buf.p, ctx->xyz_view,
+                           ctx->q_begin, ctx->q_end, pass.lo, pass.hi, d_box, (unsigned*)(d_box + 6));
+        PCT_HIP(ctx, hipGetLastError());
+        PCT_HIP(ctx, hipMemcpyAsync(ctx->pin->band_box, d_box, sizeof(init), hipMemcpyDeviceToHost, ctx->stream));
+        PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        const int* hb = ctx->pin->band_box;
+        for (int a = 0; a < 6; ++a) band_box[a] = order_to_float(hb[a]);
+        pass.box = band_box;
+        pass.owned = (int64_t)(unsigned)hb[6];
+        if (pass.owned <= 0) break;            // (cannot happen while histogram and window agree; never build a cell list for nobody)
+        pass.edge = exp2((double)log_edge0 + kBinLo + 0.25 * (best + 2));        // centre of the window
+        PCT_TRY(run_pass(pass.owned, false));
+    }
+    if (pending > 0) {               // the exact sweep answers whatever is left, over the whole box
+        pass.lo = -INFINITY;
+        pass.hi = INFINITY;
+        pass.owned = pending;
+        pass.box = nullptr;
+        // cells sized for the median wanted edge of the banded leftovers (the exact sweep widens ring by ring)
+        int64_t acc = 0, banded = 0;
+        for (int b = 0; b < kBins; ++b) banded += st.hist[b];
+        int med = kBins / 2;
+        for (int b = 0; b < kBins; ++b) { acc += st.hist[b]; if (acc * 2 >= banded) { med = b; break; } }
+        pass.edge = banded > 0 ? exp2((double)log_edge0 + kBinLo + 0.25 * (med + 0.5)) : exp2((double)log_edge0);
+        PCT_TRY(run_pass(pending, true));
+    }
     // the merged table takes the place of the pass table: public space, as after the exhaustive sweep
     swap_buf(ctx->nbr_pos, ctx->pub_pos);
     swap_buf(ctx->nbr_dist, ctx->pub_dist);

@@ -60,7 +60,60 @@ static void shape(const char* name, int64_t n, int64_t ncell, bool sharded) {
                      name, s.ntiles, name, s.chunk);
 }
 
+// choose_source on a base case with one input changed; printed as LevelBase 0, CulledPack 1, CallerRows 2, FullPack 3
+template <class F>
+static void source(const char* name, SourceInputs in, F change) {
+    change(in);
+    const GridSource s = choose_source(in);
+    printf("src_%s %d\n", name, s == GridSource::LevelBase ? 0 : s == GridSource::CulledPack ? 1 : s == GridSource::CallerRows ? 2 : 3);
+}
+
+static void sources() {
+    typedef SourceInputs& In;
+    SourceInputs plain = {};                       // a whole cloud on a fresh handle
+    plain.n_owned = plain.n = 4000;
+    SourceInputs shard = plain;                    // a range of a float32 cloud: culled
+    shard.sharded = true; shard.n_owned = 1000;
+    SourceInputs warm = plain;                     // the same cloud size again on a warm handle: speculated
+    warm.hint_edge = 0.04; warm.spec_valid = true; warm.spec_n = 4000;
+    SourceInputs level = shard;                    // a later pass of the chain
+    level.by_want = level.base_usable = level.chained = true; level.no_cull = true;
+    SourceInputs slab = shard;
+    slab.slab = true;
+
+    source("plain", plain, [](In) {});
+    source("level", level, [](In) {});
+    source("level_no_base", level, [](In in) { in.base_usable = false; });
+    source("level_no_base_cullable", level, [](In in) { in.base_usable = false; in.no_cull = false; });     // by wanted edge: never culled
+    source("base_without_want", level, [](In in) { in.by_want = false; });          // (the first pass: chained, no_cull)
+    source("level_warm", level, [](In in) { in.hint_edge = 0.04; in.spec_valid = true; in.spec_n = in.n; });
+
+    source("shard", shard, [](In) {});
+    source("shard_not_sharded", shard, [](In in) { in.sharded = false; });
+    source("shard_nobody", shard, [](In in) { in.n_owned = 0; });
+    source("shard_f64", shard, [](In in) { in.has_f64 = true; });
+    source("shard_no_cull", shard, [](In in) { in.no_cull = true; });
+    source("shard_env_no_cull", shard, [](In in) { in.env_no_cull = true; });
+    source("shard_warm", shard, [](In in) { in.hint_edge = 0.04; in.spec_valid = true; in.spec_n = in.n; });        // culling comes first
+    source("shard_no_cull_warm", shard, [](In in) { in.no_cull = true; in.hint_edge = 0.04; in.spec_valid = true; in.spec_n = in.n; });
+
+    source("slab", slab, [](In) {});
+    source("slab_whatever", slab, [](In in) { in.sharded = false; in.has_f64 = in.no_cull = in.env_no_cull = true; });   // the pack finds its points
+    source("slab_nobody", slab, [](In in) { in.n_owned = 0; });
+    source("slab_nobody_warm", slab, [](In in) { in.n_owned = 0; in.hint_edge = 0.04; in.spec_valid = true; in.spec_n = in.n; });
+
+    source("warm", warm, [](In) {});
+    source("warm_chained", warm, [](In in) { in.chained = true; });
+    source("warm_by_want", warm, [](In in) { in.by_want = in.chained = true; });
+    source("warm_no_hint", warm, [](In in) { in.hint_edge = 0; });
+    source("warm_no_record", warm, [](In in) { in.spec_valid = false; });
+    source("warm_other_size", warm, [](In in) { in.spec_n = 4001; });
+    source("warm_env_no_spec", warm, [](In in) { in.env_no_spec = true; });
+    source("warm_env_no_cull", warm, [](In in) { in.env_no_cull = true; });          // (not its switch)
+}
+
 int main() {
+    sources();
     const double targets[2] = {27.0, 29.5};
     for (double target : targets) {
         model("d2", target, 2, 1.5, 0);
@@ -194,6 +247,26 @@ def test_warm_start(out):
     for name in ("r05", "r20", "r04", "r25"):    # the interval is open
         assert out[name + "_hinted"] == 0 and close(out[name], g0), name
     assert out["level"] == 0.123 and out["level_hinted"] == 0
+
+
+def test_source_of_the_points(out):
+    """choose_source, one line on each side of every condition of the rule (*Dispatch*): by wanted edge with a
+    usable base: LevelBase; else cull iff (slab ? owned > 0 : not by wanted edge, sharded, owned > 0, not float64, not
+    no_cull, not PCT_NO_CULL); else speculate iff not by wanted edge, not chained, hint_edge > 0, spec_valid, spec_n == n,
+    not PCT_NO_SPEC; else FullPack."""
+    LEVEL_BASE, CULLED_PACK, CALLER_ROWS, FULL_PACK = range(4)
+    expected = {
+        "plain": FULL_PACK,
+        "level": LEVEL_BASE, "level_no_base": FULL_PACK, "level_no_base_cullable": FULL_PACK, "base_without_want": FULL_PACK,
+        "level_warm": LEVEL_BASE,
+        "shard": CULLED_PACK, "shard_not_sharded": FULL_PACK, "shard_nobody": FULL_PACK, "shard_f64": FULL_PACK,
+        "shard_no_cull": FULL_PACK, "shard_env_no_cull": FULL_PACK, "shard_warm": CULLED_PACK, "shard_no_cull_warm": CALLER_ROWS,
+        "slab": CULLED_PACK, "slab_whatever": CULLED_PACK, "slab_nobody": FULL_PACK, "slab_nobody_warm": CALLER_ROWS,
+        "warm": CALLER_ROWS, "warm_chained": FULL_PACK, "warm_by_want": FULL_PACK, "warm_no_hint": FULL_PACK,
+        "warm_no_record": FULL_PACK, "warm_other_size": FULL_PACK, "warm_env_no_spec": FULL_PACK, "warm_env_no_cull": CALLER_ROWS,
+    }
+    got = {k[4:]: int(v) for k, v in out.items() if k.startswith("src_")}
+    assert got == expected
 
 
 def test_bin_shape(out):
