@@ -61,6 +61,9 @@ typedef struct pct_timings {
     float total_ms;           /* the stages above, first to last (device clock stamps or events) */
     int32_t knn_launches;
     int32_t grid_iters;       /* builds of the cell-size search, plus the passes that trimmed the grid box to 6 sigma */
+    int32_t redo_adopted;     /* of redone_queries: rows whose list from the fast sweep the exact sweep took over as the
+                                 answer of the 27-cell stencil and widened from there (a sweep statistic like
+                                 ring_fallbacks; it sits here, in what was padding, so that no other field moves) */
     int64_t cells;            /* grid cells                                             */
     int64_t occupied_cells;   /* work items of the sweep (cells split into query chunks) */
     int64_t ring_fallbacks;   /* rows the exact sweep answered beyond the 27-cell stencil (of the rows it ran over) */
@@ -205,7 +208,7 @@ int pct_scatter_records(pct_ctx* ctx, const float* dev_records, int64_t n_record
 /* Cell-occupancy target of the grid search as a multiple of (k+1); <= 0 keeps
  * the default. */
 int pct_set_grid_param(pct_ctx* ctx, double occupancy_factor);
-/* Sweep statistics in pct_timings (ring_fallbacks ... redone_queries); off by default
+/* Sweep statistics in pct_timings (ring_fallbacks ... redone_queries, redo_adopted); off by default
  * because the counters cost same-address atomics. */
 int pct_set_stats(pct_ctx* ctx, int32_t enable);
 

@@ -39,7 +39,7 @@ class Timings(C.Structure):
     _fields_ = [
         ("upload_ms", C.c_float), ("grid_ms", C.c_float), ("knn_ms", C.c_float), ("knn_fast_ms", C.c_float),
         ("fit_ms", C.c_float), ("export_ms", C.c_float), ("total_ms", C.c_float),
-        ("knn_launches", C.c_int32), ("grid_iters", C.c_int32),
+        ("knn_launches", C.c_int32), ("grid_iters", C.c_int32), ("redo_adopted", C.c_int32),
         ("cells", C.c_int64), ("occupied_cells", C.c_int64),
         ("ring_fallbacks", C.c_int64), ("lds_overflows", C.c_int64),
         ("flushes", C.c_int64), ("candidate_steps", C.c_int64), ("redone_queries", C.c_int64),

@@ -91,6 +91,7 @@ static void read_sweep_stats(const pct_sweep_words& w, pct_timings* t) {
     t->flushes = (int64_t)w.flushes;
     t->candidate_steps = (int64_t)w.candidate_steps;
     t->redone_queries = (int64_t)w.redone_queries;
+    t->redo_adopted = (int32_t)w.redo_adopted;
 }
 
 // bookkeeping of the pending fused call, whose kernels have finished: timings from its clock, statistics

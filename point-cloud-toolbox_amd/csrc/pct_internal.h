@@ -86,7 +86,8 @@ struct pct_sweep_words {
     unsigned long long ring_fallbacks, lds_overflows, flushes, candidate_steps, redone_queries;   // under pct_set_stats only
     unsigned long long beyond_limits;      // queries the points left out of a culled grid could matter to (always counted)
     unsigned long long costliest;          // the costliest exact query: 64-candidate steps << 32 | row
-    int redo_count, reserved;              // rows on the redo list (always counted)
+    int redo_count;                        // rows on the redo list (always counted)
+    int redo_adopted;                      // of which k_knn_exact took the fast sweep's list over as the answer of ring 1 (under pct_set_stats only)
 };
 static_assert(sizeof(pct_sweep_words) == 64, "eight 64-bit words");
 struct pct_dev_words {                     // ctx->counters: 512 bytes of device memory

@@ -276,6 +276,10 @@ int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, in
     // (PCT_REDO_SEED=0, read per call: neither; an A/B aid)
     const char* seed_env = pct_getenv("PCT_REDO_SEED");
     a.redo_seed = plan.lean() && !plan.tree && phase == 0 && !(seed_env && seed_env[0] == '0' && seed_env[1] == 0);
+    // ... and mark the rows whose list is the proven set of their 27 cells, which the exact sweep takes over whole
+    // (Sweep::adopt; PCT_REDO_ADOPT=0, read per call: no marks)
+    const char* adopt_env = pct_getenv("PCT_REDO_ADOPT");
+    a.redo_adopt = a.redo_seed && !(adopt_env && adopt_env[0] == '0' && adopt_env[1] == 0);
     PCT_TRY(launch_sweep(ctx, plan, a, redo, redo_count));
     PCT_HIP(ctx, clock->boundary(PCT_ST_FAST_END, ctx->stream));      // end of the dominant kernel
     // exact pass: the flagged queries (device-side count, fixed grid) or, for testing, every query

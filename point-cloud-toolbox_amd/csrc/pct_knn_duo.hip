@@ -72,6 +72,7 @@ __global__ __launch_bounds__(64, ((TREE ? PCT_TREE_CAP2 : PCT_DUO_CAP) <= 768 ? 
     run_prefix<NRUNS>(run_len, lane, my_pre, m);
     pct_stamp(a.stamp);            // (behind the prologue's loads; block 0 takes neither return above on a uniform list: pct_stamp.h)
     unsigned long long redo_mask = 0ull;
+    unsigned my_trust = 0u;        // per query (lane l = query l): 1 = its redo entry carries kRedoTrusted, 2 = never (k_knn_pair)
     if (item_overflows<TREE, NRUNS>(m, CAP, run_len, lane)) {
         if (TREE || !a.seed) {
             hand_item_to_redo(a.redo, a.redo_count, a.counters, a.stats, row0, nq, lane, true, a.nbr_pos, a.pitch);
@@ -79,6 +80,7 @@ __global__ __launch_bounds__(64, ((TREE ? PCT_TREE_CAP2 : PCT_DUO_CAP) <= 768 ? 
         }
         // the item runs on the first CAP flat slots of its stencil and all its queries go to the redo list (k_knn_pair)
         redo_mask = nq >= 64 ? ~0ull : (1ull << nq) - 1ull;
+        my_trust = 2u;
         if (a.stats && lane == 0) atomicAdd(&a.counters->lds_overflows, 1ull);
         m = CAP;
     }
@@ -292,21 +294,29 @@ __global__ __launch_bounds__(64, ((TREE ? PCT_TREE_CAP2 : PCT_DUO_CAP) <= 768 ? 
             const unsigned gk = (unsigned)__builtin_amdgcn_readlane((int)my_gkey, qi);
             const unsigned tk = tau >> SLOT_BITS;
             const unsigned need_k = min(tau == kPadElem ? 0xFFFFFFFFu : tk + 1u, eps_key);
+            // equal keys: element i ^ element i + 1 below 2^SLOT_BITS <=> same key
+            unsigned n0, n1;
+            asm("s_nop 1\n"
+                "v_mov_b32_dpp %0, %2 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n"
+                "v_mov_b32_dpp %1, %3 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n"
+                "s_nop 0"
+                : "=&v"(n0), "=&v"(n1) : "v"(e[0]), "v"(e[1]));
+            n0 = lane == 63 ? (unsigned)__builtin_amdgcn_readlane((int)e[1], 0) : n0;        // entry 64 follows entry 63
+            const bool same0 = ((e[0] ^ n0) >> SLOT_BITS) == 0u && e[0] != kPadElem && n0 != kPadElem;
+            const bool same1 = ((e[1] ^ n1) >> SLOT_BITS) == 0u && e[1] != kPadElem && n1 != kPadElem && lane < 63;
             // (a query whose proof fails stores its row like any other -- ordered or not, these are k real candidates: the
             // exact sweep starts from the distance of the farthest, Sweep::seed -- and is on the redo list all the same)
-            if (need_k > min(gk, bkey) || (tau != kPadElem && tk >= key_max - 1u)) redo_mask |= 1ull << qi;
-            // equal keys among the first k + 2 entries: ordered here by the exact values (order_equal_keys).  Detection:
-            // element i ^ element i + 1 below 2^SLOT_BITS <=> same key
+            if (need_k > min(gk, bkey) || (tau != kPadElem && tk >= key_max - 1u)) {
+                redo_mask |= 1ull << qi;
+                // trusted (k_knn_pair): the set is proven -- the (k+1)-th entry exists below bkey and the saturated key, and
+                // entry k+1 does not share its key -- so what failed is g alone; never after a failed threshold search
+                // (the list is padding: tau is)
+                const bool tie = ((__builtin_amdgcn_ballot_w64(k < 64 ? same0 : same1) >> (k & 63)) & 1ull) != 0ull;
+                const bool t = a.adopt && tau != kPadElem && tk + 1u <= bkey && tk < key_max - 1u && !tie;
+                if (lane == qi && t) my_trust |= 1u;
+            }
+            // equal keys among the first k + 2 entries: ordered here by the exact values (order_equal_keys)
             {
-                unsigned n0, n1;
-                asm("s_nop 1\n"
-                    "v_mov_b32_dpp %0, %2 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n"
-                    "v_mov_b32_dpp %1, %3 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n"
-                    "s_nop 0"
-                    : "=&v"(n0), "=&v"(n1) : "v"(e[0]), "v"(e[1]));
-                n0 = lane == 63 ? (unsigned)__builtin_amdgcn_readlane((int)e[1], 0) : n0;        // entry 64 follows entry 63
-                const bool same0 = ((e[0] ^ n0) >> SLOT_BITS) == 0u && e[0] != kPadElem && n0 != kPadElem;
-                const bool same1 = ((e[1] ^ n1) >> SLOT_BITS) == 0u && e[1] != kPadElem && n1 != kPadElem && lane < 63;
                 const unsigned long long cm = (__builtin_amdgcn_ballot_w64(same0) & order_lo) | (__builtin_amdgcn_ballot_w64(same1) & order_hi);
                 if (__builtin_expect(cm != 0ull && ((redo_mask >> qi) & 1ull) == 0ull, 0)) {
                     const bool done = order_equal_keys<2, SLOT_BITS>(e, a.pts,
@@ -357,7 +367,8 @@ __global__ __launch_bounds__(64, ((TREE ? PCT_TREE_CAP2 : PCT_DUO_CAP) <= 768 ? 
         int base = 0;
         if (lane == 0) base = atomicAdd(a.redo_count, cnt);
         base = __builtin_amdgcn_readfirstlane(base);
-        if ((redo_mask >> lane) & 1ull) a.redo[base + (int)__popcll(redo_mask & ((1ull << lane) - 1ull))] = row0 + lane;
+        if ((redo_mask >> lane) & 1ull)
+            a.redo[base + (int)__popcll(redo_mask & ((1ull << lane) - 1ull))] = (int)((unsigned)(row0 + lane) | (my_trust == 1u ? kRedoTrusted : 0u));
         if (a.stats && lane == 0) atomicAdd(&a.counters->redone_queries, (unsigned long long)cnt);
     }
 }

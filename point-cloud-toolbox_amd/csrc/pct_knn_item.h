@@ -30,6 +30,7 @@ struct PairArgs {
     int k, pitch;
     int stats;
     int seed;                 // KnnArgs::redo_seed: an item whose stencil overflows the staging area runs on its first CAP slots
+    int adopt;                // KnnArgs::redo_adopt: a redo row whose list is the proven set of the 27 cells is marked (kRedoTrusted)
     unsigned magic_x, magic_xy;      // cell -> (cx, cy, cz) by multiplication: q = (x * magic) >> shift, exact for x < 2^30
     int shift_x, shift_xy;
     double eps2;
@@ -50,6 +51,7 @@ PairArgs make_pair_args(const pct_ctx* ctx, const KnnArgs& a, bool tree, int* re
     pa.n_items = (int)ctx->n_items; pa.items_q = ctx->items_q;
     pa.k = a.k; pa.pitch = a.pitch; pa.stats = a.stats; pa.eps2 = a.eps2; pa.g = a.g;
     pa.seed = a.redo_seed;
+    pa.adopt = a.redo_adopt;
     pa.stamp = a.stamp_sweep;
     pa.items_per_xcd = pct_getenv("PCT_NO_XCD_MAP") ? 0 : (int)((ctx->n_items + 7) / 8);
     if (tree) {

@@ -97,6 +97,10 @@ __global__ __launch_bounds__(64 * kPairWaves, (TREE ? 4 : Q64 ? 5 : 6)) void k_k
     run_prefix<NRUNS>(run_len, lane, my_pre, m);
     pct_stamp(a.stamp);            // (behind the prologue's loads; block 0 takes neither return above on a uniform list: pct_stamp.h)
     unsigned long long redo_mask = 0ull;                  // queries of this item the exact sweep has to take
+    // Per query (lane l = query l, as my_gkey): 1 = the query's list is the proven set of its 27 cells and only the cube
+    // cannot vouch for it -- its redo entry carries kRedoTrusted and the exact sweep starts from the list (Sweep::adopt);
+    // 2 = never, whatever the proofs say.  Written in the redo branches only.
+    unsigned my_trust = 0u;
     if (item_overflows<TREE, NRUNS>(m, CAP, run_len, lane)) {
         if (TREE || !a.seed) {
             hand_item_to_redo(a.redo, a.redo_count, a.counters, a.stats, row0, nq, lane, true, a.nbr_pos, a.pitch);
@@ -106,6 +110,7 @@ __global__ __launch_bounds__(64 * kPairWaves, (TREE ? 4 : Q64 ? 5 : 6)) void k_k
         // all the exact sweep asks of a redo row (Sweep::seed) -- the proofs below assume the whole stencil, so every
         // query of the item is on the redo list from here on, whatever they say.
         redo_mask = nq >= 64 ? ~0ull : (1ull << nq) - 1ull;
+        my_trust = 2u;                                    // (a list of a truncated stencil is the set of nothing)
         if (a.stats && lane == 0) atomicAdd(&a.counters->lds_overflows, 1ull);
         m = CAP;
     }
@@ -393,18 +398,36 @@ __global__ __launch_bounds__(64 * kPairWaves, (TREE ? 4 : Q64 ? 5 : 6)) void k_k
             const unsigned need_kb = min(tau_b == kPadElem ? 0xFFFFFFFFu : tk_b + 1u, eps_key);
             const bool amb_a = need_ka > min(g_a, bkey_a) || (tau_a != kPadElem && tk_a >= key_max - 1u);
             const bool amb_b = need_kb > min(g_b, bkey_b) || (tau_b != kPadElem && tk_b >= key_max - 1u);
-#ifndef PCT_ABL_NO_CHECK
-            if (ok_a && amb_a) { redo_mask |= 1ull << qi; ok_a = false; }
-            if (ok_b && amb_b) { redo_mask |= 1ull << qj; ok_b = false; }
-#endif
-            // equal keys among the first k+2 entries: ordered here by the exact values (order_equal_keys).  Detection:
             // element i ^ element i+1 (one v_xor with a wave_shl:1 operand per set) below 64 <=> same key
+            unsigned xa, xb;
+            asm("v_xor_b32_dpp %0, %2, %2 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n"
+                "v_xor_b32_dpp %1, %3, %3 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n"
+                "s_nop 0"
+                : "=&v"(xa), "=&v"(xb) : "v"(e_a), "v"(e_b));
+#ifndef PCT_ABL_NO_CHECK
+            // A query that goes to the redo list is `trusted` when its set is proven all the same: the (k+1)-th entry
+            // exists, its key is below every key the pre-selection cut (bkey) and below the saturated one, and entry k+1
+            // does not share it (equal keys are not put in order on a redo row: at the boundary the wrong one of the two
+            // could be inside).  Entries 0 .. k are then every candidate of the stencil with a key up to entry k's -- what
+            // failed is g alone, the cube's guarantee and the sharding limits, and that the exact sweep can mend from
+            // ring 2 on (Sweep::adopt).  The eps key is not asked: a list of k+1 real entries lies inside the eps ball.
+            const auto trusted = [&](unsigned tau, unsigned tk, unsigned bkey, unsigned x) {
+                const bool tie = ((__builtin_amdgcn_ballot_w64(x < 64u) >> k) & 1ull) != 0ull;
+                return a.adopt && tau != kPadElem && tk + 1u <= bkey && tk < key_max - 1u && !tie;
+            };
+            if (ok_a && amb_a) {
+                redo_mask |= 1ull << qi; ok_a = false;
+                const bool t = trusted(tau_a, tk_a, bkey_a, xa);
+                if (lane == qi && t) my_trust |= 1u;
+            }
+            if (ok_b && amb_b) {
+                redo_mask |= 1ull << qj; ok_b = false;
+                const bool t = trusted(tau_b, tk_b, bkey_b, xb);
+                if (lane == qj && t) my_trust |= 1u;
+            }
+#endif
+            // equal keys among the first k+2 entries: ordered here by the exact values (order_equal_keys)
             {
-                unsigned xa, xb;
-                asm("v_xor_b32_dpp %0, %2, %2 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n"
-                    "v_xor_b32_dpp %1, %3, %3 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n"
-                    "s_nop 0"
-                    : "=&v"(xa), "=&v"(xb) : "v"(e_a), "v"(e_b));
 #ifdef PCT_ABL_NO_CHECK
                 const unsigned long long cm_any = 0ull;
 #else
@@ -496,7 +519,8 @@ __global__ __launch_bounds__(64 * kPairWaves, (TREE ? 4 : Q64 ? 5 : 6)) void k_k
         int base = 0;
         if (lane == 0) base = atomicAdd(a.redo_count, cnt);
         base = __builtin_amdgcn_readfirstlane(base);
-        if ((redo_mask >> lane) & 1ull) a.redo[base + (int)__popcll(redo_mask & ((1ull << lane) - 1ull))] = row0 + lane;
+        if ((redo_mask >> lane) & 1ull)
+            a.redo[base + (int)__popcll(redo_mask & ((1ull << lane) - 1ull))] = (int)((unsigned)(row0 + lane) | (my_trust == 1u ? kRedoTrusted : 0u));
         if (a.stats && lane == 0) atomicAdd(&a.counters->redone_queries, (unsigned long long)cnt);
     }
 }

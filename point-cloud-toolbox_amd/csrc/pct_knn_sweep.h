@@ -51,7 +51,15 @@ struct KnnArgs {
     // candidates that launch found for it, or -1 in its first column (k_knn_exact reads its starting bound from them).
     // Never set for exact_only, level passes or the hierarchical list.
     int redo_seed;
+    // ... and a row whose list is proven to be the k nearest of its 27 cells carries bit 31 in its redo entry
+    // (kRedoTrusted): k_knn_exact takes the list over as the answer of ring 1 and widens from there (Sweep::adopt).  Only
+    // with redo_seed.
+    int redo_adopt;
 };
+
+// a redo list entry: the table row, and in bit 31 the fast sweep's word that the row's list is the proven set of its 27
+// cells (a list holds fewer than 2^31 - 8 rows)
+constexpr unsigned kRedoTrusted = 0x80000000u;
 
 // rows of 128 .. PCT_K_MAX neighbours (pct_knn_wide.hip): list registers R = 4 | 8
 int pct_launch_knn_exact_wide(pct_ctx* ctx, const KnnArgs& a, int blocks, const int* list, const int* list_count);
@@ -233,30 +241,36 @@ struct Sweep {
         return (dx * dx + dy * dy) + dz * dz;
     }
 
-    // Start from a bound somebody else found (after reset()).  The row's k columns are read as k claimed positions and
-    // nothing else is believed of them: if they are k distinct positions inside the cloud, none of them the query's own
-    // record `self`, then these and `self` are k+1 distinct points, and the largest of their exact squared distances
-    // B is an upper bound of the (k+1)-th smallest.  The running bound becomes (B, INT_MAX): a candidate at exactly
-    // B passes (consider), whatever its index.  Returns B, or +inf when the row gives no bound (a marker, padding,
-    // anything out of range or repeated): the sweep then starts as it always did.
-    __device__ __forceinline__ double seed(const int* __restrict__ cols, const int self, const int n) {
+    // The k columns of a redo row as the fast sweep left them: column c in register c >> 6 of lane c & 63, -1 beyond k.
+    // (They depend on the row alone: the caller issues them beside owned_pos[row], one round trip for both.)
+    __device__ __forceinline__ void load_row(const int* __restrict__ cols, int (&p)[R]) const {
         const int lane = lane_id();
-        int p[R];
-        bool bad = false;
-        double B = dist2(pts[self]);
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int col = lane + 64 * r;
             p[r] = col < k ? cols[col] : -1;
+        }
+    }
+
+    // What seed() and adopt() believe of a row's columns, and all they believe: that they are k distinct positions inside
+    // the cloud, none of them the query's own record `self`, every one at a finite distance.  d[r] = the exact squared
+    // distance of column lane + 64 r, d_self = that of the query's own record.
+    __device__ __forceinline__ bool claimed(const int (&p)[R], const int self, const int n, double (&d)[R], double& d_self) const {
+        const int lane = lane_id();
+        bool bad = false;
+        d_self = dist2(pts[self]);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int col = lane + 64 * r;
+            d[r] = 0.0;
             if (col < k) {
                 const bool in = (unsigned)p[r] < (unsigned)n && p[r] != self;
                 bad = bad || !in;
-                const double d2 = dist2(pts[in ? p[r] : self]);
-                bad = bad || !(d2 < INFINITY);
-                B = fmax(B, d2);
+                d[r] = dist2(pts[in ? p[r] : self]);
+                bad = bad || !(d[r] < INFINITY);
             }
         }
-        if (__ballot(bad) != 0ull) return INFINITY;
+        if (__ballot(bad) != 0ull) return false;
         // distinct: column i differs from every later column
         for (int i = 0; i + 1 < k; ++i) {
             int v = p[0];
@@ -270,12 +284,61 @@ struct Sweep {
                 bad = bad || (col > i && col < k && p[r] == v);
             }
         }
-        if (__ballot(bad) != 0ull) return INFINITY;
+        return __ballot(bad) == 0ull;
+    }
+
+    // the largest of the columns' distances, wave-wide
+    __device__ __forceinline__ double farthest(const double (&d)[R]) const {
+        const int lane = lane_id();
+        double B = 0.0;
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if (lane + 64 * r < k) B = fmax(B, d[r]);
         for (int o = 32; o > 0; o >>= 1) B = fmax(B, __shfl_xor(B, o));
+        return B;
+    }
+
+    // Start from a bound somebody else found (after reset()).  The row's k columns are read as k claimed positions and
+    // nothing else is believed of them (claimed): these and `self` are then k+1 distinct points, and the largest of their
+    // exact squared distances B is an upper bound of the (k+1)-th smallest.  The running bound becomes (B, INT_MAX): a
+    // candidate at exactly B passes (consider), whatever its index.  Returns B, or +inf when the row gives no bound (a
+    // marker, padding, anything out of range or repeated): the sweep then starts as it always did.
+    __device__ __forceinline__ double seed(const int (&p)[R], const int self, const int n) {
+        double d[R], d_self;
+        if (!claimed(p, self, n, d, d_self)) return INFINITY;
+        const double B = fmax(farthest(d), d_self);
         if (!(B < INFINITY)) return INFINITY;
         tau_d = B;
         tau_p = INT_MAX;
         return B;
+    }
+
+    // Start from a SET somebody else proved (after reset()): the fast sweep marked the row as "entries 0 .. k of my list
+    // are all the candidates of the 27 cells whose key is at most entry k's, and entry k+1's key is larger" (pct_knn_pair.hip,
+    // `trusted`).  Keys grow with the exact distance, so those k+1 entries are the k+1 nearest of the 27 cells under any
+    // tie-break, and nothing outside them is as near as the farthest of them.  The row holds entries 1 .. k.  The columns
+    // are checked as in seed(); then entry 0 is the query's own record if that record is in the set at all, which it is
+    // when it is strictly nearer than the farthest column (its key is then at most that column's).  With duplicates of the
+    // query the own record can sit in a column, or tie with every column: the row then says nothing about entry 0 and
+    // takes seed()'s path.  On success `best` is the k+1 points in the sweep's own order, the bound is the (k+1)-th of
+    // them, and ring 1 needs no walk.
+    __device__ __forceinline__ bool adopt(const int (&p)[R], const int self, const int n) {
+        const int lane = lane_id();
+        double d[R], d_self;
+        if (!claimed(p, self, n, d, d_self)) return false;
+        if (!(d_self < farthest(d))) return false;
+        TopK<R> b;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int col = lane + 64 * r;          // element col: column col, then (element k) the own record, then padding
+            b.d[r] = col < k ? d[r] : col == k ? d_self : (double)INFINITY;
+            b.p[r] = col < k ? p[r] : col == k ? self : INT_MAX;
+        }
+        bitonic_sort_from<R, 2>(b, false, pts);
+        best = b;
+        empty = false;
+        refresh_tau();
+        return true;
     }
 
     // take up to 64*R pending survivors into the running list
@@ -505,7 +568,11 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_knn_exact(KnnArgs a, co
     sw.pend_p = s_pend_p[w];
 
     for (int64_t item = (int64_t)blockIdx.x * kWavesPerBlock + w; item < total; item += nwaves) {
-        const int row = list ? list[item] : (int)item;          // neighbour-table row (owned queries only)
+        const int entry = list ? list[item] : (int)item;
+        const int row = entry & (int)~kRedoTrusted;              // neighbour-table row (owned queries only)
+        const bool seeded = R <= 2 && a.redo_seed && list;         // (only k_knn_pair and k_knn_duo leave lists: k <= 127)
+        int cols[R];
+        if (seeded) sw.load_row(a.nbr_pos + (int64_t)row * a.pitch, cols);
         const int q = a.owned_pos[row];
         const float4 qp = a.pts[q];
         // the query's cell comes from its float32 (tree) coordinates, as in the build
@@ -524,12 +591,15 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_knn_exact(KnnArgs a, co
         const double gz = (sw.qz - g.oz) * g.inv_cell - cz;
         // the fast sweep in front left what it found in the row: the bound starts there, not at +inf, the first flush
         // takes about k+1 survivors instead of the cube's population, and the cube loses the cells beyond the bound
-        const double seed_d2 = a.redo_seed && list ? sw.seed(a.nbr_pos + (int64_t)row * a.pitch, q, (int)a.n) : (double)INFINITY;
+        // A row the fast sweep marked brings the whole answer of ring 1 with it (Sweep::adopt): nothing of the first cube is
+        // walked, the loop below goes straight to the guarantee test of ring 1 and widens from there.
+        const bool adopted = seeded && entry < 0 && sw.adopt(cols, q, (int)a.n);
+        const double seed_d2 = adopted ? sw.tau_d : seeded ? sw.seed(cols, q, (int)a.n) : (double)INFINITY;
         ShellIter it;
         it.start(g, cy, cz, -1, 1, seed_d2, gx, gy, gz);
         // candidate loads run one step ahead of their use (a shell is many short runs, each a dependent load)
         int nbase = 0, nlim = 0;
-        bool have_next = it.next(g, cs, cx, cy, cz, nbase, nlim);
+        bool have_next = !adopted && it.next(g, cs, cx, cy, cz, nbase, nlim);
         float4 c_next = make_float4(0.f, 0.f, 0.f, 0.f);
         if (have_next && nbase + lane < nlim) c_next = a.pts[nbase + lane];
         for (;;) {
@@ -557,6 +627,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_knn_exact(KnnArgs a, co
             if (have_next && nbase + lane < nlim) c_next = a.pts[nbase + lane];
         }
         if (a.stats && lane == 0 && it.ring > 1) atomicAdd(&a.counters->ring_fallbacks, 1ull);
+        if (a.stats && lane == 0 && adopted) atomicAdd(&a.counters->redo_adopted, 1);
         sw.store(row, a.pitch, a.nbr_pos, a.nbr_dist, a.nbr_cnt);
         if (a.row_done && lane == 0) a.row_done[row] = 1;
     }
@@ -584,7 +655,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_knn_exact_tree(KnnArgs 
     sw.pend_p = s_pend_p[w];
 
     for (int64_t item = (int64_t)blockIdx.x * kWavesPerBlock + w; item < total; item += nwaves) {
-        const int row = list ? list[item] : (int)item;          // table row = Morton position of the query
+        const int row = (list ? list[item] : (int)item) & (int)~kRedoTrusted;      // table row = Morton position of the query
         if (a.ptsd) {                               // float64 clouds: native query, float32-rounded candidates (pct:74, 83)
             const double4 qd = a.ptsd[row];
             sw.qx = qd.x; sw.qy = qd.y; sw.qz = qd.z;

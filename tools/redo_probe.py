@@ -16,4 +16,4 @@ for kk in ks:
     for _ in range(3):
         h.curvature(kk, 0.0, _capi.KNN_GRID)
     t = h.timings()
-    print(kk, {k: t[k] for k in ("redone_queries", "lds_overflows", "ring_fallbacks", "occupied_cells", "occupancy", "knn_ms", "knn_fast_ms")}, flush=True)
+    print(kk, {k: t[k] for k in ("redone_queries", "redo_adopted", "lds_overflows", "ring_fallbacks", "occupied_cells", "occupancy", "knn_ms", "knn_fast_ms")}, flush=True)
