@@ -612,6 +612,38 @@ int pct_synchronize(pct_ctx* ctx);
 /* Hardware self-test of the cross-lane primitives the sweep relies on
  * (DPP / ds_swizzle lane exchanges); *failures == 0 on a healthy gfx950. */
 int pct_selftest(pct_ctx* ctx, int32_t* failures);
+/* Self-tests of the wave-level sorters every neighbour row passes through (tests/test_gpu_sort_net.py).  They run the
+ * very code the sweeps run on lists the caller supplies: host arrays in, host arrays out, device memory of their own for
+ * the length of the call -- nothing resident on the handle is read, written or dropped.
+ *
+ * pct_selftest_sort: the fast sweeps' sorting network on n_lists lists of uint32, each returned in ascending order.
+ *   network             code under test                               list length   lists per wave
+ *   PCT_NET_FAST1       the C++ network, one list register            64            1
+ *   PCT_NET_FAST2       the C++ network, two list registers           128           1
+ *   PCT_NET_SETS1       two lists side by side, one register each     64            2
+ *   PCT_NET_SETS2       two lists side by side, two registers each    128           2
+ *   PCT_NET_PAIR        the assembly block of k_knn_pair              64            2
+ *   PCT_NET_DUO         the assembly block of k_knn_duo               128           1
+ * Lists lie one after the other in `in` and `out`; with two lists per wave, lists 2 w and 2 w + 1 share wave w and
+ * n_lists must be even.  PCT_ERR_INVALID for another network, a null array, n_lists < 1.
+ *
+ * pct_selftest_sort_exact: the exact sweep's sorters over (float64 d2, int32 position) elements, lists of 64 * regs
+ * (regs = 1, 2, 4, 8), in its total order: d2, then the public index pub[position]; padding is (+inf, INT32_MAX).
+ * PCT_EXACT_ASCENDING / PCT_EXACT_DESCENDING sort each list; PCT_EXACT_MERGE_MIN replaces each ascending list (d2, pos)
+ * by the 64 * regs smallest of its union with the DESCENDING list (batch_d2, batch_pos), ascending (both null otherwise).
+ * Every real position must be in [0, n_pub).
+ *
+ * pct_selftest_order_keys: the in-place repair of equal keys on n_lists sorted lists of 64 * regs elements
+ * key << slot_bits | payload (padding 0xFFFFFFFF).  Per list, d2[list * 2^slot_bits + payload] is the exact value of the
+ * element with that payload and pub[list * 2^slot_bits + payload] its public index.  (regs, slot_bits) is one of
+ * (1, 6), (1, 9), (2, 7), (2, 10).  out: the lists; done[list] = 1 if the repair finished, 0 if it gave up. */
+enum { PCT_NET_FAST1 = 0, PCT_NET_FAST2 = 1, PCT_NET_SETS1 = 2, PCT_NET_SETS2 = 3, PCT_NET_PAIR = 4, PCT_NET_DUO = 5 };
+enum { PCT_EXACT_ASCENDING = 0, PCT_EXACT_DESCENDING = 1, PCT_EXACT_MERGE_MIN = 2 };
+int pct_selftest_sort(pct_ctx* ctx, int32_t network, const uint32_t* in, int64_t n_lists, uint32_t* out);
+int pct_selftest_sort_exact(pct_ctx* ctx, int32_t regs, int32_t mode, const double* d2, const int32_t* pos, const double* batch_d2,
+                            const int32_t* batch_pos, const int32_t* pub, int64_t n_pub, int64_t n_lists, double* out_d2, int32_t* out_pos);
+int pct_selftest_order_keys(pct_ctx* ctx, int32_t regs, int32_t slot_bits, const uint32_t* elems, const double* d2, const int32_t* pub,
+                            int64_t n_lists, uint32_t* out, int32_t* done);
 
 #ifdef __cplusplus
 }

@@ -33,6 +33,9 @@ TRI_WIND_FRAMES = 1                                     # pct_point_triangles' f
 ORIENT_ANCHORS = {"seed": ORIENT_SEED, "top": ORIENT_TOP, "view": ORIENT_VIEW}
 QUERY_AUTO, QUERY_SWEEP, QUERY_GRID = 0, 1, 2                    # pct_query_points_algo, pct_query_ball
 BALL_SORTED, BALL_DISTANCES, BALL_COUNT_ONLY = 1, 2, 4           # pct_query_ball's flags
+NET_FAST1, NET_FAST2, NET_SETS1, NET_SETS2, NET_PAIR, NET_DUO = range(6)        # pct_selftest_sort's networks
+NET_LIST = {NET_FAST1: 64, NET_FAST2: 128, NET_SETS1: 64, NET_SETS2: 128, NET_PAIR: 64, NET_DUO: 128}      # elements of a list
+EXACT_ASCENDING, EXACT_DESCENDING, EXACT_MERGE_MIN = 0, 1, 2     # pct_selftest_sort_exact's modes
 
 
 class Timings(C.Structure):
@@ -60,6 +63,7 @@ _i64p = C.POINTER(C.c_int64)
 _f32p = C.POINTER(C.c_float)
 _f64p = C.POINTER(C.c_double)
 _u8p = C.POINTER(C.c_uint8)
+_u32p = C.POINTER(C.c_uint32)
 
 # name -> (restype, argtypes); every symbol declared in include/pct_hip.h and include/pct_hip_surface.h
 SIGNATURES = {
@@ -140,6 +144,9 @@ SIGNATURES = {
     "pct_device_download": (C.c_int, [_p, _p, _p, C.c_int64]),
     "pct_synchronize": (C.c_int, [_p]),
     "pct_selftest": (C.c_int, [_p, _i32p]),
+    "pct_selftest_sort": (C.c_int, [_p, C.c_int32, _u32p, C.c_int64, _u32p]),
+    "pct_selftest_sort_exact": (C.c_int, [_p, C.c_int32, C.c_int32, _f64p, _i32p, _f64p, _i32p, _i32p, C.c_int64, C.c_int64, _f64p, _i32p]),
+    "pct_selftest_order_keys": (C.c_int, [_p, C.c_int32, C.c_int32, _u32p, _f64p, _i32p, C.c_int64, _u32p, _i32p]),
     # include/pct_hip_surface.h
     "pct_point_triangles": (C.c_int, [_p, C.c_int32]),
     "pct_get_point_fans": (C.c_int, [_p, C.c_int64, C.c_int64, _i64p, _i32p]),
@@ -910,6 +917,44 @@ class Handle:
         n = C.c_int32(-1)
         self._check(self._lib.pct_selftest(self._h, C.byref(n)))
         return n.value
+
+    # -- the wave-level sorters on caller-supplied lists (tests/test_gpu_sort_net.py) ---------------------------------
+    def selftest_sort(self, network, lists):
+        """lists (n, 64 | 128) uint32 -> each list sorted by the network `network` (NET_*)."""
+        x = np.ascontiguousarray(lists, dtype=np.uint32)
+        assert x.ndim == 2 and x.shape[1] == NET_LIST[network]
+        out = np.empty_like(x)
+        self._check(self._lib.pct_selftest_sort(self._h, network, _ptr(x, _u32p), len(x), _ptr(out, _u32p)))
+        return out
+
+    def selftest_sort_exact(self, regs, mode, d2, pos, pub, batch=None):
+        """lists (n, 64 regs) of (float64 d2, int32 position) through the exact sweep's sorter (EXACT_*); pub[position] is
+        the public index; batch = (d2, pos) of the descending lists of EXACT_MERGE_MIN."""
+        d2 = np.ascontiguousarray(d2, dtype=np.float64)
+        pos = np.ascontiguousarray(pos, dtype=np.int32)
+        pub = np.ascontiguousarray(pub, dtype=np.int32)
+        assert d2.shape == pos.shape == (len(d2), 64 * regs) and (batch is not None) == (mode == EXACT_MERGE_MIN)
+        bd = bp = None
+        if batch is not None:
+            bd, bp = np.ascontiguousarray(batch[0], dtype=np.float64), np.ascontiguousarray(batch[1], dtype=np.int32)
+            assert bd.shape == bp.shape == d2.shape
+        od, op = np.empty_like(d2), np.empty_like(pos)
+        self._check(self._lib.pct_selftest_sort_exact(self._h, regs, mode, _ptr(d2, _f64p), _ptr(pos, _i32p),
+                                                      None if bd is None else _ptr(bd, _f64p), None if bp is None else _ptr(bp, _i32p),
+                                                      _ptr(pub, _i32p), len(pub), len(d2), _ptr(od, _f64p), _ptr(op, _i32p)))
+        return od, op
+
+    def selftest_order_keys(self, regs, slot_bits, elems, d2, pub):
+        """order_equal_keys<regs, slot_bits> on lists (n, 64 regs) uint32; d2, pub (n, 2^slot_bits) by payload.
+        Returns (lists, flags)."""
+        e = np.ascontiguousarray(elems, dtype=np.uint32)
+        d2 = np.ascontiguousarray(d2, dtype=np.float64)
+        pub = np.ascontiguousarray(pub, dtype=np.int32)
+        assert e.shape == (len(e), 64 * regs) and d2.shape == pub.shape == (len(e), 1 << slot_bits)
+        out, done = np.empty_like(e), np.empty(len(e), np.int32)
+        self._check(self._lib.pct_selftest_order_keys(self._h, regs, slot_bits, _ptr(e, _u32p), _ptr(d2, _f64p), _ptr(pub, _i32p),
+                                                      len(e), _ptr(out, _u32p), _ptr(done, _i32p)))
+        return out, done != 0
 
     def synchronize(self):
         self._check(self._lib.pct_synchronize(self._h))

@@ -13,6 +13,7 @@
 #include <stdlib.h>
 #include <sys/prctl.h>
 #include <unistd.h>
+#include <vector>
 
 int pct_fail(pct_ctx* ctx, int code, const char* fmt, ...) {
     if (ctx) {
@@ -1669,6 +1670,130 @@ int pct_selftest(pct_ctx* ctx, int32_t* failures) {
     PCT_HIP(ctx, hipMemsetAsync(ctx->red.p, 0, 64, ctx->stream));
     PCT_TRY(pct_launch_selftest(ctx, (int*)ctx->red.p));
     PCT_HIP(ctx, hipMemcpyAsync(failures, ctx->red.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PCT_OK;
+}
+
+}  // extern "C"
+
+// ---- self-tests of the sorters: host arrays in and out, device memory of their own, nothing of the handle's ---------------
+namespace {
+struct DevScratch {                                    // freed when the call returns, whichever way
+    std::vector<void*> held;
+    ~DevScratch() { for (void* p : held) (void)hipFree(p); }
+    template <class T>
+    hipError_t take(T** p, size_t count) {
+        void* v = nullptr;
+        const hipError_t e = hipMalloc(&v, count * sizeof(T));
+        if (e == hipSuccess) held.push_back(v);
+        *p = (T*)v;
+        return e;
+    }
+};
+constexpr int64_t kSelftestMaxLists = 1 << 20;
+
+// public indices as the records carry them: the .w word of a float4
+std::vector<float4> pub_records(const int32_t* pub, int64_t n) {
+    std::vector<float4> r((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        float w;
+        memcpy(&w, &pub[i], 4);
+        r[(size_t)i] = make_float4(0.f, 0.f, 0.f, w);
+    }
+    return r;
+}
+}  // namespace
+
+extern "C" {
+
+int pct_selftest_sort(pct_ctx* ctx, int32_t network, const uint32_t* in, int64_t n_lists, uint32_t* out) {
+    PCT_TRY(begin_call(ctx));
+    const int regs = pct_selftest_sort_regs(network);
+    if (!regs) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sort: no network %d", (int)network);
+    if (!in || !out) return pct_fail(ctx, PCT_ERR_INVALID, "null array");
+    const bool two = network == PCT_NET_SETS1 || network == PCT_NET_SETS2 || network == PCT_NET_PAIR;
+    if (n_lists < 1 || n_lists > kSelftestMaxLists || (two && (n_lists & 1)))
+        return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sort: n_lists = %lld (1 .. 2^20; even where a wave sorts two lists)", (long long)n_lists);
+    const int n_waves = (int)(two ? n_lists / 2 : n_lists);
+    const size_t count = (size_t)n_waves * 64 * regs;
+    DevScratch mem;
+    uint32_t *d_in, *d_out;
+    PCT_HIP(ctx, mem.take(&d_in, count));
+    PCT_HIP(ctx, mem.take(&d_out, count));
+    PCT_HIP(ctx, hipMemcpyAsync(d_in, in, count * 4, hipMemcpyHostToDevice, ctx->stream));
+    PCT_TRY(pct_launch_selftest_sort(ctx, network, d_in, n_waves, d_out));
+    PCT_HIP(ctx, hipMemcpyAsync(out, d_out, count * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PCT_OK;
+}
+
+int pct_selftest_sort_exact(pct_ctx* ctx, int32_t regs, int32_t mode, const double* d2, const int32_t* pos, const double* batch_d2,
+                            const int32_t* batch_pos, const int32_t* pub, int64_t n_pub, int64_t n_lists, double* out_d2, int32_t* out_pos) {
+    PCT_TRY(begin_call(ctx));
+    if (regs != 1 && regs != 2 && regs != 4 && regs != 8) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sort_exact: list registers are 1, 2, 4 or 8, not %d", (int)regs);
+    if (mode != PCT_EXACT_ASCENDING && mode != PCT_EXACT_DESCENDING && mode != PCT_EXACT_MERGE_MIN)
+        return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sort_exact: no mode %d", (int)mode);
+    const bool merge = mode == PCT_EXACT_MERGE_MIN;
+    if (!d2 || !pos || !pub || !out_d2 || !out_pos || (merge && (!batch_d2 || !batch_pos))) return pct_fail(ctx, PCT_ERR_INVALID, "null array");
+    if (n_lists < 1 || n_lists > kSelftestMaxLists || n_pub < 1 || n_pub > (1 << 24)) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sort_exact: n_lists = %lld, n_pub = %lld", (long long)n_lists, (long long)n_pub);
+    const size_t count = (size_t)n_lists * 64 * regs;
+    // the kernels read pub[position] for tied elements: no position may point outside the table
+    for (int pass = 0; pass < (merge ? 2 : 1); ++pass) {
+        const int32_t* p = pass ? batch_pos : pos;
+        for (size_t i = 0; i < count; ++i)
+            if (p[i] != INT32_MAX && (p[i] < 0 || p[i] >= n_pub)) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sort_exact: position %d outside [0, n_pub)", (int)p[i]);
+    }
+    const std::vector<float4> rec = pub_records(pub, n_pub);
+    DevScratch mem;
+    double *d_d2, *d_bd2 = nullptr, *d_od2;
+    int *d_pos, *d_bpos = nullptr, *d_opos;
+    float4* d_pts;
+    PCT_HIP(ctx, mem.take(&d_d2, count));
+    PCT_HIP(ctx, mem.take(&d_pos, count));
+    PCT_HIP(ctx, mem.take(&d_od2, count));
+    PCT_HIP(ctx, mem.take(&d_opos, count));
+    PCT_HIP(ctx, mem.take(&d_pts, rec.size()));
+    PCT_HIP(ctx, hipMemcpyAsync(d_d2, d2, count * 8, hipMemcpyHostToDevice, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(d_pos, pos, count * 4, hipMemcpyHostToDevice, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(d_pts, rec.data(), rec.size() * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+    if (merge) {
+        PCT_HIP(ctx, mem.take(&d_bd2, count));
+        PCT_HIP(ctx, mem.take(&d_bpos, count));
+        PCT_HIP(ctx, hipMemcpyAsync(d_bd2, batch_d2, count * 8, hipMemcpyHostToDevice, ctx->stream));
+        PCT_HIP(ctx, hipMemcpyAsync(d_bpos, batch_pos, count * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    PCT_TRY(pct_launch_selftest_exact(ctx, regs, mode, d_d2, d_pos, d_bd2, d_bpos, d_pts, (int)n_lists, d_od2, d_opos));
+    PCT_HIP(ctx, hipMemcpyAsync(out_d2, d_od2, count * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(out_pos, d_opos, count * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (rec and the scratch outlive every copy: waited for here)
+    return PCT_OK;
+}
+
+int pct_selftest_order_keys(pct_ctx* ctx, int32_t regs, int32_t slot_bits, const uint32_t* elems, const double* d2, const int32_t* pub,
+                            int64_t n_lists, uint32_t* out, int32_t* done) {
+    PCT_TRY(begin_call(ctx));
+    if (!((regs == 1 && (slot_bits == 6 || slot_bits == 9)) || (regs == 2 && (slot_bits == 7 || slot_bits == 10))))
+        return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_order_keys: (regs, slot_bits) is (1, 6), (1, 9), (2, 7) or (2, 10), not (%d, %d)", (int)regs, (int)slot_bits);
+    if (!elems || !d2 || !pub || !out || !done) return pct_fail(ctx, PCT_ERR_INVALID, "null array");
+    if (n_lists < 1 || n_lists > (1 << 16)) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_order_keys: n_lists = %lld (1 .. 65536)", (long long)n_lists);
+    const size_t count = (size_t)n_lists * 64 * regs, table = (size_t)n_lists << slot_bits;
+    const std::vector<float4> rec = pub_records(pub, (int64_t)table);
+    DevScratch mem;
+    uint32_t *d_e, *d_out;
+    double* d_d2;
+    float4* d_pts;
+    int* d_done;
+    PCT_HIP(ctx, mem.take(&d_e, count));
+    PCT_HIP(ctx, mem.take(&d_out, count));
+    PCT_HIP(ctx, mem.take(&d_d2, table));
+    PCT_HIP(ctx, mem.take(&d_pts, table));
+    PCT_HIP(ctx, mem.take(&d_done, (size_t)n_lists));
+    PCT_HIP(ctx, hipMemcpyAsync(d_e, elems, count * 4, hipMemcpyHostToDevice, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(d_d2, d2, table * 8, hipMemcpyHostToDevice, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(d_pts, rec.data(), table * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+    PCT_TRY(pct_launch_selftest_order(ctx, regs, slot_bits, d_e, d_d2, d_pts, (int)n_lists, d_out, d_done));
+    PCT_HIP(ctx, hipMemcpyAsync(out, d_out, count * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(done, d_done, (size_t)n_lists * 4, hipMemcpyDeviceToHost, ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PCT_OK;
 }

@@ -535,6 +535,13 @@ int pct_launch_curvatures(pct_ctx* ctx, const float* d_coefs, int64_t rows, floa
 int pct_launch_plane_rotate(pct_ctx* ctx, const void* d_nbrs, bool f64, int64_t batch, int32_t m, double* d_out);
 int pct_launch_quadric_rows(pct_ctx* ctx, const float* d_pts, int64_t batch, int32_t m, float* d_coefs);
 int pct_launch_selftest(pct_ctx* ctx, int* d_fails);
+// the sorters' self-tests (pct_knn.hip): device arrays, one wave per list (per pair of lists where the network sorts two)
+int pct_selftest_sort_regs(int network);             // list registers of a wave under that network; 0: no such network
+int pct_launch_selftest_sort(pct_ctx* ctx, int network, const unsigned* d_in, int n_waves, unsigned* d_out);
+int pct_launch_selftest_exact(pct_ctx* ctx, int regs, int mode, const double* d2, const int* pos, const double* bd2, const int* bpos,
+                              const float4* pts, int n_lists, double* out_d2, int* out_pos);
+int pct_launch_selftest_order(pct_ctx* ctx, int regs, int slot_bits, const unsigned* elems, const double* d2, const float4* pts, int n_lists,
+                              unsigned* out, int* done);
 int pct_ensure_plain_records(pct_ctx* ctx);
 int pct_launch_fit_rows_f64(pct_ctx* ctx, const int32_t* d_idx, const int32_t* d_cnt, const int64_t* d_query, int64_t rows,
                             int32_t k, int32_t pitch, double* d_coefs, double* d_K, double* d_H);

@@ -27,10 +27,11 @@
 //                (or every query, for testing): candidates cube by cube from global memory, (fp64 d2, public index)
 //                comparisons, shell-by-shell widening until the searched cube guarantees the answer.
 //   k_knn_brute  (pct_knn_sweep.h) exhaustive sweep, wave per query: small clouds and the on-device cross-check.
-//   k_query_points, k_export*, k_item_census, k_selftest  (this file) caller-supplied queries; neighbour table (sorted
-//                space, owned rows) -> public (rows, k) index / distance arrays; the work-item census; the lane_xor self-test.
+//   k_query_points, k_export*, k_item_census, k_selftest*  (this file) caller-supplied queries; neighbour table (sorted
+//                space, owned rows) -> public (rows, k) index / distance arrays; the work-item census; the self-tests of
+//                the cross-lane primitives, the sorting networks and the repair of equal keys.
 // This file also holds the host side of a sweep: the kernel argument, the table, the one launch of the planned kernel.
-#include "pct_knn_sweep.h"
+#include "pct_knn_net.h"
 
 namespace {
 
@@ -145,6 +146,89 @@ __global__ __launch_bounds__(64) void k_selftest(int* fails) {
     bad += lane_xor<16>(v) != __shfl_xor(v, 16);
     bad += lane_xor<32>(v) != __shfl_xor(v, 32);
     if (bad) atomicAdd(fails, bad);
+}
+
+// ---------------------------------------------------------------------------
+// The wave-level sorters on caller-supplied lists (pct_selftest_sort, pct_selftest_sort_exact, pct_selftest_order_keys):
+// one wave per list -- or per pair of lists, for the forms that sort two side by side -- several waves per block as in
+// the sweeps, register j of a wave at  base + 64 j + lane.  Each kernel instantiates what a sweep instantiates and calls
+// it the way the sweep does; nothing else is computed.
+// ---------------------------------------------------------------------------
+constexpr int net_regs(int net) { return net == PCT_NET_FAST1 ? 1 : net == PCT_NET_SETS2 ? 4 : 2; }      // list registers of a wave
+
+template <int NET>
+__global__ __launch_bounds__(64 * kWavesPerBlock) void k_selftest_sort(const unsigned* __restrict__ in, unsigned* __restrict__ out, int n_waves, unsigned zero) {
+    constexpr int NR = net_regs(NET);
+    const int w = (int)blockIdx.x * kWavesPerBlock + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (w >= n_waves) return;
+    const int lane = lane_id();
+    const SortLanes c = make_sort_lanes();
+    const size_t base = (size_t)w * (64 * NR) + lane;
+    unsigned raw[NR];
+#pragma unroll
+    for (int j = 0; j < NR; ++j) raw[j] = in[base + 64 * j];
+    // `zero` is 0: the xor changes nothing, but it is a VALU write of every list register directly ahead of the network.
+    // The assembly blocks assume exactly that of their caller (their leading s_nop 1 covers a DPP read two wait states
+    // after it), so the blocks meet here the hazard window they meet in k_knn_pair / k_knn_duo -- a register that came
+    // straight from a load would be settled long before and could hide a missing wait state.
+    FastK<NR> t;
+#pragma unroll
+    for (int j = 0; j < NR; ++j) t.e[j] = raw[j] ^ zero;
+    if constexpr (NET == PCT_NET_FAST1) fast_sort_from<1, 2>(t, c);
+    else if constexpr (NET == PCT_NET_FAST2) fast_sort_from<2, 2>(t, c);
+    else if constexpr (NET == PCT_NET_SETS1) fast_sort_sets<1, 2, 2>(t, c);
+    else if constexpr (NET == PCT_NET_SETS2) fast_sort_sets<2, 2, 2>(t, c);
+    else if constexpr (NET == PCT_NET_PAIR) sort_pair_asm(t.e[0], t.e[1], c);
+    else sort_duo_asm(t.e[0], t.e[1], c);
+#pragma unroll
+    for (int j = 0; j < NR; ++j) out[base + 64 * j] = t.e[j];
+}
+
+// the exact sweep's sorters: MODE 0 / 1 = bitonic_sort_from<R, 2> ascending / descending, 2 = bitonic_merge_min<R> of
+// list (d2, pos) (ascending) with batch (bd2, bpos) (descending)
+template <int R, int MODE>
+__global__ __launch_bounds__(64 * kWavesPerBlock) void k_selftest_exact(const double* __restrict__ d2, const int* __restrict__ pos,
+                                                                        const double* __restrict__ bd2, const int* __restrict__ bpos,
+                                                                        const float4* __restrict__ pts, int n_lists,
+                                                                        double* __restrict__ out_d2, int* __restrict__ out_pos) {
+    const int w = (int)blockIdx.x * kWavesPerBlock + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (w >= n_lists) return;
+    const size_t base = (size_t)w * (64 * R) + lane_id();
+    TopK<R> t;
+#pragma unroll
+    for (int r = 0; r < R; ++r) { t.d[r] = d2[base + 64 * r]; t.p[r] = pos[base + 64 * r]; }
+    if constexpr (MODE == 2) {
+        TopK<R> b;
+#pragma unroll
+        for (int r = 0; r < R; ++r) { b.d[r] = bd2[base + 64 * r]; b.p[r] = bpos[base + 64 * r]; }
+        bitonic_merge_min<R>(t, b, pts);
+    } else {
+        bitonic_sort_from<R, 2>(t, MODE == 1, pts);
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) { out_d2[base + 64 * r] = t.d[r]; out_pos[base + 64 * r] = t.p[r]; }
+}
+
+// order_equal_keys<R, SLOT_BITS> on each list: the exact value of payload p is d2[list][p], its position is p itself and
+// its public index pts[list][p].w -- tables of 2^SLOT_BITS entries per list
+template <int R, int SLOT_BITS>
+__global__ __launch_bounds__(64 * kWavesPerBlock) void k_selftest_order(const unsigned* __restrict__ elems, const double* __restrict__ d2,
+                                                                        const float4* __restrict__ pts, int n_lists,
+                                                                        unsigned* __restrict__ out, int* __restrict__ done) {
+    const int w = (int)blockIdx.x * kWavesPerBlock + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (w >= n_lists) return;
+    const int lane = lane_id();
+    const size_t base = (size_t)w * (64 * R) + lane;
+    const double* const my_d2 = d2 + ((size_t)w << SLOT_BITS);
+    unsigned e[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) e[r] = elems[base + 64 * r];
+    const bool ok = order_equal_keys<R, SLOT_BITS>(e, pts + ((size_t)w << SLOT_BITS),
+        [&](unsigned payload) { return my_d2[payload]; },
+        [&](unsigned payload) { return (int)payload; });
+#pragma unroll
+    for (int r = 0; r < R; ++r) out[base + 64 * r] = e[r];
+    if (lane == 0) done[w] = ok ? 1 : 0;
 }
 
 // One thread per work item: population and non-empty cells of its 27-cell stencil (pct_item_census).
@@ -426,6 +510,60 @@ int pct_launch_query_points(pct_ctx* ctx, const double* d_q, int64_t m, int32_t 
 
 int pct_launch_selftest(pct_ctx* ctx, int* d_fails) {
     PCT_LAUNCH(k_selftest, dim3(1), dim3(64), 0, ctx->stream, d_fails);
+    PCT_HIP(ctx, hipGetLastError());
+    return PCT_OK;
+}
+
+int pct_selftest_sort_regs(int network) { return network >= PCT_NET_FAST1 && network <= PCT_NET_DUO ? net_regs(network) : 0; }
+
+int pct_launch_selftest_sort(pct_ctx* ctx, int network, const unsigned* d_in, int n_waves, unsigned* d_out) {
+    const dim3 grid((unsigned)((n_waves + kWavesPerBlock - 1) / kWavesPerBlock)), block(64 * kWavesPerBlock);
+    switch (network) {
+#define PCT_NET_CASE(N) case N: PCT_LAUNCH(k_selftest_sort<N>, grid, block, 0, ctx->stream, d_in, d_out, n_waves, 0u); break
+        PCT_NET_CASE(PCT_NET_FAST1); PCT_NET_CASE(PCT_NET_FAST2); PCT_NET_CASE(PCT_NET_SETS1);
+        PCT_NET_CASE(PCT_NET_SETS2); PCT_NET_CASE(PCT_NET_PAIR); PCT_NET_CASE(PCT_NET_DUO);
+#undef PCT_NET_CASE
+        default: return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sort: no network %d", network);
+    }
+    PCT_HIP(ctx, hipGetLastError());
+    return PCT_OK;
+}
+
+namespace {
+template <int R>
+void launch_selftest_exact(pct_ctx* ctx, int mode, const double* d2, const int* pos, const double* bd2, const int* bpos, const float4* pts,
+                           int n_lists, double* out_d2, int* out_pos) {
+    const dim3 grid((unsigned)((n_lists + kWavesPerBlock - 1) / kWavesPerBlock)), block(64 * kWavesPerBlock);
+    if (mode == PCT_EXACT_ASCENDING) PCT_LAUNCH_T((k_selftest_exact<R, 0>), grid, block, 0, ctx->stream, d2, pos, bd2, bpos, pts, n_lists, out_d2, out_pos);
+    else if (mode == PCT_EXACT_DESCENDING) PCT_LAUNCH_T((k_selftest_exact<R, 1>), grid, block, 0, ctx->stream, d2, pos, bd2, bpos, pts, n_lists, out_d2, out_pos);
+    else PCT_LAUNCH_T((k_selftest_exact<R, 2>), grid, block, 0, ctx->stream, d2, pos, bd2, bpos, pts, n_lists, out_d2, out_pos);
+}
+}  // namespace
+
+int pct_launch_selftest_exact(pct_ctx* ctx, int regs, int mode, const double* d2, const int* pos, const double* bd2, const int* bpos,
+                              const float4* pts, int n_lists, double* out_d2, int* out_pos) {
+    if (mode != PCT_EXACT_ASCENDING && mode != PCT_EXACT_DESCENDING && mode != PCT_EXACT_MERGE_MIN)
+        return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sort_exact: no mode %d", mode);
+    switch (regs) {
+        case 1: launch_selftest_exact<1>(ctx, mode, d2, pos, bd2, bpos, pts, n_lists, out_d2, out_pos); break;
+        case 2: launch_selftest_exact<2>(ctx, mode, d2, pos, bd2, bpos, pts, n_lists, out_d2, out_pos); break;
+        case 4: launch_selftest_exact<4>(ctx, mode, d2, pos, bd2, bpos, pts, n_lists, out_d2, out_pos); break;
+        case 8: launch_selftest_exact<8>(ctx, mode, d2, pos, bd2, bpos, pts, n_lists, out_d2, out_pos); break;
+        default: return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sort_exact: list registers are 1, 2, 4 or 8, not %d", regs);
+    }
+    PCT_HIP(ctx, hipGetLastError());
+    return PCT_OK;
+}
+
+int pct_launch_selftest_order(pct_ctx* ctx, int regs, int slot_bits, const unsigned* elems, const double* d2, const float4* pts, int n_lists,
+                              unsigned* out, int* done) {
+    const dim3 grid((unsigned)((n_lists + kWavesPerBlock - 1) / kWavesPerBlock)), block(64 * kWavesPerBlock);
+    // the pairs the sweeps instantiate: 6 | 7 slot bits behind a pre-selection (k_knn_pair, k_knn_duo, k_knn_fast), 9 | 10 without
+    if (regs == 1 && slot_bits == 6) PCT_LAUNCH_T((k_selftest_order<1, 6>), grid, block, 0, ctx->stream, elems, d2, pts, n_lists, out, done);
+    else if (regs == 1 && slot_bits == 9) PCT_LAUNCH_T((k_selftest_order<1, 9>), grid, block, 0, ctx->stream, elems, d2, pts, n_lists, out, done);
+    else if (regs == 2 && slot_bits == 7) PCT_LAUNCH_T((k_selftest_order<2, 7>), grid, block, 0, ctx->stream, elems, d2, pts, n_lists, out, done);
+    else if (regs == 2 && slot_bits == 10) PCT_LAUNCH_T((k_selftest_order<2, 10>), grid, block, 0, ctx->stream, elems, d2, pts, n_lists, out, done);
+    else return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_order_keys: (regs, slot_bits) is (1, 6), (1, 9), (2, 7) or (2, 10), not (%d, %d)", regs, slot_bits);
     PCT_HIP(ctx, hipGetLastError());
     return PCT_OK;
 }

@@ -13,19 +13,6 @@ namespace {
 // Same proofs, same bit-identical rows as k_knn_fast<2, EPS, true, true>: what could not be proven goes to
 // the redo list.  Positions (and distances) of the survivors wait in LDS for the sorted order.
 // ---------------------------------------------------------------------------
-#include "pct_sort_duo.inc"
-
-__device__ __forceinline__ void sort_duo_asm(unsigned& ea, unsigned& eb, const SortLanes& c) {
-    unsigned ta, tb;
-    asm volatile(PCT_SORT_DUO_ASM
-                 : [ea] "+v"(ea), [eb] "+v"(eb), [ta] "=&v"(ta), [tb] "=&v"(tb)
-                 : [sel0] "v"(c.sel[0]), [sel1] "v"(c.sel[1]), [sel2] "v"(c.sel[2]), [sel3] "v"(c.sel[3]), [sel4] "v"(c.sel[4]),
-                   [sel5] "v"(c.sel[5]), [a31] "v"(c.a31), [a63] "v"(c.a63));
-    const unsigned lo = PCT_SORT_DUO_RESULT_A, hi = PCT_SORT_DUO_RESULT_B;
-    ea = lo;
-    eb = hi;
-}
-
 // Staging capacity: cells are sized for 0.35 (k + 1) points, a surface's 27-cell stencil then holds 12 - 14 cells' worth --
 // 400 - 470 candidates at k = 64 .. 80: 512 slots sent 8 % of the items (k = 64) to 30 % (k = 80) to the exact sweep,
 // 768 slots (4 waves per SIMD with the 16-bit survivor list) send a handful.

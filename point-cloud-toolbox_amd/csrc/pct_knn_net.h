@@ -124,6 +124,39 @@ __device__ __forceinline__ void fast_sort_sets(FastK<NSETS * R>& t, const SortLa
 }
 
 // ---------------------------------------------------------------------------
+// The same network as hand-scheduled assembly blocks (tools/gen_sort_asm.py): two independent lists of 64, one register
+// each (k_knn_pair), and one list of 128 in two registers, element = lane + 64 * register (k_knn_duo).  The blocks
+// assume that the caller's VALU code wrote ea / eb immediately before them (their leading s_nop 1).  They live here, not
+// beside their kernels, so that the self-test (pct_knn.hip: k_selftest_sort) runs the very code the sweeps run.
+// ---------------------------------------------------------------------------
+#ifndef PCT_SORT_INC
+#define PCT_SORT_INC "pct_sort_pair.inc"
+#endif
+#include PCT_SORT_INC
+#include "pct_sort_duo.inc"
+
+__device__ __forceinline__ void sort_pair_asm(unsigned& ea, unsigned& eb, const SortLanes& c) {
+    unsigned ta, tb;
+    asm volatile(PCT_SORT_PAIR_ASM
+                 : [ea] "+v"(ea), [eb] "+v"(eb), [ta] "=&v"(ta), [tb] "=&v"(tb)
+                 : [sel0] "v"(c.sel[0]), [sel1] "v"(c.sel[1]), [sel2] "v"(c.sel[2]), [sel3] "v"(c.sel[3]), [sel4] "v"(c.sel[4]),
+                   [sel5] "v"(c.sel[5]), [a31] "v"(c.a31), [a63] "v"(c.a63));
+    ea = PCT_SORT_PAIR_RESULT_A;
+    eb = PCT_SORT_PAIR_RESULT_B;
+}
+
+__device__ __forceinline__ void sort_duo_asm(unsigned& ea, unsigned& eb, const SortLanes& c) {
+    unsigned ta, tb;
+    asm volatile(PCT_SORT_DUO_ASM
+                 : [ea] "+v"(ea), [eb] "+v"(eb), [ta] "=&v"(ta), [tb] "=&v"(tb)
+                 : [sel0] "v"(c.sel[0]), [sel1] "v"(c.sel[1]), [sel2] "v"(c.sel[2]), [sel3] "v"(c.sel[3]), [sel4] "v"(c.sel[4]),
+                   [sel5] "v"(c.sel[5]), [a31] "v"(c.a31), [a63] "v"(c.a63));
+    const unsigned lo = PCT_SORT_DUO_RESULT_A, hi = PCT_SORT_DUO_RESULT_B;
+    ea = lo;
+    eb = hi;
+}
+
+// ---------------------------------------------------------------------------
 // Equal keys inside the sorted list: the quantised key cannot order those elements, the exact values can.
 // On the reference's own generator output (theta x phi lattices, utils.py:883-914) every point has symmetric partners
 // whose squared distances differ by float32 rounding noise only -- most queries meet at least one pair of equal keys

@@ -25,21 +25,6 @@ namespace {
 // Staged batches are used in pairs (128 slots); the body is compiled per number of pairs in use, without guards
 // (1 | 2 | 3 | 4): slots of a staged pair beyond the stencil's population sit at +inf.
 // ---------------------------------------------------------------------------
-#ifndef PCT_SORT_INC
-#define PCT_SORT_INC "pct_sort_pair.inc"
-#endif
-#include PCT_SORT_INC
-
-__device__ __forceinline__ void sort_pair_asm(unsigned& ea, unsigned& eb, const SortLanes& c) {
-    unsigned ta, tb;
-    asm volatile(PCT_SORT_PAIR_ASM
-                 : [ea] "+v"(ea), [eb] "+v"(eb), [ta] "=&v"(ta), [tb] "=&v"(tb)
-                 : [sel0] "v"(c.sel[0]), [sel1] "v"(c.sel[1]), [sel2] "v"(c.sel[2]), [sel3] "v"(c.sel[3]), [sel4] "v"(c.sel[4]),
-                   [sel5] "v"(c.sel[5]), [a31] "v"(c.a31), [a63] "v"(c.a63));
-    ea = PCT_SORT_PAIR_RESULT_A;
-    eb = PCT_SORT_PAIR_RESULT_B;
-}
-
 constexpr int kPairCap = kStageCap;
 static_assert((kPairCap & (kPairCap - 1)) == 0 && kPairCap % 128 == 0 && kPairCap <= 512, "staging capacity of k_knn_pair");
 static_assert(PCT_TREE_CAP % 128 == 0 && PCT_TREE_CAP <= 1024, "staging capacity of k_knn_pair on the hierarchical cell list");

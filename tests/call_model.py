@@ -374,6 +374,9 @@ EXCLUDED = {
     "pct_matrix_norms_f64": "host pass over an array: no handle, no state",
     "pct_format_float": "pure host function",
     "pct_selftest": "hardware self-test: reads and writes no state of the path",
+    "pct_selftest_sort": "sorter self-test on caller arrays, device memory of its own: no state of the path (tests/test_gpu_sort_net.py)",
+    "pct_selftest_sort_exact": "sorter self-test on caller arrays, device memory of its own: no state of the path (tests/test_gpu_sort_net.py)",
+    "pct_selftest_order_keys": "sorter self-test on caller arrays, device memory of its own: no state of the path (tests/test_gpu_sort_net.py)",
     "pct_device_count": "takes no handle: no state to model",
     "pct_create": "lifetime: the driver creates the handle under test and every fresh reference handle with it",
     "pct_destroy": "lifetime: every fresh reference handle is closed with it before the next is opened",
