@@ -644,6 +644,35 @@ int pct_selftest_sort_exact(pct_ctx* ctx, int32_t regs, int32_t mode, const doub
                             const int32_t* batch_pos, const int32_t* pub, int64_t n_pub, int64_t n_lists, double* out_d2, int32_t* out_pos);
 int pct_selftest_order_keys(pct_ctx* ctx, int32_t regs, int32_t slot_bits, const uint32_t* elems, const double* d2, const int32_t* pub,
                             int64_t n_lists, uint32_t* out, int32_t* done);
+/* Self-tests of the kernels that plan the passes of the chained sweep (PCT_KNN_GRID_LEVELS; tests/test_gpu_levels_exact.py).
+ * As above: the very kernels, launched as the chain launches them, on host arrays of the caller; device memory of their
+ * own for the length of the call, nothing resident on the handle is read, written or dropped.
+ *
+ * pct_selftest_levels_classify: the wanted edge of the rows a pass left unanswered.  Row i of n_rows is the query with
+ * public index pub[i] (distinct, in [0, n_pub)); row_done[i] != 0: answered, nothing of it is touched; redo_m[i] =
+ * why << 29 | stencil population.  log_edge: log2 of the pass's cell edge; target: the stencil population of a
+ * well-sized pass.  want (n_pub) and bracket (n_pub pairs: largest log2 edge known too small, smallest known too
+ * large) are indexed by public index, read and rewritten in place.
+ *
+ * pct_selftest_levels_bands: the histogram of the wanted edges want[begin, end) of n points xyz (n, 3) about log_edge0,
+ * the first pass's log2 edge -- hist (160 quarter octaves) and *exact, the queries only the exact sweep answers -- and
+ * the bounding box (min xyz, max xyz) and *count of the points with lo <= want < hi.  window = -1: lo and hi as given;
+ * 0 .. 156: the bounds the chain gives the pass whose one-octave window starts at that bin.  bounds (2) answers the lo
+ * and hi used.  No member: *count = 0 and the box (+inf x 3, -inf x 3).
+ *
+ * pct_selftest_levels_merge: the answered rows of a pass into the public-space table.  pub (n_pos): public index of
+ * every position of the cell order; row r of n_rows is the query at position owned_pos[r]; nbr_pos / nbr_dist
+ * (n_rows, pitch) the pass's table (positions, negative: no neighbour), nbr_cnt (n_rows, may be null: every row holds
+ * k).  A row with row_done != 0 goes to row pub - q_begin of pub_pos / pub_dist (n_out, pitch; read and rewritten in
+ * place, as are pub_cnt (n_out, may be null) and want (n_want, by public index)): its k entries as public indices, its
+ * count, and its wanted edge set to NaN. */
+int pct_selftest_levels_classify(pct_ctx* ctx, const int32_t* row_done, const uint32_t* redo_m, const int32_t* pub, int64_t n_rows,
+                                 int64_t n_pub, float log_edge, float target, float* want, float* bracket);
+int pct_selftest_levels_bands(pct_ctx* ctx, const float* want, const float* xyz, int64_t n, int64_t begin, int64_t end, float log_edge0,
+                              int32_t window, float lo, float hi, uint32_t* hist, uint32_t* exact, float* bounds, float* box, uint32_t* count);
+int pct_selftest_levels_merge(pct_ctx* ctx, const int32_t* pub, int64_t n_pos, const int32_t* owned_pos, int32_t q_begin, const int32_t* nbr_pos,
+                              const float* nbr_dist, const int32_t* nbr_cnt, const int32_t* row_done, int64_t n_rows, int32_t k, int32_t pitch,
+                              int64_t n_out, int32_t* pub_pos, float* pub_dist, int32_t* pub_cnt, float* want, int64_t n_want);
 
 #ifdef __cplusplus
 }

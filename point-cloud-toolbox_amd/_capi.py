@@ -147,6 +147,11 @@ SIGNATURES = {
     "pct_selftest_sort": (C.c_int, [_p, C.c_int32, _u32p, C.c_int64, _u32p]),
     "pct_selftest_sort_exact": (C.c_int, [_p, C.c_int32, C.c_int32, _f64p, _i32p, _f64p, _i32p, _i32p, C.c_int64, C.c_int64, _f64p, _i32p]),
     "pct_selftest_order_keys": (C.c_int, [_p, C.c_int32, C.c_int32, _u32p, _f64p, _i32p, C.c_int64, _u32p, _i32p]),
+    "pct_selftest_levels_classify": (C.c_int, [_p, _i32p, _u32p, _i32p, C.c_int64, C.c_int64, C.c_float, C.c_float, _f32p, _f32p]),
+    "pct_selftest_levels_bands": (C.c_int, [_p, _f32p, _f32p, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_int32, C.c_float, C.c_float,
+                                            _u32p, _u32p, _f32p, _f32p, _u32p]),
+    "pct_selftest_levels_merge": (C.c_int, [_p, _i32p, C.c_int64, _i32p, C.c_int32, _i32p, _f32p, _i32p, _i32p, C.c_int64, C.c_int32, C.c_int32,
+                                            C.c_int64, _i32p, _f32p, _i32p, _f32p, C.c_int64]),
     # include/pct_hip_surface.h
     "pct_point_triangles": (C.c_int, [_p, C.c_int32]),
     "pct_get_point_fans": (C.c_int, [_p, C.c_int64, C.c_int64, _i64p, _i32p]),
@@ -955,6 +960,55 @@ class Handle:
         self._check(self._lib.pct_selftest_order_keys(self._h, regs, slot_bits, _ptr(e, _u32p), _ptr(d2, _f64p), _ptr(pub, _i32p),
                                                       len(e), _ptr(out, _u32p), _ptr(done, _i32p)))
         return out, done != 0
+
+    # -- the planning kernels of the chained sweep on caller-supplied arrays (tests/test_gpu_levels_exact.py) ----------
+    def selftest_levels_classify(self, row_done, redo_m, pub, log_edge, target, want, bracket):
+        """k_classify over rows (row_done, redo_m = why << 29 | pop, public index pub); want (n_pub) and bracket
+        (n_pub, 2) by public index.  Returns the rewritten (want, bracket); the arguments are left alone."""
+        done = np.ascontiguousarray(row_done, dtype=np.int32)
+        redo = np.ascontiguousarray(redo_m, dtype=np.uint32)
+        pub = np.ascontiguousarray(pub, dtype=np.int32)
+        want = np.array(want, dtype=np.float32, order="C")
+        bracket = np.array(bracket, dtype=np.float32, order="C")
+        assert done.shape == redo.shape == pub.shape == (len(pub),) and bracket.shape == (len(want), 2)
+        self._check(self._lib.pct_selftest_levels_classify(self._h, _ptr(done, _i32p), _ptr(redo, _u32p), _ptr(pub, _i32p), len(pub), len(want),
+                                                           float(log_edge), float(target), _ptr(want, _f32p), _ptr(bracket, _f32p)))
+        return want, bracket
+
+    def selftest_levels_bands(self, want, xyz, begin, end, log_edge0, window=-1, lo=0.0, hi=0.0):
+        """k_band_hist and k_band_box over want[begin:end], xyz (n, 3).  window >= 0: the chain's bounds of the window of
+        bins that starts there, else [lo, hi).  Returns (hist (160), exact, (lo, hi) used, box (6), count)."""
+        want = np.ascontiguousarray(want, dtype=np.float32)
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32)
+        assert xyz.shape == (len(want), 3)
+        hist, exact, count = np.empty(160, np.uint32), C.c_uint32(0), C.c_uint32(0)
+        bounds, box = np.empty(2, np.float32), np.empty(6, np.float32)
+        self._check(self._lib.pct_selftest_levels_bands(self._h, _ptr(want, _f32p), _ptr(xyz, _f32p), len(want), int(begin), int(end),
+                                                        np.float32(log_edge0).item(), int(window), np.float32(lo).item(), np.float32(hi).item(),
+                                                        _ptr(hist, _u32p), C.byref(exact), _ptr(bounds, _f32p), _ptr(box, _f32p), C.byref(count)))
+        return hist, exact.value, bounds, box, count.value
+
+    def selftest_levels_merge(self, pub, owned_pos, q_begin, nbr_pos, nbr_dist, nbr_cnt, row_done, k, pub_pos, pub_dist, pub_cnt, want):
+        """k_merge_rows: the done rows of the pass table (nbr_pos, nbr_dist (n_rows, pitch), nbr_cnt or None) into copies of
+        the public table (pub_pos, pub_dist (n_out, pitch), pub_cnt or None) and of want.  Returns those copies."""
+        pub = np.ascontiguousarray(pub, dtype=np.int32)
+        owned = np.ascontiguousarray(owned_pos, dtype=np.int32)
+        npos = np.ascontiguousarray(nbr_pos, dtype=np.int32)
+        ndist = np.ascontiguousarray(nbr_dist, dtype=np.float32)
+        ncnt = None if nbr_cnt is None else np.ascontiguousarray(nbr_cnt, dtype=np.int32)
+        done = np.ascontiguousarray(row_done, dtype=np.int32)
+        ppos = np.array(pub_pos, dtype=np.int32, order="C")
+        pdist = np.array(pub_dist, dtype=np.float32, order="C")
+        pcnt = None if pub_cnt is None else np.array(pub_cnt, dtype=np.int32, order="C")
+        want = np.array(want, dtype=np.float32, order="C")
+        pitch = npos.shape[1]
+        assert npos.shape == ndist.shape == (len(owned), pitch) and ppos.shape == pdist.shape == (len(ppos), pitch) and done.shape == owned.shape
+        assert (ncnt is None or ncnt.shape == owned.shape) and (pcnt is None or pcnt.shape == (len(ppos),))
+        self._check(self._lib.pct_selftest_levels_merge(self._h, _ptr(pub, _i32p), len(pub), _ptr(owned, _i32p), int(q_begin), _ptr(npos, _i32p),
+                                                        _ptr(ndist, _f32p), None if ncnt is None else _ptr(ncnt, _i32p), _ptr(done, _i32p),
+                                                        len(owned), int(k), pitch, len(ppos), _ptr(ppos, _i32p), _ptr(pdist, _f32p),
+                                                        None if pcnt is None else _ptr(pcnt, _i32p), _ptr(want, _f32p), len(want)))
+        return ppos, pdist, pcnt, want
 
     def synchronize(self):
         self._check(self._lib.pct_synchronize(self._h))

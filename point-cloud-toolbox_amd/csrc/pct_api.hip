@@ -1798,4 +1798,136 @@ int pct_selftest_order_keys(pct_ctx* ctx, int32_t regs, int32_t slot_bits, const
     return PCT_OK;
 }
 
+// ---- self-tests of the chained sweep's planning kernels (pct_levels.hip): as above, host arrays in and out ----------------------
+int pct_selftest_levels_classify(pct_ctx* ctx, const int32_t* row_done, const uint32_t* redo_m, const int32_t* pub, int64_t n_rows,
+                                 int64_t n_pub, float log_edge, float target, float* want, float* bracket) {
+    PCT_TRY(begin_call(ctx));
+    if (!row_done || !redo_m || !pub || !want || !bracket) return pct_fail(ctx, PCT_ERR_INVALID, "null array");
+    if (n_rows < 1 || n_rows > ((int64_t)1 << 22) || n_pub < n_rows || n_pub > ((int64_t)1 << 24))
+        return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_levels_classify: n_rows = %lld (1 .. 2^22), n_pub = %lld (n_rows .. 2^24)", (long long)n_rows, (long long)n_pub);
+    // the kernel writes want[pub] and bracket[pub] of every row: each public index inside the arrays, and once
+    std::vector<char> seen((size_t)n_pub, 0);
+    for (int64_t i = 0; i < n_rows; ++i) {
+        if (pub[i] < 0 || pub[i] >= n_pub || seen[(size_t)pub[i]]) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_levels_classify: public index %d outside [0, n_pub) or twice", (int)pub[i]);
+        seen[(size_t)pub[i]] = 1;
+    }
+    // row i is the query at position n_rows - 1 - i of the cell order: neither lookup is the identity
+    std::vector<float4> rec((size_t)n_rows);
+    std::vector<int> owned((size_t)n_rows);
+    for (int64_t i = 0; i < n_rows; ++i) {
+        float w;
+        memcpy(&w, &pub[i], 4);
+        owned[(size_t)i] = (int)(n_rows - 1 - i);
+        rec[(size_t)(n_rows - 1 - i)] = make_float4(0.f, 0.f, 0.f, w);
+    }
+    DevScratch mem;
+    int *d_done, *d_redo, *d_owned;
+    float4* d_rec;
+    float *d_want, *d_br;
+    PCT_HIP(ctx, mem.take(&d_done, (size_t)n_rows));
+    PCT_HIP(ctx, mem.take(&d_redo, (size_t)n_rows));
+    PCT_HIP(ctx, mem.take(&d_owned, (size_t)n_rows));
+    PCT_HIP(ctx, mem.take(&d_rec, (size_t)n_rows));
+    PCT_HIP(ctx, mem.take(&d_want, (size_t)n_pub));
+    PCT_HIP(ctx, mem.take(&d_br, (size_t)n_pub * 2));
+    PCT_HIP(ctx, hipMemcpyAsync(d_done, row_done, (size_t)n_rows * 4, hipMemcpyHostToDevice, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(d_redo, redo_m, (size_t)n_rows * 4, hipMemcpyHostToDevice, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(d_owned, owned.data(), (size_t)n_rows * 4, hipMemcpyHostToDevice, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(d_rec, rec.data(), (size_t)n_rows * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(d_want, want, (size_t)n_pub * 4, hipMemcpyHostToDevice, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(d_br, bracket, (size_t)n_pub * 8, hipMemcpyHostToDevice, ctx->stream));
+    PCT_TRY(pct_launch_selftest_levels_classify(ctx, d_done, d_redo, n_rows, d_rec, d_owned, log_edge, target, d_want, d_br));
+    PCT_HIP(ctx, hipMemcpyAsync(want, d_want, (size_t)n_pub * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(bracket, d_br, (size_t)n_pub * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (rec, owned and the scratch outlive every copy: waited for here)
+    return PCT_OK;
+}
+
+int pct_selftest_levels_bands(pct_ctx* ctx, const float* want, const float* xyz, int64_t n, int64_t begin, int64_t end, float log_edge0,
+                              int32_t window, float lo, float hi, uint32_t* hist, uint32_t* exact, float* bounds, float* box, uint32_t* count) {
+    PCT_TRY(begin_call(ctx));
+    if (!want || !xyz || !hist || !exact || !bounds || !box || !count) return pct_fail(ctx, PCT_ERR_INVALID, "null array");
+    if (n < 1 || n > ((int64_t)1 << 24) || begin < 0 || begin > end || end > n)
+        return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_levels_bands: n = %lld (1 .. 2^24), [begin, end) = [%lld, %lld) inside it", (long long)n, (long long)begin, (long long)end);
+    if (window < -1 || window > 156) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_levels_bands: window = %d (-1: lo and hi as given; 0 .. 156)", (int)window);
+    constexpr int kStatWords = 162, kBoxWords = 7;
+    DevScratch mem;
+    float *d_want, *d_xyz;
+    unsigned* d_stats;
+    int* d_box;
+    PCT_HIP(ctx, mem.take(&d_want, (size_t)n));
+    PCT_HIP(ctx, mem.take(&d_xyz, (size_t)n * 3));
+    PCT_HIP(ctx, mem.take(&d_stats, (size_t)kStatWords));
+    PCT_HIP(ctx, mem.take(&d_box, (size_t)kBoxWords));
+    PCT_HIP(ctx, hipMemcpyAsync(d_want, want, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(d_xyz, xyz, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream));
+    PCT_TRY(pct_launch_selftest_levels_bands(ctx, d_want, d_xyz, begin, end, log_edge0, window, lo, hi, d_stats, bounds, d_box));
+    unsigned h_stats[kStatWords];
+    int h_box[kBoxWords];
+    PCT_HIP(ctx, hipMemcpyAsync(h_stats, d_stats, sizeof(h_stats), hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(h_box, d_box, sizeof(h_box), hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(hist, h_stats, 160 * sizeof(uint32_t));
+    *exact = h_stats[160];
+    for (int a = 0; a < 6; ++a) box[a] = pct_levels_box_float(h_box[a]);
+    *count = (uint32_t)h_box[6];
+    return PCT_OK;
+}
+
+int pct_selftest_levels_merge(pct_ctx* ctx, const int32_t* pub, int64_t n_pos, const int32_t* owned_pos, int32_t q_begin, const int32_t* nbr_pos,
+                              const float* nbr_dist, const int32_t* nbr_cnt, const int32_t* row_done, int64_t n_rows, int32_t k, int32_t pitch,
+                              int64_t n_out, int32_t* pub_pos, float* pub_dist, int32_t* pub_cnt, float* want, int64_t n_want) {
+    PCT_TRY(begin_call(ctx));
+    if (!pub || !owned_pos || !nbr_pos || !nbr_dist || !row_done || !pub_pos || !pub_dist || !want) return pct_fail(ctx, PCT_ERR_INVALID, "null array");
+    if (n_pos < 1 || n_pos > ((int64_t)1 << 24) || n_rows < 1 || n_rows > ((int64_t)1 << 20) || k < 1 || pitch < k || pitch > 512 || n_out < 1 ||
+        n_out > ((int64_t)1 << 22) || n_want < 1 || n_want > ((int64_t)1 << 24) || q_begin < 0)
+        return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_levels_merge: n_pos = %lld, n_rows = %lld, k = %d, pitch = %d, n_out = %lld, n_want = %lld, q_begin = %d",
+                        (long long)n_pos, (long long)n_rows, (int)k, (int)pitch, (long long)n_out, (long long)n_want, (int)q_begin);
+    // every address the kernel forms from the caller's numbers lies inside the caller's arrays
+    for (int64_t r = 0; r < n_rows; ++r) {
+        if (owned_pos[r] < 0 || owned_pos[r] >= n_pos) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_levels_merge: owned position %d outside [0, n_pos)", (int)owned_pos[r]);
+        const int64_t p = pub[owned_pos[r]];
+        if (p < q_begin || p - q_begin >= n_out || p >= n_want) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_levels_merge: public index %lld outside the output rows or the wanted edges", (long long)p);
+        for (int j = 0; j < k; ++j)
+            if (nbr_pos[r * pitch + j] >= n_pos) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_levels_merge: neighbour position %d outside [0, n_pos)", (int)nbr_pos[r * pitch + j]);
+    }
+    const std::vector<float4> rec = pub_records(pub, n_pos);
+    const size_t in_cells = (size_t)n_rows * pitch, out_cells = (size_t)n_out * pitch;
+    DevScratch mem;
+    float4* d_rec;
+    int *d_owned, *d_npos, *d_ncnt = nullptr, *d_done, *d_ppos, *d_pcnt = nullptr;
+    float *d_ndist, *d_pdist, *d_want;
+    PCT_HIP(ctx, mem.take(&d_rec, rec.size()));
+    PCT_HIP(ctx, mem.take(&d_owned, (size_t)n_rows));
+    PCT_HIP(ctx, mem.take(&d_done, (size_t)n_rows));
+    PCT_HIP(ctx, mem.take(&d_npos, in_cells));
+    PCT_HIP(ctx, mem.take(&d_ndist, in_cells));
+    PCT_HIP(ctx, mem.take(&d_ppos, out_cells));
+    PCT_HIP(ctx, mem.take(&d_pdist, out_cells));
+    PCT_HIP(ctx, mem.take(&d_want, (size_t)n_want));
+    PCT_HIP(ctx, hipMemcpyAsync(d_rec, rec.data(), rec.size() * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(d_owned, owned_pos, (size_t)n_rows * 4, hipMemcpyHostToDevice, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(d_done, row_done, (size_t)n_rows * 4, hipMemcpyHostToDevice, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(d_npos, nbr_pos, in_cells * 4, hipMemcpyHostToDevice, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(d_ndist, nbr_dist, in_cells * 4, hipMemcpyHostToDevice, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(d_ppos, pub_pos, out_cells * 4, hipMemcpyHostToDevice, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(d_pdist, pub_dist, out_cells * 4, hipMemcpyHostToDevice, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(d_want, want, (size_t)n_want * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (nbr_cnt) {
+        PCT_HIP(ctx, mem.take(&d_ncnt, (size_t)n_rows));
+        PCT_HIP(ctx, hipMemcpyAsync(d_ncnt, nbr_cnt, (size_t)n_rows * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (pub_cnt) {
+        PCT_HIP(ctx, mem.take(&d_pcnt, (size_t)n_out));
+        PCT_HIP(ctx, hipMemcpyAsync(d_pcnt, pub_cnt, (size_t)n_out * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    PCT_TRY(pct_launch_selftest_levels_merge(ctx, d_rec, d_owned, q_begin, d_npos, d_ndist, d_ncnt, d_done, n_rows, k, pitch, d_ppos, d_pdist, d_pcnt, d_want));
+    PCT_HIP(ctx, hipMemcpyAsync(pub_pos, d_ppos, out_cells * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(pub_dist, d_pdist, out_cells * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (pub_cnt) PCT_HIP(ctx, hipMemcpyAsync(pub_cnt, d_pcnt, (size_t)n_out * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(want, d_want, (size_t)n_want * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PCT_OK;
+}
+
 }  // extern "C"

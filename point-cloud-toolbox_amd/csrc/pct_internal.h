@@ -542,6 +542,17 @@ int pct_launch_selftest_exact(pct_ctx* ctx, int regs, int mode, const double* d2
                               const float4* pts, int n_lists, double* out_d2, int* out_pos);
 int pct_launch_selftest_order(pct_ctx* ctx, int regs, int slot_bits, const unsigned* elems, const double* d2, const float4* pts, int n_lists,
                               unsigned* out, int* done);
+// the chained sweep's planning kernels on device arrays of the caller (pct_levels.hip), launched as pct_knn_levels launches
+// them.  bands: stats = 162 words (160 bins, exact, pad), window >= 0 takes [lo, hi) from the plan's window of bins that
+// starts there, used2 (host) answers the bounds the box kernel ran with, box7 = six ordered ints and the count
+int pct_launch_selftest_levels_classify(pct_ctx* ctx, const int* row_done, const int* redo_m, int64_t n_rows, const float4* sorted4,
+                                        const int* owned_pos, float log_edge, float target, float* want, float* bracket2);
+int pct_launch_selftest_levels_bands(pct_ctx* ctx, const float* want, const float* xyz, int64_t begin, int64_t end, float log_edge0,
+                                     int window, float lo, float hi, unsigned* stats, float used2[2], int* box7);
+float pct_levels_box_float(int ordered);             // an ordered int of box7 as the float the chain reads
+int pct_launch_selftest_levels_merge(pct_ctx* ctx, const float4* sorted4, const int* owned_pos, int q_begin, const int* nbr_pos,
+                                     const float* nbr_dist, const int* nbr_cnt, const int* row_done, int64_t n_rows, int k, int pitch,
+                                     int* pub_pos, float* pub_dist, int* pub_cnt, float* want);
 int pct_ensure_plain_records(pct_ctx* ctx);
 int pct_launch_fit_rows_f64(pct_ctx* ctx, const int32_t* d_idx, const int32_t* d_cnt, const int64_t* d_query, int64_t rows,
                             int32_t k, int32_t pitch, double* d_coefs, double* d_K, double* d_H);

@@ -12,6 +12,7 @@
 // - q_begin, entries = public indices -- the representation of the exhaustive sweep, so every consumer already
 // understands it).  What is left after the passes goes to the exact sweep.
 #include "pct_internal.h"
+#include "pct_levels_plan.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -19,13 +20,8 @@
 
 namespace {
 
-#ifndef PCT_LEVEL_STEP_MAX
-#define PCT_LEVEL_STEP_MAX 3.f
-#endif
-constexpr float kStepMax = PCT_LEVEL_STEP_MAX;   // largest jump (octaves of cell edge) taken on the population estimate alone
-constexpr float kWantExact = 1.0e30f;          // wanted-edge value of a query only the exact sweep can answer
-constexpr int kBins = 160;                      // histogram of wanted log2 edges, quarter octaves
-constexpr float kBinLo = -20.f;                 // relative to the first pass's log2 edge
+// (the rule -- constants, bins, windows, classify, next_pass, closing_edge -- is pct_levels_plan.h; here are the kernels
+// that evaluate it per query and the host loop that runs the passes)
 
 __device__ __forceinline__ int pub_of(const float4* __restrict__ sorted4, int pos) { return __float_as_int(sorted4[pos].w); }
 
@@ -69,26 +65,10 @@ __global__ __launch_bounds__(256) void k_classify(const int* __restrict__ row_do
         const int why = (int)(e >> 29);
         const int pub = pub_of(sorted4, owned_pos[i]);
         const float pop = (float)(e & 0x1FFFFFFFu);  // candidates the 27-cell stencil of the query's item held
-        float2 b = bracket[pub];
-        float w = kWantExact;
-        // a failure that tells nothing new (the pass edge lay outside the bracket already known) ends the search
-        const bool news = why == 1 ? log_edge > b.x : why == 2 ? log_edge < b.y : false;
-        if (why == 1) b.x = fmaxf(b.x, log_edge);          // these cells were too small for it
-        else if (why == 2) b.y = fminf(b.y, log_edge);     // ... too large
-        if (news) {
-            if (b.x > -INFINITY && b.y < INFINITY) {
-                // bisection (log scale); a pass serves a one-octave band, so a bracket much narrower than that cannot
-                // be resolved further (volumes: the workable window between "too few" and "overflow" is ~0.2 octaves)
-                w = b.y - b.x < 0.6f ? kWantExact : 0.5f * (b.x + b.y);
-            } else {
-                // population ~ edge^2 on a surface, ~ edge^3 in a volume: the square root over-shoots in a volume,
-                // the bracket then takes over
-                const float step = 0.5f * log2f(fmaxf(target / fmaxf(pop, 0.5f), 1e-6f));
-                w = why == 1 ? log_edge + fminf(fmaxf(step, 0.75f), kStepMax) : log_edge + fmaxf(fminf(step, -0.75f), -kStepMax);
-            }
-        }
-        bracket[pub] = b;
-        want[pub] = w;
+        const float2 b = bracket[pub];
+        const LevelWant c = classify(why, pop, log_edge, target, LevelBracket{b.x, b.y});
+        bracket[pub] = make_float2(c.bracket.x, c.bracket.y);
+        want[pub] = c.want;
     }
 }
 
@@ -106,18 +86,9 @@ __global__ __launch_bounds__(256) void k_band_hist(const float* __restrict__ wan
     __syncthreads();
     for (int64_t i = begin + (int64_t)blockIdx.x * 256 + threadIdx.x; i < end; i += (int64_t)gridDim.x * 256) {
         const float w = want[i];
-        if (w == w) {
-            if (w >= 0.5f * kWantExact) atomicAdd(&sh[kBins], 1u);
-            else {
-                // the bin whose float bounds -- the very expressions the host turns a window of bins into [lo, hi)
-                // with -- hold w: floor() of the scaled offset can land one bin off at a boundary, and a window
-                // that the histogram says holds 2313 queries then owned none (box [inf, -inf], a launch of no blocks)
-                int bin = (int)floorf((w - log_edge0 - kBinLo) * 4.f);
-                bin = bin < 0 ? 0 : bin >= kBins ? kBins - 1 : bin;
-                while (bin > 0 && w < log_edge0 + kBinLo + 0.25f * bin) --bin;
-                while (bin < kBins - 1 && w >= log_edge0 + kBinLo + 0.25f * (bin + 1)) ++bin;
-                atomicAdd(&sh[bin], 1u);
-            }
+        if (w == w) {                                   // bin_of(w, log_edge0), one atomic per class
+            if (wants_exact(w)) atomicAdd(&sh[kBins], 1u);
+            else atomicAdd(&sh[banded_bin(w, log_edge0)], 1u);
         }
     }
     __syncthreads();
@@ -140,7 +111,7 @@ __global__ __launch_bounds__(256) void k_band_box(const float* __restrict__ want
     unsigned cnt = 0;
     for (int64_t i = begin + (int64_t)blockIdx.x * 256 + threadIdx.x; i < end; i += (int64_t)gridDim.x * 256) {
         const float w = want[i];
-        if (w >= lo && w < hi) {
+        if (in_window(w, lo, hi)) {
             ++cnt;
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
@@ -184,6 +155,43 @@ float order_to_float(int i) {
 template <class T>
 void swap_buf(T& a, T& b) { T t = a; a = b; b = t; }
 
+// The launches of the rule's kernels with the grid sizes of the chain: pct_knn_levels and the self-test entries
+// (pct_launch_selftest_levels_*) both go through these, so the self-tests run what the chain runs.
+int launch_classify(pct_ctx* ctx, const int* row_done, const int* redo_m, int64_t n_rows, const float4* sorted4, const int* owned_pos,
+                    float log_edge, float target, float* want, float2* bracket) {
+    PCT_LAUNCH(k_classify, dim3(1024), dim3(256), 0, ctx->stream, row_done, redo_m, n_rows, sorted4, owned_pos, log_edge, target, want, bracket);
+    PCT_HIP(ctx, hipGetLastError());
+    return PCT_OK;
+}
+
+int launch_merge_rows(pct_ctx* ctx, const float4* sorted4, const int* owned_pos, int q_begin, const int* nbr_pos, const float* nbr_dist,
+                      const int* nbr_cnt, const int* row_done, int64_t n_rows, int k, int pitch, int* pub_pos, float* pub_dist, int* pub_cnt,
+                      float* want) {
+    const int64_t total = n_rows * k;
+    PCT_LAUNCH(k_merge_rows, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, sorted4, owned_pos, q_begin, nbr_pos, nbr_dist,
+                       nbr_cnt, row_done, n_rows, k, pitch, pub_pos, pub_dist, pub_cnt, want);
+    PCT_HIP(ctx, hipGetLastError());
+    return PCT_OK;
+}
+
+// d_st: cleared, then the histogram of want[begin, end)
+int launch_band_hist(pct_ctx* ctx, const float* want, int64_t begin, int64_t end, float log_edge0, BandStats* d_st) {
+    PCT_HIP(ctx, hipMemsetAsync(d_st, 0, sizeof(BandStats), ctx->stream));
+    PCT_LAUNCH(k_band_hist, dim3(512), dim3(256), 0, ctx->stream, want, begin, end, log_edge0, d_st);
+    PCT_HIP(ctx, hipGetLastError());
+    return PCT_OK;
+}
+
+// d_box (7 ints): the empty box in ordered ints and a count of 0, then box and count of the members of [lo, hi)
+constexpr int kBandBoxWords = 7;
+int launch_band_box(pct_ctx* ctx, const float* want, const float* xyz, int64_t begin, int64_t end, float lo, float hi, int* d_box) {
+    static const int init[kBandBoxWords] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN, INT32_MIN, 0};
+    PCT_HIP(ctx, hipMemcpyAsync(d_box, init, sizeof(init), hipMemcpyHostToDevice, ctx->stream));
+    PCT_LAUNCH(k_band_box, dim3(512), dim3(256), 0, ctx->stream, want, xyz, begin, end, lo, hi, d_box, (unsigned*)(d_box + 6));
+    PCT_HIP(ctx, hipGetLastError());
+    return PCT_OK;
+}
+
 }  // namespace
 
 int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps, const int* fuse_par, pct_call_clock* clock) {
@@ -193,8 +201,6 @@ int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps, const int* fuse_par, pct
     const int pitch = (k + 3) & ~3;
     const double factor = ctx->occupancy_factor > 0 ? ctx->occupancy_factor : pct_default_factor(k);
     const double target = factor * (k + 1);
-    constexpr int kMaxPasses = 14;
-    const int64_t enough = nq / 256 > 1024 ? nq / 256 : 1024;      // leftovers of this size go to the exact sweep
     const bool debug = pct_getenv("PCT_LEVELS_DEBUG") != nullptr;
 
     ctx->no_cull = true;            // the merged table and the public-space fit need every point packed
@@ -218,22 +224,17 @@ int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps, const int* fuse_par, pct
         PCT_TRY(pct_launch_knn_grid(ctx, k, eps, exact, exact ? 0 : 1, true, clock, &pass));      // (k_merge_rows below reads the distances)
         if (!exact) {
             // the stencil of a well-sized pass holds about 11 cells' worth of points on a surface
-            PCT_LAUNCH(k_classify, dim3(1024), dim3(256), 0, ctx->stream, (const int*)ctx->row_done.p, (const int*)ctx->redo_m.p,
-                               owned, (const float4*)ctx->sorted4.p, (const int*)ctx->owned_pos.p,
-                               (float)log2(ctx->grid.cell), (float)(11.0 * target),
-                               (float*)ctx->flag_buf.p, (float2*)ctx->dens_buf.p);
-            PCT_HIP(ctx, hipGetLastError());
+            PCT_TRY(launch_classify(ctx, (const int*)ctx->row_done.p, (const int*)ctx->redo_m.p, owned, (const float4*)ctx->sorted4.p,
+                                    (const int*)ctx->owned_pos.p, (float)log2(ctx->grid.cell), (float)(11.0 * target),
+                                    (float*)ctx->flag_buf.p, (float2*)ctx->dens_buf.p));
         }
         if (fuse_par) PCT_TRY(pct_launch_fit_pass(ctx, owned, *fuse_par));       // before the next pass reorders the cloud
         const double t2 = debug ? tick() : 0;
-        const int64_t total = owned * k;
-        PCT_LAUNCH(k_merge_rows, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream,
-                           (const float4*)ctx->sorted4.p, (const int*)ctx->owned_pos.p, (int)ctx->q_begin,
-                           (const int*)ctx->nbr_pos.p, (const float*)ctx->nbr_dist.p,
-                           eps > 0 ? (const int*)ctx->nbr_cnt.p : nullptr, (const int*)ctx->row_done.p, owned, k, pitch,
-                           (int*)ctx->pub_pos.p, (float*)ctx->pub_dist.p, eps > 0 ? (int*)ctx->pub_cnt.p : nullptr,
-                           (float*)ctx->flag_buf.p);
-        PCT_HIP(ctx, hipGetLastError());
+        PCT_TRY(launch_merge_rows(ctx, (const float4*)ctx->sorted4.p, (const int*)ctx->owned_pos.p, (int)ctx->q_begin,
+                                  (const int*)ctx->nbr_pos.p, (const float*)ctx->nbr_dist.p,
+                                  eps > 0 ? (const int*)ctx->nbr_cnt.p : nullptr, (const int*)ctx->row_done.p, owned, k, pitch,
+                                  (int*)ctx->pub_pos.p, (float*)ctx->pub_dist.p, eps > 0 ? (int*)ctx->pub_cnt.p : nullptr,
+                                  (float*)ctx->flag_buf.p));
         if (debug) {
             const double t3 = tick();
             fprintf(stderr, "[levels] pass %d: owned %lld exact %d | build %.3f ms (iters %d, %lld cells) sweep+classify %.3f merge %.3f\n", passes,
@@ -267,43 +268,29 @@ int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps, const int* fuse_par, pct
     BandStats st;
     int64_t pending = 0;
     for (;;) {
-        PCT_HIP(ctx, hipMemsetAsync(d_st, 0, sizeof(BandStats), ctx->stream));
-        PCT_LAUNCH(k_band_hist, dim3(512), dim3(256), 0, ctx->stream, (const float*)ctx->flag_buf.p, ctx->q_begin,
-                           ctx->q_end, log_edge0, d_st);
-        PCT_HIP(ctx, hipGetLastError());
+        PCT_TRY(launch_band_hist(ctx, (const float*)ctx->flag_buf.p, ctx->q_begin, ctx->q_end, log_edge0, d_st));
         PCT_HIP(ctx, hipMemcpyAsync(ctx->pin->band_stats, d_st, sizeof(BandStats), hipMemcpyDeviceToHost, ctx->stream));
         PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
         memcpy(&st, ctx->pin->band_stats, sizeof(BandStats));
-        int64_t banded = 0;
-        for (int b = 0; b < kBins; ++b) banded += st.hist[b];
-        pending = banded + st.exact;
-        // the one-octave window (4 bins) that holds the most queries
-        int best = 0;
-        int64_t best_cnt = -1;
-        for (int b = 0; b + 4 <= kBins; ++b) {
-            const int64_t c = (int64_t)st.hist[b] + st.hist[b + 1] + st.hist[b + 2] + st.hist[b + 3];
-            if (c > best_cnt) { best_cnt = c; best = b; }
-        }
+        // the one-octave window that holds the most queries, or the end of the chain (pct_levels_plan.h)
+        const NextPass next = next_pass(st.hist, st.exact, passes, nq, log_edge0);
+        pending = next.pending;
         if (debug)
             fprintf(stderr, "[levels] after pass %d (edge %.5g, %lld cells): pending %lld (exact-only %u), best octave at edge %.5g holds %lld\n",
                     passes - 1, ctx->grid.cell, (long long)ctx->grid.ncell, (long long)pending, st.exact,
-                    exp2(log_edge0 + kBinLo + 0.25 * (best + 2)), (long long)best_cnt);
-        if (banded <= enough || passes >= kMaxPasses || best_cnt <= enough / 8) break;
-        pass.lo = best == 0 ? -INFINITY : log_edge0 + kBinLo + 0.25f * best;
-        pass.hi = best + 4 >= kBins ? 0.4f * kWantExact : log_edge0 + kBinLo + 0.25f * (best + 4);
-        const int init[7] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN, INT32_MIN, 0};
-        PCT_HIP(ctx, hipMemcpyAsync(d_box, init, sizeof(init), hipMemcpyHostToDevice, ctx->stream));
-        PCT_LAUNCH(k_band_box, dim3(512), dim3(256), 0, ctx->stream, (const float*)ctx->flag_buf.p, ctx->xyz_view,
-                           ctx->q_begin, ctx->q_end, pass.lo, pass.hi, d_box, (unsigned*)(d_box + 6));
-        PCT_HIP(ctx, hipGetLastError());
-        PCT_HIP(ctx, hipMemcpyAsync(ctx->pin->band_box, d_box, sizeof(init), hipMemcpyDeviceToHost, ctx->stream));
+                    exp2(log_edge0 + kBinLo + 0.25 * (next.best + 2)), (long long)next.best_cnt);
+        if (next.stop) break;
+        pass.lo = next.lo;
+        pass.hi = next.hi;
+        PCT_TRY(launch_band_box(ctx, (const float*)ctx->flag_buf.p, ctx->xyz_view, ctx->q_begin, ctx->q_end, pass.lo, pass.hi, d_box));
+        PCT_HIP(ctx, hipMemcpyAsync(ctx->pin->band_box, d_box, kBandBoxWords * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
         PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
         const int* hb = ctx->pin->band_box;
         for (int a = 0; a < 6; ++a) band_box[a] = order_to_float(hb[a]);
         pass.box = band_box;
         pass.owned = (int64_t)(unsigned)hb[6];
         if (pass.owned <= 0) break;            // (cannot happen while histogram and window agree; never build a cell list for nobody)
-        pass.edge = exp2((double)log_edge0 + kBinLo + 0.25 * (best + 2));        // centre of the window
+        pass.edge = next.edge;                 // centre of the window
         PCT_TRY(run_pass(pass.owned, false));
     }
     if (pending > 0) {               // the exact sweep answers whatever is left, over the whole box
@@ -311,12 +298,7 @@ int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps, const int* fuse_par, pct
         pass.hi = INFINITY;
         pass.owned = pending;
         pass.box = nullptr;
-        // cells sized for the median wanted edge of the banded leftovers (the exact sweep widens ring by ring)
-        int64_t acc = 0, banded = 0;
-        for (int b = 0; b < kBins; ++b) banded += st.hist[b];
-        int med = kBins / 2;
-        for (int b = 0; b < kBins; ++b) { acc += st.hist[b]; if (acc * 2 >= banded) { med = b; break; } }
-        pass.edge = banded > 0 ? exp2((double)log_edge0 + kBinLo + 0.25 * (med + 0.5)) : exp2((double)log_edge0);
+        pass.edge = closing_edge(st.hist, log_edge0);
         PCT_TRY(run_pass(pending, true));
     }
     // the merged table takes the place of the pass table: public space, as after the exhaustive sweep
@@ -327,4 +309,34 @@ int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps, const int* fuse_par, pct
     ctx->knn_sorted_space = false;
     ctx->tm.levels = passes;
     return PCT_OK;
+}
+
+// ---- the rule's kernels on caller-supplied device arrays (pct_selftest_levels_*): nothing of the handle but its stream -------
+int pct_launch_selftest_levels_classify(pct_ctx* ctx, const int* row_done, const int* redo_m, int64_t n_rows, const float4* sorted4,
+                                        const int* owned_pos, float log_edge, float target, float* want, float* bracket2) {
+    return launch_classify(ctx, row_done, redo_m, n_rows, sorted4, owned_pos, log_edge, target, want, (float2*)bracket2);
+}
+
+// stats: kBins + 2 words (BandStats); window >= 0: [lo, hi) of the window of bins that starts there, as the chain's
+// host loop takes them from the plan; used2: the bounds the box kernel ran with; box7: six ordered ints and the count
+int pct_launch_selftest_levels_bands(pct_ctx* ctx, const float* want, const float* xyz, int64_t begin, int64_t end, float log_edge0,
+                                     int window, float lo, float hi, unsigned* stats, float used2[2], int* box7) {
+    static_assert(sizeof(BandStats) == (kBins + 2) * sizeof(unsigned), "BandStats is its words");
+    if (window >= 0) {
+        lo = window_lo(log_edge0, window);
+        hi = window_hi(log_edge0, window);
+    }
+    used2[0] = lo;
+    used2[1] = hi;
+    PCT_TRY(launch_band_hist(ctx, want, begin, end, log_edge0, (BandStats*)stats));
+    return launch_band_box(ctx, want, xyz, begin, end, lo, hi, box7);
+}
+
+float pct_levels_box_float(int ordered) { return order_to_float(ordered); }
+
+int pct_launch_selftest_levels_merge(pct_ctx* ctx, const float4* sorted4, const int* owned_pos, int q_begin, const int* nbr_pos,
+                                     const float* nbr_dist, const int* nbr_cnt, const int* row_done, int64_t n_rows, int k, int pitch,
+                                     int* pub_pos, float* pub_dist, int* pub_cnt, float* want) {
+    return launch_merge_rows(ctx, sorted4, owned_pos, q_begin, nbr_pos, nbr_dist, nbr_cnt, row_done, n_rows, k, pitch, pub_pos, pub_dist,
+                             pub_cnt, want);
 }

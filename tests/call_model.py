@@ -377,6 +377,9 @@ EXCLUDED = {
     "pct_selftest_sort": "sorter self-test on caller arrays, device memory of its own: no state of the path (tests/test_gpu_sort_net.py)",
     "pct_selftest_sort_exact": "sorter self-test on caller arrays, device memory of its own: no state of the path (tests/test_gpu_sort_net.py)",
     "pct_selftest_order_keys": "sorter self-test on caller arrays, device memory of its own: no state of the path (tests/test_gpu_sort_net.py)",
+    "pct_selftest_levels_classify": "planning-kernel self-test on caller arrays, device memory of its own: no state of the path (tests/test_gpu_levels_exact.py)",
+    "pct_selftest_levels_bands": "planning-kernel self-test on caller arrays, device memory of its own: no state of the path (tests/test_gpu_levels_exact.py)",
+    "pct_selftest_levels_merge": "planning-kernel self-test on caller arrays, device memory of its own: no state of the path (tests/test_gpu_levels_exact.py)",
     "pct_device_count": "takes no handle: no state to model",
     "pct_create": "lifetime: the driver creates the handle under test and every fresh reference handle with it",
     "pct_destroy": "lifetime: every fresh reference handle is closed with it before the next is opened",
