@@ -644,6 +644,22 @@ int pct_selftest_sort_exact(pct_ctx* ctx, int32_t regs, int32_t mode, const doub
                             const int32_t* batch_pos, const int32_t* pub, int64_t n_pub, int64_t n_lists, double* out_d2, int32_t* out_pos);
 int pct_selftest_order_keys(pct_ctx* ctx, int32_t regs, int32_t slot_bits, const uint32_t* elems, const double* d2, const int32_t* pub,
                             int64_t n_lists, uint32_t* out, int32_t* done);
+/* Self-test of the planned fast sweep alone (tests/test_gpu_select.py): which rows it stores as final, which it hands to the
+ * exact sweep and which of those it marks as trusted.  Unlike the self-tests above it works on the handle's cloud: it builds
+ * the cell list as pct_knn(k, eps, algo) would for the owned rows (algo: PCT_KNN_GRID only; k <= 127; needs a cloud of at
+ * most 2^24 points, PCT_ERR_INVALID otherwise, and on a handle that owns a slab), plans the sweep by the same rule under the
+ * same PCT_* switches, fills the kernel's argument as pct_knn does, launches the planned kernel once -- and stops: no exact
+ * sweep follows.  want_dist = 0: the plan of the fused call, which keeps no distances.
+ * Out, for the owned rows in public index order: idx (rows, k) public indices, -1 where the sweep stored none; dist
+ * (rows, k; may be null) the float32 distances, written only where the plan keeps them (info[9]); count (rows; may be
+ * null) the eps counts, meaningful for rows that are not flagged; flags (rows): bit 0 = the row is on the redo list,
+ * bit 1 = its entry carries the trusted mark; info (12): sweep_variant, redo_count, cell size, nx, ny, nz, origin x, y,
+ * z, distances kept, queries per work item, work items.
+ * PCT_ERR_INVALID where the redo list names a row twice or does not hold exactly redo_count entries; nothing is repaired.
+ * The table it leaves is unfinished: pct_selftest_sweep drops every result on the handle, as a new cloud does, and
+ * pct_get_neighbors after it answers PCT_ERR_NO_NEIGHBORS. */
+int pct_selftest_sweep(pct_ctx* ctx, int32_t k, double eps, int32_t algo, int32_t want_dist, int32_t* idx, float* dist, int32_t* count,
+                       uint8_t* flags, double* info);
 /* Self-tests of the kernels that plan the passes of the chained sweep (PCT_KNN_GRID_LEVELS; tests/test_gpu_levels_exact.py).
  * As above: the very kernels, launched as the chain launches them, on host arrays of the caller; device memory of their
  * own for the length of the call, nothing resident on the handle is read, written or dropped.

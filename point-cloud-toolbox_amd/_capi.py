@@ -147,6 +147,7 @@ SIGNATURES = {
     "pct_selftest_sort": (C.c_int, [_p, C.c_int32, _u32p, C.c_int64, _u32p]),
     "pct_selftest_sort_exact": (C.c_int, [_p, C.c_int32, C.c_int32, _f64p, _i32p, _f64p, _i32p, _i32p, C.c_int64, C.c_int64, _f64p, _i32p]),
     "pct_selftest_order_keys": (C.c_int, [_p, C.c_int32, C.c_int32, _u32p, _f64p, _i32p, C.c_int64, _u32p, _i32p]),
+    "pct_selftest_sweep": (C.c_int, [_p, C.c_int32, C.c_double, C.c_int32, C.c_int32, _i32p, _f32p, _i32p, _u8p, _f64p]),
     "pct_selftest_levels_classify": (C.c_int, [_p, _i32p, _u32p, _i32p, C.c_int64, C.c_int64, C.c_float, C.c_float, _f32p, _f32p]),
     "pct_selftest_levels_bands": (C.c_int, [_p, _f32p, _f32p, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_int32, C.c_float, C.c_float,
                                             _u32p, _u32p, _f32p, _f32p, _u32p]),
@@ -960,6 +961,25 @@ class Handle:
         self._check(self._lib.pct_selftest_order_keys(self._h, regs, slot_bits, _ptr(e, _u32p), _ptr(d2, _f64p), _ptr(pub, _i32p),
                                                       len(e), _ptr(out, _u32p), _ptr(done, _i32p)))
         return out, done != 0
+
+    # -- the planned fast sweep alone, on the handle's cloud (tests/test_gpu_select.py) --------------------------------
+    def selftest_sweep(self, k, eps=0.0, algo=KNN_GRID, want_dist=True):
+        """pct_knn(k, eps, algo) up to and including the one launch of the planned fast sweep; no exact sweep.  Returns a
+        dict for the owned rows in public order: idx (rows, k; -1: none), dist (rows, k) or None where the plan keeps no
+        distances, count (rows), redo / trusted (rows, bool), and sweep_variant, redo_count, cell_size, dims, origin,
+        items_q, items.  Drops every resident result."""
+        rows = self._rows
+        idx = np.empty((rows, int(k)), np.int32)
+        dist = np.full((rows, int(k)), np.nan, np.float32)
+        count = np.empty(rows, np.int32)
+        flags = np.empty(rows, np.uint8)
+        info = np.zeros(12, np.float64)
+        self._check(self._lib.pct_selftest_sweep(self._h, int(k), float(eps), int(algo), 1 if want_dist else 0, _ptr(idx, _i32p), _ptr(dist, _f32p),
+                                                 _ptr(count, _i32p), _ptr(flags, _u8p), _ptr(info, _f64p)))
+        self.k = int(k)                              # (as knn: what a getter would size its arrays by, were it not refused)
+        return {"idx": idx, "dist": dist if info[9] else None, "count": count, "redo": (flags & 1) != 0, "trusted": (flags & 2) != 0,
+                "sweep_variant": int(info[0]), "redo_count": int(info[1]), "cell_size": float(info[2]),
+                "dims": tuple(int(v) for v in info[3:6]), "origin": tuple(float(v) for v in info[6:9]), "items_q": int(info[10]), "items": int(info[11])}
 
     # -- the planning kernels of the chained sweep on caller-supplied arrays (tests/test_gpu_levels_exact.py) ----------
     def selftest_levels_classify(self, row_done, redo_m, pub, log_edge, target, want, bracket):

@@ -1798,6 +1798,93 @@ int pct_selftest_order_keys(pct_ctx* ctx, int32_t regs, int32_t slot_bits, const
     return PCT_OK;
 }
 
+// ---- self-test of the planned fast sweep (tests/test_gpu_select.py): pct_knn's cell list, plan and one launch, no exact sweep ----
+// Unlike the self-tests above this one works on the handle's cloud and in its buffers: the table it leaves is unfinished,
+// so every resident result is dropped, as by a new cloud.
+int pct_selftest_sweep(pct_ctx* ctx, int32_t k, double eps, int32_t algo, int32_t want_dist, int32_t* idx, float* dist, int32_t* count,
+                       uint8_t* flags, double* info) {
+    PCT_TRY(begin_row_call(ctx, "pct_selftest_sweep"));
+    if (!idx || !flags || !info) return pct_fail(ctx, PCT_ERR_INVALID, "null array");
+    if (ctx->n <= 0) return pct_fail(ctx, PCT_ERR_INVALID, "no cloud loaded");
+    if (algo != PCT_KNN_GRID) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sweep: PCT_KNN_GRID only, not algorithm %d", (int)algo);
+    if (k < 1 || k > 127) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sweep: k=%d outside [1,127], the fast sweeps' rows", (int)k);
+    if ((int64_t)k + 1 > ctx->n) return pct_fail(ctx, PCT_ERR_K_TOO_LARGE, "k+1=%d exceeds the cloud size %lld", k + 1, (long long)ctx->n);
+    if (ctx->n > ((int64_t)1 << 24)) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sweep: at most 2^24 points");
+    if (!(eps >= 0) || isinf(eps)) eps = 0;
+    const int64_t rows = ctx->q_end - ctx->q_begin;
+    if (rows <= 0) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sweep: no owned rows");
+    ctx->res.drop(PCT_UNFINISHED_TABLE);
+    ctx->k = k;
+    ctx->eps = eps;
+    pct_call_clock& clock = ctx->clock[0];
+    PCT_TRY(clock.open(ctx, false, true, PCT_CALL_SWEEP_HEAD));
+    PCT_HIP(ctx, clock.start(ctx->stream));
+    ctx->tm.levels = 0;
+    ctx->tm.sweep_variant = 0;
+    ctx->tm.algo = algo;
+    GridVerdict built;
+    PCT_TRY(pct_build_grid(ctx, k, eps, false, &built, &clock, nullptr));
+    if (built != GridVerdict::Built) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sweep: no cell list");
+    PCT_HIP(ctx, clock.boundary(PCT_ST_GRID_END, ctx->stream));
+    // the buffers the launcher reserves, reserved here at the same sizes and filled: a table of -1 (a row the sweep leaves
+    // alone, or marks in its first column only, exports as empty) and a list of kNoEntry (what the sweep did not write shows)
+    constexpr int kNoEntry = 0x7f7f7f7f;
+    const size_t pitch = (size_t)((k + 3) & ~3), list_len = (size_t)rows + 16;
+    PCT_TRY(pct_reserve(ctx, &ctx->nbr_pos, (size_t)rows * pitch * sizeof(int)));
+    PCT_TRY(pct_reserve(ctx, &ctx->nbr_dist, (size_t)rows * pitch * sizeof(float)));
+    PCT_TRY(pct_reserve(ctx, &ctx->nbr_cnt, (size_t)rows * sizeof(int)));
+    PCT_TRY(pct_reserve(ctx, &ctx->redo, list_len * sizeof(int)));
+    PCT_HIP(ctx, hipMemsetAsync(ctx->nbr_pos.p, 0xff, (size_t)rows * pitch * sizeof(int), ctx->stream));
+    PCT_HIP(ctx, hipMemsetAsync(ctx->nbr_dist.p, 0xff, (size_t)rows * pitch * sizeof(float), ctx->stream));
+    PCT_HIP(ctx, hipMemsetAsync(ctx->nbr_cnt.p, 0xff, (size_t)rows * sizeof(int), ctx->stream));
+    PCT_HIP(ctx, hipMemsetAsync(ctx->redo.p, 0x7f, list_len * sizeof(int), ctx->stream));
+    PCT_TRY(pct_launch_knn_grid(ctx, k, eps, false, 3, want_dist != 0, &clock, nullptr));
+    PCT_HIP(ctx, clock.boundary(PCT_ST_SWEEP_END, ctx->stream));
+    // the rows in public order, through the getter's own export
+    const size_t cells = (size_t)rows * k;
+    const bool dist_kept = ctx->dist_valid;
+    PCT_TRY(pct_ensure_row_of(ctx));
+    PCT_TRY(pct_reserve(ctx, &ctx->stage_a, cells * sizeof(int)));
+    if (dist && dist_kept) PCT_TRY(pct_reserve(ctx, &ctx->stage_b, cells * sizeof(float)));
+    if (count) PCT_TRY(pct_reserve(ctx, &ctx->stage_c, (size_t)rows * sizeof(int)));
+    PCT_TRY(pct_launch_export_neighbors(ctx, ctx->q_begin, ctx->q_end, (int*)ctx->stage_a.p, dist && dist_kept ? (float*)ctx->stage_b.p : nullptr,
+                                        count ? (int*)ctx->stage_c.p : nullptr));
+    std::vector<int> list(list_len), row_of((size_t)rows);
+    int redo_count = -1;
+    PCT_HIP(ctx, hipMemcpyAsync(idx, ctx->stage_a.p, cells * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (dist && dist_kept) PCT_HIP(ctx, hipMemcpyAsync(dist, ctx->stage_b.p, cells * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (count) PCT_HIP(ctx, hipMemcpyAsync(count, ctx->stage_c.p, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(list.data(), ctx->redo.p, list_len * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(row_of.data(), ctx->row_of.p, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipMemcpyAsync(&redo_count, &pct_dev(ctx)->sweep.redo_count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < cells; ++i)
+        if (idx[i] >= ctx->n) idx[i] = -1;                 // (the export's "no neighbour" is n)
+    // the redo list as it is: its entries are the leading ones, as many as the counter says, each row once
+    size_t written = 0;
+    for (size_t i = 0; i < list_len; ++i) written += list[i] != kNoEntry;
+    if (redo_count < 0 || (int64_t)redo_count > rows || written != (size_t)redo_count)
+        return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sweep: the redo list holds %zu entries, redo_count says %d", written, redo_count);
+    const unsigned trusted_bit = pct_redo_trusted_bit();
+    std::vector<uint8_t> by_row((size_t)rows, 0);
+    for (int i = 0; i < redo_count; ++i) {
+        if (list[(size_t)i] == kNoEntry) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sweep: entry %d of %d of the redo list was not written", i, redo_count);
+        const unsigned e = (unsigned)list[(size_t)i], row = e & ~trusted_bit;
+        if ((int64_t)row >= rows) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sweep: redo entry %d names row %u of %lld", i, row, (long long)rows);
+        if (by_row[row]) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sweep: row %u is on the redo list twice", row);
+        by_row[row] = (uint8_t)(1 | ((e & trusted_bit) ? 2 : 0));
+    }
+    for (int64_t i = 0; i < rows; ++i) {
+        if (row_of[(size_t)i] < 0 || row_of[(size_t)i] >= rows) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sweep: no table row for public index %lld", (long long)(ctx->q_begin + i));
+        flags[i] = by_row[(size_t)row_of[(size_t)i]];
+    }
+    const pct_grid& g = ctx->grid;
+    const double words[12] = {(double)ctx->tm.sweep_variant, (double)redo_count, g.cell, (double)g.nx, (double)g.ny, (double)g.nz, g.ox, g.oy, g.oz,
+                              dist_kept ? 1.0 : 0.0, (double)ctx->items_q, (double)ctx->n_items};
+    memcpy(info, words, sizeof(words));
+    return PCT_OK;
+}
+
 // ---- self-tests of the chained sweep's planning kernels (pct_levels.hip): as above, host arrays in and out ----------------------
 int pct_selftest_levels_classify(pct_ctx* ctx, const int32_t* row_done, const uint32_t* redo_m, const int32_t* pub, int64_t n_rows,
                                  int64_t n_pub, float log_edge, float target, float* want, float* bracket) {

@@ -506,6 +506,7 @@ int pct_build_grid(pct_ctx* ctx, int32_t k, double eps, bool may_give_up, GridVe
 // clock: the call's -- the end of the fast sweep is a boundary of its sweep stage; pass (null: a plain sweep): as above
 int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, int phase, bool want_dist, pct_call_clock* clock, const LevelPass* pass);
 int pct_launch_knn_brute(pct_ctx* ctx, int32_t k, double eps);
+unsigned pct_redo_trusted_bit();         // kRedoTrusted (pct_knn_sweep.h), for the host code that reads a redo list (pct_selftest_sweep)
 // census of the work items of the cell list in place: out4 = {queries, queries whose stencil overflows the staging
 // area, queries whose stencil holds fewer than 2.5 (k+1) points (too few to vouch for k+1 within one cell edge), sum over the other queries of the non-empty cells in their
 // 27-cell stencil} -- what decides between the plain and the density-adaptive sweep before anything is swept

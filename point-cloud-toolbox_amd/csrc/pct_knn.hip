@@ -336,8 +336,12 @@ int launch_sweep(pct_ctx* ctx, const SweepPlan& p, const KnnArgs& a, int* redo, 
 }  // namespace
 
 // phase 0: fast sweep + exact sweep of what it flagged (or, exact_only, the exact sweep of every query);
-// phase 1: fast sweep only, the flagged rows stay in ctx->redo (level passes); phase 2: exact sweep of ctx->redo
+// phase 1: fast sweep only, the flagged rows stay in ctx->redo (level passes); phase 2: exact sweep of ctx->redo;
+// phase 3 (pct_selftest_sweep): phase 0 -- its plan, its argument, its one launch -- without the exact sweep: the flagged
+// rows stay in ctx->redo and the table is unfinished
 int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, int phase, bool want_dist, pct_call_clock* clock, const LevelPass* pass) {
+    const bool sweep_only = phase == 3;
+    if (sweep_only) phase = 0;
     const int64_t n_rows = pct_call_rows(ctx, pass);
     const SweepPlan plan = plan_for(ctx, k, eps, false, exact_only, phase, want_dist, pass);
     if (phase != 2) {
@@ -367,7 +371,7 @@ int pct_launch_knn_grid(pct_ctx* ctx, int32_t k, double eps, bool exact_only, in
     PCT_TRY(launch_sweep(ctx, plan, a, redo, redo_count));
     PCT_HIP(ctx, clock->boundary(PCT_ST_FAST_END, ctx->stream));      // end of the dominant kernel
     // exact pass: the flagged queries (device-side count, fixed grid) or, for testing, every query
-    if (phase != 1) {
+    if (phase != 1 && !sweep_only) {
         const int64_t waves = exact_only ? n_rows : 32768;   // one query per wave for typical redo counts
         const int blocks = (int)((waves + kWavesPerBlock - 1) / kWavesPerBlock);
         const int* list = exact_only ? nullptr : redo;
@@ -415,6 +419,8 @@ int pct_launch_knn_tree(pct_ctx* ctx, int32_t k, double eps, bool want_dist, pct
     ctx->knn_sorted_space = true;
     return PCT_OK;
 }
+
+unsigned pct_redo_trusted_bit() { return kRedoTrusted; }
 
 int pct_item_census(pct_ctx* ctx, int32_t k, unsigned long long out4[4]) {
     PCT_TRY(pct_reserve(ctx, &ctx->counters, sizeof(pct_dev_words)));

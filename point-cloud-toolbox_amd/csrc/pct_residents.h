@@ -26,6 +26,7 @@ constexpr pct_drop PCT_OWNERSHIP = {kPctPerOwnedRow};                      // pc
 constexpr pct_drop PCT_PLANTING = {kPctPerOwnedRow};                       // pct_knn, pct_curvature, pct_surface_variation, pct_pca_curvatures
 constexpr pct_drop PCT_TABLE_LOST = {PCT_R_TABLE};                         // pct_voxel_downsample: its buffers were reused, nothing replanted
 constexpr pct_drop PCT_TABLE_AND_FIT_LOST = {PCT_R_TABLE | PCT_R_FIT};     // pct_pca_curvatures: the table in place holds over-fetched candidates
+constexpr pct_drop PCT_UNFINISHED_TABLE = {kPctEveryResident};             // pct_selftest_sweep: a fast sweep without its exact sweep -- as a new cloud
 
 // ---- what a result is derived from ------------------------------------------------------------------------------------------
 // Frames come from the fit, the orientation from the frames, the hole results from the triangles (include/pct_hip_holes.h).

@@ -377,6 +377,7 @@ EXCLUDED = {
     "pct_selftest_sort": "sorter self-test on caller arrays, device memory of its own: no state of the path (tests/test_gpu_sort_net.py)",
     "pct_selftest_sort_exact": "sorter self-test on caller arrays, device memory of its own: no state of the path (tests/test_gpu_sort_net.py)",
     "pct_selftest_order_keys": "sorter self-test on caller arrays, device memory of its own: no state of the path (tests/test_gpu_sort_net.py)",
+    "pct_selftest_sweep": "sweep self-test on the handle's cloud: drops every result, as a new cloud does, and leaves none -- pct_get_neighbors after it is refused (tests/test_gpu_select.py); not drawn into the random sequences",
     "pct_selftest_levels_classify": "planning-kernel self-test on caller arrays, device memory of its own: no state of the path (tests/test_gpu_levels_exact.py)",
     "pct_selftest_levels_bands": "planning-kernel self-test on caller arrays, device memory of its own: no state of the path (tests/test_gpu_levels_exact.py)",
     "pct_selftest_levels_merge": "planning-kernel self-test on caller arrays, device memory of its own: no state of the path (tests/test_gpu_levels_exact.py)",
