@@ -69,6 +69,16 @@ int pct_reserve(pct_ctx* ctx, pct_buf* b, size_t bytes) {
     return PCT_OK;
 }
 
+int pct_claim_bytes(pct_ctx* ctx, size_t bytes, void** out, const char* who) {
+    if (ctx->stage_top >= kPctStageSlots)
+        return pct_fail(ctx, PCT_ERR_INVALID, "%s: every one of the %d staging slots is claimed", who, kPctStageSlots);
+    pct_buf* slot = &ctx->stage[ctx->stage_top];
+    PCT_TRY(pct_reserve(ctx, slot, bytes));
+    ++ctx->stage_top;
+    *out = slot->p;
+    return PCT_OK;
+}
+
 int pct_reserve_fit(pct_ctx* ctx, int64_t rows) {
     PCT_TRY(pct_reserve(ctx, &ctx->coefs, (size_t)rows * 6 * sizeof(float)));
     PCT_TRY(pct_reserve(ctx, &ctx->K, (size_t)rows * sizeof(float)));
@@ -113,6 +123,22 @@ static int drain(pct_ctx* ctx) {
     finish_pending(ctx);
     ctx->tm = ctx->tm_done;
     PCT_HIP(ctx, e);
+    return PCT_OK;
+}
+
+int pct_begin_call(pct_ctx* ctx, bool wait_for_pending) {
+    if (!ctx) return PCT_ERR_INVALID;
+    ctx->err[0] = 0;
+    ctx->stage_top = 0;            // (an error return of the call before left its claims standing: nothing to clean up)
+    PCT_HIP(ctx, hipSetDevice(ctx->device));
+    if (wait_for_pending) PCT_TRY(drain(ctx));
+    return PCT_OK;
+}
+
+int pct_begin_row_call(pct_ctx* ctx, const char* what) {
+    PCT_TRY(pct_begin_call(ctx));
+    if (ctx->slab_parts >= 1)
+        return pct_fail(ctx, PCT_ERR_INVALID, "%s: this handle owns a slab, not an index range (pct_slab_records / pct_scatter_records)", what);
     return PCT_OK;
 }
 
@@ -241,38 +267,19 @@ void pct_destroy(pct_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     pct_comm_release(ctx);
-    pct_buf* all[] = {&ctx->xyz, &ctx->pts4, &ctx->pts4d, &ctx->cell_of, &ctx->cell_cnt, &ctx->cell_fill,
-                      &ctx->scan_tmp, &ctx->occ, &ctx->redo, &ctx->row_of, &ctx->owned_pos, &ctx->cell_own, &ctx->cell_oth, &ctx->own_start, &ctx->sorted4, &ctx->sorted4d, &ctx->red, &ctx->nbr_pos,
-                      &ctx->nbr_dist, &ctx->nbr_cnt, &ctx->counters, &ctx->coefs, &ctx->K, &ctx->H, &ctx->H2,
-                      &ctx->stage_a, &ctx->stage_b, &ctx->stage_c, &ctx->stage_d, &ctx->row_done, &ctx->redo_m, &ctx->flag_buf, &ctx->dens_buf, &ctx->pub_pos, &ctx->pub_dist, &ctx->pub_cnt, &ctx->qpts4, &ctx->qry, &ctx->ball_off, &ctx->ball_idx, &ctx->ball_alt, &ctx->ball_dist, &ctx->fit_flag, &ctx->lvl_src,
-                      &ctx->tree_codes, &ctx->tree_vals, &ctx->tree_lvl, &ctx->tree_head, &ctx->tree_marks, &ctx->tree_seg, &ctx->tree_runs, &ctx->tree_range, &ctx->tree_bucket, &ctx->tree_tmp,
-                      &ctx->pca, &ctx->pca_aux, &ctx->pca_nbr, &ctx->pca_orig,
-                      &ctx->bin_rec, &ctx->bin_mat, &ctx->bin_plan, &ctx->bin_base,
-                      &ctx->area, &ctx->area_closed, &ctx->area_nverts, &ctx->area_over, &ctx->frame, &ctx->frame_flip, &ctx->orient, &ctx->stamp_tickets,
-                      &ctx->fan_head, &ctx->fan_fast, &ctx->fan_wide, &ctx->fan_side, &ctx->fan_over, &ctx->tri_mask, &ctx->tri_count, &ctx->tri_off,
-                      &ctx->tri_tmp, &ctx->tri_part, &ctx->tri,
-                      &ctx->hole_cnt, &ctx->hole_off, &ctx->hole_part, &ctx->hole_gap, &ctx->hole_slot, &ctx->hole_scan, &ctx->hole_loop, &ctx->hole_tri,
-                      &ctx->hole_alt, &ctx->hole_filled, &ctx->hole_tmp};
-    for (pct_buf* b : all) pct_release(b);
-    if (ctx->pin) (void)hipHostFree(ctx->pin);
-    for (auto& e : ctx->ev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& c : ctx->clock)
-        for (auto& e : c.ev)
-            if (e) (void)hipEventDestroy(e);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
+    // the buffers free themselves when the handle is deleted: what is destroyed after them is taken out of it first
+    pct_pinned* const pin = ctx->pin;
+    const hipStream_t stream = ctx->stream;
+    std::vector<hipEvent_t> events(ctx->ev, ctx->ev + PCT_EV_COUNT);
+    for (auto& c : ctx->clock) events.insert(events.end(), c.ev, c.ev + sizeof(c.ev) / sizeof(c.ev[0]));
     delete ctx;
+    if (pin) (void)hipHostFree(pin);
+    for (hipEvent_t e : events)
+        if (e) (void)hipEventDestroy(e);
+    if (stream) (void)hipStreamDestroy(stream);
 }
 
 const char* pct_last_error(const pct_ctx* ctx) { return ctx ? ctx->err : "null context"; }
-
-static int begin_call(pct_ctx* ctx, bool wait_for_pending = true) {
-    if (!ctx) return PCT_ERR_INVALID;
-    ctx->err[0] = 0;
-    PCT_HIP(ctx, hipSetDevice(ctx->device));
-    if (wait_for_pending) PCT_TRY(drain(ctx));
-    return PCT_OK;
-}
 
 // a change of ownership -- rows [begin, end), or (parts >= 1) a slab, whose rows the build cuts: the cell order depends on it
 static void own_rows(pct_ctx* ctx, int64_t begin, int64_t end, int32_t part, int32_t parts) {
@@ -298,7 +305,7 @@ static int new_cloud(pct_ctx* ctx, int64_t n) {
 }
 
 int pct_set_points_f32(pct_ctx* ctx, const float* xyz, int64_t n) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     if (!xyz) return pct_fail(ctx, PCT_ERR_INVALID, "null coordinates");
     PCT_TRY(new_cloud(ctx, n));
     PCT_TRY(pct_reserve(ctx, &ctx->xyz, (size_t)n * 3 * sizeof(float)));
@@ -312,13 +319,13 @@ int pct_set_points_f32(pct_ctx* ctx, const float* xyz, int64_t n) {
 }
 
 int pct_set_points_f64(pct_ctx* ctx, const double* xyz, int64_t n) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     if (!xyz) return pct_fail(ctx, PCT_ERR_INVALID, "null coordinates");
     PCT_TRY(new_cloud(ctx, n));
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_a, (size_t)n * 3 * sizeof(double)));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_IO_BEGIN], ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(ctx->stage_a.p, xyz, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    PCT_TRY(pct_pack_points_f64(ctx, (const double*)ctx->stage_a.p));
+    double* d_xyz = nullptr;
+    PCT_TRY(pct_claim_upload(ctx, xyz, (size_t)n * 3, &d_xyz));
+    PCT_TRY(pct_pack_points_f64(ctx, d_xyz));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_IO_END], ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->has_f64 = true;
@@ -327,7 +334,7 @@ int pct_set_points_f64(pct_ctx* ctx, const double* xyz, int64_t n) {
 }
 
 int pct_set_points_device_f32(pct_ctx* ctx, const void* dev_xyz, int64_t n) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     if (!dev_xyz) return pct_fail(ctx, PCT_ERR_INVALID, "null coordinates");
     PCT_TRY(new_cloud(ctx, n));
     PCT_TRY(pct_reserve(ctx, &ctx->xyz, (size_t)n * 3 * sizeof(float)));
@@ -338,7 +345,7 @@ int pct_set_points_device_f32(pct_ctx* ctx, const void* dev_xyz, int64_t n) {
 }
 
 int pct_use_points_device_f32(pct_ctx* ctx, const void* dev_xyz, int64_t n) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     if (!dev_xyz) return pct_fail(ctx, PCT_ERR_INVALID, "null coordinates");
     hipPointerAttribute_t attr;
     if (hipPointerGetAttributes(&attr, dev_xyz) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
@@ -351,7 +358,7 @@ int pct_use_points_device_f32(pct_ctx* ctx, const void* dev_xyz, int64_t n) {
 }
 
 int pct_set_query_range(pct_ctx* ctx, int64_t begin, int64_t end) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     if (ctx->n <= 0) return pct_fail(ctx, PCT_ERR_INVALID, "no cloud loaded");
     if (begin < 0 || end > ctx->n || begin > end) return pct_fail(ctx, PCT_ERR_INVALID, "bad query range [%lld,%lld)", (long long)begin, (long long)end);
     own_rows(ctx, begin, end, 0, 0);
@@ -359,7 +366,7 @@ int pct_set_query_range(pct_ctx* ctx, int64_t begin, int64_t end) {
 }
 
 int pct_set_query_slab(pct_ctx* ctx, int32_t part, int32_t parts) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     if (ctx->n <= 0) return pct_fail(ctx, PCT_ERR_INVALID, "no cloud loaded");
     if (parts > PCT_SLAB_PARTS_MAX || (parts >= 1 && (part < 0 || part >= parts)))
         return pct_fail(ctx, PCT_ERR_INVALID, "bad slab %d of %d (at most %d parts)", part, parts, PCT_SLAB_PARTS_MAX);
@@ -370,17 +377,8 @@ int pct_set_query_slab(pct_ctx* ctx, int32_t part, int32_t parts) {
     return PCT_OK;
 }
 
-// begin_call of the entry points a slab handle refuses (the header's list under "Ownership"): rows by index have no meaning
-// while the rows are those of a slab
-static int begin_row_call(pct_ctx* ctx, const char* what) {
-    PCT_TRY(begin_call(ctx));
-    if (ctx->slab_parts >= 1)
-        return pct_fail(ctx, PCT_ERR_INVALID, "%s: this handle owns a slab, not an index range (pct_slab_records / pct_scatter_records)", what);
-    return PCT_OK;
-}
-
 int pct_slab_counts(pct_ctx* ctx, int64_t* counts, int32_t parts) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     if (ctx->slab_parts < 1 || !ctx->slab_split_valid || !ctx->res.has(PCT_R_FIT))
         return pct_fail(ctx, PCT_ERR_INVALID, "pct_slab_counts: no slab pass on this handle (pct_set_query_slab, pct_curvature)");
     if (!counts || parts != ctx->slab_parts) return pct_fail(ctx, PCT_ERR_INVALID, "pct_slab_counts: %d parts asked, the cloud was cut into %d", parts, ctx->slab_parts);
@@ -418,7 +416,7 @@ __global__ __launch_bounds__(256) void k_scatter_records(const float* __restrict
 }  // namespace
 
 int pct_slab_records(pct_ctx* ctx, float* dev_records, int64_t capacity_rows, int64_t* rows_out) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     if (ctx->slab_parts < 1 || !ctx->slab_split_valid || !ctx->res.has(PCT_R_FIT) || !ctx->knn_sorted_space || !ctx->res.in_row_order(PCT_R_FIT))
         return pct_fail(ctx, PCT_ERR_INVALID, "pct_slab_records: no slab pass on this handle (pct_set_query_slab, pct_curvature)");
     const int64_t rows = ctx->q_end - ctx->q_begin;
@@ -433,7 +431,7 @@ int pct_slab_records(pct_ctx* ctx, float* dev_records, int64_t capacity_rows, in
 }
 
 int pct_scatter_records(pct_ctx* ctx, const float* dev_records, int64_t n_records, int64_t begin, int64_t end, float* dev_K, float* dev_H) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     if (n_records < 0 || begin < 0 || end < begin || (n_records > 0 && !dev_records) || (end > begin && (!dev_K || !dev_H)))
         return pct_fail(ctx, PCT_ERR_INVALID, "pct_scatter_records: bad arguments");
     PCT_TRY(pct_reserve(ctx, &ctx->counters, sizeof(pct_dev_words)));
@@ -453,13 +451,13 @@ int pct_scatter_records(pct_ctx* ctx, const float* dev_records, int64_t n_record
 }
 
 int pct_set_grid_param(pct_ctx* ctx, double occupancy_factor) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     ctx->occupancy_factor = occupancy_factor > 0 ? occupancy_factor : 0.0;
     return PCT_OK;
 }
 
 int pct_set_stats(pct_ctx* ctx, int32_t enable) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     ctx->collect_stats = enable != 0;
     return PCT_OK;
 }
@@ -649,7 +647,7 @@ static void retry_without_cull(pct_ctx* ctx) {
 }
 
 int pct_knn(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     bool again = false;
     for (int attempt = 0; attempt < 2; ++attempt) {
         PCT_TRY(run_knn(ctx, k, eps, algo, ctx->clock[0], PCT_CALL_SWEEP));
@@ -670,7 +668,7 @@ static int fit_left(pct_ctx* ctx, int64_t rows, bool cloud_aligned, bool by_row)
 }
 
 int pct_fit(pct_ctx* ctx) {
-    PCT_TRY(begin_row_call(ctx, "pct_fit"));
+    PCT_TRY(pct_begin_row_call(ctx, "pct_fit"));
     if (!ctx->res.has(PCT_R_TABLE)) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "plant the neighbour table first (pct_knn)");
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_BEGIN], ctx->stream));
     bool by_row = false;
@@ -683,7 +681,7 @@ int pct_fit(pct_ctx* ctx) {
 }
 
 int pct_set_async(pct_ctx* ctx, int32_t enable) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     ctx->async_mode = enable != 0;
     return PCT_OK;
 }
@@ -723,7 +721,7 @@ int pct_curvature(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
     // repeats a pass for points it left out, and statistics are off)
     const bool async = ctx && ctx->async_mode && ctx->n > 0 && ctx->q_begin == 0 && ctx->q_end == ctx->n && ctx->slab_parts == 0 &&
                        !ctx->collect_stats;
-    PCT_TRY(begin_call(ctx, !async));
+    PCT_TRY(pct_begin_call(ctx, !async));
     if (async) return curvature_async(ctx, k, eps, algo);
     bool fit_by_row = false;
     for (int attempt = 0; attempt < 2; ++attempt) {
@@ -739,7 +737,7 @@ int pct_curvature(pct_ctx* ctx, int32_t k, double eps, int32_t algo) {
 }
 
 int pct_get_neighbors(pct_ctx* ctx, int64_t begin, int64_t end, int32_t* idx, float* dist, int32_t* count) {
-    PCT_TRY(begin_row_call(ctx, "pct_get_neighbors"));
+    PCT_TRY(pct_begin_row_call(ctx, "pct_get_neighbors"));
     if (!ctx->res.has(PCT_R_TABLE)) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "no neighbour table");
     if (begin < ctx->q_begin || end > ctx->q_end || begin > end)
         return pct_fail(ctx, PCT_ERR_INVALID, "rows [%lld,%lld) outside the owned range [%lld,%lld)", (long long)begin,
@@ -747,46 +745,45 @@ int pct_get_neighbors(pct_ctx* ctx, int64_t begin, int64_t end, int32_t* idx, fl
     const int64_t rows = end - begin;
     if (rows == 0) return PCT_OK;
     const size_t cells = (size_t)rows * ctx->k;
-    if (idx) PCT_TRY(pct_reserve(ctx, &ctx->stage_a, cells * sizeof(int)));
-    if (dist) PCT_TRY(pct_reserve(ctx, &ctx->stage_b, cells * sizeof(float)));
-    if (count) PCT_TRY(pct_reserve(ctx, &ctx->stage_c, (size_t)rows * sizeof(int)));
+    int *d_idx = nullptr, *d_cnt = nullptr;
+    float* d_dist = nullptr;
+    if (idx) PCT_TRY(pct_claim(ctx, cells, &d_idx));
+    if (dist) PCT_TRY(pct_claim(ctx, cells, &d_dist));
+    if (count) PCT_TRY(pct_claim(ctx, (size_t)rows, &d_cnt));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_IO_BEGIN], ctx->stream));
-    PCT_TRY(pct_launch_export_neighbors(ctx, begin, end, idx ? (int*)ctx->stage_a.p : nullptr,
-                                        dist ? (float*)ctx->stage_b.p : nullptr, count ? (int*)ctx->stage_c.p : nullptr));
+    PCT_TRY(pct_launch_export_neighbors(ctx, begin, end, d_idx, d_dist, d_cnt));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_IO_END], ctx->stream));
-    if (idx) PCT_HIP(ctx, hipMemcpyAsync(idx, ctx->stage_a.p, cells * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    if (dist) PCT_HIP(ctx, hipMemcpyAsync(dist, ctx->stage_b.p, cells * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (count) PCT_HIP(ctx, hipMemcpyAsync(count, ctx->stage_c.p, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const pct_column cols[] = {{d_idx, ctx->k * (int)sizeof(int), idx}, {d_dist, ctx->k * (int)sizeof(float), dist}, {d_cnt, sizeof(int), count}};
+    PCT_TRY(pct_download_columns(ctx, cols, 3, 0, rows, nullptr));
     ctx->tm.export_ms = ev_ms(ctx, PCT_EV_IO_BEGIN, PCT_EV_IO_END);
     return PCT_OK;
 }
 
 int pct_get_neighbor_rows(pct_ctx* ctx, const int64_t* rows, int64_t n_rows, int32_t* idx, float* dist, int32_t* count) {
-    PCT_TRY(begin_row_call(ctx, "pct_get_neighbor_rows"));
+    PCT_TRY(pct_begin_row_call(ctx, "pct_get_neighbor_rows"));
     if (!ctx->res.has(PCT_R_TABLE)) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "no neighbour table");
     if (!rows || n_rows <= 0) return pct_fail(ctx, PCT_ERR_INVALID, "bad row list");
     for (int64_t i = 0; i < n_rows; ++i)
         if (rows[i] < ctx->q_begin || rows[i] >= ctx->q_end)
             return pct_fail(ctx, PCT_ERR_INVALID, "row %lld outside the owned range", (long long)rows[i]);
     const size_t cells = (size_t)n_rows * ctx->k;
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_d, (size_t)n_rows * sizeof(int64_t)));
-    if (idx) PCT_TRY(pct_reserve(ctx, &ctx->stage_a, cells * sizeof(int)));
-    if (dist) PCT_TRY(pct_reserve(ctx, &ctx->stage_b, cells * sizeof(float)));
-    if (count) PCT_TRY(pct_reserve(ctx, &ctx->stage_c, (size_t)n_rows * sizeof(int)));
-    PCT_HIP(ctx, hipMemcpyAsync(ctx->stage_d.p, rows, (size_t)n_rows * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    PCT_TRY(pct_launch_export_rows(ctx, (const int64_t*)ctx->stage_d.p, n_rows, idx ? (int*)ctx->stage_a.p : nullptr,
-                                   dist ? (float*)ctx->stage_b.p : nullptr, count ? (int*)ctx->stage_c.p : nullptr));
-    if (idx) PCT_HIP(ctx, hipMemcpyAsync(idx, ctx->stage_a.p, cells * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    if (dist) PCT_HIP(ctx, hipMemcpyAsync(dist, ctx->stage_b.p, cells * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (count) PCT_HIP(ctx, hipMemcpyAsync(count, ctx->stage_c.p, (size_t)n_rows * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PCT_OK;
+    int64_t* d_rows = nullptr;
+    int *d_idx = nullptr, *d_cnt = nullptr;
+    float* d_dist = nullptr;
+    PCT_TRY(pct_claim_upload(ctx, rows, (size_t)n_rows, &d_rows));
+    if (idx) PCT_TRY(pct_claim(ctx, cells, &d_idx));
+    if (dist) PCT_TRY(pct_claim(ctx, cells, &d_dist));
+    if (count) PCT_TRY(pct_claim(ctx, (size_t)n_rows, &d_cnt));
+    PCT_TRY(pct_launch_export_rows(ctx, d_rows, n_rows, d_idx, d_dist, d_cnt));
+    const pct_column cols[] = {{d_idx, ctx->k * (int)sizeof(int), idx}, {d_dist, ctx->k * (int)sizeof(float), dist}, {d_cnt, sizeof(int), count}};
+    return pct_download_columns(ctx, cols, 3, 0, n_rows, nullptr);
 }
 
-// validates host-supplied neighbour rows and stages them on the device (stage_a: ids with a 16-byte row pitch,
-// stage_c: counts, stage_d: query ids); the public-order records are packed if they are not resident
-static int stage_neighbour_rows(pct_ctx* ctx, const int32_t* idx, const int32_t* count, const int64_t* query, int64_t rows, int32_t k, int32_t* pitch_out, bool need_pts4) {
+// validates host-supplied neighbour rows and stages them on the device, in claims that are the calling entry point's (no
+// scope: they outlive this function): ids with a 16-byte row pitch, counts and query ids (null where the caller gave
+// none); the public-order records are packed if they are not resident
+struct StagedRows { int* idx; int* cnt; int64_t* query; int32_t pitch; };
+static int stage_neighbour_rows(pct_ctx* ctx, const int32_t* idx, const int32_t* count, const int64_t* query, int64_t rows, int32_t k, StagedRows* out, bool need_pts4) {
     if (ctx->n <= 0) return pct_fail(ctx, PCT_ERR_INVALID, "no cloud loaded");
     if (!idx || rows <= 0 || k < 1 || k > 4096) return pct_fail(ctx, PCT_ERR_INVALID, "bad neighbour rows");
     // host-side validation: the reference raises IndexError on such rows (pct:640).  PCT_TRUST_ROWS=1 skips it (test
@@ -808,30 +805,22 @@ static int stage_neighbour_rows(pct_ctx* ctx, const int32_t* idx, const int32_t*
     }
     // device rows are 16-byte aligned: pitch = k rounded up to a multiple of 4
     const int32_t pitch = (k + 3) & ~3;
-    const size_t cells = (size_t)rows * pitch;
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_a, cells * sizeof(int)));
-    PCT_HIP(ctx, hipMemcpy2DAsync(ctx->stage_a.p, (size_t)pitch * sizeof(int), idx, (size_t)k * sizeof(int),
+    *out = StagedRows{nullptr, nullptr, nullptr, pitch};
+    PCT_TRY(pct_claim(ctx, (size_t)rows * pitch, &out->idx));
+    PCT_HIP(ctx, hipMemcpy2DAsync(out->idx, (size_t)pitch * sizeof(int), idx, (size_t)k * sizeof(int),
                                   (size_t)k * sizeof(int), (size_t)rows, hipMemcpyHostToDevice, ctx->stream));
-    if (count) {
-        PCT_TRY(pct_reserve(ctx, &ctx->stage_c, (size_t)rows * sizeof(int)));
-        PCT_HIP(ctx, hipMemcpyAsync(ctx->stage_c.p, count, (size_t)rows * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (query) {
-        PCT_TRY(pct_reserve(ctx, &ctx->stage_d, (size_t)rows * sizeof(int64_t)));
-        PCT_HIP(ctx, hipMemcpyAsync(ctx->stage_d.p, query, (size_t)rows * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    }
-    *pitch_out = pitch;
+    if (count) PCT_TRY(pct_claim_upload(ctx, count, (size_t)rows, &out->cnt));
+    if (query) PCT_TRY(pct_claim_upload(ctx, query, (size_t)rows, &out->query));
     return PCT_OK;
 }
 
 int pct_fit_indices(pct_ctx* ctx, const int32_t* idx, const int32_t* count, const int64_t* query, int64_t rows, int32_t k) {
-    PCT_TRY(begin_row_call(ctx, "pct_fit_indices"));
-    int32_t pitch = 0;
-    PCT_TRY(stage_neighbour_rows(ctx, idx, count, query, rows, k, &pitch, true));
+    PCT_TRY(pct_begin_row_call(ctx, "pct_fit_indices"));
+    StagedRows in;
+    PCT_TRY(stage_neighbour_rows(ctx, idx, count, query, rows, k, &in, true));
     PCT_TRY(pct_reserve_fit(ctx, rows));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_BEGIN], ctx->stream));
-    PCT_TRY(pct_launch_fit_rows(ctx, (const int*)ctx->stage_a.p, count ? (const int*)ctx->stage_c.p : nullptr,
-                                query ? (const int64_t*)ctx->stage_d.p : nullptr, rows, k, pitch, (float*)ctx->coefs.p,
+    PCT_TRY(pct_launch_fit_rows(ctx, in.idx, in.cnt, in.query, rows, k, in.pitch, (float*)ctx->coefs.p,
                                 (float*)ctx->K.p, (float*)ctx->H.p, (float*)ctx->H2.p, false));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_END], ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -842,21 +831,17 @@ int pct_fit_indices(pct_ctx* ctx, const int32_t* idx, const int32_t* count, cons
 
 int pct_fit_indices_f64(pct_ctx* ctx, const int32_t* idx, const int32_t* count, const int64_t* query, int64_t rows, int32_t k,
                         double* coefs, double* K, double* H) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     if (!coefs || !K || !H) return pct_fail(ctx, PCT_ERR_INVALID, "output arrays missing");
-    int32_t pitch = 0;
-    PCT_TRY(stage_neighbour_rows(ctx, idx, count, query, rows, k, &pitch, false));
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_b, (size_t)rows * 8 * sizeof(double)));
-    double* d_c = (double*)ctx->stage_b.p;
+    StagedRows in;
+    PCT_TRY(stage_neighbour_rows(ctx, idx, count, query, rows, k, &in, false));
+    double* d_c = nullptr;           // one claim: coefs (rows, 6) | K | H
+    PCT_TRY(pct_claim(ctx, (size_t)rows * 8, &d_c));
     double* d_K = d_c + rows * 6;
     double* d_H = d_K + rows;
-    PCT_TRY(pct_launch_fit_rows_f64(ctx, (const int*)ctx->stage_a.p, count ? (const int*)ctx->stage_c.p : nullptr,
-                                    query ? (const int64_t*)ctx->stage_d.p : nullptr, rows, k, pitch, d_c, d_K, d_H));
-    PCT_HIP(ctx, hipMemcpyAsync(coefs, d_c, (size_t)rows * 6 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(K, d_K, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(H, d_H, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PCT_OK;       // the resident float32 results and the neighbour table are untouched
+    PCT_TRY(pct_launch_fit_rows_f64(ctx, in.idx, in.cnt, in.query, rows, k, in.pitch, d_c, d_K, d_H));
+    const pct_column cols[] = {{d_c, 6 * sizeof(double), coefs}, {d_K, sizeof(double), K}, {d_H, sizeof(double), H}};
+    return pct_download_columns(ctx, cols, 3, 0, rows, nullptr);       // the resident float32 results and the neighbour table are untouched
 }
 
 // ---- queries of caller-supplied points: what pct_query_points, pct_query_points_algo and pct_query_ball share ----------------
@@ -911,7 +896,7 @@ static int build_query_grid(pct_ctx* ctx, int32_t kb, const char* who) {
 // never a list built, and query_stats stay those of the last pct_query_points_algo call.
 static int query_points(pct_ctx* ctx, const char* who, const double* q_xyz, int64_t m, int32_t k, double eps, const int32_t* algo,
                         int32_t* idx, double* dist) {
-    PCT_TRY(begin_row_call(ctx, who));
+    PCT_TRY(pct_begin_row_call(ctx, who));
     PCT_TRY(check_query_arrays(ctx, q_xyz, m, m == 0 || (idx && dist)));
     if (k < 1 || k > 128) return pct_fail(ctx, PCT_ERR_INVALID, "k=%d outside [1,128]", k);
     QueryRoute route = QueryRoute::Sweep;
@@ -924,16 +909,17 @@ static int query_points(pct_ctx* ctx, const char* who, const double* q_xyz, int6
     if (!(eps >= 0) || isinf(eps)) eps = 0;
     // (two list registers at the most: the occupancy rule of longer rows is the exact-only sweep's)
     if (route == QueryRoute::GridBuild) PCT_TRY(build_query_grid(ctx, k < 127 ? k : 127, who));
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_a, (size_t)m * 3 * sizeof(double)));
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_b, (size_t)m * k * sizeof(int32_t)));
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_c, (size_t)m * k * sizeof(double)));
-    PCT_HIP(ctx, hipMemcpyAsync(ctx->stage_a.p, q_xyz, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    double *d_q = nullptr, *d_dist = nullptr;
+    int32_t* d_idx = nullptr;
+    PCT_TRY(pct_claim_upload(ctx, q_xyz, (size_t)m * 3, &d_q));
+    PCT_TRY(pct_claim(ctx, (size_t)m * k, &d_idx));
+    PCT_TRY(pct_claim(ctx, (size_t)m * k, &d_dist));
     if (route == QueryRoute::Sweep)
-        PCT_TRY(pct_launch_query_points(ctx, (const double*)ctx->stage_a.p, m, k, eps, (int32_t*)ctx->stage_b.p, (double*)ctx->stage_c.p));
+        PCT_TRY(pct_launch_query_points(ctx, d_q, m, k, eps, d_idx, d_dist));
     else
-        PCT_TRY(pct_launch_query_grid(ctx, (const double*)ctx->stage_a.p, m, k, eps, (int32_t*)ctx->stage_b.p, (double*)ctx->stage_c.p, ctx->query_words));
-    PCT_HIP(ctx, hipMemcpyAsync(idx, ctx->stage_b.p, (size_t)m * k * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(dist, ctx->stage_c.p, (size_t)m * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        PCT_TRY(pct_launch_query_grid(ctx, d_q, m, k, eps, d_idx, d_dist, ctx->query_words));
+    PCT_TRY(pct_enqueue_download(ctx, idx, d_idx, (size_t)m * k));
+    PCT_TRY(pct_enqueue_download(ctx, dist, d_dist, (size_t)m * k));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (algo) ctx->query_stats[0] = (int64_t)route;
     if (route != QueryRoute::Sweep) {
@@ -962,7 +948,7 @@ int pct_query_stats(pct_ctx* ctx, int64_t out[4]) {
 // Radius search (pct_ball.hip).  The route is ball_route's (pct_ball_plan.h), from the same state query_points reads.
 int pct_query_ball(pct_ctx* ctx, const double* q_xyz, int64_t m, const double* r, int64_t n_r, int32_t flags, int32_t algo,
                    int64_t max_entries, int64_t* offsets) {
-    PCT_TRY(begin_row_call(ctx, "pct_query_ball"));
+    PCT_TRY(pct_begin_row_call(ctx, "pct_query_ball"));
     PCT_TRY(check_query_arrays(ctx, q_xyz, m, offsets && (m == 0 || r)));
     if (m > 0 && n_r != 1 && n_r != m) return pct_fail(ctx, PCT_ERR_INVALID, "%lld radii for %lld queries (one, or one per query)", (long long)n_r, (long long)m);
     if (flags & ~(PCT_BALL_SORTED | PCT_BALL_DISTANCES | PCT_BALL_COUNT_ONLY)) return pct_fail(ctx, PCT_ERR_INVALID, "unknown flags %d", flags);
@@ -974,13 +960,12 @@ int pct_query_ball(pct_ctx* ctx, const double* q_xyz, int64_t m, const double* r
     for (int i = 0; i < 4; ++i) ctx->ball_stats[i] = 0;
     offsets[0] = 0;
     if (m > 0) {
-        PCT_TRY(pct_reserve(ctx, &ctx->stage_a, (size_t)m * 3 * sizeof(double)));
-        PCT_TRY(pct_reserve(ctx, &ctx->stage_b, (size_t)n_r * sizeof(double)));
-        PCT_HIP(ctx, hipMemcpyAsync(ctx->stage_a.p, q_xyz, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        PCT_HIP(ctx, hipMemcpyAsync(ctx->stage_b.p, r, (size_t)n_r * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        double *d_q = nullptr, *d_r = nullptr;
+        PCT_TRY(pct_claim_upload(ctx, q_xyz, (size_t)m * 3, &d_q));
+        PCT_TRY(pct_claim_upload(ctx, r, (size_t)n_r, &d_r));
         ctx->ball_stats[0] = (int64_t)route;
-        PCT_TRY(pct_launch_ball(ctx, route != QueryRoute::Sweep, (const double*)ctx->stage_a.p, m, (const double*)ctx->stage_b.p,
-                                n_r == m && m > 1 ? 1 : 0, flags, max_entries, offsets, ctx->ball_stats + 1));
+        PCT_TRY(pct_launch_ball(ctx, route != QueryRoute::Sweep, d_q, m, d_r, n_r == m && m > 1 ? 1 : 0, flags, max_entries, offsets,
+                                ctx->ball_stats + 1));
     }
     if (flags & PCT_BALL_COUNT_ONLY) return PCT_OK;        // (nothing is kept)
     ctx->ball_has_dist = (flags & PCT_BALL_DISTANCES) != 0;
@@ -989,7 +974,7 @@ int pct_query_ball(pct_ctx* ctx, const double* q_xyz, int64_t m, const double* r
 }
 
 int pct_get_ball(pct_ctx* ctx, int64_t row_begin, int64_t row_end, int32_t* idx, double* dist) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     if (!ctx->res.has(PCT_R_BALL)) return pct_fail(ctx, PCT_ERR_INVALID, "no ball rows on this handle (pct_query_ball)");
     const int64_t have = ctx->res.rows_of(PCT_R_BALL);
     if (row_begin < 0 || row_end > have || row_begin > row_end)
@@ -1013,7 +998,7 @@ int pct_get_ball(pct_ctx* ctx, int64_t row_begin, int64_t row_end, int32_t* idx,
 // Fit of the resident ball rows about their centres (pct_fit_ball.hip).  Like pct_fit_indices it replaces the results of an
 // earlier fit and nothing else: the rows, a resident neighbour table, PCA results and the cell list stay as they are.
 int pct_fit_ball(pct_ctx* ctx, const int64_t* self_rows, int64_t m, int32_t* used) {
-    PCT_TRY(begin_row_call(ctx, "pct_fit_ball"));
+    PCT_TRY(pct_begin_row_call(ctx, "pct_fit_ball"));
     if (!ctx->res.has(PCT_R_BALL)) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "pct_fit_ball: no ball rows on this handle (pct_query_ball)");
     if (m != ctx->res.rows_of(PCT_R_BALL))
         return pct_fail(ctx, PCT_ERR_INVALID, "pct_fit_ball: %lld centres for the %lld rows of the last query", (long long)m, (long long)ctx->res.rows_of(PCT_R_BALL));
@@ -1026,20 +1011,15 @@ int pct_fit_ball(pct_ctx* ctx, const int64_t* self_rows, int64_t m, int32_t* use
     if (m == 0) return fit_left(ctx, 0, false, false);
     ctx->res.drop(pct_replacing(PCT_R_FIT));   // accepted: the fit before this one is gone, the new one is there once the kernels have run
     PCT_TRY(pct_reserve_fit(ctx, m));
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_c, (size_t)m * sizeof(int)));
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_d, (size_t)m * sizeof(int)));
-    {
-        int* self32 = (int*)malloc((size_t)m * sizeof(int));
-        if (!self32) return pct_fail(ctx, PCT_ERR_OOM, "pct_fit_ball: %lld centres", (long long)m);
-        for (int64_t i = 0; i < m; ++i) self32[i] = (int)self_rows[i];
-        const hipError_t e = hipMemcpy(ctx->stage_c.p, self32, (size_t)m * sizeof(int), hipMemcpyHostToDevice);
-        free(self32);
-        PCT_HIP(ctx, e);
-    }
+    int *d_self = nullptr, *d_used = nullptr;
+    const std::vector<int> self32(self_rows, self_rows + m);
+    PCT_TRY(pct_claim_upload(ctx, self32.data(), self32.size(), &d_self));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));               // (the copy is done before the temporary dies, whichever way)
+    PCT_TRY(pct_claim(ctx, (size_t)m, &d_used));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_BEGIN], ctx->stream));
-    PCT_TRY(pct_launch_fit_ball(ctx, (const int*)ctx->stage_c.p, m, (int*)ctx->stage_d.p));
+    PCT_TRY(pct_launch_fit_ball(ctx, d_self, m, d_used));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_END], ctx->stream));
-    if (used) PCT_HIP(ctx, hipMemcpyAsync(used, ctx->stage_d.p, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    PCT_TRY(pct_enqueue_download(ctx, used, d_used, (size_t)m));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->tm.fit_ms = ev_ms(ctx, PCT_EV_FIT_BEGIN, PCT_EV_FIT_END);
     ctx->tm.fit_svd_rows = ctx->pin->svd_rows[0];
@@ -1079,7 +1059,7 @@ static int need_for_owned_rows(pct_ctx* ctx, pct_resident r, const char* missing
 }
 
 int pct_get_fit(pct_ctx* ctx, int64_t begin, int64_t end, float* coefs, float* K, float* H, float* H2) {
-    PCT_TRY(begin_row_call(ctx, "pct_get_fit"));
+    PCT_TRY(pct_begin_row_call(ctx, "pct_get_fit"));
     if (!ctx->res.has(PCT_R_FIT)) return pct_fail(ctx, PCT_ERR_INVALID, "no fit results");
     const int64_t base = ctx->fit_cloud_aligned ? ctx->q_begin : 0;   // cloud-aligned vs row-aligned results
     PCT_TRY(check_owned_span(ctx, "the fitted range", PCT_R_FIT, begin, end, base));
@@ -1090,7 +1070,7 @@ int pct_get_fit(pct_ctx* ctx, int64_t begin, int64_t end, float* coefs, float* K
 
 // ---- per-point tangent-plane Voronoi areas and the energies over them (pct_area.hip) --------------------------------------
 int pct_point_areas(pct_ctx* ctx) {
-    PCT_TRY(begin_row_call(ctx, "pct_point_areas"));
+    PCT_TRY(pct_begin_row_call(ctx, "pct_point_areas"));
     if (!ctx->res.has(PCT_R_TABLE)) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "plant the neighbour table first (pct_knn)");
     ctx->res.drop(pct_replacing(PCT_R_AREAS));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_AREA_BEGIN], ctx->stream));
@@ -1111,7 +1091,7 @@ int pct_point_areas(pct_ctx* ctx) {
 }
 
 int pct_get_point_areas(pct_ctx* ctx, int64_t begin, int64_t end, double* area, uint8_t* closed, int32_t* nverts) {
-    PCT_TRY(begin_row_call(ctx, "pct_get_point_areas"));
+    PCT_TRY(pct_begin_row_call(ctx, "pct_get_point_areas"));
     if (!ctx->res.has(PCT_R_AREAS)) return pct_fail(ctx, PCT_ERR_INVALID, "no point areas (pct_point_areas)");
     PCT_TRY(check_owned_span(ctx, "the owned range", PCT_R_AREAS, begin, end, ctx->q_begin));
     const pct_column cols[] = {{ctx->area.p, sizeof(double), area}, {ctx->area_closed.p, 1, closed}, {ctx->area_nverts.p, sizeof(int), nverts}};
@@ -1131,22 +1111,22 @@ int pct_point_area_profile(pct_ctx* ctx, double out[2]) {
 }
 
 int pct_point_energies(pct_ctx* ctx, int32_t closed_only, double out[4]) {
-    PCT_TRY(begin_row_call(ctx, "pct_point_energies"));
+    PCT_TRY(pct_begin_row_call(ctx, "pct_point_energies"));
     if (!out) return pct_fail(ctx, PCT_ERR_INVALID, "null result");
     PCT_TRY(need_for_owned_rows(ctx, PCT_R_FIT, "no fit results"));
     PCT_TRY(need_for_owned_rows(ctx, PCT_R_AREAS, "no point areas (pct_point_areas)"));
     const int nblk = 1024;
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_d, ((size_t)nblk * 4 + 4) * sizeof(double)));
-    double* d_part = (double*)ctx->stage_d.p;
+    double* d_part = nullptr;
+    PCT_TRY(pct_claim(ctx, (size_t)nblk * 4 + 4, &d_part));
     PCT_TRY(pct_launch_point_energies(ctx, closed_only != 0, d_part, d_part + (size_t)nblk * 4));
-    PCT_HIP(ctx, hipMemcpyAsync(out, d_part + (size_t)nblk * 4, 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    PCT_TRY(pct_enqueue_download(ctx, out, d_part + (size_t)nblk * 4, 4));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PCT_OK;
 }
 
 // ---- per-point surface frames from the resident fit (pct_frame.hip) ----------------------------------------------------
 int pct_point_frames(pct_ctx* ctx, const double* viewpoint) {
-    PCT_TRY(begin_row_call(ctx, "pct_point_frames"));
+    PCT_TRY(pct_begin_row_call(ctx, "pct_point_frames"));
     if (!ctx->res.has(PCT_R_TABLE)) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "plant the neighbour table first (pct_knn)");
     PCT_TRY(need_for_owned_rows(ctx, PCT_R_FIT, "no fit results"));
     if (viewpoint && !(isfinite(viewpoint[0]) && isfinite(viewpoint[1]) && isfinite(viewpoint[2])))
@@ -1167,7 +1147,7 @@ int pct_point_frames(pct_ctx* ctx, const double* viewpoint) {
 }
 
 int pct_get_point_frames(pct_ctx* ctx, int64_t begin, int64_t end, double* normal, double* k12, double* dirs, uint8_t* flipped) {
-    PCT_TRY(begin_row_call(ctx, "pct_get_point_frames"));
+    PCT_TRY(pct_begin_row_call(ctx, "pct_get_point_frames"));
     if (!ctx->res.has(PCT_R_FRAMES)) return pct_fail(ctx, PCT_ERR_INVALID, "no point frames (pct_point_frames)");
     PCT_TRY(check_owned_span(ctx, "the owned range", PCT_R_FRAMES, begin, end, ctx->q_begin));
     const int64_t all = ctx->res.rows_of(PCT_R_FRAMES);
@@ -1187,7 +1167,7 @@ int pct_point_frame_stats(pct_ctx* ctx, int64_t out[4], double* ms) {
 // ---- consistent orientation of the resident frames (pct_orient.hip) ------------------------------------------------------
 // the orientation belongs to the frames it turned: whatever drops or replaces them drops it (pct_residents.h)
 int pct_orient_frames(pct_ctx* ctx, int32_t anchor, const double* viewpoint, int32_t max_components) {
-    PCT_TRY(begin_row_call(ctx, "pct_orient_frames"));
+    PCT_TRY(pct_begin_row_call(ctx, "pct_orient_frames"));
     if (!ctx->res.has(PCT_R_FRAMES) || !ctx->res.has(PCT_R_TABLE)) return pct_fail(ctx, PCT_ERR_INVALID, "no point frames (pct_point_frames)");
     const int64_t rows = ctx->q_end - ctx->q_begin;
     if (ctx->q_begin != 0 || ctx->q_end != ctx->n || ctx->culled || !ctx->res.covers(PCT_R_FRAMES, rows))
@@ -1221,7 +1201,7 @@ int pct_orient_frames(pct_ctx* ctx, int32_t anchor, const double* viewpoint, int
 }
 
 int pct_get_orientation(pct_ctx* ctx, int64_t begin, int64_t end, int32_t* component, int32_t* parent, int32_t* level, uint8_t* toggled) {
-    PCT_TRY(begin_row_call(ctx, "pct_get_orientation"));
+    PCT_TRY(pct_begin_row_call(ctx, "pct_get_orientation"));
     if (!ctx->res.has(PCT_R_ORIENT)) return pct_fail(ctx, PCT_ERR_INVALID, "no orientation (pct_orient_frames)");
     PCT_TRY(check_owned_span(ctx, "the cloud", PCT_R_ORIENT, begin, end, 0));
     const pct_column cols[] = {{ctx->orient_comp, sizeof(int), component}, {ctx->orient_parent, sizeof(int), parent},
@@ -1238,7 +1218,7 @@ int pct_orient_stats(pct_ctx* ctx, int64_t out[8], double* ms) {
 
 // ---- faces from the tangent-plane Voronoi cells (pct_fan.hip, include/pct_hip_surface.h) -----------------------------------
 int pct_point_triangles(pct_ctx* ctx, int32_t flags) {
-    PCT_TRY(begin_row_call(ctx, "pct_point_triangles"));
+    PCT_TRY(pct_begin_row_call(ctx, "pct_point_triangles"));
     if (!ctx->res.has(PCT_R_TABLE)) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "plant the neighbour table first (pct_knn)");
     if (ctx->q_begin != 0 || ctx->q_end != ctx->n || ctx->culled)
         return pct_fail(ctx, PCT_ERR_INVALID, "pct_point_triangles: the handle owns rows [%lld,%lld) of %lld: agreement needs the whole cloud",
@@ -1267,22 +1247,23 @@ int pct_point_triangles(pct_ctx* ctx, int32_t flags) {
 }
 
 int pct_get_point_fans(pct_ctx* ctx, int64_t begin, int64_t end, int64_t* offsets, int32_t* nbr) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     if (!ctx->res.has(PCT_R_TRIANGLES)) return pct_fail(ctx, PCT_ERR_INVALID, "no triangles (pct_point_triangles)");
     if (begin < 0 || end > ctx->res.rows_of(PCT_R_TRIANGLES) || begin > end || !offsets)
         return pct_fail(ctx, PCT_ERR_INVALID, "rows [%lld,%lld) outside the cloud", (long long)begin, (long long)end);
     const int64_t rows = end - begin;
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_a, (size_t)(rows + 1) * sizeof(int64_t)));
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_b, (size_t)(rows + 1) * sizeof(int64_t)));
-    int64_t* d_off = (int64_t*)ctx->stage_b.p;
-    PCT_TRY(pct_launch_point_fans(ctx, begin, rows, (int64_t*)ctx->stage_a.p, d_off, nullptr));
-    PCT_HIP(ctx, hipMemcpyAsync(offsets, d_off, (size_t)(rows + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    int64_t *d_count = nullptr, *d_off = nullptr;
+    PCT_TRY(pct_claim(ctx, (size_t)(rows + 1), &d_count));
+    PCT_TRY(pct_claim(ctx, (size_t)(rows + 1), &d_off));
+    PCT_TRY(pct_launch_point_fans(ctx, begin, rows, d_count, d_off, nullptr));
+    PCT_TRY(pct_enqueue_download(ctx, offsets, d_off, (size_t)(rows + 1)));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const int64_t total = offsets[rows];
     if (!nbr || total == 0) return PCT_OK;
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_d, (size_t)total * sizeof(int)));
-    PCT_TRY(pct_launch_point_fans(ctx, begin, rows, (int64_t*)ctx->stage_a.p, d_off, (int*)ctx->stage_d.p));
-    PCT_HIP(ctx, hipMemcpyAsync(nbr, ctx->stage_d.p, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    int* d_nbr = nullptr;
+    PCT_TRY(pct_claim(ctx, (size_t)total, &d_nbr));
+    PCT_TRY(pct_launch_point_fans(ctx, begin, rows, d_count, d_off, d_nbr));
+    PCT_TRY(pct_enqueue_download(ctx, nbr, d_nbr, (size_t)total));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PCT_OK;
 }
@@ -1296,7 +1277,7 @@ static int download_triangles(pct_ctx* ctx, const pct_buf& src, int64_t have, in
 }
 
 int pct_get_triangles(pct_ctx* ctx, int64_t first, int64_t count, int32_t* tri) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     if (!ctx->res.has(PCT_R_TRIANGLES)) return pct_fail(ctx, PCT_ERR_INVALID, "no triangles (pct_point_triangles)");
     return download_triangles(ctx, ctx->tri, ctx->tri_total, first, count, tri);
 }
@@ -1316,7 +1297,7 @@ int pct_point_triangle_profile(pct_ctx* ctx, double out[2]) {
 
 // ---- boundary loops and small-hole filling (pct_hole.hip, include/pct_hip_holes.h): PCT_R_HOLES, made from the triangles ------
 int pct_fill_holes(pct_ctx* ctx, int32_t max_vertices, double max_perimeter, int32_t flags) {
-    PCT_TRY(begin_row_call(ctx, "pct_fill_holes"));
+    PCT_TRY(pct_begin_row_call(ctx, "pct_fill_holes"));
     if (ctx->n > 0 && (ctx->q_begin != 0 || ctx->q_end != ctx->n || ctx->culled))
         return pct_fail(ctx, PCT_ERR_INVALID, "pct_fill_holes: the handle owns rows [%lld,%lld) of %lld: a loop may cross into other rows",
                         (long long)ctx->q_begin, (long long)ctx->q_end, (long long)ctx->n);
@@ -1342,7 +1323,7 @@ int pct_fill_holes(pct_ctx* ctx, int32_t max_vertices, double max_perimeter, int
 }
 
 static int get_triangle_rows(pct_ctx* ctx, const pct_buf& src, int64_t have, int64_t first, int64_t count, int32_t* tri) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     if (!ctx->res.has(PCT_R_HOLES)) return pct_fail(ctx, PCT_ERR_INVALID, "no hole results (pct_fill_holes)");
     return download_triangles(ctx, src, have, first, count, tri);
 }
@@ -1358,7 +1339,7 @@ int pct_get_filled_triangles(pct_ctx* ctx, int64_t first, int64_t count, int32_t
 }
 
 int pct_get_boundary_loops(pct_ctx* ctx, int64_t* offsets, int32_t* vertices, uint8_t* status) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     if (!ctx->res.has(PCT_R_HOLES)) return pct_fail(ctx, PCT_ERR_INVALID, "no hole results (pct_fill_holes)");
     if (!offsets) return pct_fail(ctx, PCT_ERR_INVALID, "null offsets");
     const int64_t loops = ctx->hole_loops, verts = ctx->hole_loop_verts;
@@ -1379,53 +1360,50 @@ int pct_fill_hole_stats(pct_ctx* ctx, int64_t out[8], double* ms) {
 }
 
 int pct_curvatures_from_coefficients(pct_ctx* ctx, const float* coefs, int64_t rows, float* K, float* H, float* H2) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     if (!coefs || rows <= 0) return pct_fail(ctx, PCT_ERR_INVALID, "bad coefficient rows");
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_a, (size_t)rows * 6 * sizeof(float)));
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_b, (size_t)rows * 3 * sizeof(float)));
-    float* d_out = (float*)ctx->stage_b.p;
-    PCT_HIP(ctx, hipMemcpyAsync(ctx->stage_a.p, coefs, (size_t)rows * 6 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    PCT_TRY(pct_launch_curvatures(ctx, (const float*)ctx->stage_a.p, rows, d_out, d_out + rows, d_out + 2 * rows));
-    if (K) PCT_HIP(ctx, hipMemcpyAsync(K, d_out, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (H) PCT_HIP(ctx, hipMemcpyAsync(H, d_out + rows, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (H2) PCT_HIP(ctx, hipMemcpyAsync(H2, d_out + 2 * rows, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PCT_OK;
+    float *d_coefs = nullptr, *d_out = nullptr;
+    PCT_TRY(pct_claim_upload(ctx, coefs, (size_t)rows * 6, &d_coefs));
+    PCT_TRY(pct_claim(ctx, (size_t)rows * 3, &d_out));
+    PCT_TRY(pct_launch_curvatures(ctx, d_coefs, rows, d_out, d_out + rows, d_out + 2 * rows));
+    const pct_column cols[] = {{d_out, sizeof(float), K}, {d_out + rows, sizeof(float), H}, {d_out + 2 * rows, sizeof(float), H2}};
+    return pct_download_columns(ctx, cols, 3, 0, rows, nullptr);
 }
 
 int pct_plane_rotate(pct_ctx* ctx, const void* nbrs, int32_t is_f64, int64_t batch, int32_t m, double* rotated) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     if (!nbrs || !rotated || batch <= 0 || m < 2 || (double)batch * m > 2.0e9) return pct_fail(ctx, PCT_ERR_INVALID, "bad neighbourhood block");
     const size_t count = (size_t)batch * m * 3, esz = is_f64 ? sizeof(double) : sizeof(float);
     if (is_f64) { const double* p = (const double*)nbrs; for (size_t i = 0; i < count; ++i) if (!isfinite(p[i])) return pct_fail(ctx, PCT_ERR_NONFINITE, "Non-finite values in input points"); }
     else { const float* p = (const float*)nbrs; for (size_t i = 0; i < count; ++i) if (!isfinite(p[i])) return pct_fail(ctx, PCT_ERR_NONFINITE, "Non-finite values in input points"); }
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_a, count * esz));
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_b, count * sizeof(double)));
-    PCT_HIP(ctx, hipMemcpyAsync(ctx->stage_a.p, nbrs, count * esz, hipMemcpyHostToDevice, ctx->stream));
-    PCT_TRY(pct_launch_plane_rotate(ctx, ctx->stage_a.p, is_f64 != 0, batch, m, (double*)ctx->stage_b.p));
-    PCT_HIP(ctx, hipMemcpyAsync(rotated, ctx->stage_b.p, count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    char* d_nbrs = nullptr;          // (bytes: float or double)
+    double* d_rot = nullptr;
+    PCT_TRY(pct_claim_upload(ctx, (const char*)nbrs, count * esz, &d_nbrs));
+    PCT_TRY(pct_claim(ctx, count, &d_rot));
+    PCT_TRY(pct_launch_plane_rotate(ctx, d_nbrs, is_f64 != 0, batch, m, d_rot));
+    PCT_TRY(pct_enqueue_download(ctx, rotated, d_rot, count));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PCT_OK;
 }
 
 int pct_fit_quadric(pct_ctx* ctx, const float* pts, int64_t batch, int32_t m, float* coefs) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     if (!pts || !coefs || batch <= 0 || m < 1 || (double)batch * m > 2.0e9) return pct_fail(ctx, PCT_ERR_INVALID, "bad point block");
     const size_t count = (size_t)batch * m * 3;
     for (size_t i = 0; i < count; ++i)
         if (!isfinite(pts[i])) return pct_fail(ctx, PCT_ERR_NONFINITE, "Input contains non-finite values.");
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_a, count * sizeof(float)));
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_b, (size_t)batch * 6 * sizeof(float)));
-    PCT_HIP(ctx, hipMemcpyAsync(ctx->stage_a.p, pts, count * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    PCT_TRY(pct_launch_quadric_rows(ctx, (const float*)ctx->stage_a.p, batch, m, (float*)ctx->stage_b.p));
-    PCT_HIP(ctx, hipMemcpyAsync(coefs, ctx->stage_b.p, (size_t)batch * 6 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    float *d_pts = nullptr, *d_coefs = nullptr;
+    PCT_TRY(pct_claim_upload(ctx, pts, count, &d_pts));
+    PCT_TRY(pct_claim(ctx, (size_t)batch * 6, &d_coefs));
+    PCT_TRY(pct_launch_quadric_rows(ctx, d_pts, batch, m, d_coefs));
+    PCT_TRY(pct_enqueue_download(ctx, coefs, d_coefs, (size_t)batch * 6));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PCT_OK;
 }
 
 int pct_neighbor_study_curvatures(pct_ctx* ctx, const int64_t* sample_rows, int64_t n_samples, int32_t n_lo, int32_t n_hi,
                                    float* K_out) {
-    PCT_TRY(begin_row_call(ctx, "pct_neighbor_study_curvatures"));
+    PCT_TRY(pct_begin_row_call(ctx, "pct_neighbor_study_curvatures"));
     if (!ctx->res.has(PCT_R_TABLE)) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "plant the neighbour table first (pct_knn)");
     if (!sample_rows || !K_out || n_samples <= 0 || n_lo < 1 || n_hi < n_lo) return pct_fail(ctx, PCT_ERR_INVALID, "bad study arguments");
     if (n_hi > ctx->k) return pct_fail(ctx, PCT_ERR_INVALID, "the study needs %d neighbours per point, the table holds %d", n_hi, ctx->k);
@@ -1434,44 +1412,37 @@ int pct_neighbor_study_curvatures(pct_ctx* ctx, const int64_t* sample_rows, int6
     const int64_t rows = n_samples * nn;
     if (rows > (int64_t)1 << 30) return pct_fail(ctx, PCT_ERR_INVALID, "study too large");
     // sample rows -> positions in the order the table is indexed by
-    int* h_pos = (int*)malloc((size_t)n_samples * sizeof(int));
-    if (!h_pos) return pct_fail(ctx, PCT_ERR_OOM, "host allocation failed");
+    std::vector<int> h_pos((size_t)n_samples);
     for (int64_t i = 0; i < n_samples; ++i) {
-        if (sample_rows[i] < ctx->q_begin || sample_rows[i] >= ctx->q_end) {
-            free(h_pos);
+        if (sample_rows[i] < ctx->q_begin || sample_rows[i] >= ctx->q_end)
             return pct_fail(ctx, PCT_ERR_INVALID, "sample row %lld outside the owned range", (long long)sample_rows[i]);
-        }
-        h_pos[i] = (int)(sample_rows[i] - ctx->q_begin);    // exhaustive table: that is the row; grid table: index into row_of
+        h_pos[(size_t)i] = (int)(sample_rows[i] - ctx->q_begin);    // exhaustive table: that is the row; grid table: index into row_of
     }
     const int32_t pitch = (n_hi + 1 + 3) & ~3;
-    int st = pct_reserve(ctx, &ctx->stage_c, (size_t)n_samples * sizeof(int));
-    if (st == PCT_OK) st = pct_reserve(ctx, &ctx->stage_a, (size_t)rows * pitch * sizeof(int));
-    if (st == PCT_OK) st = pct_reserve(ctx, &ctx->stage_b, (size_t)rows * (sizeof(int) + 9 * sizeof(float)));
-    if (st == PCT_OK) st = pct_reserve(ctx, &ctx->stage_d, (size_t)rows * sizeof(int64_t));
-    if (st != PCT_OK) { free(h_pos); return st; }
-    hipError_t e = hipMemcpyAsync(ctx->stage_c.p, h_pos, (size_t)n_samples * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    free(h_pos);
-    if (e != hipSuccess) return pct_fail(ctx, PCT_ERR_HIP, "sample upload failed: %s", hipGetErrorString(e));
-    int* d_spos = (int*)ctx->stage_c.p;
+    int *d_spos = nullptr, *d_table = nullptr, *d_cnt = nullptr;
+    int64_t* d_row_query = nullptr;
+    PCT_TRY(pct_claim_upload(ctx, h_pos.data(), h_pos.size(), &d_spos));
+    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));               // (the copy is done before the temporary dies, whichever way)
+    PCT_TRY(pct_claim(ctx, (size_t)rows * pitch, &d_table));
+    PCT_TRY(pct_claim(ctx, (size_t)rows * 10, &d_cnt));             // one claim: counts (rows) | coefs (rows, 6), K, H, H2 as float
+    PCT_TRY(pct_claim(ctx, (size_t)rows, &d_row_query));
     if (ctx->knn_sorted_space) {      // public index -> neighbour-table row, on the device
         PCT_TRY(pct_ensure_row_of(ctx));
         PCT_TRY(pct_launch_gather_int(ctx, (const int*)ctx->row_of.p, d_spos, n_samples));
     }
-    int* d_cnt = (int*)ctx->stage_b.p;
+    static_assert(sizeof(int) == sizeof(float), "the packed claim counts both as four-byte words");
     float* d_out = (float*)(d_cnt + rows);            // coefs (rows,6), K, H, H2
-    PCT_TRY(pct_launch_prefix_rows(ctx, d_spos, n_samples, n_lo, n_hi, (int*)ctx->stage_a.p, pitch, d_cnt,
-                                   (int64_t*)ctx->stage_d.p));
-    PCT_TRY(pct_launch_fit_rows(ctx, (const int*)ctx->stage_a.p, d_cnt, (const int64_t*)ctx->stage_d.p, rows, n_hi + 1, pitch,
-                                d_out, d_out + rows * 6, d_out + rows * 7, d_out + rows * 8, ctx->knn_sorted_space));
-    PCT_HIP(ctx, hipMemcpyAsync(K_out, d_out + rows * 6, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    PCT_TRY(pct_launch_prefix_rows(ctx, d_spos, n_samples, n_lo, n_hi, d_table, pitch, d_cnt, d_row_query));
+    PCT_TRY(pct_launch_fit_rows(ctx, d_table, d_cnt, d_row_query, rows, n_hi + 1, pitch, d_out, d_out + rows * 6, d_out + rows * 7,
+                                d_out + rows * 8, ctx->knn_sorted_space));
+    PCT_TRY(pct_enqueue_download(ctx, K_out, (const float*)(d_out + rows * 6), (size_t)rows));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PCT_OK;
 }
 
 int pct_mesh_energies(pct_ctx* ctx, const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles,
                       const void* gaussian, const void* mean, int32_t curvature_is_f64, double* out3) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     if (!vertices || !triangles || !gaussian || !mean || !out3 || n_vertices <= 0 || n_triangles < 0 || curvature_is_f64 < 0 ||
         curvature_is_f64 > PCT_MESH_K32_H64)
         return pct_fail(ctx, PCT_ERR_INVALID, "bad mesh arguments");
@@ -1486,25 +1457,23 @@ int pct_mesh_energies(pct_ctx* ctx, const double* vertices, int64_t n_vertices, 
     const size_t hsz = (size_t)n_vertices * (h_f64 ? sizeof(double) : sizeof(float));
     const size_t h_at = (size_t)n_vertices * sizeof(double);          // H behind room for a float64 K: aligned whatever K is
     const int nblk = (int)((n_triangles + 255) / 256 < 1024 ? (n_triangles + 255) / 256 : 1024);
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_a, (size_t)n_vertices * 3 * sizeof(double)));
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_b, (size_t)n_triangles * 3 * sizeof(int)));
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_c, h_at + hsz));
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_d, ((size_t)nblk * 3 + 3) * sizeof(double)));
-    char* d_kh = (char*)ctx->stage_c.p;
-    PCT_HIP(ctx, hipMemcpyAsync(ctx->stage_a.p, vertices, (size_t)n_vertices * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(ctx->stage_b.p, triangles, (size_t)n_triangles * 3 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    double *d_v = nullptr, *d_part = nullptr;
+    int32_t* d_tri = nullptr;
+    char* d_kh = nullptr;            // one claim: K | H at h_at
+    PCT_TRY(pct_claim_upload(ctx, vertices, (size_t)n_vertices * 3, &d_v));
+    PCT_TRY(pct_claim_upload(ctx, triangles, (size_t)n_triangles * 3, &d_tri));
+    PCT_TRY(pct_claim(ctx, h_at + hsz, &d_kh));
+    PCT_TRY(pct_claim(ctx, (size_t)nblk * 3 + 3, &d_part));
     PCT_HIP(ctx, hipMemcpyAsync(d_kh, gaussian, ksz, hipMemcpyHostToDevice, ctx->stream));
     PCT_HIP(ctx, hipMemcpyAsync(d_kh + h_at, mean, hsz, hipMemcpyHostToDevice, ctx->stream));
-    double* d_part = (double*)ctx->stage_d.p;
-    PCT_TRY(pct_launch_mesh_energies(ctx, (const double*)ctx->stage_a.p, (const int*)ctx->stage_b.p, n_triangles, d_kh,
-                                     d_kh + h_at, k_f64, h_f64, d_part, nblk, d_part + (size_t)nblk * 3));
-    PCT_HIP(ctx, hipMemcpyAsync(out3, d_part + (size_t)nblk * 3, 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    PCT_TRY(pct_launch_mesh_energies(ctx, d_v, d_tri, n_triangles, d_kh, d_kh + h_at, k_f64, h_f64, d_part, nblk, d_part + (size_t)nblk * 3));
+    PCT_TRY(pct_enqueue_download(ctx, out3, d_part + (size_t)nblk * 3, 3));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PCT_OK;
 }
 
 static int voxel_downsample(pct_ctx* ctx, const void* xyz, bool f64, int64_t n, double voxel_size, int64_t* indices, int64_t* count) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     if (!xyz || !indices || !count || n <= 0 || n >= 0x7F000000 || !(voxel_size > 0) || (!f64 && !((float)voxel_size > 0.f)))
         return pct_fail(ctx, PCT_ERR_INVALID, "bad down-sampling arguments");
     for (int64_t i = 0; i < 3 * n; ++i) {
@@ -1513,11 +1482,12 @@ static int voxel_downsample(pct_ctx* ctx, const void* xyz, bool f64, int64_t n, 
             return pct_fail(ctx, PCT_ERR_INVALID, "coordinate %lld does not map to an int32 voxel index", (long long)(i / 3));
     }
     const size_t bytes = (size_t)n * 3 * (f64 ? sizeof(double) : sizeof(float));
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_a, bytes));
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_b, (size_t)n * sizeof(int64_t)));
-    PCT_HIP(ctx, hipMemcpyAsync(ctx->stage_a.p, xyz, bytes, hipMemcpyHostToDevice, ctx->stream));
-    PCT_TRY(pct_voxel_downsample_device(ctx, ctx->stage_a.p, f64, n, voxel_size, (int64_t*)ctx->stage_b.p, count));
-    if (*count > 0) PCT_HIP(ctx, hipMemcpyAsync(indices, ctx->stage_b.p, (size_t)*count * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    char* d_xyz = nullptr;           // (bytes: float or double)
+    int64_t* d_kept = nullptr;
+    PCT_TRY(pct_claim_upload(ctx, (const char*)xyz, bytes, &d_xyz));
+    PCT_TRY(pct_claim(ctx, (size_t)n, &d_kept));
+    PCT_TRY(pct_voxel_downsample_device(ctx, d_xyz, f64, n, voxel_size, d_kept, count));
+    if (*count > 0) PCT_TRY(pct_enqueue_download(ctx, indices, d_kept, (size_t)*count));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PCT_OK;
 }
@@ -1531,7 +1501,7 @@ int pct_voxel_downsample_f32(pct_ctx* ctx, const float* xyz, int64_t n, double v
 }
 
 int pct_surface_variation(pct_ctx* ctx, int32_t k_total, float* out) {
-    PCT_TRY(begin_row_call(ctx, "pct_surface_variation"));
+    PCT_TRY(pct_begin_row_call(ctx, "pct_surface_variation"));
     if (!out || k_total < 2) return pct_fail(ctx, PCT_ERR_INVALID, "bad surface-variation arguments");
     const int64_t rows = ctx->q_end - ctx->q_begin;
     for (int attempt = 0; attempt < 2; ++attempt) {
@@ -1548,7 +1518,7 @@ int pct_surface_variation(pct_ctx* ctx, int32_t k_total, float* out) {
 }
 
 int pct_pca_curvatures(pct_ctx* ctx, int32_t k, int32_t algo, int32_t keep_neighbors, int64_t* exact_rows) {
-    PCT_TRY(begin_row_call(ctx, "pct_pca_curvatures"));
+    PCT_TRY(pct_begin_row_call(ctx, "pct_pca_curvatures"));
     if (ctx->n <= 0) return pct_fail(ctx, PCT_ERR_INVALID, "no cloud loaded");
     if (ctx->q_begin != 0 || ctx->q_end != ctx->n)
         return pct_fail(ctx, PCT_ERR_INVALID, "pct_pca_curvatures answers whole clouds (query range [%lld,%lld) of %lld points)",
@@ -1592,7 +1562,7 @@ int pct_pca_curvatures(pct_ctx* ctx, int32_t k, int32_t algo, int32_t keep_neigh
 
 int pct_get_pca(pct_ctx* ctx, int64_t begin, int64_t end, double* l1, double* l2, double* dirs, double* K, double* H,
                 int32_t* idx) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     if (!ctx->res.has(PCT_R_PCA)) return pct_fail(ctx, PCT_ERR_INVALID, "no PCA frame on this handle (pct_pca_curvatures)");
     const int64_t n = ctx->res.rows_of(PCT_R_PCA), rows = end - begin;
     if (begin < 0 || end > n || begin > end)
@@ -1617,7 +1587,7 @@ int pct_get_timings(const pct_ctx* ctx, pct_timings* out) {
     if (!ctx || !out) return PCT_ERR_INVALID;
     if (ctx->pend.on) {                    // (an asynchronous call: its times exist once its kernels have finished)
         pct_ctx* c = const_cast<pct_ctx*>(ctx);
-        PCT_TRY(begin_call(c));
+        PCT_TRY(pct_begin_call(c));
     }
     *out = ctx->tm;
     return PCT_OK;
@@ -1630,7 +1600,7 @@ int pct_get_timings_done(const pct_ctx* ctx, pct_timings* out) {
 }
 
 int pct_device_alloc(pct_ctx* ctx, int64_t bytes, void** dev_ptr) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     if (!dev_ptr || bytes <= 0) return pct_fail(ctx, PCT_ERR_INVALID, "bad allocation request");
     hipError_t e = hipMalloc(dev_ptr, (size_t)bytes);
     if (e != hipSuccess) return pct_fail(ctx, PCT_ERR_OOM, "hipMalloc(%lld) failed: %s", (long long)bytes, hipGetErrorString(e));
@@ -1638,381 +1608,27 @@ int pct_device_alloc(pct_ctx* ctx, int64_t bytes, void** dev_ptr) {
 }
 
 int pct_device_free(pct_ctx* ctx, void* dev_ptr) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     if (dev_ptr) PCT_HIP(ctx, hipFree(dev_ptr));
     return PCT_OK;
 }
 
 int pct_device_upload(pct_ctx* ctx, void* dev_dst, const void* host_src, int64_t bytes) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     PCT_HIP(ctx, hipMemcpyAsync(dev_dst, host_src, (size_t)bytes, hipMemcpyHostToDevice, ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PCT_OK;
 }
 
 int pct_device_download(pct_ctx* ctx, void* host_dst, const void* dev_src, int64_t bytes) {
-    PCT_TRY(begin_call(ctx));
+    PCT_TRY(pct_begin_call(ctx));
     PCT_HIP(ctx, hipMemcpyAsync(host_dst, dev_src, (size_t)bytes, hipMemcpyDeviceToHost, ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PCT_OK;
 }
 
 int pct_synchronize(pct_ctx* ctx) {
-    PCT_TRY(begin_call(ctx));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PCT_OK;
-}
-
-int pct_selftest(pct_ctx* ctx, int32_t* failures) {
-    PCT_TRY(begin_call(ctx));
-    if (!failures) return pct_fail(ctx, PCT_ERR_INVALID, "null output");
-    PCT_TRY(pct_reserve(ctx, &ctx->red, 64));
-    PCT_HIP(ctx, hipMemsetAsync(ctx->red.p, 0, 64, ctx->stream));
-    PCT_TRY(pct_launch_selftest(ctx, (int*)ctx->red.p));
-    PCT_HIP(ctx, hipMemcpyAsync(failures, ctx->red.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PCT_OK;
-}
-
-}  // extern "C"
-
-// ---- self-tests of the sorters: host arrays in and out, device memory of their own, nothing of the handle's ---------------
-namespace {
-struct DevScratch {                                    // freed when the call returns, whichever way
-    std::vector<void*> held;
-    ~DevScratch() { for (void* p : held) (void)hipFree(p); }
-    template <class T>
-    hipError_t take(T** p, size_t count) {
-        void* v = nullptr;
-        const hipError_t e = hipMalloc(&v, count * sizeof(T));
-        if (e == hipSuccess) held.push_back(v);
-        *p = (T*)v;
-        return e;
-    }
-};
-constexpr int64_t kSelftestMaxLists = 1 << 20;
-
-// public indices as the records carry them: the .w word of a float4
-std::vector<float4> pub_records(const int32_t* pub, int64_t n) {
-    std::vector<float4> r((size_t)n);
-    for (int64_t i = 0; i < n; ++i) {
-        float w;
-        memcpy(&w, &pub[i], 4);
-        r[(size_t)i] = make_float4(0.f, 0.f, 0.f, w);
-    }
-    return r;
-}
-}  // namespace
-
-extern "C" {
-
-int pct_selftest_sort(pct_ctx* ctx, int32_t network, const uint32_t* in, int64_t n_lists, uint32_t* out) {
-    PCT_TRY(begin_call(ctx));
-    const int regs = pct_selftest_sort_regs(network);
-    if (!regs) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sort: no network %d", (int)network);
-    if (!in || !out) return pct_fail(ctx, PCT_ERR_INVALID, "null array");
-    const bool two = network == PCT_NET_SETS1 || network == PCT_NET_SETS2 || network == PCT_NET_PAIR;
-    if (n_lists < 1 || n_lists > kSelftestMaxLists || (two && (n_lists & 1)))
-        return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sort: n_lists = %lld (1 .. 2^20; even where a wave sorts two lists)", (long long)n_lists);
-    const int n_waves = (int)(two ? n_lists / 2 : n_lists);
-    const size_t count = (size_t)n_waves * 64 * regs;
-    DevScratch mem;
-    uint32_t *d_in, *d_out;
-    PCT_HIP(ctx, mem.take(&d_in, count));
-    PCT_HIP(ctx, mem.take(&d_out, count));
-    PCT_HIP(ctx, hipMemcpyAsync(d_in, in, count * 4, hipMemcpyHostToDevice, ctx->stream));
-    PCT_TRY(pct_launch_selftest_sort(ctx, network, d_in, n_waves, d_out));
-    PCT_HIP(ctx, hipMemcpyAsync(out, d_out, count * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PCT_OK;
-}
-
-int pct_selftest_sort_exact(pct_ctx* ctx, int32_t regs, int32_t mode, const double* d2, const int32_t* pos, const double* batch_d2,
-                            const int32_t* batch_pos, const int32_t* pub, int64_t n_pub, int64_t n_lists, double* out_d2, int32_t* out_pos) {
-    PCT_TRY(begin_call(ctx));
-    if (regs != 1 && regs != 2 && regs != 4 && regs != 8) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sort_exact: list registers are 1, 2, 4 or 8, not %d", (int)regs);
-    if (mode != PCT_EXACT_ASCENDING && mode != PCT_EXACT_DESCENDING && mode != PCT_EXACT_MERGE_MIN)
-        return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sort_exact: no mode %d", (int)mode);
-    const bool merge = mode == PCT_EXACT_MERGE_MIN;
-    if (!d2 || !pos || !pub || !out_d2 || !out_pos || (merge && (!batch_d2 || !batch_pos))) return pct_fail(ctx, PCT_ERR_INVALID, "null array");
-    if (n_lists < 1 || n_lists > kSelftestMaxLists || n_pub < 1 || n_pub > (1 << 24)) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sort_exact: n_lists = %lld, n_pub = %lld", (long long)n_lists, (long long)n_pub);
-    const size_t count = (size_t)n_lists * 64 * regs;
-    // the kernels read pub[position] for tied elements: no position may point outside the table
-    for (int pass = 0; pass < (merge ? 2 : 1); ++pass) {
-        const int32_t* p = pass ? batch_pos : pos;
-        for (size_t i = 0; i < count; ++i)
-            if (p[i] != INT32_MAX && (p[i] < 0 || p[i] >= n_pub)) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sort_exact: position %d outside [0, n_pub)", (int)p[i]);
-    }
-    const std::vector<float4> rec = pub_records(pub, n_pub);
-    DevScratch mem;
-    double *d_d2, *d_bd2 = nullptr, *d_od2;
-    int *d_pos, *d_bpos = nullptr, *d_opos;
-    float4* d_pts;
-    PCT_HIP(ctx, mem.take(&d_d2, count));
-    PCT_HIP(ctx, mem.take(&d_pos, count));
-    PCT_HIP(ctx, mem.take(&d_od2, count));
-    PCT_HIP(ctx, mem.take(&d_opos, count));
-    PCT_HIP(ctx, mem.take(&d_pts, rec.size()));
-    PCT_HIP(ctx, hipMemcpyAsync(d_d2, d2, count * 8, hipMemcpyHostToDevice, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(d_pos, pos, count * 4, hipMemcpyHostToDevice, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(d_pts, rec.data(), rec.size() * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
-    if (merge) {
-        PCT_HIP(ctx, mem.take(&d_bd2, count));
-        PCT_HIP(ctx, mem.take(&d_bpos, count));
-        PCT_HIP(ctx, hipMemcpyAsync(d_bd2, batch_d2, count * 8, hipMemcpyHostToDevice, ctx->stream));
-        PCT_HIP(ctx, hipMemcpyAsync(d_bpos, batch_pos, count * 4, hipMemcpyHostToDevice, ctx->stream));
-    }
-    PCT_TRY(pct_launch_selftest_exact(ctx, regs, mode, d_d2, d_pos, d_bd2, d_bpos, d_pts, (int)n_lists, d_od2, d_opos));
-    PCT_HIP(ctx, hipMemcpyAsync(out_d2, d_od2, count * 8, hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(out_pos, d_opos, count * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (rec and the scratch outlive every copy: waited for here)
-    return PCT_OK;
-}
-
-int pct_selftest_order_keys(pct_ctx* ctx, int32_t regs, int32_t slot_bits, const uint32_t* elems, const double* d2, const int32_t* pub,
-                            int64_t n_lists, uint32_t* out, int32_t* done) {
-    PCT_TRY(begin_call(ctx));
-    if (!((regs == 1 && (slot_bits == 6 || slot_bits == 9)) || (regs == 2 && (slot_bits == 7 || slot_bits == 10))))
-        return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_order_keys: (regs, slot_bits) is (1, 6), (1, 9), (2, 7) or (2, 10), not (%d, %d)", (int)regs, (int)slot_bits);
-    if (!elems || !d2 || !pub || !out || !done) return pct_fail(ctx, PCT_ERR_INVALID, "null array");
-    if (n_lists < 1 || n_lists > (1 << 16)) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_order_keys: n_lists = %lld (1 .. 65536)", (long long)n_lists);
-    const size_t count = (size_t)n_lists * 64 * regs, table = (size_t)n_lists << slot_bits;
-    const std::vector<float4> rec = pub_records(pub, (int64_t)table);
-    DevScratch mem;
-    uint32_t *d_e, *d_out;
-    double* d_d2;
-    float4* d_pts;
-    int* d_done;
-    PCT_HIP(ctx, mem.take(&d_e, count));
-    PCT_HIP(ctx, mem.take(&d_out, count));
-    PCT_HIP(ctx, mem.take(&d_d2, table));
-    PCT_HIP(ctx, mem.take(&d_pts, table));
-    PCT_HIP(ctx, mem.take(&d_done, (size_t)n_lists));
-    PCT_HIP(ctx, hipMemcpyAsync(d_e, elems, count * 4, hipMemcpyHostToDevice, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(d_d2, d2, table * 8, hipMemcpyHostToDevice, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(d_pts, rec.data(), table * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
-    PCT_TRY(pct_launch_selftest_order(ctx, regs, slot_bits, d_e, d_d2, d_pts, (int)n_lists, d_out, d_done));
-    PCT_HIP(ctx, hipMemcpyAsync(out, d_out, count * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(done, d_done, (size_t)n_lists * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PCT_OK;
-}
-
-// ---- self-test of the planned fast sweep (tests/test_gpu_select.py): pct_knn's cell list, plan and one launch, no exact sweep ----
-// Unlike the self-tests above this one works on the handle's cloud and in its buffers: the table it leaves is unfinished,
-// so every resident result is dropped, as by a new cloud.
-int pct_selftest_sweep(pct_ctx* ctx, int32_t k, double eps, int32_t algo, int32_t want_dist, int32_t* idx, float* dist, int32_t* count,
-                       uint8_t* flags, double* info) {
-    PCT_TRY(begin_row_call(ctx, "pct_selftest_sweep"));
-    if (!idx || !flags || !info) return pct_fail(ctx, PCT_ERR_INVALID, "null array");
-    if (ctx->n <= 0) return pct_fail(ctx, PCT_ERR_INVALID, "no cloud loaded");
-    if (algo != PCT_KNN_GRID) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sweep: PCT_KNN_GRID only, not algorithm %d", (int)algo);
-    if (k < 1 || k > 127) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sweep: k=%d outside [1,127], the fast sweeps' rows", (int)k);
-    if ((int64_t)k + 1 > ctx->n) return pct_fail(ctx, PCT_ERR_K_TOO_LARGE, "k+1=%d exceeds the cloud size %lld", k + 1, (long long)ctx->n);
-    if (ctx->n > ((int64_t)1 << 24)) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sweep: at most 2^24 points");
-    if (!(eps >= 0) || isinf(eps)) eps = 0;
-    const int64_t rows = ctx->q_end - ctx->q_begin;
-    if (rows <= 0) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sweep: no owned rows");
-    ctx->res.drop(PCT_UNFINISHED_TABLE);
-    ctx->k = k;
-    ctx->eps = eps;
-    pct_call_clock& clock = ctx->clock[0];
-    PCT_TRY(clock.open(ctx, false, true, PCT_CALL_SWEEP_HEAD));
-    PCT_HIP(ctx, clock.start(ctx->stream));
-    ctx->tm.levels = 0;
-    ctx->tm.sweep_variant = 0;
-    ctx->tm.algo = algo;
-    GridVerdict built;
-    PCT_TRY(pct_build_grid(ctx, k, eps, false, &built, &clock, nullptr));
-    if (built != GridVerdict::Built) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sweep: no cell list");
-    PCT_HIP(ctx, clock.boundary(PCT_ST_GRID_END, ctx->stream));
-    // the buffers the launcher reserves, reserved here at the same sizes and filled: a table of -1 (a row the sweep leaves
-    // alone, or marks in its first column only, exports as empty) and a list of kNoEntry (what the sweep did not write shows)
-    constexpr int kNoEntry = 0x7f7f7f7f;
-    const size_t pitch = (size_t)((k + 3) & ~3), list_len = (size_t)rows + 16;
-    PCT_TRY(pct_reserve(ctx, &ctx->nbr_pos, (size_t)rows * pitch * sizeof(int)));
-    PCT_TRY(pct_reserve(ctx, &ctx->nbr_dist, (size_t)rows * pitch * sizeof(float)));
-    PCT_TRY(pct_reserve(ctx, &ctx->nbr_cnt, (size_t)rows * sizeof(int)));
-    PCT_TRY(pct_reserve(ctx, &ctx->redo, list_len * sizeof(int)));
-    PCT_HIP(ctx, hipMemsetAsync(ctx->nbr_pos.p, 0xff, (size_t)rows * pitch * sizeof(int), ctx->stream));
-    PCT_HIP(ctx, hipMemsetAsync(ctx->nbr_dist.p, 0xff, (size_t)rows * pitch * sizeof(float), ctx->stream));
-    PCT_HIP(ctx, hipMemsetAsync(ctx->nbr_cnt.p, 0xff, (size_t)rows * sizeof(int), ctx->stream));
-    PCT_HIP(ctx, hipMemsetAsync(ctx->redo.p, 0x7f, list_len * sizeof(int), ctx->stream));
-    PCT_TRY(pct_launch_knn_grid(ctx, k, eps, false, 3, want_dist != 0, &clock, nullptr));
-    PCT_HIP(ctx, clock.boundary(PCT_ST_SWEEP_END, ctx->stream));
-    // the rows in public order, through the getter's own export
-    const size_t cells = (size_t)rows * k;
-    const bool dist_kept = ctx->dist_valid;
-    PCT_TRY(pct_ensure_row_of(ctx));
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_a, cells * sizeof(int)));
-    if (dist && dist_kept) PCT_TRY(pct_reserve(ctx, &ctx->stage_b, cells * sizeof(float)));
-    if (count) PCT_TRY(pct_reserve(ctx, &ctx->stage_c, (size_t)rows * sizeof(int)));
-    PCT_TRY(pct_launch_export_neighbors(ctx, ctx->q_begin, ctx->q_end, (int*)ctx->stage_a.p, dist && dist_kept ? (float*)ctx->stage_b.p : nullptr,
-                                        count ? (int*)ctx->stage_c.p : nullptr));
-    std::vector<int> list(list_len), row_of((size_t)rows);
-    int redo_count = -1;
-    PCT_HIP(ctx, hipMemcpyAsync(idx, ctx->stage_a.p, cells * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    if (dist && dist_kept) PCT_HIP(ctx, hipMemcpyAsync(dist, ctx->stage_b.p, cells * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (count) PCT_HIP(ctx, hipMemcpyAsync(count, ctx->stage_c.p, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(list.data(), ctx->redo.p, list_len * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(row_of.data(), ctx->row_of.p, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(&redo_count, &pct_dev(ctx)->sweep.redo_count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (size_t i = 0; i < cells; ++i)
-        if (idx[i] >= ctx->n) idx[i] = -1;                 // (the export's "no neighbour" is n)
-    // the redo list as it is: its entries are the leading ones, as many as the counter says, each row once
-    size_t written = 0;
-    for (size_t i = 0; i < list_len; ++i) written += list[i] != kNoEntry;
-    if (redo_count < 0 || (int64_t)redo_count > rows || written != (size_t)redo_count)
-        return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sweep: the redo list holds %zu entries, redo_count says %d", written, redo_count);
-    const unsigned trusted_bit = pct_redo_trusted_bit();
-    std::vector<uint8_t> by_row((size_t)rows, 0);
-    for (int i = 0; i < redo_count; ++i) {
-        if (list[(size_t)i] == kNoEntry) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sweep: entry %d of %d of the redo list was not written", i, redo_count);
-        const unsigned e = (unsigned)list[(size_t)i], row = e & ~trusted_bit;
-        if ((int64_t)row >= rows) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sweep: redo entry %d names row %u of %lld", i, row, (long long)rows);
-        if (by_row[row]) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sweep: row %u is on the redo list twice", row);
-        by_row[row] = (uint8_t)(1 | ((e & trusted_bit) ? 2 : 0));
-    }
-    for (int64_t i = 0; i < rows; ++i) {
-        if (row_of[(size_t)i] < 0 || row_of[(size_t)i] >= rows) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_sweep: no table row for public index %lld", (long long)(ctx->q_begin + i));
-        flags[i] = by_row[(size_t)row_of[(size_t)i]];
-    }
-    const pct_grid& g = ctx->grid;
-    const double words[12] = {(double)ctx->tm.sweep_variant, (double)redo_count, g.cell, (double)g.nx, (double)g.ny, (double)g.nz, g.ox, g.oy, g.oz,
-                              dist_kept ? 1.0 : 0.0, (double)ctx->items_q, (double)ctx->n_items};
-    memcpy(info, words, sizeof(words));
-    return PCT_OK;
-}
-
-// ---- self-tests of the chained sweep's planning kernels (pct_levels.hip): as above, host arrays in and out ----------------------
-int pct_selftest_levels_classify(pct_ctx* ctx, const int32_t* row_done, const uint32_t* redo_m, const int32_t* pub, int64_t n_rows,
-                                 int64_t n_pub, float log_edge, float target, float* want, float* bracket) {
-    PCT_TRY(begin_call(ctx));
-    if (!row_done || !redo_m || !pub || !want || !bracket) return pct_fail(ctx, PCT_ERR_INVALID, "null array");
-    if (n_rows < 1 || n_rows > ((int64_t)1 << 22) || n_pub < n_rows || n_pub > ((int64_t)1 << 24))
-        return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_levels_classify: n_rows = %lld (1 .. 2^22), n_pub = %lld (n_rows .. 2^24)", (long long)n_rows, (long long)n_pub);
-    // the kernel writes want[pub] and bracket[pub] of every row: each public index inside the arrays, and once
-    std::vector<char> seen((size_t)n_pub, 0);
-    for (int64_t i = 0; i < n_rows; ++i) {
-        if (pub[i] < 0 || pub[i] >= n_pub || seen[(size_t)pub[i]]) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_levels_classify: public index %d outside [0, n_pub) or twice", (int)pub[i]);
-        seen[(size_t)pub[i]] = 1;
-    }
-    // row i is the query at position n_rows - 1 - i of the cell order: neither lookup is the identity
-    std::vector<float4> rec((size_t)n_rows);
-    std::vector<int> owned((size_t)n_rows);
-    for (int64_t i = 0; i < n_rows; ++i) {
-        float w;
-        memcpy(&w, &pub[i], 4);
-        owned[(size_t)i] = (int)(n_rows - 1 - i);
-        rec[(size_t)(n_rows - 1 - i)] = make_float4(0.f, 0.f, 0.f, w);
-    }
-    DevScratch mem;
-    int *d_done, *d_redo, *d_owned;
-    float4* d_rec;
-    float *d_want, *d_br;
-    PCT_HIP(ctx, mem.take(&d_done, (size_t)n_rows));
-    PCT_HIP(ctx, mem.take(&d_redo, (size_t)n_rows));
-    PCT_HIP(ctx, mem.take(&d_owned, (size_t)n_rows));
-    PCT_HIP(ctx, mem.take(&d_rec, (size_t)n_rows));
-    PCT_HIP(ctx, mem.take(&d_want, (size_t)n_pub));
-    PCT_HIP(ctx, mem.take(&d_br, (size_t)n_pub * 2));
-    PCT_HIP(ctx, hipMemcpyAsync(d_done, row_done, (size_t)n_rows * 4, hipMemcpyHostToDevice, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(d_redo, redo_m, (size_t)n_rows * 4, hipMemcpyHostToDevice, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(d_owned, owned.data(), (size_t)n_rows * 4, hipMemcpyHostToDevice, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(d_rec, rec.data(), (size_t)n_rows * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(d_want, want, (size_t)n_pub * 4, hipMemcpyHostToDevice, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(d_br, bracket, (size_t)n_pub * 8, hipMemcpyHostToDevice, ctx->stream));
-    PCT_TRY(pct_launch_selftest_levels_classify(ctx, d_done, d_redo, n_rows, d_rec, d_owned, log_edge, target, d_want, d_br));
-    PCT_HIP(ctx, hipMemcpyAsync(want, d_want, (size_t)n_pub * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(bracket, d_br, (size_t)n_pub * 8, hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (rec, owned and the scratch outlive every copy: waited for here)
-    return PCT_OK;
-}
-
-int pct_selftest_levels_bands(pct_ctx* ctx, const float* want, const float* xyz, int64_t n, int64_t begin, int64_t end, float log_edge0,
-                              int32_t window, float lo, float hi, uint32_t* hist, uint32_t* exact, float* bounds, float* box, uint32_t* count) {
-    PCT_TRY(begin_call(ctx));
-    if (!want || !xyz || !hist || !exact || !bounds || !box || !count) return pct_fail(ctx, PCT_ERR_INVALID, "null array");
-    if (n < 1 || n > ((int64_t)1 << 24) || begin < 0 || begin > end || end > n)
-        return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_levels_bands: n = %lld (1 .. 2^24), [begin, end) = [%lld, %lld) inside it", (long long)n, (long long)begin, (long long)end);
-    if (window < -1 || window > 156) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_levels_bands: window = %d (-1: lo and hi as given; 0 .. 156)", (int)window);
-    constexpr int kStatWords = 162, kBoxWords = 7;
-    DevScratch mem;
-    float *d_want, *d_xyz;
-    unsigned* d_stats;
-    int* d_box;
-    PCT_HIP(ctx, mem.take(&d_want, (size_t)n));
-    PCT_HIP(ctx, mem.take(&d_xyz, (size_t)n * 3));
-    PCT_HIP(ctx, mem.take(&d_stats, (size_t)kStatWords));
-    PCT_HIP(ctx, mem.take(&d_box, (size_t)kBoxWords));
-    PCT_HIP(ctx, hipMemcpyAsync(d_want, want, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(d_xyz, xyz, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream));
-    PCT_TRY(pct_launch_selftest_levels_bands(ctx, d_want, d_xyz, begin, end, log_edge0, window, lo, hi, d_stats, bounds, d_box));
-    unsigned h_stats[kStatWords];
-    int h_box[kBoxWords];
-    PCT_HIP(ctx, hipMemcpyAsync(h_stats, d_stats, sizeof(h_stats), hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(h_box, d_box, sizeof(h_box), hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(hist, h_stats, 160 * sizeof(uint32_t));
-    *exact = h_stats[160];
-    for (int a = 0; a < 6; ++a) box[a] = pct_levels_box_float(h_box[a]);
-    *count = (uint32_t)h_box[6];
-    return PCT_OK;
-}
-
-int pct_selftest_levels_merge(pct_ctx* ctx, const int32_t* pub, int64_t n_pos, const int32_t* owned_pos, int32_t q_begin, const int32_t* nbr_pos,
-                              const float* nbr_dist, const int32_t* nbr_cnt, const int32_t* row_done, int64_t n_rows, int32_t k, int32_t pitch,
-                              int64_t n_out, int32_t* pub_pos, float* pub_dist, int32_t* pub_cnt, float* want, int64_t n_want) {
-    PCT_TRY(begin_call(ctx));
-    if (!pub || !owned_pos || !nbr_pos || !nbr_dist || !row_done || !pub_pos || !pub_dist || !want) return pct_fail(ctx, PCT_ERR_INVALID, "null array");
-    if (n_pos < 1 || n_pos > ((int64_t)1 << 24) || n_rows < 1 || n_rows > ((int64_t)1 << 20) || k < 1 || pitch < k || pitch > 512 || n_out < 1 ||
-        n_out > ((int64_t)1 << 22) || n_want < 1 || n_want > ((int64_t)1 << 24) || q_begin < 0)
-        return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_levels_merge: n_pos = %lld, n_rows = %lld, k = %d, pitch = %d, n_out = %lld, n_want = %lld, q_begin = %d",
-                        (long long)n_pos, (long long)n_rows, (int)k, (int)pitch, (long long)n_out, (long long)n_want, (int)q_begin);
-    // every address the kernel forms from the caller's numbers lies inside the caller's arrays
-    for (int64_t r = 0; r < n_rows; ++r) {
-        if (owned_pos[r] < 0 || owned_pos[r] >= n_pos) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_levels_merge: owned position %d outside [0, n_pos)", (int)owned_pos[r]);
-        const int64_t p = pub[owned_pos[r]];
-        if (p < q_begin || p - q_begin >= n_out || p >= n_want) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_levels_merge: public index %lld outside the output rows or the wanted edges", (long long)p);
-        for (int j = 0; j < k; ++j)
-            if (nbr_pos[r * pitch + j] >= n_pos) return pct_fail(ctx, PCT_ERR_INVALID, "pct_selftest_levels_merge: neighbour position %d outside [0, n_pos)", (int)nbr_pos[r * pitch + j]);
-    }
-    const std::vector<float4> rec = pub_records(pub, n_pos);
-    const size_t in_cells = (size_t)n_rows * pitch, out_cells = (size_t)n_out * pitch;
-    DevScratch mem;
-    float4* d_rec;
-    int *d_owned, *d_npos, *d_ncnt = nullptr, *d_done, *d_ppos, *d_pcnt = nullptr;
-    float *d_ndist, *d_pdist, *d_want;
-    PCT_HIP(ctx, mem.take(&d_rec, rec.size()));
-    PCT_HIP(ctx, mem.take(&d_owned, (size_t)n_rows));
-    PCT_HIP(ctx, mem.take(&d_done, (size_t)n_rows));
-    PCT_HIP(ctx, mem.take(&d_npos, in_cells));
-    PCT_HIP(ctx, mem.take(&d_ndist, in_cells));
-    PCT_HIP(ctx, mem.take(&d_ppos, out_cells));
-    PCT_HIP(ctx, mem.take(&d_pdist, out_cells));
-    PCT_HIP(ctx, mem.take(&d_want, (size_t)n_want));
-    PCT_HIP(ctx, hipMemcpyAsync(d_rec, rec.data(), rec.size() * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(d_owned, owned_pos, (size_t)n_rows * 4, hipMemcpyHostToDevice, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(d_done, row_done, (size_t)n_rows * 4, hipMemcpyHostToDevice, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(d_npos, nbr_pos, in_cells * 4, hipMemcpyHostToDevice, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(d_ndist, nbr_dist, in_cells * 4, hipMemcpyHostToDevice, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(d_ppos, pub_pos, out_cells * 4, hipMemcpyHostToDevice, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(d_pdist, pub_dist, out_cells * 4, hipMemcpyHostToDevice, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(d_want, want, (size_t)n_want * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (nbr_cnt) {
-        PCT_HIP(ctx, mem.take(&d_ncnt, (size_t)n_rows));
-        PCT_HIP(ctx, hipMemcpyAsync(d_ncnt, nbr_cnt, (size_t)n_rows * 4, hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (pub_cnt) {
-        PCT_HIP(ctx, mem.take(&d_pcnt, (size_t)n_out));
-        PCT_HIP(ctx, hipMemcpyAsync(d_pcnt, pub_cnt, (size_t)n_out * 4, hipMemcpyHostToDevice, ctx->stream));
-    }
-    PCT_TRY(pct_launch_selftest_levels_merge(ctx, d_rec, d_owned, q_begin, d_npos, d_ndist, d_ncnt, d_done, n_rows, k, pitch, d_ppos, d_pdist, d_pcnt, d_want));
-    PCT_HIP(ctx, hipMemcpyAsync(pub_pos, d_ppos, out_cells * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(pub_dist, d_pdist, out_cells * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (pub_cnt) PCT_HIP(ctx, hipMemcpyAsync(pub_cnt, d_pcnt, (size_t)n_out * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipMemcpyAsync(want, d_want, (size_t)n_want * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PCT_TRY(pct_begin_call(ctx));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PCT_OK;
 }

@@ -397,12 +397,14 @@ int pct_launch_ball(pct_ctx* ctx, bool grid, const double* d_q, int64_t m, const
                     auto end = rocprim::make_transform_iterator((const int64_t*)d_off + r0 + 1, RelOffset{base});
                     size_t tmp_bytes = 0;
                     PCT_HIP(ctx, rocprim::segmented_radix_sort_keys(nullptr, tmp_bytes, in, out, (unsigned)size, (unsigned)(r1 - r0), begin, end, 0, bits, ctx->stream));
-                    PCT_TRY(pct_reserve(ctx, &ctx->stage_c, tmp_bytes));
-                    PCT_HIP(ctx, rocprim::segmented_radix_sort_keys(ctx->stage_c.p, tmp_bytes, in, out, (unsigned)size, (unsigned)(r1 - r0), begin, end, 0, bits, ctx->stream));
+                    pct_stage_scope stage(ctx);            // (every chunk's scratch in the same slot)
+                    char* tmp = nullptr;
+                    PCT_TRY(pct_claim(ctx, tmp_bytes, &tmp));
+                    PCT_HIP(ctx, rocprim::segmented_radix_sort_keys(tmp, tmp_bytes, in, out, (unsigned)size, (unsigned)(r1 - r0), begin, end, 0, bits, ctx->stream));
                 }
                 r0 = r1;
             }
-            const pct_buf t = ctx->ball_idx; ctx->ball_idx = ctx->ball_alt; ctx->ball_alt = t;
+            ctx->ball_idx.swap(ctx->ball_alt);
         }
     }
     if (sorted && want_dist && total > 0) {

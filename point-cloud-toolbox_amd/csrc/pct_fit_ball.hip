@@ -329,16 +329,15 @@ int pct_launch_fit_ball(pct_ctx* ctx, const int* d_self32, int64_t rows, int* d_
 
     // scratch: words (64 B) | wave list (rows) | flag list (rows) | counts (rows);  the table apart
     const size_t row_ints = ((size_t)rows + 15) & ~(size_t)15;
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_b, 64 + 3 * row_ints * sizeof(int)));
-    int* words = (int*)ctx->stage_b.p;           // [0] listed rows, [1] table rows, [2] flagged rows
+    pct_stage_scope stage(ctx);
+    int* words = nullptr;                        // [0] listed rows, [1] table rows, [2] flagged rows
+    PCT_TRY(pct_claim(ctx, 16 + 3 * row_ints, &words));
     int* list = words + 16;
     int* flag_list = list + row_ints;
     int* cnt = flag_list + row_ints;
-    int* table = nullptr;
-    if (with_table) {
-        PCT_TRY(pct_reserve(ctx, &ctx->stage_a, (size_t)ball_fit_table_bytes(rows, short_max)));
-        table = (int*)ctx->stage_a.p;
-    }
+    char* table_bytes = nullptr;
+    if (with_table) PCT_TRY(pct_claim(ctx, (size_t)ball_fit_table_bytes(rows, short_max), &table_bytes));
+    int* table = (int*)table_bytes;
     PCT_HIP(ctx, hipMemsetAsync(words, 0, 64, ctx->stream));
 
     b.f.out_by_row = 1;

@@ -75,9 +75,18 @@ struct pct_grid {
     double lim_lo[3], lim_hi[3];
 };
 
+// One device allocation and its only owner: it frees itself, cannot be copied, and changes hands by swap alone.
+struct pct_buf;
+void pct_release(pct_buf* b);              // frees early what the destructor would free
 struct pct_buf {
     void* p = nullptr;
     size_t cap = 0;
+    pct_buf() = default;
+    pct_buf(const pct_buf&) = delete;
+    pct_buf& operator=(const pct_buf&) = delete;
+    pct_buf(pct_buf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }     // (a std::vector of them may grow)
+    ~pct_buf() { pct_release(this); }
+    void swap(pct_buf& o) { void* const q = p; const size_t c = cap; p = o.p; cap = o.cap; o.p = q; o.cap = c; }
 };
 
 // The two word blocks a step's kernels and its host side talk through are laid out here and nowhere else.
@@ -150,6 +159,8 @@ enum OrientWord {                          // int words of pct_orient.hip's cont
     OW_PULLS, OW_LABELLED, OW_VALID, OW_TOGGLED, OW_PUSH_DONE, OW_COUNT
 };
 static_assert(OW_COUNT <= 16, "pct_pinned::orient_words");
+
+constexpr int kPctStageSlots = 4;   // pct_ctx::stage, where the chain of claims that sets the count is named
 
 struct pct_comm;            // RCCL communicator + exchange stream (pct_comm.hip); null on a single-GPU handle
 
@@ -291,8 +302,14 @@ struct pct_ctx {
                                    // rows of a pct_fit_indices call; kept apart from the table, which helpers may drop
 
     pct_buf fit_flag;   // int: [0] number of rows k_fit handed to k_fit_svd, [16..] the rows
-    // staging for downloads / host-index fits
-    pct_buf stage_a, stage_b, stage_c, stage_d;
+    // Staging scratch of a call, claimed in stack order and never named (pct_claim and pct_stage_scope, below).
+    // The reuse rule: a slot given back by a scope may be claimed again while kernels that read it are still queued.  Safe
+    // only because EVERY write to a slot is an operation on ctx->stream (and pct_reserve waits for the stream before it
+    // moves a buffer): nothing may write a slot any other way -- no blocking hipMemcpy, no other stream.
+    // kPctStageSlots is the deepest chain of claims: pct_fit_ball holds two (centres, member counts) while its launcher
+    // holds two more; pct_get_neighbor_rows, pct_mesh_energies, the study and pct_fit_indices_f64 reach four on their own.
+    pct_buf stage[kPctStageSlots];
+    int stage_top = 0;
     pct_buf qpts4;      // float4 {x,y,z,index} of EVERY point in public order, for pct_query_points (built on first use)
     bool qpts4_valid = false;
     // pct_query_points_algo (pct_query.hip): scratch of a query through the cell list -- its words, the queries' cell ids
@@ -407,10 +424,6 @@ inline double pct_default_factor(int k) {
     if (n > 128) return 0.35;                         // wave-per-query exact sweep only: ~3 (k+1) candidates in the 27 cells of a surface
     return n <= 85 ? 0.52 : n <= 101 ? 0.52 - 0.07 * (n - 85) / 16.0 : 0.45 - 0.05 * (n - 101) / 27.0;
 }
-int pct_reserve(pct_ctx* ctx, pct_buf* b, size_t bytes);
-int pct_reserve_fit(pct_ctx* ctx, int64_t rows);     // the handle's fit results (ctx->coefs, K, H, H2) for `rows` rows
-inline pct_dev_words* pct_dev(pct_ctx* ctx) { return (pct_dev_words*)ctx->counters.p; }     // after pct_reserve(&ctx->counters, sizeof(pct_dev_words))
-void pct_release(pct_buf* b);
 
 // Morton codes of the hierarchical cell list: 21 bits per axis, x in bit 0 of every triple
 __host__ __device__ inline unsigned long long pct_spread3(unsigned v) {         // bit i -> bit 3 i
@@ -475,6 +488,38 @@ __device__ inline int64_t pct_code_lower_bound(const unsigned long long* __restr
         int s_ = (expr);         \
         if (s_ != PCT_OK) return s_; \
     } while (0)
+
+int pct_reserve(pct_ctx* ctx, pct_buf* b, size_t bytes);
+int pct_reserve_fit(pct_ctx* ctx, int64_t rows);     // the handle's fit results (ctx->coefs, K, H, H2) for `rows` rows
+inline pct_dev_words* pct_dev(pct_ctx* ctx) { return (pct_dev_words*)ctx->counters.p; }     // after pct_reserve(&ctx->counters, sizeof(pct_dev_words))
+// The call's staging slots (pct_ctx::stage has the rules).  Every helper counts elements of T and enqueues on ctx->stream;
+// who: the claimant, for the error that refuses a claim past the last slot -- the caller's name unless given.
+int pct_claim_bytes(pct_ctx* ctx, size_t bytes, void** out, const char* who);        // the lowest unclaimed slot, reserved to `bytes`
+struct pct_stage_scope {                   // what is claimed while it lives is given back when it dies
+    pct_ctx* const ctx;
+    const int mark;
+    explicit pct_stage_scope(pct_ctx* c) : ctx(c), mark(c->stage_top) {}
+    ~pct_stage_scope() { ctx->stage_top = mark; }
+};
+template <class T>
+int pct_claim(pct_ctx* ctx, size_t count, T** out, const char* who = __builtin_FUNCTION()) {
+    return pct_claim_bytes(ctx, count * sizeof(T), (void**)out, who);
+}
+template <class T>                         // ... filled with the host array, which must outlive the copy
+int pct_claim_upload(pct_ctx* ctx, const T* host, size_t count, T** out, const char* who = __builtin_FUNCTION()) {
+    PCT_TRY(pct_claim(ctx, count, out, who));
+    PCT_HIP(ctx, hipMemcpyAsync(*out, host, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    return PCT_OK;
+}
+template <class T>                         // count elements to the host; host == null: not asked for
+int pct_enqueue_download(pct_ctx* ctx, T* host, const T* dev, size_t count) {
+    if (host && count) PCT_HIP(ctx, hipMemcpyAsync(host, dev, count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+    return PCT_OK;
+}
+// pct_api.hip: the first statement of every entry point (device, error text, the pending asynchronous call, no staging
+// claimed), and of those a slab handle refuses (the header's list under "Ownership": its rows are not rows by index)
+int pct_begin_call(pct_ctx* ctx, bool wait_for_pending = true);
+int pct_begin_row_call(pct_ctx* ctx, const char* what);
 
 // What one call asks of another, and what it answers, travels in arguments and results -- never parked on the handle.
 // Which pinned parity slot (statistics mirror, SVD row count) the fits of a call write, and whether its fit kernel may
@@ -570,7 +615,8 @@ int pct_launch_gather_int(pct_ctx* ctx, const int* d_map, int* d_inout, int64_t 
 // pct_rows.hip.  One column of a per-row result on its way to the host: where row 0 lies on the device, the bytes of a row,
 // the caller's array (null: not asked for).  pct_download_columns: rows [first, first + rows) of every column asked for,
 // one copy each (one for a run of columns adjacent on both sides) and one wait; map (null: the rows lie in the order asked
-// for) names the stored row of every row -- then at most kPctRowColumns columns, gathered by one kernel into stage_a first.
+// for) names the stored row of every row -- then at most kPctRowColumns columns, gathered by one kernel into a staging claim
+// of its own first.
 // pct_enqueue_columns: without the wait.
 struct pct_column { const void* base; int bytes; void* host; };
 constexpr int kPctRowColumns = 4;

@@ -152,9 +152,6 @@ float order_to_float(int i) {
     return f;
 }
 
-template <class T>
-void swap_buf(T& a, T& b) { T t = a; a = b; b = t; }
-
 // The launches of the rule's kernels with the grid sizes of the chain: pct_knn_levels and the self-test entries
 // (pct_launch_selftest_levels_*) both go through these, so the self-tests run what the chain runs.
 int launch_classify(pct_ctx* ctx, const int* row_done, const int* redo_m, int64_t n_rows, const float4* sorted4, const int* owned_pos,
@@ -249,7 +246,9 @@ int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps, const int* fuse_par, pct
     if (eps > 0) PCT_TRY(pct_reserve(ctx, &ctx->pub_cnt, (size_t)nq * sizeof(int)));
     PCT_TRY(pct_reserve(ctx, &ctx->flag_buf, (size_t)ctx->n * sizeof(float)));
     PCT_TRY(pct_reserve(ctx, &ctx->dens_buf, (size_t)ctx->n * sizeof(float2)));
-    PCT_TRY(pct_reserve(ctx, &ctx->stage_d, sizeof(BandStats) + 64));
+    pct_stage_scope stage(ctx);      // the band statistics, for all the passes
+    char* d_bands = nullptr;
+    PCT_TRY(pct_claim(ctx, sizeof(BandStats) + 64, &d_bands));
     PCT_LAUNCH(k_init_want, dim3((unsigned)((ctx->n + 255) / 256)), dim3(256), 0, ctx->stream, (float*)ctx->flag_buf.p,
                        (float2*)ctx->dens_buf.p, ctx->n);
     PCT_HIP(ctx, hipGetLastError());
@@ -263,8 +262,8 @@ int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps, const int* fuse_par, pct
     pass.want = (const float*)ctx->flag_buf.p;
     float band_box[6];               // of the owned points of a banded pass
     const float log_edge0 = (float)log2(ctx->grid.cell);
-    BandStats* d_st = (BandStats*)ctx->stage_d.p;
-    int* d_box = (int*)((char*)ctx->stage_d.p + sizeof(BandStats));        // 6 ints + count
+    BandStats* d_st = (BandStats*)d_bands;
+    int* d_box = (int*)(d_bands + sizeof(BandStats));        // 6 ints + count
     BandStats st;
     int64_t pending = 0;
     for (;;) {
@@ -302,9 +301,9 @@ int pct_knn_levels(pct_ctx* ctx, int32_t k, double eps, const int* fuse_par, pct
         PCT_TRY(run_pass(pending, true));
     }
     // the merged table takes the place of the pass table: public space, as after the exhaustive sweep
-    swap_buf(ctx->nbr_pos, ctx->pub_pos);
-    swap_buf(ctx->nbr_dist, ctx->pub_dist);
-    if (eps > 0) swap_buf(ctx->nbr_cnt, ctx->pub_cnt);
+    ctx->nbr_pos.swap(ctx->pub_pos);
+    ctx->nbr_dist.swap(ctx->pub_dist);
+    if (eps > 0) ctx->nbr_cnt.swap(ctx->pub_cnt);
     ctx->nbr_pitch = pitch;
     ctx->knn_sorted_space = false;
     ctx->tm.levels = passes;

@@ -440,8 +440,7 @@ int pct_build_tree(pct_ctx* ctx, int32_t k, double eps, const float* expect_bbox
             PCT_TRY(pct_reserve(ctx, &bigger, room * 27 * sizeof(int2)));
             PCT_HIP(ctx, hipMemcpyAsync(bigger.p, ctx->tree_runs.p, (size_t)n_segs * 27 * sizeof(int2), hipMemcpyDeviceToDevice, ctx->stream));
             PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            pct_release(&ctx->tree_runs);
-            ctx->tree_runs = bigger;
+            ctx->tree_runs.swap(bigger);       // (the smaller table is freed with `bigger`)
         }
         const int64_t waves = n_segs;
         const int blocks = (int)((waves + 3) / 4 < 8192 ? (waves + 3) / 4 : 8192);
