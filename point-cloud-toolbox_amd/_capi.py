@@ -641,15 +641,22 @@ class Handle:
         self._check(self._lib.pct_get_point_areas(self._h, int(begin), int(end), _ptr(a, _f64p), _ptr(c, _u8p), _ptr(n, _i32p)))
         return a, c, n
 
+    def _stage_stats(self, call, counters, ms_names=("ms",)):
+        """What a surface stage's statistics getters answer, as one dict: ``call(out, ms)`` fills an int64 and a float64
+        array through them; ``counters`` names the leading words of the one, ``ms_names`` those of the other."""
+        out, ms = np.zeros(8, np.int64), np.zeros(3, np.float64)
+        call(out, ms)
+        return {**{k: int(v) for k, v in zip(counters, out)}, **{k: float(v) for k, v in zip(ms_names, ms)}}
+
     def point_area_stats(self):
         """Of the last ``point_areas``: {rows, closed, nan, overflow (rows redone with room for k + 4 vertices), ms (device
         time of its kernels), survivors (neighbours that passed the rejection test, summed over the rows)}."""
-        out = np.zeros(4, np.int64)
-        self._check(self._lib.pct_point_area_stats(self._h, _ptr(out, _i64p)))
-        prof = np.zeros(2, np.float64)
-        self._check(self._lib.pct_point_area_profile(self._h, _ptr(prof, _f64p)))
-        return {"rows": int(out[0]), "closed": int(out[1]), "nan": int(out[2]), "overflow": int(out[3]),
-                "ms": float(prof[0]), "survivors": int(prof[1])}
+        def call(out, ms):
+            self._check(self._lib.pct_point_area_stats(self._h, _ptr(out, _i64p)))
+            self._check(self._lib.pct_point_area_profile(self._h, _ptr(ms, _f64p)))
+        d = self._stage_stats(call, ("rows", "closed", "nan", "overflow"), ("ms", "survivors"))
+        d["survivors"] = int(d["survivors"])         # (a count that travels as a double)
+        return d
 
     # -- surface frames from the resident fit: fitted normals, k1 / k2 and their directions ---------------------------
     def point_frames(self, viewpoint=None):
@@ -672,10 +679,8 @@ class Handle:
 
     def point_frame_stats(self):
         """Of the last ``point_frames``: {rows, nan, flipped, umbilic, ms (device time of its kernel)}."""
-        out = np.zeros(4, np.int64)
-        ms = np.zeros(1, np.float64)
-        self._check(self._lib.pct_point_frame_stats(self._h, _ptr(out, _i64p), _ptr(ms, _f64p)))
-        return {"rows": int(out[0]), "nan": int(out[1]), "flipped": int(out[2]), "umbilic": int(out[3]), "ms": float(ms[0])}
+        return self._stage_stats(lambda out, ms: self._check(self._lib.pct_point_frame_stats(self._h, _ptr(out, _i64p), _ptr(ms, _f64p))),
+                                 ("rows", "nan", "flipped", "umbilic"))
 
     # -- consistent orientation of those frames: a flood over the resident table --------------------------------------------
     def orient_frames(self, anchor="top", viewpoint=None, max_components=None):
@@ -699,11 +704,8 @@ class Handle:
 
     def orient_stats(self):
         """Of the last ``orient_frames``: {valid, components, unlabelled, toggled, levels, pulls, launches, waits, ms}."""
-        out = np.zeros(8, np.int64)
-        ms = np.zeros(1, np.float64)
-        self._check(self._lib.pct_orient_stats(self._h, _ptr(out, _i64p), _ptr(ms, _f64p)))
-        names = ("valid", "components", "unlabelled", "toggled", "levels", "pulls", "launches", "waits")
-        return {**{k: int(v) for k, v in zip(names, out)}, "ms": float(ms[0])}
+        return self._stage_stats(lambda out, ms: self._check(self._lib.pct_orient_stats(self._h, _ptr(out, _i64p), _ptr(ms, _f64p))),
+                                 ("valid", "components", "unlabelled", "toggled", "levels", "pulls", "launches", "waits"))
 
     # -- faces from the tangent-plane Voronoi cells (include/pct_hip_surface.h) ----------------------------------------------
     def point_triangles(self, wind_frames=False, flags=0):
@@ -726,13 +728,11 @@ class Handle:
     def point_triangle_stats(self):
         """Of the last ``point_triangles``: {rows, rows_with_corner, corners, triangles, wide_rows, largest_fan,
         boundary_edges, ms, fan_ms, agree_ms (device times: the call, its fan kernels, agreement and emission)}."""
-        out = np.zeros(8, np.int64)
-        ms = np.zeros(1, np.float64)
-        self._check(self._lib.pct_point_triangle_stats(self._h, _ptr(out, _i64p), _ptr(ms, _f64p)))
-        prof = np.zeros(2, np.float64)
-        self._check(self._lib.pct_point_triangle_profile(self._h, _ptr(prof, _f64p)))
-        names = ("rows", "rows_with_corner", "corners", "triangles", "wide_rows", "largest_fan", "boundary_edges")
-        return {**{k: int(v) for k, v in zip(names, out)}, "ms": float(ms[0]), "fan_ms": float(prof[0]), "agree_ms": float(prof[1])}
+        def call(out, ms):
+            self._check(self._lib.pct_point_triangle_stats(self._h, _ptr(out, _i64p), _ptr(ms, _f64p)))
+            self._check(self._lib.pct_point_triangle_profile(self._h, _ptr(ms[1:], _f64p)))
+        return self._stage_stats(call, ("rows", "rows_with_corner", "corners", "triangles", "wide_rows", "largest_fan", "boundary_edges"),
+                                 ("ms", "fan_ms", "agree_ms"))
 
     def get_triangles(self, first=0, count=None):
         """(count, 3) int32 public indices, ascending by (v0, v1, v2); by default all of them."""
@@ -752,11 +752,8 @@ class Handle:
     def fill_hole_stats(self):
         """Of the last ``fill_holes``: {boundary_edges (before), gaps, odd_gaps, loops, filled, perimeter, blocked,
         patch_triangles, ms (device time of the call)}."""
-        out = np.zeros(8, np.int64)
-        ms = np.zeros(1, np.float64)
-        self._check(self._lib.pct_fill_hole_stats(self._h, _ptr(out, _i64p), _ptr(ms, _f64p)))
-        names = ("boundary_edges", "gaps", "odd_gaps", "loops", "filled", "perimeter", "blocked", "patch_triangles")
-        return {**{k: int(v) for k, v in zip(names, out)}, "ms": float(ms[0])}
+        return self._stage_stats(lambda out, ms: self._check(self._lib.pct_fill_hole_stats(self._h, _ptr(out, _i64p), _ptr(ms, _f64p))),
+                                 ("boundary_edges", "gaps", "odd_gaps", "loops", "filled", "perimeter", "blocked", "patch_triangles"))
 
     def get_hole_triangles(self, first=0, count=None):
         """(count, 3) int32: the patch triangles, ascending; by default all of them."""

@@ -87,14 +87,6 @@ int pct_reserve_fit(pct_ctx* ctx, int64_t rows) {
     return PCT_OK;
 }
 
-static float ev_ms(pct_ctx* ctx, int a, int b) { return pct_event_ms(ctx->ev[a], ctx->ev[b]); }
-
-// what a statistics getter answers: the numbers stored with the result while it is in place, zeros otherwise
-template <typename T>
-static void stats_or_zero(bool live, const T* src, int n, T* out) {
-    for (int i = 0; i < n; ++i) out[i] = live ? src[i] : T(0);
-}
-
 // the statistics a sweep left, as the timings report them
 static void read_sweep_stats(const pct_sweep_words& w, pct_timings* t) {
     t->ring_fallbacks = (int64_t)w.ring_fallbacks;
@@ -140,6 +132,26 @@ int pct_begin_row_call(pct_ctx* ctx, const char* what) {
     if (ctx->slab_parts >= 1)
         return pct_fail(ctx, PCT_ERR_INVALID, "%s: this handle owns a slab, not an index range (pct_slab_records / pct_scatter_records)", what);
     return PCT_OK;
+}
+
+// ---- what the row getters share, those of the surface stages included ----------------------------------------------------
+// the range error of a row getter: rows [begin, end) within the rows r covers, which start at base; what: "the owned range", ...
+int pct_check_owned_span(pct_ctx* ctx, const char* what, pct_resident r, int64_t begin, int64_t end, int64_t base) {
+    if (begin < base || end > base + ctx->res.rows_of(r) || begin > end)
+        return pct_fail(ctx, PCT_ERR_INVALID, "rows [%lld,%lld) outside %s", (long long)begin, (long long)end, what);
+    return PCT_OK;
+}
+
+// rows [first, first + rows) of r's columns to the caller: through row_of where r is stored in table-row order (row_of
+// outlives the table, PCT_TABLE_LOST: whatever rewrites the cell order drops r, and query_state keeps a query's build away)
+int pct_get_rows(pct_ctx* ctx, pct_resident r, const pct_column* cols, int ncol, int64_t first, int64_t rows) {
+    if (rows == 0) return PCT_OK;
+    const int* map = nullptr;
+    if (ctx->res.in_row_order(r)) {
+        PCT_TRY(pct_ensure_row_of(ctx));
+        map = (const int*)ctx->row_of.p;
+    }
+    return pct_download_columns(ctx, cols, ncol, first, rows, map);
 }
 
 extern "C" {
@@ -314,7 +326,7 @@ int pct_set_points_f32(pct_ctx* ctx, const float* xyz, int64_t n) {
     ctx->xyz_view = (const float*)ctx->xyz.p;
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_IO_END], ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->tm.upload_ms = ev_ms(ctx, PCT_EV_IO_BEGIN, PCT_EV_IO_END);
+    ctx->tm.upload_ms = pct_ev_ms(ctx, PCT_EV_IO_BEGIN, PCT_EV_IO_END);
     return PCT_OK;
 }
 
@@ -329,7 +341,7 @@ int pct_set_points_f64(pct_ctx* ctx, const double* xyz, int64_t n) {
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_IO_END], ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->has_f64 = true;
-    ctx->tm.upload_ms = ev_ms(ctx, PCT_EV_IO_BEGIN, PCT_EV_IO_END);
+    ctx->tm.upload_ms = pct_ev_ms(ctx, PCT_EV_IO_BEGIN, PCT_EV_IO_END);
     return PCT_OK;
 }
 
@@ -675,7 +687,7 @@ int pct_fit(pct_ctx* ctx) {
     PCT_TRY(pct_launch_fit_table(ctx, FitSlot{0, false, nullptr}, nullptr, &by_row));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_END], ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->tm.fit_ms = ev_ms(ctx, PCT_EV_FIT_BEGIN, PCT_EV_FIT_END);
+    ctx->tm.fit_ms = pct_ev_ms(ctx, PCT_EV_FIT_BEGIN, PCT_EV_FIT_END);
     ctx->tm.fit_svd_rows = ctx->pin->svd_rows[0];
     return fit_left(ctx, ctx->q_end - ctx->q_begin, true, by_row);
 }
@@ -755,7 +767,7 @@ int pct_get_neighbors(pct_ctx* ctx, int64_t begin, int64_t end, int32_t* idx, fl
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_IO_END], ctx->stream));
     const pct_column cols[] = {{d_idx, ctx->k * (int)sizeof(int), idx}, {d_dist, ctx->k * (int)sizeof(float), dist}, {d_cnt, sizeof(int), count}};
     PCT_TRY(pct_download_columns(ctx, cols, 3, 0, rows, nullptr));
-    ctx->tm.export_ms = ev_ms(ctx, PCT_EV_IO_BEGIN, PCT_EV_IO_END);
+    ctx->tm.export_ms = pct_ev_ms(ctx, PCT_EV_IO_BEGIN, PCT_EV_IO_END);
     return PCT_OK;
 }
 
@@ -824,7 +836,7 @@ int pct_fit_indices(pct_ctx* ctx, const int32_t* idx, const int32_t* count, cons
                                 (float*)ctx->K.p, (float*)ctx->H.p, (float*)ctx->H2.p, false));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_END], ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->tm.fit_ms = ev_ms(ctx, PCT_EV_FIT_BEGIN, PCT_EV_FIT_END);
+    ctx->tm.fit_ms = pct_ev_ms(ctx, PCT_EV_FIT_BEGIN, PCT_EV_FIT_END);
     ctx->tm.fit_svd_rows = ctx->pin->svd_rows[0];
     return fit_left(ctx, rows, false, false);         // (a resident neighbour table is untouched and stays valid)
 }
@@ -1021,7 +1033,7 @@ int pct_fit_ball(pct_ctx* ctx, const int64_t* self_rows, int64_t m, int32_t* use
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_END], ctx->stream));
     PCT_TRY(pct_enqueue_download(ctx, used, d_used, (size_t)m));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->tm.fit_ms = ev_ms(ctx, PCT_EV_FIT_BEGIN, PCT_EV_FIT_END);
+    ctx->tm.fit_ms = pct_ev_ms(ctx, PCT_EV_FIT_BEGIN, PCT_EV_FIT_END);
     ctx->tm.fit_svd_rows = ctx->pin->svd_rows[0];
     return fit_left(ctx, m, false, false);
 }
@@ -1032,331 +1044,14 @@ int pct_ball_stats(pct_ctx* ctx, int64_t out[4]) {
     return PCT_OK;
 }
 
-// ---- what the row getters, the statistics getters and the calls that build on a resident share ---------------------------
-// the range error of a row getter: rows [begin, end) within the rows r covers, which start at base; what: "the owned range", ...
-static int check_owned_span(pct_ctx* ctx, const char* what, pct_resident r, int64_t begin, int64_t end, int64_t base) {
-    if (begin < base || end > base + ctx->res.rows_of(r) || begin > end)
-        return pct_fail(ctx, PCT_ERR_INVALID, "rows [%lld,%lld) outside %s", (long long)begin, (long long)end, what);
-    return PCT_OK;
-}
-
-// rows [first, first + rows) of r's columns to the caller: through row_of where r is stored in table-row order (row_of
-// outlives the table, PCT_TABLE_LOST: whatever rewrites the cell order drops r, and query_state keeps a query's build away)
-static int get_rows(pct_ctx* ctx, pct_resident r, const pct_column* cols, int ncol, int64_t first, int64_t rows) {
-    if (rows == 0) return PCT_OK;
-    const int* map = nullptr;
-    if (ctx->res.in_row_order(r)) {
-        PCT_TRY(pct_ensure_row_of(ctx));
-        map = (const int*)ctx->row_of.p;
-    }
-    return pct_download_columns(ctx, cols, ncol, first, rows, map);
-}
-
-// r is in place for every owned row (the fit: the cloud-aligned one), else PCT_ERR_INVALID with `missing`
-static int need_for_owned_rows(pct_ctx* ctx, pct_resident r, const char* missing) {
-    if (ctx->res.covers(r, ctx->q_end - ctx->q_begin) && (r != PCT_R_FIT || ctx->fit_cloud_aligned)) return PCT_OK;
-    return pct_fail(ctx, PCT_ERR_INVALID, "%s", missing);
-}
-
 int pct_get_fit(pct_ctx* ctx, int64_t begin, int64_t end, float* coefs, float* K, float* H, float* H2) {
     PCT_TRY(pct_begin_row_call(ctx, "pct_get_fit"));
     if (!ctx->res.has(PCT_R_FIT)) return pct_fail(ctx, PCT_ERR_INVALID, "no fit results");
     const int64_t base = ctx->fit_cloud_aligned ? ctx->q_begin : 0;   // cloud-aligned vs row-aligned results
-    PCT_TRY(check_owned_span(ctx, "the fitted range", PCT_R_FIT, begin, end, base));
+    PCT_TRY(pct_check_owned_span(ctx, "the fitted range", PCT_R_FIT, begin, end, base));
     const pct_column cols[] = {{ctx->coefs.p, 6 * sizeof(float), coefs}, {ctx->K.p, sizeof(float), K}, {ctx->H.p, sizeof(float), H},
                                {ctx->H2.p, sizeof(float), H2}};
-    return get_rows(ctx, PCT_R_FIT, cols, 4, begin - base, end - begin);
-}
-
-// ---- per-point tangent-plane Voronoi areas and the energies over them (pct_area.hip) --------------------------------------
-int pct_point_areas(pct_ctx* ctx) {
-    PCT_TRY(pct_begin_row_call(ctx, "pct_point_areas"));
-    if (!ctx->res.has(PCT_R_TABLE)) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "plant the neighbour table first (pct_knn)");
-    ctx->res.drop(pct_replacing(PCT_R_AREAS));
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_AREA_BEGIN], ctx->stream));
-    bool by_row = false;
-    PCT_TRY(pct_launch_point_areas(ctx, &by_row));
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_AREA_END], ctx->stream));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));              // the call's one wait: results, statistics words, events
-    const unsigned long long* w = ctx->pin->area_words;
-    const int64_t rows = ctx->q_end - ctx->q_begin;
-    ctx->area_stats[0] = rows;
-    ctx->area_stats[1] = (int64_t)w[1];
-    ctx->area_stats[2] = (int64_t)w[2];
-    ctx->area_stats[3] = (int64_t)w[0];
-    ctx->area_profile[0] = ev_ms(ctx, PCT_EV_AREA_BEGIN, PCT_EV_AREA_END);
-    ctx->area_profile[1] = (double)w[3];
-    ctx->res.leave(PCT_R_AREAS, by_row, rows);
-    return PCT_OK;
-}
-
-int pct_get_point_areas(pct_ctx* ctx, int64_t begin, int64_t end, double* area, uint8_t* closed, int32_t* nverts) {
-    PCT_TRY(pct_begin_row_call(ctx, "pct_get_point_areas"));
-    if (!ctx->res.has(PCT_R_AREAS)) return pct_fail(ctx, PCT_ERR_INVALID, "no point areas (pct_point_areas)");
-    PCT_TRY(check_owned_span(ctx, "the owned range", PCT_R_AREAS, begin, end, ctx->q_begin));
-    const pct_column cols[] = {{ctx->area.p, sizeof(double), area}, {ctx->area_closed.p, 1, closed}, {ctx->area_nverts.p, sizeof(int), nverts}};
-    return get_rows(ctx, PCT_R_AREAS, cols, 3, begin - ctx->q_begin, end - begin);
-}
-
-int pct_point_area_stats(pct_ctx* ctx, int64_t out[4]) {
-    if (!ctx || !out) return PCT_ERR_INVALID;
-    stats_or_zero(ctx->res.has(PCT_R_AREAS), ctx->area_stats, 4, out);
-    return PCT_OK;
-}
-
-int pct_point_area_profile(pct_ctx* ctx, double out[2]) {
-    if (!ctx || !out) return PCT_ERR_INVALID;
-    stats_or_zero(ctx->res.has(PCT_R_AREAS), ctx->area_profile, 2, out);
-    return PCT_OK;
-}
-
-int pct_point_energies(pct_ctx* ctx, int32_t closed_only, double out[4]) {
-    PCT_TRY(pct_begin_row_call(ctx, "pct_point_energies"));
-    if (!out) return pct_fail(ctx, PCT_ERR_INVALID, "null result");
-    PCT_TRY(need_for_owned_rows(ctx, PCT_R_FIT, "no fit results"));
-    PCT_TRY(need_for_owned_rows(ctx, PCT_R_AREAS, "no point areas (pct_point_areas)"));
-    const int nblk = 1024;
-    double* d_part = nullptr;
-    PCT_TRY(pct_claim(ctx, (size_t)nblk * 4 + 4, &d_part));
-    PCT_TRY(pct_launch_point_energies(ctx, closed_only != 0, d_part, d_part + (size_t)nblk * 4));
-    PCT_TRY(pct_enqueue_download(ctx, out, d_part + (size_t)nblk * 4, 4));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PCT_OK;
-}
-
-// ---- per-point surface frames from the resident fit (pct_frame.hip) ----------------------------------------------------
-int pct_point_frames(pct_ctx* ctx, const double* viewpoint) {
-    PCT_TRY(pct_begin_row_call(ctx, "pct_point_frames"));
-    if (!ctx->res.has(PCT_R_TABLE)) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "plant the neighbour table first (pct_knn)");
-    PCT_TRY(need_for_owned_rows(ctx, PCT_R_FIT, "no fit results"));
-    if (viewpoint && !(isfinite(viewpoint[0]) && isfinite(viewpoint[1]) && isfinite(viewpoint[2])))
-        return pct_fail(ctx, PCT_ERR_INVALID, "pct_point_frames: the viewpoint is not finite");
-    ctx->res.drop(pct_replacing(PCT_R_FRAMES));
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FRAME_BEGIN], ctx->stream));
-    bool by_row = false;
-    PCT_TRY(pct_launch_point_frames(ctx, viewpoint, &by_row));
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FRAME_END], ctx->stream));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));              // the call's one wait: results, statistics words, events
-    const unsigned long long* w = ctx->pin->frame_words;
-    const int64_t rows = ctx->q_end - ctx->q_begin;
-    ctx->frame_stats[0] = rows;
-    for (int i = 0; i < 3; ++i) ctx->frame_stats[1 + i] = (int64_t)w[i];
-    ctx->frame_ms = ev_ms(ctx, PCT_EV_FRAME_BEGIN, PCT_EV_FRAME_END);
-    ctx->res.leave(PCT_R_FRAMES, by_row, rows);
-    return PCT_OK;
-}
-
-int pct_get_point_frames(pct_ctx* ctx, int64_t begin, int64_t end, double* normal, double* k12, double* dirs, uint8_t* flipped) {
-    PCT_TRY(pct_begin_row_call(ctx, "pct_get_point_frames"));
-    if (!ctx->res.has(PCT_R_FRAMES)) return pct_fail(ctx, PCT_ERR_INVALID, "no point frames (pct_point_frames)");
-    PCT_TRY(check_owned_span(ctx, "the owned range", PCT_R_FRAMES, begin, end, ctx->q_begin));
-    const int64_t all = ctx->res.rows_of(PCT_R_FRAMES);
-    const double* f = (const double*)ctx->frame.p;
-    const pct_column cols[] = {{f, 3 * sizeof(double), normal}, {f + all * 3, 2 * sizeof(double), k12}, {f + all * 5, 6 * sizeof(double), dirs},
-                               {(const unsigned char*)ctx->frame_flip.p + 64, 1, flipped}};
-    return get_rows(ctx, PCT_R_FRAMES, cols, 4, begin - ctx->q_begin, end - begin);
-}
-
-int pct_point_frame_stats(pct_ctx* ctx, int64_t out[4], double* ms) {
-    if (!ctx || !out) return PCT_ERR_INVALID;
-    stats_or_zero(ctx->res.has(PCT_R_FRAMES), ctx->frame_stats, 4, out);
-    if (ms) stats_or_zero(ctx->res.has(PCT_R_FRAMES), &ctx->frame_ms, 1, ms);
-    return PCT_OK;
-}
-
-// ---- consistent orientation of the resident frames (pct_orient.hip) ------------------------------------------------------
-// the orientation belongs to the frames it turned: whatever drops or replaces them drops it (pct_residents.h)
-int pct_orient_frames(pct_ctx* ctx, int32_t anchor, const double* viewpoint, int32_t max_components) {
-    PCT_TRY(pct_begin_row_call(ctx, "pct_orient_frames"));
-    if (!ctx->res.has(PCT_R_FRAMES) || !ctx->res.has(PCT_R_TABLE)) return pct_fail(ctx, PCT_ERR_INVALID, "no point frames (pct_point_frames)");
-    const int64_t rows = ctx->q_end - ctx->q_begin;
-    if (ctx->q_begin != 0 || ctx->q_end != ctx->n || ctx->culled || !ctx->res.covers(PCT_R_FRAMES, rows))
-        return pct_fail(ctx, PCT_ERR_INVALID, "pct_orient_frames: the handle owns rows [%lld,%lld) of %lld: the flood needs the whole cloud",
-                        (long long)ctx->q_begin, (long long)ctx->q_end, (long long)ctx->n);
-    if (anchor != PCT_ORIENT_SEED && anchor != PCT_ORIENT_TOP && anchor != PCT_ORIENT_VIEW)
-        return pct_fail(ctx, PCT_ERR_INVALID, "pct_orient_frames: unknown anchor %d", anchor);
-    if (anchor == PCT_ORIENT_VIEW && !(viewpoint && isfinite(viewpoint[0]) && isfinite(viewpoint[1]) && isfinite(viewpoint[2])))
-        return pct_fail(ctx, PCT_ERR_INVALID, "pct_orient_frames: PCT_ORIENT_VIEW needs a finite viewpoint");
-    const int max_comp = max_components <= 0 ? 65536 : max_components;
-    ctx->res.drop(pct_replacing(PCT_R_ORIENT));        // (behind every refusal: a refused call leaves the orientation of an earlier one)
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_ORIENT_BEGIN], ctx->stream));
-    const int status = pct_run_orient(ctx, anchor, anchor == PCT_ORIENT_VIEW ? viewpoint : nullptr, max_comp, ctx->orient_stats);
-    if (status != PCT_OK) {
-        (void)hipStreamSynchronize(ctx->stream);           // (nothing of a failed flood stays in flight)
-        return status;
-    }
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_ORIENT_END], ctx->stream));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int* w = ctx->pin->orient_words;
-    const int64_t valid = w[OW_VALID], labelled = w[OW_LABELLED];
-    ctx->orient_stats[0] = valid;
-    ctx->orient_stats[1] = w[OW_NCOMP];
-    ctx->orient_stats[2] = valid - labelled;
-    ctx->orient_stats[3] = w[OW_TOGGLED];
-    ctx->orient_stats[4] = w[OW_LEVELS];
-    ctx->orient_stats[5] = w[OW_PULLS];
-    ctx->orient_ms = ev_ms(ctx, PCT_EV_ORIENT_BEGIN, PCT_EV_ORIENT_END);
-    ctx->res.leave(PCT_R_ORIENT, false, rows);
-    return PCT_OK;
-}
-
-int pct_get_orientation(pct_ctx* ctx, int64_t begin, int64_t end, int32_t* component, int32_t* parent, int32_t* level, uint8_t* toggled) {
-    PCT_TRY(pct_begin_row_call(ctx, "pct_get_orientation"));
-    if (!ctx->res.has(PCT_R_ORIENT)) return pct_fail(ctx, PCT_ERR_INVALID, "no orientation (pct_orient_frames)");
-    PCT_TRY(check_owned_span(ctx, "the cloud", PCT_R_ORIENT, begin, end, 0));
-    const pct_column cols[] = {{ctx->orient_comp, sizeof(int), component}, {ctx->orient_parent, sizeof(int), parent},
-                               {ctx->orient_level, sizeof(int), level}, {ctx->orient_toggle, 1, toggled}};
-    return pct_download_columns(ctx, cols, 4, begin, end - begin, nullptr);
-}
-
-int pct_orient_stats(pct_ctx* ctx, int64_t out[8], double* ms) {
-    if (!ctx || !out) return PCT_ERR_INVALID;
-    stats_or_zero(ctx->res.has(PCT_R_ORIENT), ctx->orient_stats, 8, out);
-    if (ms) stats_or_zero(ctx->res.has(PCT_R_ORIENT), &ctx->orient_ms, 1, ms);
-    return PCT_OK;
-}
-
-// ---- faces from the tangent-plane Voronoi cells (pct_fan.hip, include/pct_hip_surface.h) -----------------------------------
-int pct_point_triangles(pct_ctx* ctx, int32_t flags) {
-    PCT_TRY(pct_begin_row_call(ctx, "pct_point_triangles"));
-    if (!ctx->res.has(PCT_R_TABLE)) return pct_fail(ctx, PCT_ERR_NO_NEIGHBORS, "plant the neighbour table first (pct_knn)");
-    if (ctx->q_begin != 0 || ctx->q_end != ctx->n || ctx->culled)
-        return pct_fail(ctx, PCT_ERR_INVALID, "pct_point_triangles: the handle owns rows [%lld,%lld) of %lld: agreement needs the whole cloud",
-                        (long long)ctx->q_begin, (long long)ctx->q_end, (long long)ctx->n);
-    if (flags & ~PCT_TRI_WIND_FRAMES) return pct_fail(ctx, PCT_ERR_INVALID, "pct_point_triangles: unknown flags %d", flags);
-    const bool wind = (flags & PCT_TRI_WIND_FRAMES) != 0;
-    if (wind) PCT_TRY(need_for_owned_rows(ctx, PCT_R_FRAMES, "no point frames (pct_point_frames)"));
-    ctx->res.drop(pct_replacing(PCT_R_TRIANGLES));     // (behind every refusal: a refused call leaves the triangles of an earlier one)
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_TRI_BEGIN], ctx->stream));
-    const int status = pct_launch_point_triangles(ctx, wind, ctx->ev[PCT_EV_TRI_MID]);
-    if (status != PCT_OK) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return status;
-    }
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_TRI_END], ctx->stream));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const unsigned long long* w = ctx->pin->tri_words;
-    ctx->tri_total = (int64_t)w[7];
-    const int64_t st[8] = {ctx->n, (int64_t)w[1], (int64_t)w[2], ctx->tri_total, (int64_t)w[0], (int64_t)w[3], (int64_t)w[4], 0};
-    for (int i = 0; i < 8; ++i) ctx->tri_stats[i] = st[i];
-    ctx->tri_ms[0] = ev_ms(ctx, PCT_EV_TRI_BEGIN, PCT_EV_TRI_END);
-    ctx->tri_ms[1] = ev_ms(ctx, PCT_EV_TRI_BEGIN, PCT_EV_TRI_MID);
-    ctx->tri_ms[2] = ev_ms(ctx, PCT_EV_TRI_MID, PCT_EV_TRI_END);
-    ctx->res.leave(PCT_R_TRIANGLES, false, ctx->n);    // (kept by public index)
-    return PCT_OK;
-}
-
-int pct_get_point_fans(pct_ctx* ctx, int64_t begin, int64_t end, int64_t* offsets, int32_t* nbr) {
-    PCT_TRY(pct_begin_call(ctx));
-    if (!ctx->res.has(PCT_R_TRIANGLES)) return pct_fail(ctx, PCT_ERR_INVALID, "no triangles (pct_point_triangles)");
-    if (begin < 0 || end > ctx->res.rows_of(PCT_R_TRIANGLES) || begin > end || !offsets)
-        return pct_fail(ctx, PCT_ERR_INVALID, "rows [%lld,%lld) outside the cloud", (long long)begin, (long long)end);
-    const int64_t rows = end - begin;
-    int64_t *d_count = nullptr, *d_off = nullptr;
-    PCT_TRY(pct_claim(ctx, (size_t)(rows + 1), &d_count));
-    PCT_TRY(pct_claim(ctx, (size_t)(rows + 1), &d_off));
-    PCT_TRY(pct_launch_point_fans(ctx, begin, rows, d_count, d_off, nullptr));
-    PCT_TRY(pct_enqueue_download(ctx, offsets, d_off, (size_t)(rows + 1)));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int64_t total = offsets[rows];
-    if (!nbr || total == 0) return PCT_OK;
-    int* d_nbr = nullptr;
-    PCT_TRY(pct_claim(ctx, (size_t)total, &d_nbr));
-    PCT_TRY(pct_launch_point_fans(ctx, begin, rows, d_count, d_off, d_nbr));
-    PCT_TRY(pct_enqueue_download(ctx, nbr, d_nbr, (size_t)total));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PCT_OK;
-}
-
-// triangles [first, first + count) of an ascending (have, 3) array
-static int download_triangles(pct_ctx* ctx, const pct_buf& src, int64_t have, int64_t first, int64_t count, int32_t* tri) {
-    if (first < 0 || count < 0 || first + count > have || (count > 0 && !tri))
-        return pct_fail(ctx, PCT_ERR_INVALID, "triangles [%lld,%lld) outside the %lld resident", (long long)first, (long long)(first + count), (long long)have);
-    const pct_column col = {src.p, 3 * sizeof(int), tri};
-    return pct_download_columns(ctx, &col, 1, first, count, nullptr);
-}
-
-int pct_get_triangles(pct_ctx* ctx, int64_t first, int64_t count, int32_t* tri) {
-    PCT_TRY(pct_begin_call(ctx));
-    if (!ctx->res.has(PCT_R_TRIANGLES)) return pct_fail(ctx, PCT_ERR_INVALID, "no triangles (pct_point_triangles)");
-    return download_triangles(ctx, ctx->tri, ctx->tri_total, first, count, tri);
-}
-
-int pct_point_triangle_stats(pct_ctx* ctx, int64_t out[8], double* ms) {
-    if (!ctx || !out) return PCT_ERR_INVALID;
-    stats_or_zero(ctx->res.has(PCT_R_TRIANGLES), ctx->tri_stats, 8, out);
-    if (ms) stats_or_zero(ctx->res.has(PCT_R_TRIANGLES), &ctx->tri_ms[0], 1, ms);
-    return PCT_OK;
-}
-
-int pct_point_triangle_profile(pct_ctx* ctx, double out[2]) {
-    if (!ctx || !out) return PCT_ERR_INVALID;
-    stats_or_zero(ctx->res.has(PCT_R_TRIANGLES), &ctx->tri_ms[1], 2, out);
-    return PCT_OK;
-}
-
-// ---- boundary loops and small-hole filling (pct_hole.hip, include/pct_hip_holes.h): PCT_R_HOLES, made from the triangles ------
-int pct_fill_holes(pct_ctx* ctx, int32_t max_vertices, double max_perimeter, int32_t flags) {
-    PCT_TRY(pct_begin_row_call(ctx, "pct_fill_holes"));
-    if (ctx->n > 0 && (ctx->q_begin != 0 || ctx->q_end != ctx->n || ctx->culled))
-        return pct_fail(ctx, PCT_ERR_INVALID, "pct_fill_holes: the handle owns rows [%lld,%lld) of %lld: a loop may cross into other rows",
-                        (long long)ctx->q_begin, (long long)ctx->q_end, (long long)ctx->n);
-    if (!ctx->res.has(PCT_R_TRIANGLES)) return pct_fail(ctx, PCT_ERR_INVALID, "no triangles (pct_point_triangles)");
-    if (max_vertices < 3 || max_vertices > PCT_HOLE_MAX_VERTICES)
-        return pct_fail(ctx, PCT_ERR_INVALID, "pct_fill_holes: max_vertices=%d outside [3,%d]", max_vertices, PCT_HOLE_MAX_VERTICES);
-    if (!(max_perimeter > 0.0)) return pct_fail(ctx, PCT_ERR_INVALID, "pct_fill_holes: max_perimeter must be positive (+inf: no cap)");
-    if (flags != 0) return pct_fail(ctx, PCT_ERR_INVALID, "pct_fill_holes: unknown flags %d", flags);
-    ctx->res.drop(pct_replacing(PCT_R_HOLES));         // (behind every refusal: a refused call leaves the results of an earlier one)
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_HOLE_BEGIN], ctx->stream));
-    int64_t st[8];
-    const int status = pct_launch_fill_holes(ctx, max_vertices, max_perimeter, st);
-    if (status != PCT_OK) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return status;
-    }
-    PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_HOLE_END], ctx->stream));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < 8; ++i) ctx->hole_stats[i] = st[i];
-    ctx->hole_ms = ev_ms(ctx, PCT_EV_HOLE_BEGIN, PCT_EV_HOLE_END);
-    ctx->res.leave(PCT_R_HOLES, false, ctx->n);
-    return PCT_OK;
-}
-
-static int get_triangle_rows(pct_ctx* ctx, const pct_buf& src, int64_t have, int64_t first, int64_t count, int32_t* tri) {
-    PCT_TRY(pct_begin_call(ctx));
-    if (!ctx->res.has(PCT_R_HOLES)) return pct_fail(ctx, PCT_ERR_INVALID, "no hole results (pct_fill_holes)");
-    return download_triangles(ctx, src, have, first, count, tri);
-}
-
-int pct_get_hole_triangles(pct_ctx* ctx, int64_t first, int64_t count, int32_t* tri) {
-    if (!ctx) return PCT_ERR_INVALID;
-    return get_triangle_rows(ctx, ctx->hole_tri, ctx->hole_patches, first, count, tri);
-}
-
-int pct_get_filled_triangles(pct_ctx* ctx, int64_t first, int64_t count, int32_t* tri) {
-    if (!ctx) return PCT_ERR_INVALID;
-    return get_triangle_rows(ctx, ctx->hole_filled, ctx->tri_total + ctx->hole_patches, first, count, tri);
-}
-
-int pct_get_boundary_loops(pct_ctx* ctx, int64_t* offsets, int32_t* vertices, uint8_t* status) {
-    PCT_TRY(pct_begin_call(ctx));
-    if (!ctx->res.has(PCT_R_HOLES)) return pct_fail(ctx, PCT_ERR_INVALID, "no hole results (pct_fill_holes)");
-    if (!offsets) return pct_fail(ctx, PCT_ERR_INVALID, "null offsets");
-    const int64_t loops = ctx->hole_loops, verts = ctx->hole_loop_verts;
-    const char* base = (const char*)ctx->hole_loop.p;
-    const size_t off_bytes = (size_t)(loops + 1) * sizeof(int64_t), vert_bytes = (size_t)verts * sizeof(int);
-    PCT_HIP(ctx, hipMemcpyAsync(offsets, base, off_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (status && loops > 0) PCT_HIP(ctx, hipMemcpyAsync(status, base + off_bytes + vert_bytes, (size_t)loops, hipMemcpyDeviceToHost, ctx->stream));
-    if (vertices && verts > 0) PCT_HIP(ctx, hipMemcpyAsync(vertices, base + off_bytes, vert_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return PCT_OK;
-}
-
-int pct_fill_hole_stats(pct_ctx* ctx, int64_t out[8], double* ms) {
-    if (!ctx || !out) return PCT_ERR_INVALID;
-    stats_or_zero(ctx->res.has(PCT_R_HOLES), ctx->hole_stats, 8, out);
-    if (ms) stats_or_zero(ctx->res.has(PCT_R_HOLES), &ctx->hole_ms, 1, ms);
-    return PCT_OK;
+    return pct_get_rows(ctx, PCT_R_FIT, cols, 4, begin - base, end - begin);
 }
 
 int pct_curvatures_from_coefficients(pct_ctx* ctx, const float* coefs, int64_t rows, float* K, float* H, float* H2) {
@@ -1551,7 +1246,7 @@ int pct_pca_curvatures(pct_ctx* ctx, int32_t k, int32_t algo, int32_t keep_neigh
     PCT_TRY(st);
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_FIT_END], ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->tm.fit_ms = ev_ms(ctx, PCT_EV_FIT_BEGIN, PCT_EV_FIT_END);
+    ctx->tm.fit_ms = pct_ev_ms(ctx, PCT_EV_FIT_BEGIN, PCT_EV_FIT_END);
     ctx->tm.total_ms = ctx->clock[0].since_begin(ctx->ev[PCT_EV_FIT_END]);
     ctx->res.leave(PCT_R_PCA, false, ctx->n);
     ctx->pca_has_nbr = keep_neighbors != 0;
@@ -1577,7 +1272,7 @@ int pct_get_pca(pct_ctx* ctx, int64_t begin, int64_t end, double* l1, double* l2
     PCT_TRY(pct_enqueue_columns(ctx, cols, 6, begin, rows, nullptr));
     PCT_HIP(ctx, hipEventRecord(ctx->ev[PCT_EV_IO_END], ctx->stream));
     PCT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->tm.export_ms = ev_ms(ctx, PCT_EV_IO_BEGIN, PCT_EV_IO_END);
+    ctx->tm.export_ms = pct_ev_ms(ctx, PCT_EV_IO_BEGIN, PCT_EV_IO_END);
     return PCT_OK;
 }
 

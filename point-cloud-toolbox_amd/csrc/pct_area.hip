@@ -197,7 +197,15 @@ int pct_launch_point_areas(pct_ctx* ctx, bool* by_row) {
     return PCT_OK;
 }
 
-// d_out4 = {bending, stretching, area, rows used}; d_partial: room for 4 doubles per block (at most 1024 blocks)
+// rows, closed rows, NaN rows, overflow rows; behind the milliseconds, as a double: neighbours past the rejection test
+void pct_area_report(pct_ctx* ctx, pct_stage_report* rep) {
+    const unsigned long long* w = ctx->pin->area_words;
+    const int64_t st[4] = {ctx->q_end - ctx->q_begin, (int64_t)w[AW_CLOSED], (int64_t)w[AW_NAN], (int64_t)w[AW_OVERFLOW]};
+    for (int i = 0; i < 4; ++i) rep->stats[i] = st[i];
+    rep->ms[1] = (double)w[AW_SURVIVORS];
+}
+
+// d_out4 ={bending, stretching, area, rows used}; d_partial: room for 4 doubles per block (at most 1024 blocks)
 int pct_launch_point_energies(pct_ctx* ctx, bool closed_only, double* d_partial, double* d_out4) {
     const int64_t rows = ctx->q_end - ctx->q_begin;
     const int nblk = (int)((rows + kEnergyBlock - 1) / kEnergyBlock < 1024 ? (rows + kEnergyBlock - 1) / kEnergyBlock : 1024);

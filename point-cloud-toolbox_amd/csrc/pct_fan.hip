@@ -425,6 +425,16 @@ int pct_launch_point_triangles(pct_ctx* ctx, bool wind_frames, hipEvent_t mid) {
     return PCT_OK;
 }
 
+// rows, rows with a corner, corners, triangles, rows redone wide, largest fan, boundary edges; the triangle count stays on
+// the handle for the getters and the hole filling
+void pct_fan_report(pct_ctx* ctx, pct_stage_report* rep) {
+    const unsigned long long* w = ctx->pin->tri_words;
+    ctx->tri_total = (int64_t)w[7];
+    const int64_t st[8] = {ctx->n, (int64_t)w[FW_ROWS_CORNER], (int64_t)w[FW_CORNERS], ctx->tri_total, (int64_t)w[FW_OVERFLOW],
+                           (int64_t)w[FW_MAX_FAN], (int64_t)w[FW_BOUNDARY], 0};
+    for (int i = 0; i < 8; ++i) rep->stats[i] = st[i];
+}
+
 // Natural neighbours of public rows [first, first + rows): d_off (rows + 1) always, d_nbr (may be null) the entries
 int pct_launch_point_fans(pct_ctx* ctx, int64_t first, int64_t rows, int64_t* d_count, int64_t* d_off, int* d_nbr) {
     const int2* head = (const int2*)ctx->fan_head.p;

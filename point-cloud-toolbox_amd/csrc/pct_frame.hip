@@ -285,3 +285,10 @@ int pct_launch_point_frames(pct_ctx* ctx, const double* viewpoint, bool* by_row)
     *by_row = sorted;
     return PCT_OK;
 }
+
+// rows, NaN rows, flipped rows, umbilic rows
+void pct_frame_report(pct_ctx* ctx, pct_stage_report* rep) {
+    const unsigned long long* w = ctx->pin->frame_words;
+    const int64_t st[4] = {ctx->q_end - ctx->q_begin, (int64_t)w[FW_NAN], (int64_t)w[FW_FLIPPED], (int64_t)w[FW_UMBILIC]};
+    for (int i = 0; i < 4; ++i) rep->stats[i] = st[i];
+}

@@ -388,7 +388,7 @@ __global__ __launch_bounds__(256) void k_hole_pack(int64_t gaps, HoleSlots o, co
 
 }  // namespace
 
-int pct_launch_fill_holes(pct_ctx* ctx, int max_vertices, double max_perimeter, int64_t stats8[8]) {
+int pct_launch_fill_holes(pct_ctx* ctx, int max_vertices, double max_perimeter, pct_stage_report* rep) {
     const int64_t n = ctx->res.rows_of(PCT_R_TRIANGLES), total = ctx->tri_total;
     hipStream_t st = ctx->stream;
     HoleView h = {};
@@ -494,6 +494,6 @@ int pct_launch_fill_holes(pct_ctx* ctx, int max_vertices, double max_perimeter, 
     ctx->hole_loop_verts = sum.verts;
     ctx->hole_patches = patches;
     const int64_t out[8] = {boundary, gaps, odd, loops, sum.filled, sum.perimeter, sum.blocked, patches};
-    for (int q = 0; q < 8; ++q) stats8[q] = out[q];
+    for (int q = 0; q < 8; ++q) rep->stats[q] = out[q];
     return PCT_OK;
 }

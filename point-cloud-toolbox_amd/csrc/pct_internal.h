@@ -142,23 +142,23 @@ static_assert(sizeof(pct_pinned) <= 4096, "pct_create allocates 4096 bytes");
 
 // The handle's stopwatch pairs.  The stages of a sweep or a fused call are not among them: they are timed by the call's
 // clock (pct_clock.h), which owns the events of its boundaries.
+// The surface stages (pct_stage, below) share one triple: every call that records it ends in a wait for the stream and
+// turns the events into milliseconds before it returns, so no event's meaning outlives its call.
 enum pct_event {                           // ctx->ev
     PCT_EV_IO_BEGIN, PCT_EV_IO_END,        // an upload or an export
     PCT_EV_FIT_BEGIN, PCT_EV_FIT_END,      // a fit on its own (pct_fit and its siblings)
     PCT_EV_SCAN_TOTALS,                    // the cell list's scan totals are in pinned memory (pct_build_grid)
-    PCT_EV_AREA_BEGIN, PCT_EV_AREA_END,    // pct_point_areas
-    PCT_EV_FRAME_BEGIN, PCT_EV_FRAME_END,  // pct_point_frames
-    PCT_EV_ORIENT_BEGIN, PCT_EV_ORIENT_END,// pct_orient_frames
-    PCT_EV_TRI_BEGIN, PCT_EV_TRI_MID, PCT_EV_TRI_END,   // pct_point_triangles: the fan kernels | agreement and emission
-    PCT_EV_HOLE_BEGIN, PCT_EV_HOLE_END,    // pct_fill_holes
+    PCT_EV_STAGE_BEGIN, PCT_EV_STAGE_MID, PCT_EV_STAGE_END,   // a surface stage (pct_api_surface.hip: run_stage); mid: pct_point_triangles alone
     PCT_EV_COUNT
 };
 
-enum OrientWord {                          // int words of pct_orient.hip's control block, mirrored to pct_pinned::orient_words
-    OW_CNT_A = 0, OW_CNT_B, OW_UCNT0, OW_UCNT1, OW_UPAR, OW_SEED_BEST, OW_NCOMP, OW_RUNNING, OW_FINISHED, OW_LEVELS,
-    OW_PULLS, OW_LABELLED, OW_VALID, OW_TOGGLED, OW_PUSH_DONE, OW_COUNT
-};
-static_assert(OW_COUNT <= 16, "pct_pinned::orient_words");
+// The surface stages -- what is computed from the resident neighbour table, one resident result each -- and the numbers of a
+// stage's last call as its statistics getters serve them while that result is in place (zeros once it is gone).
+enum pct_stage { PCT_STAGE_AREAS, PCT_STAGE_FRAMES, PCT_STAGE_ORIENT, PCT_STAGE_TRIANGLES, PCT_STAGE_HOLES, PCT_STAGE_COUNT };
+constexpr pct_resident kPctStageResident[PCT_STAGE_COUNT] = {PCT_R_AREAS, PCT_R_FRAMES, PCT_R_ORIENT, PCT_R_TRIANGLES, PCT_R_HOLES};
+// stats: the public counters in their getter's order; ms: device milliseconds of the call, then whatever doubles the stage's
+// profile getter serves (triangles: fan kernels, agreement and emission; areas: the survivor count)
+struct pct_stage_report { int64_t stats[8]; double ms[3]; };
 
 constexpr int kPctStageSlots = 4;   // pct_ctx::stage, where the chain of claims that sets the count is named
 
@@ -336,20 +336,18 @@ struct pct_ctx {
 
     pct_timings tm = {};
 
+    pct_stage_report report[PCT_STAGE_COUNT] = {};    // of every surface stage's last call (pct_api_surface.hip: run_stage fills, stage_numbers serves)
+
     // per-point tangent-plane Voronoi areas (pct_area.hip) of the owned rows of the resident table (PCT_R_AREAS: in the order
     // and for the rows res records, as the fit)
     pct_buf area;          // double (owned)
     pct_buf area_closed;   // uint8 (owned)
     pct_buf area_nverts;   // int32 (owned)
     pct_buf area_over;     // eight statistics words, then int32 (owned): the rows redone with room for k + 4 vertices
-    int64_t area_stats[4] = {0, 0, 0, 0};   // rows, closed rows, NaN rows, overflow rows
-    double area_profile[2] = {0, 0};        // device milliseconds of the two kernels, neighbours past the rejection test
 
     // per-point surface frames (pct_frame.hip) of the owned rows of the resident table and its fit (PCT_R_FRAMES: as the areas)
     pct_buf frame;         // double (owned): normal (rows, 3) | k1 k2 (rows, 2) | directions (rows, 3, 2)
     pct_buf frame_flip;    // eight statistics words, then uint8 (owned): the viewpoint turned the row's normal
-    int64_t frame_stats[4] = {0, 0, 0, 0};  // rows, NaN rows, flipped rows, umbilic rows
-    double frame_ms = 0;                    // device milliseconds of its kernel
 
     // consistent orientation of those frames (pct_orient.hip): one allocation, carved up per call; the four results in
     // public order, int32 / uint8 (owned)
@@ -358,8 +356,6 @@ struct pct_ctx {
     const int* orient_parent = nullptr;
     const int* orient_level = nullptr;
     const unsigned char* orient_toggle = nullptr;
-    int64_t orient_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // valid rows, components, unlabelled, toggled, levels, pull rounds, launches, waits
-    double orient_ms = 0;
 
     // fans and triangles of the resident table of a whole-cloud handle (pct_fan.hip), everything by public index: they
     // depend on neither the table nor row_of once computed
@@ -373,8 +369,6 @@ struct pct_ctx {
     pct_buf tri;           // int32 (triangles, 3), ascending
     int32_t tri_wpitch = 0;
     int64_t tri_total = 0;
-    int64_t tri_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    double tri_ms[3] = {0, 0, 0};           // device milliseconds: the call, its fan kernels, agreement and emission
 
     // boundary loops and patches of those triangles (pct_hole.hip, include/pct_hip_holes.h): PCT_R_HOLES, made from the
     // triangles -- whatever drops or replaces them drops these
@@ -388,8 +382,6 @@ struct pct_ctx {
     pct_buf hole_filled;            // int32 (triangles + patches, 3) ascending
     pct_buf hole_tmp;               // scan, sort and merge scratch
     int64_t hole_loops = 0, hole_loop_verts = 0, hole_patches = 0;
-    int64_t hole_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    double hole_ms = 0;
 };
 
 int pct_fail(pct_ctx* ctx, int code, const char* fmt, ...);
@@ -520,6 +512,7 @@ int pct_enqueue_download(pct_ctx* ctx, T* host, const T* dev, size_t count) {
 // claimed), and of those a slab handle refuses (the header's list under "Ownership": its rows are not rows by index)
 int pct_begin_call(pct_ctx* ctx, bool wait_for_pending = true);
 int pct_begin_row_call(pct_ctx* ctx, const char* what);
+inline float pct_ev_ms(pct_ctx* ctx, pct_event a, pct_event b) { return pct_event_ms(ctx->ev[a], ctx->ev[b]); }   // after the wait for both
 
 // What one call asks of another, and what it answers, travels in arguments and results -- never parked on the handle.
 // Which pinned parity slot (statistics mirror, SVD row count) the fits of a call write, and whether its fit kernel may
@@ -623,29 +616,41 @@ constexpr int kPctRowColumns = 4;
 int pct_enqueue_columns(pct_ctx* ctx, const pct_column* cols, int ncol, int64_t first, int64_t rows, const int* map);
 int pct_download_columns(pct_ctx* ctx, const pct_column* cols, int ncol, int64_t first, int64_t rows, const int* map);
 int pct_ensure_row_of(pct_ctx* ctx);     // before any read of ctx->row_of
+// pct_api.hip, for every row getter (pct_api_surface.hip has the surface stages'): the range error of rows [begin, end)
+// outside the rows r covers, which start at base (what: "the owned range", ...); rows [first, first + rows) of r's columns
+// to the caller, in whichever order r is stored
+int pct_check_owned_span(pct_ctx* ctx, const char* what, pct_resident r, int64_t begin, int64_t end, int64_t base);
+int pct_get_rows(pct_ctx* ctx, pct_resident r, const pct_column* cols, int ncol, int64_t first, int64_t rows);
 int pct_launch_export_rows(pct_ctx* ctx, const int64_t* d_rows, int64_t n_rows, int32_t* d_idx, float* d_dist, int32_t* d_cnt);
 int pct_launch_mesh_energies(pct_ctx* ctx, const double* d_v, const int* d_tri, int64_t n_tri, const void* d_K, const void* d_H,
                              bool k_f64, bool h_f64, double* d_partial, int nblk, double* d_out);
-// pct_area.hip: areas of the owned rows of the resident table (statistics words to ctx->pin->area_words; *by_row: stored in
-// table-row order), and the energies over them: d_out4 = {bending, stretching, area, rows used}
+// The surface stages.  A launcher enqueues its kernels and the copy of its statistics words into pinned memory; its
+// pct_*_report, called once the stream has been waited for, turns those words into the public counters of rep->stats --
+// the words' layout is known to the stage's file alone.  What a launcher knows on the host it writes into rep itself.
+// pct_area.hip: areas of the owned rows of the resident table (*by_row: stored in table-row order), and the energies over
+// them: d_out4 = {bending, stretching, area, rows used}
 int pct_launch_point_areas(pct_ctx* ctx, bool* by_row);
+void pct_area_report(pct_ctx* ctx, pct_stage_report* rep);
 int pct_launch_point_energies(pct_ctx* ctx, bool closed_only, double* d_partial, double* d_out4);
-// pct_frame.hip: surface frames of the owned rows of the resident table from its resident fit (statistics words to
-// ctx->pin->frame_words; viewpoint: three finite doubles or null; *by_row: stored in table-row order)
+// pct_frame.hip: surface frames of the owned rows of the resident table from its resident fit (viewpoint: three finite
+// doubles or null; *by_row: stored in table-row order)
 int pct_launch_point_frames(pct_ctx* ctx, const double* viewpoint, bool* by_row);
+void pct_frame_report(pct_ctx* ctx, pct_stage_report* rep);
 // pct_orient.hip: the flood over the resident table, the anchor and the apply pass on the resident frames of a whole-cloud
-// handle; the control words are on their way to ctx->pin->orient_words on return (complete after the stream's next wait),
-// stats8[6] and [7] (kernel launches, host waits) are filled here
-int pct_run_orient(pct_ctx* ctx, int anchor, const double* viewpoint, int max_comp, int64_t stats8[8]);
+// handle; rep->stats[6] and [7] (kernel launches, host waits) are filled here, the rest by the report
+int pct_run_orient(pct_ctx* ctx, int anchor, const double* viewpoint, int max_comp, pct_stage_report* rep);
+void pct_orient_report(pct_ctx* ctx, pct_stage_report* rep);
 // pct_fan.hip: fans and triangles of the resident table of a whole-cloud handle (mid: recorded between the fan kernels and
-// the agreement; the statistics words are on their way to ctx->pin->tri_words on return, the triangle count is in [7]),
-// and the natural neighbours of public rows [first, first + rows) as CSR (d_count: rows + 1 words of scratch)
+// the agreement; the report also leaves ctx->tri_total), and the natural neighbours of public rows [first, first + rows)
+// as CSR (d_count: rows + 1 words of scratch)
 int pct_launch_point_triangles(pct_ctx* ctx, bool wind_frames, hipEvent_t mid);
+void pct_fan_report(pct_ctx* ctx, pct_stage_report* rep);
 int pct_launch_point_fans(pct_ctx* ctx, int64_t first, int64_t rows, int64_t* d_count, int64_t* d_off, int* d_nbr);
 // pct_hole.hip: gaps, loops, patches and the filled array of the resident fans and triangles; waits for the stream three
 // times (the gap count, the loop and patch counts, the end) and leaves ctx->hole_loops / hole_loop_verts / hole_patches and
-// stats8 = {boundary edges, gaps, odd gaps, loops, filled, left for the perimeter, blocked, patch triangles}
-int pct_launch_fill_holes(pct_ctx* ctx, int max_vertices, double max_perimeter, int64_t stats8[8]);
+// rep->stats = {boundary edges, gaps, odd gaps, loops, filled, left for the perimeter, blocked, patch triangles}: every
+// one of its words has been read on the host by then, so it has no report of its own
+int pct_launch_fill_holes(pct_ctx* ctx, int max_vertices, double max_perimeter, pct_stage_report* rep);
 int pct_voxel_downsample_device(pct_ctx* ctx, const void* d_xyz, bool f64, int64_t n, double voxel, int64_t* d_out, int64_t* count);
 int pct_launch_surface_variation(pct_ctx* ctx, float* d_out);
 // PCA principal curvatures (pct_pca.hip).  The sweep fetches up to PCT_PCA_EXTRA candidates beyond k per point, re-ranked

@@ -26,6 +26,12 @@
 
 namespace {
 
+enum OrientWord {                          // int words of the control block (OrientState::ctl), mirrored to pct_pinned::orient_words
+    OW_CNT_A = 0, OW_CNT_B, OW_UCNT0, OW_UCNT1, OW_UPAR, OW_SEED_BEST, OW_NCOMP, OW_RUNNING, OW_FINISHED, OW_LEVELS,
+    OW_PULLS, OW_LABELLED, OW_VALID, OW_TOGGLED, OW_PUSH_DONE, OW_COUNT
+};
+static_assert(OW_COUNT <= sizeof(pct_pinned::orient_words) / sizeof(int), "pct_pinned::orient_words");
+
 constexpr int kOrientBlock = 256;
 constexpr int kOrientGrid = 1024;          // blocks of a level kernel: 4096 waves stride over the frontier
 constexpr int kLevelsDefault = 8;          // push levels per group (even: the pairs end on list A)
@@ -397,9 +403,10 @@ size_t pct_orient_bytes(int64_t rows, int max_comp) {
            c * (sizeof(unsigned long long) + 2 * sizeof(int)) + ((c + 63) & ~(size_t)63) + 64;
 }
 
-// The flood, the anchor and the apply pass on the resident frames of a whole-cloud handle.  stats8 = {valid rows, components,
-// rows left unlabelled, toggled rows, levels, pull rounds, kernel launches, host waits}, complete on return.
-int pct_run_orient(pct_ctx* ctx, int anchor, const double* viewpoint, int max_comp, int64_t stats8[8]) {
+// The flood, the anchor and the apply pass on the resident frames of a whole-cloud handle.  rep->stats = {valid rows,
+// components, rows left unlabelled, toggled rows, levels, pull rounds, kernel launches, host waits}: the last two from
+// here, the others from the control words (pct_orient_report), which are on their way to pinned memory on return.
+int pct_run_orient(pct_ctx* ctx, int anchor, const double* viewpoint, int max_comp, pct_stage_report* rep) {
     const int64_t rows64 = ctx->q_end - ctx->q_begin;
     const int rows = (int)rows64;
     const bool sorted = ctx->knn_sorted_space;
@@ -500,7 +507,13 @@ int pct_run_orient(pct_ctx* ctx, int anchor, const double* viewpoint, int max_co
     ++launches;
     PCT_HIP(ctx, hipGetLastError());
     PCT_HIP(ctx, hipMemcpyAsync(ctx->pin->orient_words, s.ctl, 16 * sizeof(int), hipMemcpyDeviceToHost, st));
-    stats8[6] = launches;
-    stats8[7] = waits + 1;                                 // (the caller's wait for the apply pass and the events)
+    rep->stats[6] = launches;
+    rep->stats[7] = waits + 1;                             // (the caller's wait for the apply pass and the events)
     return PCT_OK;
+}
+
+void pct_orient_report(pct_ctx* ctx, pct_stage_report* rep) {
+    const int* w = ctx->pin->orient_words;
+    const int64_t st[6] = {w[OW_VALID], w[OW_NCOMP], (int64_t)w[OW_VALID] - w[OW_LABELLED], w[OW_TOGGLED], w[OW_LEVELS], w[OW_PULLS]};
+    for (int i = 0; i < 6; ++i) rep->stats[i] = st[i];
 }
